@@ -19,6 +19,16 @@ scaling).  The one exchange of the path -- the final PCM gather to rank 0 over
 RCCL, 576 MB per rank -- runs once after the timed region and is reported as
 `gather_ms` / `gather_GBps`.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  Everything
+else the line can carry -- the CPU baseline, the from-idle and larger-batch legs, the
+float-PCM roofline, the parity checks against the CPU decoder, the end-to-end and
+streaming-API extras, and at N > 1 the boundary parity and the strong-scaling leg --
+runs only with --full.
+
+--dump-outputs DIR writes the PCM the last timed step handed its caller (rank 0's
+gathered PCM at N > 1) as DIR/pcm.npy, float32; the inputs are seeded, so two builds
+can be compared output for output.
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -44,6 +54,8 @@ HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md: 8.0 TB/s spec
 ALGO_FLOP_PER_FRAME = 552e3           # direct-form flops of one stereo frame (41.5 k IMDCT + 91.6 k polyphase + ~5 k per gc)
 FP32_PEAK_TFLOPS = 157.3              # MI355X fp32 vector = fp32 matrix peak (the IMDCT / matrixing run on v_mfma_f32_16x16x4_f32)
 RT_FRAMES_PER_S = 44100.0 / 1152.0
+DUMP_BYTES_MAX = 64 << 20             # --dump-outputs: all files together
+BUSY_CLOCKS_S = 0.1                   # a plain N = 1 run: the headline's own launches before its warm-up (busy_clocks)
 
 
 def effective_cpus():
@@ -192,6 +204,17 @@ def measured_traffic(frames, n_halo):
         return None, None
 
 
+def dump_outputs(d, pcm):
+    """--dump-outputs: the int16 PCM [frames][2304] the timed path handed its caller in its last step, as float32 (exact
+    for int16).  Over DUMP_BYTES_MAX: a fixed, seeded sample of whole frames, in frame order."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    cap = (DUMP_BYTES_MAX - 4096) // (pcm.shape[1] * 4)       # (4096: room for the .npy header)
+    if pcm.shape[0] > cap:
+        pcm = pcm[np.sort(np.random.default_rng(0x5EED).choice(pcm.shape[0], cap, replace=False))]
+    np.save(os.path.join(d, "pcm.npy"), pcm.astype(np.float32))
+
+
 def self_launch(n_ranks):
     """`python bench.py --gpus N` without a launcher around it: run `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N bench.py <the same arguments>` as a child process (one rank per GPU, rendezvous on 127.0.0.1 at a
@@ -240,7 +263,16 @@ def main():
     ap.add_argument("--big", type=int, default=131072, help="frames of the extra large-batch roofline probe (0 = skip)")
     ap.add_argument("--slices", type=int, default=8, help="N > 1: pieces a rank's shard is decoded and sent in per step (never under 4096 frames each)")
     ap.add_argument("--strong-frames", type=int, default=1000000, help="N > 1: frames of the fixed stream of the strong-scaling leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline, from-idle and larger-batch legs, parity checks, "
+                         "end-to-end and streaming-API extras, N > 1 boundary parity and strong-scaling leg (the options above that "
+                         "select or size these apply with --full only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the PCM of the last timed step (rank 0's gathered PCM at N > 1) as DIR/pcm.npy, float32, at most 64 MB "
+                         "(a fixed, seeded sample of frames beyond that)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # the plain command (`python bench.py --gpus N ...`): start the N ranks here, as a FRESH child -- this process has
@@ -251,7 +283,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     # the CPU legs run first: they fork workers, which must happen before this process touches the GPU
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu:
         cpu = cpu_baseline(FRAMES_PER_GPU, args.cpu_seconds, args.cpu_all_seconds)
 
     import torch
@@ -371,11 +403,20 @@ def main():
 
         return extra
 
+    def busy_clocks():
+        """a plain N = 1 run's stand-in for larger_launches: the headline's own launches for BUSY_CLOCKS_S of wall time, in
+        front of the warm-up, so that the timed steps run at the clocks of a busy decoder, as they do behind those legs"""
+        t_end = time.perf_counter() + BUSY_CLOCKS_S
+        while time.perf_counter() < t_end:
+            for _ in range(64):
+                step()
+            torch.cuda.synchronize()
+
     # from_idle_gpu: the same W + K launches once from an idle GPU, reported beside the headline -- the figure that compares
     # like with like across rounds (rounds 1-3 timed the headline this way); --no-from-idle leaves it out, so that a
     # rocprofv3 summary of the command holds the headline's launches only
     from_idle = None
-    if world == 1 and args.from_idle and (args.shard or args.big):
+    if args.full and world == 1 and args.from_idle and (args.shard or args.big):
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -393,7 +434,7 @@ def main():
                      "frames_per_s": round(n * args.steps / wall, 1),
                      "achieved": round(ach_i, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach_i / HBM_PEAK_GBS, 5),
                      "what": "the same %d warm-up + %d timed launches as the headline, run first, before any other GPU work of this process" % (args.warmup, args.steps)}
-    extra_legs = larger_launches() if world == 1 else {}
+    extra_legs = larger_launches() if world == 1 and args.full else {}
 
     # ---- N > 1: the step is decode + the path's one exchange, pipelined (BASELINE configs[4]: "... with RCCL PCM gather") ----
     # A rank's shard is decoded in S consecutive pieces (the synthesis state goes from piece to piece through a state
@@ -544,6 +585,8 @@ def main():
             dt = dt_dec
         kernel_name = eng.last_launch_kernel()
     else:
+        if not args.full:
+            busy_clocks()
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
@@ -587,18 +630,20 @@ def main():
             # thing that was timed
             plain = torch.cat([b_.cpu() for b_ in bufs]).numpy().view(np.int16).reshape(-1, 2304)
             gathered = plain if pipeline_error else pipe.gathered.cpu().numpy().view(np.int16).reshape(-1, 2304)
-            same_as_plain = bool(np.array_equal(gathered, plain))
             if args.dump_gathered:
                 np.save(args.dump_gathered, gathered)
-            try:
-                parity = boundary_parity(gathered, seed, n, world)
-                parity["pipelined_gather_equals_one_piece_gather"] = same_as_plain
-            except Exception as e:                                       # a check beside the number, never fatal
-                parity = {"error": repr(e)}
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, gathered)
+            if args.full:
+                try:
+                    parity = boundary_parity(gathered, seed, n, world)
+                    parity["pipelined_gather_equals_one_piece_gather"] = bool(np.array_equal(gathered, plain))
+                except Exception as e:                                   # a check beside the number, never fatal
+                    parity = {"error": repr(e)}
             del gathered, plain
         del bufs, mine
         # strong scaling: the FIXED stream of BASELINE configs[4] (1 M frames) over this many GPUs, the same pipelined step
-        ns = args.strong_frames // world if args.strong_frames else 0
+        ns = args.strong_frames // world if args.strong_frames and args.full else 0
         if ns and ns != n and not pipeline_error:
             try:
                 pipe = None
@@ -677,7 +722,9 @@ def main():
                             # matrix pipe really does, from the PMC pass of this kernel (profiles/*_pmc_summary.json):
                             "what_frac_is": "direct-form-equivalent flops / time / peak: an algorithmic rate, NOT the matrix pipe's utilisation",
                             "mfma_busy_frac": round(MFMA_BUSY_FRAC, 4) if (MFMA_BUSY_FRAC and traffic) else None}
-    if world == 1:
+    if world == 1 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, pcm.cpu().numpy())
+    if world == 1 and args.full:
         # BASELINE.json's metric, second half ("PCM max-abs-diff vs ref"): the PCM the last timed step left in HBM, all
         # of it, against the CPU decoder on the same generated frames.  After the timed region; the checker is never timed.
         try:
@@ -687,7 +734,8 @@ def main():
                                "the whole batch of the last timed step (int16 PCM, P:2028-2031)")
         except Exception as e:
             parity = {"error": repr(e)}
-    out["parity"] = parity
+    if args.full:
+        out["parity"] = parity
     c5_pcm = extra_legs.pop("_c5_pcm", None)
     if c5_pcm is not None:
         # the C5 shard's own parity (after every timed region): its first 256 frames -- the shard boundary, decoded from the
@@ -737,8 +785,11 @@ def main():
         out["clocks"] = ("busy: the legs on launches of 125 000 / 131 072 frames (c5_shard_1gpu, roofline_large_batch, roofline_float_pcm: "
                          "about 60 ms of launches) ran before the warm-up and the timed region; `from_idle_gpu` = the same W + K launches measured first, "
                          "from an idle GPU: the figure to compare across rounds")
+    elif world == 1 and not args.full:
+        out["clocks"] = ("busy: the headline's own launches ran for %.1f s before the warm-up and the timed region, in place of "
+                         "the larger legs of --full" % BUSY_CLOCKS_S)
 
-    if world == 1 and not args.no_e2e:
+    if world == 1 and args.full and not args.no_e2e:
         # beside the hot-path metric: the same path fed from a bitstream in host memory to PCM in host memory (host scan ->
         # device Huffman -> transforms; PCIe both ways and the host stages included).  A reported extra, never `value`.
         try:

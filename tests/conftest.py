@@ -20,13 +20,11 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def reference():
-    """The real reference decoder compiled into oracle/_ref (skip when absent)."""
+    """The real reference decoder compiled into oracle/_ref, or None where it is not built: the tests that take it then
+    check against its stored outputs (tests/golden/ref_digests.json) alone."""
     from oracle import oracle as orc
-    if os.path.exists("/root/reference/pdmp3.c"):
-        orc.build()
-    if not orc.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    return orc.Reference()
+    orc.build()                                         # (compiles oracle/_ref where the reference's source is present)
+    return orc.Reference() if orc.have_ref() else None
 
 
 @pytest.fixture(scope="session")

@@ -23,7 +23,7 @@ def test_bench_two_ranks_gathered_pcm_equals_unsharded(engine, tmp_path):
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--frames", str(n), "--dump-gathered", out, "--strong-frames", "24000"]
+           "--frames", str(n), "--dump-gathered", out, "--strong-frames", "24000", "--full"]
     # a fresh child process (never an exec from this process, which has initialised the GPU)
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -71,7 +71,7 @@ def test_bench_plain_command_starts_its_own_ranks():
     starts the ranks itself as a fresh child torch.distributed.run and relays the one JSON line and the exit code"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(PDMP3_BENCH_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "3000"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--frames", "3000", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

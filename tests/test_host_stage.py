@@ -4,8 +4,9 @@ emission) against the oracle's bitstream front end, on the real clip and on
 packer-made streams (pdmp3_amd/packer).  No GPU involved: the parse-only handle
 taps the gc records the engine would be given.  Bar: records bit-identical.
 
-Where oracle/_ref is present the same streams also pin the ORACLE front end to
-the reference (records + PCM bit-identical).
+The same streams also pin the ORACLE front end to the reference (records + PCM
+bit-identical): to oracle/_ref where it is built, everywhere to the digests of its
+outputs (tests/golden/ref_digests.json).
 """
 import os
 
@@ -13,8 +14,11 @@ import numpy as np
 import pytest
 
 from pdmp3_amd.packer import packer
+from util import cli_digest, ref_digests
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
+FRONT_END_VS_REF = ["cbr320_js_441", "vbr_48k_stereo_crc_tab33", "mono_32k_96", "short_heavy_dual"]
+FRONT_END_TAP = 400
 
 STREAMS = {
     "cbr320_js_441": dict(n_frames=120, seed=11, sfreq=0, mode=1, mode_ext=2, bitrate_index=14),
@@ -98,10 +102,12 @@ def test_api_library_exports():
         assert hasattr(lib, n), n
 
 
-@pytest.mark.parametrize("name", ["cbr320_js_441", "vbr_48k_stereo_crc_tab33", "mono_32k_96", "short_heavy_dual"])
+@pytest.mark.parametrize("name", FRONT_END_VS_REF)
 def test_oracle_front_end_vs_reference(oracle, reference, name):
     mp3 = packer.generate(**STREAMS[name])
-    p_ref, sp_r, sd_r = reference.decode_buffer_like_cli(mp3, tap_frames=400)
-    p_orc, sp_o, sd_o = oracle.decode_buffer_like_cli(mp3, tap_frames=400)
-    assert p_ref == p_orc
-    assert _records_equal((sp_r, sd_r), (sp_o, sd_o))
+    p_orc, sp_o, sd_o = oracle.decode_buffer_like_cli(mp3, tap_frames=FRONT_END_TAP)
+    assert cli_digest(p_orc, sp_o, sd_o) == ref_digests()["front_end"][name]
+    if reference is not None:
+        p_ref, sp_r, sd_r = reference.decode_buffer_like_cli(mp3, tap_frames=FRONT_END_TAP)
+        assert p_ref == p_orc
+        assert _records_equal((sp_r, sd_r), (sp_o, sd_o))

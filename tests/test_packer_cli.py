@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF_CLI_SPECS = [dict(n_frames=50, seed=0xC1, sfreq=0, mode=1, mode_ext=2, bitrate_index=9),
+                 dict(n_frames=40, seed=5, sfreq=1, mode=0, mode_ext=0, vbr=True, block_pct=(40, 10, 40, 10))]
 
 
 @pytest.mark.parametrize("what,frames", [("c1", 60), ("c3", 50), ("c4", 12), ("custom", 40)])
@@ -36,18 +38,21 @@ def test_generator_cli(oracle, tmp_path, what, frames):
 
 def test_generated_stream_through_the_reference_cli(oracle, reference, tmp_path):
     """oracle/_ref/pdmp3_ref_cli = the reference's pdmp3.c + main.c compiled here: its .raw for a generated file is the
-    oracle's output, byte for byte"""
+    oracle's output, byte for byte -- run where it is built, and everywhere against the digests of its .raw files
+    (tests/golden/ref_digests.json)"""
+    from util import ref_digests
     cli = os.path.join(ROOT, "oracle", "_ref", "pdmp3_ref_cli")
-    if not os.path.exists(cli):
-        pytest.skip("oracle/_ref/pdmp3_ref_cli not built")
     from pdmp3_amd.packer import packer
-    for k, spec in enumerate([dict(n_frames=50, seed=0xC1, sfreq=0, mode=1, mode_ext=2, bitrate_index=9),
-                              dict(n_frames=40, seed=5, sfreq=1, mode=0, mode_ext=0, vbr=True, block_pct=(40, 10, 40, 10))]):
+    for k, spec in enumerate(REF_CLI_SPECS):
         mp3 = packer.generate(**spec)
+        want = oracle.decode_buffer_like_cli(mp3)
+        assert hashlib.sha256(want).hexdigest() == ref_digests()["cli_raw"][k]
+        if not os.path.exists(cli):
+            continue
         p = tmp_path / ("s%d.mp3" % k)
         p.write_bytes(mp3)
         subprocess.check_call([cli, str(p)], timeout=120, stderr=subprocess.DEVNULL)
-        assert open(str(p) + ".raw", "rb").read() == oracle.decode_buffer_like_cli(mp3)
+        assert open(str(p) + ".raw", "rb").read() == want
 
 
 def test_reference_main_links_against_the_library(tmp_path):

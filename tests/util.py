@@ -1,3 +1,4 @@
+import functools
 import hashlib
 
 import numpy as np
@@ -5,6 +6,25 @@ import numpy as np
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+@functools.lru_cache(maxsize=None)
+def ref_digests():
+    """tests/golden/ref_digests.json: sha256 digests of the compiled reference's outputs on the inputs of the tests that
+    compare against it (tools/make_golden.py), so that they check something where oracle/_ref is not built"""
+    import json
+    import os
+    return json.load(open(os.path.join(os.path.dirname(__file__), "golden", "ref_digests.json")))
+
+
+def cli_digest(pcm_bytes, sp, sd):
+    """a CLI-style decode with tapped records, as stored in ref_digests.json: [PCM sha, record count, spectra sha, side sha]"""
+    return [hashlib.sha256(pcm_bytes).hexdigest(), int(sp.shape[0]), sha(sp), sha(sd.view(np.uint8))]
+
+
+def quad_list(q):
+    """a Huffman quadruple result ((v, w, x, y), bits consumed, status) in JSON form"""
+    return [[int(t) for t in q[0]], int(q[1]), int(q[2])]
 
 
 def nch_of(side):

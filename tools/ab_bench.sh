@@ -8,7 +8,7 @@ mkdir -p $OUT
 for rep in $(seq 1 $REPS); do
   for so in pdmp3_amd/variants/*.so; do
     n=$(basename $so .so)
-    PDMP3_HIP_LIB=$PWD/$so timeout 300 python3 bench.py --no-cpu --no-e2e --steps 300 --warmup 30 > $OUT/$n.$rep.json 2>$OUT/$n.$rep.err
+    PDMP3_HIP_LIB=$PWD/$so timeout 300 python3 bench.py --full --no-cpu --no-e2e --steps 300 --warmup 30 > $OUT/$n.$rep.json 2>$OUT/$n.$rep.err
     python3 - <<PY
 import json
 try:

@@ -10,5 +10,5 @@ cut -c1-150 $OUT/bulk_stats/bulk_kernel_stats.csv
 for i in 1 2 3; do timeout 300 python3 tools/bulk_bench.py --frames 137813 --threads 4 --reps 8 --device-out 2> /dev/null | tail -1 | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('device-out', d['runs'][0]['frames_per_s'])"; done
 PDMP3_BULK_TRACE=1 timeout 300 python3 tools/bulk_bench.py --frames 137813 --threads 4 --reps 8 --device-out 2>&1 >/dev/null | grep "split scan" | tail -3 | cut -c1-330
 for j in 1 2 4; do timeout 600 python3 tools/bulk_bench.py --c4 $j --device-out 2> /dev/null | tail -1 | cut -c100-260; done
-timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps(d['end_to_end'])[:700])"
+timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps(d['end_to_end'])[:700])"
 PDMP3_BULK_TRACE=2 timeout 300 python3 tools/bulk_bench.py --c4 1 --device-out --reps 1 > /dev/null 2> $OUT/c4_trace.txt; grep -c . $OUT/c4_trace.txt

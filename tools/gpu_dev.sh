@@ -11,7 +11,7 @@ else
   timeout 800 python3 -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?"
 fi
 tail -4 $OUT/pytest.log
-timeout 300 python3 bench.py --no-cpu > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 300 python3 bench.py --full --no-cpu > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 python3 - <<PY
 import json
 d = json.load(open("$OUT/bench.json"))

@@ -6,12 +6,12 @@ TAG=${1:-r06}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 bench.py --steps 200 --warmup 20 --no-cpu --no-e2e --no-from-idle > $OUT/bench_under_rocprof.json 2> $OUT/stats.log; echo "stats rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-e2e --no-from-idle > $OUT/bench_under_rocprof.json 2> $OUT/stats.log; echo "stats rc=$?"
 cat $OUT/stats/bench_kernel_stats.csv
 # the same from an idle GPU (no larger launches before the timed region): the clocks' share of the headline
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_idle -o bench -- python3 bench.py --steps 200 --warmup 20 --no-cpu --no-e2e --big 0 --shard 0 > $OUT/bench_idle_under_rocprof.json 2> $OUT/stats_idle.log; echo "idle stats rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_idle -o bench -- python3 bench.py --full --steps 200 --warmup 20 --no-cpu --no-e2e --big 0 --shard 0 > $OUT/bench_idle_under_rocprof.json 2> $OUT/stats_idle.log; echo "idle stats rc=$?"
 head -3 $OUT/stats_idle/bench_kernel_stats.csv
-pmc() { name=$1; shift; timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -o p -- python3 bench.py --steps 20 --warmup 2 --no-cpu --no-e2e --big 0 --shard 0 > /dev/null 2> $OUT/$name.log; echo "$name rc=$?"; }
+pmc() { name=$1; shift; timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $OUT/$name -o p -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu --no-e2e --big 0 --shard 0 > /dev/null 2> $OUT/$name.log; echo "$name rc=$?"; }
 pmc fetch FETCH_SIZE
 pmc write WRITE_SIZE
 pmc sq1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_SMEM
@@ -21,7 +21,7 @@ pmc sq3 SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_F32
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/bulk_stats -o bulk -- python3 tools/bulk_bench.py --frames 40000 --threads 2 --reps 2 > $OUT/bulk_under_rocprof.json 2> $OUT/bulk_stats.log; echo "bulk stats rc=$?"
 cat $OUT/bulk_stats/bulk_kernel_stats.csv | cut -c1-160
 # un-profiled lines
-timeout 600 python3 bench.py 2> /dev/null > $OUT/bench.json; echo "bench rc=$?"; cat $OUT/bench.json
+timeout 600 python3 bench.py --full 2> /dev/null > $OUT/bench.json; echo "bench rc=$?"; cat $OUT/bench.json
 timeout 600 python3 tools/bulk_bench.py --frames 137813 --threads 2 2> /dev/null | tail -1 > $OUT/bulk_decode.json; cat $OUT/bulk_decode.json
 timeout 600 python3 tools/bulk_bench.py --frames 137813 --threads 1,8,16,32 --host-huffman 2> /dev/null | tail -1 > $OUT/bulk_decode_host_huffman.json; cat $OUT/bulk_decode_host_huffman.json
 for j in 1 4 6; do timeout 600 python3 tools/bulk_bench.py --c4 $j 2> /dev/null | tail -1; done > $OUT/bulk_c4.json; cat $OUT/bulk_c4.json

@@ -12,5 +12,5 @@ echo "== pytest -m gpu"
 timeout 2400 python3 -m pytest tests -m gpu -x -q -s --durations=15 > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"
 tail -15 $OUT/pytest_gpu.log
 echo "== bench"
-timeout 600 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+timeout 600 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
 cat $OUT/bench.json; tail -3 $OUT/bench.err

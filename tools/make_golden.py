@@ -11,6 +11,9 @@ C2 generator.  Nothing of the reference's source is stored.
                                 float32 of the first 2 frames, sha256 of the inputs
   tests/golden/c2_prefix.npz    PCM of the first 32 frames of the C2 stream + sha256 of the
                                 PCM of all 2048 frames
+  tests/golden/ref_digests.json sha256 of the reference's outputs on the inputs of the tests that compare the oracle
+                                with it (test_oracle, test_host_stage, test_stream_oracle, test_packer_cli,
+                                test_table33_pin): what those tests check where oracle/_ref is not built
 """
 import hashlib
 import os
@@ -71,6 +74,42 @@ def main():
                "first": 2773, "total_words": total, "words": [int(t) for t in words], "quads": quads},
               open(os.path.join(gold, "huff_table33.json"), "w"), indent=0)
     print("table 33 tree:", " ".join("%04x" % t for t in words))
+    ref_digests(ref)
+
+
+def ref_digests(ref):
+    import json
+    import subprocess
+    import tempfile
+    import test_host_stage
+    import test_oracle
+    import test_packer_cli
+    import test_stream_oracle
+    from util import cli_digest, quad_list
+    from pdmp3_amd.packer import packer
+    out = {"what": "sha256 of the compiled reference's outputs (oracle/_ref) on the inputs of the tests that compare the "
+                   "oracle with it; tools/make_golden.py"}
+    out["bit_exact"] = {}
+    for name in corpus.ALL_CASES:
+        sp, sd = corpus.case(name, n=test_oracle.VS_REF_FRAMES, seed=test_oracle.VS_REF_SEED)
+        pcm, stg = ref.decode(sp, sd, stages=True)
+        out["bit_exact"][name] = [sha(pcm), sha(stg.view(np.uint32))]
+    out["front_end"] = {name: cli_digest(*ref.decode_buffer_like_cli(packer.generate(**test_host_stage.STREAMS[name]),
+                                                                      tap_frames=test_host_stage.FRONT_END_TAP))
+                        for name in test_host_stage.FRONT_END_VS_REF}
+    out["clip"] = cli_digest(*ref.decode_buffer_like_cli(open(test_stream_oracle.CLIP, "rb").read(), tap_frames=64))
+    cli = os.path.join(ROOT, "oracle", "_ref", "pdmp3_ref_cli")
+    out["cli_raw"] = []
+    with tempfile.TemporaryDirectory() as d:
+        for k, spec in enumerate(test_packer_cli.REF_CLI_SPECS):
+            p = os.path.join(d, "s%d.mp3" % k)
+            open(p, "wb").write(packer.generate(**spec))
+            subprocess.check_call([cli, p], timeout=120, stderr=subprocess.DEVNULL)
+            out["cli_raw"].append(hashlib.sha256(open(p + ".raw", "rb").read()).hexdigest())
+    out["h1_quads"] = {"%02x" % bits: quad_list(ref.huffman_quad_at(2261, bits, 8)) for bits in range(256)}
+    json.dump(out, open(os.path.join(ROOT, "tests", "golden", "ref_digests.json"), "w"), indent=0)
+    print("ref_digests.json: %d + %d + 1 + %d decodes, 256 H1 quadruples" % (len(out["bit_exact"]), len(out["front_end"]),
+                                                                          len(out["cli_raw"])))
 
 
 if __name__ == "__main__":
