@@ -87,16 +87,21 @@ int pdmp3_amd_bulk_threads(const pdmp3_amd_bulk* b);
  * PDMP3_BULK_SCAN_THREADS) decoded to their end, and streams it gave up half way -- irregular ones: resync, tags, a
  * truncation the ring's feed cadence shows -- and decoded again with the one-thread scan.  Same PCM either way. */
 void pdmp3_amd_bulk_split_scans(const pdmp3_amd_bulk* b, long long* taken, long long* given_up);
+/* Frames whose scalefactors + Huffman data the device stage (*device) and the host pool (*host) decoded over the decoder's
+ * life: the frames of every stream it decoded to its end, by the stage that decoded them (a stream the split scan gave up
+ * counts once).  Either pointer may be NULL. */
+void pdmp3_amd_bulk_huffman_frames(const pdmp3_amd_bulk* b, long long* device, long long* host);
 /* ISO-correct switches (include/pdmp3.h: PDMP3_ISO_*, pdmp3_amd_set_quirks) for the streams decoded from now on;
  * 0 (the default) = the reference's behaviour, bit for bit.  The CLI driver reads the mask from $PDMP3_CLI_ISO. */
 int pdmp3_amd_bulk_set_quirks(pdmp3_amd_bulk* b, unsigned iso_mask);
-/* PDMP3_ISO_LSF (MPEG-2 LSF / MPEG-2.5 streams, which the reference rejects): the device's Huffman stage reads MPEG-1 side
- * info only, so LSF streams take the HOST Huffman stage -- a host_huffman decoder decodes them in its windows like any
- * stream (a window closes where the version, or an LSF stream's channel count, changes); a device-Huffman decoder
- * hands a stream that holds an LSF frame ANYWHERE to a host-Huffman decoder it creates for the purpose (same device,
- * threads, window and switches; the call is synchronous then): at once when the stream opens with an LSF header, else when
- * its scan meets the first one (what had gone to the GPU by then is dropped, the stream is decoded again from its first
- * byte) -- what counts as a frame never depends on which stage decodes the Huffman data. */
+/* PDMP3_ISO_LSF (MPEG-2 LSF / MPEG-2.5 streams, which the reference rejects): both Huffman stages take LSF frames.  A
+ * window closes where the version, or an LSF stream's channel count, changes, and goes to the engine as an LSF window
+ * (pdmp3_hip_stream_set_lsf): a device-Huffman decoder hands the LSF form of pdmp3_frame_bits to the device, which builds
+ * the host stage's records from it, byte for byte; a host_huffman decoder decodes them on its pool.  LSF, MPEG-1 and
+ * mixed-version streams go through either kind of decoder in their own calls, asynchronously where the call is.  The split
+ * scan (several scanner threads) is MPEG-1 only: a stream in which it meets an LSF frame anywhere, its last bytes included,
+ * is given up and decoded from its first byte by the one-thread scan -- what counts as a frame never depends on which
+ * scan or stage reads it. */
 
 /* PCM bytes (return value) and frames pdmp3() would produce for this stream;
  * header / side-info / reservoir pass only, no Huffman, no GPU.  Use it to
@@ -145,6 +150,9 @@ long long pdmp3_amd_bulk_parse(pdmp3_amd_bulk* b, const unsigned char* mp3, size
 /* The scan alone, in the device-Huffman form: per frame the pdmp3_frame_bits and PDMP3_RESERVOIR_BYTES of
  * reservoir that the engine would be given (host tests). */
 pdmp3_amd_bulk* pdmp3_amd_bulk_new_parse_bits(void);
+/* ... and the scan a device-Huffman decoder runs: with PDMP3_ISO_LSF (pdmp3_amd_bulk_set_quirks) it takes MPEG-2 LSF / 2.5
+ * frames, in the LSF form of pdmp3_frame_bits, where the one above ends at the first of them.  For both parse entries. */
+pdmp3_amd_bulk* pdmp3_amd_bulk_new_parse_bits_lsf(void);
 long long pdmp3_amd_bulk_parse_bits(pdmp3_amd_bulk* b, const unsigned char* mp3, size_t n, pdmp3_frame_bits* bits,
                                     uint8_t* reservoir, size_t cap_frames, long long* pcm_bytes);
 

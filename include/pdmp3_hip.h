@@ -315,7 +315,8 @@ int pdmp3_hip_stream_submit(pdmp3_hip_stream* hs, int slot, int n_frames);
 int pdmp3_hip_stream_set_f32(pdmp3_hip_stream* hs, int on);
 /* The records of the following submits are LSF frames (on != 0: decoded like pdmp3_hip_decode_lsf_frames, PCM in its layout;
  * the _to forms take row_bytes 2304 for stereo and 1152 for mono frames then) or MPEG-1 frames again (0).  Batches are
- * homogeneous: the host splits them where the stream changes version or channel count.  Not for the _bits forms. */
+ * homogeneous: the host splits them where the stream changes version or channel count.  The _bits / _pool forms take it
+ * too: their frame bits are then in the LSF form (pdmp3_frame_bits, below), and the device builds LSF records from them. */
 int pdmp3_hip_stream_set_lsf(pdmp3_hip_stream* hs, int on);
 /* undo the slot's latest pdmp3_hip_stream_submit beyond its first keep_frames frames: the carried synthesis state
  * (P:1755, P:1983) becomes what it was after frame keep_frames - 1 of that batch.  Blocks.  (pdmp3_read hands frames
@@ -363,9 +364,26 @@ typedef struct pdmp3_frame_bits {
                                                TABLE33 selects the code book, SF21 / SF12 keep the one-past-the-end
                                                scalefactor slots of the records zero, MS_BOUND / IS_SHORT / IS_BOUND
                                                become the records' PDMP3_GC_ISO_* bits */
-  uint8_t  reserved[12];
+  uint8_t  lsf;                             /* 0 = an MPEG-1 frame; 1 = MPEG-2 LSF, 2 = MPEG-2.5 (PDMP3_LSF_VERSION_MASK) */
+  uint8_t  sfc_hi;                          /* LSF: bit ch = bit 8 of channel ch's 9-bit scalefac_compress */
+  uint8_t  reserved[10];                    /* must be zero */
   pdmp3_gc_bits gc[4];                      /* [gr][ch] */
 } pdmp3_frame_bits;                         /* 80 bytes */
+
+/* The LSF form of pdmp3_frame_bits (ISO/IEC 13818-3; pdmp3_gc_side.lsf above; not the reference).  An LSF frame is ONE
+ * granule: gc[0][ch] hold its side info exactly as for MPEG-1, gc[2] and gc[3] are zero and ignored, scfsi is zero.
+ *   lsf                 the version; the sampling frequency is kLsfSampleRates[3 * lsf + (frame & 3)] (lsf_tables.h)
+ *   gc[ch].scalefac_compress + ((sfc_hi >> ch) & 1) << 8
+ *                       the 9-bit scalefac_compress, resolved on the device into the four partitions' slen and sizes
+ *                       (lsf_tables.h lsf_slen_of / kLsfNsfb; channel 1 of a frame with mode_extension bit 0 set takes the
+ *                       intensity-stereo code, which frame's PDMP3_FR_MODEEXT says)
+ *   gc[ch].flags        PDMP3_GC_PREFLAG set where scalefac_compress >= 500 implies it
+ *   gc[ch].region0_count / region1_count   the implicit 7 / 8 and 20 - region0_count of a window-switching block filled
+ *                       in, as for MPEG-1; the boundaries come from the LSF long-band table of the frame's rate
+ *   gc[ch].count1table_select   2 where the stream's bit is set (the standard's table B)
+ * A window of pdmp3_hip_stream_submit_bits / _pool_to is homogeneous: all of its frames are LSF (pdmp3_hip_stream_set_lsf
+ * on) and of one channel count, or all MPEG-1 (off).  The records the device builds from it are the host stage's, byte for
+ * byte, in the per-frame layout (gc records [1][ch] of an LSF frame: frame, iso and lsf bytes only). */
 
 /* pinned staging of a slot: n frames of side info and n reservoir rows */
 pdmp3_frame_bits* pdmp3_hip_stream_slot_bits(pdmp3_hip_stream* hs, int slot);

@@ -13,15 +13,15 @@ PDMP3_OK, PDMP3_ERR, PDMP3_NEED_MORE, PDMP3_NEW_FORMAT, PDMP3_NO_SPACE = 0, -1, 
 PDMP3_ENC_SIGNED_16 = 0xD0
 _LIB = None
 
-BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_new_on", "pdmp3_amd_bulk_delete", "pdmp3_amd_bulk_threads", "pdmp3_amd_bulk_split_scans", "pdmp3_amd_bulk_set_quirks",
+BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_new_on", "pdmp3_amd_bulk_delete", "pdmp3_amd_bulk_threads", "pdmp3_amd_bulk_split_scans", "pdmp3_amd_bulk_huffman_frames", "pdmp3_amd_bulk_set_quirks",
                 "pdmp3_amd_scan_buffer", "pdmp3_amd_scan_buffer_iso", "pdmp3_amd_corpus_assign", "pdmp3_amd_corpus_decode", "pdmp3_amd_bulk_decode", "pdmp3_amd_bulk_decode_async", "pdmp3_amd_bulk_wait", "pdmp3_amd_bulk_new_parse_only", "pdmp3_amd_bulk_parse",
-                "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav"]
+                "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_new_parse_bits_lsf", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
                           ("flags", "u1"), ("table_select", "u1", (3,)), ("subblock_gain", "u1", (3,)),
                           ("region0_count", "u1"), ("region1_count", "u1"), ("count1table_select", "u1")])
-FRAME_BITS_DTYPE = np.dtype([("frame", "u1"), ("scfsi", "u1", (2,)), ("iso", "u1"), ("reserved", "u1", (12,)), ("gc", GC_BITS_DTYPE, (4,))])
+FRAME_BITS_DTYPE = np.dtype([("frame", "u1"), ("scfsi", "u1", (2,)), ("iso", "u1"), ("lsf", "u1"), ("sfc_hi", "u1"), ("reserved", "u1", (10,)), ("gc", GC_BITS_DTYPE, (4,))])
 RESERVOIR_BYTES = 2064
 API_EXPORTS = ["pdmp3_new", "pdmp3_delete", "pdmp3_open_feed", "pdmp3_feed", "pdmp3_read",
                "pdmp3_decode", "pdmp3_getformat", "pdmp3", "pdmp3_amd_set_encoding", "pdmp3_amd_set_quirks"]
@@ -79,6 +79,10 @@ def load_library():
     lib.pdmp3_amd_bulk_new_on.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.pdmp3_amd_bulk_new_parse_bits.restype = vp
     lib.pdmp3_amd_bulk_new_parse_bits.argtypes = []
+    lib.pdmp3_amd_bulk_new_parse_bits_lsf.restype = vp
+    lib.pdmp3_amd_bulk_new_parse_bits_lsf.argtypes = []
+    lib.pdmp3_amd_bulk_huffman_frames.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.pdmp3_amd_bulk_huffman_frames.restype = None
     lib.pdmp3_amd_bulk_parse_bits.restype = C.c_longlong
     lib.pdmp3_amd_bulk_parse_bits.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_longlong)]
     lib.pdmp3_amd_bulk_decode_async.restype = C.c_longlong
@@ -319,6 +323,13 @@ class BulkDecoder:
         self.lib.pdmp3_amd_bulk_split_scans(self.h, C.byref(a), C.byref(g))
         return a.value, g.value
 
+    def huffman_frames(self):
+        """-> (frames whose scalefactors + Huffman data the device decoded, frames the host pool decoded), over the
+        decoder's life"""
+        d, h = C.c_longlong(0), C.c_longlong(0)
+        self.lib.pdmp3_amd_bulk_huffman_frames(self.h, C.byref(d), C.byref(h))
+        return d.value, h.value
+
     def wait(self):
         if self.lib.pdmp3_amd_bulk_wait(self.h) != 0:
             raise RuntimeError("pdmp3_amd_bulk_wait: engine failure")
@@ -358,18 +369,19 @@ class BulkDecoder:
         return sp[:n], sd[:n], pcm_bytes.value
 
 
-def parse_bits(mp3, iso=0):
+def parse_bits(mp3, iso=0, lsf=False):
     """Stage A of the bulk pipeline alone: per frame the side info (pdmp3_frame_bits) and the reservoir snapshot
-    that pdmp3_hip_stream_submit_bits is given.  No GPU."""
+    that pdmp3_hip_stream_submit_bits is given.  No GPU.  lsf=True: the scan a device-Huffman decoder runs, which with
+    iso & ISO_LSF takes MPEG-2 LSF / 2.5 frames (the LSF form of pdmp3_frame_bits); False: the scan ends at the first one."""
     lib = load_library()
     lib.pdmp3_amd_bulk_set_quirks.argtypes = [C.c_void_p, C.c_uint]
-    _, frames = scan_buffer(mp3)
+    _, frames = scan_buffer(mp3, iso if lsf else 0)
     cap = frames + 1
     bits = np.zeros(cap, dtype=FRAME_BITS_DTYPE)
     res = np.zeros((cap, RESERVOIR_BYTES), dtype=np.uint8)
     assert FRAME_BITS_DTYPE.itemsize == 80
     a = _as_u8(mp3)
-    h = lib.pdmp3_amd_bulk_new_parse_bits()
+    h = lib.pdmp3_amd_bulk_new_parse_bits_lsf() if lsf else lib.pdmp3_amd_bulk_new_parse_bits()
     lib.pdmp3_amd_bulk_set_quirks(h, iso)
     pcm_bytes = C.c_longlong(0)
     n = lib.pdmp3_amd_bulk_parse_bits(h, a.ctypes.data_as(C.c_void_p), len(mp3), bits.ctypes.data_as(C.c_void_p),
@@ -383,16 +395,19 @@ def parse_bits(mp3, iso=0):
 ROW_DESC_DTYPE = np.dtype([("row_off", "<u4"), ("s_off", "<u4"), ("top", "<u2"), ("back", "<u2"), ("up", "<u2"), ("reserved", "<u2")])
 
 
-def parse_pool(mp3):
-    """Stage A alone in the compact form the engine is given: (bits, row descriptors, pool).  No GPU."""
+def parse_pool(mp3, iso=0, lsf=False):
+    """Stage A alone in the compact form the engine is given: (bits, row descriptors, pool).  No GPU.  iso / lsf as for
+    parse_bits."""
     lib = load_library()
-    _, frames = scan_buffer(mp3)
+    lib.pdmp3_amd_bulk_set_quirks.argtypes = [C.c_void_p, C.c_uint]
+    _, frames = scan_buffer(mp3, iso if lsf else 0)
     cap = frames + 1
     bits = np.zeros(cap, dtype=FRAME_BITS_DTYPE)
     desc = np.zeros(cap, dtype=ROW_DESC_DTYPE)
     pool = np.zeros(cap * 2064 + 16384, dtype=np.uint8)
     a = _as_u8(mp3)
-    h = lib.pdmp3_amd_bulk_new_parse_bits()
+    h = lib.pdmp3_amd_bulk_new_parse_bits_lsf() if lsf else lib.pdmp3_amd_bulk_new_parse_bits()
+    lib.pdmp3_amd_bulk_set_quirks(h, iso)
     used = C.c_size_t(0)
     lib.pdmp3_amd_bulk_parse_pool.restype = C.c_longlong
     lib.pdmp3_amd_bulk_parse_pool.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,

@@ -51,9 +51,16 @@ static const uint8_t kLsfNsfb[6][3][4] = {
   {{8, 8, 5, 0}, {15, 12, 9, 0}, {6, 18, 9, 0}},
 };
 
+// (the device's scalefactor stage resolves scalefac_compress itself: unpack_core.h)
+#if defined(__HIPCC__)
+#define LSF_HD __host__ __device__
+#else
+#define LSF_HD
+#endif
+
 // scalefac_compress (9 bits) -> class and the four slen (13818-3 2.4.3.2).  is_right = channel 1 of a frame with
 // mode_extension bit 0 (intensity stereo) set.  Returns the class; *preflag as the standard derives it.
-static inline int lsf_slen_of(unsigned sfc, int is_right, uint8_t slen[4], int* preflag) {
+static inline LSF_HD int lsf_slen_of(unsigned sfc, int is_right, uint8_t slen[4], int* preflag) {
   *preflag = 0;
   if (is_right) {
     const unsigned h = sfc >> 1;

@@ -38,6 +38,7 @@
 #pragma once
 
 #include "decode_core.h"
+#include "lsf_tables.h"
 
 // A row's 32-bit word as the big-endian number it is in the stream.  The kernel keeps its rows byte-swapped in LDS
 // (engine.hip k_unpack swaps while it copies them in): one v_perm per word and symbol less in the loops.
@@ -242,8 +243,35 @@ PD_HD unsigned lut_symbol_slow(const uint32_t* lut, unsigned base, BitPos& b) {
   return leaf;
 }
 
+// Which frames a caller hands over (include/pdmp3_hip.h: the LSF form of pdmp3_frame_bits).  The engine's windows are
+// homogeneous, so its kernels know it per launch (kFramesMpeg1 / kFramesLsf: the MPEG-1 code is what it was before LSF
+// came in); the host build reads every frame's own lsf byte (kFramesAny, the default).
+constexpr int kFramesMpeg1 = 0, kFramesLsf = 1, kFramesAny = 2;
+template <int K>
+PD_HD bool frame_is_lsf(const pdmp3_frame_bits& F) { return K == kFramesAny ? F.lsf != 0 : K == kFramesLsf; }
+
+// LSF (13818-3 2.4.3.2; cf. host/frame_parse.c decode_main): channel ch's 9-bit scalefac_compress -> the four slen and the
+// partition sizes of its block shape (lsf_tables.h); channel 1 of an intensity-stereo frame takes the other code
+PD_HD int lsf_parts(const pdmp3_frame_bits& F, int ch, uint8_t slen[4], const uint8_t** nsf) {
+  const pdmp3_gc_bits& s = F.gc[ch];
+  const unsigned sfc = s.scalefac_compress | ((F.sfc_hi >> ch) & 1u) << 8;
+  const unsigned mode = (F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT, mext = (F.frame & PDMP3_FR_MODEEXT_MASK) >> PDMP3_FR_MODEEXT_SHIFT;
+  int pf;
+  const int cls = lsf_slen_of(sfc, ch == 1 && mode == 1 && (mext & 1u), slen, &pf);
+  const bool shrt = (s.flags & PDMP3_GC_WIN_SWITCH) && ((s.flags & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT) == 2;
+  *nsf = kLsfNsfb[cls][shrt ? ((s.flags & PDMP3_GC_MIXED) ? 2 : 1) : 0];
+  return cls;
+}
+
 // bits of part 2 (scalefactors) of one granule-channel, from the side info alone (P:1376-1437)
+template <int K = kFramesAny>
 PD_HD unsigned part2_bits(const UnpackTables& U, const pdmp3_frame_bits& F, int gr, int ch) {
+  if (frame_is_lsf<K>(F)) {                      // (LSF: one granule, four partitions, no scfsi)
+    uint8_t slen[4];
+    const uint8_t* nsf;
+    (void)lsf_parts(F, ch, slen, &nsf);
+    return nsf[0] * slen[0] + nsf[1] * slen[1] + nsf[2] * slen[2] + nsf[3] * slen[3];
+  }
   const pdmp3_gc_bits& s = F.gc[gr * 2 + ch];
   const unsigned slen1 = U.slen[s.scalefac_compress * 2], slen2 = U.slen[s.scalefac_compress * 2 + 1];
   const bool shrt = (s.flags & PDMP3_GC_WIN_SWITCH) && ((s.flags & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT) == 2;
@@ -465,18 +493,39 @@ PD_HD void unpack_value(const uint8_t* row, const SymRec rec, int16_t* is) {
 // ---------------------------------------------------------------------------
 // bit position of granule-channel g's part 2: every one before it ends at start + part2_3_length -- or, when that is
 // zero, right after its scalefactors (P:2062: Read_Huffman returns before touching the position)
+template <int K = kFramesAny>
 PD_HD unsigned part2_start_of(const UnpackTables& U, const pdmp3_frame_bits& F, int g, int nch) {
   unsigned pos = 0;
   for (int q = 0; q < g; q++) {
     if ((q & 1) >= nch) continue;
     const unsigned p23 = F.gc[q].part2_3_length;
-    pos += p23 ? p23 : part2_bits(U, F, q >> 1, q & 1);
+    pos += p23 ? p23 : part2_bits<K>(U, F, q >> 1, q & 1);
   }
   return pos;
 }
 
+// side_fields of an LSF frame (below)
+PD_HD void side_fields_lsf(const pdmp3_frame_bits& F, int g, int nch, pdmp3_gc_side* rec) {
+  const int ch = g & 1;
+  rec->lsf = F.lsf;
+  if (ch >= nch || g >= 2) return;
+  const pdmp3_gc_bits& s = F.gc[g];
+  rec->global_gain = s.global_gain;
+  rec->flags = s.flags;
+  rec->subblock_gain[0] = s.subblock_gain[0]; rec->subblock_gain[1] = s.subblock_gain[1]; rec->subblock_gain[2] = s.subblock_gain[2];
+  if (g == 1 && ((F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 1 && (F.frame & (1u << PDMP3_FR_MODEEXT_SHIFT))) {
+    uint8_t slen[4];
+    const uint8_t* nsf;
+    (void)lsf_parts(F, 1, slen, &nsf);
+    if (s.scalefac_compress & 1u) rec->lsf |= PDMP3_LSF_IS_SCALE;
+    for (int k = 0; k < 4; k++) { rec->lsf_slen[k] = slen[k]; rec->lsf_nsfb[k] = nsf[k]; }
+  }
+}
 // The fields of a gc record that are the frame's own side info, into a record that is ZERO: everything but the
-// scalefactors and count1, which the merge fills in (the values that survive frames).
+// scalefactors and count1, which the merge fills in (the values that survive frames).  An LSF frame's records carry its
+// version (all four), its granule's fields, and for channel 1 of an intensity-stereo frame the partitions of its
+// intensity positions (frame_parse.c emit_records); records [1][ch] keep frame, iso and lsf only.
+template <int K = kFramesAny>
 PD_HD void side_fields(const pdmp3_frame_bits& F, int g, pdmp3_gc_side* rec) {
   const int ch = g & 1;
   const int nch = ((F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3 ? 1 : 2;
@@ -484,6 +533,7 @@ PD_HD void side_fields(const pdmp3_frame_bits& F, int g, pdmp3_gc_side* rec) {
   // the ISO switches of the frame (include/pdmp3.h PDMP3_ISO_*: MS_BOUND = 2, IS_SHORT = 4) as the records' PDMP3_GC_ISO_* bits
   rec->iso = (uint8_t)(((F.iso & 0x02u) ? PDMP3_GC_ISO_MS_ALL : 0u) | ((F.iso & 0x04u) ? PDMP3_GC_ISO_IS_SHORT : 0u) |
                        ((F.iso & 0x20u) ? PDMP3_GC_ISO_IS_STD : 0u));
+  if (frame_is_lsf<K>(F)) { side_fields_lsf(F, g, nch, rec); return; }
   if (ch >= nch) return;
   const pdmp3_gc_bits& s = F.gc[g];
   rec->global_gain = s.global_gain;
@@ -492,7 +542,36 @@ PD_HD void side_fields(const pdmp3_frame_bits& F, int g, pdmp3_gc_side* rec) {
   if (g == 3 && !(F.iso & 0x10u)) rec->scalefac_s[12][0] = rec->scalefac_s[12][1] = rec->scalefac_s[12][2] = PDMP3_SF_PEEK;   // (PDMP3_ISO_SF12: stays 0)
 }
 
+// LSF: the four partitions in band order (short: band by band, window by window; mixed: six long bands, then short bands
+// 3..11; frame_parse.c decode_main).  Every scalefactor of the granule is written -- what is not transmitted is 0 -- and
+// count1 is the frame's own, 0 without Huffman data (unpack_tail overwrites it where there is some).
+PD_HD void unpack_scalefactors_lsf(const UnpackTables& U, const uint8_t* res, const pdmp3_frame_bits& F, int g, int nch, GcRaw* raw) {
+  if (g >= 2) return;                            // (one granule)
+  raw->count1_set = 1;
+  uint8_t slen[4];
+  const uint8_t* nsf;
+  (void)lsf_parts(F, g, slen, &nsf);
+  const pdmp3_gc_bits& s = F.gc[g];
+  const bool shrt = (s.flags & PDMP3_GC_WIN_SWITCH) && ((s.flags & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT) == 2;
+  const bool mixed = shrt && (s.flags & PDMP3_GC_MIXED);
+  BitPos b{res, part2_start_of<kFramesLsf>(U, F, g, nch)};
+  RegWin r;
+  rw_open(r, res, b.pos);
+  unsigned n = 0;                                // (partition sizes add up to 21 long, 36 short, 6 + 27 mixed: kLsfNsfb)
+  for (int k = 0; k < 4; k++)
+    for (unsigned i = 0; i < nsf[k]; i++, n++) {
+      const uint8_t v = (uint8_t)get_field(b, r, slen[k]);
+      if (!shrt) raw->sf_l[n] = v;
+      else if (!mixed) raw->sf_s[n] = v;
+      else if (n < 6) raw->sf_l[n] = v;
+      else raw->sf_s[n + 3] = v;
+    }
+  raw->sf_l_set = 0x1fffffu;
+  raw->sf_s_set = 0xfffu;
+}
+
 // the scalefactors the stream carries for this granule-channel (P:1383-1430), as the merge's input
+template <int K = kFramesAny>
 PD_HD void unpack_scalefactors(const UnpackTables& U, const uint8_t* res, const pdmp3_frame_bits& F, int g, GcRaw* raw) {
   const int gr = g >> 1, ch = g & 1;
   const int nch = ((F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3 ? 1 : 2;
@@ -501,8 +580,9 @@ PD_HD void unpack_scalefactors(const UnpackTables& U, const uint8_t* res, const 
     for (int i = 0; i < 20; i++) w32[i] = 0;
   }
   if (ch >= nch) return;
+  if (frame_is_lsf<K>(F)) { unpack_scalefactors_lsf(U, res, F, g, nch, raw); return; }
   const pdmp3_gc_bits& s = F.gc[g];
-  BitPos b{res, part2_start_of(U, F, g, nch)};
+  BitPos b{res, part2_start_of<K>(U, F, g, nch)};
   const unsigned slen1 = U.slen[s.scalefac_compress * 2], slen2 = U.slen[s.scalefac_compress * 2 + 1];
   const bool wsf = (s.flags & PDMP3_GC_WIN_SWITCH) != 0;
   const unsigned bt = (s.flags & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT;
@@ -534,28 +614,45 @@ PD_HD void unpack_scalefactors(const UnpackTables& U, const uint8_t* res, const 
 }
 
 // both (the sequential form; k_unpack writes the merge's input only and k_merge_apply builds the whole record)
+template <int K = kFramesAny>
 PD_HD void unpack_records(const UnpackTables& U, const uint8_t* res, const pdmp3_frame_bits& F, int g, pdmp3_gc_side* rec,
                           GcRaw* raw) {
   uint32_t* r32 = reinterpret_cast<uint32_t*>(rec);
   for (int i = 0; i < 32; i++) r32[i] = 0;
-  side_fields(F, g, rec);
-  unpack_scalefactors(U, res, F, g, raw);
+  side_fields<K>(F, g, rec);
+  unpack_scalefactors<K>(U, res, F, g, raw);
 }
 
-// false: no Huffman data (channel absent, or part2_3_length == 0: spectra stay zero, count1 keeps its old value, H6)
+// false: no Huffman data (channel absent, or part2_3_length == 0: spectra stay zero, count1 keeps its old value, H6 --
+// an LSF frame's is 0 then: unpack_scalefactors_lsf)
+template <int K = kFramesAny>
 PD_HD bool unpack_plan(const UnpackTables& U, const pdmp3_frame_bits& F, int g, SymPlan& P, SymState& st) {
   const int gr = g >> 1, ch = g & 1;
   const int nch = ((F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3 ? 1 : 2;
   const int sfreq = (F.frame & PDMP3_FR_SFREQ_MASK) > 2 ? 2 : (F.frame & PDMP3_FR_SFREQ_MASK);
   if (ch >= nch) return false;
+  const bool lsf = frame_is_lsf<K>(F);
+  if (lsf && gr == 1) return false;              // (an LSF frame is one granule)
   const pdmp3_gc_bits& s = F.gc[g];
   if (s.part2_3_length == 0) return false;
-  const unsigned part2_start = part2_start_of(U, F, g, nch);
+  const unsigned part2_start = part2_start_of<K>(U, F, g, nch);
   const bool wsf = (s.flags & PDMP3_GC_WIN_SWITCH) != 0;
   const unsigned bt = (s.flags & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT;
   // ---- Huffman (P:2051-2115)
   P.end = part2_start + s.part2_3_length - 1;
   unsigned r1, r2;
+  if (lsf) {
+    // the same rule over the LSF long-band table of the frame's rate (frame_parse.c decode_huffman): nothing lies beyond band
+    // 22; at 8 kHz three short bands are 72 lines.  (Two reads per lane from the constant table: UnpackTables is the
+    // workgroup's LDS image, and the MPEG-1 launches' LDS stays what it was.)
+    const unsigned sf9 = 3u * F.lsf + (F.frame & PDMP3_FR_SFREQ_MASK), row = sf9 >= 3 && sf9 <= 8 ? sf9 - 3 : 0;
+    if (wsf && bt == 2) { r1 = sf9 == 8 ? 72 : 36; r2 = 576; }
+    else {
+      const unsigned i1 = s.region0_count + 1u, i2 = s.region0_count + s.region1_count + 2u;
+      r1 = kLsfSfbLong[row][i1 > 22 ? 22 : i1];
+      r2 = kLsfSfbLong[row][i2 > 22 ? 22 : i2];
+    }
+  } else
   if (wsf && bt == 2) { r1 = 36; r2 = 576; }
   else {
     const unsigned i1 = s.region0_count + 1u, i2 = s.region0_count + s.region1_count + 2u;
@@ -575,7 +672,7 @@ PD_HD bool unpack_plan(const UnpackTables& U, const pdmp3_frame_bits& F, int g, 
   }
   // count1 region: table 32 or the reference's mis-pointed table 33 (H1); both books are <= 8 bits deep
   P.qbase = U.book_base[U.book_of_table[32 + s.count1table_select]];
-  st.pos = part2_start + part2_bits(U, F, gr, ch);
+  st.pos = part2_start + part2_bits<K>(U, F, gr, ch);
   st.line = 0;
   return true;
 }
@@ -604,12 +701,13 @@ PD_HD void unpack_tail(const UnpackTables& U, const uint32_t* lut, const uint8_t
 }
 
 // the three in a row (host test build; reference form of what k_unpack does with four waves)
+template <int K = kFramesAny>
 PD_HD void unpack_gc(const UnpackTables& U, const uint32_t* lut, const uint8_t* res, const pdmp3_frame_bits& F, int g,
                      int16_t* spectra_gc, pdmp3_gc_side* rec, GcRaw* raw) {
   SymPlan P;
   SymState st;
-  unpack_records(U, res, F, g, rec, raw);
-  if (!unpack_plan(U, F, g, P, st)) return;
+  unpack_records<K>(U, res, F, g, rec, raw);
+  if (!unpack_plan<K>(U, F, g, P, st)) return;
   Win2 w;
   w2_open(w, res, st.pos);
   while (sym_active(P.nbig, P.end, st))
@@ -624,7 +722,9 @@ PD_HD void unpack_gc(const UnpackTables& U, const uint32_t* lut, const uint8_t* 
 //   t < 232          count1[g]
 // state[kMergeSlots] (uint16) carries the values from one window to the next.
 // ---------------------------------------------------------------------------
+template <int K = kFramesAny>
 PD_HD bool gc_active(const pdmp3_frame_bits& F, int g) {
+  if (frame_is_lsf<K>(F) && g >= 2) return false;   // (an LSF frame's records [1][ch] carry no values)
   return (g & 1) == 0 || ((F.frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) != 3;
 }
 
@@ -674,25 +774,29 @@ PD_HD MergeIn merge_load(int t, const GcRaw* raw_f /* raw + f * 4 */, bool newst
 }
 
 // slot t's value after frame f goes into the frame's records: its own field, and where the reference's
-// one-past-the-end reads land (the first element of the NEXT [gr][ch] block)
+// one-past-the-end reads land (the first element of the NEXT [gr][ch] block; an LSF frame's stay 0, as
+// with PDMP3_ISO_SF21 | PDMP3_ISO_SF12)
+template <int K = kFramesAny>
 PD_HD void merge_store(int t, const pdmp3_frame_bits& F, pdmp3_gc_side* R /* rec + f * 4 */, unsigned val) {
+  const unsigned iso = F.iso | (frame_is_lsf<K>(F) ? 0x18u : 0u);
   if (t < 84) {
     const int g = t / 21, sfb = t - 21 * g;
-    if (gc_active(F, g)) R[g].scalefac_l[sfb] = (uint8_t)val;
-    if (sfb == 0 && g >= 1 && gc_active(F, g - 1) && !(F.iso & 0x08u)) R[g - 1].scalefac_l[21] = (uint8_t)val;   // (PDMP3_ISO_SF21: stays 0)
+    if (gc_active<K>(F, g)) R[g].scalefac_l[sfb] = (uint8_t)val;
+    if (sfb == 0 && g >= 1 && gc_active<K>(F, g - 1) && !(iso & 0x08u)) R[g - 1].scalefac_l[21] = (uint8_t)val;   // (PDMP3_ISO_SF21: stays 0)
   } else if (t < 228) {
     const int u = t - 84, g = u / 36, k = u - 36 * g, sfb = k / 3, w = k - 3 * sfb;
-    if (gc_active(F, g)) R[g].scalefac_s[sfb][w] = (uint8_t)val;
-    if (sfb == 0 && g >= 1 && gc_active(F, g - 1) && !(F.iso & 0x10u)) R[g - 1].scalefac_s[12][w] = (uint8_t)val;   // (PDMP3_ISO_SF12)
-    if (k == 0 && g == 0 && gc_active(F, 3) && !(F.iso & 0x08u)) R[3].scalefac_l[21] = (uint8_t)val;   // last block: scalefac_s follows
+    if (gc_active<K>(F, g)) R[g].scalefac_s[sfb][w] = (uint8_t)val;
+    if (sfb == 0 && g >= 1 && gc_active<K>(F, g - 1) && !(iso & 0x10u)) R[g - 1].scalefac_s[12][w] = (uint8_t)val;   // (PDMP3_ISO_SF12)
+    if (k == 0 && g == 0 && gc_active<K>(F, 3) && !(iso & 0x08u)) R[3].scalefac_l[21] = (uint8_t)val;   // last block: scalefac_s follows
   } else {
     const int g = t - 228;
-    if (gc_active(F, g)) R[g].count1 = (uint16_t)val;
+    if (gc_active<K>(F, g)) R[g].count1 = (uint16_t)val;
   }
 }
 
 // sequential form (host test build; the device kernel k_merge does the same with wave scans over 64 frames)
 // state_in must not alias state_out: granule-1 slots also read their twin's incoming value
+template <int K = kFramesAny>
 PD_HD void merge_slot(int t, const GcRaw* raw, const pdmp3_frame_bits* F, int n, const uint16_t* state_in, uint16_t* state,
                       pdmp3_gc_side* rec) {
   const int tw = merge_twin(t);
@@ -702,7 +806,7 @@ PD_HD void merge_slot(int t, const GcRaw* raw, const pdmp3_frame_bits* F, int n,
     if (m.set0) val0 = m.val0;
     if (m.set) val = m.val;
     if (m.copy) val = val0;
-    merge_store(t, F[f], rec + (size_t)f * 4, val);
+    merge_store<K>(t, F[f], rec + (size_t)f * 4, val);
   }
   state[t] = (uint16_t)val;
 }
@@ -734,12 +838,14 @@ struct MergeLane {
   uint16_t own_off, alias_off;                       // byte offsets in the frame's records; alias_off 0xffff: none
   uint8_t own_g, alias_g, alias_iso, own16;          // stores happen when gc own_g / alias_g is active and (iso & alias_iso) == 0
 };
-// per frame: bit 0 PDMP3_FR_NEWSTREAM, bits 8-11 gc g is active, bits 16-23 the frame's PDMP3_ISO_* switches
-PD_HD uint32_t merge_frame_meta(unsigned frame, unsigned iso) {
+// per frame: bit 0 PDMP3_FR_NEWSTREAM, bits 8-11 gc g is active, bits 16-23 the frame's PDMP3_ISO_* switches (an LSF frame:
+// granule 0 only, and the one-past-the-end slots stay 0 -- merge_store)
+PD_HD uint32_t merge_frame_meta(unsigned frame, unsigned iso, bool lsf = false) {
   const bool mono = ((frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3;
+  if (lsf) return ((frame & PDMP3_FR_NEWSTREAM) ? 1u : 0u) | (mono ? 0x100u : 0x300u) | ((iso | 0x18u) & 0xffu) << 16;
   return ((frame & PDMP3_FR_NEWSTREAM) ? 1u : 0u) | (mono ? 0x500u : 0xf00u) | (iso & 0xffu) << 16;
 }
-PD_HD uint32_t merge_frame_meta(const pdmp3_frame_bits& F) { return merge_frame_meta(F.frame, F.iso); }
+PD_HD uint32_t merge_frame_meta(const pdmp3_frame_bits& F) { return merge_frame_meta(F.frame, F.iso, F.lsf != 0); }
 static_assert(offsetof(pdmp3_frame_bits, frame) == 0 && offsetof(pdmp3_frame_bits, iso) == 3, "k_merge_apply reads both with the record's first word");
 PD_HD MergeLane merge_lane(int t) {
   MergeLane L{};

@@ -287,23 +287,26 @@ int bulk_rotate(struct bulk* b) {
 
 /* ---- bits mode: stage A writes side info + reservoir snapshot straight into the engine's pinned slot; scale-
  * factors, Huffman and the frame-to-frame merge run on the device (include/pdmp3_hip.h, submit_bits) ---- */
+/* (an LSF frame: include/pdmp3_hip.h, the LSF form -- one granule, the 9-bit scalefac_compress split over gc[ch] and sfc_hi) */
 static void fill_frame_bits(const pdmp3_handle* id, pdmp3_frame_bits* fb, int newstream) {
   const frame_header* H = &id->hdr;
   const side_info* S = &id->si;
-  const unsigned nch = H->mode == 3 ? 1 : 2;
+  const unsigned nch = H->mode == 3 ? 1 : 2, ngr = H->ver ? 1 : 2;
   memset(fb, 0, sizeof *fb);
   fb->frame = (uint8_t)((H->sfreq & 3) | (H->mode << PDMP3_FR_MODE_SHIFT) | (H->mode_ext << PDMP3_FR_MODEEXT_SHIFT) |
                         (id->need_reset ? PDMP3_FR_RESET : 0) | (newstream ? PDMP3_FR_NEWSTREAM : 0));
   fb->iso = (uint8_t)id->iso;
+  fb->lsf = (uint8_t)H->ver;
   for (unsigned ch = 0; ch < nch; ch++)
     for (unsigned g4 = 0; g4 < 4; g4++) if (S->scfsi[ch][g4]) fb->scfsi[ch] |= (uint8_t)(1u << g4);
-  for (unsigned gr = 0; gr < 2; gr++)
+  for (unsigned gr = 0; gr < ngr; gr++)
     for (unsigned ch = 0; ch < nch; ch++) {
       pdmp3_gc_bits* g = &fb->gc[gr * 2 + ch];
       g->part2_3_length = (uint16_t)S->part2_3_length[gr][ch];
       g->big_values = (uint16_t)S->big_values[gr][ch];
       g->global_gain = (uint8_t)S->global_gain[gr][ch];
       g->scalefac_compress = (uint8_t)S->scalefac_compress[gr][ch];
+      if (S->scalefac_compress[gr][ch] & 0x100u) fb->sfc_hi |= (uint8_t)(1u << ch);
       g->flags = (uint8_t)((S->scalefac_scale[gr][ch] ? PDMP3_GC_SCALEFAC_SCALE : 0) |
                            (S->preflag[gr][ch] ? PDMP3_GC_PREFLAG : 0) |
                            (S->win_switch[gr][ch] ? PDMP3_GC_WIN_SWITCH : 0) |
@@ -404,7 +407,7 @@ void* bulk_submitter(void* arg) {
     const int slot = b->sub_slot[b->sub_tail & 7], n = b->sub_n[b->sub_tail & 7], row = b->sub_row[b->sub_tail & 7];
     void* dst = b->sub_dst[b->sub_tail & 7];
     const size_t pool = b->sub_pool[b->sub_tail & 7];
-    const int gn = b->sub_gath[b->sub_tail & 7];
+    const int gn = b->sub_gath[b->sub_tail & 7], lsf = b->sub_lsf[b->sub_tail & 7];
     pthread_mutex_unlock(&b->sub_mu);
     const double t0 = now_s();
     if (pool) {
@@ -416,8 +419,10 @@ void* bulk_submitter(void* arg) {
     b->sub_copied = b->sub_tail + 1;
     pthread_cond_broadcast(&b->sub_done_cv);
     pthread_mutex_unlock(&b->sub_mu);
-    const int rc = pool ? pdmp3_hip_stream_submit_pool_to(b->hs, slot, n, pool, dst, row)
-                        : pdmp3_hip_stream_submit_bits_to(b->hs, slot, n, dst, row);
+    int rc = pdmp3_hip_stream_set_lsf(b->hs, lsf);   /* (this thread alone submits bits-mode windows: the setting is the window's) */
+    if (rc == PDMP3_HIP_OK)
+      rc = pool ? pdmp3_hip_stream_submit_pool_to(b->hs, slot, n, pool, dst, row)
+                : pdmp3_hip_stream_submit_bits_to(b->hs, slot, n, dst, row);
     if (rc != PDMP3_HIP_OK) fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
     const double t2 = now_s();
     b->t_sub_gather += t1 - t0; b->t_sub_call += t2 - t1;
@@ -429,10 +434,10 @@ void* bulk_submitter(void* arg) {
     pthread_mutex_unlock(&b->sub_mu);
   }
 }
-static long long sub_enqueue(struct bulk* b, int slot, int n, void* dst, int row, size_t pool_bytes, int gath_n) {
+static long long sub_enqueue(struct bulk* b, int slot, int n, void* dst, int row, size_t pool_bytes, int gath_n, int lsf) {
   pthread_mutex_lock(&b->sub_mu);
   const long long seq = b->sub_head;
-  b->sub_slot[b->sub_head & 7] = slot; b->sub_n[b->sub_head & 7] = n;
+  b->sub_slot[b->sub_head & 7] = slot; b->sub_n[b->sub_head & 7] = n; b->sub_lsf[b->sub_head & 7] = lsf;
   b->sub_dst[b->sub_head & 7] = dst; b->sub_row[b->sub_head & 7] = row; b->sub_pool[b->sub_head & 7] = pool_bytes;
   b->sub_gath[b->sub_head & 7] = gath_n;
   b->sub_head++;
@@ -574,10 +579,22 @@ void pool_materialize(struct bulk* b) {
 }
 
 
+/* The engine takes a window's frames in one kind of launch: all MPEG-1, or all LSF of one channel count
+ * (pdmp3_hip_stream_set_lsf).  The frame being staged (id->hdr) opens a new window where it is of another kind -- before
+ * its main data goes into the pool (pool mode: fill_reservoir_pool) or its snapshot is taken (bits_push). */
+static int bits_split_kinds(struct bulk* b, const pdmp3_handle* id) {
+  if (!b->hs || b->win_sink || !b->bits_open || !b->bits_n) return PDMP3_OK;
+  const pdmp3_frame_bits* f0 = &b->bits_dst[0];
+  const int mono0 = ((f0->frame & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3;
+  if (f0->lsf == id->hdr.ver && (!id->hdr.ver || mono0 == (id->hdr.mode == 3))) return PDMP3_OK;
+  return bits_close_window(b);
+}
+
 /* Get_Main_Data (P:1096-1122) of the frame being staged, into the pool.  Same return codes and the same effect on
  * main_top and the ring as fill_reservoir. */
 int fill_reservoir_pool(pdmp3_handle* id, unsigned size, unsigned begin) {
   struct bulk* b = id->pool_sink;
+  if (bits_split_kinds(b, id) != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }
   if (!b->bits_open && bits_open_window(b) != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }
   if (b->cur_staged) { b->failed = 1; return PDMP3_ERR; }   /* (every frame staged here is pushed: the pool is the only copy) */
   const int regular = begin <= id->main_top && size <= ring_filled(id) && begin + size <= sizeof id->main_vec;
@@ -631,13 +648,15 @@ int bits_close_window(struct bulk* b) {
     f->dst = b->pcm_emitted < b->pcm_cap ? b->pcm + b->pcm_emitted : NULL;
     f->dst_cap = b->pcm_emitted < b->pcm_cap ? b->pcm_cap - b->pcm_emitted : 0;
     f->all_stereo = f->nch[0];
+    f->lsf = b->bits_dst[0].lsf != 0;             /* (bits_split_kinds: the window's frames are all of its first one's kind) */
     for (int i = 0; i < f->n; i++) {
       if (f->nch[i] != f->nch[0]) f->all_stereo = 0;
-      b->pcm_emitted += 2304u * f->nch[i];
+      b->pcm_emitted += (f->lsf ? 1152u : 2304u) * f->nch[i];
     }
     const double t0 = now_s();
     flight_plan(b, f);
-    f->sub_seq = sub_enqueue(b, b->bits_slot, b->bits_n, f->direct ? f->dst : NULL, f->all_stereo == 1 ? 2304 : 4608, b->pool_mode ? b->pool_tail : 0, b->g_pushed[b->bits_slot] ? -1 : b->gath_n);
+    f->sub_seq = sub_enqueue(b, b->bits_slot, b->bits_n, f->direct ? f->dst : NULL, (f->all_stereo == 1 ? 2304 : 4608) >> (f->lsf ? 1 : 0),
+                             b->pool_mode ? b->pool_tail : 0, b->g_pushed[b->bits_slot] ? -1 : b->gath_n, f->lsf);
     b->t_submit += now_s() - t0;
     f->active = 1;
   }
@@ -648,6 +667,7 @@ int bits_close_window(struct bulk* b) {
 
 static int bits_push(struct bulk* b) {
   pdmp3_handle* id = b->id;
+  if (!b->pool_mode && bits_split_kinds(b, id) != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }   /* (pool mode: fill_reservoir_pool did) */
   if (!b->bits_open && bits_open_window(b) != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }
   if (!b->hs && !b->win_sink && (size_t)b->frames > b->rec_cap) { b->failed = 1; return PDMP3_ERR; }
   const int i = b->bits_n++;

@@ -5,7 +5,6 @@
 
 void pdmp3_amd_bulk_delete(struct bulk* b) {
   if (!b) return;
-  if (b->lsf_alt) { pdmp3_amd_bulk_delete(b->lsf_alt); b->lsf_alt = NULL; }
   if (b->th) {
     pthread_mutex_lock(&b->mu);
     b->quit = 1;
@@ -44,7 +43,6 @@ void pdmp3_amd_bulk_delete(struct bulk* b) {
  * parse-only decoder (host tests on machines without a GPU). */
 static struct bulk* bulk_new(int threads, int window_frames, int with_engine, int bits_mode, int device) {
   pthread_once(&g_lut_once, build_luts);
-  const int window_arg = window_frames;
   if (threads <= 0) {
     const int c = usable_cpus();
     threads = c > 64 ? 64 : c;
@@ -67,8 +65,6 @@ static struct bulk* bulk_new(int threads, int window_frames, int with_engine, in
   if (!b) return NULL;
   b->cap = window_frames;
   b->target = target;
-  b->device = device;
-  b->window_arg = window_arg;
   {
     /* split scan (par_drive): 12 scanners where the process has 32 CPUs, 8 with 16 (they live for the few milliseconds of a
      * stream's scan; with the PCM left in HBM the scanners, the upload and the kernels all take about 0.2 ms per 8192 frames, and
@@ -81,6 +77,7 @@ static struct bulk* bulk_new(int threads, int window_frames, int with_engine, in
     if (b->scan_threads > PAR_MAX_SCANNERS) b->scan_threads = PAR_MAX_SCANNERS;
   }
   b->bits_mode = bits_mode;
+  b->bits_lsf = bits_mode && with_engine;       /* (the device builds LSF records too; the legacy parse-bits entry stops at LSF) */
   b->id = (pdmp3_handle*)calloc(1, sizeof *b->id);
   if (!b->id) { free(b); return NULL; }
   b->id->host_only = 1;
@@ -156,7 +153,20 @@ struct bulk* pdmp3_amd_bulk_new(int threads, int window_frames) {
 }
 struct bulk* pdmp3_amd_bulk_new_parse_only(int threads, int window_frames) { return bulk_new(threads, window_frames, 0, 0, 0); }
 struct bulk* pdmp3_amd_bulk_new_parse_bits(void) { return bulk_new(1, 1, 0, 1, 0); }
+/* the same scan as a device-Huffman decoder's: with PDMP3_ISO_LSF it takes MPEG-2 LSF / 2.5 frames (their side info in the LSF
+ * form of pdmp3_frame_bits) instead of ending at the first one */
+struct bulk* pdmp3_amd_bulk_new_parse_bits_lsf(void) {
+  struct bulk* b = bulk_new(1, 1, 0, 1, 0);
+  if (b) b->bits_lsf = 1;
+  return b;
+}
 int pdmp3_amd_bulk_threads(const struct bulk* b) { return b ? b->nth : 0; }
+/* frames whose scalefactors + Huffman data the device stage and the host pool decoded over the decoder's life (streams decoded
+ * to their end; a stream the split scan gave up counts once) -- which stage ran, for tests and the curious */
+void pdmp3_amd_bulk_huffman_frames(const struct bulk* b, long long* device, long long* host) {
+  if (device) *device = b ? b->huff_dev : 0;
+  if (host) *host = b ? b->huff_host : 0;
+}
 /* streams this decoder's split scan (several scanner threads: device destinations, or PDMP3_BULK_SCAN_THREADS) decoded to
  * their end, and streams it gave up half way and decoded again with the one-thread scan (irregular ones: resync, tags,
  * truncation in the middle of the ring's cadence) -- same PCM either way; for tests and for whoever wonders about the rate */
@@ -180,6 +190,7 @@ static void bulk_begin(struct bulk* b) {
   id->pool_sink = b->pool_mode ? b : NULL;
   id->side_to_bits = b->bits_mode && !getenv("PDMP3_BULK_SLOW_SIDE_INFO");
   id->bits_scan = b->bits_mode;
+  id->bits_lsf = b->bits_lsf;
   id->lsf_seen = 0;
   /* (windows, flights, a running copy job: the pipeline keeps going across streams) */
   b->win[b->cur].n = 0;
@@ -226,16 +237,8 @@ static int bulk_drain(struct bulk* b) {
 static long long bulk_decode_impl(struct bulk* b, const unsigned char* mp3, size_t n, unsigned char* pcm, size_t pcm_cap,
                                   long* rate, int* channels, int drain) {
   if (!b || !b->hs || (!mp3 && n) || (!pcm && pcm_cap)) return -1;
-  /* PDMP3_ISO_LSF on a decoder whose Huffman stage is on the device: that stage reads MPEG-1 side info only, so a stream
-   * that opens with an MPEG-2 LSF / 2.5 header goes through a host-Huffman decoder this one keeps for the purpose
-   * (same device, same threads and window, same switches; the call is synchronous then) */
-  if (b->bits_mode && (b->id->iso & PDMP3_ISO_LSF) && n >= 4 && mp3[0] == 0xff && (mp3[1] & 0xe0) == 0xe0 && (mp3[1] & 0x18) != 0x18 && (mp3[1] & 0x18) != 0x08) {
-    if (!b->lsf_alt) b->lsf_alt = bulk_new(b->nth, b->window_arg, 1, 0, b->device);
-    if (!b->lsf_alt) return -1;
-    if (bulk_drain(b) != PDMP3_OK) return -1;     /* (this decoder's own streams first: the PCM destinations may overlap) */
-    b->lsf_alt->id->iso = b->id->iso;
-    return bulk_decode_impl(b->lsf_alt, mp3, n, pcm, pcm_cap, rate, channels, 1);
-  }
+  /* (PDMP3_ISO_LSF: MPEG-2 LSF / 2.5 frames go through the device's Huffman stage like MPEG-1 ones, in windows of their own --
+   *  bulk.c bits_split_kinds; the split scan is MPEG-1 only and gives such a stream to the one-thread scan) */
   bulk_begin(b);
   /* Device Huffman: nothing to reset on the host side -- the stream's first frame carries PDMP3_FR_RESET (synthesis
    * state) and, unless parse state is carried over (pdmp3()), PDMP3_FR_NEWSTREAM (scalefactors / count1), so
@@ -284,18 +287,6 @@ static long long bulk_decode_impl(struct bulk* b, const unsigned char* mp3, size
     }
   }
   if (total == PAR_NOT_TAKEN || total == PAR_GIVEN_UP) total = bulk_drive(b, mp3, n);
-  if (b->bits_mode && b->id->lsf_seen) {
-    /* an LSF frame somewhere behind the stream's first bytes (an ID3 tag in front, junk, an MPEG-1 stream that goes on as LSF): what
-     * has gone to the engine is let through and dropped, and the stream is decoded again by the host-Huffman decoder */
-    b->id->lsf_seen = 0;
-    (void)bits_close_window(b);
-    (void)bulk_drain(b);
-    b->failed = 0;
-    if (!b->lsf_alt) b->lsf_alt = bulk_new(b->nth, b->window_arg, 1, 0, b->device);
-    if (!b->lsf_alt) return -1;
-    b->lsf_alt->id->iso = b->id->iso;
-    return bulk_decode_impl(b->lsf_alt, mp3, n, pcm, pcm_cap, rate, channels, 1);
-  }
   const double t_driven = now_s();
   b->t_drive += t_driven - t_in;
   int ok = !b->failed;
@@ -304,6 +295,7 @@ static long long bulk_decode_impl(struct bulk* b, const unsigned char* mp3, size
     ok = ok && bulk_rotate(b) == PDMP3_OK;               /* the partly filled last window */
     ok = ok && bulk_finish_b(b) == PDMP3_OK;
   }
+  if (ok) { if (b->bits_mode) b->huff_dev += b->frames; else b->huff_host += b->frames; }
   if (drain || !b->bits_mode || !ok) ok = bulk_drain(b) == PDMP3_OK && ok;
   else if (b->pool_mode) ok = sub_drain_copied(b) == PDMP3_OK && ok;      /* the submitter has taken the main data out of `mp3` */
   b->t_tail += now_s() - t_driven;

@@ -76,8 +76,9 @@ struct bulk {
   int trace2; double tr_t0;           /* $PDMP3_BULK_TRACE >= 2: per-window lines, times from the stream's start */
   int count_only;                     /* scan: stage A alone */
   int bits_mode;                      /* main data goes to the device undecoded (pdmp3_hip_stream_submit_bits) */
-  int device, window_arg;             /* what bulk_new was given (the LSF decoder below is made with the same) */
-  struct bulk* lsf_alt;               /* bits mode + PDMP3_ISO_LSF: the host-Huffman decoder LSF streams go through (bulk_decode_impl) */
+  int bits_lsf;                       /* bits mode: the one-thread scan takes MPEG-2 LSF / 2.5 frames (with PDMP3_ISO_LSF) */
+  long long huff_dev, huff_host;      /* frames whose scalefactors + Huffman data the device / the host pool decoded
+                                         (pdmp3_amd_bulk_huffman_frames) */
   pdmp3_frame_bits* bits_dst; uint8_t* res_dst;   /* where stage A writes the current window (bits mode) */
   int bits_n, bits_slot, bits_open;
   pdmp3_frame_bits* rec_bits; uint8_t* rec_res;   /* parse-only bits mode: caller memory */
@@ -127,7 +128,7 @@ struct bulk {
   int sub_started, sub_quit, sub_rc;
   pthread_mutex_t sub_mu;
   pthread_cond_t sub_cv, sub_done_cv;
-  int sub_slot[8], sub_n[8], sub_row[8];
+  int sub_slot[8], sub_n[8], sub_row[8], sub_lsf[8];
   size_t sub_pool[8];                 /* pool bytes of the window (0: snapshot rows) */
   int sub_gath[8];                    /* entries of the slot's copy list */
   void* sub_dst[8];

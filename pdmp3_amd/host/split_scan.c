@@ -491,6 +491,12 @@ static void* par_scanner(void* arg) {
         fed += take;
       }
     }
+    if (id->lsf_seen) {
+      /* an MPEG-2 LSF / 2.5 frame (PDMP3_ISO_LSF), which the split scan does not take -- anywhere, the stream's last bytes
+       * included: the stream is given up and decoded by the one-thread scan, which does */
+      pthread_mutex_lock(&P->mu); P->irregular = 1; P->abort = 1; pthread_cond_broadcast(&P->cv); pthread_mutex_unlock(&P->mu);
+      break;
+    }
     if (wb->failed || P->abort) break;
     if (P->quit) { A->rc = 0; break; }
     if (pw_close_window(wb) != PDMP3_OK) break;         /* (the window, full or -- the stream's last -- partly filled) */

@@ -4,6 +4,11 @@ stream (44.1 kHz joint stereo 320 kbps).  Host stages alone
 (--parse-only, runs anywhere) or end to end on the GPU box.
 
   python tools/bulk_bench.py --frames 137813 --threads 1,8,32,64
+
+--lsf VERSION (1 = MPEG-2 LSF, 2 = MPEG-2.5) with --sfreq: an LSF stream instead (joint stereo, 64 kbps; PDMP3_ISO_LSF on
+every decoder), e.g. an hour at 22.05 kHz:
+
+  python tools/bulk_bench.py --lsf 1 --sfreq 0 --frames 137812 --threads 4 --device-out [--host-huffman]
 """
 import argparse
 import json
@@ -90,20 +95,31 @@ def main():
     ap.add_argument("--pinned", action="store_true", help="PCM into pinned host buffers (pdmp3_amd_pcm_alloc): no host copy")
     ap.add_argument("--gpus", type=int, default=1, help="--c4: decoder j runs on GPU j %% GPUS")
     ap.add_argument("--host-huffman", action="store_true", help="scalefactors + Huffman on the host pool instead of the device")
+    ap.add_argument("--lsf", type=int, default=0, choices=(0, 1, 2), metavar="VERSION",
+                    help="an MPEG-2 LSF (1) or MPEG-2.5 (2) stream at --sfreq, joint stereo 64 kbps, decoded with PDMP3_ISO_LSF")
+    ap.add_argument("--sfreq", type=int, default=0, choices=(0, 1, 2), help="--lsf: the header's sampling-frequency field")
     args = ap.parse_args()
+    if args.lsf and (args.parse_only or args.c4):
+        ap.error("--lsf: whole-stream decodes of one stream only")
     from pdmp3_amd.packer import packer
     from pdmp3_amd import api
     if args.c4:
         return c4(args, api)
     t0 = time.perf_counter()
-    mp3 = packer.generate(n_frames=args.frames, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)
+    if args.lsf:
+        mp3 = packer.generate(n_frames=args.frames, seed=0xC3, version=args.lsf, sfreq=args.sfreq, mode=1, mode_ext=2, bitrate_index=8)
+    else:
+        mp3 = packer.generate(n_frames=args.frames, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)
+    iso = api.ISO_LSF if args.lsf else 0
     a = np.frombuffer(mp3, dtype=np.uint8)
     t_gen = time.perf_counter() - t0
     t0 = time.perf_counter()
-    total, frames = api.scan_buffer(a)
+    total, frames = api.scan_buffer(a, iso)
     t_scan = time.perf_counter() - t0
-    rt = 44100.0 / 1152.0
-    out = {"frames": frames, "mp3_bytes": len(mp3), "pcm_bytes": total, "packer_s": round(t_gen, 2),
+    rate = [[44100, 48000, 32000], [22050, 24000, 16000], [11025, 12000, 8000]][args.lsf][args.sfreq if args.lsf else 0]
+    rt = rate / (576.0 if args.lsf else 1152.0)
+    out = {"frames": frames, "mp3_bytes": len(mp3), "pcm_bytes": total, "packer_s": round(t_gen, 2), "rate": rate,
+           "stream": ("MPEG-2 LSF" if args.lsf == 1 else "MPEG-2.5") + " joint stereo 64 kbps" if args.lsf else "MPEG-1 joint stereo 320 kbps",
            "scan_ms": round(t_scan * 1e3, 2), "scan_frames_per_s": round(frames / t_scan, 1), "host_cpus": os.cpu_count(),
            "runs": []}
     pin = api.PinnedPCM(total // 2) if args.pinned else None
@@ -114,6 +130,8 @@ def main():
         dout = torch.empty(max(total, 2) // 2, dtype=torch.int16, device="cuda:0")
     for th in [int(x) for x in args.threads.split(",")]:
         b = api.BulkDecoder(threads=th, window_frames=args.window, parse_only=args.parse_only, host_huffman=args.host_huffman)
+        if iso:
+            b.set_quirks(iso)
         best = None
         for _ in range(args.reps):
             t0 = time.perf_counter()
@@ -127,8 +145,10 @@ def main():
                 assert got == total
             dt = time.perf_counter() - t0
             best = dt if best is None else min(best, dt)
+        huff = b.huffman_frames() if not args.parse_only else (0, 0)
         b.close()
         out["runs"].append({"threads": th, "seconds": round(best, 4), "frames_per_s": round(frames / best, 1),
+                            "huffman_frames_device_host": list(huff),
                             "x_realtime": round(frames / best / rt, 1), "mode": "parse" if args.parse_only else ("decode, host Huffman" if args.host_huffman else "decode, device Huffman"),
                             "pcm": "device" if dout is not None else "pinned" if args.pinned else "pageable"})
     print(json.dumps(out))
