@@ -170,3 +170,92 @@ def case(name, n=N_GOLDEN, seed=None):
     if seed is None:
         seed = (sum(ord(ch) * (i + 1) for i, ch in enumerate(name)) * 2654435761) & 0x7FFFFFFF
     return make_frames(n, seed, **kw)
+
+
+def frame_is_rare(side):
+    """per frame: does the kernels' frame_is_rare() (pdmp3_amd/csrc/decode_core.h) hold -- joint stereo with
+    mode_extension bit 0 (intensity stereo), or an LSF record"""
+    fr = side["frame"].reshape(side.shape[0], -1)[:, 0].astype(np.int64)
+    lsf = side["lsf"].reshape(side.shape[0], -1)[:, 0].astype(np.int64)
+    return (((fr >> FR_MODE_SHIFT) & 3) == MODE_JOINT) & (((fr >> FR_MODEEXT_SHIFT) & 1) != 0) | ((lsf & 3) != 0)
+
+
+def composite(n_frames, seed, sparse=False):
+    """One stream with every kind of frame the launch logic tells apart, for the launch-shape tests (the other corpora are
+    one kind of frame each, 64 frames long).  make_frames() segments at the realistic level, joined without a reset (only
+    frame 0 and the `reset_every` segment carry FR_RESET); the cycle below repeats, with other seeds, up to n_frames:
+
+      long M/S runs of mixed block types at 44.1 and 48 kHz with LONE intensity-stereo frames in them (mode_ext 1 and 3,
+      long and short blocks; at least 60 frames without intensity stereo on either side), mono runs of 1, 2, 70, 130 and 66
+      frames -- the run of 1 and the run of 130 directly behind an intensity-stereo frame, the run of 66 directly behind a
+      RESET frame --, plain stereo and dual channel at 32 kHz, a segment that draws mode_ext per frame with all the ISO
+      switches set, a segment with a RESET every 17 frames that ends in one.  The rate changes at segment boundaries.
+
+    sparse: the same, the M/S runs four times as long and the mode_ext-per-frame segment 8 frames, which leaves fewer than
+    one frame_is_rare() frame in 300 (a big launch of chunks: most chunks ordinary, a few rare).
+
+    -> (spectra, side, segments, rare): segments = [(first frame, end, label)], rare = indices of the frame_is_rare() frames"""
+    k = 4 if sparse else 1
+    ms = dict(mode=MODE_JOINT, mode_ext=2, block_mix=(40, 15, 30, 15))
+    mono = dict(mode=MODE_MONO, mode_ext=0, block_mix=(50, 15, 20, 15))
+    lng, sht = dict(block_mix=(100, 0, 0, 0), count1_range=(100, 500)), dict(block_mix=(10, 0, 90, 0), count1_range=(100, 500))
+    cycle = [
+        ("ms", 100 * k, dict(ms, sfreq=0)),
+        ("is", 1, dict(lng, mode=MODE_JOINT, mode_ext=1, sfreq=0)),
+        ("mono1", 1, dict(mono, sfreq=0)),
+        ("ms", 70 * k, dict(ms, sfreq=0)),
+        ("is", 1, dict(sht, mode=MODE_JOINT, mode_ext=3, sfreq=0)),
+        ("ms", 64 * k, dict(ms, sfreq=0)),
+        ("mono70", 70, dict(mono, sfreq=0)),
+        ("ms", 61 * k, dict(ms, sfreq=1, block_mix=(10, 10, 70, 10), count1_range=(380, 576))),
+        ("is", 1, dict(sht, mode=MODE_JOINT, mode_ext=1, sfreq=1)),
+        ("ms", 62 * k, dict(ms, sfreq=1)),
+        ("mono2", 2, dict(mono, sfreq=1)),
+        ("ms", 60 * k, dict(ms, sfreq=1)),
+        ("is", 1, dict(lng, mode=MODE_JOINT, mode_ext=3, sfreq=1)),      # (M/S + intensity stereo: channel 1 is not what plain M/S makes of it)
+        ("mono130", 130, dict(mono, sfreq=1, mode_ext=2, block_mix=(30, 10, 50, 10))),
+        ("stereo", 70, dict(mode=MODE_STEREO, mode_ext=0, sfreq=2, block_mix=(50, 15, 20, 15))),
+        ("dual", 60, dict(mode=MODE_DUAL, mode_ext=2, sfreq=2, block_mix=(60, 10, 20, 10))),
+        ("ext_varies", 8 if sparse else 100, dict(ms, sfreq=0, mode_ext_choices=(2, 2, 2, 3, 1, 0, 2), count1_range=(100, 576), iso=7)),
+        ("ms", 60 * k, dict(ms, sfreq=0, iso=7)),
+        ("resets", 86, dict(ms, sfreq=1, reset_every=17)),          # (86 = 5 x 17 + 1: the segment's last frame is a RESET frame)
+        ("mono66", 66, dict(mono, sfreq=1)),
+    ]
+    sp_parts, sd_parts, segments = [], [], []
+    at = i = 0
+    while at < n_frames:
+        label, n, kw = cycle[i % len(cycle)]
+        n = min(n, n_frames - at)
+        sp, sd = make_frames(n, (int(seed) * 1000003 + 7919 * i) & 0x7FFFFFFF, gain_range=FS_GAIN, sf_max=8, **kw)
+        if i:
+            sd["frame"][0] &= ~np.uint8(FR_RESET)
+        sp_parts.append(sp)
+        sd_parts.append(sd)
+        segments.append((at, at + n, label))
+        at += n
+        i += 1
+    spectra, side = np.concatenate(sp_parts), np.concatenate(sd_parts)
+    return spectra, side, segments, np.flatnonzero(frame_is_rare(side))
+
+
+def rare_chunks(side, chunk_frames):
+    """Which chunks of a launch cut into chunks of chunk_frames frames must run the copy of the chunk code that has intensity
+    stereo in it (on the device: are k_decode_rare's, not k_decode's).  The rule, restated from what a chunk decodes: its own
+    frames; its halo (inside the four frames before it); and, when the frame before it is a mono frame without RESET, the
+    pre-halo that fetches channel 1 from the last two-channel-or-RESET frame before that one, and the frame in front of it.
+    -> bool per chunk"""
+    n = side.shape[0]
+    fr = side["frame"].reshape(n, -1)[:, 0].astype(np.int64)
+    rare = frame_is_rare(side)
+    mono = ((fr >> FR_MODE_SHIFT) & 3) == MODE_MONO
+    reset = (fr & FR_RESET) != 0
+    anchor = np.maximum.accumulate(np.where(~mono | reset, np.arange(n), -1))      # last two-channel-or-RESET frame <= f
+    out = np.zeros((n + chunk_frames - 1) // chunk_frames, dtype=bool)
+    for c in range(out.size):
+        f0, f1 = c * chunk_frames, min(n, (c + 1) * chunk_frames)
+        if rare[max(0, f0 - 4):f1].any():
+            out[c] = True
+        elif f0 >= 2 and mono[f0 - 1] and not reset[f0 - 1]:
+            fs = int(anchor[f0 - 2])
+            out[c] = fs >= 0 and bool(rare[fs] or (fs > 0 and rare[fs - 1]))
+    return out

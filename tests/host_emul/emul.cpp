@@ -170,6 +170,19 @@ extern "C" int emul_decode_frames_ring(const int16_t* spectra, const pdmp3_gc_si
   return 0;
 }
 
+// chunk_is_rare (which of the two copies of its code a chunk runs, and on the device which of k_decode / k_decode_rare
+// takes it) as a wave, per chunk of a launch of n_frames frames cut into chunks of chunk_frames: out[chunk] = 0 / 1
+extern "C" void emul_chunk_is_rare(const pdmp3_gc_side* side, int n_frames, int chunk_frames, uint8_t* out) {
+  if (chunk_frames <= 0) chunk_frames = n_frames;
+  DecodeArgs a{nullptr, side, nullptr, nullptr, nullptr, nullptr, nullptr, n_frames, chunk_frames, nullptr, nullptr, nullptr, 0u};
+  const int nchunks = (n_frames + chunk_frames - 1) / chunk_frames;
+  for (int c = 0; c < nchunks; ++c) {
+    bool r = false;
+    emu::run_wave([&] { const bool v = chunk_is_rare(a, c); if (emu::lane() == 0) r = v; });
+    out[c] = r ? 1 : 0;
+  }
+}
+
 extern "C" size_t emul_state_floats() { return kStateFloats; }
 
 extern "C" void emul_generate_frames(uint64_t seed, int64_t first, int n, int16_t* spectra, pdmp3_gc_side* side) {

@@ -11,7 +11,7 @@ import pytest
 
 import corpus
 from conftest import C2_SEED
-from util import assert_pcm_close, nch_of
+from util import assert_pcm_close, check_launch_pcm, nch_of, sentinel_buffer
 
 
 def _p(a):
@@ -296,3 +296,149 @@ def test_emul_int16_conversion_lane_form_equals_the_reference_conversion(emul):
     ok = ~(s > np.float32(65538.0))                     # NaNs stay in: the fast form must get them right by itself
     assert np.array_equal(fast[ok], exact[ok])
     assert (exact[np.isnan(s)] == -32767).all() and (fast[np.isnan(s)] == -32767).all()
+
+
+# ---- the composite stream (corpus.composite): every kind of frame the launch logic tells apart, in one stream ----------
+# The CPU twin of tests/test_gpu_launch_shapes.py: the kernels' source on the host in every form -- chunks of many lengths
+# (the rare / ordinary copy per chunk by chunk_is_rare, as on the device), the granule form with every line-table hint and
+# with every far wait given up, float PCM -- against the oracle, into sentinel-filled buffers, bit-identical to each other.
+COMPOSITE_FRAMES = 1066                            # one cycle of corpus.composite
+COMPOSITE_SEED = 20240
+RARE_CHUNK_LENGTHS = [1, 7, 61, 64, 65, 100, 257]
+
+
+@pytest.fixture(scope="module")
+def composite(oracle, emul):
+    sp, sd, segments, rare = corpus.composite(COMPOSITE_FRAMES, COMPOSITE_SEED)
+    want, want_f32 = oracle.decode_f32(sp, sd)
+    whole, whole_state = _emul_into_sentinel(emul, sp, sd, "chunks", 0)
+    return dict(sp=sp, sd=sd, segments=segments, rare=rare, want=want, want_f32=want_f32, whole=whole, whole_state=whole_state)
+
+
+def _emul_into_sentinel(emul, sp, sd, form, arg=0, f32=False, debug=0):
+    """-> (sentinel buffer decoded into, state block left behind)"""
+    n = sp.shape[0]
+    out = sentinel_buffer(n, f32)
+    st = np.zeros(emul.emul_state_floats(), np.float32)
+    if form == "chunks" and f32:
+        emul.emul_decode_frames_f32(_p(sp), _p(sd), n, _p(st), _p(out), arg)
+    elif form == "chunks":
+        emul.emul_decode_frames(_p(sp), _p(sd), n, _p(st), _p(out), None, arg)
+    else:
+        emul.emul_decode_frames_granules(_p(sp), _p(sd), n, _p(st), None if f32 else _p(out), _p(out) if f32 else None, debug, arg)
+    return out, st
+
+
+def test_composite_holds_what_it_promises():
+    """conditions on the input (no decoder involved): lone intensity-stereo frames 60 frames from any other, mono runs of
+    1, 2, 66, 70 and 130 frames, one behind an intensity-stereo frame and one behind a RESET frame, every mode, the three
+    rates, the ISO switches, RESET frames in mid-stream; the sparse form: fewer than one rare frame in 300"""
+    sp, sd, segments, rare = corpus.composite(COMPOSITE_FRAMES, COMPOSITE_SEED)
+    assert sp.shape[0] == COMPOSITE_FRAMES and segments[0][0] == 0 and segments[-1][1] == COMPOSITE_FRAMES
+    assert all(a[1] == b[0] for a, b in zip(segments[:-1], segments[1:]))
+    fr = sd["frame"][:, 0, 0].astype(int)
+    mode, reset = (fr >> 2) & 3, (fr & 0x40) != 0
+    lone = [a for a, b, label in segments if label == "is"]
+    assert len(lone) == 4 and all(f in rare for f in lone)
+    for f in lone:
+        assert not any(0 < abs(int(r) - f) < 60 for r in rare), f
+    assert sorted({(int(fr[f]) >> 4) & 3 for f in lone}) == [1, 3]
+    runs = {label: (a, b) for a, b, label in segments if label.startswith("mono")}
+    assert sorted(b - a for a, b in runs.values()) == [1, 2, 66, 70, 130]
+    assert all((mode[a:b] == 3).all() and mode[a - 1] != 3 and mode[b] != 3 for a, b in runs.values() if b < COMPOSITE_FRAMES)
+    assert runs["mono1"][0] - 1 in rare and runs["mono130"][0] - 1 in rare and reset[runs["mono66"][0] - 1]
+    assert set(mode) == {0, 1, 2, 3} and set(fr & 3) == {0, 1, 2} and set(sd["iso"][:, 0, 0]) == {0, 7}
+    assert reset[0] and reset[1:].sum() == 5 and not reset[[a for a, b, label in segments[1:]]].any()
+    ext = [(a, b) for a, b, label in segments if label == "ext_varies"][0]
+    k = np.isin(np.arange(*ext), rare)
+    assert 10 <= k.sum() <= k.size - 10 and (k[1:] != k[:-1]).sum() >= 20             # rare and ordinary frames alternating
+    n = 14400
+    sp, sd, segments, rare = corpus.composite(n, COMPOSITE_SEED + 1, sparse=True)
+    assert 20 <= rare.size < n / 300
+    assert {"is", "mono1", "mono2", "mono70", "mono130", "mono66", "stereo", "dual", "ext_varies", "resets"} <= {s[2] for s in segments}
+
+
+@pytest.mark.parametrize("chunk", RARE_CHUNK_LENGTHS + [0])
+def test_emul_composite_chunks(emul, composite, chunk):
+    c = composite
+    got, st = _emul_into_sentinel(emul, c["sp"], c["sd"], "chunks", chunk)
+    dmax, share = check_launch_pcm(got, c["want"], c["sd"], "chunk %d" % chunk)
+    print("composite, chunks of %d: max %d LSB, %.4f %% of the samples differ" % (chunk, dmax, 100 * share))
+    assert np.array_equal(got, c["whole"]), "chunks of %d: PCM differs from the whole stream as one chunk" % chunk
+    assert np.array_equal(st.view(np.uint32), c["whole_state"].view(np.uint32))
+    kinds = corpus.rare_chunks(c["sd"], chunk or COMPOSITE_FRAMES)
+    assert chunk in (257, 0) or (kinds.any() and not kinds.all())                      # both copies of the chunk code ran
+
+
+@pytest.mark.parametrize("sf_hint,debug", [(0, 0), (1, 0), (2, 0), (0, 1), (2, 1)])
+def test_emul_composite_granules(emul, composite, sf_hint, debug):
+    c = composite
+    got, st = _emul_into_sentinel(emul, c["sp"], c["sd"], "granules", sf_hint, debug=debug)
+    dmax, share = check_launch_pcm(got, c["want"], c["sd"], "granules, hint %d, debug %d" % (sf_hint, debug))
+    print("composite, granule form (sf_hint %d, debug %d): max %d LSB, %.4f %% differ" % (sf_hint, debug, dmax, 100 * share))
+    assert np.array_equal(got, c["whole"])
+    assert np.array_equal(st.view(np.uint32), c["whole_state"].view(np.uint32))
+
+
+def test_emul_composite_float_pcm(emul, composite):
+    c = composite
+    assert 1.0 < float(np.abs(c["want_f32"]).max()) < 1.5             # (the level the 1e-5 bar is literal at)
+    outs = []
+    for form, arg, debug in (("chunks", 0, 0), ("chunks", 61, 0), ("chunks", 7, 0), ("granules", 0, 0), ("granules", 1, 1)):
+        got, st = _emul_into_sentinel(emul, c["sp"], c["sd"], form, arg, f32=True, debug=debug)
+        dmax, _ = check_launch_pcm(got, c["want_f32"], c["sd"], "float, %s %d" % (form, arg), tol=1e-5)
+        print("composite, float PCM (%s %d): max difference %.3g" % (form, arg, dmax))
+        body = got[:-64].astype(np.float64)
+        q = np.clip(np.trunc(body * 32767.0), -32767, 32767).astype(np.int16)
+        same = q == c["whole"][:-64]
+        assert same[c["whole"][:-64] != 0x5A5A].all(), "trunc(f32 * 32767) != the int16 PCM"
+        assert np.array_equal(st.view(np.uint32), c["whole_state"].view(np.uint32))
+        outs.append(got)
+    assert all(np.array_equal(o.view(np.uint32), outs[0].view(np.uint32)) for o in outs[1:])
+
+
+def _emul_rare(emul, sd, chunk):
+    out = np.zeros((sd.shape[0] + chunk - 1) // chunk, np.uint8)
+    emul.emul_chunk_is_rare(_p(sd), sd.shape[0], chunk, _p(out))
+    return out.astype(bool)
+
+
+def test_chunk_is_rare_on_the_composite(emul, composite):
+    """chunk_is_rare() as a wave against corpus.rare_chunks (the rule restated): beyond its first trip of 64 frames, and
+    through mono runs longer than a wave.  A false negative decodes an intensity-stereo frame without intensity stereo."""
+    sd = composite["sd"]
+    for chunk in RARE_CHUNK_LENGTHS:
+        want = corpus.rare_chunks(sd, chunk)
+        assert np.array_equal(_emul_rare(emul, sd, chunk), want), chunk
+        assert want.any() and not want.all()
+    sd2 = corpus.composite(5000, COMPOSITE_SEED + 1, sparse=True)[1]
+    for chunk in RARE_CHUNK_LENGTHS:
+        assert np.array_equal(_emul_rare(emul, sd2, chunk), corpus.rare_chunks(sd2, chunk)), chunk
+
+
+def test_chunk_is_rare_one_rare_frame_around_mono_runs(emul):
+    """200 random placements: joint stereo, a mono run of 0 .. 140 frames somewhere (a RESET frame in or before it now and
+    then), ONE intensity-stereo frame anywhere near it.  Only the frame bytes matter to chunk_is_rare."""
+    rs = np.random.RandomState(77)
+    n = 420
+    hits = 0
+    for trial in range(200):
+        sd = np.zeros((n, 2, 2), dtype=corpus.SIDE_DTYPE)
+        fr = np.full(n, (corpus.MODE_JOINT << corpus.FR_MODE_SHIFT) | (2 << corpus.FR_MODEEXT_SHIFT), np.uint8)
+        m = int(rs.randint(0, 141))
+        a = int(rs.randint(5, n - m - 5))
+        fr[a:a + m] = (corpus.MODE_MONO << corpus.FR_MODE_SHIFT) | (int(rs.randint(0, 4)) << corpus.FR_MODEEXT_SHIFT)
+        near = [a - 2, a - 1, a, a + m - 1, a + m, a + m + 1]
+        q = int(near[rs.randint(0, 6)] if rs.rand() < 0.6 else rs.randint(0, n))
+        q = min(max(q, 0), n - 1)
+        if (fr[q] >> corpus.FR_MODE_SHIFT) & 3 == corpus.MODE_JOINT:
+            fr[q] |= 1 << corpus.FR_MODEEXT_SHIFT
+        if rs.rand() < 0.3:
+            fr[min(n - 1, max(0, a + int(rs.randint(-3, m + 3))))] |= corpus.FR_RESET
+        fr[0] |= corpus.FR_RESET
+        sd["frame"] = fr[:, None, None]
+        for chunk in RARE_CHUNK_LENGTHS:
+            want = corpus.rare_chunks(sd, chunk)
+            assert np.array_equal(_emul_rare(emul, sd, chunk), want), (trial, chunk, a, m, q)
+            hits += int(want.any())
+    assert hits > 700

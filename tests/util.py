@@ -65,3 +65,47 @@ def level(pcm):
     if a.size == 0:
         return 0, 0, 0.0
     return int(np.median(a)), int(np.percentile(a, 99)), float((a >= 32767).mean())
+
+
+# What a launch must leave alone: tests decode into buffers pre-filled with these (int16 / the bits of a float32) and look
+SENTINEL = 0x5A5A
+SENTINEL_F32_BITS = 0x5A5A5A5A
+GUARD = 64                                        # values behind the last frame's place that belong to the buffer
+
+
+def sentinel_buffer(n_frames, f32=False):
+    """numpy buffer for n_frames frames of PCM plus the guard, every value the sentinel"""
+    if f32:
+        return np.full(n_frames * 2304 + GUARD, SENTINEL_F32_BITS, dtype=np.uint32).view(np.float32)
+    return np.full(n_frames * 2304 + GUARD, SENTINEL, dtype=np.int16)
+
+
+def check_launch_pcm(got_flat, want, side, what="", tol=None):
+    """got_flat: what a decode of the records `side` left in a sentinel_buffer(); want: the oracle's [n][2304] (int16 or float32).
+    Every sample the contract of include/pdmp3_hip.h has written (a mono frame: the first half of its place) is within
+    +-1 LSB of the oracle's and at most 2 % of them differ at all (float: within tol absolute); everything else -- the second
+    half of a mono frame's place, the guard -- still holds the sentinel.  -> (max difference, share of differing samples)"""
+    n = want.shape[0]
+    f32 = want.dtype == np.float32
+    assert got_flat.size == n * 2304 + GUARD and got_flat.dtype == want.dtype
+    bits = got_flat.view(np.uint32) if f32 else got_flat
+    sent = SENTINEL_F32_BITS if f32 else SENTINEL
+    assert (bits[n * 2304:] == sent).all(), "%s: written behind the last frame" % what
+    fr = side["frame"].reshape(n, -1)[:, 0]
+    written = np.ones((n, 2304), dtype=bool)
+    written[((fr >> 2) & 3) == 3, 1152:] = False
+    body = bits[:n * 2304].reshape(n, 2304)
+    bad = np.flatnonzero((body != sent)[~written])
+    assert bad.size == 0, "%s: %d values written into the unused half of mono frames' places" % (what, bad.size)
+    got = got_flat[:n * 2304].reshape(n, 2304)
+    if f32:
+        d = np.abs(got[written].astype(np.float64) - want[written])
+        assert not np.isnan(d).any() and d.max() <= tol, "%s: float PCM differs by %g > %g" % (what, d.max(), tol)
+        return float(d.max()), float((d > 0).mean())
+    d = np.abs(got.astype(np.int32) - want.astype(np.int32))
+    d[~written] = 0
+    assert d.max() <= 1, "%s: PCM max-abs-diff %d LSB > 1 (at %s; a frame left at the sentinel reads %d)" % (
+        what, d.max(), np.unravel_index(d.argmax(), d.shape), SENTINEL)
+    share = float((d[written] > 0).mean())
+    assert share <= 0.02, "%s: %.3f %% of the samples differ from the oracle's" % (what, 100 * share)
+    return int(d.max()), share
