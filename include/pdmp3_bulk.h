@@ -177,6 +177,71 @@ long long pdmp3_amd_stream_loop(const unsigned char* mp3, size_t n, unsigned cha
  * CLI driver writes "<first name>.wav" instead of ".raw" when PDMP3_CLI_WAV=1 is set.  PDMP3_OK or PDMP3_ERR. */
 int pdmp3_amd_write_wav(const char* path, const void* pcm, size_t bytes, long rate, int channels, int float32);
 
+/* ---- Frame ranges and batches of clips ----
+ * A range's PCM is DEFINED as a byte slice of what pdmp3() writes for the whole stream: frames [a, b) are the bytes
+ * [pcm_offset(a), pcm_offset(b)) of the whole-stream decode, bit for bit.  Nothing else changes; no entry point above
+ * returns anything other than it did.
+ *
+ * A stream index is built once per stream: the one-thread scan in its count-only form (what counts as a frame and each
+ * frame's PCM size are exactly pdmp3_amd_scan_buffer_iso's, whichever form the index takes -- a mono frame of a stereo
+ * stream is 2304 bytes, an LSF frame half of an MPEG-1 one), and, where the split scan's pre-pass takes the stream (MPEG-1,
+ * no resync, H9, H16 / H18 or tags; the same verdict as for the whole-stream decoder), the pre-pass's snapshots every
+ * `spacing` frames (256 by default), from which a scan can start in the middle of the stream.  A stream the pre-pass does
+ * not take (every LSF stream among them) keeps no snapshot: its clips are scanned from frame 0 (pdmp3_amd_index_split says
+ * which).  Memory: 13 bytes per frame (PCM offset, flag byte, the side-info bits of the halo rule), 24 more per frame with
+ * snapshots (the pre-pass's frame records, which a scan started from a snapshot reads); per `spacing` frames 128 bytes of
+ * halo checkpoint and, with snapshots, 128 bytes + 4 per frame whose main data is still visible in the reservoir.  About
+ * 5.3 MB for an hour at 44.1 kHz (137 812 frames), next to the 57 MB of a 128 kbps stream; built in 0.2-0.3 ms per MB of
+ * stream on one core.  The index does not keep the
+ * stream: the clip calls are given the same bytes again (n is checked).
+ * iso_mask: only PDMP3_ISO_LSF matters (it changes what counts as a frame); a decoder's switches must agree with it.
+ * A stream whose scan ends in a ring replay gives an index whose frame count is PDMP3_BULK_REPLAY. */
+typedef struct pdmp3_amd_index pdmp3_amd_index;
+pdmp3_amd_index* pdmp3_amd_index_new(const unsigned char* mp3, size_t n, unsigned iso_mask);
+/* ... with snapshots every `spacing` frames (<= 0: the default).  No result depends on it (tests build with two). */
+pdmp3_amd_index* pdmp3_amd_index_new_spacing(const unsigned char* mp3, size_t n, unsigned iso_mask, int spacing);
+void pdmp3_amd_index_delete(pdmp3_amd_index* ix);
+long long pdmp3_amd_index_frames(const pdmp3_amd_index* ix);   /* == pdmp3_amd_scan_buffer_iso's frames, or PDMP3_BULK_REPLAY */
+/* bytes of pdmp3()'s output before `frame`; frame == frames gives the total; -1 outside [0, frames] */
+long long pdmp3_amd_index_pcm_offset(const pdmp3_amd_index* ix, long long frame);
+/* all frames + 1 of them into out[0 .. min(cap, frames + 1)); returns frames + 1 (or the index's negative frame count) */
+long long pdmp3_amd_index_pcm_offsets(const pdmp3_amd_index* ix, long long* out, size_t cap);
+/* 1: the pre-pass took the stream (snapshots); 0: the one-thread scan built the index (scans start at frame 0) */
+int pdmp3_amd_index_split(const pdmp3_amd_index* ix);
+
+/* A clip: frames [first_frame, first_frame + n_frames) of a stream, both clamped to the index's frames.  dst is pageable,
+ * pinned (pdmp3_amd_pcm_alloc) or device memory of the decoder's GPU, as for pdmp3_amd_bulk_decode. */
+typedef struct {
+  const unsigned char* mp3; size_t n; const pdmp3_amd_index* index;
+  long long first_frame, n_frames;
+  void* dst; size_t dst_cap;
+} pdmp3_amd_clip;
+/* Decodes a batch of clips, of one stream or of many.  pcm_bytes[k] = pcm_offset(b) - pcm_offset(a) of clip k's clamped
+ * range [a, b); dst[0 .. min(that, dst_cap)) receives exactly those bytes of the whole-stream output (interleaved int16 as
+ * pdmp3_amd_bulk_decode writes it); nothing past them is written.  Each clip is decoded from a frame `first` <= a that the
+ * halo rule picks so that the result is exact -- two frames, further back past mono runs, and as far
+ * back as the frames that last set a scalefactor or count1 value the range reads -- and is scanned from the index's nearest
+ * snapshot at or before `first`; the PCM of [first, a) is thrown away on the GPU (k_clip_pack places the kept frames: on
+ * the device for device destinations, mono / stereo / LSF mixed or not; through the slot's pinned buffer, kept bytes only,
+ * for host ones).  The clips' frames share the engine's windows (a window costs the GPU about 150 us whatever its size);
+ * a clip's first frame carries PDMP3_FR_RESET and PDMP3_FR_NEWSTREAM; windows split where the version changes, as for a
+ * whole stream; a clip longer than a window goes on in the next with its state carried.
+ * Synchronous: every clip is in place on return; earlier asynchronous decodes are waited for first.  Returns 0; -1 on a
+ * bad argument, an engine failure, a decoder with host Huffman or parse only (not supported), or a decoder whose
+ * PDMP3_ISO_LSF switch differs from an index's; PDMP3_BULK_REPLAY when a clip's index says so (those clips' pcm_bytes
+ * are PDMP3_BULK_REPLAY too and nothing of them is written; the others are decoded). */
+int pdmp3_amd_bulk_decode_clips(pdmp3_amd_bulk* b, const pdmp3_amd_clip* clips, int n_clips, long long* pcm_bytes);
+/* frames the decoder's clips kept (the sum of their clamped n_frames) and frames it decoded in front of them and threw
+ * away (the sum of a - first) over its life: a stream that forces long halos shows here.  Either pointer may be NULL. */
+void pdmp3_amd_bulk_clip_stats(const pdmp3_amd_bulk* b, long long* clip_frames, long long* halo_frames);
+/* Host tests (a decoder of pdmp3_amd_bulk_new_parse_only): the host stage on ONE range, with the same index and the same
+ * halo rule as the clip decode: the records of frames [first, b) into spectra / side (cap_frames frames), *decoded_from =
+ * first.  lookback = 0 leaves out the scalefactor / count1 part of the rule (the synthesis halo alone: tests show that
+ * it matters).  Returns b - first, or -1 / PDMP3_BULK_REPLAY. */
+long long pdmp3_amd_bulk_parse_range(pdmp3_amd_bulk* b, const unsigned char* mp3, size_t n, const pdmp3_amd_index* ix,
+                                     long long first_frame, long long n_frames, int lookback, int16_t* spectra, pdmp3_gc_side* side,
+                                     size_t cap_frames, long long* decoded_from);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

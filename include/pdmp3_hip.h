@@ -436,6 +436,24 @@ size_t pdmp3_hip_stream_pool_bytes(const pdmp3_hip_stream* hs);            /* ca
 /* like pdmp3_hip_stream_submit_bits_to, from the slot's bits, descriptors and the first pool_bytes of its pool */
 int pdmp3_hip_stream_submit_pool_to(pdmp3_hip_stream* hs, int slot, int n_frames, size_t pool_bytes, void* pinned_dst, int row_bytes);
 
+/* Clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips): a window whose PCM does not go to one contiguous place.  The
+ * batch is decoded like pdmp3_hip_stream_submit_bits (snapshot rows), its PCM stays in the slot's device buffer -- frame f at
+ * byte f * 4608 of an MPEG-1 window, in pdmp3_hip_decode_lsf_frames' layout in an LSF one -- and k_clip_pack then copies
+ * each piece: `bytes` bytes from offset `src` of that buffer to device address `dst` (memory of the engine's device: a
+ * caller's tensor, or the slot's clip stage).  Pieces must not overlap each other's destinations; src + bytes stays inside
+ * the batch's PCM.  stage_bytes > 0: the first stage_bytes of the slot's clip stage (pdmp3_hip_stream_slot_clip_stage) are
+ * then downloaded into the slot's pinned PCM buffer (pdmp3_hip_stream_slot_pcm), from where the host copies them to host
+ * destinations.  At most max_frames pieces; returns at once, pdmp3_hip_stream_wait() as for the other submits. */
+typedef struct pdmp3_clip_piece {
+  uint64_t dst;                             /* device address of the piece's first byte                 */
+  uint32_t src;                             /* byte offset in the batch's PCM                           */
+  uint32_t bytes;
+} pdmp3_clip_piece;                         /* 16 bytes */
+int pdmp3_hip_stream_submit_bits_clips(pdmp3_hip_stream* hs, int slot, int n_frames, const pdmp3_clip_piece* pieces, int n_pieces,
+                                       size_t stage_bytes);
+/* device memory of max_frames * 4608 bytes per slot (allocated on first use), NULL on failure */
+void* pdmp3_hip_stream_slot_clip_stage(pdmp3_hip_stream* hs, int slot);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -64,6 +64,9 @@ int pdmp3_node_ranks(const pdmp3_node* node);
  * byte per frame -- says so) and discards the PCM of the first *discard = lo - *first frames.  frame_flags may be NULL. */
 void pdmp3_node_shard(long long n_frames, int rank, int world, const uint8_t* frame_flags,
                       long long* first, long long* count, long long* discard);
+/* The halo rule of pdmp3_node_shard by itself: the first frame a decode that emits frames from `lo` on has to start at
+ * (frame_flags[0 .. lo) are read).  The whole-stream decoder's clips (include/pdmp3_bulk.h) take their synthesis halo from it. */
+long long pdmp3_node_halo_start(long long lo, const uint8_t* frame_flags);
 
 /* A stream that is at hand as records in HOST memory (spectra: n_frames x 2304 int16, side: n_frames x 4 records, the
  * layout of pdmp3_hip_decode_frames) -> n_frames x 4608 bytes of PCM in d_pcm, DEVICE memory on devices[0].  Every rank

@@ -15,7 +15,9 @@ _LIB = None
 
 BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_new_on", "pdmp3_amd_bulk_delete", "pdmp3_amd_bulk_threads", "pdmp3_amd_bulk_split_scans", "pdmp3_amd_bulk_huffman_frames", "pdmp3_amd_bulk_set_quirks",
                 "pdmp3_amd_scan_buffer", "pdmp3_amd_scan_buffer_iso", "pdmp3_amd_corpus_assign", "pdmp3_amd_corpus_decode", "pdmp3_amd_bulk_decode", "pdmp3_amd_bulk_decode_async", "pdmp3_amd_bulk_wait", "pdmp3_amd_bulk_new_parse_only", "pdmp3_amd_bulk_parse",
-                "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_new_parse_bits_lsf", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav"]
+                "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_new_parse_bits_lsf", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav",
+                "pdmp3_amd_index_new", "pdmp3_amd_index_new_spacing", "pdmp3_amd_index_delete", "pdmp3_amd_index_frames", "pdmp3_amd_index_pcm_offset",
+                "pdmp3_amd_index_pcm_offsets", "pdmp3_amd_index_split", "pdmp3_amd_bulk_decode_clips", "pdmp3_amd_bulk_clip_stats", "pdmp3_amd_bulk_parse_range"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -93,6 +95,22 @@ def load_library():
     lib.pdmp3_amd_pcm_free.argtypes = [vp]
     lib.pdmp3_amd_bulk_parse.restype = C.c_longlong
     lib.pdmp3_amd_bulk_parse.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, C.POINTER(C.c_longlong)]
+    if hasattr(lib, "pdmp3_amd_index_new_spacing"):          # (frame ranges and clips: absent from older builds, PDMP3_HOST_LIB A/B runs)
+        ll = C.c_longlong
+        lib.pdmp3_amd_index_new_spacing.restype = vp
+        lib.pdmp3_amd_index_new_spacing.argtypes = [vp, C.c_size_t, C.c_uint, C.c_int]
+        lib.pdmp3_amd_index_delete.argtypes = [vp]
+        lib.pdmp3_amd_index_delete.restype = None
+        lib.pdmp3_amd_index_frames.argtypes = [vp]
+        lib.pdmp3_amd_index_frames.restype = ll
+        lib.pdmp3_amd_index_pcm_offsets.argtypes = [vp, vp, C.c_size_t]
+        lib.pdmp3_amd_index_pcm_offsets.restype = ll
+        lib.pdmp3_amd_index_split.argtypes = [vp]
+        lib.pdmp3_amd_bulk_decode_clips.argtypes = [vp, vp, C.c_int, vp]
+        lib.pdmp3_amd_bulk_clip_stats.argtypes = [vp, C.POINTER(ll), C.POINTER(ll)]
+        lib.pdmp3_amd_bulk_clip_stats.restype = None
+        lib.pdmp3_amd_bulk_parse_range.argtypes = [vp, vp, C.c_size_t, vp, ll, ll, C.c_int, vp, vp, C.c_size_t, C.POINTER(ll)]
+        lib.pdmp3_amd_bulk_parse_range.restype = ll
     _LIB = lib
     return lib
 
@@ -247,6 +265,64 @@ def scan_buffer(mp3, iso=0):
     return total, frames.value
 
 
+PDMP3_BULK_REPLAY = -2
+
+
+class StreamIndex:
+    """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
+    built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
+    .pcm_offsets (numpy int64, frames + 1 entries: bytes of the whole-stream output in front of each frame), .split (the
+    split scan's pre-pass took the stream: clips are scanned from its snapshots; False: from frame 0).  iso: the decoder's
+    switches (only ISO_LSF matters); spacing: frames between snapshots (0: the library's default).  The index does not keep
+    the stream: the decode calls are given the same bytes."""
+
+    def __init__(self, mp3, iso=0, spacing=0):
+        self.lib = load_library()
+        a = _as_u8(mp3)
+        self.n = len(mp3)
+        self.iso = iso
+        self.h = self.lib.pdmp3_amd_index_new_spacing(a.ctypes.data_as(C.c_void_p), len(mp3), iso, int(spacing))
+        if not self.h:
+            raise MemoryError("pdmp3_amd_index_new failed")
+        self.frames = self.lib.pdmp3_amd_index_frames(self.h)
+        self.replay = self.frames == PDMP3_BULK_REPLAY
+        self.split = bool(self.lib.pdmp3_amd_index_split(self.h))
+        self.pcm_offsets = None
+        if not self.replay:
+            self.pcm_offsets = np.empty(self.frames + 1, dtype=np.int64)
+            self.lib.pdmp3_amd_index_pcm_offsets(self.h, self.pcm_offsets.ctypes.data_as(C.c_void_p), self.frames + 1)
+
+    def clamp(self, first, count):
+        """the range [a, b) a clip of (first, count) stands for"""
+        a = min(max(int(first), 0), self.frames)
+        return a, a + min(max(int(count), 0), self.frames - a)
+
+    def close(self):
+        if self.h:
+            self.lib.pdmp3_amd_index_delete(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                          # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def _int16_buffer(o, ndim):
+    """(address, bytes) of a contiguous int16 numpy array or torch tensor"""
+    if hasattr(o, "data_ptr"):
+        assert o.dim() == ndim and o.is_contiguous() and o.element_size() == 2
+        return o.data_ptr(), o.numel() * 2
+    assert o.ndim == ndim and o.flags["C_CONTIGUOUS"] and o.dtype == np.int16
+    return o.ctypes.data, o.nbytes
+
+
+class _Clip(C.Structure):                          # include/pdmp3_bulk.h pdmp3_amd_clip
+    _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("first_frame", C.c_longlong),
+                ("n_frames", C.c_longlong), ("dst", C.c_void_p), ("dst_cap", C.c_size_t)]
+
+
 class BulkDecoder:
     """include/pdmp3_bulk.h: whole-stream decode, host Huffman on a thread pool + pipelined GPU batches.
     parse_only=True: host stages only (records out), for machines without a GPU."""
@@ -355,8 +431,82 @@ class BulkDecoder:
         assert got == total, (got, total)
         return out[:total // 2]
 
+    def decode_clips(self, clips, out):
+        """pdmp3_amd_bulk_decode_clips: clips = sequence of (mp3, StreamIndex, first frame, frames); out = ONE int16 array
+        of shape [K, stride] -- a torch tensor (device memory of the decoder's GPU, or host memory) or a numpy array
+        (pageable, or a view of pinned memory) -- or a list of K contiguous 1-D ones; row k receives clip k's PCM: exactly the bytes [pcm_offsets[a],
+        pcm_offsets[b]) of the whole-stream output for the clip's clamped range [a, b), as far as the row holds them.  Bytes
+        past a clip's count are not written.  Synchronous.  -> numpy int64 byte counts, one per clip.  RingReplay (with
+        .pcm_bytes) when a clip's stream is one the scan calls a ring replay; the other clips are decoded all the same."""
+        k = len(clips)
+        if isinstance(out, (list, tuple)):             # (or one 1-D int16 buffer per clip)
+            assert len(out) >= k
+            dst = [_int16_buffer(o, 1) for o in out[:k]]
+        elif hasattr(out, "data_ptr"):
+            assert out.dim() == 2 and out.shape[0] >= k and out.stride(1) == 1 and out.element_size() == 2
+            dst = [(out.data_ptr() + i * out.stride(0) * 2, out.shape[1] * 2) for i in range(k)]
+        else:
+            assert out.ndim == 2 and out.shape[0] >= k and out.strides[1] == 2 and out.dtype == np.int16
+            dst = [(out.ctypes.data + i * out.strides[0], out.shape[1] * 2) for i in range(k)]
+        arr = (_Clip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, first, count) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _Clip(a.ctypes.data, len(mp3), ix.h, int(first), int(count), dst[i][0], dst[i][1])
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips(self.h, arr, k, got)
+        pcm_bytes = np.array(got[:k], dtype=np.int64)
+        if rc == PDMP3_BULK_REPLAY:
+            e = RingReplay("the reference replays its input ring on a clip's stream (no finite output)")
+            e.pcm_bytes = pcm_bytes
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return pcm_bytes
+
+    def decode_range(self, mp3, index, first, count):
+        """frames [first, first + count) of the stream (clamped to index.frames) -> int16 numpy: exactly that slice of
+        decode(mp3)"""
+        if index.replay:
+            raise RingReplay("the reference replays its input ring on this stream (no finite output)")
+        a, b = index.clamp(first, count)
+        nbytes = int(index.pcm_offsets[b] - index.pcm_offsets[a])
+        out = np.empty((1, max(nbytes // 2, 1)), dtype=np.int16)
+        got = self.decode_clips([(mp3, index, first, count)], out)
+        assert got[0] == nbytes, (got[0], nbytes)
+        return out[0, :nbytes // 2]
+
+    def clip_stats(self):
+        """-> (frames the decoder's clips kept, frames it decoded in front of them and threw away), over its life"""
+        c, h = C.c_longlong(0), C.c_longlong(0)
+        self.lib.pdmp3_amd_bulk_clip_stats(self.h, C.byref(c), C.byref(h))
+        return c.value, h.value
+
+    def parse_range(self, mp3, index, first, count, lookback=True):
+        """parse-only decoders (host tests): pdmp3_amd_bulk_parse_range -> (first frame decoded, spectra, side) of the frames
+        [that first frame, b): the records the host stage gives for the range by itself, halo included.  lookback=False: the
+        synthesis halo alone."""
+        a = _as_u8(mp3)
+        f0 = C.c_longlong(0)
+        args = (self.h, a.ctypes.data_as(C.c_void_p), len(mp3), index.h, int(first), int(count), 1 if lookback else 0)
+        n = self.lib.pdmp3_amd_bulk_parse_range(*args, None, None, 0, C.byref(f0))     # (the first frame it would decode)
+        if n == PDMP3_BULK_REPLAY:
+            raise RingReplay("the reference replays its input ring on this stream (no finite output)")
+        _, b = index.clamp(first, count)
+        cap = max(b - f0.value, 0)
+        sp = np.zeros((max(cap, 1), 2, 2, 576), dtype=np.int16)
+        sd = np.zeros((max(cap, 1), 2, 2), dtype=SIDE_DTYPE)
+        if cap:
+            n = self.lib.pdmp3_amd_bulk_parse_range(*args, sp.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), cap,
+                                                    C.byref(f0))
+            if n != cap:
+                raise RuntimeError("pdmp3_amd_bulk_parse_range failed (%d)" % n)
+        return f0.value, sp[:cap], sd[:cap]
+
     def parse(self, mp3):
-        _, frames = scan_buffer(mp3)
+        _, frames = scan_buffer(mp3, getattr(self, "iso", 0))
         cap = frames + 1                           # frames of a failed last read are parsed too
         sp = np.zeros((cap, 2, 2, 576), dtype=np.int16)
         sd = np.zeros((cap, 2, 2), dtype=SIDE_DTYPE)

@@ -188,6 +188,8 @@ hipError_t pdmp3_launch_unpack_lsf(dim3 grid, hipStream_t s, const UnpackTables*
                                    int n_frames, int16_t* spectra, GcRaw* raw, int tab_n16, unsigned long long* prof);
 hipError_t pdmp3_launch_merge_apply_lsf(dim3 grid, hipStream_t s, const GcRaw* raw, const pdmp3_frame_bits* bits, int n_frames, const uint32_t* outc,
                                         const uint32_t* sup, const uint16_t* state_in, uint16_t* state_out, pdmp3_gc_side* side);
+// clip.hip
+hipError_t pdmp3_launch_clip_pack(hipStream_t s, const pdmp3_clip_piece* pieces, int n_pieces, const void* src);
 
 // reservoir rows from the pool (unpack_core.h row_chunk16): a wave per frame, 16 bytes per lane and trip (a 4-byte word
 // per thread was 21 us for 8192 frames, 1.2 TB/s)
@@ -715,6 +717,7 @@ struct StreamSlot {
   pdmp3_frame_bits* d_bits; uint8_t* d_res; GcRaw* d_raw; uint32_t* d_outc; unsigned* d_mcnt;
   pdmp3_row_desc* h_desc; pdmp3_row_desc* d_desc; uint8_t* d_pool;   // compact bits input: pinned descriptors; the pool is h_res
   uint8_t* h_in; uint8_t* d_in;   // the blocks h_desc | h_bits | h_res and d_desc | d_bits | d_pool point into
+  pdmp3_clip_piece* h_pieces; pdmp3_clip_piece* d_pieces; uint8_t* d_stage;   // clips (allocated on first use): the pieces' table, the stage
   int busy;
   int direct;                     // the latest record submit ran on the pinned host buffers themselves (submit_records)
 };
@@ -745,6 +748,7 @@ extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
     (void)hipFree(t.d_spectra); (void)hipFree(t.d_side); (void)hipFree(t.d_pcm); (void)hipFree(t.d_pair_sp); (void)hipFree(t.d_pair_sd);
     (void)hipHostFree(t.h_in);
     (void)hipFree(t.d_in); (void)hipFree(t.d_res); (void)hipFree(t.d_raw); (void)hipFree(t.d_outc); (void)hipFree(t.d_mcnt);
+    (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
   }
   (void)hipFree(hs->d_sfstate);
   if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
@@ -1096,7 +1100,8 @@ extern "C" pdmp3_row_desc* pdmp3_hip_stream_slot_rowdesc(pdmp3_hip_stream* hs, i
 extern "C" uint8_t* pdmp3_hip_stream_slot_pool(pdmp3_hip_stream* hs, int slot) { return pdmp3_hip_stream_slot_reservoir(hs, slot); }
 extern "C" size_t pdmp3_hip_stream_pool_bytes(const pdmp3_hip_stream* hs) { return hs ? (size_t)hs->max_frames * PDMP3_RESERVOIR_BYTES + PDMP3_POOL_SLACK_BYTES : 0; }
 
-static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes = 0);
+static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes = 0, int clip_pieces = -1,
+                       size_t stage_bytes = 0);
 // row_bytes of a _to destination: 4608 / 2304 for MPEG-1 windows, 2304 (stereo) / 1152 (mono) for LSF ones
 static bool bits_row_ok(const pdmp3_hip_stream* hs, int row_bytes) {
   if (hs && hs->lsf) return row_bytes == PDMP3_FRAME_PCM_BYTES / 2 || row_bytes == PDMP3_FRAME_PCM_BYTES / 4;
@@ -1117,7 +1122,33 @@ extern "C" int pdmp3_hip_stream_submit_bits_to(pdmp3_hip_stream* hs, int slot, i
     return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_to: row_bytes must be 4608 or 2304 (LSF: 2304 or 1152)", hipSuccess);
   return submit_bits(hs, slot, n_frames, pinned_dst, row_bytes);
 }
-static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes) {
+static int ensure_clip(pdmp3_hip_stream* hs, StreamSlot& t) {
+  if (t.d_stage) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  const size_t n = (size_t)hs->max_frames;
+  HIP_TRY(hipHostMalloc((void**)&t.h_pieces, n * sizeof(pdmp3_clip_piece), hipHostMallocDefault), "hipHostMalloc clip pieces");
+  HIP_TRY(hipMalloc((void**)&t.d_pieces, n * sizeof(pdmp3_clip_piece)), "hipMalloc clip pieces");
+  HIP_TRY(hipMalloc((void**)&t.d_stage, n * PDMP3_FRAME_PCM_BYTES), "hipMalloc clip stage");
+  return PDMP3_HIP_OK;
+}
+extern "C" void* pdmp3_hip_stream_slot_clip_stage(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot) || ensure_clip(hs, hs->s[slot]) != PDMP3_HIP_OK) return nullptr;
+  return hs->s[slot].d_stage;
+}
+extern "C" int pdmp3_hip_stream_submit_bits_clips(pdmp3_hip_stream* hs, int slot, int n_frames, const pdmp3_clip_piece* pieces, int n_pieces,
+                                                  size_t stage_bytes) {
+  if (!SLOT_OK(hs, slot) || n_pieces < 0 || n_pieces > hs->max_frames || (n_pieces && !pieces) ||
+      stage_bytes > (size_t)hs->max_frames * PDMP3_FRAME_PCM_BYTES || hs->f32)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: slot still in flight (wait for it first)", hipSuccess);
+  const int rc = ensure_clip(hs, t);
+  if (rc != PDMP3_HIP_OK) return rc;
+  if (n_pieces) memcpy(t.h_pieces, pieces, (size_t)n_pieces * sizeof *pieces);
+  return submit_bits(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES, 0, n_pieces, stage_bytes);
+}
+static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes, int clip_pieces,
+                       size_t stage_bytes) {
   if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames)
     return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits: bad argument", hipSuccess);
   StreamSlot& t = hs->s[slot];
@@ -1202,7 +1233,13 @@ static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_
   { float* x = hs->d_state; hs->d_state = hs->d_state_tmp; hs->d_state_tmp = x; }   // (the new state is where the kernel left it)
   HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
   hs->have_state_ev = 1;
-  if (pcm_out == t.d_pcm) {
+  if (clip_pieces >= 0) {     // clips: the PCM stays in d_pcm, k_clip_pack places the kept frames (clip.hip)
+    if (clip_pieces) {
+      HIP_TRY(hipMemcpyAsync(t.d_pieces, t.h_pieces, (size_t)clip_pieces * sizeof(pdmp3_clip_piece), hipMemcpyHostToDevice, t.stream), "H2D clip pieces");
+      HIP_TRY(pdmp3_launch_clip_pack(t.stream, t.d_pieces, clip_pieces, t.d_pcm), "launch k_clip_pack");
+    }
+    if (stage_bytes) HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_stage, stage_bytes, hipMemcpyDeviceToHost, t.stream), "D2H clip stage");
+  } else if (pcm_out == t.d_pcm) {
     rc = download_pcm(t, n, host_dst, row, lsf);
     if (rc != PDMP3_HIP_OK) return rc;
   }

@@ -98,12 +98,8 @@ struct pdmp3_node {
 
 extern "C" int pdmp3_node_ranks(const pdmp3_node* node) { return node ? node->n : 0; }
 
-// == pdmp3_amd/sharding.py frame_range / halo_start / shard_with_halo
-extern "C" void pdmp3_node_shard(long long n_frames, int rank, int world, const uint8_t* flags,
-                                 long long* first_out, long long* count_out, long long* discard_out) {
-  const long long base = n_frames / world, rem = n_frames % world;
-  const long long lo = rank * base + (rank < rem ? rank : rem);
-  const long long hi = lo + base + (rank < rem ? 1 : 0);
+// == pdmp3_amd/sharding.py halo_start
+extern "C" long long pdmp3_node_halo_start(long long lo, const uint8_t* flags) {
   long long first = lo - 2 > 0 ? lo - 2 : 0;                          // the fixed halo: two frames
   if (flags && lo > 0) {
     auto mono = [&](long long f) { return ((flags[f] & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 3; };
@@ -120,6 +116,16 @@ extern "C" void pdmp3_node_shard(long long n_frames, int rank, int world, const 
       }
     }
   }
+  return first;
+}
+
+// == pdmp3_amd/sharding.py frame_range / shard_with_halo
+extern "C" void pdmp3_node_shard(long long n_frames, int rank, int world, const uint8_t* flags,
+                                 long long* first_out, long long* count_out, long long* discard_out) {
+  const long long base = n_frames / world, rem = n_frames % world;
+  const long long lo = rank * base + (rank < rem ? rank : rem);
+  const long long hi = lo + base + (rank < rem ? 1 : 0);
+  const long long first = pdmp3_node_halo_start(lo, flags);
   if (first_out) *first_out = first;
   if (count_out) *count_out = hi - first;
   if (discard_out) *discard_out = lo - first;

@@ -76,7 +76,7 @@ def load_library():
     return lib
 
 
-NODE_EXPORTS = ["pdmp3_node_create", "pdmp3_node_destroy", "pdmp3_node_ranks", "pdmp3_node_shard",
+NODE_EXPORTS = ["pdmp3_node_create", "pdmp3_node_destroy", "pdmp3_node_ranks", "pdmp3_node_shard", "pdmp3_node_halo_start",
                 "pdmp3_node_decode_records", "pdmp3_node_decode_generated"]
 NODE_RCCL, NODE_COPY = 0, 1
 

@@ -712,12 +712,17 @@ static int bits_push(struct bulk* b) {
 static int bulk_push(struct bulk* b) {
   pdmp3_handle* id = b->id;
   b->frames++;
-  if (b->count_only) { id->need_reset = 0; return PDMP3_OK; }
+  if (b->count_only) { if (b->ix_note) b->ix_note(b); id->need_reset = 0; return PDMP3_OK; }
   if (b->bits_mode) return bits_push(b);
   bulk_window* w = &b->win[b->cur];
   /* the engine takes LSF frames in launches of their own, all of one channel count: such a frame opens a new window */
   if (w->n && (id->hdr.ver != w->jobs[0].hdr.ver || (id->hdr.ver && (id->hdr.mode == 3) != (w->jobs[0].hdr.mode == 3)))) {
-    if (bulk_rotate(b) != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }
+    /* (the window ends in front of this frame, which `frames` already counts: parse-only decoders place a window's records
+     *  at frames - n) */
+    b->frames--;
+    const int rc = bulk_rotate(b);
+    b->frames++;
+    if (rc != PDMP3_OK) { b->failed = 1; return PDMP3_ERR; }
     w = &b->win[b->cur];
   }
   frame_job* j = &w->jobs[w->n++];

@@ -177,7 +177,7 @@ void pdmp3_amd_bulk_split_scans(const struct bulk* b, long long* taken, long lon
 /* the ISO-correct switches (include/pdmp3.h: pdmp3_amd_set_quirks) for the streams this decoder is given from now on */
 int pdmp3_amd_bulk_set_quirks(struct bulk* b, unsigned iso_mask) { return b ? pdmp3_amd_set_quirks(b->id, iso_mask) : PDMP3_ERR; }
 
-static void bulk_begin(struct bulk* b) {
+void bulk_begin(struct bulk* b) {
   pdmp3_handle* id = b->id;
   /* a fresh handle per stream -- unless the caller is pdmp3(), which decodes all its files with ONE handle: parse
    * state left by the previous file shows in the next one, so it is kept (b->carry) */

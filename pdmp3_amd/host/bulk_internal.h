@@ -164,6 +164,10 @@ struct bulk {
   int slot_arena_n[BULK_SLOTS];
   double t_submit, t_gpuwait, t_poolwait;   /* PDMP3_BULK_TRACE=1: where the scanning thread waits */
   double t_sub_gather, t_sub_call, t_drive, t_subwait, t_tail;          /* ... and what the submitter thread spends on the main-data copies / the engine calls */
+  /* clips (clip.c) */
+  void (*ix_note)(struct bulk* b);    /* count-only scan: called for every frame (a stream index being built) */
+  struct pdmp3_amd_index* ix;
+  long long clip_frames, clip_halo;   /* pdmp3_amd_bulk_clip_stats */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -307,6 +311,10 @@ HOST_LOCAL int pw_close_window(struct bulk* b);
 HOST_LOCAL void pc_free(par_cache* pc);
 HOST_LOCAL long long par_drive(struct bulk* b, const unsigned char* mp3, size_t n, int K);
 HOST_LOCAL void header_fields(uint32_t h, frame_header* H);
+HOST_LOCAL int par_prepass(struct par_scan* P);
+HOST_LOCAL void span_init(const unsigned char* mp3, const hop_rec* rec, const span_snap* S, pdmp3_handle* id);
+/* bulk_api.c */
+HOST_LOCAL void bulk_begin(struct bulk* b);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

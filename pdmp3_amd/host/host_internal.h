@@ -15,6 +15,7 @@
  *   bulk.c          whole-stream decoder: stages A-D on one scanning thread, worker pool, submitter, main-data copies
  *   split_scan.c    whole-stream decoder: the scan split over threads (pre-pass, hop threads, scanners, stitcher)
  *   bulk_api.c      whole-stream decoder: pdmp3_amd_bulk_* entry points (new / delete / decode / wait / parse hooks)
+ *   clip.c          stream indices, the halo rule of a frame range, clips (pdmp3_amd_index_*, pdmp3_amd_bulk_decode_clips)
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

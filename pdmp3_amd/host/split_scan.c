@@ -251,7 +251,7 @@ static void* par_hop_thread(void* arg) {
 }
 
 /* The pre-pass.  Returns 0 when the whole stream is regular (P->n_frames frames), -1 otherwise. */
-static int par_prepass(struct par_scan* P) {
+int par_prepass(struct par_scan* P) {
   const unsigned char* mp3 = P->mp3;
   const size_t n = P->n;
   pdmp3_handle* h = (pdmp3_handle*)calloc(1, sizeof *h);
@@ -360,26 +360,27 @@ static void* par_prepass_thread(void* arg) {
 }
 
 /* `len` bytes of the stream's main data, from position `off` of their concatenation, whose last byte belongs to frame `g` or an earlier one */
-static void md_read(const struct par_scan* P, long long g, uint64_t off, unsigned len, uint8_t* out) {
-  while (g > 0 && P->rec[g - 1].md_end > off) g--;      /* the frame that holds byte `off` */
+static void md_read(const unsigned char* mp3, const hop_rec* rec, long long g, uint64_t off, unsigned len, uint8_t* out) {
+  while (g > 0 && rec[g - 1].md_end > off) g--;         /* the frame that holds byte `off` */
   while (len) {
-    const hop_rec* r = &P->rec[g];
+    const hop_rec* r = &rec[g];
     const uint64_t start = r->md_end - (uint64_t)(r->top - r->begin);
     const unsigned in = (unsigned)(off - start), have = (unsigned)(r->md_end - off);
     const unsigned k = have < len ? have : len;
-    memcpy(out, P->mp3 + r->md_src + in, k);
+    memcpy(out, mp3 + r->md_src + in, k);
     out += k; off += k; len -= k; g++;
   }
 }
 
-/* a scanner's handle as the sequential scanner's would be in front of frame S->frame */
-static void span_init(const struct par_scan* P, const span_snap* S, pdmp3_handle* id) {
-  id->vsrc = P->mp3; id->vfed = S->vfed;
+/* a scanner's handle as the sequential scanner's would be in front of frame S->frame (rec: the pre-pass's records of the
+ * stream `mp3`; also the clips' scans from a stream index, clip.c) */
+void span_init(const unsigned char* mp3, const hop_rec* rec, const span_snap* S, pdmp3_handle* id) {
+  id->vsrc = mp3; id->vfed = S->vfed;
   id->istart = S->istart; id->iend = S->iend; id->processed = S->processed;
   id->l_istart = S->istart; id->l_processed = S->processed;
   id->new_header = 1; id->l_new_header = 1; id->need_reset = 0; id->ostart = 0;
-  const hop_rec* last = &P->rec[S->frame - 1];
-  header_fields(be32(P->mp3 + last->x), &id->hdr);
+  const hop_rec* last = &rec[S->frame - 1];
+  header_fields(be32(mp3 + last->x), &id->hdr);
   id->l_hdr = id->hdr;
   id->last_nch = last->nch;
   /* the reservoir buffer: [0, top) of the newest frame, above it what older frames with larger tops left (sky), zero
@@ -389,9 +390,9 @@ static void span_init(const struct par_scan* P, const span_snap* S, pdmp3_handle
   unsigned covered = 0;
   for (int i = S->sky_n - 1; i >= 0; i--) {
     const long long g = S->sky[i];
-    const hop_rec* r = &P->rec[g];
+    const hop_rec* r = &rec[g];
     if (r->top <= covered) continue;
-    md_read(P, g, r->md_end - r->top + covered, r->top - covered, id->main_vec + covered);
+    md_read(mp3, rec, g, r->md_end - r->top + covered, r->top - covered, id->main_vec + covered);
     covered = r->top;
   }
   /* side-info fields that a frame only sets on one side of win_switch_flag and otherwise leaves as they were (H20) */
@@ -400,8 +401,8 @@ static void span_init(const struct par_scan* P, const span_snap* S, pdmp3_handle
     for (int which = 0; which < 2; which++) {
       const long long f = which ? S->last_ws1[g] : S->last_ws0[g];
       if (f < 0) continue;
-      const hop_rec* r = &P->rec[f];
-      const uint8_t* v = P->mp3 + r->x + 4 + r->crc;
+      const hop_rec* r = &rec[f];
+      const uint8_t* v = mp3 + r->x + 4 + r->crc;
       const unsigned pos = (r->nch == 1 ? 18u : 20u) + 59u * (gr * r->nch + ch);
       uint8_t tmp[48];
       memcpy(tmp, v, 40); memset(tmp + 40, 0, 8);       /* (side_word reads 8 bytes at a time) */
@@ -472,7 +473,7 @@ static void* par_scanner(void* arg) {
     if (w == 0) { pdmp3_open_feed(id); id->vsrc = P->mp3; id->vfed = 0; }
     else {
       const span_snap* S = &P->snap[w];
-      span_init(P, S, id);
+      span_init(P->mp3, P->rec, S, id);
       fed = S->fed;
       wb->frames = S->frame;
     }

@@ -9,6 +9,12 @@ stream (44.1 kHz joint stereo 320 kbps).  Host stages alone
 every decoder), e.g. an hour at 22.05 kHz:
 
   python tools/bulk_bench.py --lsf 1 --sfreq 0 --frames 137812 --threads 4 --device-out [--host-huffman]
+
+--clips K --clip-frames F: K clips of F frames at random places (fixed seed) in the C4 corpus -- or, with --c3, in the C3 hour --
+into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files whole and slicing (see clips()):
+
+  python tools/bulk_bench.py --clips 64 --clip-frames 191
+  python tools/bulk_bench.py --clips 1 --clip-frames 191 --c3
 """
 import argparse
 import json
@@ -82,6 +88,100 @@ def c4(args, api):
                       "host_cpus": os.cpu_count()}))
 
 
+def clips(args, api):
+    """K clips of F frames at random places (fixed seed) in the C4 corpus (python -m pdmp3_amd.packer c4) -- or, with --c3,
+    in the C3 file (python -m pdmp3_amd.packer c3) -- into one [K, stride] int16 tensor in device memory, two ways, run
+    after run in turn: pdmp3_amd_bulk_decode_clips (indices built beforehand, their build timed on its own), and what there
+    was without it -- every file a clip falls in decoded whole with decode_into_device (asynchronously, back to back) and the
+    clips sliced out of it on the device.  The two results are compared once, bit for bit.  Medians of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    t0 = time.perf_counter()
+    if args.c3:
+        specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)]
+    else:
+        specs = c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    t_gen = time.perf_counter() - t0
+    t_ix, ixs = [], []
+    for f in files:
+        t0 = time.perf_counter()
+        ixs.append(api.StreamIndex(f))
+        t_ix.append(time.perf_counter() - t0)
+    rng = random.Random(args.seed)
+    K, F = args.clips, args.clip_frames
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    spans = [(int(ixs[i].pcm_offsets[a]) // 2, int(ixs[i].pcm_offsets[min(a + F, ixs[i].frames)]) // 2) for i, a in sel]
+    stride = max(hi - lo for lo, hi in spans)
+    dev = "cuda:0"
+    out_c = torch.zeros((K, stride), dtype=torch.int16, device=dev)
+    out_w = torch.zeros((K, stride), dtype=torch.int16, device=dev)
+    need = sorted(set(i for i, _ in sel))
+    whole = {i: torch.empty(max(int(ixs[i].pcm_offsets[-1]), 2) // 2, dtype=torch.int16, device=dev) for i in need}
+    dec_c = api.BulkDecoder(threads=args.clip_threads)
+    dec_w = api.BulkDecoder(threads=args.clip_threads)
+    batch = [(files[i], ixs[i], a, F) for i, a in sel]
+    torch.cuda.synchronize()
+
+    def clip_route():
+        dec_c.decode_clips(batch, out_c)
+
+    def whole_route():
+        for i in need:
+            dec_w.decode_into_device(files[i], whole[i], wait=False)
+        dec_w.wait()
+        for k, (i, _) in enumerate(sel):
+            lo, hi = spans[k]
+            out_w[k, :hi - lo].copy_(whole[i][lo:hi])
+        torch.cuda.synchronize()
+
+    times = {"clips": [], "whole files": []}
+    halo = None
+    for r in range(args.warmup_runs + args.runs):
+        order = [("clips", clip_route), ("whole files", whole_route)]
+        if r % 2:
+            order.reverse()
+        for name, fn in order:
+            h0 = dec_c.clip_stats()[1]
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if name == "clips" and halo is None:
+                halo = (dec_c.clip_stats()[1] - h0) / K
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            assert torch.equal(out_c, out_w), "clips differ from the whole-file decodes sliced"
+    dec_c.close()
+    dec_w.close()
+    kept = sum(min(a + F, ixs[i].frames) - a for i, a in sel)
+    mb = [len(f) / 1e6 for f in files]
+    res = {"workload": "%d clips of %d frames: %s" % (K, F, "C3 file (137813 frames, 320 kbps joint stereo)" if args.c3 else
+                                                       "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "destination": "device memory ([K, stride] int16 tensor)", "runs": args.runs, "kept_frames": kept,
+           "files_decoded_whole": len(need), "whole_file_frames": int(sum(ixs[i].frames for i in need)),
+           "halo_frames_per_clip": round(halo, 2), "packer_s": round(t_gen, 2),
+           "index_build_ms_per_file": {"median": round(statistics.median(t_ix) * 1e3, 3), "min": round(min(t_ix) * 1e3, 3),
+                                       "max": round(max(t_ix) * 1e3, 3)},
+           "index_build_ms_per_mb": round(sum(t_ix) * 1e3 / sum(mb), 3), "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1), "min": round(K / max(ts), 1), "max": round(K / min(ts), 1)},
+                     "kept_frames_per_s": {"median": round(kept / statistics.median(ts), 1), "min": round(kept / max(ts), 1),
+                                           "max": round(kept / min(ts), 1)}}
+    w = times["whole files"]
+    res["clip_route_wins_by_more_than_the_whole_route_spread"] = bool(statistics.median(w) - statistics.median(times["clips"]) > max(w) - min(w))
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20000)
@@ -98,7 +198,19 @@ def main():
     ap.add_argument("--lsf", type=int, default=0, choices=(0, 1, 2), metavar="VERSION",
                     help="an MPEG-2 LSF (1) or MPEG-2.5 (2) stream at --sfreq, joint stereo 64 kbps, decoded with PDMP3_ISO_LSF")
     ap.add_argument("--sfreq", type=int, default=0, choices=(0, 1, 2), help="--lsf: the header's sampling-frequency field")
+    ap.add_argument("--clips", type=int, default=0, metavar="K",
+                    help="K clips (pdmp3_amd_bulk_decode_clips) at random places in the C4 corpus into device memory, against "
+                         "decoding the whole files and slicing (see clips())")
+    ap.add_argument("--clip-frames", type=int, default=191, metavar="F", help="--clips: frames per clip (191: 5 s at 44.1 kHz)")
+    ap.add_argument("--c3", action="store_true", help="--clips: out of the C3 file (one hour) instead of the C4 corpus")
+    ap.add_argument("--runs", type=int, default=12, help="--clips: timed runs of each route (medians, min, max)")
+    ap.add_argument("--warmup-runs", type=int, default=2)
+    ap.add_argument("--clip-threads", type=int, default=0, help="--clips: the decoders' copy threads (0: the library's choice)")
+    ap.add_argument("--seed", type=int, default=20261016)
     args = ap.parse_args()
+    if args.clips:
+        from pdmp3_amd import api
+        return clips(args, api)
     if args.lsf and (args.parse_only or args.c4):
         ap.error("--lsf: whole-stream decodes of one stream only")
     from pdmp3_amd.packer import packer
