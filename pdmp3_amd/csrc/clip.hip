@@ -1,5 +1,5 @@
 // clip.hip -- k_clip_pack: the PCM of a window of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips) from the slot's
-// frame-major buffer to where each kept frame belongs.  Launched by engine.hip submit_bits for
+// frame-major buffer to where each kept frame belongs.  Launched by stream.hip submit_bits for
 // pdmp3_hip_stream_submit_bits_clips.  A translation unit of its own, so that the decode, unpack and merge kernels' code is
 // what it is without it (as engine_lsf.hip).
 #include <hip/hip_runtime.h>

@@ -1,4 +1,7 @@
-// engine.hip -- gfx950 kernels + the C-ABI of include/pdmp3_hip.h.
+// engine.hip -- the gfx950 kernels, and the part of the C-ABI of include/pdmp3_hip.h that launches them: the engine
+// context, launch_decode (which kernel, which grid) behind the bare decode entry points, the device Huffman stage's
+// launches (unpack_window_head / _carry), generate, the debug entries.  The pdmp3_hip_stream object is stream.hip;
+// what the two share is engine_internal.h.
 //
 // Launch geometry: one 64-lane workgroup (= one wavefront) per chunk of
 // `chunk_frames` frames; a launch of N frames makes ceil(N/chunk) workgroups,
@@ -15,11 +18,10 @@
 #include <string.h>
 
 #include "decode_core.h"
+#include "engine_internal.h"
 #include "gen_core.h"
 #include "host_tables.h"
 #include "unpack_core.h"
-#include <atomic>
-#include <mutex>
 #include <new>
 
 using namespace pdmp3;
@@ -183,13 +185,6 @@ __global__ __launch_bounds__(64) void k_generate(uint64_t seed, int64_t first, i
 // main-data decoding on the device: unpack_kernels.h (the LSF instantiations: engine_lsf.hip)
 // ---------------------------------------------------------------------------
 #include "unpack_kernels.h"
-// engine_lsf.hip
-hipError_t pdmp3_launch_unpack_lsf(dim3 grid, hipStream_t s, const UnpackTables* tabs, const pdmp3_frame_bits* bits, const uint8_t* res,
-                                   int n_frames, int16_t* spectra, GcRaw* raw, int tab_n16, unsigned long long* prof);
-hipError_t pdmp3_launch_merge_apply_lsf(dim3 grid, hipStream_t s, const GcRaw* raw, const pdmp3_frame_bits* bits, int n_frames, const uint32_t* outc,
-                                        const uint32_t* sup, const uint16_t* state_in, uint16_t* state_out, pdmp3_gc_side* side);
-// clip.hip
-hipError_t pdmp3_launch_clip_pack(hipStream_t s, const pdmp3_clip_piece* pieces, int n_pieces, const void* src);
 
 // reservoir rows from the pool (unpack_core.h row_chunk16): a wave per frame, 16 bytes per lane and trip (a 4-byte word
 // per thread was 21 us for 8192 frames, 1.2 TB/s)
@@ -247,69 +242,16 @@ __global__ __launch_bounds__(kMergeLanes) void k_merge_outcome(const GcRaw* raw,
 }
 
 
-// Scratch of a chained launch (DecodeArgs::chain_*): launches that are ordered one after the other share a buffer --
-// those of one pdmp3_hip_stream (its slots' kernels are chained by the state event), or those of bare calls on one HIP
-// stream; launches that may overlap never do.
-struct ChainBuf {
-  const void* key;          // whose launches share it: a pdmp3_hip_stream's state scratch, or the HIP stream of bare calls
-  bool used;
-  int cap;                  // frames
-  unsigned epoch;           // of the last launch that used it; flags of older launches are smaller, never equal
-  float* state;             // cap x 2 kGranFloats floats
-  unsigned* flag;           // cap x 4 flags
-  unsigned long long last_use;   // launch counter value of its latest use (the least recently used one is evicted)
-  // bare calls on this HIP stream (no stream object, which has its own): where the kernel leaves the closing state before it
-  // is copied over the caller's, and an LSF launch's regrouped records.  Stream-ordered like the rest: a call's launches are
-  // through with them before the next call's on the same stream start.
-  float* state_tmp;
-  int16_t* pair_sp; pdmp3_gc_side* pair_sd; int pair_cap;   // record-frames
-};
-// what a launch gets of it (a copy made under the lock: another thread's launch may replace the buffers right after)
+// what a launch gets of a ChainBuf (engine_internal.h; a copy made under the lock: another thread's launch may replace the
+// buffers right after)
 struct ChainUse { float* state; unsigned* flag; unsigned epoch; };
-constexpr int kChainBufs = 32;
-
-constexpr int kRareSlots = 4096;      // a flag word per launch, taken round robin: two launches share one only if 4096 others lie between them
-struct pdmp3_hip_ctx {
-  int device;
-  int wave_slots;           // waves of k_decode the device holds at once (CUs x 4 SIMDs x 2)
-  UnpackTables* d_unpack;
-  int unpack_n16;                // its used part, in 16-byte units
-  unsigned long long* d_uprof;   // development only: PDMP3_HIP_UNPACK_PROF=1
-  float* d_pow43;
-  uint16_t* d_linetab;
-  float* d_win;
-  float* d_frag;            // frag_long [10][64] | frag_short [10][64] | frag_mat [8][64] | taps [16][64]
-  void* d_tab_image;        // [kNumSfreq] TabLds images
-  unsigned* d_rare_flags;   // [kRareSlots] epoch numbers (DecodeArgs::rare_flag): "this launch of chunks holds a chunk for k_decode_rare"
-  std::atomic<unsigned> rare_epoch;
-  int chain_mode;           // PDMP3_HIP_CHAIN=0: independent chunks with halos everywhere; otherwise launches up to
-                            // gran_max_frames take the granule kernel (k_decode_g)
-  int gran_max_frames;      // launches up to this many frames take the granule kernel (PDMP3_HIP_GRAN_MAX)
-  int ring_min_frames;      // launches from this many frames on take the persistent granule kernel (PDMP3_HIP_RING_MIN; 0: never)
-  int cus;
-  int wave_slots_gran;      // waves of k_decode_g the device holds at once (CUs x 4 SIMDs x 4)
-  unsigned debug_flags;     // PDMP3_HIP_DEBUG_FAR_TIMEOUT=1: every wait for another workgroup gives up at once (tests)
-  std::atomic<int> last_kind;   // PDMP3_HIP_LAUNCH_* of the latest decode launch, any thread (reports only)
-  int direct_max_frames;    // record batches of a stream up to this size run on the pinned host buffers directly (PDMP3_HIP_DIRECT_MAX)
-  int gran_w8;              // development: PDMP3_HIP_GRAN_W=8 -- every launch of the granule kernel in workgroups of 8 waves
-  int sf_hint;              // sampling-frequency index the granule kernel's line tables are loaded for (PDMP3_HIP_SF_HINT; 0 = 44.1 kHz)
-  std::mutex chain_mu;
-  unsigned long long chain_clock;
-  ChainBuf chain[kChainBufs];
-};
 
 static thread_local char g_err[256] = "";
 
-static int fail(int code, const char* what, hipError_t e) {
+int fail(int code, const char* what, hipError_t e) {
   snprintf(g_err, sizeof g_err, "%s: %s", what, e == hipSuccess ? "" : hipGetErrorString(e));
   return code;
 }
-
-#define HIP_TRY(call, what)                                   \
-  do {                                                        \
-    hipError_t e_ = (call);                                   \
-    if (e_ != hipSuccess) return fail(PDMP3_HIP_EDEVICE, what, e_); \
-  } while (0)
 
 extern "C" const char* pdmp3_hip_last_error(void) { return g_err; }
 // (for the library's other translation unit, node.hip: the calling thread's error text)
@@ -324,6 +266,11 @@ extern "C" int pdmp3_hip_pci_bus_id(const pdmp3_hip_ctx* c, char* buf, int len) 
 
 extern "C" int pdmp3_hip_last_launch_kind(const pdmp3_hip_ctx* c) { return c ? c->last_kind.load(std::memory_order_relaxed) : PDMP3_HIP_LAUNCH_NONE; }
 
+static void chain_free(ChainBuf* b) {                      // (hipFree waits for whatever still uses the memory)
+  (void)hipFree(b->state); (void)hipFree(b->flag); (void)hipFree(b->state_tmp); (void)hipFree(b->pair_sp); (void)hipFree(b->pair_sd);
+  *b = ChainBuf{};
+}
+
 extern "C" void pdmp3_hip_destroy(pdmp3_hip_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
@@ -335,7 +282,7 @@ extern "C" void pdmp3_hip_destroy(pdmp3_hip_ctx* c) {
   (void)hipFree(c->d_rare_flags);
   (void)hipFree(c->d_unpack);
   (void)hipFree(c->d_uprof);
-  for (ChainBuf& b : c->chain) { (void)hipFree(b.state); (void)hipFree(b.flag); }
+  for (ChainBuf& b : c->chain) chain_free(&b);
   delete c;
 }
 
@@ -435,10 +382,6 @@ static int auto_chunk(int n_frames, int slots) {
 // streaming API decoding single channels of single frames from zero spectra, in 3-30 % of fresh processes depending on the box
 // (tests/fuzz_gpu.py -> tests/test_gpu_lsf.py's CLI test).  Everything is hipMalloc'ed once now and kept: a free or a regrow
 // synchronises, which happens when a stream's launches grow, not per launch.
-static void chain_free(ChainBuf* b) {                      // (hipFree waits for whatever still uses the memory)
-  (void)hipFree(b->state); (void)hipFree(b->flag); (void)hipFree(b->state_tmp); (void)hipFree(b->pair_sp); (void)hipFree(b->pair_sd);
-  *b = ChainBuf{};
-}
 static ChainBuf* chain_entry(pdmp3_hip_ctx* c, const void* key) {   // (c->chain_mu held)
   ChainBuf* b = nullptr;
   for (ChainBuf& x : c->chain) if (x.used && x.key == key) { b = &x; break; }
@@ -512,72 +455,119 @@ static bool chain_get(pdmp3_hip_ctx* c, const void* key, hipStream_t s, int n_fr
   return true;
 }
 
-static void chain_release(pdmp3_hip_ctx* c, const void* key) {     // (its launches are complete)
+void chain_release(pdmp3_hip_ctx* c, const void* key) {     // (its launches are complete)
   std::lock_guard<std::mutex> lock(c->chain_mu);
   for (ChainBuf& x : c->chain)
     if (x.used && x.key == key) chain_free(&x);
 }
 
-// d_state_tmp: where the kernel leaves the new state before it is copied over d_state (chunk 0 and the channel-1
+// What launch_decode chose; the functions below only launch it.
+struct DecodePlan {
+  int kind;            // PDMP3_HIP_LAUNCH_*: the kernel family (the granule kernel's: its waves per workgroup, 8 or 16)
+  int n_wgs;
+  int frames_per_wg;   // the persistent kernel's range
+};
+
+// the hipLaunchKernelGGL ladders over F32 (x W), one per kernel family
+#if defined(PDMP3_WITH_RING_KERNEL)
+static void launch_ring(const DecodeArgs& a, const GlobalTables& T, const DecodePlan& p, bool f32, hipStream_t s) {
+  if (f32) hipLaunchKernelGGL((k_decode_p<true>), dim3(p.n_wgs), dim3(64 * 16), 0, s, a, T, p.frames_per_wg);
+  else hipLaunchKernelGGL((k_decode_p<false>), dim3(p.n_wgs), dim3(64 * 16), 0, s, a, T, p.frames_per_wg);
+}
+#endif
+static void launch_granules(const DecodeArgs& a, const GlobalTables& T, const DecodePlan& p, bool f32, hipStream_t s) {
+  const int W = p.kind;
+  if (W == 8) {
+    if (f32) hipLaunchKernelGGL((k_decode_g<true, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+    else hipLaunchKernelGGL((k_decode_g<false, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+  } else {
+    if (f32) hipLaunchKernelGGL((k_decode_g<true, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+    else hipLaunchKernelGGL((k_decode_g<false, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+  }
+}
+// chunks with halos: the profiling / dumping forms, every chunk to k_decode_rare (LSF), or k_decode with k_decode_rare
+// behind it for the chunks it leaves out (told through this launch's flag word)
+static void launch_chunks(pdmp3_hip_ctx* c, const DecodeArgs& a, const GlobalTables& T, const DecodePlan& p, bool f32, bool lsf, hipStream_t s) {
+  const int nchunks = p.n_wgs;
+  if (a.prof) hipLaunchKernelGGL(k_decode_prof, dim3(nchunks), dim3(64), 0, s, a, T);
+  else if (a.stages) hipLaunchKernelGGL(k_decode<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, (unsigned*)nullptr, 0u);
+  else if (lsf) {                                // every chunk of an LSF launch is k_decode_rare's
+    if (f32) hipLaunchKernelGGL(k_decode_rare<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 1, (const unsigned*)nullptr, 0u);
+    else hipLaunchKernelGGL(k_decode_rare<false>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 1, (const unsigned*)nullptr, 0u);
+  } else {
+    const unsigned ep = c->rare_epoch.fetch_add(1);
+    unsigned* flag = c->d_rare_flags + (ep % kRareSlots);
+    if (f32) {
+      hipLaunchKernelGGL((k_decode<false, true>), dim3(nchunks), dim3(64), 0, s, a, T, nchunks, flag, ep);
+      hipLaunchKernelGGL(k_decode_rare<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 0, (const unsigned*)flag, ep);
+    } else {
+      // (development: PDMP3_HIP_DEBUG_LDS_PAD = bytes of dynamic LDS added to every workgroup of the chunk kernel, which
+      //  lowers the number of waves a CU holds -- 24576: one wave per SIMD instead of two; tools/occupancy_scaling.py)
+      static const int lds_pad = [] { const char* e = getenv("PDMP3_HIP_DEBUG_LDS_PAD"); return e ? atoi(e) : 0; }();
+      hipLaunchKernelGGL(k_decode<false>, dim3(nchunks), dim3(64), (size_t)lds_pad, s, a, T, nchunks, flag, ep);
+      hipLaunchKernelGGL(k_decode_rare<false>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 0, (const unsigned*)flag, ep);
+    }
+  }
+}
+
+// One decode launch (engine_internal.h DecodeLaunch).
+// state_tmp: where the kernel leaves the new state before it is copied over the state (chunk 0 and the channel-1
 // pre-halo read the OLD state while the last chunk writes the new one).  Streams own one; a bare
 // pdmp3_hip_decode_frames call takes the one kept for its HIP stream (bare_state_tmp), so that calls on different HIP streams never share it.
-static int launch_decode(pdmp3_hip_ctx* c, const int16_t* d_spectra, const pdmp3_gc_side* d_side, int n_frames,
-                         void* d_state, int16_t* d_pcm, float* d_stages, int chunk_frames, void* stream,
-                         unsigned long long* d_prof = nullptr, float* d_state_tmp = nullptr, float* d_pcm_f32 = nullptr,
-                         const void* owner = nullptr, bool leave_state_in_tmp = false, bool lsf = false,
-                         int16_t* pair_sp = nullptr, pdmp3_gc_side* pair_sd = nullptr) {
-  // owner: the stream object whose launches these are (they are ordered: one chain scratch for all of them);
-  // leave_state_in_tmp: the caller swaps its two state buffers instead of having the new state copied back
-  if (!c || n_frames < 0) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames: bad argument", hipSuccess);
-  if (n_frames == 0) return PDMP3_HIP_OK;
-  if (!d_spectra || !d_side || !(d_pcm || d_pcm_f32))
+int launch_decode(pdmp3_hip_ctx* c, const DecodeLaunch& q) {
+  if (!c || q.n_frames < 0) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames: bad argument", hipSuccess);
+  if (q.n_frames == 0) return PDMP3_HIP_OK;
+  if (!q.spectra || !q.side || !q.pcm)
     return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames: NULL buffer", hipSuccess);
-  if (((uintptr_t)d_spectra | (uintptr_t)d_side | (uintptr_t)d_pcm | (uintptr_t)d_pcm_f32) & 15)
+  if (((uintptr_t)q.spectra | (uintptr_t)q.side | (uintptr_t)q.pcm) & 15)
     return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames: buffers must be 16-byte aligned", hipSuccess);
-  if (n_frames == 0) return PDMP3_HIP_OK;
-  hipStream_t s = (hipStream_t)stream;
+  hipStream_t s = q.stream;
   HIP_TRY(hipSetDevice(c->device), "hipSetDevice");     // (a bare call may come from a thread whose current device is another one)
+  const void* chain_key = q.owner ? q.owner : (const void*)s;   // (a stream object, or the bare call's HIP stream)
   // LSF (pdmp3_gc_side.lsf != 0): a frame is ONE granule.  The kernels keep their two-granule frames: the
   // launch's n frames are regrouped on the device into ceil(n / 2) record-frames whose granules are consecutive FRAMES
   // (k_lsf_pair: [0][ch] of frame 2 p and of frame 2 p + 1), decoded by the chunk kernel -- an odd last frame is a
   // record-frame of one granule (DecodeArgs::n_gran) -- and the PCM comes out in stream order, 576 sample-frames a frame.
-  int16_t* d_pair_sp = nullptr;
-  pdmp3_gc_side* d_pair_sd = nullptr;
-  int n_gran = 0;
-  if (lsf) {
-    if (d_stages || d_prof) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_lsf_frames: no stage dumps / profiles of LSF launches", hipSuccess);
+  const int16_t* d_spectra = q.spectra;
+  const pdmp3_gc_side* d_side = q.side;
+  int n_frames = q.n_frames, chunk_frames = q.chunk_frames, n_gran = 0;
+  if (q.lsf) {
+    if (q.stages || q.prof) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_lsf_frames: no stage dumps / profiles of LSF launches", hipSuccess);
     const int np = (n_frames + 1) / 2;
     // (a stream object brings its own buffers for the pairs, kept from batch to batch: pair_sp / pair_sd; a bare call's are the
-    //  stream-ordered allocator's)
-    if (pair_sp) { d_pair_sp = pair_sp; d_pair_sd = pair_sd; }
-    else if (!bare_pairs(c, owner ? owner : (const void*)s, np, &d_pair_sp, &d_pair_sd)) return fail(PDMP3_HIP_ENOMEM, "hipMalloc LSF pairs", hipSuccess);
+    //  ones kept for its HIP stream)
+    int16_t* d_pair_sp = q.pair_sp;
+    pdmp3_gc_side* d_pair_sd = q.pair_sd;
+    if (!d_pair_sp && !bare_pairs(c, chain_key, np, &d_pair_sp, &d_pair_sd)) return fail(PDMP3_HIP_ENOMEM, "hipMalloc LSF pairs", hipSuccess);
     hipLaunchKernelGGL(k_lsf_pair, dim3(np), dim3(256), 0, s, d_spectra, d_side, n_frames, d_pair_sp, d_pair_sd);
     n_gran = n_frames;
     d_spectra = d_pair_sp; d_side = d_pair_sd; n_frames = np;
     if (chunk_frames <= 1) chunk_frames = 0;             // (never the granule kernels: they hand on whole frames)
   }
-  const int chunk_frames_arg = lsf ? 2 : chunk_frames;   // (0 = the engine's choice; an LSF launch: chunks)
+  const int chunk_frames_arg = q.lsf ? 2 : chunk_frames;   // (0 = the engine's choice; an LSF launch: chunks)
   if (chunk_frames <= 0) chunk_frames = auto_chunk(n_frames, c->wave_slots);
-  if (d_stages || chunk_frames > n_frames) chunk_frames = n_frames;
+  if (q.stages || chunk_frames > n_frames) chunk_frames = n_frames;
+  float* d_state_tmp = q.state_tmp;
+  if (q.state && !d_state_tmp && !bare_state_tmp(c, chain_key, &d_state_tmp)) return fail(PDMP3_HIP_ENOMEM, "hipMalloc state", hipSuccess);
   DecodeArgs a;
   a.spectra = d_spectra;
   a.side = d_side;
-  a.pcm = d_pcm;
-  a.pcm_f32 = d_pcm_f32;
-  a.state_in = (const float*)d_state;
-  const void* chain_key = owner ? owner : (const void*)s;   // (a stream object, or the bare call's HIP stream)
-  if (d_state && !d_state_tmp && !bare_state_tmp(c, chain_key, &d_state_tmp)) return fail(PDMP3_HIP_ENOMEM, "hipMalloc state", hipSuccess);
-  a.state_out = d_state ? d_state_tmp : nullptr;
-  a.stages = d_stages;
+  a.pcm = q.f32 ? nullptr : (int16_t*)q.pcm;               // (one destination: DecodeLaunch)
+  a.pcm_f32 = q.f32 ? (float*)q.pcm : nullptr;
+  a.state_in = (const float*)q.state;
+  a.state_out = q.state ? d_state_tmp : nullptr;
+  a.stages = q.stages;
   a.n_frames = n_frames;
   a.chunk_frames = chunk_frames;
-  a.prof = d_prof;
+  a.prof = q.prof;
   a.chain_state = nullptr; a.chain_flag = nullptr; a.chain_epoch = 0; a.debug_flags = c->debug_flags; a.sf_hint = c->sf_hint;
   a.n_gran = n_gran;
+
+  // ---- the choice: which kernel family, which grid ----
   bool gran = false, ring = false;
-  const bool plain = !d_stages && !d_prof;
+  const bool plain = !q.stages && !q.prof;
   // the persistent granule kernel: launches of at least ring_min_frames frames (and chunk_frames = -3: always)
-  const bool ring_prof = d_prof && chunk_frames_arg == -4;          // (development: the persistent kernel with per-turn stamps)
+  const bool ring_prof = q.prof && chunk_frames_arg == -4;          // (development: the persistent kernel with per-turn stamps)
   if ((plain || ring_prof) && c->chain_mode != 0 && n_frames >= 16 &&
       (chunk_frames_arg == PDMP3_HIP_CHUNK_PERSISTENT || ring_prof || (chunk_frames_arg <= 1 && chunk_frames_arg >= 0 && c->ring_min_frames > 0 && n_frames >= c->ring_min_frames)))
     ring = true;
@@ -587,7 +577,7 @@ static int launch_decode(pdmp3_hip_ctx* c, const int16_t* d_spectra, const pdmp3
   }
   ring = false;
 #endif
-  const bool gran_prof = d_prof && chunk_frames_arg == -2;          // (development: the granule kernel with per-wave stamps)
+  const bool gran_prof = q.prof && chunk_frames_arg == -2;          // (development: the granule kernel with per-wave stamps)
   if (!ring && (plain || gran_prof) && c->chain_mode != 0 && chunk_frames_arg <= 1 && n_frames <= c->gran_max_frames) {
     // one granule per wave (run_granule): tails and matrixing rows are handed from wave to wave, no halo.  Waits for
     // another workgroup are bounded (then: halo), so the launch finishes whatever part of it is resident; up to
@@ -599,61 +589,34 @@ static int launch_decode(pdmp3_hip_ctx* c, const int16_t* d_spectra, const pdmp3
       gran = true;
     }
   }
-  GlobalTables T{c->d_pow43, c->d_linetab, c->d_win, c->d_frag, c->d_frag + 10 * 64, c->d_frag + 20 * 64, c->d_frag + 28 * 64, c->d_tab_image};
-  const int nchunks = (n_frames + a.chunk_frames - 1) / a.chunk_frames;
-#if defined(PDMP3_WITH_RING_KERNEL)
+  DecodePlan p{PDMP3_HIP_LAUNCH_CHUNKS, (n_frames + a.chunk_frames - 1) / a.chunk_frames, 0};
   if (ring) {
     // one workgroup per CU while a range keeps at least 8 frames (= one turn of the 16 waves)
     const int cus = c->cus > 0 ? c->cus : 256;
     int per = (n_frames + cus - 1) / cus;
     if (per < 8) per = 8;
-    const int n_wgs = (n_frames + per - 1) / per;
     a.chunk_frames = 1;
-    c->last_kind = PDMP3_HIP_LAUNCH_PERSISTENT;
-    if (d_pcm_f32) hipLaunchKernelGGL((k_decode_p<true>), dim3(n_wgs), dim3(64 * 16), 0, s, a, T, per);
-    else hipLaunchKernelGGL((k_decode_p<false>), dim3(n_wgs), dim3(64 * 16), 0, s, a, T, per);
-  } else
-#endif
-  if (gran) {
+    p = DecodePlan{PDMP3_HIP_LAUNCH_PERSISTENT, (n_frames + per - 1) / per, per};
+  } else if (gran) {
     // (workgroups of 8 waves while that gives every CU at most one of them)
-    const bool small = 2 * n_frames <= c->wave_slots_gran / 2 || c->gran_w8;
-    const int W = small ? 8 : 16;
-    c->last_kind = W;
-    const int n_wgs = (2 * n_frames + W - 1) / W;
-    if (small) {
-      if (d_pcm_f32) hipLaunchKernelGGL((k_decode_g<true, 8>), dim3(n_wgs), dim3(64 * W), 0, s, a, T);
-      else hipLaunchKernelGGL((k_decode_g<false, 8>), dim3(n_wgs), dim3(64 * W), 0, s, a, T);
-    } else {
-      if (d_pcm_f32) hipLaunchKernelGGL((k_decode_g<true, 16>), dim3(n_wgs), dim3(64 * W), 0, s, a, T);
-      else hipLaunchKernelGGL((k_decode_g<false, 16>), dim3(n_wgs), dim3(64 * W), 0, s, a, T);
-    }
-  } else {
-    c->last_kind = PDMP3_HIP_LAUNCH_CHUNKS;
-    if (d_prof) hipLaunchKernelGGL(k_decode_prof, dim3(nchunks), dim3(64), 0, s, a, T);
-    else if (d_stages) hipLaunchKernelGGL(k_decode<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, (unsigned*)nullptr, 0u);
-    else if (lsf) {                                // every chunk of an LSF launch is k_decode_rare's
-      if (d_pcm_f32) hipLaunchKernelGGL(k_decode_rare<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 1, (const unsigned*)nullptr, 0u);
-      else hipLaunchKernelGGL(k_decode_rare<false>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 1, (const unsigned*)nullptr, 0u);
-    } else {
-      const unsigned ep = c->rare_epoch.fetch_add(1);
-      unsigned* flag = c->d_rare_flags + (ep % kRareSlots);
-      if (d_pcm_f32) {
-        hipLaunchKernelGGL((k_decode<false, true>), dim3(nchunks), dim3(64), 0, s, a, T, nchunks, flag, ep);
-        hipLaunchKernelGGL(k_decode_rare<true>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 0, (const unsigned*)flag, ep);
-      } else {
-        // (development: PDMP3_HIP_DEBUG_LDS_PAD = bytes of dynamic LDS added to every workgroup of the chunk kernel, which
-        //  lowers the number of waves a CU holds -- 24576: one wave per SIMD instead of two; tools/occupancy_scaling.py)
-        static const int lds_pad = [] { const char* e = getenv("PDMP3_HIP_DEBUG_LDS_PAD"); return e ? atoi(e) : 0; }();
-        hipLaunchKernelGGL(k_decode<false>, dim3(nchunks), dim3(64), (size_t)lds_pad, s, a, T, nchunks, flag, ep);
-        hipLaunchKernelGGL(k_decode_rare<false>, dim3(nchunks), dim3(64), 0, s, a, T, nchunks, 0, (const unsigned*)flag, ep);
-      }
-    }
+    const int W = (2 * n_frames <= c->wave_slots_gran / 2 || c->gran_w8) ? 8 : 16;
+    p = DecodePlan{W, (2 * n_frames + W - 1) / W, 0};
   }
+  c->last_kind = p.kind;
+
+  // ---- the launch ----
+  GlobalTables T{c->d_pow43, c->d_linetab, c->d_win, c->d_frag, c->d_frag + 10 * 64, c->d_frag + 20 * 64, c->d_frag + 28 * 64, c->d_tab_image};
+#if defined(PDMP3_WITH_RING_KERNEL)
+  if (ring) launch_ring(a, T, p, q.f32, s);
+  else
+#endif
+  if (gran) launch_granules(a, T, p, q.f32, s);
+  else launch_chunks(c, a, T, p, q.f32, q.lsf, s);
   hipError_t e = hipGetLastError();
   const char* what = "launch k_decode";
-  if (e == hipSuccess && d_state && !leave_state_in_tmp) {
+  if (e == hipSuccess && q.state && !q.leave_state_in_tmp) {
     what = "state copy";
-    e = hipMemcpyAsync(d_state, d_state_tmp, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, s);
+    e = hipMemcpyAsync(q.state, d_state_tmp, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, s);
   }
   if (e != hipSuccess) return fail(PDMP3_HIP_EDEVICE, what, e);
   return PDMP3_HIP_OK;
@@ -670,598 +633,115 @@ extern "C" int pdmp3_hip_release_stream_scratch(pdmp3_hip_ctx* ctx, void* stream
   return PDMP3_HIP_OK;
 }
 
+// the request of a bare call: records in, PCM out, the caller's state block (or none) on the caller's HIP stream
+static DecodeLaunch bare_request(const int16_t* d_spectra, const pdmp3_gc_side* d_side, int n_frames, void* d_state, void* d_pcm, void* stream) {
+  DecodeLaunch q;
+  q.spectra = d_spectra; q.side = d_side; q.n_frames = n_frames;
+  q.pcm = d_pcm;
+  q.state = d_state;
+  q.stream = (hipStream_t)stream;
+  return q;
+}
+
 extern "C" int pdmp3_hip_decode_frames(pdmp3_hip_ctx* ctx, const int16_t* d_spectra, const pdmp3_gc_side* d_side,
                                        int n_frames, void* d_state, int16_t* d_pcm, int chunk_frames, void* stream) {
-  return launch_decode(ctx, d_spectra, d_side, n_frames, d_state, d_pcm, nullptr, chunk_frames, stream);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, d_state, d_pcm, stream);
+  q.chunk_frames = chunk_frames;
+  return launch_decode(ctx, q);
 }
 
 extern "C" int pdmp3_hip_decode_frames_f32(pdmp3_hip_ctx* ctx, const int16_t* d_spectra, const pdmp3_gc_side* d_side,
                                            int n_frames, void* d_state, float* d_pcm, int chunk_frames, void* stream) {
   if (!d_pcm) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames_f32: d_pcm is NULL", hipSuccess);
-  return launch_decode(ctx, d_spectra, d_side, n_frames, d_state, nullptr, nullptr, chunk_frames, stream, nullptr, nullptr, d_pcm);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, d_state, d_pcm, stream);
+  q.f32 = true;
+  q.chunk_frames = chunk_frames;
+  return launch_decode(ctx, q);
 }
 
 // LSF frames (include/pdmp3_hip.h): n_frames one-granule frames of one channel count -> PCM in stream order
 extern "C" int pdmp3_hip_decode_lsf_frames(pdmp3_hip_ctx* ctx, const int16_t* d_spectra, const pdmp3_gc_side* d_side,
                                            int n_frames, void* d_state, int16_t* d_pcm, void* stream) {
-  return launch_decode(ctx, d_spectra, d_side, n_frames, d_state, d_pcm, nullptr, 0, stream, nullptr, nullptr, nullptr, nullptr, false, true);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, d_state, d_pcm, stream);
+  q.lsf = true;
+  return launch_decode(ctx, q);
 }
 extern "C" int pdmp3_hip_decode_lsf_frames_f32(pdmp3_hip_ctx* ctx, const int16_t* d_spectra, const pdmp3_gc_side* d_side,
                                                int n_frames, void* d_state, float* d_pcm, void* stream) {
   if (!d_pcm) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_lsf_frames_f32: d_pcm is NULL", hipSuccess);
-  return launch_decode(ctx, d_spectra, d_side, n_frames, d_state, nullptr, nullptr, 0, stream, nullptr, nullptr, d_pcm, nullptr, false, true);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, d_state, d_pcm, stream);
+  q.lsf = true;
+  q.f32 = true;
+  return launch_decode(ctx, q);
 }
 
 extern "C" int pdmp3_hip_decode_frames_stages(pdmp3_hip_ctx* ctx, const int16_t* d_spectra, const pdmp3_gc_side* d_side,
                                               int n_frames, void* d_state, int16_t* d_pcm, float* d_stages, void* stream) {
   if (!d_stages) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames_stages: d_stages is NULL", hipSuccess);
-  return launch_decode(ctx, d_spectra, d_side, n_frames, d_state, d_pcm, d_stages, 0, stream);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, d_state, d_pcm, stream);
+  q.stages = d_stages;
+  return launch_decode(ctx, q);
 }
 
 // ---------------------------------------------------------------------------
-// host-buffer streaming helper (pinned staging, hipMemcpyAsync both ways)
+// The device Huffman stage of one window (engine_internal.h UnpackWindow): stream.hip orders these behind the window's
+// uploads and the previous window's state; the kernels, their grids and templates are here (the LSF instantiations:
+// engine_lsf.hip).
 // ---------------------------------------------------------------------------
-// One pdmp3_hip_stream = one decoder's carried state + up to kMaxSlots staging slots.  Each slot has its own
-// HIP stream (H2D -> k_decode -> D2H), so slot w+1's upload overlaps slot w's kernel and download over the
-// two PCIe directions; the kernels themselves are chained in submit order through `ev_state` because each one
-// starts from the synthesis state its predecessor left (and they share the stream's d_state_tmp).
-constexpr int kMaxSlots = 8;
-struct StreamSlot {
-  hipStream_t stream;
-  hipEvent_t done;
-  int16_t* h_spectra; pdmp3_gc_side* h_side; int16_t* h_pcm;     // pinned
-  int16_t* d_spectra; pdmp3_gc_side* d_side; int16_t* d_pcm;
-  int16_t* d_pair_sp; pdmp3_gc_side* d_pair_sd;                   // LSF launches: the regrouped records (allocated on first use, (max_frames + 1) / 2 frames)
-  // bitstream-level input (allocated on first use)
-  pdmp3_frame_bits* h_bits; uint8_t* h_res;                       // pinned
-  pdmp3_frame_bits* d_bits; uint8_t* d_res; GcRaw* d_raw; uint32_t* d_outc; unsigned* d_mcnt;
-  pdmp3_row_desc* h_desc; pdmp3_row_desc* d_desc; uint8_t* d_pool;   // compact bits input: pinned descriptors; the pool is h_res
-  uint8_t* h_in; uint8_t* d_in;   // the blocks h_desc | h_bits | h_res and d_desc | d_bits | d_pool point into
-  pdmp3_clip_piece* h_pieces; pdmp3_clip_piece* d_pieces; uint8_t* d_stage;   // clips (allocated on first use): the pieces' table, the stage
-  int busy;
-  int direct;                     // the latest record submit ran on the pinned host buffers themselves (submit_records)
-};
-struct pdmp3_hip_stream {
-  pdmp3_hip_ctx* ctx;
-  int max_frames, n_slots;
-  StreamSlot s[kMaxSlots];
-  hipEvent_t ev_state;       // recorded after the latest kernel + state copy
-  int have_state_ev;
-  float* d_state;
-  float* d_state_tmp;
-  float* d_state_prev;       // d_state as it was before the latest submit of decoded records (pdmp3_hip_stream_rewind)
-  uint16_t* d_sfstate;       // [2][256]: scalefactors / count1 carried from frame to frame (unpack_core.h), double-buffered
-  int sf_cur;
-  int have_bits;
-  int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
-  int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
-};
-
-extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
-  if (!hs) return;
-  (void)hipSetDevice(hs->ctx->device);
-  for (int i = 0; i < hs->n_slots; ++i) {
-    StreamSlot& t = hs->s[i];
-    if (t.stream) { (void)hipStreamSynchronize(t.stream); (void)hipStreamDestroy(t.stream); }
-    if (t.done) (void)hipEventDestroy(t.done);
-    (void)hipHostFree(t.h_spectra); (void)hipHostFree(t.h_side); (void)hipHostFree(t.h_pcm);
-    (void)hipFree(t.d_spectra); (void)hipFree(t.d_side); (void)hipFree(t.d_pcm); (void)hipFree(t.d_pair_sp); (void)hipFree(t.d_pair_sd);
-    (void)hipHostFree(t.h_in);
-    (void)hipFree(t.d_in); (void)hipFree(t.d_res); (void)hipFree(t.d_raw); (void)hipFree(t.d_outc); (void)hipFree(t.d_mcnt);
-    (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
+// PDMP3_HIP_UNPACK_PROF=1 (development only: serialises): one line per k_unpack launch from the stamps of its workgroups
+static int unpack_prof_print(pdmp3_hip_ctx* c, hipStream_t s, int n_frames, int blocks) {
+  static std::vector<unsigned long long> hp(2048 * 8);
+  HIP_TRY(hipStreamSynchronize(s), "unpack prof sync");
+  HIP_TRY(hipMemcpy(hp.data(), c->d_uprof, (size_t)blocks * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost), "unpack prof D2H");
+  double d[5] = {0, 0, 0, 0, 0}, trips = 0, tmax = 0;
+  for (int b = 0; b < blocks; b++) {
+    for (int k = 0; k < 5; k++) d[k] += (double)(hp[b * 8 + k + 1] - hp[b * 8 + k]);
+    trips += (double)hp[b * 8 + 6];
+    const double tot = (double)(hp[b * 8 + 5] - hp[b * 8]);
+    if (tot > tmax) tmax = tot;
   }
-  (void)hipFree(hs->d_sfstate);
-  if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
-  (void)hipFree(hs->d_state);
-  chain_release(hs->ctx, hs);
-  (void)hipFree(hs->d_state_tmp);
-  (void)hipFree(hs->d_state_prev);
-  free(hs);
-}
-
-extern "C" int pdmp3_hip_stream_create_slots(pdmp3_hip_ctx* ctx, int max_frames, int n_slots, pdmp3_hip_stream** out) {
-  if (!ctx || !out || max_frames < 1 || n_slots < 1 || n_slots > kMaxSlots)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_create: bad argument", hipSuccess);
-  *out = nullptr;
-  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
-  pdmp3_hip_stream* hs = (pdmp3_hip_stream*)calloc(1, sizeof *hs);
-  if (!hs) return fail(PDMP3_HIP_ENOMEM, "calloc", hipSuccess);
-  hs->ctx = ctx;
-  hs->max_frames = max_frames;
-  hs->n_slots = n_slots;
-  const size_t n = (size_t)max_frames;
-#define HS_TRY(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { pdmp3_hip_stream_destroy(hs); return fail(PDMP3_HIP_EDEVICE, what, e_); } } while (0)
-  for (int i = 0; i < n_slots; ++i) {
-    StreamSlot& t = hs->s[i];
-    HS_TRY(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking), "hipStreamCreate");
-    HS_TRY(hipEventCreateWithFlags(&t.done, hipEventDisableTiming), "hipEventCreate");
-    HS_TRY(hipHostMalloc((void**)&t.h_spectra, n * PDMP3_FRAME_SPECTRA_BYTES, hipHostMallocDefault), "hipHostMalloc spectra");
-    HS_TRY(hipHostMalloc((void**)&t.h_side, n * PDMP3_FRAME_SIDE_BYTES, hipHostMallocDefault), "hipHostMalloc side");
-    HS_TRY(hipHostMalloc((void**)&t.h_pcm, n * PDMP3_FRAME_PCM_BYTES, hipHostMallocDefault), "hipHostMalloc pcm");
-    HS_TRY(hipMalloc((void**)&t.d_spectra, n * PDMP3_FRAME_SPECTRA_BYTES), "hipMalloc spectra");
-    HS_TRY(hipMalloc((void**)&t.d_side, n * PDMP3_FRAME_SIDE_BYTES), "hipMalloc side");
-    HS_TRY(hipMalloc((void**)&t.d_pcm, n * PDMP3_FRAME_PCM_BYTES), "hipMalloc pcm");
-  }
-  HS_TRY(hipEventCreateWithFlags(&hs->ev_state, hipEventDisableTiming), "hipEventCreate");
-  HS_TRY(hipMalloc((void**)&hs->d_state, pdmp3_hip_state_bytes()), "hipMalloc state");
-  HS_TRY(hipMalloc((void**)&hs->d_state_tmp, pdmp3_hip_state_bytes()), "hipMalloc state");
-  HS_TRY(hipMalloc((void**)&hs->d_state_prev, pdmp3_hip_state_bytes()), "hipMalloc state");
-  HS_TRY(hipMemsetAsync(hs->d_state, 0, pdmp3_hip_state_bytes(), hs->s[0].stream), "memset state");
-  HS_TRY(hipStreamSynchronize(hs->s[0].stream), "sync");
-#undef HS_TRY
-  *out = hs;
+  fprintf(stderr, "k_unpack prof: %d frames %d wgs | ticks/wg: setup %.0f head %.0f loop %.0f drain %.0f tail %.0f | trips %.1f -> %.1f ticks/trip | longest wg %.0f\n",
+          n_frames, blocks, d[0] / blocks, d[1] / blocks, d[2] / blocks, d[3] / blocks, d[4] / blocks, trips / blocks,
+          trips > 0 ? d[2] / trips : 0.0, tmax);
   return PDMP3_HIP_OK;
 }
 
-extern "C" int pdmp3_hip_stream_create(pdmp3_hip_ctx* ctx, int max_frames, pdmp3_hip_stream** out) {
-  return pdmp3_hip_stream_create_slots(ctx, max_frames, 1, out);
-}
+// rows of outcomes in UnpackWindow::outc: one per block of kMergeBlk frames, then one per super-block
+static unsigned merge_blocks(int n_frames) { return (unsigned)((n_frames + kMergeBlk - 1) / kMergeBlk); }
 
-static int drain_slots(pdmp3_hip_stream* hs) {
-  for (int i = 0; i < hs->n_slots; ++i) {
-    HIP_TRY(hipStreamSynchronize(hs->s[i].stream), "stream sync");
-    hs->s[i].busy = 0;
-  }
-  return PDMP3_HIP_OK;
-}
-
-extern "C" int pdmp3_hip_stream_reset(pdmp3_hip_stream* hs) {
-  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_reset: NULL", hipSuccess);
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  int rc = drain_slots(hs);
-  if (rc != PDMP3_HIP_OK) return rc;
-  hs->have_state_ev = 0;
-  HIP_TRY(hipMemsetAsync(hs->d_state, 0, pdmp3_hip_state_bytes(), hs->s[0].stream), "memset state");
-  if (hs->d_sfstate) HIP_TRY(hipMemsetAsync(hs->d_sfstate, 0, 2 * 256 * sizeof(uint16_t), hs->s[0].stream), "memset sfstate");
-  HIP_TRY(hipStreamSynchronize(hs->s[0].stream), "sync");
-  return PDMP3_HIP_OK;
-}
-
-#define SLOT_OK(hs, i) ((hs) && (i) >= 0 && (i) < (hs)->n_slots)
-extern "C" int pdmp3_hip_stream_slots(const pdmp3_hip_stream* hs) { return hs ? hs->n_slots : 0; }
-extern "C" int pdmp3_hip_stream_capacity(const pdmp3_hip_stream* hs) { return hs ? hs->max_frames : 0; }
-extern "C" int16_t* pdmp3_hip_stream_slot_spectra(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_spectra : nullptr; }
-extern "C" pdmp3_gc_side* pdmp3_hip_stream_slot_side(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_side : nullptr; }
-extern "C" const int16_t* pdmp3_hip_stream_slot_pcm(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_pcm : nullptr; }
-extern "C" int16_t* pdmp3_hip_stream_spectra(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_spectra(hs, 0); }
-extern "C" pdmp3_gc_side* pdmp3_hip_stream_side(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_side(hs, 0); }
-extern "C" const int16_t* pdmp3_hip_stream_pcm(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_pcm(hs, 0); }
-
-// PCM of a batch to its destination: into the slot's pinned buffer, or -- when the caller hands over pinned host
-// memory (pdmp3_hip_host_alloc) or DEVICE memory of its own -- straight to where it is wanted, `row` bytes per frame (4608; 2304 = mono frames
-// packed densely out of their 4608-byte slots).
-static int download_pcm(StreamSlot& t, size_t n, void* host_dst, int row, bool lsf = false) {
-  if (lsf && host_dst) {
-    // LSF frames (pdmp3_hip_decode_lsf_frames): stereo frames lie back to back, 2304 bytes each; mono frames in pairs in the
-    // first half of a 4608-byte place
-    if (row == PDMP3_FRAME_PCM_BYTES / 2) {
-      HIP_TRY(hipMemcpyAsync(host_dst, t.d_pcm, n * (size_t)row, hipMemcpyDefault, t.stream), "pcm (direct, LSF)");
-    } else {
-      if (n / 2) HIP_TRY(hipMemcpy2DAsync(host_dst, 2304, t.d_pcm, PDMP3_FRAME_PCM_BYTES, 2304, n / 2, hipMemcpyDefault, t.stream), "pcm (direct, LSF mono)");
-      if (n & 1) HIP_TRY(hipMemcpyAsync((char*)host_dst + (n / 2) * 2304, (const char*)t.d_pcm + (n / 2) * PDMP3_FRAME_PCM_BYTES, 1152, hipMemcpyDefault, t.stream), "pcm (direct, LSF mono tail)");
-    }
-    return PDMP3_HIP_OK;
-  }
-  if (!host_dst) {
-    HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_pcm, n * PDMP3_FRAME_PCM_BYTES, hipMemcpyDeviceToHost, t.stream), "D2H pcm");
-  } else if (row == PDMP3_FRAME_PCM_BYTES) {
-    HIP_TRY(hipMemcpyAsync(host_dst, t.d_pcm, n * PDMP3_FRAME_PCM_BYTES, hipMemcpyDefault, t.stream), "pcm (direct)");
-  } else {
-    HIP_TRY(hipMemcpy2DAsync(host_dst, (size_t)row, t.d_pcm, PDMP3_FRAME_PCM_BYTES, (size_t)row, n, hipMemcpyDefault, t.stream),
-            "pcm (direct, packed)");
-  }
-  return PDMP3_HIP_OK;
-}
-
-extern "C" int pdmp3_hip_host_alloc(size_t bytes, void** out) {
-  if (!out) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_host_alloc: out is NULL", hipSuccess);
-  *out = nullptr;
-  HIP_TRY(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault), "hipHostMalloc");
-  return PDMP3_HIP_OK;
-}
-extern "C" void pdmp3_hip_host_free(void* p) { if (p) (void)hipHostFree(p); }
-extern "C" int pdmp3_hip_host_is_pinned(const void* p, size_t bytes) {
-  if (!p) return 0;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (a.type != hipMemoryTypeHost && a.type != hipMemoryTypeDevice) return 0;
-  if (bytes > 1) {
-    hipPointerAttribute_t e;
-    if (hipPointerGetAttributes(&e, (const char*)p + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (e.type != a.type) return 0;
-  }
-  return a.type == hipMemoryTypeHost ? 1 : 2;
-}
-
-extern "C" int pdmp3_hip_copy_to_dest(void* dst, const void* src_host, size_t bytes) {
-  if (!bytes) return PDMP3_HIP_OK;
-  if (!dst || !src_host) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_copy_to_dest: NULL", hipSuccess);
-  HIP_TRY(hipMemcpy(dst, src_host, bytes, hipMemcpyDefault), "copy to destination");
-  return PDMP3_HIP_OK;
-}
-
-// PCM of the record-level submits (pdmp3_hip_stream_submit / _decode) as float from now on (on != 0) or int16 again.
-// Call with nothing in flight; the slots' PCM buffers are re-allocated.  The accessors return the same pointers'
-// new values, to be read as float: frame f at floats [f*2304, f*2304+2304).
-extern "C" int pdmp3_hip_stream_set_f32(pdmp3_hip_stream* hs, int on) {
-  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_set_f32: NULL", hipSuccess);
-  on = on ? 1 : 0;
-  if (hs->f32 == on) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  int rc = drain_slots(hs);
-  if (rc != PDMP3_HIP_OK) return rc;
-  const size_t bytes = (size_t)hs->max_frames * (on ? PDMP3_FRAME_PCM_F32_BYTES : PDMP3_FRAME_PCM_BYTES);
-  for (int i = 0; i < hs->n_slots; ++i) {
-    StreamSlot& t = hs->s[i];
-    (void)hipHostFree(t.h_pcm); t.h_pcm = nullptr;
-    (void)hipFree(t.d_pcm); t.d_pcm = nullptr;
-    HIP_TRY(hipHostMalloc((void**)&t.h_pcm, bytes, hipHostMallocDefault), "hipHostMalloc pcm");
-    HIP_TRY(hipMalloc((void**)&t.d_pcm, bytes), "hipMalloc pcm");
-  }
-  hs->f32 = on;
-  return PDMP3_HIP_OK;
-}
-
-static int submit_records(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row);
-extern "C" int pdmp3_hip_stream_submit(pdmp3_hip_stream* hs, int slot, int n_frames) {
-  return submit_records(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES);
-}
-extern "C" int pdmp3_hip_stream_submit_to(pdmp3_hip_stream* hs, int slot, int n_frames, void* pinned_dst, int row_bytes) {
-  if (pinned_dst && hs && hs->lsf) {
-    if (row_bytes != PDMP3_FRAME_PCM_BYTES / 2 && row_bytes != PDMP3_FRAME_PCM_BYTES / 4)
-      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_to: row_bytes of LSF frames must be 2304 (stereo) or 1152 (mono)", hipSuccess);
-  } else
-  if (pinned_dst && row_bytes != PDMP3_FRAME_PCM_BYTES && row_bytes != PDMP3_FRAME_PCM_BYTES / 2)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_to: row_bytes must be 4608 or 2304", hipSuccess);
-  return submit_records(hs, slot, n_frames, pinned_dst, row_bytes);
-}
-// the slot's buffers for an LSF launch's regrouped records (launch_decode pair_sp / pair_sd): allocated once, on the first LSF submit
-static int slot_pairs(pdmp3_hip_stream* hs, StreamSlot& t) {
-  if (!hs->lsf || t.d_pair_sp) return PDMP3_HIP_OK;
-  const size_t np = ((size_t)hs->max_frames + 1) / 2;
-  HIP_TRY(hipMalloc((void**)&t.d_pair_sp, np * PDMP3_FRAME_SPECTRA_BYTES), "hipMalloc LSF pairs");
-  if (hipMalloc((void**)&t.d_pair_sd, np * PDMP3_FRAME_SIDE_BYTES) != hipSuccess) { (void)hipFree(t.d_pair_sp); t.d_pair_sp = nullptr; return fail(PDMP3_HIP_ENOMEM, "hipMalloc LSF pairs", hipGetLastError()); }
-  return PDMP3_HIP_OK;
-}
-static int submit_records(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row) {
-  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit: bad argument", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit: slot still in flight (wait for it first)", hipSuccess);
-  if (n_frames == 0) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  { const int rcp = slot_pairs(hs, t); if (rcp != PDMP3_HIP_OK) return rcp; }
-  const size_t n = (size_t)n_frames;
-  if (hs->f32 && host_dst) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_to: not with float PCM", hipSuccess);
-  // Small batches (the streaming API's read-ahead: a handful of frames per call): no copies at all.  The kernel reads the
-  // records from the slot's PINNED host buffers and writes the PCM into pinned host memory itself -- a few KB each way,
-  // one PCIe round trip under the waves' first phase instead of two copy commands in front of the kernel and one behind
-  // it -- and the three state buffers rotate instead of being copied (previous <- current <- next).  Per batch: one
-  // launch, two event records, one wait.  (PDMP3_HIP_DIRECT_MAX: largest such batch in frames, 0 = never.)
-  t.direct = 0;
-  // (the kernel itself stores into host_dst on this path: only where it certainly can -- pinned host memory, or memory of
-  //  THIS device; registered / managed memory and another GPU's memory take the copy path, whose hipMemcpyAsync sorts it out)
-  bool dst_ok = true;
-  if (host_dst) {
-    hipPointerAttribute_t pa;
-    if (hipPointerGetAttributes(&pa, host_dst) != hipSuccess) { (void)hipGetLastError(); dst_ok = false; }
-    else dst_ok = (pa.type == hipMemoryTypeHost && !pa.isManaged) || (pa.type == hipMemoryTypeDevice && pa.device == hs->ctx->device);
-  }
-  if (n_frames <= hs->ctx->direct_max_frames && dst_ok && (!host_dst || row == PDMP3_FRAME_PCM_BYTES) && !(hs->lsf && host_dst)) {
-    // (a stream object with ONE slot -- the streaming API's -- has one HIP stream: its batches are in order anyway, and
-    //  its wait is for that stream: no events at all, each of which is a call here and a packet of its own on the queue)
-    const bool lone = hs->n_slots == 1;
-    if (!lone && hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
-    void* dst = host_dst ? host_dst : (void*)t.h_pcm;
-    int rc = hs->f32
-        ? launch_decode(hs->ctx, t.h_spectra, t.h_side, n_frames, hs->d_state, nullptr, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, (float*)dst, hs, true, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd)
-        : launch_decode(hs->ctx, t.h_spectra, t.h_side, n_frames, hs->d_state, (int16_t*)dst, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, nullptr, hs, true, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd);
-    if (rc != PDMP3_HIP_OK) return rc;
-    float* const was_prev = hs->d_state_prev;
-    hs->d_state_prev = hs->d_state;            // (what pdmp3_hip_stream_rewind goes back to)
-    hs->d_state = hs->d_state_tmp;             // the kernel left the new state here
-    hs->d_state_tmp = was_prev;
-    if (!lone) {
-      HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
-      hs->have_state_ev = 1;
-      HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
-    }
-    t.busy = 1;
-    t.direct = lone ? 2 : 1;                   // 2: pdmp3_hip_stream_wait synchronises the stream
-    return PDMP3_HIP_OK;
-  }
-  HIP_TRY(hipMemcpyAsync(t.d_spectra, t.h_spectra, n * PDMP3_FRAME_SPECTRA_BYTES, hipMemcpyHostToDevice, t.stream), "H2D spectra");
-  HIP_TRY(hipMemcpyAsync(t.d_side, t.h_side, n * PDMP3_FRAME_SIDE_BYTES, hipMemcpyHostToDevice, t.stream), "H2D side");
-  if (hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
-  HIP_TRY(hipMemcpyAsync(hs->d_state_prev, hs->d_state, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, t.stream), "keep the state");
-  int rc = hs->f32
-      ? launch_decode(hs->ctx, t.d_spectra, t.d_side, n_frames, hs->d_state, nullptr, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, (float*)t.d_pcm, hs, false, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd)
-      : launch_decode(hs->ctx, t.d_spectra, t.d_side, n_frames, hs->d_state, t.d_pcm, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, nullptr, hs, false, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd);
-  if (rc != PDMP3_HIP_OK) return rc;
-  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
-  hs->have_state_ev = 1;
-  if (hs->f32) HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_pcm, n * PDMP3_FRAME_PCM_F32_BYTES, hipMemcpyDeviceToHost, t.stream), "D2H pcm");
-  else rc = download_pcm(t, n, host_dst, row, hs->lsf != 0);
-  if (rc != PDMP3_HIP_OK) return rc;
-  HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
-  t.busy = 1;
-  return PDMP3_HIP_OK;
-}
-
-// The records of this stream object's following submits are LSF frames (on != 0: decoded like pdmp3_hip_decode_lsf_frames,
-// the PCM in its layout) or MPEG-1 frames again.  A setting of the host's for the next submit; the synthesis state is
-// the same block either way.
-extern "C" int pdmp3_hip_stream_set_lsf(pdmp3_hip_stream* hs, int on) {
-  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_set_lsf: NULL", hipSuccess);
-  hs->lsf = on != 0;
-  return PDMP3_HIP_OK;
-}
-
-extern "C" int pdmp3_hip_stream_wait(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot)) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_wait: bad argument", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (!t.busy) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  if (t.direct == 2) HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  else HIP_TRY(hipEventSynchronize(t.done), "event sync");
-  t.busy = 0;
-  return PDMP3_HIP_OK;
-}
-
-// 1: pdmp3_hip_stream_wait(hs, slot) would return at once (nothing submitted, or the GPU is through with it); 0: not yet.
-// For the thread that would call the wait (the whole-stream decoder asks how much the GPU still has to do before it
-// decides how many frames the next window gets).
-extern "C" int pdmp3_hip_stream_done(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot)) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_done: bad argument", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (!t.busy) return 1;
-  const hipError_t e = t.direct == 2 ? hipStreamQuery(t.stream) : hipEventQuery(t.done);
-  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
-  return 1;                                     // (done, or an error the wait will report)
-}
-
-// Undo the slot's latest pdmp3_hip_stream_submit beyond its first keep_frames frames: the carried synthesis state
-// becomes what it was after frame keep_frames - 1 of that batch (the state before the batch, then the kept frames
-// again -- their records are still in the slot's device buffers).  Blocks until done.
-extern "C" int pdmp3_hip_stream_rewind(pdmp3_hip_stream* hs, int slot, int keep_frames) {
-  if (!SLOT_OK(hs, slot) || keep_frames < 0 || keep_frames > hs->max_frames)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_rewind: bad argument", hipSuccess);
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  StreamSlot& t = hs->s[slot];
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  t.busy = 0;
-  HIP_TRY(hipMemcpyAsync(hs->d_state, hs->d_state_prev, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, t.stream), "restore the state");
-  if (keep_frames) {
-    // (the records are where the submit took them from: the pinned host buffers if it ran on those)
-    const int16_t* sp = t.direct ? t.h_spectra : t.d_spectra;
-    const pdmp3_gc_side* sd = t.direct ? t.h_side : t.d_side;
-    const int rc = hs->f32
-        ? launch_decode(hs->ctx, sp, sd, keep_frames, hs->d_state, nullptr, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, (float*)t.d_pcm, hs, false, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd)
-        : launch_decode(hs->ctx, sp, sd, keep_frames, hs->d_state, t.d_pcm, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, nullptr, hs, false, hs->lsf != 0, t.d_pair_sp, t.d_pair_sd);
-    if (rc != PDMP3_HIP_OK) return rc;
-  }
-  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
-  hs->have_state_ev = 1;
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
-}
-
-// ---- bitstream-level input ------------------------------------------------
-static int ensure_bits(pdmp3_hip_stream* hs) {
-  if (hs->have_bits) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  const size_t n = (size_t)hs->max_frames;
-  for (int i = 0; i < hs->n_slots; ++i) {
-    StreamSlot& t = hs->s[i];
-    // descriptors | side info | rows or pool: ONE pinned block and one device block with the same layout, so that the
-    // compact input of a window goes up in one copy (a hipMemcpyAsync call costs the submitting thread 20-40 us here)
-    const size_t desc_bytes = n * sizeof(pdmp3_row_desc), bits_bytes = n * sizeof(pdmp3_frame_bits);
-    const size_t pool_cap = n * PDMP3_RESERVOIR_BYTES + PDMP3_POOL_SLACK_BYTES + 16;
-    HIP_TRY(hipHostMalloc((void**)&t.h_in, desc_bytes + bits_bytes + pool_cap, hipHostMallocDefault), "hipHostMalloc window input");
-    HIP_TRY(hipMalloc((void**)&t.d_in, desc_bytes + bits_bytes + pool_cap), "hipMalloc window input");
-    t.h_desc = reinterpret_cast<pdmp3_row_desc*>(t.h_in);
-    t.h_bits = reinterpret_cast<pdmp3_frame_bits*>(t.h_in + desc_bytes);
-    t.h_res = t.h_in + desc_bytes + bits_bytes;
-    t.d_desc = reinterpret_cast<pdmp3_row_desc*>(t.d_in);
-    t.d_bits = reinterpret_cast<pdmp3_frame_bits*>(t.d_in + desc_bytes);
-    t.d_pool = t.d_in + desc_bytes + bits_bytes;
-    HIP_TRY(hipMalloc((void**)&t.d_res, n * PDMP3_RESERVOIR_BYTES + 16), "hipMalloc reservoir");
-    HIP_TRY(hipMalloc((void**)&t.d_raw, n * 4 * sizeof(GcRaw)), "hipMalloc raw");
-    // rows of outcomes: one per block of kMergeBlk frames, then one per super-block; the super-blocks' counters (zero between launches)
-    const size_t mblk = (n + kMergeBlk - 1) / kMergeBlk, msup = (mblk + kMergeSuper - 1) / kMergeSuper;
-    HIP_TRY(hipMalloc((void**)&t.d_outc, (mblk + msup) * kMergeLanes * sizeof(uint32_t)), "hipMalloc merge outcomes");
-    HIP_TRY(hipMalloc((void**)&t.d_mcnt, (msup + 1) * sizeof(unsigned)), "hipMalloc merge counters");
-    HIP_TRY(hipMemset(t.d_mcnt, 0, (msup + 1) * sizeof(unsigned)), "memset merge counters");
-  }
-  HIP_TRY(hipMalloc((void**)&hs->d_sfstate, 2 * 256 * sizeof(uint16_t)), "hipMalloc sfstate");
-  HIP_TRY(hipMemset(hs->d_sfstate, 0, 2 * 256 * sizeof(uint16_t)), "memset sfstate");
-  // hipMemset returns before the device has run it, and the slots' streams are non-blocking: they do not wait for the null
-  // stream.  Without this wait the zeroing of the scalefactor state could land AFTER the first window's k_merge_apply had
-  // written it -- the second window of a fresh decoder then started from zeros (round 6: one whole-stream decode in ~2000
-  // with fresh decoders differed by 1-3 LSB in frames 17-18; tools/ubench/malloc_async_probe.cpp mode M shows the mechanism)
-  HIP_TRY(hipDeviceSynchronize(), "device sync after the memsets");
-  hs->have_bits = 1;
-  return PDMP3_HIP_OK;
-}
-
-extern "C" pdmp3_frame_bits* pdmp3_hip_stream_slot_bits(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
-  return hs->s[slot].h_bits;
-}
-extern "C" uint8_t* pdmp3_hip_stream_slot_reservoir(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
-  return hs->s[slot].h_res;
-}
-
-extern "C" pdmp3_row_desc* pdmp3_hip_stream_slot_rowdesc(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
-  return hs->s[slot].h_desc;
-}
-extern "C" uint8_t* pdmp3_hip_stream_slot_pool(pdmp3_hip_stream* hs, int slot) { return pdmp3_hip_stream_slot_reservoir(hs, slot); }
-extern "C" size_t pdmp3_hip_stream_pool_bytes(const pdmp3_hip_stream* hs) { return hs ? (size_t)hs->max_frames * PDMP3_RESERVOIR_BYTES + PDMP3_POOL_SLACK_BYTES : 0; }
-
-static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes = 0, int clip_pieces = -1,
-                       size_t stage_bytes = 0);
-// row_bytes of a _to destination: 4608 / 2304 for MPEG-1 windows, 2304 (stereo) / 1152 (mono) for LSF ones
-static bool bits_row_ok(const pdmp3_hip_stream* hs, int row_bytes) {
-  if (hs && hs->lsf) return row_bytes == PDMP3_FRAME_PCM_BYTES / 2 || row_bytes == PDMP3_FRAME_PCM_BYTES / 4;
-  return row_bytes == PDMP3_FRAME_PCM_BYTES || row_bytes == PDMP3_FRAME_PCM_BYTES / 2;
-}
-extern "C" int pdmp3_hip_stream_submit_pool_to(pdmp3_hip_stream* hs, int slot, int n_frames, size_t pool_bytes, void* pinned_dst, int row_bytes) {
-  if (pinned_dst && !bits_row_ok(hs, row_bytes))
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_pool_to: row_bytes must be 4608 or 2304 (LSF: 2304 or 1152)", hipSuccess);
-  if (!pool_bytes || !hs || pool_bytes > pdmp3_hip_stream_pool_bytes(hs))
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_pool_to: bad pool size", hipSuccess);
-  return submit_bits(hs, slot, n_frames, pinned_dst, row_bytes, pool_bytes);
-}
-extern "C" int pdmp3_hip_stream_submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames) {
-  return submit_bits(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES);
-}
-extern "C" int pdmp3_hip_stream_submit_bits_to(pdmp3_hip_stream* hs, int slot, int n_frames, void* pinned_dst, int row_bytes) {
-  if (pinned_dst && !bits_row_ok(hs, row_bytes))
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_to: row_bytes must be 4608 or 2304 (LSF: 2304 or 1152)", hipSuccess);
-  return submit_bits(hs, slot, n_frames, pinned_dst, row_bytes);
-}
-static int ensure_clip(pdmp3_hip_stream* hs, StreamSlot& t) {
-  if (t.d_stage) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  const size_t n = (size_t)hs->max_frames;
-  HIP_TRY(hipHostMalloc((void**)&t.h_pieces, n * sizeof(pdmp3_clip_piece), hipHostMallocDefault), "hipHostMalloc clip pieces");
-  HIP_TRY(hipMalloc((void**)&t.d_pieces, n * sizeof(pdmp3_clip_piece)), "hipMalloc clip pieces");
-  HIP_TRY(hipMalloc((void**)&t.d_stage, n * PDMP3_FRAME_PCM_BYTES), "hipMalloc clip stage");
-  return PDMP3_HIP_OK;
-}
-extern "C" void* pdmp3_hip_stream_slot_clip_stage(pdmp3_hip_stream* hs, int slot) {
-  if (!SLOT_OK(hs, slot) || ensure_clip(hs, hs->s[slot]) != PDMP3_HIP_OK) return nullptr;
-  return hs->s[slot].d_stage;
-}
-extern "C" int pdmp3_hip_stream_submit_bits_clips(pdmp3_hip_stream* hs, int slot, int n_frames, const pdmp3_clip_piece* pieces, int n_pieces,
-                                                  size_t stage_bytes) {
-  if (!SLOT_OK(hs, slot) || n_pieces < 0 || n_pieces > hs->max_frames || (n_pieces && !pieces) ||
-      stage_bytes > (size_t)hs->max_frames * PDMP3_FRAME_PCM_BYTES || hs->f32)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: bad argument", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: slot still in flight (wait for it first)", hipSuccess);
-  const int rc = ensure_clip(hs, t);
-  if (rc != PDMP3_HIP_OK) return rc;
-  if (n_pieces) memcpy(t.h_pieces, pieces, (size_t)n_pieces * sizeof *pieces);
-  return submit_bits(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES, 0, n_pieces, stage_bytes);
-}
-static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes, int clip_pieces,
-                       size_t stage_bytes) {
-  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits: bad argument", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits: slot still in flight (wait for it first)", hipSuccess);
-  if (n_frames == 0) return PDMP3_HIP_OK;
-  int rc = ensure_bits(hs);
-  if (rc != PDMP3_HIP_OK) return rc;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  const bool lsf = hs->lsf != 0;
-  if (lsf) { rc = slot_pairs(hs, t); if (rc != PDMP3_HIP_OK) return rc; }   // (the records regrouped for the transforms: launch_decode)
-  const size_t n = (size_t)n_frames;
-  t.direct = 0;               // (the records of this submit are the device's: a rewind replays d_spectra, never h_spectra)
-  if (pool_bytes) {           // compact input: descriptors, side info and pool up in one copy, rows rebuilt on the device
-    // (Tried: k_rows reading descriptors, side info and pool straight from the pinned host block, no copy at all -- the
-    //  kernel then runs at PCIe speed and the pipeline, which is bound by the kernels of a window, lost 20 %.)
-    const size_t head = (size_t)hs->max_frames * (sizeof(pdmp3_row_desc) + sizeof(pdmp3_frame_bits));
-    HIP_TRY(hipMemcpyAsync(t.d_in, t.h_in, head + pool_bytes, hipMemcpyHostToDevice, t.stream), "H2D window input");
-    hipLaunchKernelGGL(k_rows, dim3((unsigned)((n_frames + kRowsWaves - 1) / kRowsWaves)), dim3(64 * kRowsWaves), 0, t.stream, t.d_desc, t.d_pool, t.d_res, n_frames);
+int unpack_window_head(pdmp3_hip_ctx* c, const UnpackWindow& w) {
+  const int n_frames = w.n_frames;
+  if (w.desc) {
+    hipLaunchKernelGGL(k_rows, dim3((unsigned)((n_frames + kRowsWaves - 1) / kRowsWaves)), dim3(64 * kRowsWaves), 0, w.stream, w.desc, w.pool, w.res, n_frames);
     HIP_TRY(hipGetLastError(), "launch k_rows");
-  } else {
-    HIP_TRY(hipMemcpyAsync(t.d_bits, t.h_bits, n * sizeof(pdmp3_frame_bits), hipMemcpyHostToDevice, t.stream), "H2D bits");
-    HIP_TRY(hipMemcpyAsync(t.d_res, t.h_res, n * PDMP3_RESERVOIR_BYTES, hipMemcpyHostToDevice, t.stream), "H2D reservoir");
   }
-  {
-    int blocks = (n_frames + kUnpackRows - 1) / kUnpackRows;
-    if (blocks > 2048) blocks = 2048;
-    if (lsf) HIP_TRY(pdmp3_launch_unpack_lsf(dim3(blocks), t.stream, hs->ctx->d_unpack, t.d_bits, t.d_res, n_frames, t.d_spectra, t.d_raw,
-                                             hs->ctx->unpack_n16, hs->ctx->d_uprof), "launch k_unpack (LSF)");
-    else {
-      hipLaunchKernelGGL(k_unpack<false>, dim3(blocks), dim3(kUnpackThreads), 0, t.stream, hs->ctx->d_unpack, t.d_bits, t.d_res,
-                         n_frames, t.d_spectra, t.d_raw, hs->ctx->unpack_n16, hs->ctx->d_uprof);
-      HIP_TRY(hipGetLastError(), "launch k_unpack");
-    }
-    if (hs->ctx->d_uprof) {                            // development only: serialises, prints one line per launch
-      static std::vector<unsigned long long> hp(2048 * 8);
-      HIP_TRY(hipStreamSynchronize(t.stream), "unpack prof sync");
-      HIP_TRY(hipMemcpy(hp.data(), hs->ctx->d_uprof, (size_t)blocks * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost), "unpack prof D2H");
-      double d[5] = {0, 0, 0, 0, 0}, trips = 0, tmax = 0;
-      for (int b = 0; b < blocks; b++) {
-        for (int k = 0; k < 5; k++) d[k] += (double)(hp[b * 8 + k + 1] - hp[b * 8 + k]);
-        trips += (double)hp[b * 8 + 6];
-        const double tot = (double)(hp[b * 8 + 5] - hp[b * 8]);
-        if (tot > tmax) tmax = tot;
-      }
-      fprintf(stderr, "k_unpack prof: %d frames %d wgs | ticks/wg: setup %.0f head %.0f loop %.0f drain %.0f tail %.0f | trips %.1f -> %.1f ticks/trip | longest wg %.0f\n",
-              n_frames, blocks, d[0] / blocks, d[1] / blocks, d[2] / blocks, d[3] / blocks, d[4] / blocks, trips / blocks,
-              trips > 0 ? d[2] / trips : 0.0, tmax);
-    }
-  }
-  // what each block of 64 frames does to the values that survive frames needs nothing of the batch before ...
-  const unsigned merge_blocks_n = (unsigned)((n_frames + kMergeBlk - 1) / kMergeBlk);
-  uint32_t* d_sup = t.d_outc + (size_t)merge_blocks_n * kMergeLanes;
-  hipLaunchKernelGGL(k_merge_outcome, dim3(merge_blocks_n), dim3(kMergeLanes), 0, t.stream, t.d_raw, t.d_bits, n_frames, t.d_outc, d_sup, t.d_mcnt);
-  HIP_TRY(hipGetLastError(), "launch k_merge_outcome");
-  // ... everything from here on continues it (scalefactor / count1 carry, synthesis state)
-  if (hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
-  if (lsf) HIP_TRY(pdmp3_launch_merge_apply_lsf(dim3(merge_blocks_n), t.stream, t.d_raw, t.d_bits, n_frames, t.d_outc, d_sup,
-                                                hs->d_sfstate + 256 * hs->sf_cur, hs->d_sfstate + 256 * (hs->sf_cur ^ 1), t.d_side), "launch k_merge_apply (LSF)");
+  int blocks = (n_frames + kUnpackRows - 1) / kUnpackRows;
+  if (blocks > 2048) blocks = 2048;
+  if (w.lsf) HIP_TRY(pdmp3_launch_unpack_lsf(dim3(blocks), w.stream, c->d_unpack, w.bits, w.res, n_frames, w.spectra, w.raw,
+                                             c->unpack_n16, c->d_uprof), "launch k_unpack (LSF)");
   else {
-    hipLaunchKernelGGL(k_merge_apply<false>, dim3(merge_blocks_n), dim3(kMergeLanes), 0, t.stream, t.d_raw, t.d_bits, n_frames, t.d_outc, d_sup,
-                       hs->d_sfstate + 256 * hs->sf_cur, hs->d_sfstate + 256 * (hs->sf_cur ^ 1), t.d_side);
+    hipLaunchKernelGGL(k_unpack<false>, dim3(blocks), dim3(kUnpackThreads), 0, w.stream, c->d_unpack, w.bits, w.res,
+                       n_frames, w.spectra, w.raw, c->unpack_n16, c->d_uprof);
+    HIP_TRY(hipGetLastError(), "launch k_unpack");
+  }
+  if (c->d_uprof) { const int rc = unpack_prof_print(c, w.stream, n_frames, blocks); if (rc != PDMP3_HIP_OK) return rc; }
+  // what each block of 64 frames does to the values that survive frames needs nothing of the batch before ...
+  const unsigned nblk = merge_blocks(n_frames);
+  hipLaunchKernelGGL(k_merge_outcome, dim3(nblk), dim3(kMergeLanes), 0, w.stream, w.raw, w.bits, n_frames, w.outc, w.outc + (size_t)nblk * kMergeLanes, w.mcnt);
+  HIP_TRY(hipGetLastError(), "launch k_merge_outcome");
+  return PDMP3_HIP_OK;
+}
+
+// ... everything from here on continues it (scalefactor / count1 carry, synthesis state)
+int unpack_window_carry(const UnpackWindow& w) {
+  const unsigned nblk = merge_blocks(w.n_frames);
+  const uint32_t* d_sup = w.outc + (size_t)nblk * kMergeLanes;
+  if (w.lsf) HIP_TRY(pdmp3_launch_merge_apply_lsf(dim3(nblk), w.stream, w.raw, w.bits, w.n_frames, w.outc, d_sup, w.sf_in, w.sf_out, w.side), "launch k_merge_apply (LSF)");
+  else {
+    hipLaunchKernelGGL(k_merge_apply<false>, dim3(nblk), dim3(kMergeLanes), 0, w.stream, w.raw, w.bits, w.n_frames, w.outc, d_sup, w.sf_in, w.sf_out, w.side);
     HIP_TRY(hipGetLastError(), "launch k_merge_apply");
   }
-  hs->sf_cur ^= 1;
-  // A destination in THIS device's memory that takes whole 4608-byte rows: the kernel stores the PCM there itself (the
-  // copy from the slot's buffer was 11 us of a window's 235 -- 75 MB through HBM for 8192 frames; end to end, A/B on one
-  // box, four runs each: 26.5 against 25.9 M frames/s).  Pinned host memory
-  // stays with the copy command: stores over PCIe from 256 CUs are slower than the DMA engine.
-  // (LSF windows: their PCM layout is pdmp3_hip_decode_lsf_frames', which download_pcm sorts out)
-  int16_t* pcm_out = t.d_pcm;
-  if (!lsf && host_dst && row == PDMP3_FRAME_PCM_BYTES && !((uintptr_t)host_dst & 15)) {
-    hipPointerAttribute_t pa, pe;
-    if (hipPointerGetAttributes(&pa, host_dst) == hipSuccess &&
-        hipPointerGetAttributes(&pe, (const char*)host_dst + n * PDMP3_FRAME_PCM_BYTES - 1) == hipSuccess) {
-      if (pa.type == hipMemoryTypeDevice && pe.type == hipMemoryTypeDevice && pa.device == hs->ctx->device && pe.device == hs->ctx->device && !pa.isManaged)
-        pcm_out = (int16_t*)host_dst;
-    } else (void)hipGetLastError();
-  }
-  rc = launch_decode(hs->ctx, t.d_spectra, t.d_side, n_frames, hs->d_state, pcm_out, nullptr, 0, t.stream, nullptr, hs->d_state_tmp, nullptr, hs, true,
-                     lsf, t.d_pair_sp, t.d_pair_sd);
-  if (rc != PDMP3_HIP_OK) return rc;
-  { float* x = hs->d_state; hs->d_state = hs->d_state_tmp; hs->d_state_tmp = x; }   // (the new state is where the kernel left it)
-  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
-  hs->have_state_ev = 1;
-  if (clip_pieces >= 0) {     // clips: the PCM stays in d_pcm, k_clip_pack places the kept frames (clip.hip)
-    if (clip_pieces) {
-      HIP_TRY(hipMemcpyAsync(t.d_pieces, t.h_pieces, (size_t)clip_pieces * sizeof(pdmp3_clip_piece), hipMemcpyHostToDevice, t.stream), "H2D clip pieces");
-      HIP_TRY(pdmp3_launch_clip_pack(t.stream, t.d_pieces, clip_pieces, t.d_pcm), "launch k_clip_pack");
-    }
-    if (stage_bytes) HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_stage, stage_bytes, hipMemcpyDeviceToHost, t.stream), "D2H clip stage");
-  } else if (pcm_out == t.d_pcm) {
-    rc = download_pcm(t, n, host_dst, row, lsf);
-    if (rc != PDMP3_HIP_OK) return rc;
-  }
-  HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
-  t.busy = 1;
   return PDMP3_HIP_OK;
-}
-
-extern "C" int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side) {
-  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames || !spectra || !side)
-    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_fetch_records: bad argument", hipSuccess);
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  HIP_TRY(hipStreamSynchronize(hs->s[slot].stream), "stream sync");
-  HIP_TRY(hipMemcpy(spectra, hs->s[slot].d_spectra, (size_t)n_frames * PDMP3_FRAME_SPECTRA_BYTES, hipMemcpyDeviceToHost), "D2H spectra");
-  HIP_TRY(hipMemcpy(side, hs->s[slot].d_side, (size_t)n_frames * PDMP3_FRAME_SIDE_BYTES, hipMemcpyDeviceToHost), "D2H side");
-  return PDMP3_HIP_OK;
-}
-
-extern "C" int pdmp3_hip_stream_decode(pdmp3_hip_stream* hs, int n_frames) {
-  int rc = pdmp3_hip_stream_submit(hs, 0, n_frames);
-  if (rc != PDMP3_HIP_OK) return rc;
-  return pdmp3_hip_stream_wait(hs, 0);
 }
 
 extern "C" int pdmp3_hip_generate_frames(pdmp3_hip_ctx* ctx, uint64_t seed, int64_t first_frame, int n_frames,
@@ -1334,5 +814,8 @@ extern "C" int pdmp3_hip_debug_profile_phases(pdmp3_hip_ctx* ctx, const int16_t*
                                               int n_frames, int16_t* d_pcm, int chunk_frames,
                                               unsigned long long* d_prof, void* stream) {
   if (!d_prof) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_debug_profile_phases: d_prof is NULL", hipSuccess);
-  return launch_decode(ctx, d_spectra, d_side, n_frames, nullptr, d_pcm, nullptr, chunk_frames, stream, d_prof);
+  DecodeLaunch q = bare_request(d_spectra, d_side, n_frames, nullptr, d_pcm, stream);
+  q.chunk_frames = chunk_frames;
+  q.prof = d_prof;
+  return launch_decode(ctx, q);
 }

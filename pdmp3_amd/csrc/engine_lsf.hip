@@ -1,5 +1,5 @@
 // engine_lsf.hip -- the LSF instantiations of the device Huffman stage's kernels (unpack_kernels.h), launched by
-// engine.hip submit_bits for windows of MPEG-2 LSF / MPEG-2.5 frames (pdmp3_hip_stream_set_lsf).  A translation unit of
+// engine.hip unpack_window_head / _carry (stream.hip submit_bits) for windows of MPEG-2 LSF / MPEG-2.5 frames (pdmp3_hip_stream_set_lsf).  A translation unit of
 // their own, so that the MPEG-1 kernels' code is what it is without them (unpack_kernels.h).
 #include <hip/hip_runtime.h>
 

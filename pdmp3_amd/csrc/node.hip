@@ -15,7 +15,7 @@
 #include <rccl/rccl.h>                    // types and prototypes only: every entry point is taken from dlsym
 #include "../../include/pdmp3_node.h"
 
-extern "C" void pdmp3_hip_set_error_(const char* text);
+#include "engine_internal.h"             // pdmp3_hip_set_error_ only: everything else here goes through the C-ABI
 
 namespace {
 

@@ -1,0 +1,554 @@
+// stream.hip -- pdmp3_hip_stream of include/pdmp3_hip.h: the host-buffer streaming helper (pinned staging,
+// hipMemcpyAsync both ways).  Host code only: buffers, events and the order of a slot's commands.  Which kernel runs on
+// which grid is engine.hip's business (engine_internal.h: launch_decode, unpack_window_head / _carry).
+#include <hip/hip_runtime.h>
+
+#include <stddef.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "engine_internal.h"
+#include "unpack_core.h"
+
+using namespace pdmp3;
+
+// One pdmp3_hip_stream = one decoder's carried state + up to kMaxSlots staging slots.  Each slot has its own
+// HIP stream (H2D -> k_decode -> D2H), so slot w+1's upload overlaps slot w's kernel and download over the
+// two PCIe directions; the kernels themselves are chained in submit order through `ev_state` because each one
+// starts from the synthesis state its predecessor left (and they share the stream's d_state_tmp).
+constexpr int kMaxSlots = 8;
+struct StreamSlot {
+  hipStream_t stream;
+  hipEvent_t done;
+  int16_t* h_spectra; pdmp3_gc_side* h_side; int16_t* h_pcm;     // pinned
+  int16_t* d_spectra; pdmp3_gc_side* d_side; int16_t* d_pcm;
+  int16_t* d_pair_sp; pdmp3_gc_side* d_pair_sd;                   // LSF launches: the regrouped records (allocated on first use, (max_frames + 1) / 2 frames)
+  // bitstream-level input (allocated on first use)
+  pdmp3_frame_bits* h_bits; uint8_t* h_res;                       // pinned
+  pdmp3_frame_bits* d_bits; uint8_t* d_res; GcRaw* d_raw; uint32_t* d_outc; unsigned* d_mcnt;
+  pdmp3_row_desc* h_desc; pdmp3_row_desc* d_desc; uint8_t* d_pool;   // compact bits input: pinned descriptors; the pool is h_res
+  uint8_t* h_in; uint8_t* d_in;   // the blocks h_desc | h_bits | h_res and d_desc | d_bits | d_pool point into
+  pdmp3_clip_piece* h_pieces; pdmp3_clip_piece* d_pieces; uint8_t* d_stage;   // clips (allocated on first use): the pieces' table, the stage
+  int busy;
+  int direct;                     // the latest record submit ran on the pinned host buffers themselves (submit_records)
+};
+struct pdmp3_hip_stream {
+  pdmp3_hip_ctx* ctx;
+  int max_frames, n_slots;
+  StreamSlot s[kMaxSlots];
+  hipEvent_t ev_state;       // recorded after the latest kernel + state copy
+  int have_state_ev;
+  float* d_state;
+  float* d_state_tmp;
+  float* d_state_prev;       // d_state as it was before the latest submit of decoded records (pdmp3_hip_stream_rewind)
+  uint16_t* d_sfstate;       // [2][256]: scalefactors / count1 carried from frame to frame (unpack_core.h), double-buffered
+  int sf_cur;
+  int have_bits;
+  int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
+  int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
+};
+
+extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
+  if (!hs) return;
+  (void)hipSetDevice(hs->ctx->device);
+  for (int i = 0; i < hs->n_slots; ++i) {
+    StreamSlot& t = hs->s[i];
+    if (t.stream) { (void)hipStreamSynchronize(t.stream); (void)hipStreamDestroy(t.stream); }
+    if (t.done) (void)hipEventDestroy(t.done);
+    (void)hipHostFree(t.h_spectra); (void)hipHostFree(t.h_side); (void)hipHostFree(t.h_pcm);
+    (void)hipFree(t.d_spectra); (void)hipFree(t.d_side); (void)hipFree(t.d_pcm); (void)hipFree(t.d_pair_sp); (void)hipFree(t.d_pair_sd);
+    (void)hipHostFree(t.h_in);
+    (void)hipFree(t.d_in); (void)hipFree(t.d_res); (void)hipFree(t.d_raw); (void)hipFree(t.d_outc); (void)hipFree(t.d_mcnt);
+    (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
+  }
+  (void)hipFree(hs->d_sfstate);
+  if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
+  (void)hipFree(hs->d_state);
+  chain_release(hs->ctx, hs);
+  (void)hipFree(hs->d_state_tmp);
+  (void)hipFree(hs->d_state_prev);
+  free(hs);
+}
+
+extern "C" int pdmp3_hip_stream_create_slots(pdmp3_hip_ctx* ctx, int max_frames, int n_slots, pdmp3_hip_stream** out) {
+  if (!ctx || !out || max_frames < 1 || n_slots < 1 || n_slots > kMaxSlots)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_create: bad argument", hipSuccess);
+  *out = nullptr;
+  HIP_TRY(hipSetDevice(ctx->device), "hipSetDevice");
+  pdmp3_hip_stream* hs = (pdmp3_hip_stream*)calloc(1, sizeof *hs);
+  if (!hs) return fail(PDMP3_HIP_ENOMEM, "calloc", hipSuccess);
+  hs->ctx = ctx;
+  hs->max_frames = max_frames;
+  hs->n_slots = n_slots;
+  const size_t n = (size_t)max_frames;
+#define HS_TRY(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) { pdmp3_hip_stream_destroy(hs); return fail(PDMP3_HIP_EDEVICE, what, e_); } } while (0)
+  for (int i = 0; i < n_slots; ++i) {
+    StreamSlot& t = hs->s[i];
+    HS_TRY(hipStreamCreateWithFlags(&t.stream, hipStreamNonBlocking), "hipStreamCreate");
+    HS_TRY(hipEventCreateWithFlags(&t.done, hipEventDisableTiming), "hipEventCreate");
+    HS_TRY(hipHostMalloc((void**)&t.h_spectra, n * PDMP3_FRAME_SPECTRA_BYTES, hipHostMallocDefault), "hipHostMalloc spectra");
+    HS_TRY(hipHostMalloc((void**)&t.h_side, n * PDMP3_FRAME_SIDE_BYTES, hipHostMallocDefault), "hipHostMalloc side");
+    HS_TRY(hipHostMalloc((void**)&t.h_pcm, n * PDMP3_FRAME_PCM_BYTES, hipHostMallocDefault), "hipHostMalloc pcm");
+    HS_TRY(hipMalloc((void**)&t.d_spectra, n * PDMP3_FRAME_SPECTRA_BYTES), "hipMalloc spectra");
+    HS_TRY(hipMalloc((void**)&t.d_side, n * PDMP3_FRAME_SIDE_BYTES), "hipMalloc side");
+    HS_TRY(hipMalloc((void**)&t.d_pcm, n * PDMP3_FRAME_PCM_BYTES), "hipMalloc pcm");
+  }
+  HS_TRY(hipEventCreateWithFlags(&hs->ev_state, hipEventDisableTiming), "hipEventCreate");
+  HS_TRY(hipMalloc((void**)&hs->d_state, pdmp3_hip_state_bytes()), "hipMalloc state");
+  HS_TRY(hipMalloc((void**)&hs->d_state_tmp, pdmp3_hip_state_bytes()), "hipMalloc state");
+  HS_TRY(hipMalloc((void**)&hs->d_state_prev, pdmp3_hip_state_bytes()), "hipMalloc state");
+  HS_TRY(hipMemsetAsync(hs->d_state, 0, pdmp3_hip_state_bytes(), hs->s[0].stream), "memset state");
+  HS_TRY(hipStreamSynchronize(hs->s[0].stream), "sync");
+#undef HS_TRY
+  *out = hs;
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_stream_create(pdmp3_hip_ctx* ctx, int max_frames, pdmp3_hip_stream** out) {
+  return pdmp3_hip_stream_create_slots(ctx, max_frames, 1, out);
+}
+
+static int drain_slots(pdmp3_hip_stream* hs) {
+  for (int i = 0; i < hs->n_slots; ++i) {
+    HIP_TRY(hipStreamSynchronize(hs->s[i].stream), "stream sync");
+    hs->s[i].busy = 0;
+  }
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_stream_reset(pdmp3_hip_stream* hs) {
+  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_reset: NULL", hipSuccess);
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  int rc = drain_slots(hs);
+  if (rc != PDMP3_HIP_OK) return rc;
+  hs->have_state_ev = 0;
+  HIP_TRY(hipMemsetAsync(hs->d_state, 0, pdmp3_hip_state_bytes(), hs->s[0].stream), "memset state");
+  if (hs->d_sfstate) HIP_TRY(hipMemsetAsync(hs->d_sfstate, 0, 2 * 256 * sizeof(uint16_t), hs->s[0].stream), "memset sfstate");
+  HIP_TRY(hipStreamSynchronize(hs->s[0].stream), "sync");
+  return PDMP3_HIP_OK;
+}
+
+#define SLOT_OK(hs, i) ((hs) && (i) >= 0 && (i) < (hs)->n_slots)
+extern "C" int pdmp3_hip_stream_slots(const pdmp3_hip_stream* hs) { return hs ? hs->n_slots : 0; }
+extern "C" int pdmp3_hip_stream_capacity(const pdmp3_hip_stream* hs) { return hs ? hs->max_frames : 0; }
+extern "C" int16_t* pdmp3_hip_stream_slot_spectra(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_spectra : nullptr; }
+extern "C" pdmp3_gc_side* pdmp3_hip_stream_slot_side(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_side : nullptr; }
+extern "C" const int16_t* pdmp3_hip_stream_slot_pcm(pdmp3_hip_stream* hs, int slot) { return SLOT_OK(hs, slot) ? hs->s[slot].h_pcm : nullptr; }
+extern "C" int16_t* pdmp3_hip_stream_spectra(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_spectra(hs, 0); }
+extern "C" pdmp3_gc_side* pdmp3_hip_stream_side(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_side(hs, 0); }
+extern "C" const int16_t* pdmp3_hip_stream_pcm(pdmp3_hip_stream* hs) { return pdmp3_hip_stream_slot_pcm(hs, 0); }
+
+// PCM of a batch to its destination: into the slot's pinned buffer, or -- when the caller hands over pinned host
+// memory (pdmp3_hip_host_alloc) or DEVICE memory of its own -- straight to where it is wanted, `row` bytes per frame (4608; 2304 = mono frames
+// packed densely out of their 4608-byte slots).
+static int download_pcm(StreamSlot& t, size_t n, void* host_dst, int row, bool lsf = false) {
+  if (lsf && host_dst) {
+    // LSF frames (pdmp3_hip_decode_lsf_frames): stereo frames lie back to back, 2304 bytes each; mono frames in pairs in the
+    // first half of a 4608-byte place
+    if (row == PDMP3_FRAME_PCM_BYTES / 2) {
+      HIP_TRY(hipMemcpyAsync(host_dst, t.d_pcm, n * (size_t)row, hipMemcpyDefault, t.stream), "pcm (direct, LSF)");
+    } else {
+      if (n / 2) HIP_TRY(hipMemcpy2DAsync(host_dst, 2304, t.d_pcm, PDMP3_FRAME_PCM_BYTES, 2304, n / 2, hipMemcpyDefault, t.stream), "pcm (direct, LSF mono)");
+      if (n & 1) HIP_TRY(hipMemcpyAsync((char*)host_dst + (n / 2) * 2304, (const char*)t.d_pcm + (n / 2) * PDMP3_FRAME_PCM_BYTES, 1152, hipMemcpyDefault, t.stream), "pcm (direct, LSF mono tail)");
+    }
+    return PDMP3_HIP_OK;
+  }
+  if (!host_dst) {
+    HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_pcm, n * PDMP3_FRAME_PCM_BYTES, hipMemcpyDeviceToHost, t.stream), "D2H pcm");
+  } else if (row == PDMP3_FRAME_PCM_BYTES) {
+    HIP_TRY(hipMemcpyAsync(host_dst, t.d_pcm, n * PDMP3_FRAME_PCM_BYTES, hipMemcpyDefault, t.stream), "pcm (direct)");
+  } else {
+    HIP_TRY(hipMemcpy2DAsync(host_dst, (size_t)row, t.d_pcm, PDMP3_FRAME_PCM_BYTES, (size_t)row, n, hipMemcpyDefault, t.stream),
+            "pcm (direct, packed)");
+  }
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_host_alloc(size_t bytes, void** out) {
+  if (!out) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_host_alloc: out is NULL", hipSuccess);
+  *out = nullptr;
+  HIP_TRY(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault), "hipHostMalloc");
+  return PDMP3_HIP_OK;
+}
+extern "C" void pdmp3_hip_host_free(void* p) { if (p) (void)hipHostFree(p); }
+// What the runtime knows of the first and the last byte of [p, p + bytes) (bytes <= 1: of the first, `last` = `first`);
+// false: it does not know one of them.  What makes a range good enough differs from caller to caller.
+struct PtrRange { hipPointerAttribute_t first, last; };
+static bool classify_range(const void* p, size_t bytes, PtrRange* r) {
+  if (hipPointerGetAttributes(&r->first, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+  r->last = r->first;
+  if (bytes > 1 && hipPointerGetAttributes(&r->last, (const char*)p + bytes - 1) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return true;
+}
+extern "C" int pdmp3_hip_host_is_pinned(const void* p, size_t bytes) {
+  PtrRange r;
+  if (!p || !classify_range(p, bytes, &r)) return 0;
+  if (r.first.type != hipMemoryTypeHost && r.first.type != hipMemoryTypeDevice) return 0;
+  if (r.last.type != r.first.type) return 0;
+  return r.first.type == hipMemoryTypeHost ? 1 : 2;
+}
+
+extern "C" int pdmp3_hip_copy_to_dest(void* dst, const void* src_host, size_t bytes) {
+  if (!bytes) return PDMP3_HIP_OK;
+  if (!dst || !src_host) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_copy_to_dest: NULL", hipSuccess);
+  HIP_TRY(hipMemcpy(dst, src_host, bytes, hipMemcpyDefault), "copy to destination");
+  return PDMP3_HIP_OK;
+}
+
+// PCM of the record-level submits (pdmp3_hip_stream_submit / _decode) as float from now on (on != 0) or int16 again.
+// Call with nothing in flight; the slots' PCM buffers are re-allocated.  The accessors return the same pointers'
+// new values, to be read as float: frame f at floats [f*2304, f*2304+2304).
+extern "C" int pdmp3_hip_stream_set_f32(pdmp3_hip_stream* hs, int on) {
+  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_set_f32: NULL", hipSuccess);
+  on = on ? 1 : 0;
+  if (hs->f32 == on) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  int rc = drain_slots(hs);
+  if (rc != PDMP3_HIP_OK) return rc;
+  const size_t bytes = (size_t)hs->max_frames * (on ? PDMP3_FRAME_PCM_F32_BYTES : PDMP3_FRAME_PCM_BYTES);
+  for (int i = 0; i < hs->n_slots; ++i) {
+    StreamSlot& t = hs->s[i];
+    (void)hipHostFree(t.h_pcm); t.h_pcm = nullptr;
+    (void)hipFree(t.d_pcm); t.d_pcm = nullptr;
+    HIP_TRY(hipHostMalloc((void**)&t.h_pcm, bytes, hipHostMallocDefault), "hipHostMalloc pcm");
+    HIP_TRY(hipMalloc((void**)&t.d_pcm, bytes), "hipMalloc pcm");
+  }
+  hs->f32 = on;
+  return PDMP3_HIP_OK;
+}
+
+static int submit_records(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row);
+// row_bytes of a _to destination: 4608 / 2304 for MPEG-1 frames, 2304 (stereo) / 1152 (mono) for LSF ones
+static bool row_bytes_ok(const pdmp3_hip_stream* hs, int row_bytes) {
+  if (hs && hs->lsf) return row_bytes == PDMP3_FRAME_PCM_BYTES / 2 || row_bytes == PDMP3_FRAME_PCM_BYTES / 4;
+  return row_bytes == PDMP3_FRAME_PCM_BYTES || row_bytes == PDMP3_FRAME_PCM_BYTES / 2;
+}
+extern "C" int pdmp3_hip_stream_submit(pdmp3_hip_stream* hs, int slot, int n_frames) {
+  return submit_records(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES);
+}
+extern "C" int pdmp3_hip_stream_submit_to(pdmp3_hip_stream* hs, int slot, int n_frames, void* pinned_dst, int row_bytes) {
+  if (pinned_dst && !row_bytes_ok(hs, row_bytes))
+    return fail(PDMP3_HIP_EINVAL, hs && hs->lsf ? "pdmp3_hip_stream_submit_to: row_bytes of LSF frames must be 2304 (stereo) or 1152 (mono)"
+                                                : "pdmp3_hip_stream_submit_to: row_bytes must be 4608 or 2304", hipSuccess);
+  return submit_records(hs, slot, n_frames, pinned_dst, row_bytes);
+}
+// the slot's buffers for an LSF launch's regrouped records (launch_decode pair_sp / pair_sd): allocated once, on the first LSF submit
+static int slot_pairs(pdmp3_hip_stream* hs, StreamSlot& t) {
+  if (!hs->lsf || t.d_pair_sp) return PDMP3_HIP_OK;
+  const size_t np = ((size_t)hs->max_frames + 1) / 2;
+  HIP_TRY(hipMalloc((void**)&t.d_pair_sp, np * PDMP3_FRAME_SPECTRA_BYTES), "hipMalloc LSF pairs");
+  if (hipMalloc((void**)&t.d_pair_sd, np * PDMP3_FRAME_SIDE_BYTES) != hipSuccess) { (void)hipFree(t.d_pair_sp); t.d_pair_sp = nullptr; return fail(PDMP3_HIP_ENOMEM, "hipMalloc LSF pairs", hipGetLastError()); }
+  return PDMP3_HIP_OK;
+}
+// The decode launch of n of the slot's records at sp / sd on the slot's HIP stream: PCM to `pcm` (float if the stream object
+// is set so), from the stream object's state to its state_tmp.
+static DecodeLaunch slot_request(pdmp3_hip_stream* hs, StreamSlot& t, const int16_t* sp, const pdmp3_gc_side* sd, int n, void* pcm, bool leave_state_in_tmp) {
+  DecodeLaunch q;
+  q.spectra = sp; q.side = sd; q.n_frames = n;
+  q.lsf = hs->lsf != 0; q.pair_sp = t.d_pair_sp; q.pair_sd = t.d_pair_sd;
+  q.pcm = pcm; q.f32 = hs->f32 != 0;
+  q.state = hs->d_state; q.state_tmp = hs->d_state_tmp; q.leave_state_in_tmp = leave_state_in_tmp;
+  q.stream = t.stream; q.owner = hs;
+  return q;
+}
+static int submit_records(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row) {
+  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit: slot still in flight (wait for it first)", hipSuccess);
+  if (n_frames == 0) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  { const int rcp = slot_pairs(hs, t); if (rcp != PDMP3_HIP_OK) return rcp; }
+  const size_t n = (size_t)n_frames;
+  if (hs->f32 && host_dst) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_to: not with float PCM", hipSuccess);
+  // Small batches (the streaming API's read-ahead: a handful of frames per call): no copies at all.  The kernel reads the
+  // records from the slot's PINNED host buffers and writes the PCM into pinned host memory itself -- a few KB each way,
+  // one PCIe round trip under the waves' first phase instead of two copy commands in front of the kernel and one behind
+  // it -- and the three state buffers rotate instead of being copied (previous <- current <- next).  Per batch: one
+  // launch, two event records, one wait.  (PDMP3_HIP_DIRECT_MAX: largest such batch in frames, 0 = never.)
+  t.direct = 0;
+  // (the kernel itself stores into host_dst on this path: only where it certainly can -- pinned host memory, or memory of
+  //  THIS device; registered / managed memory and another GPU's memory take the copy path, whose hipMemcpyAsync sorts it out)
+  bool dst_ok = true;
+  if (host_dst) {
+    PtrRange r;                                  // (its first byte)
+    dst_ok = classify_range(host_dst, 1, &r) &&
+             ((r.first.type == hipMemoryTypeHost && !r.first.isManaged) || (r.first.type == hipMemoryTypeDevice && r.first.device == hs->ctx->device));
+  }
+  if (n_frames <= hs->ctx->direct_max_frames && dst_ok && (!host_dst || row == PDMP3_FRAME_PCM_BYTES) && !(hs->lsf && host_dst)) {
+    // (a stream object with ONE slot -- the streaming API's -- has one HIP stream: its batches are in order anyway, and
+    //  its wait is for that stream: no events at all, each of which is a call here and a packet of its own on the queue)
+    const bool lone = hs->n_slots == 1;
+    if (!lone && hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
+    void* dst = host_dst ? host_dst : (void*)t.h_pcm;
+    int rc = launch_decode(hs->ctx, slot_request(hs, t, t.h_spectra, t.h_side, n_frames, dst, true));
+    if (rc != PDMP3_HIP_OK) return rc;
+    float* const was_prev = hs->d_state_prev;
+    hs->d_state_prev = hs->d_state;            // (what pdmp3_hip_stream_rewind goes back to)
+    hs->d_state = hs->d_state_tmp;             // the kernel left the new state here
+    hs->d_state_tmp = was_prev;
+    if (!lone) {
+      HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
+      hs->have_state_ev = 1;
+      HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
+    }
+    t.busy = 1;
+    t.direct = lone ? 2 : 1;                   // 2: pdmp3_hip_stream_wait synchronises the stream
+    return PDMP3_HIP_OK;
+  }
+  HIP_TRY(hipMemcpyAsync(t.d_spectra, t.h_spectra, n * PDMP3_FRAME_SPECTRA_BYTES, hipMemcpyHostToDevice, t.stream), "H2D spectra");
+  HIP_TRY(hipMemcpyAsync(t.d_side, t.h_side, n * PDMP3_FRAME_SIDE_BYTES, hipMemcpyHostToDevice, t.stream), "H2D side");
+  if (hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
+  HIP_TRY(hipMemcpyAsync(hs->d_state_prev, hs->d_state, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, t.stream), "keep the state");
+  int rc = launch_decode(hs->ctx, slot_request(hs, t, t.d_spectra, t.d_side, n_frames, t.d_pcm, false));
+  if (rc != PDMP3_HIP_OK) return rc;
+  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
+  hs->have_state_ev = 1;
+  if (hs->f32) HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_pcm, n * PDMP3_FRAME_PCM_F32_BYTES, hipMemcpyDeviceToHost, t.stream), "D2H pcm");
+  else rc = download_pcm(t, n, host_dst, row, hs->lsf != 0);
+  if (rc != PDMP3_HIP_OK) return rc;
+  HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
+  t.busy = 1;
+  return PDMP3_HIP_OK;
+}
+
+// The records of this stream object's following submits are LSF frames (on != 0: decoded like pdmp3_hip_decode_lsf_frames,
+// the PCM in its layout) or MPEG-1 frames again.  A setting of the host's for the next submit; the synthesis state is
+// the same block either way.
+extern "C" int pdmp3_hip_stream_set_lsf(pdmp3_hip_stream* hs, int on) {
+  if (!hs) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_set_lsf: NULL", hipSuccess);
+  hs->lsf = on != 0;
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_stream_wait(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot)) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_wait: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (!t.busy) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  if (t.direct == 2) HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  else HIP_TRY(hipEventSynchronize(t.done), "event sync");
+  t.busy = 0;
+  return PDMP3_HIP_OK;
+}
+
+// 1: pdmp3_hip_stream_wait(hs, slot) would return at once (nothing submitted, or the GPU is through with it); 0: not yet.
+// For the thread that would call the wait (the whole-stream decoder asks how much the GPU still has to do before it
+// decides how many frames the next window gets).
+extern "C" int pdmp3_hip_stream_done(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot)) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_done: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (!t.busy) return 1;
+  const hipError_t e = t.direct == 2 ? hipStreamQuery(t.stream) : hipEventQuery(t.done);
+  if (e == hipErrorNotReady) { (void)hipGetLastError(); return 0; }
+  return 1;                                     // (done, or an error the wait will report)
+}
+
+// Undo the slot's latest pdmp3_hip_stream_submit beyond its first keep_frames frames: the carried synthesis state
+// becomes what it was after frame keep_frames - 1 of that batch (the state before the batch, then the kept frames
+// again -- their records are still in the slot's device buffers).  Blocks until done.
+extern "C" int pdmp3_hip_stream_rewind(pdmp3_hip_stream* hs, int slot, int keep_frames) {
+  if (!SLOT_OK(hs, slot) || keep_frames < 0 || keep_frames > hs->max_frames)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_rewind: bad argument", hipSuccess);
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  StreamSlot& t = hs->s[slot];
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  t.busy = 0;
+  HIP_TRY(hipMemcpyAsync(hs->d_state, hs->d_state_prev, pdmp3_hip_state_bytes(), hipMemcpyDeviceToDevice, t.stream), "restore the state");
+  if (keep_frames) {
+    // (the records are where the submit took them from: the pinned host buffers if it ran on those)
+    const int16_t* sp = t.direct ? t.h_spectra : t.d_spectra;
+    const pdmp3_gc_side* sd = t.direct ? t.h_side : t.d_side;
+    const int rc = launch_decode(hs->ctx, slot_request(hs, t, sp, sd, keep_frames, t.d_pcm, false));
+    if (rc != PDMP3_HIP_OK) return rc;
+  }
+  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
+  hs->have_state_ev = 1;
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+
+// ---- bitstream-level input ------------------------------------------------
+static int ensure_bits(pdmp3_hip_stream* hs) {
+  if (hs->have_bits) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  const size_t n = (size_t)hs->max_frames;
+  for (int i = 0; i < hs->n_slots; ++i) {
+    StreamSlot& t = hs->s[i];
+    // descriptors | side info | rows or pool: ONE pinned block and one device block with the same layout, so that the
+    // compact input of a window goes up in one copy (a hipMemcpyAsync call costs the submitting thread 20-40 us here)
+    const size_t desc_bytes = n * sizeof(pdmp3_row_desc), bits_bytes = n * sizeof(pdmp3_frame_bits);
+    const size_t pool_cap = n * PDMP3_RESERVOIR_BYTES + PDMP3_POOL_SLACK_BYTES + 16;
+    HIP_TRY(hipHostMalloc((void**)&t.h_in, desc_bytes + bits_bytes + pool_cap, hipHostMallocDefault), "hipHostMalloc window input");
+    HIP_TRY(hipMalloc((void**)&t.d_in, desc_bytes + bits_bytes + pool_cap), "hipMalloc window input");
+    t.h_desc = reinterpret_cast<pdmp3_row_desc*>(t.h_in);
+    t.h_bits = reinterpret_cast<pdmp3_frame_bits*>(t.h_in + desc_bytes);
+    t.h_res = t.h_in + desc_bytes + bits_bytes;
+    t.d_desc = reinterpret_cast<pdmp3_row_desc*>(t.d_in);
+    t.d_bits = reinterpret_cast<pdmp3_frame_bits*>(t.d_in + desc_bytes);
+    t.d_pool = t.d_in + desc_bytes + bits_bytes;
+    HIP_TRY(hipMalloc((void**)&t.d_res, n * PDMP3_RESERVOIR_BYTES + 16), "hipMalloc reservoir");
+    HIP_TRY(hipMalloc((void**)&t.d_raw, n * 4 * sizeof(GcRaw)), "hipMalloc raw");
+    // rows of outcomes: one per block of kMergeBlk frames, then one per super-block; the super-blocks' counters (zero between launches)
+    const size_t mblk = (n + kMergeBlk - 1) / kMergeBlk, msup = (mblk + kMergeSuper - 1) / kMergeSuper;
+    HIP_TRY(hipMalloc((void**)&t.d_outc, (mblk + msup) * kMergeLanes * sizeof(uint32_t)), "hipMalloc merge outcomes");
+    HIP_TRY(hipMalloc((void**)&t.d_mcnt, (msup + 1) * sizeof(unsigned)), "hipMalloc merge counters");
+    HIP_TRY(hipMemset(t.d_mcnt, 0, (msup + 1) * sizeof(unsigned)), "memset merge counters");
+  }
+  HIP_TRY(hipMalloc((void**)&hs->d_sfstate, 2 * 256 * sizeof(uint16_t)), "hipMalloc sfstate");
+  HIP_TRY(hipMemset(hs->d_sfstate, 0, 2 * 256 * sizeof(uint16_t)), "memset sfstate");
+  // hipMemset returns before the device has run it, and the slots' streams are non-blocking: they do not wait for the null
+  // stream.  Without this wait the zeroing of the scalefactor state could land AFTER the first window's k_merge_apply had
+  // written it -- the second window of a fresh decoder then started from zeros (round 6: one whole-stream decode in ~2000
+  // with fresh decoders differed by 1-3 LSB in frames 17-18; tools/ubench/malloc_async_probe.cpp mode M shows the mechanism)
+  HIP_TRY(hipDeviceSynchronize(), "device sync after the memsets");
+  hs->have_bits = 1;
+  return PDMP3_HIP_OK;
+}
+
+extern "C" pdmp3_frame_bits* pdmp3_hip_stream_slot_bits(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
+  return hs->s[slot].h_bits;
+}
+extern "C" uint8_t* pdmp3_hip_stream_slot_reservoir(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
+  return hs->s[slot].h_res;
+}
+
+extern "C" pdmp3_row_desc* pdmp3_hip_stream_slot_rowdesc(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot) || ensure_bits(hs) != PDMP3_HIP_OK) return nullptr;
+  return hs->s[slot].h_desc;
+}
+extern "C" uint8_t* pdmp3_hip_stream_slot_pool(pdmp3_hip_stream* hs, int slot) { return pdmp3_hip_stream_slot_reservoir(hs, slot); }
+extern "C" size_t pdmp3_hip_stream_pool_bytes(const pdmp3_hip_stream* hs) { return hs ? (size_t)hs->max_frames * PDMP3_RESERVOIR_BYTES + PDMP3_POOL_SLACK_BYTES : 0; }
+
+static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes = 0, int clip_pieces = -1,
+                       size_t stage_bytes = 0);
+extern "C" int pdmp3_hip_stream_submit_pool_to(pdmp3_hip_stream* hs, int slot, int n_frames, size_t pool_bytes, void* pinned_dst, int row_bytes) {
+  if (pinned_dst && !row_bytes_ok(hs, row_bytes))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_pool_to: row_bytes must be 4608 or 2304 (LSF: 2304 or 1152)", hipSuccess);
+  if (!pool_bytes || !hs || pool_bytes > pdmp3_hip_stream_pool_bytes(hs))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_pool_to: bad pool size", hipSuccess);
+  return submit_bits(hs, slot, n_frames, pinned_dst, row_bytes, pool_bytes);
+}
+extern "C" int pdmp3_hip_stream_submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames) {
+  return submit_bits(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES);
+}
+extern "C" int pdmp3_hip_stream_submit_bits_to(pdmp3_hip_stream* hs, int slot, int n_frames, void* pinned_dst, int row_bytes) {
+  if (pinned_dst && !row_bytes_ok(hs, row_bytes))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_to: row_bytes must be 4608 or 2304 (LSF: 2304 or 1152)", hipSuccess);
+  return submit_bits(hs, slot, n_frames, pinned_dst, row_bytes);
+}
+static int ensure_clip(pdmp3_hip_stream* hs, StreamSlot& t) {
+  if (t.d_stage) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  const size_t n = (size_t)hs->max_frames;
+  HIP_TRY(hipHostMalloc((void**)&t.h_pieces, n * sizeof(pdmp3_clip_piece), hipHostMallocDefault), "hipHostMalloc clip pieces");
+  HIP_TRY(hipMalloc((void**)&t.d_pieces, n * sizeof(pdmp3_clip_piece)), "hipMalloc clip pieces");
+  HIP_TRY(hipMalloc((void**)&t.d_stage, n * PDMP3_FRAME_PCM_BYTES), "hipMalloc clip stage");
+  return PDMP3_HIP_OK;
+}
+extern "C" void* pdmp3_hip_stream_slot_clip_stage(pdmp3_hip_stream* hs, int slot) {
+  if (!SLOT_OK(hs, slot) || ensure_clip(hs, hs->s[slot]) != PDMP3_HIP_OK) return nullptr;
+  return hs->s[slot].d_stage;
+}
+extern "C" int pdmp3_hip_stream_submit_bits_clips(pdmp3_hip_stream* hs, int slot, int n_frames, const pdmp3_clip_piece* pieces, int n_pieces,
+                                                  size_t stage_bytes) {
+  if (!SLOT_OK(hs, slot) || n_pieces < 0 || n_pieces > hs->max_frames || (n_pieces && !pieces) ||
+      stage_bytes > (size_t)hs->max_frames * PDMP3_FRAME_PCM_BYTES || hs->f32)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits_clips: slot still in flight (wait for it first)", hipSuccess);
+  const int rc = ensure_clip(hs, t);
+  if (rc != PDMP3_HIP_OK) return rc;
+  if (n_pieces) memcpy(t.h_pieces, pieces, (size_t)n_pieces * sizeof *pieces);
+  return submit_bits(hs, slot, n_frames, nullptr, PDMP3_FRAME_PCM_BYTES, 0, n_pieces, stage_bytes);
+}
+static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_dst, int row, size_t pool_bytes, int clip_pieces,
+                       size_t stage_bytes) {
+  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_submit_bits: slot still in flight (wait for it first)", hipSuccess);
+  if (n_frames == 0) return PDMP3_HIP_OK;
+  int rc = ensure_bits(hs);
+  if (rc != PDMP3_HIP_OK) return rc;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  const bool lsf = hs->lsf != 0;
+  if (lsf) { rc = slot_pairs(hs, t); if (rc != PDMP3_HIP_OK) return rc; }   // (the records regrouped for the transforms: launch_decode)
+  const size_t n = (size_t)n_frames;
+  t.direct = 0;               // (the records of this submit are the device's: a rewind replays d_spectra, never h_spectra)
+  if (pool_bytes) {           // compact input: descriptors, side info and pool up in one copy, rows rebuilt on the device
+    // (Tried: k_rows reading descriptors, side info and pool straight from the pinned host block, no copy at all -- the
+    //  kernel then runs at PCIe speed and the pipeline, which is bound by the kernels of a window, lost 20 %.)
+    const size_t head = (size_t)hs->max_frames * (sizeof(pdmp3_row_desc) + sizeof(pdmp3_frame_bits));
+    HIP_TRY(hipMemcpyAsync(t.d_in, t.h_in, head + pool_bytes, hipMemcpyHostToDevice, t.stream), "H2D window input");
+  } else {
+    HIP_TRY(hipMemcpyAsync(t.d_bits, t.h_bits, n * sizeof(pdmp3_frame_bits), hipMemcpyHostToDevice, t.stream), "H2D bits");
+    HIP_TRY(hipMemcpyAsync(t.d_res, t.h_res, n * PDMP3_RESERVOIR_BYTES, hipMemcpyHostToDevice, t.stream), "H2D reservoir");
+  }
+  UnpackWindow w;
+  w.stream = t.stream; w.n_frames = n_frames; w.lsf = lsf;
+  w.desc = pool_bytes ? t.d_desc : nullptr; w.pool = t.d_pool;
+  w.bits = t.d_bits; w.res = t.d_res;
+  w.spectra = t.d_spectra; w.raw = t.d_raw;
+  w.outc = t.d_outc; w.mcnt = t.d_mcnt;
+  w.sf_in = hs->d_sfstate + 256 * hs->sf_cur; w.sf_out = hs->d_sfstate + 256 * (hs->sf_cur ^ 1);
+  w.side = t.d_side;
+  // what the window's frames do to the values that survive frames needs nothing of the batch before ...
+  rc = unpack_window_head(hs->ctx, w);
+  if (rc != PDMP3_HIP_OK) return rc;
+  // ... everything from here on continues it (scalefactor / count1 carry, synthesis state)
+  if (hs->have_state_ev) HIP_TRY(hipStreamWaitEvent(t.stream, hs->ev_state, 0), "wait for the previous batch's state");
+  rc = unpack_window_carry(w);
+  if (rc != PDMP3_HIP_OK) return rc;
+  hs->sf_cur ^= 1;
+  // A destination in THIS device's memory that takes whole 4608-byte rows: the kernel stores the PCM there itself (the
+  // copy from the slot's buffer was 11 us of a window's 235 -- 75 MB through HBM for 8192 frames; end to end, A/B on one
+  // box, four runs each: 26.5 against 25.9 M frames/s).  Pinned host memory
+  // stays with the copy command: stores over PCIe from 256 CUs are slower than the DMA engine.
+  // (LSF windows: their PCM layout is pdmp3_hip_decode_lsf_frames', which download_pcm sorts out)
+  int16_t* pcm_out = t.d_pcm;
+  if (!lsf && host_dst && row == PDMP3_FRAME_PCM_BYTES && !((uintptr_t)host_dst & 15)) {
+    PtrRange r;                                  // (its first and its last byte)
+    if (classify_range(host_dst, n * PDMP3_FRAME_PCM_BYTES, &r) && r.first.type == hipMemoryTypeDevice && r.last.type == hipMemoryTypeDevice &&
+        r.first.device == hs->ctx->device && r.last.device == hs->ctx->device && !r.first.isManaged)
+      pcm_out = (int16_t*)host_dst;
+  }
+  DecodeLaunch q = slot_request(hs, t, t.d_spectra, t.d_side, n_frames, pcm_out, true);
+  q.f32 = false;              // (a window of bits comes out as int16 whatever pdmp3_hip_stream_set_f32 says)
+  rc = launch_decode(hs->ctx, q);
+  if (rc != PDMP3_HIP_OK) return rc;
+  { float* x = hs->d_state; hs->d_state = hs->d_state_tmp; hs->d_state_tmp = x; }   // (the new state is where the kernel left it)
+  HIP_TRY(hipEventRecord(hs->ev_state, t.stream), "record state event");
+  hs->have_state_ev = 1;
+  if (clip_pieces >= 0) {     // clips: the PCM stays in d_pcm, k_clip_pack places the kept frames (clip.hip)
+    if (clip_pieces) {
+      HIP_TRY(hipMemcpyAsync(t.d_pieces, t.h_pieces, (size_t)clip_pieces * sizeof(pdmp3_clip_piece), hipMemcpyHostToDevice, t.stream), "H2D clip pieces");
+      HIP_TRY(pdmp3_launch_clip_pack(t.stream, t.d_pieces, clip_pieces, t.d_pcm), "launch k_clip_pack");
+    }
+    if (stage_bytes) HIP_TRY(hipMemcpyAsync(t.h_pcm, t.d_stage, stage_bytes, hipMemcpyDeviceToHost, t.stream), "D2H clip stage");
+  } else if (pcm_out == t.d_pcm) {
+    rc = download_pcm(t, n, host_dst, row, lsf);
+    if (rc != PDMP3_HIP_OK) return rc;
+  }
+  HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
+  t.busy = 1;
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side) {
+  if (!SLOT_OK(hs, slot) || n_frames < 0 || n_frames > hs->max_frames || !spectra || !side)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_stream_fetch_records: bad argument", hipSuccess);
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  HIP_TRY(hipStreamSynchronize(hs->s[slot].stream), "stream sync");
+  HIP_TRY(hipMemcpy(spectra, hs->s[slot].d_spectra, (size_t)n_frames * PDMP3_FRAME_SPECTRA_BYTES, hipMemcpyDeviceToHost), "D2H spectra");
+  HIP_TRY(hipMemcpy(side, hs->s[slot].d_side, (size_t)n_frames * PDMP3_FRAME_SIDE_BYTES, hipMemcpyDeviceToHost), "D2H side");
+  return PDMP3_HIP_OK;
+}
+
+extern "C" int pdmp3_hip_stream_decode(pdmp3_hip_stream* hs, int n_frames) {
+  int rc = pdmp3_hip_stream_submit(hs, 0, n_frames);
+  if (rc != PDMP3_HIP_OK) return rc;
+  return pdmp3_hip_stream_wait(hs, 0);
+}

@@ -1,6 +1,6 @@
 // unpack_kernels.h -- the device Huffman stage's kernels that come in an MPEG-1 and an LSF form (unpack_core.h on the GPU):
 // k_unpack and k_merge_apply (k_rows and k_merge_outcome, which do not care, are in engine.hip).  Included by engine.hip,
-// which launches the MPEG-1 forms, and by engine_lsf.hip, which holds the LSF
+// which launches the MPEG-1 forms (unpack_window_head / _carry), and by engine_lsf.hip, which holds the LSF
 // instantiations of k_unpack / k_merge_apply in a module of their own: compiled into one module with the MPEG-1 ones they
 // changed the MPEG-1 kernels' code (out-of-line helpers that two kernels share lose the constants of their one caller).
 #pragma once
