@@ -242,6 +242,63 @@ long long pdmp3_amd_bulk_parse_range(pdmp3_amd_bulk* b, const unsigned char* mp3
                                      long long first_frame, long long n_frames, int lookback, int16_t* spectra, pdmp3_gc_side* side,
                                      size_t cap_frames, long long* decoded_from);
 
+/* ---- Clips by sample position as float batches ----
+ * What a loader feeds to a model: K clips addressed in samples, as one dense planar float32 batch [K][C][T] at ONE sampling
+ * frequency and channel count, made on the GPU from the clips' int16 PCM while it is still in device memory.  Every value is
+ * defined from the whole-stream int16 output above; nothing any entry point above returns changes.
+ *
+ * Time line.  A stream has ONE FORMAT when all its frames have the same sampling frequency and the same samples per frame
+ * spf (1152 MPEG-1, 576 LSF); channel counts may change.  It then has N = frames * spf samples per channel, sample n lies in
+ * frame n / spf, and x_c[n] is the whole-stream int16 output / 32768 for 0 <= n < N and 0 outside; a mono frame inside a stereo
+ * stream gives its samples to both channels.  A stream whose frames differ in rate or spf has no time line.
+ * Channels.  Cs = 2 if any frame is stereo, else 1.  Asked for C = 1 from Cs = 2: x[n] = (l + r) / 65536 with l, r the int16
+ * values (exact in binary32); C = 2 from Cs = 1: both channels equal.  The downmix comes before the filter.
+ * Rate.  in = the stream's, out = the requested one, g = gcd, M = in / g, L = out / g, Z = width, and
+ *     u(n, j) = rolloff * (n L - j M) / max(L, M)
+ *     h(n, j) = rolloff * min(L, M) / M * sinc(u) * cos^2(pi u / (2 Z))   for |u| < Z, else 0;   sinc(u) = sin(pi u) / (pi u)
+ *     y_c[j]  = sum over n of h(n, j) * x_c[n]          for 0 <= j < J = ceil(N L / M), 0.0 from J on
+ * (a Hann-windowed sinc with its cut-off at rolloff * min(in, out) / 2: torchaudio's sinc_interp_hann with the same two
+ * parameters).  h depends on j through (j M) mod L alone: the table of L rows is computed on the host in binary64, rounded
+ * once to binary32 and kept by the decoder per (in, out, Z, rolloff); the GPU multiplies and adds in binary32.  out == in: no
+ * filter at all, y_c[j] = x_c[j] exactly. */
+/* 1: the stream has one format (*rate, *channels = Cs, *frame_samples = spf), 0: its frames differ in rate or spf (only
+ * *channels is set), -1: a replay index or NULL.  An index without frames has one format with rate 0.  Pointers may be NULL. */
+int pdmp3_amd_index_format(const pdmp3_amd_index* ix, long* rate, int* channels, int* frame_samples);
+/* N = frames * spf of a stream with one format, else -1 */
+long long pdmp3_amd_index_samples(const pdmp3_amd_index* ix);
+
+/* Planning, plain C (host tests reach both).  The input samples [*first_in, *first_in + *n_in) that output samples [start,
+ * start + n) at rate `out` read from a stream at rate `in`, before any clamping to [0, N): every n with |u(n, j)| < Z for
+ * one of those j, and at most one sample more on either side.  width 0 = 6 (1 .. 64), rolloff 0 = 0.99 (in (0, 1]); out == in:
+ * [start, start + n).  0, or -1 on a bad argument. */
+int pdmp3_amd_audio_span(long in, long out, int width, double rolloff, long long start, long long n, long long* first_in, long long* n_in);
+/* The filter table of the pair: *rows = L rows of *taps coefficients, row r = (j M) mod L, whose tap k multiplies input sample
+ * floor(j M / L) + *first_tap + k.  Returns the coefficient count rows * taps and writes them to table[0 .. min(that, cap));
+ * -1 on a bad argument, out == in (no table) or a table of more than 2^22 coefficients. */
+long long pdmp3_amd_audio_table(long in, long out, int width, double rolloff, float* table, size_t cap, long* rows, int* taps, int* first_tap);
+
+/* A clip of the batch: output samples [start, start + n_samples) of the stream at the requested rate.  dst: device memory of
+ * the decoder's GPU (written by the kernel itself) or host memory (kernel into a device stage, copied out); channel c's
+ * n_samples floats at dst + c * chan_stride. */
+typedef struct {
+  const unsigned char* mp3; size_t n; const pdmp3_amd_index* index;
+  long long start; float* dst; size_t chan_stride;
+} pdmp3_amd_audio_clip;
+/* 0 = default: the stream's own rate, the clips' common Cs (their Cs must agree then), width 6, rolloff 0.99 */
+typedef struct { long rate; int channels; long long n_samples; int width; double rolloff; } pdmp3_amd_audio_spec;
+#define PDMP3_BULK_MIXED_FORMAT (-3)
+/* Row k receives y_c[start + t] for 0 <= t < n_samples, 0.0 where start + t >= J (the batch is dense), and valid[k] =
+ * clamp(J - start, 0, n_samples).  The frames a clip's input span touches go through the clip path above unchanged -- halo
+ * rule, snapshots, windows, k_clip_pack -- into a device stage the decoder owns; k_clip_audio then writes the rows.
+ * Synchronous; device-Huffman decoders only; the decoder's PDMP3_ISO_LSF must match every index.  Returns 0; -1 on a bad
+ * argument (start < 0, n_samples < 0, width outside 1 .. 64, rolloff outside (0, 1], channels 0 with clips whose Cs differ, a
+ * filter table of more than 2^22 coefficients) and as pdmp3_amd_bulk_decode_clips.  A clip whose index is a replay: valid[k]
+ * = PDMP3_BULK_REPLAY and the call returns that; one whose stream has no one format: valid[k] = PDMP3_BULK_MIXED_FORMAT and the
+ * call returns that unless a replay does; nothing of such a row is written and the other clips are decoded.
+ * pdmp3_amd_bulk_clip_stats counts these clips' frames and halos too. */
+int pdmp3_amd_bulk_decode_clips_audio(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips,
+                                      const pdmp3_amd_audio_spec* spec, long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -454,6 +454,46 @@ int pdmp3_hip_stream_submit_bits_clips(pdmp3_hip_stream* hs, int slot, int n_fra
 /* device memory of max_frames * 4608 bytes per slot (allocated on first use), NULL on failure */
 void* pdmp3_hip_stream_slot_clip_stage(pdmp3_hip_stream* hs, int slot);
 
+/* Clips as float batches (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_audio).  The clips' int16 PCM
+ * is placed by clip windows (above) in a device stage the stream object owns; k_clip_audio (resample.hip) then writes every
+ * clip's row of the batch: planar float32, channels made (downmix / doubling), resampled by the clip's filter table or
+ * copied at the stream's own rate, zeros behind the stream's end.
+ * One clip of the launch: its staged frames are [frame0, frame0 + n_frames) of its stream, frame f's PCM at
+ * src + (frames[frame_tab + f - frame0] >> 1) * 1152 and mono when that entry's bit 0 is set (a stereo frame: spf samples
+ * of L, R interleaved; a mono one: spf samples).  Output sample t of channel c, dst[c * chan_stride + t], is sample
+ * start + t of the stream at the new rate: j M = q L + r picks row r of the clip's table (taps coefficients at
+ * tables[table + r * taps]), whose tap k multiplies input sample q + d0 + k (0 outside [0, n_in)); M == L: input sample j
+ * itself; j >= n_out: 0.0.  flags: where the workgroups keep the input span and the table (the host's choice by size). */
+#define PDMP3_AUDIO_TILE 1024                /* output samples (per channel) of a workgroup                */
+#define PDMP3_AUDIO_LDS_BYTES (64u * 1024u) /* LDS a workgroup may take: span_cap floats per channel, then the table */
+#define PDMP3_AUDIO_LDS_X 1u                /* the tile's input span is converted into LDS first */
+#define PDMP3_AUDIO_LDS_TABLE 2u            /* ... and the whole table lies behind it */
+typedef struct pdmp3_audio_desc {
+  uint64_t src;                             /* device address of the clip's staged PCM (16-byte aligned)  */
+  uint64_t dst;                             /* device address of channel 0's first float                  */
+  uint64_t chan_stride;                     /* floats between the channels of the row                     */
+  int64_t start;                            /* the row's first output sample                              */
+  int64_t n_in, n_out;                      /* N and J: samples of the stream at its rate, at the new one */
+  int64_t frame0;
+  uint32_t n_frames, frame_tab;
+  uint32_t M, L;                            /* in / gcd, out / gcd                                        */
+  uint32_t spf;                             /* samples per frame and channel: 1152 or 576                 */
+  uint32_t table;                           /* floats in front of the clip's table in `tables`            */
+  int32_t taps, d0;
+  uint32_t flags, span_cap;                 /* PDMP3_AUDIO_LDS_*; input samples a tile reads at most      */
+} pdmp3_audio_desc;                         /* 96 bytes */
+/* The stream object's audio stages: device memory (hipMalloc, kept and grown on demand; call with nothing of the audio
+ * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory.  NULL on
+ * failure. */
+void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes);
+/* Uploads the launch's tables (descs, frames, tables: host memory) and runs k_clip_audio on the slot's HIP stream, behind
+ * whatever the slot ran last (the last clip window's k_clip_pack); n_samples output samples per row, channels = 1 or 2.
+ * Blocks until the rows are written. */
+int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_audio_desc* descs, int n_clips, const uint32_t* frames,
+                         size_t n_frames, const float* tables, size_t n_coef, long long n_samples, int channels);
+/* plain copy of `bytes` from device memory (an audio stage) to host memory; blocks until it is done */
+int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -17,7 +17,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_scan_buffer", "pdmp3_amd_scan_buffer_iso", "pdmp3_amd_corpus_assign", "pdmp3_amd_corpus_decode", "pdmp3_amd_bulk_decode", "pdmp3_amd_bulk_decode_async", "pdmp3_amd_bulk_wait", "pdmp3_amd_bulk_new_parse_only", "pdmp3_amd_bulk_parse",
                 "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_new_parse_bits_lsf", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav",
                 "pdmp3_amd_index_new", "pdmp3_amd_index_new_spacing", "pdmp3_amd_index_delete", "pdmp3_amd_index_frames", "pdmp3_amd_index_pcm_offset",
-                "pdmp3_amd_index_pcm_offsets", "pdmp3_amd_index_split", "pdmp3_amd_bulk_decode_clips", "pdmp3_amd_bulk_clip_stats", "pdmp3_amd_bulk_parse_range"]
+                "pdmp3_amd_index_pcm_offsets", "pdmp3_amd_index_split", "pdmp3_amd_bulk_decode_clips", "pdmp3_amd_bulk_clip_stats", "pdmp3_amd_bulk_parse_range",
+                "pdmp3_amd_index_format", "pdmp3_amd_index_samples", "pdmp3_amd_audio_span", "pdmp3_amd_audio_table", "pdmp3_amd_bulk_decode_clips_audio"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -111,6 +112,15 @@ def load_library():
         lib.pdmp3_amd_bulk_clip_stats.restype = None
         lib.pdmp3_amd_bulk_parse_range.argtypes = [vp, vp, C.c_size_t, vp, ll, ll, C.c_int, vp, vp, C.c_size_t, C.POINTER(ll)]
         lib.pdmp3_amd_bulk_parse_range.restype = ll
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_audio"):    # (clips as float batches: absent from older builds)
+        ll = C.c_longlong
+        lib.pdmp3_amd_index_format.argtypes = [vp, C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_index_samples.argtypes = [vp]
+        lib.pdmp3_amd_index_samples.restype = ll
+        lib.pdmp3_amd_audio_span.argtypes = [C.c_long, C.c_long, C.c_int, C.c_double, ll, ll, C.POINTER(ll), C.POINTER(ll)]
+        lib.pdmp3_amd_audio_table.argtypes = [C.c_long, C.c_long, C.c_int, C.c_double, vp, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_audio_table.restype = ll
+        lib.pdmp3_amd_bulk_decode_clips_audio.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -251,6 +261,11 @@ class RingReplay(RuntimeError):
     """PDMP3_BULK_REPLAY: the reference would replay its input ring on this stream (include/pdmp3_bulk.h)"""
 
 
+class MixedFormat(RuntimeError):
+    """PDMP3_BULK_MIXED_FORMAT: a clip's stream changes its sampling frequency or samples per frame: it has no time line in
+    samples (include/pdmp3_bulk.h).  .valid / .out: what BulkDecoder.decode_clips_audio would have returned"""
+
+
 def scan_buffer(mp3, iso=0):
     """(pcm_bytes, frames) the CLI driver would produce for this stream (include/pdmp3_bulk.h); iso: the decoder's switches
     (PDMP3_ISO_LSF changes what counts as a frame)"""
@@ -266,6 +281,29 @@ def scan_buffer(mp3, iso=0):
 
 
 PDMP3_BULK_REPLAY = -2
+PDMP3_BULK_MIXED_FORMAT = -3
+
+
+def audio_span(rate_in, rate_out, start, n, width=0, rolloff=0.0):
+    """pdmp3_amd_audio_span -> (first input sample, count) that output samples [start, start + n) read, unclamped"""
+    lib = load_library()
+    a, c = C.c_longlong(0), C.c_longlong(0)
+    if lib.pdmp3_amd_audio_span(int(rate_in), int(rate_out), int(width), float(rolloff), int(start), int(n), C.byref(a), C.byref(c)) != 0:
+        raise ValueError("pdmp3_amd_audio_span: bad argument")
+    return a.value, c.value
+
+
+def audio_table(rate_in, rate_out, width=0, rolloff=0.0):
+    """pdmp3_amd_audio_table -> (float32 numpy [rows, taps], first tap): row (j M) mod L, tap k on input sample j M // L + first
+    tap + k"""
+    lib = load_library()
+    rows, taps, d0 = C.c_long(0), C.c_int(0), C.c_int(0)
+    n = lib.pdmp3_amd_audio_table(int(rate_in), int(rate_out), int(width), float(rolloff), None, 0, C.byref(rows), C.byref(taps), C.byref(d0))
+    if n < 0:
+        raise ValueError("pdmp3_amd_audio_table: bad argument, equal rates or a table of more than 2^22 coefficients")
+    t = np.empty((rows.value, taps.value), dtype=np.float32)
+    lib.pdmp3_amd_audio_table(int(rate_in), int(rate_out), int(width), float(rolloff), t.ctypes.data_as(C.c_void_p), t.size, None, None, None)
+    return t, d0.value
 
 
 class StreamIndex:
@@ -287,6 +325,11 @@ class StreamIndex:
         self.frames = self.lib.pdmp3_amd_index_frames(self.h)
         self.replay = self.frames == PDMP3_BULK_REPLAY
         self.split = bool(self.lib.pdmp3_amd_index_split(self.h))
+        # the stream's format (clips by sample position): one_format False = its frames differ in rate or samples per frame
+        rate, ch, spf = C.c_long(0), C.c_int(0), C.c_int(0)
+        self.one_format = self.lib.pdmp3_amd_index_format(self.h, C.byref(rate), C.byref(ch), C.byref(spf)) == 1
+        self.rate, self.channels, self.frame_samples = rate.value, ch.value, spf.value
+        self.samples = self.lib.pdmp3_amd_index_samples(self.h)
         self.pcm_offsets = None
         if not self.replay:
             self.pcm_offsets = np.empty(self.frames + 1, dtype=np.int64)
@@ -321,6 +364,15 @@ def _int16_buffer(o, ndim):
 class _Clip(C.Structure):                          # include/pdmp3_bulk.h pdmp3_amd_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("first_frame", C.c_longlong),
                 ("n_frames", C.c_longlong), ("dst", C.c_void_p), ("dst_cap", C.c_size_t)]
+
+
+class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
+    _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
+                ("chan_stride", C.c_size_t)]
+
+
+class _AudioSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("n_samples", C.c_longlong), ("width", C.c_int), ("rolloff", C.c_double)]
 
 
 class BulkDecoder:
@@ -477,6 +529,53 @@ class BulkDecoder:
         got = self.decode_clips([(mp3, index, first, count)], out)
         assert got[0] == nbytes, (got[0], nbytes)
         return out[0, :nbytes // 2]
+
+    def decode_clips_audio(self, clips, n_samples, sample_rate=0, channels=0, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_audio: clips = sequence of (mp3, StreamIndex, first sample at the new rate) -> (out, valid):
+        out float32 [K, C, n_samples], planar, every clip at sample_rate (0: each stream's own) with `channels` channels (0: the
+        clips' common count), resampled on the GPU by a Hann-windowed sinc (width zero crossings, default 6; rolloff, default
+        0.99: torchaudio's sinc_interp_hann), zeros behind a stream's end; valid[k] = samples of row k that lie inside the
+        stream.  out: a float32 torch tensor on the decoder's device (made when not given; its rows and channels may be
+        strided, the samples not) or a numpy array.  Synchronous.  RingReplay / MixedFormat (with .out and .valid: those
+        clips' rows are not written, valid is PDMP3_BULK_REPLAY / PDMP3_BULK_MIXED_FORMAT there) when a clip's stream has no
+        finite output / no one format; the other clips are decoded all the same."""
+        k, t = len(clips), int(n_samples)
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_audio: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, t), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        if hasattr(out, "data_ptr"):
+            assert out.dim() == 3 and tuple(out.shape[1:]) == (c, t) and out.shape[0] >= k and out.element_size() == 4 and (t <= 1 or out.stride(2) == 1)
+            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
+        else:
+            assert out.ndim == 3 and out.shape[1:] == (c, t) and out.shape[0] >= k and out.dtype == np.float32 and (t <= 1 or out.strides[2] == 4)
+            assert out.strides[1] % 4 == 0
+            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        spec = _AudioSpec(int(sample_rate), int(channels), t, int(width), float(rolloff))
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_audio(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_audio failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
 
     def clip_stats(self):
         """-> (frames the decoder's clips kept, frames it decoded in front of them and threw away), over its life"""

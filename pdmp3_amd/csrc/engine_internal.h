@@ -5,6 +5,7 @@
 //   stream.hip      pdmp3_hip_stream: buffers, events and ordering of the slots' submits; names no kernel
 //   engine_lsf.hip  the LSF instantiations of the Huffman stage's kernels
 //   clip.hip        k_clip_pack
+//   resample.hip    k_clip_audio (its arithmetic: resample_core.h)
 //   node.hip        include/pdmp3_node.h over the C-ABI
 #ifndef PDMP3_ENGINE_INTERNAL_H
 #define PDMP3_ENGINE_INTERNAL_H
@@ -136,5 +137,8 @@ hipError_t pdmp3_launch_merge_apply_lsf(dim3 grid, hipStream_t s, const pdmp3::G
                                         const uint32_t* sup, const uint16_t* state_in, uint16_t* state_out, pdmp3_gc_side* side);
 // ---- clip.hip ----
 hipError_t pdmp3_launch_clip_pack(hipStream_t s, const pdmp3_clip_piece* pieces, int n_pieces, const void* src);
+// ---- resample.hip ----
+hipError_t pdmp3_launch_clip_audio(hipStream_t s, const pdmp3_audio_desc* descs, int n_clips, const uint32_t* frames, const float* tables,
+                                   long long n_samples, int channels, unsigned lds_bytes);
 
 #endif

@@ -9,6 +9,7 @@
 
 #include "engine_internal.h"
 #include "unpack_core.h"
+#include "resample_core.h"
 
 using namespace pdmp3;
 
@@ -46,6 +47,8 @@ struct pdmp3_hip_stream {
   int have_bits;
   int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
   int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
+  void* d_audio[2]; size_t audio_cap[2];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations
+  uint8_t* d_audio_args; size_t audio_args_cap;   // ... and a launch's descriptors | frame table | filter tables
 };
 
 extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
@@ -62,6 +65,7 @@ extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
     (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
   }
   (void)hipFree(hs->d_sfstate);
+  (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio_args);
   if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
   (void)hipFree(hs->d_state);
   chain_release(hs->ctx, hs);
@@ -534,6 +538,71 @@ static int submit_bits(pdmp3_hip_stream* hs, int slot, int n_frames, void* host_
   }
   HIP_TRY(hipEventRecord(t.done, t.stream), "record done event");
   t.busy = 1;
+  return PDMP3_HIP_OK;
+}
+
+// ---- clips as float batches (resample.hip) ----
+// plain hipMalloc, never stream-ordered; the old block goes first: nothing of the audio path is in flight
+static int grow_device(void** p, size_t* cap, size_t bytes, const char* what) {
+  if (*p && *cap >= bytes) return PDMP3_HIP_OK;
+  (void)hipFree(*p);
+  *p = nullptr; *cap = 0;
+  const size_t want = bytes + bytes / 4 + 4096;
+  HIP_TRY(hipMalloc(p, want), what);
+  *cap = want;
+  return PDMP3_HIP_OK;
+}
+extern "C" void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes) {
+  if (!hs || which < 0 || which > 1) return nullptr;
+  if (hipSetDevice(hs->ctx->device) != hipSuccess) return nullptr;
+  if (grow_device(&hs->d_audio[which], &hs->audio_cap[which], bytes ? bytes : 16, "hipMalloc audio stage") != PDMP3_HIP_OK) return nullptr;
+  return hs->d_audio[which];
+}
+extern "C" int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_audio_desc* descs, int n_clips, const uint32_t* frames,
+                                    size_t n_frames, const float* tables, size_t n_coef, long long n_samples, int channels) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || (n_frames && !frames) || (n_coef && !tables) || n_samples < 0 ||
+      (channels != 1 && channels != 2))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_audio: bad argument", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_audio: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !n_samples) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // the LDS of the launch: the largest any of its clips asks for
+  unsigned lds = 0;
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_audio_desc& d = descs[k];
+    if (d.M == d.L || !(d.flags & PDMP3_AUDIO_LDS_X)) continue;
+    size_t b = (size_t)d.span_cap * channels * sizeof(float);
+    if (d.flags & PDMP3_AUDIO_LDS_TABLE) b += (((size_t)d.L * (size_t)d.taps + 3) & ~(size_t)3) * sizeof(float);
+    if ((d.span_cap & 3u) || (d.table & 3u) || d.taps < 1 || b > pdmp3::kAudioLdsMax)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_audio: a clip's span and table do not fit LDS as its flags say", hipSuccess);
+    if (b > lds) lds = (unsigned)b;
+  }
+  // descriptors | frame table | filter tables: one block, each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_audio_desc) + 255) & ~(size_t)255;
+  const size_t frame_bytes = (n_frames * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t table_bytes = n_coef * sizeof(float);
+  { void* p = hs->d_audio_args;
+    const int rc = grow_device(&p, &hs->audio_args_cap, desc_bytes + frame_bytes + table_bytes + 16, "hipMalloc audio tables");
+    hs->d_audio_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_audio_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_audio_desc), hipMemcpyHostToDevice, t.stream), "H2D audio descriptors");
+  if (n_frames) HIP_TRY(hipMemcpyAsync(a + desc_bytes, frames, n_frames * sizeof(uint32_t), hipMemcpyHostToDevice, t.stream), "H2D audio frame table");
+  if (n_coef) HIP_TRY(hipMemcpyAsync(a + desc_bytes + frame_bytes, tables, table_bytes, hipMemcpyHostToDevice, t.stream), "H2D filter tables");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_audio(t.stream, reinterpret_cast<const pdmp3_audio_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                    reinterpret_cast<const uint32_t*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + frame_bytes),
+                                    n_samples, channels, lds),
+            "launch k_clip_audio");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {
+  if (!bytes) return PDMP3_HIP_OK;
+  if (!host_dst || !dev_src) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_copy_from_device: NULL", hipSuccess);
+  HIP_TRY(hipMemcpy(host_dst, dev_src, bytes, hipMemcpyDeviceToHost), "copy from the device");
   return PDMP3_HIP_OK;
 }
 

@@ -67,6 +67,11 @@ typedef struct pre_window {
 } pre_window;
 struct par_scan;
 
+/* clips as float batches (clip_audio.c): a pair of sampling frequencies and its filter's shape.  M == L: no filter */
+#define AUDIO_TABLE_MAX (1LL << 22)   /* coefficients of a table at most */
+typedef struct { long in, out; int width; double rolloff; long M, L; int d0, taps; } audio_plan;
+typedef struct audio_tab { audio_plan p; float* h; struct audio_tab* next; } audio_tab;
+
 struct bulk {
   pdmp3_handle* id;
   int cap;                            /* frames a window holds */
@@ -168,6 +173,7 @@ struct bulk {
   void (*ix_note)(struct bulk* b);    /* count-only scan: called for every frame (a stream index being built) */
   struct pdmp3_amd_index* ix;
   long long clip_frames, clip_halo;   /* pdmp3_amd_bulk_clip_stats */
+  struct audio_tab* audio_tabs;       /* clips as float batches: the filter tables made so far, one per (in, out, width, rolloff) */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -315,6 +321,9 @@ HOST_LOCAL int par_prepass(struct par_scan* P);
 HOST_LOCAL void span_init(const unsigned char* mp3, const hop_rec* rec, const span_snap* S, pdmp3_handle* id);
 /* bulk_api.c */
 HOST_LOCAL void bulk_begin(struct bulk* b);
+/* clip_audio.c: 0, or -1 on a bad argument or a row of more than AUDIO_TABLE_MAX taps; the L x taps coefficients */
+HOST_LOCAL int audio_plan_init(audio_plan* p, long in, long out, int width, double rolloff);
+HOST_LOCAL void audio_plan_table(const audio_plan* p, float* table);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

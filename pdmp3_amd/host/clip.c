@@ -35,6 +35,8 @@ struct pdmp3_amd_index {
                                         value came from (-1: none since the stream's start, the value is 0) */
   hop_rec* rec;                      /* split: the pre-pass's records */
   span_snap* snap; long long n_snap; /* split: snap[k] in front of frame k * spacing (k >= 1, where ready) */
+  long rate; int spf;                /* the first frame's sampling frequency and samples per frame and channel ... */
+  int mixed, stereo;                 /* ... a later frame's differ (no time line: DESIGN.md section 9); some frame is stereo */
 };
 
 /* granule 0's writes (w0), granule 1's copies from granule 0 (cp, as bits of gc 2 / 3), granule 1's writes (w1) and the groups
@@ -120,6 +122,10 @@ static void ix_note(struct bulk* b) {                /* bulk_push, count-only sc
   const side_info* S = &id->si;
   const unsigned nch = H->mode == 3 ? 1 : 2;
   ix->off[f + 1] = ix->off[f] + 2LL * frame_samples(H) * nch;
+  const long rate = (long)kLsfSampleRates[sfreq9(H)];
+  if (f == 0) { ix->rate = rate; ix->spf = (int)frame_samples(H); }
+  else if (rate != ix->rate || (int)frame_samples(H) != ix->spf) ix->mixed = 1;
+  if (nch == 2) ix->stereo = 1;
   ix->fr[f] = (uint8_t)((H->mode << PDMP3_FR_MODE_SHIFT) | (id->need_reset ? PDMP3_FR_RESET : 0));
   uint32_t hb = H->ver ? HB_LSF : 0;
   for (unsigned ch = 0; ch < nch; ch++)
@@ -240,6 +246,17 @@ long long pdmp3_amd_index_pcm_offsets(const pdmp3_amd_index* ix, long long* out,
   return ix->frames + 1;
 }
 int pdmp3_amd_index_split(const pdmp3_amd_index* ix) { return ix ? ix->split : 0; }
+int pdmp3_amd_index_format(const pdmp3_amd_index* ix, long* rate, int* channels, int* frame_samples) {
+  if (!ix || ix->frames < 0) return -1;
+  if (channels) *channels = ix->stereo ? 2 : 1;
+  if (ix->mixed) return 0;
+  if (rate) *rate = ix->rate;
+  if (frame_samples) *frame_samples = ix->spf;
+  return 1;
+}
+long long pdmp3_amd_index_samples(const pdmp3_amd_index* ix) {
+  return ix && ix->frames >= 0 && !ix->mixed ? ix->frames * ix->spf : -1;
+}
 
 /* ---- scanning a range ---- */
 /* bulk_drive's loop from wherever the handle stands (fed: stream bytes fed so far), until the sink's frame limit.
@@ -462,4 +479,166 @@ out:
 void pdmp3_amd_bulk_clip_stats(const struct bulk* b, long long* clip_frames, long long* halo_frames) {
   if (clip_frames) *clip_frames = b ? b->clip_frames : 0;
   if (halo_frames) *halo_frames = b ? b->clip_halo : 0;
+}
+
+/* ---- clips as float batches ---- */
+/* the decoder's table of the pair (made once, kept) */
+static const audio_tab* audio_table(struct bulk* b, const audio_plan* p) {
+  for (audio_tab* t = b->audio_tabs; t; t = t->next)
+    if (t->p.in == p->in && t->p.out == p->out && t->p.width == p->width && t->p.rolloff == p->rolloff) return t;
+  audio_tab* t = (audio_tab*)calloc(1, sizeof *t);
+  if (t) t->h = (float*)malloc((size_t)p->L * (size_t)p->taps * sizeof(float));
+  if (!t || !t->h) { free(t); return NULL; }
+  t->p = *p;
+  audio_plan_table(p, t->h);
+  t->next = b->audio_tabs;
+  b->audio_tabs = t;
+  return t;
+}
+/* what a workgroup of k_clip_audio keeps in LDS (include/pdmp3_hip.h pdmp3_audio_desc): the input span of its
+ * PDMP3_AUDIO_TILE output samples if that fits, the table too if it fits behind it */
+static void audio_lds(pdmp3_audio_desc* d, int channels) {
+  const unsigned long long span = ((unsigned long long)(d->L - 1) + (unsigned long long)(PDMP3_AUDIO_TILE - 1) * d->M) / d->L + (unsigned)d->taps;
+  const unsigned long long cap = (span + 3) & ~3ULL, xb = cap * (unsigned)channels * 4;
+  d->flags = 0; d->span_cap = 0;
+  if (xb > PDMP3_AUDIO_LDS_BYTES) return;
+  d->flags = PDMP3_AUDIO_LDS_X;
+  d->span_cap = (uint32_t)cap;
+  if (xb + ((((unsigned long long)d->L * (unsigned)d->taps) + 3) & ~3ULL) * 4 <= PDMP3_AUDIO_LDS_BYTES) d->flags |= PDMP3_AUDIO_LDS_TABLE;
+}
+
+int pdmp3_amd_bulk_decode_clips_audio(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_audio_spec* spec,
+                                      long long* valid) {
+  if (!b || !b->hs || !b->bits_mode || !spec || n_clips < 0 || (n_clips && (!clips || !valid)) || spec->n_samples < 0) return -1;
+  const long long T = spec->n_samples;
+  int C = spec->channels, rc = 0;
+  if (C < 0 || C > 2) return -1;
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    if (!c->index || (!c->mp3 && c->n) || c->n != c->index->n || c->start < 0 || (T && !c->dst)) return -1;
+    if ((c->index->iso & PDMP3_ISO_LSF) != (b->id->iso & PDMP3_ISO_LSF)) return -1;
+    if (c->index->frames < 0 || c->index->mixed) continue;
+    const int cs = c->index->stereo ? 2 : 1;
+    if (!spec->channels) {
+      if (C && C != cs) return -1;                   /* (no channel count asked for, and the clips' differ) */
+      C = cs;
+    }
+  }
+  if (!C) C = 1;                                     /* (no clip to decode) */
+  for (int k = 0; k < n_clips; k++) if (C == 2 && T && clips[k].chan_stride < (size_t)T) return -1;
+  pdmp3_amd_clip* pc = (pdmp3_amd_clip*)calloc((size_t)n_clips + 1, sizeof *pc);
+  long long* pb = (long long*)calloc((size_t)n_clips + 1, sizeof *pb);
+  pdmp3_audio_desc* ds = (pdmp3_audio_desc*)calloc((size_t)n_clips + 1, sizeof *ds);
+  int* host = (int*)calloc((size_t)n_clips + 1, sizeof *host);       /* per descriptor: its clip, if that one's rows go to host memory, else -1 */
+  const audio_tab** tabs = (const audio_tab**)calloc((size_t)n_clips + 1, sizeof *tabs);   /* the launch's distinct tables */
+  uint32_t* ft = NULL;
+  float* coef = NULL;
+  int nd = 0, ntab = 0;
+  size_t n_ft = 0, n_coef = 0, in_bytes = 0, out_floats = 0;
+  if (!pc || !pb || !ds || !host || !tabs) { rc = -1; goto out; }
+  /* pass 1: every clip's plan -- its frames [a, e), its table, where its PCM and (host destinations) its rows are staged */
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    const pdmp3_amd_index* ix = c->index;
+    if (ix->frames < 0) { valid[k] = PDMP3_BULK_REPLAY; rc = PDMP3_BULK_REPLAY; continue; }
+    if (ix->mixed) { valid[k] = PDMP3_BULK_MIXED_FORMAT; if (rc != PDMP3_BULK_REPLAY) rc = PDMP3_BULK_MIXED_FORMAT; continue; }
+    audio_plan p;
+    const long in = ix->frames ? ix->rate : (spec->rate ? spec->rate : 44100);      /* (a stream without frames: only zeros come of it) */
+    if (audio_plan_init(&p, in, spec->rate ? spec->rate : in, spec->width, spec->rolloff) != 0) { rc = -1; goto out; }
+    if (p.M != p.L && (long long)p.L * p.taps > AUDIO_TABLE_MAX) { rc = -1; goto out; }
+    const long long N = ix->frames * (ix->frames ? ix->spf : 0);
+    const long long J = (long long)(((__int128)N * p.L + p.M - 1) / p.M);
+    long long first, cnt;
+    if (pdmp3_amd_audio_span(p.in, p.out, p.width, p.rolloff, c->start, T, &first, &cnt) != 0) { rc = -1; goto out; }
+    valid[k] = J - c->start < 0 ? 0 : J - c->start < T ? J - c->start : T;
+    if (!T) continue;
+    long long lo = first < 0 ? 0 : first, hi = first + cnt > N ? N : first + cnt;
+    if (!valid[k] || hi <= lo) lo = hi = 0;          /* (wholly behind the stream's end: zeros) */
+    const long long a = hi > lo ? lo / ix->spf : 0, e = hi > lo ? (hi - 1) / ix->spf + 1 : 0;
+    pdmp3_audio_desc* d = &ds[nd];
+    d->start = c->start; d->n_in = N; d->n_out = J;
+    d->frame0 = a; d->n_frames = (uint32_t)(e - a); d->frame_tab = (uint32_t)n_ft;
+    d->M = (uint32_t)p.M; d->L = (uint32_t)p.L; d->spf = (uint32_t)(ix->frames ? ix->spf : 1152);
+    d->taps = p.taps; d->d0 = p.d0;
+    d->chan_stride = c->chan_stride;
+    if (e - a > 0x7fffffff || n_ft + (size_t)(e - a) > 0xffffffffu) { rc = -1; goto out; }
+    if (p.M != p.L) {
+      const audio_tab* t = audio_table(b, &p);
+      if (!t) { rc = -1; goto out; }
+      int i = 0;
+      while (i < ntab && tabs[i] != t) i++;
+      if (i == ntab) tabs[ntab++] = t;
+      d->table = (uint32_t)i;                        /* (its place among the launch's tables; the offset follows below) */
+      audio_lds(d, C);
+    }
+    /* the clip's int16 PCM: one 16-byte aligned place of the stage (every frame's PCM is a multiple of 1152 bytes) */
+    pc[nd].mp3 = c->mp3; pc[nd].n = c->n; pc[nd].index = ix;
+    pc[nd].first_frame = a; pc[nd].n_frames = e - a;
+    pc[nd].dst_cap = (size_t)(ix->off[e] - ix->off[a]);
+    d->src = in_bytes;                               /* (offsets until the stages are there) */
+    in_bytes += pc[nd].dst_cap;
+    n_ft += (size_t)(e - a);
+    const size_t row_bytes = ((size_t)(C - 1) * c->chan_stride + (size_t)T) * sizeof(float);
+    if (pdmp3_hip_host_is_pinned(c->dst, row_bytes) == 2) { host[nd] = -1; d->dst = (uint64_t)(uintptr_t)c->dst; }
+    else { host[nd] = k; d->dst = out_floats; d->chan_stride = (uint64_t)T; out_floats += (size_t)C * (size_t)T; }
+    nd++;
+  }
+  if (!nd) goto out;
+  /* the frame table and the launch's tables, each table at a multiple of four floats */
+  ft = (uint32_t*)malloc((n_ft + 1) * sizeof *ft);
+  size_t* tab_at = (size_t*)calloc((size_t)ntab + 1, sizeof *tab_at);
+  if (tab_at) for (int i = 0; i < ntab; i++) { tab_at[i] = n_coef; n_coef += ((size_t)tabs[i]->p.L * (size_t)tabs[i]->p.taps + 3) & ~(size_t)3; }
+  if (tab_at) coef = (float*)calloc(n_coef + 4, sizeof *coef);
+  if (!ft || !tab_at || !coef || n_coef > 0xffffffffu) { free(tab_at); rc = -1; goto out; }
+  for (int i = 0; i < ntab; i++) memcpy(coef + tab_at[i], tabs[i]->h, (size_t)tabs[i]->p.L * (size_t)tabs[i]->p.taps * sizeof(float));
+  if (pdmp3_amd_bulk_wait(b) != 0) { free(tab_at); rc = -1; goto out; }
+  uint8_t* in_stage = (uint8_t*)pdmp3_hip_stream_audio_stage(b->hs, 0, in_bytes);
+  float* out_stage = out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, out_floats * sizeof(float)) : NULL;
+  if (!in_stage || (out_floats && !out_stage)) { free(tab_at); rc = -1; goto out; }
+  for (int i = 0; i < nd; i++) {
+    pdmp3_audio_desc* d = &ds[i];
+    const pdmp3_amd_index* ix = pc[i].index;
+    pc[i].dst = in_stage + d->src;
+    d->src = (uint64_t)(uintptr_t)pc[i].dst;
+    if (host[i] >= 0) d->dst = (uint64_t)(uintptr_t)(out_stage + d->dst);
+    if (d->M != d->L) d->table = (uint32_t)tab_at[d->table];
+    for (uint32_t f = 0; f < d->n_frames; f++) {
+      const long long at = ix->off[d->frame0 + f] - ix->off[d->frame0];
+      const int mono = ((ix->fr[d->frame0 + f] >> PDMP3_FR_MODE_SHIFT) & 3) == 3;
+      ft[d->frame_tab + f] = (uint32_t)(at / 1152) << 1 | (uint32_t)mono;
+    }
+  }
+  free(tab_at);
+  /* the clips' frames through the clip path as it is, into the stage; then the one kernel behind the last window */
+  {
+    const int r = pdmp3_amd_bulk_decode_clips(b, pc, nd, pb);
+    if (r != 0) { rc = -1; goto out; }
+  }
+  if (pdmp3_hip_clip_audio(b->hs, CLIP_SLOT, ds, nd, ft, n_ft, coef, n_coef, T, C) != PDMP3_HIP_OK) {
+    fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
+    rc = -1; goto out;
+  }
+  /* host destinations: rows that lie one behind the other in the caller's memory as they do in the stage leave in one copy */
+  for (int i = 0; i < nd; i++) {
+    if (host[i] < 0) continue;
+    const pdmp3_amd_audio_clip* c = &clips[host[i]];
+    const float* from = (const float*)(uintptr_t)ds[i].dst;
+    if (C == 2 && c->chan_stride != (size_t)T) {
+      if (pdmp3_hip_copy_from_device(c->dst, from, (size_t)T * sizeof(float)) != PDMP3_HIP_OK ||
+          pdmp3_hip_copy_from_device(c->dst + c->chan_stride, from + T, (size_t)T * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+      continue;
+    }
+    size_t floats = (size_t)C * (size_t)T;
+    int j = i + 1;
+    for (; j < nd && host[j] >= 0; j++) {
+      const pdmp3_amd_audio_clip* n = &clips[host[j]];
+      if (n->dst != c->dst + floats || (C == 2 && n->chan_stride != (size_t)T)) break;
+      floats += (size_t)C * (size_t)T;
+    }
+    if (pdmp3_hip_copy_from_device(c->dst, from, floats * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+    i = j - 1;
+  }
+out:
+  free(pc); free(pb); free(ds); free(host); free((void*)tabs); free(ft); free(coef);
+  return rc;
 }

@@ -16,6 +16,7 @@
  *   split_scan.c    whole-stream decoder: the scan split over threads (pre-pass, hop threads, scanners, stitcher)
  *   bulk_api.c      whole-stream decoder: pdmp3_amd_bulk_* entry points (new / delete / decode / wait / parse hooks)
  *   clip.c          stream indices, the halo rule of a frame range, clips (pdmp3_amd_index_*, pdmp3_amd_bulk_decode_clips)
+ *   clip_audio.c    clips as float batches: the input span of a clip, the filter table of a pair of sampling frequencies
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

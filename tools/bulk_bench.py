@@ -15,6 +15,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
 
   python tools/bulk_bench.py --clips 64 --clip-frames 191
   python tools/bulk_bench.py --clips 1 --clip-frames 191 --c3
+  python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
 """
 import argparse
 import json
@@ -182,6 +183,108 @@ def clips(args, api):
     print(json.dumps(res))
 
 
+def clips_audio(args, api):
+    """--clips K --clip-frames F --audio RATE [--mono]: the clips of clips() (same seed, same places) as one float32 batch
+    [K, C, T] at RATE in device memory, T = the length of F MPEG-1 frames at 44.1 kHz, three ways, run after run in turn:
+    pdmp3_amd_bulk_decode_clips_audio; the plain clip call on the same clips (int16, every clip at its own rate: what there was
+    before); and the plain clip call followed by the chain of torch kernels the audio call replaces (de-interleave, / 32768,
+    mean, one strided conv1d per source rate with the same filter table, pad).  The chain starts every clip at its frame's first
+    sample, the audio call at the first output sample at or behind it: the two are not compared value by value (the tests
+    check the audio call against the definition).  Medians of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, C = args.clips, args.clip_frames, args.audio, 1 if args.mono else 2
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    T = F * 1152 * rate // 44100
+    spans = [(int(ixs[i].pcm_offsets[a]) // 2, int(ixs[i].pcm_offsets[min(a + F, ixs[i].frames)]) // 2) for i, a in sel]
+    stride = max(hi - lo for lo, hi in spans)
+    dev = "cuda:0"
+    out_p = torch.zeros((K, stride), dtype=torch.int16, device=dev)
+    out_a = torch.zeros((K, C, T), dtype=torch.float32, device=dev)
+    out_t = torch.zeros((K, C, T), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    plain = [(files[i], ixs[i], a, F) for i, a in sel]
+    audio = []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        audio.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    kern = {}
+    for r in sorted(set(ixs[i].rate for i, _ in sel)):
+        if r and r != rate:
+            tab, d0 = api.audio_table(r, rate)
+            g = gcd(r, rate)
+            m, l = r // g, rate // g
+            w = np.zeros((l, 1, (l - 1) * m // l + tab.shape[1]), dtype=np.float32)
+            for p in range(l):
+                w[p, 0, p * m // l:p * m // l + tab.shape[1]] = tab[p * m % l]
+            kern[r] = (torch.from_numpy(w).to(dev), m, l, -d0)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, C, out=out_a)
+
+    def plain_route():
+        dec.decode_clips(plain, out_p)
+
+    def torch_route():
+        dec.decode_clips(plain, out_p)
+        out_t.zero_()
+        for k, (i, a) in enumerate(sel):
+            ix = ixs[i]
+            if not ix.frames:
+                continue
+            lo, hi = spans[k]
+            x = out_p[k, :hi - lo]
+            x = (x.view(-1, 2).t() if ix.channels == 2 else x.view(1, -1)).to(torch.float32) / 32768.0   # (the corpus has no mono frames inside stereo files)
+            if C == 1:
+                x = x.mean(dim=0, keepdim=True)
+            elif x.shape[0] == 1:
+                x = x.expand(2, -1)
+            if ix.rate != rate:
+                w, m, l, left = kern[ix.rate]
+                x = torch.nn.functional.pad(x.unsqueeze(1), (left, w.shape[2]))
+                x = torch.nn.functional.conv1d(x, w, stride=m).transpose(1, 2).reshape(x.shape[0], -1)
+            n = min(T, x.shape[1])
+            out_t[k, :, :n] = x[:, :n]
+        torch.cuda.synchronize()
+
+    routes = [("audio clips", audio_route), ("plain clips", plain_route), ("plain clips + torch chain", torch_route)]
+    times = {name: [] for name, _ in routes}
+    frames = {}
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            c0 = dec.clip_stats()
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            c1 = dec.clip_stats()
+            frames[name] = {"kept": c1[0] - c0[0], "halo": c1[1] - c0[1]}
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length (%d samples at %d Hz, %d channel(s)): %s" % (
+               K, F, T, rate, C, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}, "frames_decoded": frames[name]}
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20000)
@@ -207,10 +310,14 @@ def main():
     ap.add_argument("--warmup-runs", type=int, default=2)
     ap.add_argument("--clip-threads", type=int, default=0, help="--clips: the decoders' copy threads (0: the library's choice)")
     ap.add_argument("--seed", type=int, default=20261016)
+    ap.add_argument("--audio", type=int, default=0, metavar="RATE",
+                    help="--clips: the clips as one float32 batch at RATE (pdmp3_amd_bulk_decode_clips_audio) against the plain clip "
+                         "call and against the plain call followed by torch kernels (see clips_audio())")
+    ap.add_argument("--mono", action="store_true", help="--audio: downmixed to one channel")
     args = ap.parse_args()
     if args.clips:
         from pdmp3_amd import api
-        return clips(args, api)
+        return clips_audio(args, api) if args.audio else clips(args, api)
     if args.lsf and (args.parse_only or args.c4):
         ap.error("--lsf: whole-stream decodes of one stream only")
     from pdmp3_amd.packer import packer
