@@ -276,6 +276,12 @@ int pdmp3_amd_audio_span(long in, long out, int width, double rolloff, long long
  * floor(j M / L) + *first_tap + k.  Returns the coefficient count rows * taps and writes them to table[0 .. min(that, cap));
  * -1 on a bad argument, out == in (no table) or a table of more than 2^22 coefficients. */
 long long pdmp3_amd_audio_table(long in, long out, int width, double rolloff, float* table, size_t cap, long* rows, int* taps, int* first_tap);
+/* What a workgroup of k_clip_audio keeps in LDS for a clip of the pair in a call with `channels` (1 or 2) channels, as the
+ * decode call itself decides it (the same function): *flags = PDMP3_AUDIO_LDS_X (1: the input span of a tile of 1024 output
+ * samples, *span_cap samples a channel, a multiple of 4) | PDMP3_AUDIO_LDS_TABLE (2: the table behind it) of
+ * include/pdmp3_hip.h pdmp3_audio_desc; 0, 0: every output sample straight from memory, and at out == in (no filter).  0, or
+ * -1 on a bad argument or another channel count.  Either pointer may be NULL. */
+int pdmp3_amd_audio_lds_plan(long in, long out, int width, double rolloff, int channels, unsigned* flags, unsigned* span_cap);
 
 /* A clip of the batch: output samples [start, start + n_samples) of the stream at the requested rate.  dst: device memory of
  * the decoder's GPU (written by the kernel itself) or host memory (kernel into a device stage, copied out); channel c's

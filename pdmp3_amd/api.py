@@ -18,7 +18,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_bulk_new_parse_bits", "pdmp3_amd_bulk_new_parse_bits_lsf", "pdmp3_amd_bulk_parse_bits", "pdmp3_amd_bulk_parse_pool", "pdmp3_amd_pcm_alloc", "pdmp3_amd_pcm_free", "pdmp3_amd_stream_loop", "pdmp3_amd_write_wav",
                 "pdmp3_amd_index_new", "pdmp3_amd_index_new_spacing", "pdmp3_amd_index_delete", "pdmp3_amd_index_frames", "pdmp3_amd_index_pcm_offset",
                 "pdmp3_amd_index_pcm_offsets", "pdmp3_amd_index_split", "pdmp3_amd_bulk_decode_clips", "pdmp3_amd_bulk_clip_stats", "pdmp3_amd_bulk_parse_range",
-                "pdmp3_amd_index_format", "pdmp3_amd_index_samples", "pdmp3_amd_audio_span", "pdmp3_amd_audio_table", "pdmp3_amd_bulk_decode_clips_audio"]
+                "pdmp3_amd_index_format", "pdmp3_amd_index_samples", "pdmp3_amd_audio_span", "pdmp3_amd_audio_table", "pdmp3_amd_bulk_decode_clips_audio",
+                "pdmp3_amd_audio_lds_plan"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -121,6 +122,8 @@ def load_library():
         lib.pdmp3_amd_audio_table.argtypes = [C.c_long, C.c_long, C.c_int, C.c_double, vp, C.c_size_t, C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int)]
         lib.pdmp3_amd_audio_table.restype = ll
         lib.pdmp3_amd_bulk_decode_clips_audio.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_audio_lds_plan"):             # (the LDS plan of a pair, for the tests: absent from older builds)
+        lib.pdmp3_amd_audio_lds_plan.argtypes = [C.c_long, C.c_long, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
     _LIB = lib
     return lib
 
@@ -304,6 +307,16 @@ def audio_table(rate_in, rate_out, width=0, rolloff=0.0):
     t = np.empty((rows.value, taps.value), dtype=np.float32)
     lib.pdmp3_amd_audio_table(int(rate_in), int(rate_out), int(width), float(rolloff), t.ctypes.data_as(C.c_void_p), t.size, None, None, None)
     return t, d0.value
+
+
+def audio_lds_plan(rate_in, rate_out, channels, width=0, rolloff=0.0):
+    """pdmp3_amd_audio_lds_plan -> (flags, span_cap): what k_clip_audio keeps in LDS for a clip of the pair in a call with
+    `channels` channels (flags 1: the input span, 3: the table too, 0: nothing -- every sample straight from memory)"""
+    lib = load_library()
+    f, s = C.c_uint(0), C.c_uint(0)
+    if lib.pdmp3_amd_audio_lds_plan(int(rate_in), int(rate_out), int(width), float(rolloff), int(channels), C.byref(f), C.byref(s)) != 0:
+        raise ValueError("pdmp3_amd_audio_lds_plan: bad argument")
+    return f.value, s.value
 
 
 class StreamIndex:

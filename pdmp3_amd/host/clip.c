@@ -506,6 +506,18 @@ static void audio_lds(pdmp3_audio_desc* d, int channels) {
   d->span_cap = (uint32_t)cap;
   if (xb + ((((unsigned long long)d->L * (unsigned)d->taps) + 3) & ~3ULL) * 4 <= PDMP3_AUDIO_LDS_BYTES) d->flags |= PDMP3_AUDIO_LDS_TABLE;
 }
+/* ... for the host tests: the plan a clip of this pair gets in a call with `channels` channels */
+int pdmp3_amd_audio_lds_plan(long in, long out, int width, double rolloff, int channels, unsigned* flags, unsigned* span_cap) {
+  audio_plan p;
+  pdmp3_audio_desc d;
+  if (audio_plan_init(&p, in, out, width, rolloff) != 0 || (channels != 1 && channels != 2)) return -1;
+  memset(&d, 0, sizeof d);
+  d.M = (uint32_t)p.M; d.L = (uint32_t)p.L; d.taps = p.taps;
+  if (p.M != p.L) audio_lds(&d, channels);
+  if (flags) *flags = d.flags;
+  if (span_cap) *span_cap = d.span_cap;
+  return 0;
+}
 
 int pdmp3_amd_bulk_decode_clips_audio(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_audio_spec* spec,
                                       long long* valid) {

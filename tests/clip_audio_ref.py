@@ -1,6 +1,6 @@
 """The definitions of clips as float batches (include/pdmp3_bulk.h) restated in binary64 with numpy alone
 -- independent of the library's table builder and of the kernel: Python / int64 integers for n L - j M, everything else float64.
-Used by test_clip_audio_host.py and test_gpu_clip_audio.py."""
+Used by test_clip_audio_host.py, test_gpu_clip_audio.py and test_gpu_clip_audio_paths.py."""
 from math import gcd
 
 import numpy as np
@@ -48,14 +48,38 @@ def resample64(x, rate_in, rate_out, width, rolloff, start, count):
         if j_end > start:
             y[:, :j_end - start] = x[:, start:j_end]
         return y, bound
-    for a in range(start, j_end, 4096):
-        js = np.arange(a, min(a + 4096, j_end), dtype=np.int64)
+    m, l = ratio(rate_in, rate_out)
+    step = max(1, min(4096, (1 << 23) // (2 * (int(width * max(l, m) / rolloff) // l + 2) + 1)))   # (rows a pass: 64 MB an array at most)
+    for a in range(start, j_end, step):
+        js = np.arange(a, min(a + step, j_end), dtype=np.int64)
         n, h, inside = taps(rate_in, rate_out, width, rolloff, js)
         ok = (n >= 0) & (n < n_in)
         xv = np.where(ok[None], x[:, np.clip(n, 0, max(n_in - 1, 0))], 0.0) if n_in else np.zeros((c,) + n.shape)
         y[:, a - start:a - start + len(js)] = (h[None] * xv).sum(axis=2)
         bound[:, a - start:a - start + len(js)] = (inside.sum(axis=1) + 2)[None] * 2.0 ** -24 * (np.abs(h)[None] * np.abs(xv)).sum(axis=2)
     return y, bound
+
+
+LDS_X, LDS_TABLE, TILE, LDS_BYTES = 1, 2, 1024, 64 * 1024    # include/pdmp3_hip.h PDMP3_AUDIO_*
+
+# (in, out, Z, rolloff) with output rates that are no MPEG rates: tables of tens of thousands of rows, of one row, of thousands
+# of taps -- all three LDS plans among them (test_clip_audio_host.py pins which)
+ODD_PAIRS = [(44100, 44099, 6, 0.99), (48000, 47999, 6, 0.99), (8000, 44101, 6, 0.99), (44100, 22051, 6, 0.99), (32000, 96000, 6, 0.99),
+             (8000, 192000, 16, 0.99), (11025, 48000, 64, 0.99), (44100, 8000, 64, 0.99), (48000, 4000, 64, 0.5), (48000, 1000, 6, 0.99),
+             (44100, 100, 6, 0.99), (22050, 7, 1, 1.0)]
+
+
+def lds_plan(m, l, taps, channels):
+    """pdmp3_amd/host/clip.c audio_lds restated: (flags, span_cap) of a clip with the ratio M : L and `taps` coefficients a row in a
+    call with `channels` channels -- the input span of a tile in LDS if it fits 64 KB, the table behind it if that fits too"""
+    span = ((l - 1) + (TILE - 1) * m) // l + taps
+    cap = (span + 3) & ~3
+    if cap * channels * 4 > LDS_BYTES:
+        return 0, 0
+    flags = LDS_X
+    if cap * channels * 4 + ((l * taps + 3) & ~3) * 4 <= LDS_BYTES:
+        flags |= LDS_TABLE
+    return flags, cap
 
 
 def timeline(whole, pcm_offsets, spf, stereo):
