@@ -305,6 +305,67 @@ typedef struct { long rate; int channels; long long n_samples; int width; double
 int pdmp3_amd_bulk_decode_clips_audio(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips,
                                       const pdmp3_amd_audio_spec* spec, long long* valid);
 
+/* ---- Log-mel features of clips ----
+ * What speech and audio models consume, made on the GPU behind k_clip_audio while the resampled signal is in device memory:
+ * K clips as one planar float32 batch [K][C][n_mels][F], frames innermost.  Nothing any entry point above returns changes.
+ *
+ * Signal.  y_c[j] is the resampled signal above at the requested rate sr and channel count for 0 <= j < J, and 0.0 outside.
+ * The input of the feature stage is the binary32 value pdmp3_amd_bulk_decode_clips_audio produces for y_c[j].
+ * Window.  Periodic Hann, w[n] = 0.5 - 0.5 cos(2 pi n / N), N = n_fft (even, 16 .. 1024).
+ * Frame.  A clip is (stream, index, start), start >= 0 a sample position at sr.  Frame f is centred on sample start + f H
+ * (H = hop, 1 .. N); with K = N / 2 + 1 bins
+ *     X[f, k] = sum over n < N of w[n] y[start + f H - N / 2 + n] e^(-2 pi i k n / N),      P[f, k] = Re^2 + Im^2.
+ * Samples in front of 0 and from J on are zeros; NO reflection is used, and inside a stream the window sees the stream's real
+ * neighbours, not padding.  So the first and the last N / (2 H) frames of a STREAM differ from a transform that reflects its
+ * input at the ends (torch.stft center=True, librosa), and every other frame -- a clip's first and last ones included -- is
+ * the usual definition on the stream's own samples.
+ * Filterbank.  n_mels + 2 points equally spaced in mel between f_min and f_max (0 = sr / 2; 0 <= f_min < f_max <= sr / 2),
+ * mapped back to Hz as f_0 .. f_(n_mels + 1); the frequency of bin k is k sr / N;
+ *     W[m, k] = max(0, min((k sr / N - f_m) / (f_(m+1) - f_m), (f_(m+2) - k sr / N) / (f_(m+2) - f_(m+1)))),
+ * norm = 1 multiplies row m by 2 / (f_(m+2) - f_m).  scale = 1 (HTK): mel = 2595 log10(1 + f / 700); scale = 0 (Slaney):
+ * mel = 3 f / 200 below 1000 Hz, 15 + 27 ln(f / 1000) / ln 6.4 from there on.  M[f, m] = sum over k of W[m, k] P[f, k].
+ * Output.  out_mode 0: M; 1: ln max(M, floor); 2: log10 max(M, floor); 3 ("whisper"): with g = log10 max(the largest M of the
+ * row -- all its frames, bands and channels --, floor):  (max(log10 max(M, floor), g - 8) + 4) / 4.  floor > 0 is rounded to
+ * binary32 first.  valid[k] = clamp(ceil((J - start) / H), 0, F) counts the frames whose centre lies inside the stream;
+ * frames behind the stream's end are the transform of zeros: M = 0, or the floor's logarithm.
+ * The DFT coefficients (window folded in) and the filterbank are computed on the host in binary64 and rounded once to
+ * binary32; the GPU multiplies and adds in binary32 (v_mfma_f32_16x16x4_f32: fused multiply-add chains). */
+typedef struct {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_audio_spec (rate 0: the clips' common own rate) */
+  int n_fft, hop, n_mels;
+  double f_min, f_max;                                  /* f_max 0 = rate / 2 */
+  int scale, norm;                                      /* 0 Slaney / 1 HTK; 0 none / 1 Slaney's area normalisation */
+  long long n_frames;
+  int out_mode;                                         /* 0 power, 1 ln, 2 log10, 3 whisper */
+  double floor;                                         /* > 0 */
+} pdmp3_amd_mel_spec;
+/* Planning, plain C (host tests reach all of it).  0 when the spec's numbers are acceptable at sampling frequency sr, else -1:
+ * n_fft odd or outside 16 .. 1024, hop outside 1 .. n_fft, n_mels outside 1 .. 256, f_min < 0, f_max > sr / 2, f_min >= f_max,
+ * scale / norm / out_mode unknown, n_frames < 0, floor not > 0 (or smaller than binary32's least normal number). */
+int pdmp3_amd_mel_check(const pdmp3_amd_mel_spec* spec, long sr);
+/* The samples [*first, *first + *count) that frames 0 .. n_frames - 1 of a clip at `start` read, before any clamping:
+ * [start - N / 2, start + (n_frames - 1) H + N / 2); count 0 for no frame.  0, or -1 on a bad argument. */
+int pdmp3_amd_mel_span(int n_fft, int hop, long long start, long long n_frames, long long* first, long long* count);
+/* The DFT table as k_clip_mel's B operand: *rows = n_fft rounded up to 4 rows of *cols = 2 Kp floats, Kp = K rounded up to
+ * 16; row n holds w[n] cos(2 pi k n / N) at column k and -w[n] sin(2 pi k n / N) at column Kp + k for k < K; the padding rows
+ * and columns are 0.  The angle is reduced as the integer k n mod N.  Returns rows * cols and writes min(that, cap) floats;
+ * -1 on a bad n_fft. */
+long long pdmp3_amd_mel_dft_table(int n_fft, float* table, size_t cap, int* rows, int* cols);
+/* The filterbank, dense [n_mels][K].  Returns n_mels * K and writes min(that, cap) floats; -1 on a bad argument. */
+long long pdmp3_amd_mel_filterbank(long sr, int n_fft, int n_mels, double f_min, double f_max, int scale, int norm, float* w, size_t cap);
+/* What a workgroup of k_clip_mel takes: *tile frames (32, or 16 where 32 need more than 64 KB of LDS), the LDS floats between
+ * two hops' worth of the signal (*row_pad: hop + row_pad = 2 mod 32, no bank conflicts between the rows of a tile) and the
+ * LDS of a workgroup in bytes.  0, or -1 on a bad argument.  Pointers may be NULL. */
+int pdmp3_amd_mel_tile(int n_fft, int hop, int n_mels, int* tile, int* row_pad, unsigned* lds_bytes);
+/* Row k receives channel c's [n_mels][n_frames] floats at dst + c * chan_stride (pdmp3_amd_audio_clip; chan_stride >= n_mels *
+ * n_frames).  The call decodes the samples the frames read with pdmp3_amd_bulk_decode_clips_audio itself into a device stage
+ * the decoder owns, and k_clip_mel (csrc/mel.hip) writes the rows; host destinations go through a second stage.  Synchronous.
+ * Returns, refuses (PDMP3_BULK_REPLAY / PDMP3_BULK_MIXED_FORMAT per clip in valid[k], the other clips decoded) and counts
+ * (pdmp3_amd_bulk_clip_stats) as pdmp3_amd_bulk_decode_clips_audio; -1 also where pdmp3_amd_mel_check says so and for rate 0
+ * with clips of different rates. */
+int pdmp3_amd_bulk_decode_clips_mel(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mel_spec* spec,
+                                    long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -483,8 +483,8 @@ typedef struct pdmp3_audio_desc {
   uint32_t flags, span_cap;                 /* PDMP3_AUDIO_LDS_*; input samples a tile reads at most      */
 } pdmp3_audio_desc;                         /* 96 bytes */
 /* The stream object's audio stages: device memory (hipMalloc, kept and grown on demand; call with nothing of the audio
- * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory.  NULL on
- * failure. */
+ * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory; 2: the
+ * resampled signal the log-mel call reads (below).  NULL on failure. */
 void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes);
 /* Uploads the launch's tables (descs, frames, tables: host memory) and runs k_clip_audio on the slot's HIP stream, behind
  * whatever the slot ran last (the last clip window's k_clip_pack); n_samples output samples per row, channels = 1 or 2.
@@ -493,6 +493,35 @@ int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_audio_desc*
                          size_t n_frames, const float* tables, size_t n_coef, long long n_samples, int channels);
 /* plain copy of `bytes` from device memory (an audio stage) to host memory; blocks until it is done */
 int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes);
+
+/* Log-mel features of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_mel).  k_clip_mel
+ * (mel.hip) reads rows of the resampled signal that k_clip_audio wrote into audio stage 2 and writes [n_mels][n_frames]
+ * floats per channel.  One clip of the launch: sample t of channel c of its row is src[c * src_chan_stride + t], 0 <= t <
+ * n_in, and stands for the signal at start - n_fft / 2 + lead + t: `lead` zeros lie in front of it (a clip that starts inside
+ * the stream's first n_fft / 2 samples); everything outside [0, n_in) is 0.  Frame f reads t = f hop - lead + n, n < n_fft. */
+typedef struct pdmp3_mel_desc {
+  uint64_t src, dst;                        /* device addresses: channel 0's first sample, channel 0's first output float */
+  uint64_t src_chan_stride, dst_chan_stride; /* floats between the channels                                              */
+  uint32_t lead, pad_;
+} pdmp3_mel_desc;                           /* 40 bytes */
+typedef struct pdmp3_mel_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t n_fft, rows;                      /* N; N rounded up to 4: the DFT table's rows                               */
+  int32_t hop, row_pad;                     /* H; LDS floats between two hops' worth of the signal                      */
+  int32_t bins16, n_mels, mels16;           /* Kp, n_mels, n_mels rounded up to 16                                      */
+  int32_t n_frames, tile;                   /* F; frames of a workgroup: 16 or 32                                       */
+  int32_t channels, out_mode;
+  float floor;
+  uint32_t span_floats;                     /* LDS floats of the workgroup's first region (the signal, then the mel tile) */
+  uint32_t lds_bytes;
+} pdmp3_mel_params;
+#define PDMP3_MEL_LDS_SOFT (64u * 1024u)    /* a tile of 32 frames is taken where it fits this, else 16 frames          */
+#define PDMP3_MEL_LDS_MAX (160u * 1024u - 64u) /* ... which a static array of this size serves (k_clip_mel_big)  */
+/* Uploads the descriptors, the DFT table (rows x 2 bins16 floats) and the transposed padded filterbank (bins16 x mels16
+ * floats) -- host memory -- and runs k_clip_mel (and, out_mode 3, the finishing kernel) on the slot's HIP stream.  Blocks
+ * until the rows are written. */
+int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt,
+                       const pdmp3_mel_params* params);
 
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);

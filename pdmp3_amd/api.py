@@ -19,7 +19,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_index_new", "pdmp3_amd_index_new_spacing", "pdmp3_amd_index_delete", "pdmp3_amd_index_frames", "pdmp3_amd_index_pcm_offset",
                 "pdmp3_amd_index_pcm_offsets", "pdmp3_amd_index_split", "pdmp3_amd_bulk_decode_clips", "pdmp3_amd_bulk_clip_stats", "pdmp3_amd_bulk_parse_range",
                 "pdmp3_amd_index_format", "pdmp3_amd_index_samples", "pdmp3_amd_audio_span", "pdmp3_amd_audio_table", "pdmp3_amd_bulk_decode_clips_audio",
-                "pdmp3_amd_audio_lds_plan"]
+                "pdmp3_amd_audio_lds_plan",
+                "pdmp3_amd_mel_check", "pdmp3_amd_mel_span", "pdmp3_amd_mel_dft_table", "pdmp3_amd_mel_filterbank", "pdmp3_amd_mel_tile",
+                "pdmp3_amd_bulk_decode_clips_mel"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -124,6 +126,15 @@ def load_library():
         lib.pdmp3_amd_bulk_decode_clips_audio.argtypes = [vp, vp, C.c_int, vp, vp]
     if hasattr(lib, "pdmp3_amd_audio_lds_plan"):             # (the LDS plan of a pair, for the tests: absent from older builds)
         lib.pdmp3_amd_audio_lds_plan.argtypes = [C.c_long, C.c_long, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_mel"):      # (log-mel features of clips: absent from older builds)
+        lib.pdmp3_amd_mel_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_mel_span.argtypes = [C.c_int, C.c_int, ll, ll, C.POINTER(ll), C.POINTER(ll)]
+        lib.pdmp3_amd_mel_dft_table.argtypes = [C.c_int, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_mel_dft_table.restype = ll
+        lib.pdmp3_amd_mel_filterbank.argtypes = [C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t]
+        lib.pdmp3_amd_mel_filterbank.restype = ll
+        lib.pdmp3_amd_mel_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_mel.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -317,6 +328,71 @@ def audio_lds_plan(rate_in, rate_out, channels, width=0, rolloff=0.0):
     if lib.pdmp3_amd_audio_lds_plan(int(rate_in), int(rate_out), int(width), float(rolloff), int(channels), C.byref(f), C.byref(s)) != 0:
         raise ValueError("pdmp3_amd_audio_lds_plan: bad argument")
     return f.value, s.value
+
+
+class _MelSpec(C.Structure):                       # include/pdmp3_bulk.h pdmp3_amd_mel_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("n_mels", C.c_int), ("f_min", C.c_double), ("f_max", C.c_double), ("scale", C.c_int), ("norm", C.c_int),
+                ("n_frames", C.c_longlong), ("out_mode", C.c_int), ("floor", C.c_double)]
+
+
+MEL_SCALES = {"slaney": 0, "htk": 1}
+MEL_NORMS = {None: 0, "none": 0, "slaney": 1}
+MEL_MODES = {"power": 0, "log": 1, "ln": 1, "log10": 2, "whisper": 3}
+
+
+def _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff):
+    return _MelSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), int(n_mels), float(f_min), float(f_max),
+                    MEL_SCALES[scale] if isinstance(scale, str) else int(scale), MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm),
+                    int(n_frames), MEL_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+
+
+def mel_check(sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney", mode="log10", floor=1e-10,
+              n_frames=1):
+    """pdmp3_amd_mel_check -> True when pdmp3_amd_bulk_decode_clips_mel would accept these numbers at sample_rate"""
+    spec = _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, 1, 0, 0.0)
+    return load_library().pdmp3_amd_mel_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def mel_span(n_fft, hop, start, n_frames):
+    """pdmp3_amd_mel_span -> (first sample, count) that frames 0 .. n_frames - 1 of a clip at `start` read, unclamped"""
+    a, c = C.c_longlong(0), C.c_longlong(0)
+    if load_library().pdmp3_amd_mel_span(int(n_fft), int(hop), int(start), int(n_frames), C.byref(a), C.byref(c)) != 0:
+        raise ValueError("pdmp3_amd_mel_span: bad argument")
+    return a.value, c.value
+
+
+def mel_dft_table(n_fft):
+    """pdmp3_amd_mel_dft_table -> float32 numpy [rows, 2 Kp] as k_clip_mel reads it: row n, w[n] cos at column k, -w[n] sin at
+    column Kp + k, zeros in the padding"""
+    lib = load_library()
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_mel_dft_table(int(n_fft), None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_mel_dft_table: n_fft must be even, 16 .. 1024")
+    t = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mel_dft_table(int(n_fft), t.ctypes.data_as(C.c_void_p), t.size, None, None)
+    return t
+
+
+def mel_filterbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney"):
+    """pdmp3_amd_mel_filterbank -> float32 numpy [n_mels, n_fft // 2 + 1]"""
+    lib = load_library()
+    sc = MEL_SCALES[scale] if isinstance(scale, str) else int(scale)
+    no = MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm)
+    n = lib.pdmp3_amd_mel_filterbank(int(sample_rate), int(n_fft), int(n_mels), float(f_min), float(f_max), sc, no, None, 0)
+    if n < 0:
+        raise ValueError("pdmp3_amd_mel_filterbank: bad argument")
+    w = np.full((int(n_mels), int(n_fft) // 2 + 1), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mel_filterbank(int(sample_rate), int(n_fft), int(n_mels), float(f_min), float(f_max), sc, no, w.ctypes.data_as(C.c_void_p), w.size)
+    return w
+
+
+def mel_tile(n_fft, hop, n_mels):
+    """pdmp3_amd_mel_tile -> (frames of a workgroup of k_clip_mel, LDS floats between two hops, LDS bytes of a workgroup)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_mel_tile(int(n_fft), int(hop), int(n_mels), C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_mel_tile: bad argument")
+    return t.value, p.value, b.value
 
 
 class StreamIndex:
@@ -587,6 +663,55 @@ class BulkDecoder:
             raise e
         if rc != 0:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_audio failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
+
+    def decode_clips_mel(self, clips, n_frames, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=0.0, scale="slaney",
+                         norm="slaney", mode="log10", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_mel: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        out float32 [K, C, n_mels, n_frames], frame f of a clip centred on sample start + f hop of the stream resampled as
+        decode_clips_audio does (width, rolloff), periodic Hann window of n_fft, zeros outside the stream and no reflection;
+        scale "slaney" / "htk", norm "slaney" / None, mode "power" / "log" / "log10" / "whisper", floor the clamp of the log modes;
+        valid[k] = frames of row k whose centre lies inside the stream.  out: a float32 torch tensor on the decoder's device (made
+        when not given; rows and channels may be strided) or a numpy array.  Synchronous.  RingReplay / MixedFormat (with .out
+        and .valid) as decode_clips_audio."""
+        k, f, nm = len(clips), int(n_frames), int(n_mels)
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_mel: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, nm, f), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        if hasattr(out, "data_ptr"):
+            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, nm, f) and out.shape[0] >= k and out.element_size() == 4
+            assert nm * f <= 1 or ((f <= 1 or out.stride(3) == 1) and (nm <= 1 or out.stride(2) == f))
+            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
+        else:
+            assert out.ndim == 4 and out.shape[1:] == (c, nm, f) and out.shape[0] >= k and out.dtype == np.float32
+            assert nm * f <= 1 or ((f <= 1 or out.strides[3] == 4) and (nm <= 1 or out.strides[2] == 4 * f))
+            assert out.strides[1] % 4 == 0
+            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        spec = _mel_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff)
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_mel(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel failed (a bad argument, a decoder without device Huffman, switches "
                                "that differ from an index's, or an engine failure)")
         return out, valid
 

@@ -140,5 +140,8 @@ hipError_t pdmp3_launch_clip_pack(hipStream_t s, const pdmp3_clip_piece* pieces,
 // ---- resample.hip ----
 hipError_t pdmp3_launch_clip_audio(hipStream_t s, const pdmp3_audio_desc* descs, int n_clips, const uint32_t* frames, const float* tables,
                                    long long n_samples, int channels, unsigned lds_bytes);
+// ---- mel.hip ----
+hipError_t pdmp3_launch_clip_mel(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt, unsigned* row_max,
+                                 const pdmp3_mel_params* params);
 
 #endif

@@ -47,8 +47,9 @@ struct pdmp3_hip_stream {
   int have_bits;
   int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
   int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
-  void* d_audio[2]; size_t audio_cap[2];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations
+  void* d_audio[3]; size_t audio_cap[3];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call
   uint8_t* d_audio_args; size_t audio_args_cap;   // ... and a launch's descriptors | frame table | filter tables
+  uint8_t* d_mel_args; size_t mel_args_cap;       // log-mel features: a launch's descriptors | row maxima | DFT table | filterbank
 };
 
 extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
@@ -65,7 +66,8 @@ extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
     (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
   }
   (void)hipFree(hs->d_sfstate);
-  (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio_args);
+  (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio[2]); (void)hipFree(hs->d_audio_args);
+  (void)hipFree(hs->d_mel_args);
   if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
   (void)hipFree(hs->d_state);
   chain_release(hs->ctx, hs);
@@ -553,7 +555,7 @@ static int grow_device(void** p, size_t* cap, size_t bytes, const char* what) {
   return PDMP3_HIP_OK;
 }
 extern "C" void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes) {
-  if (!hs || which < 0 || which > 1) return nullptr;
+  if (!hs || which < 0 || which > 2) return nullptr;
   if (hipSetDevice(hs->ctx->device) != hipSuccess) return nullptr;
   if (grow_device(&hs->d_audio[which], &hs->audio_cap[which], bytes ? bytes : 16, "hipMalloc audio stage") != PDMP3_HIP_OK) return nullptr;
   return hs->d_audio[which];
@@ -596,6 +598,53 @@ extern "C" int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_
                                     reinterpret_cast<const uint32_t*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + frame_bytes),
                                     n_samples, channels, lds),
             "launch k_clip_audio");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+// ---- log-mel features (mel.hip) ----
+extern "C" int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt,
+                                  const pdmp3_mel_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !dft || !fbt || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: bad argument", hipSuccess);
+  const pdmp3_mel_params& P = *params;
+  // what the kernel's indexing relies on
+  if (P.n_fft < 16 || P.n_fft > 1024 || (P.n_fft & 1) || P.rows != ((P.n_fft + 3) & ~3) || P.hop < 1 || P.hop > P.n_fft || P.row_pad < 0 ||
+      P.bins16 != ((P.n_fft / 2 + 1 + 15) & ~15) || P.n_mels < 1 || P.n_mels > 256 || P.mels16 != ((P.n_mels + 15) & ~15) ||
+      (P.tile != 16 && P.tile != 32) || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 || P.out_mode > 3 || P.n_frames < 0 || P.n_in < 0 ||
+      !(P.floor > 0.0f) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: bad parameters", hipSuccess);
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.rows, chunks = (span + P.hop - 1) / P.hop;
+    const size_t first = chunks * (size_t)(P.hop + P.row_pad), mt = (size_t)P.mels16 * (P.tile + 1);
+    if (P.span_floats < first || P.span_floats < mt || (size_t)P.lds_bytes < ((size_t)P.span_floats + (size_t)P.tile * (P.bins16 + 2)) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: a tile's span, powers and mel tile do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: too many frames", hipSuccess);
+  }
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | row maxima | DFT table | filterbank: one block, each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
+  const size_t max_bytes = ((size_t)n_clips * sizeof(unsigned) + 255) & ~(size_t)255;
+  const size_t dft_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
+  const size_t fb_bytes = (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float);
+  { void* p = hs->d_mel_args;
+    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + max_bytes + dft_bytes + fb_bytes + 16, "hipMalloc mel tables");
+    hs->d_mel_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_mel_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D mel descriptors");
+  HIP_TRY(hipMemsetAsync(a + desc_bytes, 0, max_bytes, t.stream), "memset mel maxima");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes + max_bytes, dft, dft_bytes, hipMemcpyHostToDevice, t.stream), "H2D DFT table");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes + max_bytes + dft_bytes, fbt, fb_bytes, hipMemcpyHostToDevice, t.stream), "H2D filterbank");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_mel(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                  reinterpret_cast<const float*>(a + desc_bytes + max_bytes), reinterpret_cast<const float*>(a + desc_bytes + max_bytes + dft_bytes),
+                                  reinterpret_cast<unsigned*>(a + desc_bytes) + k, &P),
+            "launch k_clip_mel");
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }

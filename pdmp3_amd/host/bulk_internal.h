@@ -71,6 +71,9 @@ struct par_scan;
 #define AUDIO_TABLE_MAX (1LL << 22)   /* coefficients of a table at most */
 typedef struct { long in, out; int width; double rolloff; long M, L; int d0, taps; } audio_plan;
 typedef struct audio_tab { audio_plan p; float* h; struct audio_tab* next; } audio_tab;
+/* log-mel features (clip_mel.c): a DFT table per n_fft (fb == 0) or a filterbank, transposed and padded as k_clip_mel
+ * reads it ([bins16][mels16]), per (sr, n_fft, n_mels, f_min, f_max, scale, norm) */
+typedef struct mel_tab { int fb; long sr; int n_fft, n_mels; double f_min, f_max; int scale, norm; float* t; struct mel_tab* next; } mel_tab;
 
 struct bulk {
   pdmp3_handle* id;
@@ -174,6 +177,7 @@ struct bulk {
   struct pdmp3_amd_index* ix;
   long long clip_frames, clip_halo;   /* pdmp3_amd_bulk_clip_stats */
   struct audio_tab* audio_tabs;       /* clips as float batches: the filter tables made so far, one per (in, out, width, rolloff) */
+  struct mel_tab* mel_tabs;           /* log-mel features: the DFT tables and filterbanks made so far */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -324,6 +328,10 @@ HOST_LOCAL void bulk_begin(struct bulk* b);
 /* clip_audio.c: 0, or -1 on a bad argument or a row of more than AUDIO_TABLE_MAX taps; the L x taps coefficients */
 HOST_LOCAL int audio_plan_init(audio_plan* p, long in, long out, int width, double rolloff);
 HOST_LOCAL void audio_plan_table(const audio_plan* p, float* table);
+/* clip_mel.c: the tables' contents (the caller has checked the arguments) and the kernel's tile and LDS (0, or -1) */
+HOST_LOCAL void mel_dft_fill(int n_fft, float* t);
+HOST_LOCAL int mel_fb_fill(long sr, int n_fft, int n_mels, double f_min, double f_max, int scale, int norm, float* w);
+HOST_LOCAL int mel_plan(int n_fft, int hop, int n_mels, pdmp3_mel_params* p);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

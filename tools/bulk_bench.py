@@ -16,6 +16,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
   python tools/bulk_bench.py --clips 64 --clip-frames 191
   python tools/bulk_bench.py --clips 1 --clip-frames 191 --c3
   python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
+  python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mel                     (clips_mel(): log-mel features, 30 s a clip)
 """
 import argparse
 import json
@@ -285,6 +286,98 @@ def clips_audio(args, api):
     print(json.dumps(res))
 
 
+def clips_mel(args, api):
+    """--clips K --clip-frames F --mel: the clips of clips() (same seed, same places), F MPEG-1 frames' length each, as log-mel
+    features [K, 1, 80, frames] at 16 kHz mono (n_fft 400, hop 160, Slaney, log10) in device memory, three ways, run after run in
+    turn: (a) pdmp3_amd_bulk_decode_clips_audio for the samples the frames read (the call the feature call makes itself: what
+    there was before); (b) (a) followed by the chain of torch kernels the feature call replaces -- torch.stft with the same
+    window, abs() ** 2, a matmul with the same filterbank, log10; a dense matmul against the same DFT table where torch.stft
+    cannot run --; (c) pdmp3_amd_bulk_decode_clips_mel.  (b) and (c) are compared once (largest difference of the log10 values,
+    printed, not asserted: the tests check (c) against the definition).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop, n_mels, floor = args.clips, args.clip_frames, 16000, 400, 160, 80, 1e-10
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    Fm = (F * 1152 * rate // 44100) // hop
+    T = (Fm - 1) * hop + n_fft
+    dev = "cuda:0"
+    mel, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        mel.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - n_fft // 2))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_t = torch.zeros((K, 1, n_mels, Fm), dtype=torch.float32, device=dev)
+    out_m = torch.zeros((K, 1, n_mels, Fm), dtype=torch.float32, device=dev)
+    window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32, device=dev)
+    fb = torch.from_numpy(api.mel_filterbank(rate, n_fft, n_mels)).to(dev)
+    kp = (n_fft // 2 + 1 + 15) // 16 * 16
+    table = torch.from_numpy(api.mel_dft_table(n_fft)[:n_fft]).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    how = {"stft": "torch.stft"}
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+        y = out_a[:, 0]
+        if how["stft"] == "torch.stft":
+            try:
+                p = torch.stft(y, n_fft, hop_length=hop, window=window, center=False, return_complex=True).abs() ** 2      # [K, bins, Fm]
+            except Exception as e:                      # noqa: BLE001  (no FFT library on this build)
+                how["stft"] = "dense matmul against the DFT table (torch.stft: %s)" % type(e).__name__
+        if how["stft"] != "torch.stft":
+            x = y.unfold(1, n_fft, hop) @ table                                                                          # [K, Fm, 2 Kp]
+            p = (x[:, :, :n_fft // 2 + 1] ** 2 + x[:, :, kp:kp + n_fft // 2 + 1] ** 2).transpose(1, 2)
+        out_t[:, 0] = torch.log10(torch.clamp(fb @ p, min=floor))
+        torch.cuda.synchronize()
+
+    def mel_route():
+        dec.decode_clips_mel(mel, Fm, rate, n_fft, hop, n_mels, floor=floor, out=out_m)
+
+    routes = [("audio clips", audio_route), ("audio clips + torch chain", torch_route), ("mel clips", mel_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = float((out_t - out_m).abs().max())
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as %d frames x %d bands at %d Hz mono (n_fft %d, hop %d, log10): %s" % (
+               K, F, Fm, n_mels, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_chain": how["stft"],
+           "largest_difference_of_the_two_log10_results": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    b = times["audio clips + torch chain"]
+    res["mel_minus_audio_ms"] = round((statistics.median(times["mel clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
+    res["mel_not_above_torch_chain_by_more_than_its_spread"] = bool(statistics.median(times["mel clips"]) - statistics.median(b) <= max(b) - min(b))
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20000)
@@ -314,10 +407,13 @@ def main():
                     help="--clips: the clips as one float32 batch at RATE (pdmp3_amd_bulk_decode_clips_audio) against the plain clip "
                          "call and against the plain call followed by torch kernels (see clips_audio())")
     ap.add_argument("--mono", action="store_true", help="--audio: downmixed to one channel")
+    ap.add_argument("--mel", action="store_true",
+                    help="--clips: the clips as log-mel features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mel) against the audio call "
+                         "for the same samples and against that call followed by torch kernels (see clips_mel())")
     args = ap.parse_args()
     if args.clips:
         from pdmp3_amd import api
-        return clips_audio(args, api) if args.audio else clips(args, api)
+        return clips_mel(args, api) if args.mel else clips_audio(args, api) if args.audio else clips(args, api)
     if args.lsf and (args.parse_only or args.c4):
         ap.error("--lsf: whole-stream decodes of one stream only")
     from pdmp3_amd.packer import packer
