@@ -366,6 +366,93 @@ int pdmp3_amd_mel_tile(int n_fft, int hop, int n_mels, int* tile, int* row_pad, 
 int pdmp3_amd_bulk_decode_clips_mel(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mel_spec* spec,
                                     long long* valid);
 
+/* ---- Kaldi-style filterbank features of clips ----
+ * Kaldi's `fbank` front end (torchaudio.compliance.kaldi.fbank's options, by their names there) on the same resampled signal:
+ * K clips as one planar float32 batch [K][C][F][D], frames by coefficients, coefficients innermost.  New entry points only;
+ * nothing any entry point above returns changes.
+ *
+ * Signal.  y_c[j] as for the log-mel call: the resampled signal at the requested rate sr and channel count for 0 <= j < J,
+ * 0.0 outside; its binary32 value is what pdmp3_amd_bulk_decode_clips_audio produces.
+ * Framing.  Nw = win_length samples (2 .. 1024), H = hop (1 .. Nw).  The DFT length N is the least power of two >= Nw with
+ * round_to_power_of_two, else N = Nw (an odd Nw is then refused).  A clip is (stream, index, start), start >= 0.  Frame f is
+ *     s[n] = scale * y[start + f H + n],   0 <= n < Nw:
+ * left-aligned; samples outside [0, J) are zeros, nothing is reflected.
+ * Steps.
+ *  1. remove_dc_offset:  a[n] = s[n] - (1 / Nw) sum s      (off: a = s)
+ *  2. raw energy:        E = sum a[n]^2                    (behind step 1, in front of step 3)
+ *  3. pre-emphasis, rho = preemphasis_coefficient in [0, 1]:  p[n] = a[n] - rho a[n - 1] for n >= 1, p[0] = a[0] - rho a[0]
+ *  4. window w[n], t = 2 pi n / (Nw - 1):  0 povey (0.5 - 0.5 cos t)^0.85;  1 hanning 0.5 - 0.5 cos t;  2 hamming
+ *     0.54 - 0.46 cos t;  3 rectangular 1;  4 blackman b - 0.5 cos t + (0.5 - b) cos 2t, b = blackman_coeff
+ *  5. X[k] = sum over n < Nw of w[n] p[n] e^(-2 pi i k n / N) for k = 0 .. N / 2 - 1 (the Nyquist bin is not used);
+ *     P[k] = Re^2 + Im^2
+ *  6. mel(f) = 1127 ln(1 + f / 700), lo = low_freq, hi = high_freq (<= 0: that offset from sr / 2), 0 <= lo < hi <= sr / 2;
+ *     d = (mel(hi) - mel(lo)) / (n_mels + 1), l_m = mel(lo) + m d, c_m = l_m + d, r_m = l_m + 2 d,
+ *     W[m, k] = max(0, min((mel(k sr / N) - l_m) / (c_m - l_m), (r_m - mel(k sr / N)) / (r_m - c_m))),  M[m] = sum_k W[m, k] P[k]
+ *  7. out_mode 0: M;  1 (use_log_fbank): ln max(M, eps), eps = 2^-23 (binary32's epsilon, as Kaldi and torchaudio)
+ *  8. use_energy: one column more, ln max(E, eps) -- where energy_floor > 0 the larger of that and ln energy_floor --, in
+ *     front of the mel columns, behind them with htk_compat; out_mode 0: E itself.  D = n_mels + use_energy.
+ *  9. subtract_mean: from every column of a (clip, channel) its mean over the frames f < valid[k] is subtracted, from the
+ *     frames at and behind valid[k] too; nothing where valid[k] = 0.
+ * scale must be finite and > 0: 1.0 gives what kaldi.fbank gives on the audio call's [-1, 1) batch, 32768.0 Kaldi's int16
+ * convention.  Not offered, and refused by pdmp3_amd_fbank_check when asked for: dither (random), use_power = false,
+ * raw_energy = false, VTLN (vtln_warp other than 1), snip_edges = false (Kaldi reflects at the edges then; a clip here has the
+ * stream's real neighbours, so a caller moves `start` instead).
+ * valid[k] = the frames wholly inside [0, J): 0 if J - start < Nw, else min(F, (J - start - Nw) / H + 1).  Frames behind it
+ * are the transform of whatever real samples they cover, and zeros.  With start = 0 and F = valid the rows are Kaldi's
+ * snip_edges = true output of the whole stream.
+ * Steps 1, 3, 4 and the zero padding to N are linear maps on a frame: they are folded into the DFT table on the host in
+ * binary64 and rounded once to binary32 (pdmp3_amd_fbank_table); the filterbank likewise.  The GPU multiplies and adds in
+ * binary32 (v_mfma_f32_16x16x4_f32); the energy is a two-pass mean / sum of squares in binary32. */
+typedef struct {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_audio_spec (rate 0: the clips' common own rate) */
+  int win_length, hop, n_mels;
+  int round_to_power_of_two, remove_dc_offset;          /* 0 / 1 */
+  double preemphasis;                                   /* rho */
+  int window;                                           /* 0 povey, 1 hanning, 2 hamming, 3 rectangular, 4 blackman */
+  double blackman_coeff;
+  double low_freq, high_freq;
+  int out_mode;                                         /* 0 power, 1 ln */
+  int use_energy, htk_compat;                           /* 0 / 1 */
+  double energy_floor;                                  /* >= 0; 0: none */
+  int subtract_mean;                                    /* 0 / 1 */
+  double scale;                                         /* > 0 */
+  long long n_frames;
+  /* what is not offered: each must be 0 (vtln_warp: 0 or 1.0) */
+  double dither, vtln_warp;
+  int no_power, no_raw_energy, no_snip_edges;
+} pdmp3_amd_fbank_spec;
+/* Planning, plain C (host tests reach all of it).  0 when the spec's numbers are acceptable at sampling frequency sr, else -1:
+ * win_length outside 2 .. 1024 (or odd without round_to_power_of_two), hop outside 1 .. win_length, n_mels outside 1 .. 256,
+ * preemphasis outside [0, 1], an unknown window / out_mode / flag, blackman_coeff not finite, low_freq < 0, hi > sr / 2,
+ * low_freq >= hi, energy_floor < 0 or not finite, scale not finite or not > 0 (or one whose table leaves binary32),
+ * n_frames < 0, and every option that is not offered. */
+int pdmp3_amd_fbank_check(const pdmp3_amd_fbank_spec* spec, long sr);
+/* N of (win_length, round_to_power_of_two), or -1 */
+int pdmp3_amd_fbank_dft_length(int win_length, int round_to_power_of_two);
+/* The folded table in k_clip_mel's B-operand layout: *rows = Nw rounded up to 4 rows of *cols = 2 Kp floats, Kp = N / 2
+ * rounded up to 16; Re at column k, Im at Kp + k for k < N / 2, 0 in the padding.  With c[n] = w[n] cos(2 pi (k n mod N) / N)
+ * (Im: -w[n] sin) and c[Nw] = 0:  d[n] = c[n] - rho c[n + 1], d[0] loses rho c[0] besides, T[n] = scale (d[n] - (sum d) / Nw)
+ * (no sum term without remove_dc_offset); binary64, rounded once.  Only the spec's framing, window, rho, DC and scale fields
+ * are read.  Returns rows * cols and writes min(that, cap) floats; -1 on a bad argument. */
+long long pdmp3_amd_fbank_table(const pdmp3_amd_fbank_spec* spec, float* table, size_t cap, int* rows, int* cols);
+/* The filterbank, dense [n_mels][N / 2], binary64 rounded once (n_dft even, 2 .. 1024).  Returns n_mels * N / 2 and writes
+ * min(that, cap) floats; -1 on a bad argument. */
+long long pdmp3_amd_fbank_filterbank(long sr, int n_dft, int n_mels, double low_freq, double high_freq, float* w, size_t cap);
+/* valid[k] of a clip at `start` of a stream of J samples; -1 on a bad argument */
+long long pdmp3_amd_fbank_valid(long long J, long long start, int win_length, int hop, long long n_frames);
+/* What a workgroup of k_clip_fbank takes, as the call itself decides it: *tile frames (32, or 16 where 32 need more than 64 KB
+ * of LDS), *row_pad (hop + row_pad = 2 mod 32) and the LDS bytes: the span in chunks of hop + row_pad floats or the mel tile
+ * [mels16][tile + 1] where that is larger, then the powers [tile][Kp + 2] (a row's first spare float holds the frame's
+ * energy).  More than 64 KB at a tile of 16: the static-array kernel.  0, or -1 on a bad argument.  Pointers may be NULL. */
+int pdmp3_amd_fbank_tile(int win_length, int n_dft, int hop, int n_mels, int* tile, int* row_pad, unsigned* lds_bytes);
+/* Row k receives channel c's [n_frames][D] floats at dst + c * chan_stride (pdmp3_amd_audio_clip; chan_stride >= n_frames * D).
+ * The call decodes the span from `start` on, (F - 1) H + Nw samples, with pdmp3_amd_bulk_decode_clips_audio itself into a
+ * device stage the decoder owns, and k_clip_fbank (csrc/fbank.hip) writes the rows; host destinations go through a second
+ * stage.  Synchronous.  Returns, refuses (per clip in valid[k]) and counts as pdmp3_amd_bulk_decode_clips_mel; -1 also where
+ * pdmp3_amd_fbank_check says so. */
+int pdmp3_amd_bulk_decode_clips_fbank(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
+                                      long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -523,6 +523,38 @@ typedef struct pdmp3_mel_params {
 int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt,
                        const pdmp3_mel_params* params);
 
+/* Kaldi-style filterbank features of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_fbank).
+ * k_clip_fbank (fbank.hip) reads rows of the resampled signal in audio stage 2 and writes [n_frames][D] floats per channel,
+ * D = n_mels + use_energy, coefficients innermost.  One clip of the launch: sample t of channel c of its row is
+ * src[c * src_chan_stride + t], 0 <= t < n_in, the signal at start + t; everything outside [0, n_in) is 0.  Frame f reads
+ * t = f hop + n, n < win.  valid: the frames wholly inside the stream (subtract_mean averages over them). */
+typedef struct pdmp3_fbank_desc {
+  uint64_t src, dst;                        /* device addresses: channel 0's first sample, channel 0's first output float */
+  uint64_t src_chan_stride, dst_chan_stride; /* floats between the channels                                              */
+  uint32_t valid, pad_;
+} pdmp3_fbank_desc;                         /* 40 bytes */
+typedef struct pdmp3_fbank_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t win, rows;                        /* Nw; Nw rounded up to 4: the folded table's rows                          */
+  int32_t n_dft;                            /* N: Nw, or the least power of two >= Nw                                   */
+  int32_t hop, row_pad;                     /* H; LDS floats between two hops' worth of the signal                      */
+  int32_t bins16, n_mels, mels16;           /* N / 2 rounded up to 16, n_mels, n_mels rounded up to 16                  */
+  int32_t n_frames, tile;                   /* F; frames of a workgroup: 16 or 32                                       */
+  int32_t channels, out_mode;               /* out_mode 0: M (and E), 1: their logarithms                               */
+  int32_t use_energy, htk_compat;           /* the energy column: in front, or (htk_compat) behind the mel columns      */
+  int32_t subtract_mean, remove_dc;         /* remove_dc: the energy is taken of s - mean (the table carries it for the DFT) */
+  float scale;                              /* of the samples the energy is taken of (the table carries it for the DFT) */
+  float eps;                                /* the floor of the logarithms: 2^-23                                       */
+  float energy_log_floor;                   /* ln energy_floor as binary32, -inf for none                               */
+  uint32_t span_floats;                     /* LDS floats of the workgroup's first region (the signal, then the mel tile) */
+  uint32_t lds_bytes;
+} pdmp3_fbank_params;
+/* Uploads the descriptors, the folded table (rows x 2 bins16 floats) and the transposed padded filterbank (bins16 x mels16
+ * floats) -- host memory -- into one device block and runs k_clip_fbank (and, subtract_mean, k_clip_fbank_finish) on the
+ * slot's HIP stream.  The LDS limits are the log-mel call's (PDMP3_MEL_LDS_SOFT / _MAX).  Blocks until the rows are written. */
+int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
+                         const pdmp3_fbank_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

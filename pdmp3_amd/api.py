@@ -21,7 +21,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_index_format", "pdmp3_amd_index_samples", "pdmp3_amd_audio_span", "pdmp3_amd_audio_table", "pdmp3_amd_bulk_decode_clips_audio",
                 "pdmp3_amd_audio_lds_plan",
                 "pdmp3_amd_mel_check", "pdmp3_amd_mel_span", "pdmp3_amd_mel_dft_table", "pdmp3_amd_mel_filterbank", "pdmp3_amd_mel_tile",
-                "pdmp3_amd_bulk_decode_clips_mel"]
+                "pdmp3_amd_bulk_decode_clips_mel",
+                "pdmp3_amd_fbank_check", "pdmp3_amd_fbank_dft_length", "pdmp3_amd_fbank_table", "pdmp3_amd_fbank_filterbank", "pdmp3_amd_fbank_valid",
+                "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -135,6 +137,17 @@ def load_library():
         lib.pdmp3_amd_mel_filterbank.restype = ll
         lib.pdmp3_amd_mel_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_mel.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_fbank"):    # (Kaldi-style filterbank features of clips: absent from older builds)
+        lib.pdmp3_amd_fbank_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_fbank_dft_length.argtypes = [C.c_int, C.c_int]
+        lib.pdmp3_amd_fbank_table.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_fbank_table.restype = ll
+        lib.pdmp3_amd_fbank_filterbank.argtypes = [C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, vp, C.c_size_t]
+        lib.pdmp3_amd_fbank_filterbank.restype = ll
+        lib.pdmp3_amd_fbank_valid.argtypes = [ll, ll, C.c_int, C.c_int, ll]
+        lib.pdmp3_amd_fbank_valid.restype = ll
+        lib.pdmp3_amd_fbank_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_fbank.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -392,6 +405,94 @@ def mel_tile(n_fft, hop, n_mels):
     t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
     if load_library().pdmp3_amd_mel_tile(int(n_fft), int(hop), int(n_mels), C.byref(t), C.byref(p), C.byref(b)) != 0:
         raise ValueError("pdmp3_amd_mel_tile: bad argument")
+    return t.value, p.value, b.value
+
+
+class _FbankSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_fbank_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("win_length", C.c_int), ("hop", C.c_int),
+                ("n_mels", C.c_int), ("round_to_power_of_two", C.c_int), ("remove_dc_offset", C.c_int), ("preemphasis", C.c_double),
+                ("window", C.c_int), ("blackman_coeff", C.c_double), ("low_freq", C.c_double), ("high_freq", C.c_double), ("out_mode", C.c_int),
+                ("use_energy", C.c_int), ("htk_compat", C.c_int), ("energy_floor", C.c_double), ("subtract_mean", C.c_int), ("scale", C.c_double),
+                ("n_frames", C.c_longlong), ("dither", C.c_double), ("vtln_warp", C.c_double), ("no_power", C.c_int), ("no_raw_energy", C.c_int),
+                ("no_snip_edges", C.c_int)]
+
+
+FBANK_WINDOWS = {"povey": 0, "hanning": 1, "hamming": 2, "rectangular": 3, "blackman": 4}
+
+
+def _fbank_spec(n_frames=1, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None, hop=None,
+                round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42,
+                low_freq=20.0, high_freq=0.0, use_log_fbank=True, use_energy=False, htk_compat=False, energy_floor=1.0, subtract_mean=False,
+                scale=1.0, channels=1, width=0, rolloff=0.0, dither=0.0, use_power=True, raw_energy=True, snip_edges=True, vtln_warp=1.0):
+    """torchaudio.compliance.kaldi.fbank's arguments -> pdmp3_amd_fbank_spec.  Nw = int(sample_rate * frame_length * 0.001) as
+    Kaldi computes it, hop likewise; win_length / hop in samples override them.  An unknown window_type gives one the check
+    refuses.  sample_rate 0 (the clips' own rate) needs win_length and hop."""
+    sr = int(sample_rate)
+    nw = int(win_length) if win_length is not None else int(sr * frame_length * 0.001)
+    h = int(hop) if hop is not None else int(sr * frame_shift * 0.001)
+    win = FBANK_WINDOWS.get(window_type, -1) if isinstance(window_type, str) else int(window_type)
+    return _FbankSpec(sr, int(channels), int(width), float(rolloff), nw, h, int(num_mel_bins), int(bool(round_to_power_of_two)),
+                      int(bool(remove_dc_offset)), float(preemphasis_coefficient), win, float(blackman_coeff), float(low_freq), float(high_freq),
+                      int(use_log_fbank) if isinstance(use_log_fbank, (bool, int)) else -1, int(bool(use_energy)), int(bool(htk_compat)),
+                      float(energy_floor), int(bool(subtract_mean)), float(scale), int(n_frames), float(dither), float(vtln_warp),
+                      int(not use_power), int(not raw_energy), int(not snip_edges))
+
+
+def fbank_check(sample_rate=16000, **kw):
+    """pdmp3_amd_fbank_check -> True when pdmp3_amd_bulk_decode_clips_fbank would accept these arguments (decode_clips_fbank's,
+    and dither / use_power / raw_energy / snip_edges / vtln_warp, which are refused unless they have torchaudio's defaults)"""
+    spec = _fbank_spec(sample_rate=sample_rate, **kw)
+    return load_library().pdmp3_amd_fbank_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def fbank_dft_length(win_length, round_to_power_of_two=True):
+    """pdmp3_amd_fbank_dft_length -> N"""
+    n = load_library().pdmp3_amd_fbank_dft_length(int(win_length), int(bool(round_to_power_of_two)))
+    if n < 0:
+        raise ValueError("pdmp3_amd_fbank_dft_length: win_length must be 2 .. 1024, and even without round_to_power_of_two")
+    return n
+
+
+def fbank_table(win_length=400, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",
+                blackman_coeff=0.42, scale=1.0):
+    """pdmp3_amd_fbank_table -> float32 numpy [Nw rounded up to 4, 2 Kp] as k_clip_fbank reads it: DC removal, pre-emphasis, the
+    window, the zero padding to N and `scale` folded into the DFT; Re at column k, Im at Kp + k, zeros in the padding"""
+    lib = load_library()
+    spec = _fbank_spec(win_length=win_length, hop=1, round_to_power_of_two=round_to_power_of_two, remove_dc_offset=remove_dc_offset,
+                       preemphasis_coefficient=preemphasis_coefficient, window_type=window_type, blackman_coeff=blackman_coeff, scale=scale)
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_fbank_table(C.byref(spec), None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_fbank_table: bad argument")
+    t = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_fbank_table(C.byref(spec), t.ctypes.data_as(C.c_void_p), t.size, None, None)
+    return t
+
+
+def fbank_filterbank(sample_rate, n_dft, num_mel_bins, low_freq=20.0, high_freq=0.0):
+    """pdmp3_amd_fbank_filterbank -> float32 numpy [num_mel_bins, n_dft // 2]"""
+    lib = load_library()
+    n = lib.pdmp3_amd_fbank_filterbank(int(sample_rate), int(n_dft), int(num_mel_bins), float(low_freq), float(high_freq), None, 0)
+    if n < 0:
+        raise ValueError("pdmp3_amd_fbank_filterbank: bad argument")
+    w = np.full((int(num_mel_bins), int(n_dft) // 2), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_fbank_filterbank(int(sample_rate), int(n_dft), int(num_mel_bins), float(low_freq), float(high_freq), w.ctypes.data_as(C.c_void_p), w.size)
+    return w
+
+
+def fbank_valid(n_out, start, win_length, hop, n_frames):
+    """pdmp3_amd_fbank_valid -> the frames of a clip at `start` that lie wholly inside a stream of n_out samples"""
+    v = load_library().pdmp3_amd_fbank_valid(int(n_out), int(start), int(win_length), int(hop), int(n_frames))
+    if v < 0:
+        raise ValueError("pdmp3_amd_fbank_valid: bad argument")
+    return v
+
+
+def fbank_tile(win_length, n_dft, hop, num_mel_bins):
+    """pdmp3_amd_fbank_tile -> (frames of a workgroup of k_clip_fbank, LDS floats between two hops, LDS bytes of a workgroup;
+    more than 64 KB: the static-array kernel)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_fbank_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_fbank_tile: bad argument")
     return t.value, p.value, b.value
 
 
@@ -712,6 +813,60 @@ class BulkDecoder:
             raise e
         if rc != 0:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
+
+    def decode_clips_fbank(self, clips, n_frames, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None,
+                           hop=None, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",
+                           blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, use_log_fbank=True, use_energy=False, htk_compat=False,
+                           energy_floor=1.0, subtract_mean=False, scale=1.0, channels=1, width=0, rolloff=0.0, out=None, **not_offered):
+        """pdmp3_amd_bulk_decode_clips_fbank: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        out float32 [K, C, n_frames, D], D = num_mel_bins + use_energy, what torchaudio.compliance.kaldi.fbank (its argument names
+        and defaults) gives for scale * the stream resampled as decode_clips_audio does, frame f from sample start + f hop on,
+        zeros outside the stream and no reflection; scale 32768.0: Kaldi's int16 convention.  win_length / hop in samples override
+        frame_length / frame_shift in milliseconds.  valid[k] = frames of row k that lie wholly inside the stream (subtract_mean
+        averages over them).  dither, use_power=False, raw_energy=False, snip_edges=False and vtln_warp are refused.  out: a
+        float32 torch tensor on the decoder's device (made when not given; rows and channels may be strided) or a numpy array.
+        Synchronous.  RingReplay / MixedFormat (with .out and .valid) as decode_clips_audio."""
+        k, f, d = len(clips), int(n_frames), int(num_mel_bins) + int(bool(use_energy))
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_fbank: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, f, d), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        if hasattr(out, "data_ptr"):
+            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, f, d) and out.shape[0] >= k and out.element_size() == 4
+            assert f * d <= 1 or ((d <= 1 or out.stride(3) == 1) and (f <= 1 or out.stride(2) == d))
+            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
+        else:
+            assert out.ndim == 4 and out.shape[1:] == (c, f, d) and out.shape[0] >= k and out.dtype == np.float32
+            assert f * d <= 1 or ((d <= 1 or out.strides[3] == 4) and (f <= 1 or out.strides[2] == 4 * d))
+            assert out.strides[1] % 4 == 0
+            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        spec = _fbank_spec(f, sample_rate, frame_length, frame_shift, num_mel_bins, win_length, hop, round_to_power_of_two, remove_dc_offset,
+                           preemphasis_coefficient, window_type, blackman_coeff, low_freq, high_freq, use_log_fbank, use_energy, htk_compat,
+                           energy_floor, subtract_mean, scale, channels, width, rolloff, **not_offered)
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_fbank(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_fbank failed (a bad argument, a decoder without device Huffman, switches "
                                "that differ from an index's, or an engine failure)")
         return out, valid
 

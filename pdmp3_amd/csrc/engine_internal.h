@@ -143,5 +143,8 @@ hipError_t pdmp3_launch_clip_audio(hipStream_t s, const pdmp3_audio_desc* descs,
 // ---- mel.hip ----
 hipError_t pdmp3_launch_clip_mel(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt, unsigned* row_max,
                                  const pdmp3_mel_params* params);
+// ---- fbank.hip ----
+hipError_t pdmp3_launch_clip_fbank(hipStream_t s, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt, float* sums,
+                                   const pdmp3_fbank_params* params);
 
 #endif

@@ -37,6 +37,7 @@ void pdmp3_amd_bulk_delete(struct bulk* b) {
   pc_free(b->pc);
   while (b->audio_tabs) { audio_tab* t = b->audio_tabs; b->audio_tabs = t->next; free(t->h); free(t); }
   while (b->mel_tabs) { mel_tab* t = b->mel_tabs; b->mel_tabs = t->next; free(t->t); free(t); }
+  while (b->fbank_tabs) { fbank_tab* t = b->fbank_tabs; b->fbank_tabs = t->next; free(t->t); free(t); }
   free(b->id);
   free(b);
 }

@@ -74,6 +74,11 @@ typedef struct audio_tab { audio_plan p; float* h; struct audio_tab* next; } aud
 /* log-mel features (clip_mel.c): a DFT table per n_fft (fb == 0) or a filterbank, transposed and padded as k_clip_mel
  * reads it ([bins16][mels16]), per (sr, n_fft, n_mels, f_min, f_max, scale, norm) */
 typedef struct mel_tab { int fb; long sr; int n_fft, n_mels; double f_min, f_max; int scale, norm; float* t; struct mel_tab* next; } mel_tab;
+/* Kaldi-style filterbank features (clip_fbank.c): a folded table per (Nw, N, window, b, rho, DC, scale) (fb == 0) or a
+ * filterbank, transposed and padded as k_clip_fbank reads it ([bins16][mels16]), per (sr, N, n_mels, lo, hi) */
+typedef struct fbank_tab {
+  int fb; long sr; int win, n_dft, n_mels, window, dc; double b, rho, scale, lo, hi; float* t; struct fbank_tab* next;
+} fbank_tab;
 
 struct bulk {
   pdmp3_handle* id;
@@ -178,6 +183,7 @@ struct bulk {
   long long clip_frames, clip_halo;   /* pdmp3_amd_bulk_clip_stats */
   struct audio_tab* audio_tabs;       /* clips as float batches: the filter tables made so far, one per (in, out, width, rolloff) */
   struct mel_tab* mel_tabs;           /* log-mel features: the DFT tables and filterbanks made so far */
+  struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -332,6 +338,11 @@ HOST_LOCAL void audio_plan_table(const audio_plan* p, float* table);
 HOST_LOCAL void mel_dft_fill(int n_fft, float* t);
 HOST_LOCAL int mel_fb_fill(long sr, int n_fft, int n_mels, double f_min, double f_max, int scale, int norm, float* w);
 HOST_LOCAL int mel_plan(int n_fft, int hop, int n_mels, pdmp3_mel_params* p);
+/* clip_fbank.c: the same for the Kaldi-style features; fbank_frame_ok: the fields the folded table reads are acceptable */
+HOST_LOCAL int fbank_frame_ok(const pdmp3_amd_fbank_spec* s);
+HOST_LOCAL void fbank_table_fill(const pdmp3_amd_fbank_spec* s, float* t);
+HOST_LOCAL void fbank_fb_fill(long sr, int n_dft, int n_mels, double lo, double hi, float* w);
+HOST_LOCAL int fbank_plan(int win, int n_dft, int hop, int n_mels, pdmp3_fbank_params* p);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

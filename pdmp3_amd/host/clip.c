@@ -4,6 +4,8 @@
 #include "bulk_internal.h"
 #include "../../include/pdmp3_node.h"
 
+#include <math.h>
+
 #define IX_SPACING 256               /* frames between two snapshots: a clip's scan starts at most this far in front of it */
 
 /* What a frame does to the state the merge carries from frame to frame (frame_parse.c apply_main, unpack_core.h): per
@@ -775,6 +777,160 @@ int pdmp3_amd_bulk_decode_clips_mel(struct bulk* b, const pdmp3_amd_audio_clip* 
   for (int i = 0; i < nd; i++) if (host[i] >= 0) ds[i].dst = (uint64_t)(uintptr_t)(out_stage + ds[i].dst);
   P.n_in = T; P.n_frames = (int32_t)F; P.channels = C; P.out_mode = spec->out_mode; P.floor = (float)spec->floor;
   if (pdmp3_hip_clip_mel(b->hs, CLIP_SLOT, ds, nd, dft->t, fbt->t, &P) != PDMP3_HIP_OK) {
+    fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
+    rc = -1; goto out;
+  }
+  /* host destinations: rows that lie one behind the other in the caller's memory as they do in the stage leave in one copy */
+  for (int i = 0; i < nd; i++) {
+    if (host[i] < 0) continue;
+    const pdmp3_amd_audio_clip* c = &clips[host[i]];
+    const float* from = (const float*)(uintptr_t)ds[i].dst;
+    if (C == 2 && c->chan_stride != per) {
+      if (pdmp3_hip_copy_from_device(c->dst, from, per * sizeof(float)) != PDMP3_HIP_OK ||
+          pdmp3_hip_copy_from_device(c->dst + c->chan_stride, from + per, per * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+      continue;
+    }
+    size_t floats = (size_t)C * per;
+    int j = i + 1;
+    for (; j < nd && host[j] >= 0; j++) {
+      const pdmp3_amd_audio_clip* n = &clips[host[j]];
+      if (n->dst != c->dst + floats || (C == 2 && n->chan_stride != per)) break;
+      floats += (size_t)C * per;
+    }
+    if (pdmp3_hip_copy_from_device(c->dst, from, floats * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+    i = j - 1;
+  }
+out:
+  free(ac); free(av); free(ds); free(host);
+  return rc;
+}
+
+/* ---- Kaldi-style filterbank features of clips ---- */
+/* the decoder's folded table of the spec's framing, or (fb) its filterbank as k_clip_fbank reads it: [bins16][mels16], made
+ * once, kept */
+static const fbank_tab* fbank_table(struct bulk* b, int fb, long sr, const pdmp3_amd_fbank_spec* s) {
+  const int N = pdmp3_amd_fbank_dft_length(s->win_length, s->round_to_power_of_two);
+  const int K = N / 2, Kp = (K + 15) & ~15, Mp = (s->n_mels + 15) & ~15;
+  for (fbank_tab* t = b->fbank_tabs; t; t = t->next) {
+    if (t->fb != fb || t->n_dft != N) continue;
+    if (fb ? (t->sr == sr && t->n_mels == s->n_mels && t->lo == s->low_freq && t->hi == s->high_freq)
+           : (t->win == s->win_length && t->window == s->window && t->dc == s->remove_dc_offset && t->rho == s->preemphasis &&
+              t->scale == s->scale && (s->window != 4 || t->b == s->blackman_coeff)))
+      return t;
+  }
+  fbank_tab* t = (fbank_tab*)calloc(1, sizeof *t);
+  if (!t) return NULL;
+  t->fb = fb; t->n_dft = N;
+  if (!fb) {
+    t->win = s->win_length; t->window = s->window; t->dc = s->remove_dc_offset; t->rho = s->preemphasis; t->scale = s->scale; t->b = s->blackman_coeff;
+    t->t = (float*)malloc((size_t)((s->win_length + 3) & ~3) * (size_t)(2 * Kp) * sizeof(float));
+    if (t->t) fbank_table_fill(s, t->t);
+  } else {
+    t->sr = sr; t->n_mels = s->n_mels; t->lo = s->low_freq; t->hi = s->high_freq;
+    float* w = (float*)malloc((size_t)s->n_mels * (size_t)K * sizeof(float));
+    t->t = (float*)calloc((size_t)Kp * (size_t)Mp, sizeof(float));
+    if (w && t->t) {
+      fbank_fb_fill(sr, N, s->n_mels, s->low_freq, s->high_freq, w);
+      for (int m = 0; m < s->n_mels; m++)
+        for (int k = 0; k < K; k++) t->t[(size_t)k * (size_t)Mp + (size_t)m] = w[(size_t)m * (size_t)K + (size_t)k];
+    } else { free(t->t); t->t = NULL; }
+    free(w);
+  }
+  if (!t->t) { free(t); return NULL; }
+  t->next = b->fbank_tabs;
+  b->fbank_tabs = t;
+  return t;
+}
+
+int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
+                                      long long* valid) {
+  if (!b || !b->hs || !b->bits_mode || !spec || n_clips < 0 || (n_clips && (!clips || !valid)) || spec->n_frames < 0) return -1;
+  const long long F = spec->n_frames;
+  int C = spec->channels, rc = 0;
+  long sr = spec->rate;
+  if (C < 0 || C > 2 || sr < 0) return -1;
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    if (!c->index || (!c->mp3 && c->n) || c->n != c->index->n || c->start < 0 || (F && !c->dst)) return -1;
+    if ((c->index->iso & PDMP3_ISO_LSF) != (b->id->iso & PDMP3_ISO_LSF)) return -1;
+    if (c->index->frames < 0 || c->index->mixed) continue;
+    const int cs = c->index->stereo ? 2 : 1;
+    if (!spec->channels) {
+      if (C && C != cs) return -1;                   /* (no channel count asked for, and the clips' differ) */
+      C = cs;
+    }
+    if (!spec->rate && c->index->frames) {
+      if (sr && sr != c->index->rate) return -1;     /* (no rate asked for, and the clips' differ: one filterbank a call) */
+      sr = c->index->rate;
+    }
+  }
+  if (!C) C = 1;
+  if (!sr) sr = 44100;                               /* (no clip to decode, or only streams without frames) */
+  if (pdmp3_amd_fbank_check(spec, sr) != 0) return -1;
+  const int Nw = spec->win_length, H = spec->hop, D = spec->n_mels + spec->use_energy;
+  pdmp3_fbank_params P;
+  memset(&P, 0, sizeof P);
+  if (fbank_plan(Nw, pdmp3_amd_fbank_dft_length(Nw, spec->round_to_power_of_two), H, spec->n_mels, &P) != 0) return -1;
+  if (F > 0x7fffffffLL / (D > H ? D : H) - 2 * Nw) return -1;          /* (a row's samples and floats stay inside 31 bits) */
+  const size_t per = (size_t)D * (size_t)F;                           /* floats of a channel's output */
+  for (int k = 0; k < n_clips; k++) if (C == 2 && F && clips[k].chan_stride < per) return -1;
+  const long long T = F ? (F - 1) * H + Nw : 0;                       /* samples of a row: what F frames read, from `start` on */
+  const size_t Ts = ((size_t)T + 3) & ~(size_t)3;
+  pdmp3_amd_audio_clip* ac = (pdmp3_amd_audio_clip*)calloc((size_t)n_clips + 1, sizeof *ac);
+  long long* av = (long long*)calloc((size_t)n_clips + 1, sizeof *av);
+  pdmp3_fbank_desc* ds = (pdmp3_fbank_desc*)calloc((size_t)n_clips + 1, sizeof *ds);
+  int* host = (int*)calloc((size_t)n_clips + 1, sizeof *host);       /* per descriptor: its clip, if that one's rows go to host memory, else -1 */
+  int nd = 0;
+  size_t out_floats = 0;
+  if (!ac || !av || !ds || !host) { rc = -1; goto out; }
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    const pdmp3_amd_index* ix = c->index;
+    if (ix->frames < 0) { valid[k] = PDMP3_BULK_REPLAY; rc = PDMP3_BULK_REPLAY; continue; }
+    if (ix->mixed) { valid[k] = PDMP3_BULK_MIXED_FORMAT; if (rc != PDMP3_BULK_REPLAY) rc = PDMP3_BULK_MIXED_FORMAT; continue; }
+    audio_plan p;
+    if (audio_plan_init(&p, ix->frames ? ix->rate : sr, sr, spec->width, spec->rolloff) != 0) { rc = -1; goto out; }
+    const long long Nin = ix->frames * (ix->frames ? ix->spf : 0);
+    const long long J = (long long)(((__int128)Nin * p.L + p.M - 1) / p.M);
+    valid[k] = pdmp3_amd_fbank_valid(J, c->start, Nw, H, F);
+    if (!F) continue;
+    ac[nd].mp3 = c->mp3; ac[nd].n = c->n; ac[nd].index = ix;
+    ac[nd].start = c->start;
+    ac[nd].chan_stride = Ts;
+    ds[nd].valid = (uint32_t)valid[k];
+    ds[nd].src_chan_stride = Ts;
+    const size_t row_bytes = ((size_t)(C - 1) * c->chan_stride + per) * sizeof(float);
+    if (pdmp3_hip_host_is_pinned(c->dst, row_bytes) == 2) { host[nd] = -1; ds[nd].dst = (uint64_t)(uintptr_t)c->dst; ds[nd].dst_chan_stride = c->chan_stride; }
+    else { host[nd] = k; ds[nd].dst = out_floats; ds[nd].dst_chan_stride = per; out_floats += (size_t)C * per; }
+    nd++;
+  }
+  if (!nd) goto out;
+  const fbank_tab* dft = fbank_table(b, 0, sr, spec);
+  const fbank_tab* fbt = fbank_table(b, 1, sr, spec);
+  if (!dft || !fbt) { rc = -1; goto out; }
+  if (pdmp3_amd_bulk_wait(b) != 0) { rc = -1; goto out; }
+  float* sig = (float*)pdmp3_hip_stream_audio_stage(b->hs, 2, (size_t)nd * (size_t)C * Ts * sizeof(float));
+  if (!sig) { rc = -1; goto out; }
+  for (int i = 0; i < nd; i++) {
+    ac[i].dst = sig + (size_t)i * (size_t)C * Ts;
+    ds[i].src = (uint64_t)(uintptr_t)ac[i].dst;
+  }
+  /* the rows through the audio call as it is (device destinations: k_clip_audio writes them itself) */
+  {
+    pdmp3_amd_audio_spec as;
+    memset(&as, 0, sizeof as);
+    as.rate = sr; as.channels = C; as.n_samples = T; as.width = spec->width; as.rolloff = spec->rolloff;
+    if (pdmp3_amd_bulk_decode_clips_audio(b, ac, nd, &as, av) != 0) { rc = -1; goto out; }
+  }
+  /* (the audio call may have grown stage 1 for nothing of ours: it is free for the rows of host destinations) */
+  float* out_stage = out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, out_floats * sizeof(float)) : NULL;
+  if (out_floats && !out_stage) { rc = -1; goto out; }
+  for (int i = 0; i < nd; i++) if (host[i] >= 0) ds[i].dst = (uint64_t)(uintptr_t)(out_stage + ds[i].dst);
+  P.n_in = T; P.n_frames = (int32_t)F; P.channels = C; P.out_mode = spec->out_mode;
+  P.use_energy = spec->use_energy; P.htk_compat = spec->htk_compat; P.subtract_mean = spec->subtract_mean; P.remove_dc = spec->remove_dc_offset;
+  P.scale = (float)spec->scale; P.eps = 0x1p-23f;
+  P.energy_log_floor = spec->energy_floor > 0.0 ? (float)log(spec->energy_floor) : -INFINITY;
+  if (pdmp3_hip_clip_fbank(b->hs, CLIP_SLOT, ds, nd, dft->t, fbt->t, &P) != PDMP3_HIP_OK) {
     fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
     rc = -1; goto out;
   }

@@ -17,6 +17,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
   python tools/bulk_bench.py --clips 1 --clip-frames 191 --c3
   python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mel                     (clips_mel(): log-mel features, 30 s a clip)
+  python tools/bulk_bench.py --clips 64 --clip-frames 1149 --fbank                   (clips_fbank(): Kaldi-style filterbank features)
 """
 import argparse
 import json
@@ -378,6 +379,106 @@ def clips_mel(args, api):
     print(json.dumps(res))
 
 
+def clips_fbank(args, api):
+    """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
+    length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
+    ln) in device memory, three ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the same spans (the call
+    the feature call makes itself); (b) (a) followed by the chain of torch kernels that computes the same definition for the
+    whole batch -- unfold, mean, pre-emphasis, window, pad, rfft, abs() ** 2, matmul, log; a dense matmul against the plain
+    DFT where torch.fft cannot run --; (c) pdmp3_amd_bulk_decode_clips_fbank.  (b) and (c) are compared once (largest
+    difference of the ln values above -10, printed, not asserted: the tests check (c) against the definition).  Medians and
+    min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, nw, hop, n_mels, rho = args.clips, args.clip_frames, 16000, 400, 160, 80, 0.97
+    n = api.fbank_dft_length(nw)
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    seconds = max(F * 1152 // 44100, 1)
+    Fm = 1 + (seconds * rate - nw) // hop                                          # (Kaldi's snip_edges count: 2998 for 30 s)
+    T = (Fm - 1) * hop + nw
+    dev = "cuda:0"
+    clips = []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_t = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
+    out_f = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
+    t = 2.0 * np.pi * np.arange(nw) / (nw - 1)
+    window = torch.from_numpy(((0.5 - 0.5 * np.cos(t)) ** 0.85).astype(np.float32)).to(dev)
+    fbt = torch.from_numpy(api.fbank_filterbank(rate, n, n_mels).T.copy()).to(dev)                     # [N / 2, n_mels]
+    ang = 2.0 * np.pi * ((np.arange(nw)[:, None] * np.arange(n // 2)[None, :]) % n) / n
+    plain = torch.from_numpy(np.hstack([np.cos(ang), -np.sin(ang)]).astype(np.float32)).to(dev)        # [Nw, N]: Re | Im
+    eps = float(np.finfo(np.float32).eps)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    how = {"dft": "torch.fft.rfft"}
+
+    def audio_route():
+        dec.decode_clips_audio(clips, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(clips, T, rate, 1, out=out_a)
+        fr = out_a[:, 0].unfold(1, nw, hop)                                                               # [K, Fm, Nw]
+        fr = fr - fr.mean(dim=2, keepdim=True)
+        fr = fr - rho * torch.nn.functional.pad(fr, (1, 0), mode="replicate")[:, :, :-1]
+        fr = fr * window
+        if how["dft"] == "torch.fft.rfft":
+            try:
+                p = torch.fft.rfft(torch.nn.functional.pad(fr, (0, n - nw)), dim=2).abs()[:, :, :n // 2] ** 2
+            except Exception as e:                      # noqa: BLE001  (no FFT library on this build)
+                how["dft"] = "dense matmul against the plain DFT (torch.fft.rfft: %s)" % type(e).__name__
+        if how["dft"] != "torch.fft.rfft":
+            x = fr @ plain
+            p = x[:, :, :n // 2] ** 2 + x[:, :, n // 2:] ** 2
+        out_t[:, 0] = torch.log(torch.clamp(p @ fbt, min=eps))
+        torch.cuda.synchronize()
+
+    def fbank_route():
+        dec.decode_clips_fbank(clips, Fm, rate, win_length=nw, hop=hop, num_mel_bins=n_mels, out=out_f)
+
+    routes = [("audio clips", audio_route), ("audio clips + torch chain", torch_route), ("fbank clips", fbank_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            big = out_t > -10.0
+            diff = float((out_t - out_f)[big].abs().max()) if bool(big.any()) else 0.0
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as %d frames x %d bins at %d Hz mono (Nw %d, hop %d, N %d, povey, ln): %s" % (
+               K, F, Fm, n_mels, rate, nw, hop, n, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_chain": how["dft"],
+           "largest_difference_of_the_two_ln_results_above_minus_10": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    b = times["audio clips + torch chain"]
+    res["fbank_minus_audio_ms"] = round((statistics.median(times["fbank clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
+    res["torch_chain_minus_audio_ms"] = round((statistics.median(b) - statistics.median(times["audio clips"])) * 1e3, 3)
+    res["fbank_faster_than_torch_chain_by_more_than_its_spread"] = bool(statistics.median(b) - statistics.median(times["fbank clips"]) > max(b) - min(b))
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20000)
@@ -410,9 +511,14 @@ def main():
     ap.add_argument("--mel", action="store_true",
                     help="--clips: the clips as log-mel features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mel) against the audio call "
                          "for the same samples and against that call followed by torch kernels (see clips_mel())")
+    ap.add_argument("--fbank", action="store_true",
+                    help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
+                         "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
     args = ap.parse_args()
     if args.clips:
         from pdmp3_amd import api
+        if args.fbank:
+            return clips_fbank(args, api)
         return clips_mel(args, api) if args.mel else clips_audio(args, api) if args.audio else clips(args, api)
     if args.lsf and (args.parse_only or args.c4):
         ap.error("--lsf: whole-stream decodes of one stream only")
