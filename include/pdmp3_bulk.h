@@ -453,6 +453,54 @@ int pdmp3_amd_fbank_tile(int win_length, int n_dft, int hop, int n_mels, int* ti
 int pdmp3_amd_bulk_decode_clips_fbank(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
                                       long long* valid);
 
+/* ---- Kaldi-style MFCC features of clips ----
+ * Kaldi's `mfcc` front end (torchaudio.compliance.kaldi.mfcc's options, by their names there) on the same resampled signal:
+ * K clips as one planar float32 batch [K][C][F][num_ceps], frames by cepstra, cepstra innermost.  New entry points only;
+ * nothing any entry point above returns changes.
+ *
+ * Signal, framing and steps 1 .. 6 and 8 are the filterbank call's above (framing, DC removal, raw energy, pre-emphasis,
+ * window, DFT without the Nyquist bin, the mel triangles, the energy column's value), with the same options, the same scale
+ * and the same valid[k].  Then, with Nm = n_mels (num_mel_bins), Q = cepstral_lifter:
+ *     L[m]   = ln max(M[m], eps),  eps = 2^-23                  (always the logarithm: there is no power mode)
+ *     B[c,m] = sqrt(1 / Nm) for c = 0;  sqrt(2 / Nm) cos(pi (m + 1/2) c / Nm) for 1 <= c < num_ceps
+ *     l[c]   = 1 + (Q / 2) sin(pi c / Q);  Q = 0: l[c] = 1
+ *     C[c]   = l[c] * sum_m B[c,m] L[m]
+ *     use_energy:    C[0] = max(ln max(E, eps), ln energy_floor)  (step 8; it replaces C0, a frame keeps num_ceps columns)
+ *     htk_compat:    C[0] moves behind C[num_ceps - 1]; without use_energy it is multiplied by sqrt(2) on the way
+ *     subtract_mean: every column minus its mean over the frames f < valid[k]   (as step 9)
+ * Conditions: 1 <= num_ceps <= n_mels; cepstral_lifter finite and >= 0; out_mode must be 1; everything pdmp3_amd_fbank_check
+ * refuses is refused here too (dither, use_power = false, raw_energy = false, VTLN, snip_edges = false).  torchaudio's defaults
+ * for kaldi.mfcc: num_ceps 13, num_mel_bins 23, cepstral_lifter 22.0, use_energy false, energy_floor 1.0, low_freq 20,
+ * high_freq 0.
+ * The lifter, the sqrt(2) and the column order are linear: they are folded into the DCT table on the host in binary64 and
+ * rounded once to binary32 (pdmp3_amd_mfcc_dct_table).  The GPU takes the logarithm of the mel tile where the filterbank left
+ * it and multiplies it by the table in binary32 (v_mfma_f32_16x16x4_f32); the log-mel values never leave the compute unit. */
+typedef struct {
+  pdmp3_amd_fbank_spec fbank;                           /* out_mode must be 1 */
+  int num_ceps;                                         /* 1 .. fbank.n_mels */
+  double cepstral_lifter;                               /* Q >= 0; 0: no lifter */
+} pdmp3_amd_mfcc_spec;
+/* 0 when pdmp3_amd_fbank_check accepts spec->fbank at sr, its out_mode is 1, 1 <= num_ceps <= n_mels and cepstral_lifter is
+ * finite and >= 0; else -1. */
+int pdmp3_amd_mfcc_check(const pdmp3_amd_mfcc_spec* spec, long sr);
+/* The folded DCT table as k_clip_mfcc reads it: *rows = mels16 (n_mels rounded up to 16) rows of *cols = ceps16 (num_ceps
+ * rounded up to 16) floats, Bt[m][col] = l[c] s B[c,m] where c is the cepstral index output column col holds (col itself;
+ * with htk_compat columns 0 .. num_ceps - 2 hold c = 1 .. num_ceps - 1 and the last holds c = 0) and s = sqrt(2) only for
+ * c = 0 with htk_compat and without use_energy; binary64, rounded once.  The column that holds the energy (use_energy) is
+ * all zeros, and so is the padding.  Only n_mels, use_energy, htk_compat, num_ceps and cepstral_lifter are read.  Returns
+ * rows * cols and writes min(that, cap) floats; -1 on a bad argument. */
+long long pdmp3_amd_mfcc_dct_table(const pdmp3_amd_mfcc_spec* spec, float* table, size_t cap, int* rows, int* cols);
+/* What a workgroup of k_clip_mfcc takes, as the call itself decides it: as pdmp3_amd_fbank_tile, but behind the first region
+ * lie max(Kp + 2, ceps16 + 1) floats a frame: the cepstra [tile][ceps16 + 1] take the place of the powers [tile][Kp + 2]
+ * (a row's spare float holds the frame's energy in both) and can be the larger of the two.  0, or -1 on a bad argument. */
+int pdmp3_amd_mfcc_tile(int win_length, int n_dft, int hop, int n_mels, int num_ceps, int* tile, int* row_pad, unsigned* lds_bytes);
+/* Row k receives channel c's [n_frames][num_ceps] floats at dst + c * chan_stride (chan_stride >= n_frames * num_ceps).
+ * Everything else -- the audio call in front, the stages, host destinations, the per-clip refusals in valid[k], rate 0 /
+ * channels 0, width, rolloff, the counts, n_clips = 0 and n_frames = 0 -- as pdmp3_amd_bulk_decode_clips_fbank; k_clip_mfcc
+ * (csrc/mfcc.hip) writes the rows.  -1 also where pdmp3_amd_mfcc_check says so. */
+int pdmp3_amd_bulk_decode_clips_mfcc(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mfcc_spec* spec,
+                                     long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

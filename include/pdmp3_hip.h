@@ -555,6 +555,23 @@ typedef struct pdmp3_fbank_params {
 int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
                          const pdmp3_fbank_params* params);
 
+/* Kaldi-style MFCC features of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_mfcc).
+ * k_clip_mfcc (mfcc.hip) is k_clip_fbank up to the mel tile, takes its logarithm in LDS and multiplies it by the folded DCT
+ * table: [n_frames][n_ceps] floats per channel, cepstra innermost.  The descriptor is pdmp3_fbank_desc.  fb: the filterbank
+ * stages' parameters as pdmp3_hip_clip_fbank takes them, with out_mode 1, and span_floats / lds_bytes of this kernel: the
+ * first region as there, then max(bins16 + 2, ceps16 + 1) floats a frame -- the powers, later the cepstra [tile][ceps16 + 1]
+ * (a row's spare float holds the frame's energy). */
+typedef struct pdmp3_mfcc_params {
+  pdmp3_fbank_params fb;
+  int32_t n_ceps, ceps16;                   /* num_ceps (1 .. n_mels); rounded up to 16: the folded DCT table's columns    */
+} pdmp3_mfcc_params;
+/* Uploads the descriptors, the folded table (rows x 2 bins16 floats), the transposed padded filterbank (bins16 x mels16) and
+ * the folded DCT table (mels16 x ceps16: lifter, htk_compat's sqrt 2 and column order in it, zeros in the energy's column and
+ * in the padding) -- host memory -- into one device block with the column sums behind them and runs k_clip_mfcc (and,
+ * subtract_mean, k_clip_mfcc_finish) on the slot's HIP stream.  Blocks until the rows are written. */
+int pdmp3_hip_clip_mfcc(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
+                        const float* dct, const pdmp3_mfcc_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -23,7 +23,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_mel_check", "pdmp3_amd_mel_span", "pdmp3_amd_mel_dft_table", "pdmp3_amd_mel_filterbank", "pdmp3_amd_mel_tile",
                 "pdmp3_amd_bulk_decode_clips_mel",
                 "pdmp3_amd_fbank_check", "pdmp3_amd_fbank_dft_length", "pdmp3_amd_fbank_table", "pdmp3_amd_fbank_filterbank", "pdmp3_amd_fbank_valid",
-                "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank"]
+                "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank",
+                "pdmp3_amd_mfcc_check", "pdmp3_amd_mfcc_dct_table", "pdmp3_amd_mfcc_tile", "pdmp3_amd_bulk_decode_clips_mfcc"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -148,6 +149,12 @@ def load_library():
         lib.pdmp3_amd_fbank_valid.restype = ll
         lib.pdmp3_amd_fbank_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_fbank.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_mfcc"):     # (Kaldi-style MFCC features of clips: absent from older builds)
+        lib.pdmp3_amd_mfcc_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_mfcc_dct_table.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_mfcc_dct_table.restype = ll
+        lib.pdmp3_amd_mfcc_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_mfcc.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -493,6 +500,52 @@ def fbank_tile(win_length, n_dft, hop, num_mel_bins):
     t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
     if load_library().pdmp3_amd_fbank_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), C.byref(t), C.byref(p), C.byref(b)) != 0:
         raise ValueError("pdmp3_amd_fbank_tile: bad argument")
+    return t.value, p.value, b.value
+
+
+class _MfccSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_mfcc_spec
+    _fields_ = [("fbank", _FbankSpec), ("num_ceps", C.c_int), ("cepstral_lifter", C.c_double)]
+
+
+def _mfcc_spec(num_ceps=13, cepstral_lifter=22.0, **kw):
+    """torchaudio.compliance.kaldi.mfcc's arguments -> pdmp3_amd_mfcc_spec (the filterbank's through _fbank_spec; a
+    cepstral_lifter that is no number gives one the check refuses)"""
+    try:
+        q = float(cepstral_lifter)
+    except (TypeError, ValueError):
+        q = float("nan")
+    return _MfccSpec(_fbank_spec(**kw), int(num_ceps), q)
+
+
+def mfcc_check(sample_rate=16000, **kw):
+    """pdmp3_amd_mfcc_check -> True when pdmp3_amd_bulk_decode_clips_mfcc would accept these arguments (decode_clips_mfcc's,
+    and use_log_fbank / dither / use_power / raw_energy / snip_edges / vtln_warp, which are refused unless they have
+    torchaudio's defaults)"""
+    spec = _mfcc_spec(sample_rate=sample_rate, **kw)
+    return load_library().pdmp3_amd_mfcc_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def mfcc_dct_table(num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, htk_compat=False, use_energy=False):
+    """pdmp3_amd_mfcc_dct_table -> float32 numpy [num_mel_bins rounded up to 16, num_ceps rounded up to 16] as k_clip_mfcc reads
+    it: the orthonormal DCT-II rows with the lifter, htk_compat's sqrt 2 and the column order folded in; zeros in the column
+    that holds the energy and in the padding"""
+    lib = load_library()
+    spec = _mfcc_spec(num_ceps, cepstral_lifter, num_mel_bins=num_mel_bins, htk_compat=htk_compat, use_energy=use_energy)
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_mfcc_dct_table(C.byref(spec), None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_mfcc_dct_table: bad argument")
+    t = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mfcc_dct_table(C.byref(spec), t.ctypes.data_as(C.c_void_p), t.size, None, None)
+    return t
+
+
+def mfcc_tile(win_length, n_dft, hop, num_mel_bins, num_ceps):
+    """pdmp3_amd_mfcc_tile -> (frames of a workgroup of k_clip_mfcc, LDS floats between two hops, LDS bytes of a workgroup;
+    more than 64 KB: the static-array kernel)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_mfcc_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), int(num_ceps), C.byref(t), C.byref(p),
+                                          C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_mfcc_tile: bad argument")
     return t.value, p.value, b.value
 
 
@@ -867,6 +920,61 @@ class BulkDecoder:
             raise e
         if rc != 0:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_fbank failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
+
+    def decode_clips_mfcc(self, clips, n_frames, sample_rate=16000, num_ceps=13, cepstral_lifter=22.0, num_mel_bins=23, frame_length=25.0,
+                          frame_shift=10.0, win_length=None, hop=None, round_to_power_of_two=True, remove_dc_offset=True,
+                          preemphasis_coefficient=0.97, window_type="povey", blackman_coeff=0.42, low_freq=20.0, high_freq=0.0, use_energy=False,
+                          htk_compat=False, energy_floor=1.0, subtract_mean=False, scale=1.0, channels=1, width=0, rolloff=0.0, out=None,
+                          **not_offered):
+        """pdmp3_amd_bulk_decode_clips_mfcc: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        out float32 [K, C, n_frames, num_ceps], what torchaudio.compliance.kaldi.mfcc (its argument names and defaults) gives for
+        scale * the stream resampled as decode_clips_audio does: the cepstra of decode_clips_fbank's log filterbank, liftered, with
+        C0 or (use_energy) the log energy in its place, in front or (htk_compat) behind the others.  Everything else --
+        framing, valid, what is refused, `out`, RingReplay / MixedFormat -- as decode_clips_fbank.  Synchronous."""
+        k, f, d = len(clips), int(n_frames), int(num_ceps)
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_mfcc: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, f, max(d, 0)), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        if hasattr(out, "data_ptr"):
+            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, f, d) and out.shape[0] >= k and out.element_size() == 4
+            assert f * d <= 1 or ((d <= 1 or out.stride(3) == 1) and (f <= 1 or out.stride(2) == d))
+            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
+        else:
+            assert out.ndim == 4 and out.shape[1:] == (c, f, d) and out.shape[0] >= k and out.dtype == np.float32
+            assert f * d <= 1 or ((d <= 1 or out.strides[3] == 4) and (f <= 1 or out.strides[2] == 4 * d))
+            assert out.strides[1] % 4 == 0
+            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        spec = _mfcc_spec(num_ceps, cepstral_lifter, n_frames=f, sample_rate=sample_rate, frame_length=frame_length, frame_shift=frame_shift,
+                          num_mel_bins=num_mel_bins, win_length=win_length, hop=hop, round_to_power_of_two=round_to_power_of_two,
+                          remove_dc_offset=remove_dc_offset, preemphasis_coefficient=preemphasis_coefficient, window_type=window_type,
+                          blackman_coeff=blackman_coeff, low_freq=low_freq, high_freq=high_freq, use_energy=use_energy, htk_compat=htk_compat,
+                          energy_floor=energy_floor, subtract_mean=subtract_mean, scale=scale, channels=channels, width=width, rolloff=rolloff,
+                          **not_offered)
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_mfcc(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mfcc failed (a bad argument, a decoder without device Huffman, switches "
                                "that differ from an index's, or an engine failure)")
         return out, valid
 

@@ -146,5 +146,8 @@ hipError_t pdmp3_launch_clip_mel(hipStream_t s, const pdmp3_mel_desc* descs, int
 // ---- fbank.hip ----
 hipError_t pdmp3_launch_clip_fbank(hipStream_t s, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt, float* sums,
                                    const pdmp3_fbank_params* params);
+// ---- mfcc.hip ----
+hipError_t pdmp3_launch_clip_mfcc(hipStream_t s, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt, const float* dct,
+                                  float* sums, const pdmp3_mfcc_params* params);
 
 #endif

@@ -50,7 +50,7 @@ struct pdmp3_hip_stream {
   void* d_audio[3]; size_t audio_cap[3];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call
   uint8_t* d_audio_args; size_t audio_args_cap;   // ... and a launch's descriptors | frame table | filter tables
   uint8_t* d_mel_args; size_t mel_args_cap;       // log-mel features: a launch's descriptors | row maxima | DFT table | filterbank
-  uint8_t* d_fbank_args; size_t fbank_args_cap;   // Kaldi-style features: a launch's descriptors | folded table | filterbank | column sums
+  uint8_t* d_fbank_args; size_t fbank_args_cap;   // Kaldi-style features (fbank, mfcc): a launch's descriptors | tables | column sums
 };
 
 extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
@@ -699,6 +699,64 @@ extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_
                                     reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + dft_bytes),
                                     P.subtract_mean ? sums + (size_t)k * clip_sums : sums, &P),
             "launch k_clip_fbank");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+// ---- Kaldi-style MFCC features (mfcc.hip) ----
+extern "C" int pdmp3_hip_clip_mfcc(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
+                                   const float* dct, const pdmp3_mfcc_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !dft || !fbt || !dct || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: bad argument", hipSuccess);
+  const pdmp3_fbank_params& P = params->fb;
+  // what the kernel's indexing relies on
+  if (P.win < 2 || P.win > 1024 || P.rows != ((P.win + 3) & ~3) || P.n_dft < P.win || P.n_dft > 1024 || (P.n_dft & 1) || P.hop < 1 || P.hop > P.win ||
+      P.row_pad < 0 || P.bins16 != ((P.n_dft / 2 + 15) & ~15) || P.n_mels < 1 || P.n_mels > 256 || P.mels16 != ((P.n_mels + 15) & ~15) ||
+      (P.tile != 16 && P.tile != 32) || (P.channels != 1 && P.channels != 2) || P.out_mode != 1 || P.n_frames < 0 || P.n_in < 0 ||
+      (P.use_energy & ~1) || (P.htk_compat & ~1) || (P.subtract_mean & ~1) || (P.remove_dc & ~1) || !(P.eps > 0.0f) || !(P.scale > 0.0f) ||
+      P.lds_bytes > PDMP3_MEL_LDS_MAX || params->n_ceps < 1 || params->n_ceps > P.n_mels || params->ceps16 != ((params->n_ceps + 15) & ~15))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: bad parameters", hipSuccess);
+  const size_t tiles = ((size_t)P.n_frames + P.tile - 1) / P.tile, D = (size_t)params->n_ceps;
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.rows, chunks = (span + P.hop - 1) / P.hop;
+    const size_t first = chunks * (size_t)(P.hop + P.row_pad), mt = (size_t)P.mels16 * (P.tile + 1);
+    const size_t pw = (size_t)P.tile * (P.bins16 + 2), ct = (size_t)P.tile * (params->ceps16 + 1);
+    if (P.span_floats < first || P.span_floats < mt || (size_t)P.lds_bytes < ((size_t)P.span_floats + (pw > ct ? pw : ct)) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: a tile's span, powers, mel tile and cepstra do not fit the LDS asked for", hipSuccess);
+    if (tiles * P.channels > 0x7fffffffULL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: too many frames", hipSuccess);
+  }
+  for (int k = 0; k < n_clips; k++)
+    if ((long long)descs[k].valid > (long long)P.n_frames) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: a clip's valid frames exceed its frames", hipSuccess);
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | folded table | filterbank | folded DCT table | (subtract_mean) column sums [clip][channel][tile][n_ceps]: one
+  // block, each part 256-byte aligned -- the block of the filterbank call, which has returned before this one starts
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_fbank_desc) + 255) & ~(size_t)255;
+  const size_t dft_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
+  const size_t fb_bytes = ((size_t)P.bins16 * (size_t)P.mels16 * sizeof(float) + 255) & ~(size_t)255;
+  const size_t dct_bytes = ((size_t)P.mels16 * (size_t)params->ceps16 * sizeof(float) + 255) & ~(size_t)255;
+  const size_t clip_sums = (size_t)P.channels * tiles * D;               // (floats)
+  const size_t sum_bytes = P.subtract_mean ? (size_t)n_clips * clip_sums * sizeof(float) : 0;
+  { void* p = hs->d_fbank_args;
+    const int rc = grow_device(&p, &hs->fbank_args_cap, desc_bytes + dft_bytes + fb_bytes + dct_bytes + sum_bytes + 16, "hipMalloc mfcc tables");
+    hs->d_fbank_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_fbank_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_fbank_desc), hipMemcpyHostToDevice, t.stream), "H2D mfcc descriptors");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes, dft, dft_bytes, hipMemcpyHostToDevice, t.stream), "H2D folded DFT table");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes + dft_bytes, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float), hipMemcpyHostToDevice, t.stream), "H2D filterbank");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes + dft_bytes + fb_bytes, dct, (size_t)P.mels16 * (size_t)params->ceps16 * sizeof(float), hipMemcpyHostToDevice, t.stream),
+          "H2D folded DCT table");
+  float* const sums = reinterpret_cast<float*>(a + desc_bytes + dft_bytes + fb_bytes + dct_bytes);
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_mfcc(t.stream, reinterpret_cast<const pdmp3_fbank_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                   reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + dft_bytes),
+                                   reinterpret_cast<const float*>(a + desc_bytes + dft_bytes + fb_bytes),
+                                   P.subtract_mean ? sums + (size_t)k * clip_sums : sums, params),
+            "launch k_clip_mfcc");
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }

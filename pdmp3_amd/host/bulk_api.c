@@ -38,6 +38,7 @@ void pdmp3_amd_bulk_delete(struct bulk* b) {
   while (b->audio_tabs) { audio_tab* t = b->audio_tabs; b->audio_tabs = t->next; free(t->h); free(t); }
   while (b->mel_tabs) { mel_tab* t = b->mel_tabs; b->mel_tabs = t->next; free(t->t); free(t); }
   while (b->fbank_tabs) { fbank_tab* t = b->fbank_tabs; b->fbank_tabs = t->next; free(t->t); free(t); }
+  while (b->mfcc_tabs) { mfcc_tab* t = b->mfcc_tabs; b->mfcc_tabs = t->next; free(t->t); free(t); }
   free(b->id);
   free(b);
 }

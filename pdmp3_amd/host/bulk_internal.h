@@ -79,6 +79,9 @@ typedef struct mel_tab { int fb; long sr; int n_fft, n_mels; double f_min, f_max
 typedef struct fbank_tab {
   int fb; long sr; int win, n_dft, n_mels, window, dc; double b, rho, scale, lo, hi; float* t; struct fbank_tab* next;
 } fbank_tab;
+/* Kaldi-style MFCC features (clip_mfcc.c): a folded DCT table as k_clip_mfcc reads it ([mels16][ceps16]) per (n_mels,
+ * num_ceps, cepstral_lifter, htk_compat, use_energy) */
+typedef struct mfcc_tab { int n_mels, n_ceps, htk, energy; double lifter; float* t; struct mfcc_tab* next; } mfcc_tab;
 
 struct bulk {
   pdmp3_handle* id;
@@ -184,6 +187,7 @@ struct bulk {
   struct audio_tab* audio_tabs;       /* clips as float batches: the filter tables made so far, one per (in, out, width, rolloff) */
   struct mel_tab* mel_tabs;           /* log-mel features: the DFT tables and filterbanks made so far */
   struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
+  struct mfcc_tab* mfcc_tabs;         /* Kaldi-style MFCC features: the folded DCT tables made so far */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -343,6 +347,9 @@ HOST_LOCAL int fbank_frame_ok(const pdmp3_amd_fbank_spec* s);
 HOST_LOCAL void fbank_table_fill(const pdmp3_amd_fbank_spec* s, float* t);
 HOST_LOCAL void fbank_fb_fill(long sr, int n_dft, int n_mels, double lo, double hi, float* w);
 HOST_LOCAL int fbank_plan(int win, int n_dft, int hop, int n_mels, pdmp3_fbank_params* p);
+/* clip_mfcc.c: the folded DCT table [mels16][ceps16] of a spec the check accepts; the plan of a workgroup of k_clip_mfcc */
+HOST_LOCAL void mfcc_dct_fill(const pdmp3_amd_mfcc_spec* s, float* t);
+HOST_LOCAL int mfcc_plan(int win, int n_dft, int hop, int n_mels, int n_ceps, pdmp3_mfcc_params* q);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

@@ -842,8 +842,27 @@ static const fbank_tab* fbank_table(struct bulk* b, int fb, long sr, const pdmp3
   return t;
 }
 
-int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
-                                      long long* valid) {
+/* the decoder's folded DCT table of the spec as k_clip_mfcc reads it: [mels16][ceps16], made once, kept */
+static const mfcc_tab* mfcc_table(struct bulk* b, const pdmp3_amd_mfcc_spec* s) {
+  const pdmp3_amd_fbank_spec* f = &s->fbank;
+  for (mfcc_tab* t = b->mfcc_tabs; t; t = t->next)
+    if (t->n_mels == f->n_mels && t->n_ceps == s->num_ceps && t->lifter == s->cepstral_lifter && t->htk == f->htk_compat && t->energy == f->use_energy)
+      return t;
+  mfcc_tab* t = (mfcc_tab*)calloc(1, sizeof *t);
+  if (!t) return NULL;
+  t->n_mels = f->n_mels; t->n_ceps = s->num_ceps; t->lifter = s->cepstral_lifter; t->htk = f->htk_compat; t->energy = f->use_energy;
+  t->t = (float*)malloc((size_t)((f->n_mels + 15) & ~15) * (size_t)((s->num_ceps + 15) & ~15) * sizeof(float));
+  if (!t->t) { free(t); return NULL; }
+  mfcc_dct_fill(s, t->t);
+  t->next = b->mfcc_tabs;
+  b->mfcc_tabs = t;
+  return t;
+}
+
+/* the filterbank call (mfcc == NULL) and the MFCC call (spec == &mfcc->fbank): they differ in the check, the coefficients of a
+ * frame, the plan of a workgroup and the launch */
+static int kaldi_clips(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
+                       const pdmp3_amd_mfcc_spec* mfcc, long long* valid) {
   if (!b || !b->hs || !b->bits_mode || !spec || n_clips < 0 || (n_clips && (!clips || !valid)) || spec->n_frames < 0) return -1;
   const long long F = spec->n_frames;
   int C = spec->channels, rc = 0;
@@ -866,11 +885,13 @@ int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip
   }
   if (!C) C = 1;
   if (!sr) sr = 44100;                               /* (no clip to decode, or only streams without frames) */
-  if (pdmp3_amd_fbank_check(spec, sr) != 0) return -1;
-  const int Nw = spec->win_length, H = spec->hop, D = spec->n_mels + spec->use_energy;
-  pdmp3_fbank_params P;
-  memset(&P, 0, sizeof P);
-  if (fbank_plan(Nw, pdmp3_amd_fbank_dft_length(Nw, spec->round_to_power_of_two), H, spec->n_mels, &P) != 0) return -1;
+  if ((mfcc ? pdmp3_amd_mfcc_check(mfcc, sr) : pdmp3_amd_fbank_check(spec, sr)) != 0) return -1;
+  const int Nw = spec->win_length, H = spec->hop, D = mfcc ? mfcc->num_ceps : spec->n_mels + spec->use_energy;
+  pdmp3_mfcc_params Q;
+  memset(&Q, 0, sizeof Q);
+  pdmp3_fbank_params* const P = &Q.fb;
+  if ((mfcc ? mfcc_plan(Nw, pdmp3_amd_fbank_dft_length(Nw, spec->round_to_power_of_two), H, spec->n_mels, mfcc->num_ceps, &Q)
+            : fbank_plan(Nw, pdmp3_amd_fbank_dft_length(Nw, spec->round_to_power_of_two), H, spec->n_mels, P)) != 0) return -1;
   if (F > 0x7fffffffLL / (D > H ? D : H) - 2 * Nw) return -1;          /* (a row's samples and floats stay inside 31 bits) */
   const size_t per = (size_t)D * (size_t)F;                           /* floats of a channel's output */
   for (int k = 0; k < n_clips; k++) if (C == 2 && F && clips[k].chan_stride < per) return -1;
@@ -907,7 +928,8 @@ int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip
   if (!nd) goto out;
   const fbank_tab* dft = fbank_table(b, 0, sr, spec);
   const fbank_tab* fbt = fbank_table(b, 1, sr, spec);
-  if (!dft || !fbt) { rc = -1; goto out; }
+  const mfcc_tab* dct = mfcc ? mfcc_table(b, mfcc) : NULL;
+  if (!dft || !fbt || (mfcc && !dct)) { rc = -1; goto out; }
   if (pdmp3_amd_bulk_wait(b) != 0) { rc = -1; goto out; }
   float* sig = (float*)pdmp3_hip_stream_audio_stage(b->hs, 2, (size_t)nd * (size_t)C * Ts * sizeof(float));
   if (!sig) { rc = -1; goto out; }
@@ -926,11 +948,12 @@ int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip
   float* out_stage = out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, out_floats * sizeof(float)) : NULL;
   if (out_floats && !out_stage) { rc = -1; goto out; }
   for (int i = 0; i < nd; i++) if (host[i] >= 0) ds[i].dst = (uint64_t)(uintptr_t)(out_stage + ds[i].dst);
-  P.n_in = T; P.n_frames = (int32_t)F; P.channels = C; P.out_mode = spec->out_mode;
-  P.use_energy = spec->use_energy; P.htk_compat = spec->htk_compat; P.subtract_mean = spec->subtract_mean; P.remove_dc = spec->remove_dc_offset;
-  P.scale = (float)spec->scale; P.eps = 0x1p-23f;
-  P.energy_log_floor = spec->energy_floor > 0.0 ? (float)log(spec->energy_floor) : -INFINITY;
-  if (pdmp3_hip_clip_fbank(b->hs, CLIP_SLOT, ds, nd, dft->t, fbt->t, &P) != PDMP3_HIP_OK) {
+  P->n_in = T; P->n_frames = (int32_t)F; P->channels = C; P->out_mode = spec->out_mode;
+  P->use_energy = spec->use_energy; P->htk_compat = spec->htk_compat; P->subtract_mean = spec->subtract_mean; P->remove_dc = spec->remove_dc_offset;
+  P->scale = (float)spec->scale; P->eps = 0x1p-23f;
+  P->energy_log_floor = spec->energy_floor > 0.0 ? (float)log(spec->energy_floor) : -INFINITY;
+  if ((mfcc ? pdmp3_hip_clip_mfcc(b->hs, CLIP_SLOT, ds, nd, dft->t, fbt->t, dct->t, &Q)
+            : pdmp3_hip_clip_fbank(b->hs, CLIP_SLOT, ds, nd, dft->t, fbt->t, P)) != PDMP3_HIP_OK) {
     fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
     rc = -1; goto out;
   }
@@ -957,4 +980,16 @@ int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip
 out:
   free(ac); free(av); free(ds); free(host);
   return rc;
+}
+
+int pdmp3_amd_bulk_decode_clips_fbank(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_fbank_spec* spec,
+                                      long long* valid) {
+  return kaldi_clips(b, clips, n_clips, spec, NULL, valid);
+}
+
+/* ---- Kaldi-style MFCC features of clips ---- */
+int pdmp3_amd_bulk_decode_clips_mfcc(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mfcc_spec* spec,
+                                     long long* valid) {
+  if (!spec) return -1;
+  return kaldi_clips(b, clips, n_clips, &spec->fbank, spec, valid);
 }

@@ -18,6 +18,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
   python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mel                     (clips_mel(): log-mel features, 30 s a clip)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --fbank                   (clips_fbank(): Kaldi-style filterbank features)
+  python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mfcc                    (clips_mfcc(): Kaldi-style MFCC features)
 """
 import argparse
 import json
@@ -479,6 +480,86 @@ def clips_fbank(args, api):
     print(json.dumps(res))
 
 
+def clips_mfcc(args, api):
+    """--clips K --clip-frames F --mfcc: the clips of clips_fbank() (same seed, same places, same frames) as Kaldi-style MFCC
+    features [K, 1, frames, 13] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512, 23 bands, lifter 22) in device memory,
+    three ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the same spans (the call the feature calls
+    make themselves); (b) pdmp3_amd_bulk_decode_clips_fbank for the 23 log bands followed by torch.matmul with the DCT table
+    the loader builds itself (lifter folded in, as pdmp3_amd_mfcc_dct_table gives it) and the copy into the output -- what a
+    loader does today; (c) pdmp3_amd_bulk_decode_clips_mfcc.  (b) and (c) are compared once (largest difference, printed, not
+    asserted: the tests check (c) against the definition).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, nw, hop, n_mels, n_ceps, lift = args.clips, args.clip_frames, 16000, 400, 160, 23, 13, 22.0
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    seconds = max(F * 1152 // 44100, 1)
+    Fm = 1 + (seconds * rate - nw) // hop
+    T = (Fm - 1) * hop + nw
+    dev = "cuda:0"
+    clips = []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_l = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
+    out_t = torch.zeros((K, 1, Fm, n_ceps), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, Fm, n_ceps), dtype=torch.float32, device=dev)
+    dct = torch.from_numpy(api.mfcc_dct_table(n_mels, n_ceps, lift)[:n_mels, :n_ceps].copy()).to(dev)      # [n_mels, n_ceps]
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(clips, T, rate, 1, out=out_a)
+
+    def fbank_route():
+        dec.decode_clips_fbank(clips, Fm, rate, win_length=nw, hop=hop, num_mel_bins=n_mels, out=out_l)
+        torch.matmul(out_l, dct, out=out_t)
+        torch.cuda.synchronize()
+
+    def mfcc_route():
+        dec.decode_clips_mfcc(clips, Fm, rate, n_ceps, lift, n_mels, win_length=nw, hop=hop, out=out_c)
+
+    routes = [("audio clips", audio_route), ("fbank clips + torch.matmul", fbank_route), ("mfcc clips", mfcc_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = float((out_t - out_c).abs().max())
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as %d frames x %d cepstra of %d bands at %d Hz mono (Nw %d, hop %d, povey, lifter %g): %s" % (
+               K, F, Fm, n_ceps, n_mels, rate, nw, hop, lift, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "largest_difference_of_the_two_results": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    b = times["fbank clips + torch.matmul"]
+    res["mfcc_minus_audio_ms"] = round((statistics.median(times["mfcc clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
+    res["fbank_matmul_minus_audio_ms"] = round((statistics.median(b) - statistics.median(times["audio clips"])) * 1e3, 3)
+    res["mfcc_faster_than_fbank_matmul_by_more_than_its_spread"] = bool(statistics.median(b) - statistics.median(times["mfcc clips"]) > max(b) - min(b))
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20000)
@@ -514,9 +595,14 @@ def main():
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
+    ap.add_argument("--mfcc", action="store_true",
+                    help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
+                         "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
     if args.clips:
         from pdmp3_amd import api
+        if args.mfcc:
+            return clips_mfcc(args, api)
         if args.fbank:
             return clips_fbank(args, api)
         return clips_mel(args, api) if args.mel else clips_audio(args, api) if args.audio else clips(args, api)
