@@ -501,6 +501,62 @@ int pdmp3_amd_mfcc_tile(int win_length, int n_dft, int hop, int n_mels, int num_
 int pdmp3_amd_bulk_decode_clips_mfcc(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mfcc_spec* spec,
                                      long long* valid);
 
+/* ---- The short-time Fourier transform of clips ----
+ * What the three feature calls above compute first and discard: K clips as one planar float32 batch [K][C][bins][F], frames
+ * innermost, complex or as magnitude, power or its logarithm.  New entry points only; nothing above returns anything else.
+ *
+ * Signal, clip, frame position, valid.  As the log-mel call: y_c[j] is the binary32 output of
+ * pdmp3_amd_bulk_decode_clips_audio at the requested rate and channel count for 0 <= j < J and 0.0 outside; frame f of a clip
+ * at `start` is centred on sample start + f H and reads y[start + f H - N / 2 + n], 0 <= n < N; NO reflection, real
+ * neighbours inside the stream; valid[k] = clamp(ceil((J - start) / H), 0, F).  This is torch.stft(center=False) applied to
+ * the span from start - N / 2 on, and center=True with pad_mode="constant" at a stream's two ends only.
+ * Window.  N = n_fft is even, 16 .. 1024; win_length Nw, 1 <= Nw <= N (0: N); `window` points to Nw binary32 values of the
+ * caller's (finite), NULL: the periodic Hann window of Nw, 0.5 - 0.5 cos(2 pi i / Nw).  The frame's window w[n] is `window`
+ * at n = (N - Nw) / 2 + i (integer division, as torch.stft) and 0 elsewhere.
+ * Transform.  bins = N / 2 + 1;  X[f, k] = s sum over n < N of w[n] y[start + f H - N / 2 + n] e^(-2 pi i k n / N),
+ * s = N^(-1/2) with `normalized`, else 1.
+ * Output.  out_mode 0 complex: [K][C][bins][F][2], Re and Im interleaved -- the memory of a [K, C, bins, F] complex64
+ * tensor; 1 magnitude sqrt(Re^2 + Im^2); 2 power Re^2 + Im^2; 3 ln max(power, floor); 4 log10 max(power, floor); modes 1 .. 4
+ * are [K][C][bins][F].  floor > 0 is rounded to binary32 first and is read in modes 3 and 4 only.  Frames behind the
+ * stream's end are the transform of zeros.
+ * The coefficients s w[n] cos and -s w[n] sin are computed on the host in binary64 from the binary32 window values and
+ * rounded once; the GPU multiplies and adds in binary32 (v_mfma_f32_16x16x4_f32), the square root is correctly rounded.
+ * Not offered: n_fft above 1024 (the transform is a matrix product, N^2 a frame), the inverse transform, reflection at a
+ * stream's ends, a frames-major layout. */
+typedef struct {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec */
+  int n_fft, hop, win_length;                           /* win_length 0 = n_fft */
+  const float* window;                                  /* win_length values, NULL = periodic Hann */
+  int normalized;                                       /* 0, or 1: scaled by n_fft^(-1/2) */
+  long long n_frames;
+  int out_mode;                                         /* 0 complex, 1 magnitude, 2 power, 3 ln, 4 log10 */
+  double floor;                                         /* modes 3 and 4: > 0 */
+} pdmp3_amd_stft_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: n_fft odd or outside 16 .. 1024, hop outside
+ * 1 .. n_fft, win_length outside 0 .. n_fft, a window value that is not finite, normalized not 0 or 1, out_mode unknown,
+ * n_frames < 0, and in modes 3 and 4 a floor not > 0 (or smaller than binary32's least normal number). */
+int pdmp3_amd_stft_check(const pdmp3_amd_stft_spec* spec, long sr);
+/* The folded table in pdmp3_amd_mel_dft_table's layout: *rows = n_fft rounded up to 4 rows of *cols = 2 Kp floats, Kp = bins
+ * rounded up to 16; row n holds s w[n] cos(2 pi k n / N) at column k and -s w[n] sin(2 pi k n / N) at column Kp + k, the
+ * angle reduced as the integer k n mod N; the rows outside the window's support and all padding are exactly 0.  With a NULL
+ * window, win_length = n_fft and normalized = 0 it is pdmp3_amd_mel_dft_table(n_fft) bit for bit.  Only n_fft, win_length,
+ * window and normalized are read.  Returns rows * cols and writes min(that, cap) floats; -1 on a bad argument. */
+long long pdmp3_amd_stft_table(const pdmp3_amd_stft_spec* spec, float* table, size_t cap, int* rows, int* cols);
+/* What a workgroup of k_clip_stft takes, the function the call itself uses: *tile frames (32 where the LDS below fits 64 KB,
+ * else 16), *row_pad (hop + row_pad = 2 mod 32) and the LDS bytes: the tile's span in chunks of hop + row_pad floats, rounded
+ * up to 4 floats, then four staging tiles of (out_mode 0 ? 2 : 1) x 16 x (tile + 4) floats.  A tile of 16 frames that needs
+ * more than 64 KB runs in a kernel with a static array (k_clip_stft_big).  0, or -1 on a bad argument.  Pointers may be NULL. */
+int pdmp3_amd_stft_tile(int n_fft, int hop, int out_mode, int* tile, int* row_pad, unsigned* lds_bytes);
+/* Row k receives channel c's [bins][n_frames] floats (mode 0: [bins][n_frames][2]) at dst + c * chan_stride
+ * (pdmp3_amd_audio_clip; chan_stride >= that many floats).  Everything else -- the
+ * audio call in front, the stages, host destinations, the per-clip refusals in valid[k], rate 0 / channels 0, width, rolloff,
+ * the counts, n_clips = 0 and n_frames = 0 -- as pdmp3_amd_bulk_decode_clips_mel; k_clip_stft (csrc/stft.hip) writes the
+ * rows.  The decoder keeps the folded tables of the last PDMP3_STFT_TABLES distinct (n_fft, win_length, normalized, window
+ * contents) and drops the least recently used one for a new one.  -1 also where pdmp3_amd_stft_check says so. */
+#define PDMP3_STFT_TABLES 4
+int pdmp3_amd_bulk_decode_clips_stft(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_stft_spec* spec,
+                                     long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -572,6 +572,28 @@ typedef struct pdmp3_mfcc_params {
 int pdmp3_hip_clip_mfcc(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
                         const float* dct, const pdmp3_mfcc_params* params);
 
+/* The short-time Fourier transform of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_stft).
+ * k_clip_stft (stft.hip) reads rows of the resampled signal in audio stage 2 as k_clip_mel does -- the descriptor is
+ * pdmp3_mel_desc -- and writes [bins][n_frames] floats per channel, frames innermost; out_mode 0: [bins][n_frames][2], Re and
+ * Im interleaved.  The LDS of a workgroup: span_floats for the tile's span in chunks of hop + row_pad floats, then a staging
+ * tile per wave of (out_mode 0 ? 2 : 1) planes of 16 rows of tile + 4 floats. */
+typedef struct pdmp3_stft_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t n_fft, rows;                      /* N; N rounded up to 4: the folded table's rows                            */
+  int32_t hop, row_pad;                     /* H; LDS floats between two hops' worth of the signal                      */
+  int32_t bins, bins16;                     /* K = N / 2 + 1; Kp = K rounded up to 16                                   */
+  int32_t n_frames, tile;                   /* F; frames of a workgroup: 16 or 32                                       */
+  int32_t channels, out_mode;               /* out_mode 0 complex, 1 magnitude, 2 power, 3 ln, 4 log10                  */
+  float floor;                              /* of the logarithms (modes 3 and 4)                                        */
+  uint32_t span_floats;                     /* LDS floats of the tile's span, a multiple of 4                           */
+  uint32_t lds_bytes;
+} pdmp3_stft_params;
+/* Uploads the descriptors and the folded table (rows x 2 bins16 floats: window and scale in it) -- host memory -- and runs
+ * k_clip_stft on the slot's HIP stream.  The LDS limits are the log-mel call's (PDMP3_MEL_LDS_SOFT / _MAX).  Blocks until the
+ * rows are written. */
+int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table,
+                        const pdmp3_stft_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -24,7 +24,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_bulk_decode_clips_mel",
                 "pdmp3_amd_fbank_check", "pdmp3_amd_fbank_dft_length", "pdmp3_amd_fbank_table", "pdmp3_amd_fbank_filterbank", "pdmp3_amd_fbank_valid",
                 "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank",
-                "pdmp3_amd_mfcc_check", "pdmp3_amd_mfcc_dct_table", "pdmp3_amd_mfcc_tile", "pdmp3_amd_bulk_decode_clips_mfcc"]
+                "pdmp3_amd_mfcc_check", "pdmp3_amd_mfcc_dct_table", "pdmp3_amd_mfcc_tile", "pdmp3_amd_bulk_decode_clips_mfcc",
+                "pdmp3_amd_stft_check", "pdmp3_amd_stft_table", "pdmp3_amd_stft_tile", "pdmp3_amd_bulk_decode_clips_stft"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -155,6 +156,12 @@ def load_library():
         lib.pdmp3_amd_mfcc_dct_table.restype = ll
         lib.pdmp3_amd_mfcc_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_mfcc.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_stft"):     # (the short-time Fourier transform of clips: absent from older builds)
+        lib.pdmp3_amd_stft_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_stft_table.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_stft_table.restype = ll
+        lib.pdmp3_amd_stft_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_stft.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -546,6 +553,62 @@ def mfcc_tile(win_length, n_dft, hop, num_mel_bins, num_ceps):
     if load_library().pdmp3_amd_mfcc_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), int(num_ceps), C.byref(t), C.byref(p),
                                           C.byref(b)) != 0:
         raise ValueError("pdmp3_amd_mfcc_tile: bad argument")
+    return t.value, p.value, b.value
+
+
+class _StftSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_stft_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("win_length", C.c_int), ("window", C.c_void_p), ("normalized", C.c_int), ("n_frames", C.c_longlong), ("out_mode", C.c_int),
+                ("floor", C.c_double)]
+
+
+STFT_MODES = {"complex": 0, "magnitude": 1, "power": 2, "log": 3, "ln": 3, "log10": 4}
+
+
+def _stft_spec(n_frames=1, sample_rate=16000, n_fft=400, hop=160, win_length=None, window=None, normalized=False, mode="complex", floor=1e-10,
+               channels=1, width=0, rolloff=0.0):
+    """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
+    w = None
+    if window is not None:
+        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
+        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
+            raise ValueError("stft: window must hold win_length values")
+        win_length = w.size
+    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    spec = _StftSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, w.ctypes.data if w is not None else None,
+                     int(bool(normalized)), int(n_frames), STFT_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+    return spec, w
+
+
+def stft_check(sample_rate=16000, **kw):
+    """pdmp3_amd_stft_check -> True when pdmp3_amd_bulk_decode_clips_stft would accept these numbers (decode_clips_stft's
+    argument names) at sample_rate"""
+    try:
+        spec, keep = _stft_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError):
+        return False
+    return load_library().pdmp3_amd_stft_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def stft_table(n_fft=400, win_length=None, window=None, normalized=False):
+    """pdmp3_amd_stft_table -> float32 numpy [rows, 2 Kp] as k_clip_stft reads it: row n, s w[n] cos at column k, -s w[n] sin at
+    column Kp + k, zeros outside the window's support and in the padding"""
+    lib = load_library()
+    spec, keep = _stft_spec(n_fft=n_fft, win_length=win_length, window=window, normalized=normalized)
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_stft_table(C.byref(spec), None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_stft_table: bad argument")
+    t = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_stft_table(C.byref(spec), t.ctypes.data_as(C.c_void_p), t.size, None, None)
+    return t
+
+
+def stft_tile(n_fft, hop, mode="complex"):
+    """pdmp3_amd_stft_tile -> (frames of a workgroup of k_clip_stft, LDS floats between two hops, LDS bytes of a workgroup)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
+    if load_library().pdmp3_amd_stft_tile(int(n_fft), int(hop), m, C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_stft_tile: bad argument")
     return t.value, p.value, b.value
 
 
@@ -975,6 +1038,69 @@ class BulkDecoder:
             raise e
         if rc != 0:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_mfcc failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
+
+    def decode_clips_stft(self, clips, n_frames, sample_rate=16000, n_fft=400, hop=160, win_length=None, window=None, normalized=False,
+                          mode="complex", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_stft: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        the short-time Fourier transform [K, C, n_fft // 2 + 1, n_frames], frame f of a clip centred on sample start + f hop of the
+        stream resampled as decode_clips_audio does (width, rolloff), zeros outside the stream and no reflection: torch.stft with
+        center=False on the span from start - n_fft // 2 on.  window: win_length values (numpy or torch), None: the periodic
+        Hann window of win_length (None: n_fft), centred in n_fft as torch.stft does; normalized: scaled by n_fft ** -0.5.
+        mode "complex" (complex64) / "magnitude" / "power" / "log" / "log10" (float32; floor clamps the power of the last
+        two).  valid[k] = frames of row k whose centre lies inside the stream.  out: a torch tensor on the decoder's device
+        (made when not given; rows and channels may be strided) or a numpy array; mode "complex": complex64 [K, C, bins, F]
+        or float32 [K, C, bins, F, 2].  Synchronous.  RingReplay / MixedFormat (with .out and .valid) as decode_clips_audio."""
+        k, f, nb = len(clips), int(n_frames), int(n_fft) // 2 + 1
+        m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_stft: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, nb, f), dtype=torch.complex64 if m == 0 else torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        # the destination as float32 [K, C, bins, F] (mode "complex": [K, C, bins, F, 2]): a view of the caller's memory
+        if hasattr(out, "data_ptr"):
+            import torch
+            v = torch.view_as_real(out) if out.is_complex() else out
+            assert v.dtype == torch.float32
+            shape, strides, base = tuple(v.shape), tuple(v.stride()), v.data_ptr()
+        else:
+            v = out.view(np.float32).reshape(out.shape + (2,)) if out.dtype == np.complex64 else out
+            assert v.dtype == np.float32 and all(s % 4 == 0 for s in v.strides)
+            shape, strides, base = v.shape, tuple(s // 4 for s in v.strides), v.ctypes.data
+        inner = (nb, f, 2) if m == 0 else (nb, f)
+        assert len(shape) == 2 + len(inner) and shape[1:] == (c,) + inner and shape[0] >= k
+        want = 1
+        for n, s in zip(reversed(inner), reversed(strides[2:])):                       # (a row's floats are dense)
+            assert n <= 1 or s == want or nb * f == 0
+            want *= n
+        s0, s1 = strides[0] * 4, strides[1]
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        try:
+            spec, wkeep = _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
+        except ValueError as e:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_stft: %s" % e)
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_stft(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_stft failed (a bad argument, a decoder without device Huffman, switches "
                                "that differ from an index's, or an engine failure)")
         return out, valid
 

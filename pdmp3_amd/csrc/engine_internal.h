@@ -149,5 +149,7 @@ hipError_t pdmp3_launch_clip_fbank(hipStream_t s, const pdmp3_fbank_desc* descs,
 // ---- mfcc.hip ----
 hipError_t pdmp3_launch_clip_mfcc(hipStream_t s, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt, const float* dct,
                                   float* sums, const pdmp3_mfcc_params* params);
+// ---- stft.hip ----
+hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_stft_params* params);
 
 #endif

@@ -49,7 +49,7 @@ struct pdmp3_hip_stream {
   int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
   void* d_audio[3]; size_t audio_cap[3];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call
   uint8_t* d_audio_args; size_t audio_args_cap;   // ... and a launch's descriptors | frame table | filter tables
-  uint8_t* d_mel_args; size_t mel_args_cap;       // log-mel features: a launch's descriptors | row maxima | DFT table | filterbank
+  uint8_t* d_mel_args; size_t mel_args_cap;       // log-mel features: a launch's descriptors | row maxima | DFT table | filterbank; the STFT call: descriptors | folded table
   uint8_t* d_fbank_args; size_t fbank_args_cap;   // Kaldi-style features (fbank, mfcc): a launch's descriptors | tables | column sums
 };
 
@@ -647,6 +647,48 @@ extern "C" int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_me
                                   reinterpret_cast<const float*>(a + desc_bytes + max_bytes), reinterpret_cast<const float*>(a + desc_bytes + max_bytes + dft_bytes),
                                   reinterpret_cast<unsigned*>(a + desc_bytes) + k, &P),
             "launch k_clip_mel");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+// ---- the short-time Fourier transform (stft.hip) ----
+extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table,
+                                   const pdmp3_stft_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !table || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: bad argument", hipSuccess);
+  const pdmp3_stft_params& P = *params;
+  // what the kernel's indexing relies on
+  if (P.n_fft < 16 || P.n_fft > 1024 || (P.n_fft & 1) || P.rows != ((P.n_fft + 3) & ~3) || P.hop < 1 || P.hop > P.n_fft || P.row_pad < 0 ||
+      P.bins != P.n_fft / 2 + 1 || P.bins16 != ((P.bins + 15) & ~15) || (P.tile != 16 && P.tile != 32) || (P.channels != 1 && P.channels != 2) ||
+      P.out_mode < 0 || P.out_mode > 4 || P.n_frames < 0 || P.n_in < 0 || (P.out_mode >= 3 && !(P.floor > 0.0f)) || (P.span_floats & 3u) ||
+      P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: bad parameters", hipSuccess);
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.rows, chunks = (span + P.hop - 1) / P.hop;
+    const size_t stage = (size_t)4 * (P.out_mode == 0 ? 2 : 1) * 16 * (size_t)(P.tile + 4);
+    if (P.span_floats < chunks * (size_t)(P.hop + P.row_pad) || (size_t)P.lds_bytes < ((size_t)P.span_floats + stage) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: a tile's span and staging tiles do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: too many frames", hipSuccess);
+  }
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | folded table: one block (the log-mel call's; the two never overlap in time), each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
+  const size_t tab_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
+  { void* p = hs->d_mel_args;
+    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc stft tables");
+    hs->d_mel_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_mel_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D stft descriptors");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes, table, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft table");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_stft(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                   reinterpret_cast<const float*>(a + desc_bytes), &P),
+            "launch k_clip_stft");
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }

@@ -82,6 +82,9 @@ typedef struct fbank_tab {
 /* Kaldi-style MFCC features (clip_mfcc.c): a folded DCT table as k_clip_mfcc reads it ([mels16][ceps16]) per (n_mels,
  * num_ceps, cepstral_lifter, htk_compat, use_energy) */
 typedef struct mfcc_tab { int n_mels, n_ceps, htk, energy; double lifter; float* t; struct mfcc_tab* next; } mfcc_tab;
+/* the short-time Fourier transform (clip_stft.c): a folded table per (N, Nw, normalized, the window's values: a copy of the
+ * caller's, NULL for the Hann window); a short list, the most recently used first */
+typedef struct stft_tab { int n_fft, win, normalized; float* window; float* t; struct stft_tab* next; } stft_tab;
 
 struct bulk {
   pdmp3_handle* id;
@@ -188,6 +191,7 @@ struct bulk {
   struct mel_tab* mel_tabs;           /* log-mel features: the DFT tables and filterbanks made so far */
   struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
   struct mfcc_tab* mfcc_tabs;         /* Kaldi-style MFCC features: the folded DCT tables made so far */
+  struct stft_tab* stft_tabs;         /* the short-time Fourier transform: the last PDMP3_STFT_TABLES folded tables */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -350,6 +354,11 @@ HOST_LOCAL int fbank_plan(int win, int n_dft, int hop, int n_mels, pdmp3_fbank_p
 /* clip_mfcc.c: the folded DCT table [mels16][ceps16] of a spec the check accepts; the plan of a workgroup of k_clip_mfcc */
 HOST_LOCAL void mfcc_dct_fill(const pdmp3_amd_mfcc_spec* s, float* t);
 HOST_LOCAL int mfcc_plan(int win, int n_dft, int hop, int n_mels, int n_ceps, pdmp3_mfcc_params* q);
+/* clip_stft.c: the folded table of a spec the check accepts, the plan of a workgroup of k_clip_stft (0, or -1) and the
+ * decoder's table of the spec (NULL: no memory) */
+HOST_LOCAL void stft_table_fill(const pdmp3_amd_stft_spec* s, float* t);
+HOST_LOCAL int stft_plan(int n_fft, int hop, int out_mode, pdmp3_stft_params* p);
+HOST_LOCAL const float* stft_table(struct bulk* b, const pdmp3_amd_stft_spec* s);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

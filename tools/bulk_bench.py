@@ -17,6 +17,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
   python tools/bulk_bench.py --clips 1 --clip-frames 191 --c3
   python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mel                     (clips_mel(): log-mel features, 30 s a clip)
+  python tools/bulk_bench.py --clips 64 --clip-frames 1149 --stft                    (clips_stft(): the short-time Fourier transform)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --fbank                   (clips_fbank(): Kaldi-style filterbank features)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mfcc                    (clips_mfcc(): Kaldi-style MFCC features)
 """
@@ -380,6 +381,100 @@ def clips_mel(args, api):
     print(json.dumps(res))
 
 
+def clips_stft(args, api):
+    """--clips K --clip-frames F --stft: the clips of clips() (same seed, same places), F MPEG-1 frames' length each, as their
+    short-time Fourier transform [K, 1, 201, frames] complex64 at 16 kHz mono (n_fft 400, hop 160, periodic Hann) in device
+    memory, three ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the samples the frames read (the call
+    the new call makes itself); (b) (a) followed by torch.stft on the device (the same window, center=False on the padded
+    span): what a loader does today; a dense matmul against the same table where torch.stft cannot run; (c)
+    pdmp3_amd_bulk_decode_clips_stft.  (b) and (c) are compared once (largest difference, printed, not asserted: the tests
+    check (c) against the definition).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop = args.clips, args.clip_frames, 16000, 400, 160
+    bins = n_fft // 2 + 1
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    Fm = (F * 1152 * rate // 44100) // hop
+    T = (Fm - 1) * hop + n_fft
+    dev = "cuda:0"
+    stft, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        stft.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - n_fft // 2))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_t = torch.zeros((K, 1, bins, Fm), dtype=torch.complex64, device=dev)
+    out_s = torch.zeros((K, 1, bins, Fm), dtype=torch.complex64, device=dev)
+    window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32, device=dev)
+    kp = (bins + 15) // 16 * 16
+    table = torch.from_numpy(api.stft_table(n_fft)[:n_fft]).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    how = {"stft": "torch.stft"}
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+        y = out_a[:, 0]
+        if how["stft"] == "torch.stft":
+            try:
+                out_t[:, 0] = torch.stft(y, n_fft, hop_length=hop, window=window, center=False, return_complex=True)       # [K, bins, Fm]
+            except Exception as e:                      # noqa: BLE001  (no FFT library on this build)
+                how["stft"] = "dense matmul against the table (torch.stft: %s)" % type(e).__name__
+        if how["stft"] != "torch.stft":
+            x = y.unfold(1, n_fft, hop) @ table                                                                          # [K, Fm, 2 Kp]
+            out_t[:, 0] = torch.complex(x[:, :, :bins], x[:, :, kp:kp + bins]).transpose(1, 2)
+        torch.cuda.synchronize()
+
+    def stft_route():
+        dec.decode_clips_stft(stft, Fm, rate, n_fft, hop, out=out_s)
+
+    routes = [("audio clips", audio_route), ("audio clips + torch.stft", torch_route), ("stft clips", stft_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = float((out_t - out_s).abs().max())
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as %d frames x %d bins complex64 at %d Hz mono (n_fft %d, hop %d): %s" % (
+               K, F, Fm, bins, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
+           "largest_difference_of_the_two_results": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    res["stft_minus_audio_ms"] = round((med["stft clips"] - med["audio clips"]) * 1e3, 3)
+    res["torch_minus_audio_ms"] = round((med["audio clips + torch.stft"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(spread * 1e3, 3)
+    res["stft_cheaper_than_torch_stft_by_more_than_the_spread"] = bool(med["audio clips + torch.stft"] - med["stft clips"] > spread)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -592,6 +687,9 @@ def main():
     ap.add_argument("--mel", action="store_true",
                     help="--clips: the clips as log-mel features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mel) against the audio call "
                          "for the same samples and against that call followed by torch kernels (see clips_mel())")
+    ap.add_argument("--stft", action="store_true",
+                    help="--clips: the clips' short-time Fourier transform at 16 kHz mono (pdmp3_amd_bulk_decode_clips_stft) against the audio "
+                         "call alone and the audio call followed by torch.stft")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -601,6 +699,8 @@ def main():
     args = ap.parse_args()
     if args.clips:
         from pdmp3_amd import api
+        if args.stft:
+            return clips_stft(args, api)
         if args.mfcc:
             return clips_mfcc(args, api)
         if args.fbank:
