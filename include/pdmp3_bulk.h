@@ -521,8 +521,9 @@ int pdmp3_amd_bulk_decode_clips_mfcc(pdmp3_amd_bulk* b, const pdmp3_amd_audio_cl
  * stream's end are the transform of zeros.
  * The coefficients s w[n] cos and -s w[n] sin are computed on the host in binary64 from the binary32 window values and
  * rounded once; the GPU multiplies and adds in binary32 (v_mfma_f32_16x16x4_f32), the square root is correctly rounded.
- * Not offered: n_fft above 1024 (the transform is a matrix product, N^2 a frame), the inverse transform, reflection at a
- * stream's ends, a frames-major layout. */
+ * Not offered here: n_fft above 1024 (the transform is a matrix product, N^2 a frame; n_fft 2048 and 4096 are served by the
+ * two-stage calls below, pdmp3_amd_stft_long_*), the inverse transform, reflection at a stream's ends, a frames-major
+ * layout. */
 typedef struct {
   long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec */
   int n_fft, hop, win_length;                           /* win_length 0 = n_fft */
@@ -556,6 +557,50 @@ int pdmp3_amd_stft_tile(int n_fft, int hop, int out_mode, int* tile, int* row_pa
 #define PDMP3_STFT_TABLES 4
 int pdmp3_amd_bulk_decode_clips_stft(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_stft_spec* spec,
                                      long long* valid);
+
+/* ---- The short-time Fourier transform of clips at n_fft 2048 and 4096 ----
+ * The definition of the section above, unchanged, on a wider domain: the same spec struct, signal, clip, framing, valid[k],
+ * window rules (win_length 0 .. N, the caller's binary32 window or periodic Hann, centred as torch.stft centres it),
+ * `normalized`, the five output modes with their floor rules and the same layouts, bins = N / 2 + 1.  What differs: n_fft is
+ * 2048 or 4096 only (hop 1 .. n_fft); a window length that is no power of two -- 1764, 1920 -- is a shorter window inside
+ * the next power of two.  New entry points only: the calls above keep refusing n_fft = 2048.
+ * The arithmetic.  N = 64 N2 (N2 = 32 or 64), n = N2 n1 + n2, k = k1 + 64 k2; all tables are computed on the host in
+ * binary64, every angle reduced as an integer modulo its period, and rounded once to binary32.
+ *   0. wt[n] = fl32(s w[n]), 0 outside the window's support; xw[n] = wt[n] y[n], one binary32 product a sample.
+ *   1. Y[n2][k1] = sum over n1 < 64 of xw[N2 n1 + n2] e^(-2 pi i n1 k1 / 64), k1 < 64: real by complex on
+ *      v_mfma_f32_16x16x4_f32, one fused multiply-add chain for Re and one for Im, n1 ascending.
+ *   2. Z = Y T, T[n2][k1] = fl32(e^(-2 pi i n2 k1 / N)):  Zr = fma(Yr, Tr, -(Yi Ti)),  Zi = fma(Yr, Ti, Yi Tr).
+ *   3. X[k1 + 64 k2] = sum over n2 < N2 of Z[n2][k1] e^(-2 pi i n2 k2 / N2), k2 < N2 / 2: Re and Im are each ONE fused
+ *      multiply-add chain over the 2 N2 real terms in the order n2 ascending, Zr's term before Zi's: with a = 2 pi n2 k2 / N2,
+ *      Re takes Zr cos a, then Zi sin a; Im takes Zr (-sin a), then Zi cos a.  The Nyquist bin N / 2 is the same chain at
+ *      k1 = 0, k2 = N2 / 2, whose coefficients are exact: (-1)^n2 for the cosine, 0 for the sine.
+ *   4. What is stored is section 13's: the pair, the correctly rounded square root, the power fma(Im, Im, Re Re), logf, log10f.
+ * Every frame's values come from the same chains whatever its place in a tile or clip, and Im of bins 0 and N / 2 is exactly
+ * zero (the sine coefficients there are exact zeros). */
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: as pdmp3_amd_stft_check, with n_fft 2048 or
+ * 4096 only. */
+int pdmp3_amd_stft_long_check(const pdmp3_amd_stft_spec* spec, long sr);
+/* The four tables of the spec's frame, one behind the other as the kernel reads them, with their shapes in shapes[8] (rows,
+ * columns of each; may be NULL): wt [1][N]; the 64-point DFT [64][128], cos(2 pi n1 k1 / 64) at column k1 and -sin at column
+ * 64 + k1; the N2-point half DFT [2 N2][N2], row 2 n2 + part, columns k2 < N2 / 2 Re's coefficients (cos a for part 0, sin a
+ * for part 1) and columns N2 / 2 + k2 Im's (-sin a, cos a); the twiddles [N2][128], cos(2 pi n2 k1 / N) at column k1 and
+ * -sin at column 64 + k1.  Only n_fft, win_length, window and normalized are read.  Returns the floats of all four and
+ * writes min(that, cap) of them; -1 on a bad argument. */
+long long pdmp3_amd_stft_long_tables(const pdmp3_amd_stft_spec* spec, float* tables, size_t cap, int* shapes);
+/* What a workgroup of k_clip_stft_long takes, the function the call itself uses.  A workgroup of eight waves takes *tile
+ * frames and 16 of the 64 values of k1: 16 frames where the LDS below fits PDMP3_MEL_LDS_MAX (include/pdmp3_hip.h), else 8,
+ * else 4.  The LDS bytes: a first region of max((tile - 1) hop + n_fft, (out_mode 0 ? 2 : 1) x 16 x N2 / 2 x (tile + 1))
+ * floats rounded up to 4 -- the tile's span, later the staging tile -- then Z, tile x N2 x 32 floats.  *row_pad is 0: the
+ * span lies plain in LDS.  Every plan is above 64 KB and runs on a static array.  0, or -1 on a bad argument.  Pointers may
+ * be NULL. */
+int pdmp3_amd_stft_long_plan(int n_fft, int hop, int out_mode, int* tile, int* row_pad, unsigned* lds_bytes);
+/* pdmp3_amd_bulk_decode_clips_stft in everything -- rows, destinations, the audio call in front, the stages, the per-clip
+ * refusals in valid[k], rate 0 / channels 0, the counts, n_clips = 0 and n_frames = 0 -- with the check above and
+ * k_clip_stft_long (csrc/stft_long.hip) writing the rows.  The decoder makes the three tables that depend on n_fft alone
+ * once per n_fft and keeps them for its life (two sets at most); wt is filled on every call.  -1 also where
+ * pdmp3_amd_stft_long_check says so. */
+int pdmp3_amd_bulk_decode_clips_stft_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_stft_spec* spec,
+                                          long long* valid);
 
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the

@@ -594,6 +594,28 @@ typedef struct pdmp3_stft_params {
 int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table,
                         const pdmp3_stft_params* params);
 
+/* The short-time Fourier transform of clips at n_fft 2048 and 4096 (include/pdmp3_bulk.h
+ * pdmp3_amd_bulk_decode_clips_stft_long).  k_clip_stft_long (stft_long.hip) reads the rows as
+ * k_clip_stft does (pdmp3_mel_desc) and writes the same layouts.  N = 64 n2; a workgroup of eight waves takes `tile` frames
+ * and 16 of the 64 values of k1.  Its LDS: span_floats for the tile's span, plain ((tile - 1) hop + n_fft floats; later the
+ * staging tile of (out_mode 0 ? 2 : 1) x 16 x n2 / 2 x (tile + 1) floats), then Z: tile x n2 x 32 floats. */
+typedef struct pdmp3_stft_long_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t n_fft, n2;                        /* N: 2048 or 4096; N / 64                                                  */
+  int32_t hop, bins;                        /* H; K = N / 2 + 1                                                         */
+  int32_t n_frames, tile;                   /* F; frames of a workgroup: 16 or 8 (N 2048), 8 or 4 (N 4096)              */
+  int32_t channels, out_mode;               /* out_mode 0 complex, 1 magnitude, 2 power, 3 ln, 4 log10                  */
+  float floor;                              /* of the logarithms (modes 3 and 4)                                        */
+  uint32_t span_floats;                     /* LDS floats of the first region, a multiple of 4                          */
+  uint32_t lds_bytes;
+} pdmp3_stft_long_params;
+/* Uploads the descriptors and the four tables (one block of n_fft + 8192 + 2 n2^2 + 128 n2 floats: wt, the 64-point DFT, the
+ * n2-point half DFT, the twiddles; csrc/stft_long_core.h has the layouts) -- host memory -- and runs k_clip_stft_long on the
+ * slot's HIP stream.  lds_bytes <= PDMP3_MEL_LDS_MAX: the kernel has a static array of that size.  Blocks until the rows are
+ * written. */
+int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                             const pdmp3_stft_long_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

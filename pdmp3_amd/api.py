@@ -25,7 +25,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_fbank_check", "pdmp3_amd_fbank_dft_length", "pdmp3_amd_fbank_table", "pdmp3_amd_fbank_filterbank", "pdmp3_amd_fbank_valid",
                 "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank",
                 "pdmp3_amd_mfcc_check", "pdmp3_amd_mfcc_dct_table", "pdmp3_amd_mfcc_tile", "pdmp3_amd_bulk_decode_clips_mfcc",
-                "pdmp3_amd_stft_check", "pdmp3_amd_stft_table", "pdmp3_amd_stft_tile", "pdmp3_amd_bulk_decode_clips_stft"]
+                "pdmp3_amd_stft_check", "pdmp3_amd_stft_table", "pdmp3_amd_stft_tile", "pdmp3_amd_bulk_decode_clips_stft",
+                "pdmp3_amd_stft_long_check", "pdmp3_amd_stft_long_tables", "pdmp3_amd_stft_long_plan", "pdmp3_amd_bulk_decode_clips_stft_long"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -162,6 +163,12 @@ def load_library():
         lib.pdmp3_amd_stft_table.restype = ll
         lib.pdmp3_amd_stft_tile.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_stft.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_stft_long"):    # (... at n_fft 2048 and 4096: absent from older builds)
+        lib.pdmp3_amd_stft_long_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_stft_long_tables.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int)]
+        lib.pdmp3_amd_stft_long_tables.restype = ll
+        lib.pdmp3_amd_stft_long_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_stft_long.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -612,6 +619,45 @@ def stft_tile(n_fft, hop, mode="complex"):
     return t.value, p.value, b.value
 
 
+def stft_long_check(sample_rate=44100, n_fft=2048, hop=512, **kw):
+    """pdmp3_amd_stft_long_check -> True when pdmp3_amd_bulk_decode_clips_stft_long would accept these numbers
+    (decode_clips_stft_long's argument names) at sample_rate"""
+    try:
+        spec, keep = _stft_spec(sample_rate=sample_rate, n_fft=n_fft, hop=hop, **kw)
+    except (ValueError, KeyError):
+        return False
+    return load_library().pdmp3_amd_stft_long_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def stft_long_tables(n_fft=2048, win_length=None, window=None, normalized=False):
+    """pdmp3_amd_stft_long_tables -> the four float32 tables of the two-stage transform as k_clip_stft_long reads them:
+    (wt [N], the 64-point DFT [64, 128], the N2-point half DFT [2 N2, N2], the twiddles [N2, 128]), N2 = n_fft // 64"""
+    lib = load_library()
+    spec, keep = _stft_spec(n_fft=n_fft, hop=n_fft, win_length=win_length, window=window, normalized=normalized)
+    shapes = (C.c_int * 8)()
+    count = lib.pdmp3_amd_stft_long_tables(C.byref(spec), None, 0, shapes)
+    if count < 0:
+        raise ValueError("pdmp3_amd_stft_long_tables: bad argument")
+    t = np.full(count, np.nan, dtype=np.float32)
+    lib.pdmp3_amd_stft_long_tables(C.byref(spec), t.ctypes.data_as(C.c_void_p), t.size, None)
+    out, at = [], 0
+    for i in range(4):
+        n = shapes[2 * i] * shapes[2 * i + 1]
+        out.append(t[at:at + n].reshape((shapes[2 * i], shapes[2 * i + 1]) if i else (n,)))
+        at += n
+    assert at == count
+    return tuple(out)
+
+
+def stft_long_plan(n_fft, hop, mode="complex"):
+    """pdmp3_amd_stft_long_plan -> (frames of a workgroup of k_clip_stft_long, 0, LDS bytes of a workgroup)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
+    if load_library().pdmp3_amd_stft_long_plan(int(n_fft), int(hop), m, C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_stft_long_plan: bad argument")
+    return t.value, p.value, b.value
+
+
 class StreamIndex:
     """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
     built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
@@ -1052,13 +1098,25 @@ class BulkDecoder:
         two).  valid[k] = frames of row k whose centre lies inside the stream.  out: a torch tensor on the decoder's device
         (made when not given; rows and channels may be strided) or a numpy array; mode "complex": complex64 [K, C, bins, F]
         or float32 [K, C, bins, F, 2].  Synchronous.  RingReplay / MixedFormat (with .out and .valid) as decode_clips_audio."""
+        return self._clips_stft("stft", clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width,
+                                rolloff, out)
+
+    def decode_clips_stft_long(self, clips, n_frames, sample_rate=44100, n_fft=2048, hop=512, win_length=None, window=None, normalized=False,
+                               mode="complex", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_stft_long: decode_clips_stft in everything -- arguments, definition, modes, out, valid,
+        exceptions -- at n_fft 2048 or 4096 (hop 1 .. n_fft; win_length 1764 or 1920 is a shorter window inside 2048), computed
+        as a two-stage transform by k_clip_stft_long."""
+        return self._clips_stft("stft_long", clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels,
+                                width, rolloff, out)
+
+    def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out):
         k, f, nb = len(clips), int(n_frames), int(n_fft) // 2 + 1
         m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
         c = int(channels)
         if not c:
             cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
             if len(cs) > 1:
-                raise ValueError("decode_clips_stft: channels=0 and the clips' channel counts differ")
+                raise ValueError("decode_clips_%s: channels=0 and the clips' channel counts differ" % call)
             c = cs.pop() if cs else 1
         if out is None:
             import torch
@@ -1090,9 +1148,9 @@ class BulkDecoder:
         try:
             spec, wkeep = _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
         except ValueError as e:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_stft: %s" % e)
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s: %s" % (call, e))
         got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_stft(self.h, arr, k, C.byref(spec), got)
+        rc = getattr(self.lib, "pdmp3_amd_bulk_decode_clips_" + call)(self.h, arr, k, C.byref(spec), got)
         valid = np.array(got[:k], dtype=np.int64)
         if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
             e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
@@ -1100,8 +1158,8 @@ class BulkDecoder:
             e.valid, e.out = valid, out
             raise e
         if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_stft failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)" % call)
         return out, valid
 
     def clip_stats(self):

@@ -692,6 +692,49 @@ extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_m
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }
+// ---- the short-time Fourier transform at n_fft 2048 and 4096 (stft_long.hip) ----
+extern "C" int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                                        const pdmp3_stft_long_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !tables || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: bad argument", hipSuccess);
+  const pdmp3_stft_long_params& P = *params;
+  // what the kernel's indexing relies on
+  if ((P.n_fft != 2048 && P.n_fft != 4096) || P.n2 != P.n_fft / 64 || P.hop < 1 || P.hop > P.n_fft || P.bins != P.n_fft / 2 + 1 ||
+      (P.tile != 16 && P.tile != 8 && P.tile != 4) || (P.n2 == 32 && P.tile == 4) || (P.n2 == 64 && P.tile == 16) ||
+      (P.channels != 1 && P.channels != 2) || P.out_mode < 0 || P.out_mode > 4 || P.n_frames < 0 || P.n_in < 0 ||
+      (P.out_mode >= 3 && !(P.floor > 0.0f)) || (P.span_floats & 3u) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: bad parameters", hipSuccess);
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.n_fft;
+    const size_t stage = (size_t)(P.out_mode == 0 ? 2 : 1) * 16 * (size_t)(P.n2 / 2) * (size_t)(P.tile + 1);
+    const size_t z = (size_t)P.tile * P.n2 * 32;
+    if (P.span_floats < span || P.span_floats < stage || (size_t)P.lds_bytes < ((size_t)P.span_floats + z) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: a tile's span, staging tile and Z do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * 4 * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: too many frames", hipSuccess);
+  }
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | the four tables: one block (the log-mel call's; the calls never overlap in time), each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
+  const size_t tab_bytes = ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float);
+  { void* p = hs->d_mel_args;
+    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc stft tables");
+    hs->d_mel_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_mel_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D stft descriptors");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes, tables, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft tables");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_stft_long(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                        reinterpret_cast<const float*>(a + desc_bytes), &P),
+            "launch k_clip_stft_long");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
                                     const pdmp3_fbank_params* params) {

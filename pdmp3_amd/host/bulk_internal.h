@@ -192,6 +192,7 @@ struct bulk {
   struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
   struct mfcc_tab* mfcc_tabs;         /* Kaldi-style MFCC features: the folded DCT tables made so far */
   struct stft_tab* stft_tabs;         /* the short-time Fourier transform: the last PDMP3_STFT_TABLES folded tables */
+  float* stft_long_tabs[2];           /* ... at n_fft 2048 and 4096: a call's block of tables, made once; its wt is filled per call */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -359,6 +360,10 @@ HOST_LOCAL int mfcc_plan(int win, int n_dft, int hop, int n_mels, int n_ceps, pd
 HOST_LOCAL void stft_table_fill(const pdmp3_amd_stft_spec* s, float* t);
 HOST_LOCAL int stft_plan(int n_fft, int hop, int out_mode, pdmp3_stft_params* p);
 HOST_LOCAL const float* stft_table(struct bulk* b, const pdmp3_amd_stft_spec* s);
+/* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
+ * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
+HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);
+HOST_LOCAL const float* stft_long_tables(struct bulk* b, const pdmp3_amd_stft_spec* s);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

@@ -18,6 +18,7 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
   python tools/bulk_bench.py --clips 64 --clip-frames 191 --audio 16000 [--mono]     (clips_audio(): the float batch at one rate)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mel                     (clips_mel(): log-mel features, 30 s a clip)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --stft                    (clips_stft(): the short-time Fourier transform)
+  python tools/bulk_bench.py --stft-long                                             (clips_stft(long=True): 64 clips of 30 s at 44.1 kHz, n_fft 2048, hop 512)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --fbank                   (clips_fbank(): Kaldi-style filterbank features)
   python tools/bulk_bench.py --clips 64 --clip-frames 1149 --mfcc                    (clips_mfcc(): Kaldi-style MFCC features)
 """
@@ -381,8 +382,10 @@ def clips_mel(args, api):
     print(json.dumps(res))
 
 
-def clips_stft(args, api):
-    """--clips K --clip-frames F --stft: the clips of clips() (same seed, same places), F MPEG-1 frames' length each, as their
+def clips_stft(args, api, long=False):
+    """--stft-long (long): the same three routes for 64 clips of 30 s (--clips / --clip-frames change that) at 44.1 kHz mono,
+    n_fft 2048, hop 512, complex, with pdmp3_amd_bulk_decode_clips_stft_long as route (c).  Asserts nothing.
+    --clips K --clip-frames F --stft: the clips of clips() (same seed, same places), F MPEG-1 frames' length each, as their
     short-time Fourier transform [K, 1, 201, frames] complex64 at 16 kHz mono (n_fft 400, hop 160, periodic Hann) in device
     memory, three ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the samples the frames read (the call
     the new call makes itself); (b) (a) followed by torch.stft on the device (the same window, center=False on the padded
@@ -400,6 +403,8 @@ def clips_stft(args, api):
     ixs = [api.StreamIndex(f) for f in files]
     rng = random.Random(args.seed)
     K, F, rate, n_fft, hop = args.clips, args.clip_frames, 16000, 400, 160
+    if long:
+        rate, n_fft, hop = 44100, 2048, 512
     bins = n_fft // 2 + 1
     sel = []
     for _ in range(K):
@@ -420,7 +425,12 @@ def clips_stft(args, api):
     out_s = torch.zeros((K, 1, bins, Fm), dtype=torch.complex64, device=dev)
     window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32, device=dev)
     kp = (bins + 15) // 16 * 16
-    table = torch.from_numpy(api.stft_table(n_fft)[:n_fft]).to(dev)
+    if long:                                            # (the direct table at this length, for the fallback of route (b) alone)
+        ang = 2.0 * np.pi * ((np.arange(n_fft)[:, None] * np.arange(kp)[None, :]) % n_fft) / n_fft
+        w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft))[:, None]
+        table = torch.from_numpy(np.concatenate([w * np.cos(ang), -w * np.sin(ang)], axis=1).astype(np.float32)).to(dev)
+    else:
+        table = torch.from_numpy(api.stft_table(n_fft)[:n_fft]).to(dev)
     dec = api.BulkDecoder(threads=args.clip_threads)
     torch.cuda.synchronize()
     how = {"stft": "torch.stft"}
@@ -442,7 +452,7 @@ def clips_stft(args, api):
         torch.cuda.synchronize()
 
     def stft_route():
-        dec.decode_clips_stft(stft, Fm, rate, n_fft, hop, out=out_s)
+        (dec.decode_clips_stft_long if long else dec.decode_clips_stft)(stft, Fm, rate, n_fft, hop, out=out_s)
 
     routes = [("audio clips", audio_route), ("audio clips + torch.stft", torch_route), ("stft clips", stft_route)]
     times = {name: [] for name, _ in routes}
@@ -690,6 +700,9 @@ def main():
     ap.add_argument("--stft", action="store_true",
                     help="--clips: the clips' short-time Fourier transform at 16 kHz mono (pdmp3_amd_bulk_decode_clips_stft) against the audio "
                          "call alone and the audio call followed by torch.stft")
+    ap.add_argument("--stft-long", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as their short-time Fourier transform at 44.1 kHz mono, n_fft 2048, "
+                         "hop 512 (pdmp3_amd_bulk_decode_clips_stft_long) against the audio call alone and the audio call followed by torch.stft")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -697,10 +710,14 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
+    if args.stft_long:
+        args.clips = args.clips or 64
+        if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
+            args.clip_frames = 1149
     if args.clips:
         from pdmp3_amd import api
-        if args.stft:
-            return clips_stft(args, api)
+        if args.stft or args.stft_long:
+            return clips_stft(args, api, long=args.stft_long)
         if args.mfcc:
             return clips_mfcc(args, api)
         if args.fbank:
