@@ -197,3 +197,50 @@ def fbank(y, pos0, start, n_frames, nw, hop, w, n_valid, round_pow2=True, remove
         outs.append(out)
         bounds.append(bound)
     return np.stack(outs), np.stack(bounds)
+
+
+# ---- the plan of a workgroup of k_clip_fbank restated, and the classes of a geometry ("launch forms") ----
+def form(nw, n, hop, n_mels):
+    """-> (tile, row_pad, lds_bytes, classes): clip_mel_ref.form with this kernel's rows (Nw rounded up to 4) and bins (N / 2
+    rounded up to 16, no Nyquist bin)"""
+    import clip_mel_ref as mref
+    rows, kp, mp = (nw + 3) // 4 * 4, (n // 2 + 15) // 16 * 16, (n_mels + 15) // 16 * 16
+    for tile in (32, 16):
+        first, what = mref.plan_first(rows, hop, mp, tile)
+        lds = (first + tile * (kp + 2)) * 4
+        if lds <= mref.LDS_SOFT:
+            break
+    assert lds <= mref.LDS_MAX
+    c = {mref.launch_of(tile, lds), what} | mref.shape_classes(nw, rows, hop, kp, n_mels)
+    if mref.LDS_SOFT - 64 < lds <= mref.LDS_SOFT:
+        c.add("edge-64k")
+    return tile, (2 - hop) % 32, lds, c
+
+
+def _e(win, hop, n_mels, rate, stream, channels=1, **options):
+    return dict(dict(win_length=win, hop=hop, num_mel_bins=n_mels, sample_rate=rate, channels=channels, **options), stream=stream)
+
+
+# the shapes whose launch forms no speech front end reaches; `stream` names one of test_gpu_clip_audio's, the rest are
+# decode_clips_fbank's arguments.  (2, 1, 1) is left out on purpose: its single band has weight 0 on the only bin, so the
+# definition has nothing to compare.
+EDGES = {
+    "taco-1024-256-80-stereo": _e(1024, 256, 80, 22050, "22k", 2),                # tile16-dyn, 52 512 B
+    "551-220-80": _e(551, 220, 80, 22050, "22k"),                                 # 25 ms at 22.05 kHz, Nw odd
+    "1024-450-last-dynamic": _e(1024, 450, 80, 22050, "48k"),
+    "1024-451-first-static": _e(1024, 451, 80, 22050, "48k"),
+    "900-hop4-exactly-64k": _e(900, 4, 80, 16000, "16k-mono"),
+    "960-hop4-n-equals-nw-exactly-64k": _e(960, 4, 80, 16000, "16k-mono", round_to_power_of_two=False),
+    "401-hop3-rectangular-rho-1": _e(401, 3, 20, 16000, "32k", window_type="rectangular", preemphasis_coefficient=1.0),
+    "512-hop2-256-bands": _e(512, 2, 256, 16000, "32k", round_to_power_of_two=False),
+    "551-hop3-256-bands-hamming": _e(551, 3, 256, 16000, "48k", window_type="hamming"),       # 59 968 B
+    "18-hop1-5-bands-stereo": _e(18, 1, 5, 8000, "8k", 2, low_freq=0.0),
+    # (one tap of the window is not 0: int16-scaled, as Kaldi's input is, so that a quiet stretch stays above the floors)
+    "3-hop2-4-bands": _e(3, 2, 4, 8000, "8k", low_freq=0.0, scale=32768.0),
+    "16-hop4-1-band": _e(16, 4, 1, 8000, "8k", low_freq=0.0, scale=32768.0),
+    "64-hop5-15-bands": _e(64, 5, 15, 8000, "8k", low_freq=0.0, scale=32768.0),
+    "64-hop5-17-bands-stereo": _e(64, 5, 17, 8000, "8k", 2, low_freq=0.0, scale=32768.0),
+    "1024-hop1024-256-bands-own-rate": _e(1024, 1024, 256, 0, "44k-mono", round_to_power_of_two=False),
+}
+EXACT_EDGE = ("900-hop4-exactly-64k", "960-hop4-n-equals-nw-exactly-64k")
+WITH_EVERYTHING = dict(use_energy=True, subtract_mean=True, htk_compat=True)

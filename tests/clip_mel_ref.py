@@ -136,3 +136,76 @@ def mel(y, pos0, start, n_frames, n_fft, hop, w, mode, floor):
     out = (v + 4.0) / 4.0
     bound = (np.maximum(tl, tg) + U * np.abs(v + 4.0)) / 4.0 * (1.0 + 4.0 * U)
     return out, bound
+
+
+# ---- the plan of a workgroup of k_clip_mel restated, and the classes of a geometry ("launch forms") ----
+LDS_SOFT = 64 * 1024                               # a dynamic request ends here; above it the static-array kernel
+LDS_MAX = 160 * 1024 - 64
+ODD_BANDS = (1, 15, 17, 256)
+
+
+def plan_first(rows, hop, n_bands16, tile):
+    """the first LDS region of a tile: (floats, "span" or "mel-tile") -- the span in chunks of hop + row_pad floats, or the mel
+    tile [bands16][tile + 1] where that is larger, rounded up to 4 floats"""
+    pad = (2 - hop) % 32
+    span = -(-((tile - 1) * hop + rows) // hop) * (hop + pad)
+    mt = n_bands16 * (tile + 1)
+    return (max(span, mt) + 3) // 4 * 4, "mel-tile" if mt > span else "span"
+
+
+def launch_of(tile, lds):
+    return "tile32" if tile == 32 else "tile16-dyn" if lds <= LDS_SOFT else "tile16-static"
+
+
+def shape_classes(n, rows, hop, bins16, n_bands=None):
+    """what the lane walk, the row padding, the DFT stage's waves and the band count add to a form's classes"""
+    c = set()
+    if hop < 4:
+        c.add("hop<4")
+    if rows != n:
+        c.add("rows-padded")
+    if bins16 // 16 < 4:
+        c.add("idle-waves")
+    if n_bands in ODD_BANDS:
+        c.add("bands-%d" % n_bands)
+    return c
+
+
+def form(n_fft, hop, n_mels):
+    """-> (tile, row_pad, lds_bytes, classes): 32 frames where their LDS fits 64 KB, else 16; the classes are the launch form,
+    what sizes the first region, and shape_classes()"""
+    rows, kp, mp = (n_fft + 3) // 4 * 4, (n_fft // 2 + 1 + 15) // 16 * 16, (n_mels + 15) // 16 * 16
+    for tile in (32, 16):
+        first, what = plan_first(rows, hop, mp, tile)
+        lds = (first + tile * (kp + 2)) * 4
+        if lds <= LDS_SOFT:
+            break
+    assert lds <= LDS_MAX
+    c = {launch_of(tile, lds), what} | shape_classes(n_fft, rows, hop, kp, n_mels)
+    if LDS_SOFT - 64 < lds <= LDS_SOFT:
+        c.add("edge-64k")
+    return tile, (2 - hop) % 32, lds, c
+
+
+def _e(n_fft, hop, n_mels, rate, stream, channels=1, scale="slaney", norm="slaney"):
+    return dict(n_fft=n_fft, hop=hop, n_mels=n_mels, sample_rate=rate, stream=stream, channels=channels, scale=scale, norm=norm)
+
+
+# the shapes whose launch forms no speech front end reaches; `stream` names one of test_gpu_clip_audio's
+EDGES = {
+    "taco-1024-256-80-stereo": _e(1024, 256, 80, 22050, "22k", 2),                # tile16-dyn: the Tacotron / HiFi-GAN front end
+    "1024-418-last-dynamic": _e(1024, 418, 80, 22050, "48k"),
+    "1024-419-first-static": _e(1024, 419, 80, 22050, "48k"),
+    "1024-hop3-static": _e(1024, 3, 80, 16000, "32k"),                            # chunks of 34 floats: 82 480 B
+    "1024-hop4-static": _e(1024, 4, 80, 16000, "32k"),
+    "958-hop4-exactly-64k": _e(958, 4, 80, 16000, "16k-mono"),
+    "806-hop3-16-bands": _e(806, 3, 16, 16000, "16k-mono", scale="htk"),
+    "512-hop2-256-bands": _e(512, 2, 256, 16000, "32k"),                          # first region: the mel tile
+    "64-hop1-256-bands": _e(64, 1, 256, 8000, "8k", scale="htk", norm=None),
+    "16-hop16-256-bands-stereo": _e(16, 16, 256, 8000, "8k", 2),
+    "16-hop1-1-band": _e(16, 1, 1, 8000, "8k"),
+    "398-hop3-20-bands": _e(398, 3, 20, 16000, "48k", scale="htk", norm=None),
+    "1022-hop1-17-bands-own-rate": _e(1022, 1, 17, 0, "44k-mono"),
+    "18-hop5-15-bands": _e(18, 5, 15, 16000, "16k-mono"),
+}
+EXACT_EDGE = ("958-hop4-exactly-64k",)

@@ -89,3 +89,43 @@ def mfcc(y, pos0, start, n_frames, nw, hop, w, n_valid, num_ceps=13, q=22.0, rou
         bound = bound + dmu + U * (np.abs(v) + bound + dmu)
         out = v
     return out, bound
+
+
+# ---- the plan of a workgroup of k_clip_mfcc restated, and the classes of a geometry ("launch forms") ----
+def form(nw, n, hop, n_mels, num_ceps):
+    """-> (tile, row_pad, lds_bytes, classes): clip_fbank_ref.form with the second region the larger of the powers
+    [tile][bins16 + 2] and the cepstra [tile][ceps16 + 1]"""
+    import clip_mel_ref as mref
+    rows, kp, mp, cp = (nw + 3) // 4 * 4, (n // 2 + 15) // 16 * 16, (n_mels + 15) // 16 * 16, (num_ceps + 15) // 16 * 16
+    for tile in (32, 16):
+        first, what = mref.plan_first(rows, hop, mp, tile)
+        lds = (first + tile * max(kp + 2, cp + 1)) * 4
+        if lds <= mref.LDS_SOFT:
+            break
+    assert lds <= mref.LDS_MAX
+    c = {mref.launch_of(tile, lds), what, "cepstra" if cp + 1 > kp + 2 else "powers"} | mref.shape_classes(nw, rows, hop, kp, n_mels)
+    if mref.LDS_SOFT - 64 < lds <= mref.LDS_SOFT:
+        c.add("edge-64k")
+    return tile, (2 - hop) % 32, lds, c
+
+
+def _e(win, hop, n_mels, num_ceps, rate, stream, channels=1, **options):
+    return dict(dict(win_length=win, hop=hop, num_mel_bins=n_mels, num_ceps=num_ceps, sample_rate=rate, channels=channels, **options), stream=stream)
+
+
+# the shapes whose launch forms no speech front end reaches; `stream` names one of test_gpu_clip_audio's, the rest are
+# decode_clips_mfcc's arguments
+EDGES = {
+    "taco-1024-256-80-40-stereo": _e(1024, 256, 80, 40, 22050, "22k", 2),
+    "551-220-80-13": _e(551, 220, 80, 13, 22050, "22k"),
+    "900-hop4-exactly-64k": _e(900, 4, 80, 13, 16000, "16k-mono"),
+    "960-hop4-n-equals-nw-exactly-64k": _e(960, 4, 80, 13, 16000, "16k-mono", round_to_power_of_two=False),
+    "401-hop3-20-20-mean-energy": _e(401, 3, 20, 20, 16000, "32k", subtract_mean=True, use_energy=True),
+    "512-hop2-256-256": _e(512, 2, 256, 256, 16000, "32k", round_to_power_of_two=False),
+    "16-hop4-1-band-1-cepstrum": _e(16, 4, 1, 1, 8000, "8k", low_freq=0.0, scale=32768.0),
+    "64-hop5-15-bands": _e(64, 5, 15, 15, 8000, "8k", low_freq=0.0, scale=32768.0),
+    "64-hop5-17-bands-13-cepstra-stereo": _e(64, 5, 17, 13, 8000, "8k", 2, low_freq=0.0, scale=32768.0),
+    # first region the mel tile, second region the cepstra, 16 column tiles over four waves
+    "64-hop64-256-256": _e(64, 64, 256, 256, 16000, "16k-mono", round_to_power_of_two=False, low_freq=0.0),
+}
+EXACT_EDGE = ("900-hop4-exactly-64k", "960-hop4-n-equals-nw-exactly-64k")

@@ -147,3 +147,44 @@ def power_as_the_product(re, im):
         near = (np.nextafter(flat_o[i], np.float32(-np.inf)), flat_o[i], np.nextafter(flat_o[i], np.float32(np.inf)))
         flat_o[i] = min(near, key=lambda v: (abs(Fraction(float(v)) - x), int(np.float32(v).view(np.uint32)) & 1))
     return out
+
+
+# ---- the classes of a geometry of k_clip_stft ("launch forms"); the plan itself is tile_plan() above ----
+def form(n_fft, hop, mode):
+    """-> (tile, row_pad, lds_bytes, classes): tile_plan's launch path under the names the other feature kernels' forms have,
+    and clip_mel_ref.shape_classes()"""
+    tile, pad, lds, path = tile_plan(n_fft, hop, mode)
+    c = {"tile16-dyn" if path == "tile16" else path} | mref.shape_classes(n_fft, (n_fft + 3) // 4 * 4, hop, (n_fft // 2 + 1 + 15) // 16 * 16)
+    if mref.LDS_SOFT - 64 < lds <= mref.LDS_SOFT:
+        c.add("edge-64k")
+    return tile, pad, lds, c
+
+
+def _edge_window(nw):
+    return (np.random.default_rng(nw).random(nw, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
+
+
+def _e(n_fft, hop, rate, stream, channels=1, modes=("complex",), **options):
+    return dict(dict(n_fft=n_fft, hop=hop, sample_rate=rate, channels=channels, **options), stream=stream, modes=modes)
+
+
+ALL_MODES = tuple(MODES)
+# the shapes whose launch forms no speech front end reaches; `stream` names one of test_gpu_clip_audio's, `modes` the modes whose
+# launch form the shape is there for (the device test runs all five), the rest are decode_clips_stft's arguments
+EDGES = {
+    "1024-352-stereo-two-forms": _e(1024, 352, 22050, "22k", 2, ALL_MODES),       # mode 0: tile 16; modes 1 - 4: tile 32
+    "1024-322-last-tile32": _e(1024, 322, 22050, "48k"),
+    "1024-323-first-tile16": _e(1024, 323, 22050, "48k"),
+    "1024-802-last-dynamic": _e(1024, 802, 0, "48k"),
+    "1024-803-first-static": _e(1024, 803, 0, "48k"),
+    "1024-386-power-last-tile32": _e(1024, 386, 22050, "48k", modes=("power",)),
+    "1024-387-power-first-tile16": _e(1024, 387, 22050, "48k", modes=("power",)),
+    "1024-866-power-last-dynamic": _e(1024, 866, 0, "48k", modes=("power",)),
+    "1024-867-power-first-static": _e(1024, 867, 0, "48k", modes=("power",)),
+    "1024-256-stereo": _e(1024, 256, 22050, "22k", 2),                            # 54 560 B, a large tile 32
+    "944-hop3-64k": _e(944, 3, 16000, "16k-mono"),                                # 65 488 B
+    "1022-hop2-normalized": _e(1022, 2, 16000, "32k", normalized=True),
+    "398-hop3-own-window": _e(398, 3, 16000, "32k", window=_edge_window(398)),
+    "1024-700-window-1000": _e(1024, 700, 0, "44k-mono", win_length=1000, window=_edge_window(1000)),
+}
+EXACT_EDGE = ("944-hop3-64k",)

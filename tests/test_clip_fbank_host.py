@@ -143,6 +143,16 @@ def test_valid_against_brute_force_around_both_ends():
             api.fbank_valid(*bad)
 
 
+
+def tile_sweep():
+    """(Nw, N, hop, n_mels) of the grid the plan's preconditions are walked over (tests/test_clip_forms_host.py walks it too)"""
+    for nw, pow2 in ((2, True), (16, False), (200, True), (398, False), (400, True), (400, False), (401, True), (513, True), (1024, True)):
+        n = ref.dft_length(nw, pow2)
+        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 80, 128, 160, 450, 480, nw // 2, nw - 1, nw]) & set(range(1, nw + 1))):
+            for n_mels in (1, 23, 80, 256):
+                yield nw, n, hop, n_mels
+
+
 def test_the_tile_keeps_the_kernels_preconditions():
     """every (Nw, N, H, n_mels): the span in its padded chunks, the mel tile over it and the powers (with a spare float a row for
     the energy) behind it fit the LDS the product asks for -- 64 KB, or the static variant's array at a tile of 16 --, 32 frames
@@ -150,22 +160,19 @@ def test_the_tile_keeps_the_kernels_preconditions():
     from pdmp3_amd import api
     tiles = {16: 0, 32: 0}
     static = 0
-    for nw, pow2 in ((2, True), (16, False), (200, True), (398, False), (400, True), (400, False), (401, True), (513, True), (1024, True)):
-        n = ref.dft_length(nw, pow2)
-        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 80, 128, 160, 450, 480, nw // 2, nw - 1, nw]) & set(range(1, nw + 1))):
-            for n_mels in (1, 23, 80, 256):
-                tile, pad, lds = api.fbank_tile(nw, n, hop, n_mels)
-                kp, mp, rows = (n // 2 + 15) // 16 * 16, (n_mels + 15) // 16 * 16, (nw + 3) // 4 * 4
-                assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024 - 64
-                first = lds // 4 - tile * (kp + 2)
-                sp = (tile - 1) * hop + rows
-                assert first >= -(-sp // hop) * (hop + pad) and first >= mp * (tile + 1)
-                if tile == 16:
-                    assert (max(-(-(31 * hop + rows) // hop) * (hop + pad), mp * 33) + 32 * (kp + 2)) * 4 > 64 * 1024
-                    static += lds > 64 * 1024
-                else:
-                    assert lds <= 64 * 1024
-                tiles[tile] += 1
+    for nw, n, hop, n_mels in tile_sweep():
+        tile, pad, lds = api.fbank_tile(nw, n, hop, n_mels)
+        kp, mp, rows = (n // 2 + 15) // 16 * 16, (n_mels + 15) // 16 * 16, (nw + 3) // 4 * 4
+        assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024 - 64
+        first = lds // 4 - tile * (kp + 2)
+        sp = (tile - 1) * hop + rows
+        assert first >= -(-sp // hop) * (hop + pad) and first >= mp * (tile + 1)
+        if tile == 16:
+            assert (max(-(-(31 * hop + rows) // hop) * (hop + pad), mp * 33) + 32 * (kp + 2)) * 4 > 64 * 1024
+            static += lds > 64 * 1024
+        else:
+            assert lds <= 64 * 1024
+        tiles[tile] += 1
     assert tiles[16] and tiles[32] and static
     assert api.fbank_tile(400, 512, 160, 80) == (32, 2, 55056)
     t, _, lds = api.fbank_tile(1024, 1024, 480, 80)
@@ -224,6 +231,22 @@ EMUL_CASES = [
     (18, 1, True, 5, 8000, 2, 2, 70, 40, dict(window_type="hamming", low=0.0)),             # H = 1
     (16, 16, False, 5, 8000, 1, 0, 33, 400, dict(window_type="hamming")),
 ]
+
+
+def edge_options(e):
+    """decode_clips_fbank's argument names of an entry of EDGES -> the options of a case"""
+    names = dict(window_type="window_type", preemphasis_coefficient="rho", low_freq="low", remove_dc_offset="remove_dc", scale="scale")
+    return {names[k]: v for k, v in e.items() if k in names}
+
+
+def _edge_case(e):
+    """an entry of clip_fbank_ref.EDGES as a case: one full tile and a partial one, the row all signal; the own rate: 44.1 kHz"""
+    pow2 = e.get("round_to_power_of_two", True)
+    tile = ref.form(e["win_length"], ref.dft_length(e["win_length"], pow2), e["hop"], e["num_mel_bins"])[0]
+    return (e["win_length"], e["hop"], pow2, e["num_mel_bins"], e["sample_rate"] or 44100, e["channels"], 57, tile + 3, None, edge_options(e))
+
+
+EMUL_CASES += [_edge_case(e) for e in ref.EDGES.values()]
 
 
 def _run_emul(lib, y_rows, Ts, T, channels, F, nv, nw, hop, pow2, n_mels, sr, o, mode, energy, sub):

@@ -127,6 +127,15 @@ EMUL_CASES = [
 ]
 
 
+def _edge_case(e):
+    """an entry of clip_mel_ref.EDGES as a case: one full tile and a partial one, the row all signal; the own rate: 44.1 kHz"""
+    tile = ref.form(e["n_fft"], e["hop"], e["n_mels"])[0]
+    return (e["n_fft"], e["hop"], e["n_mels"], e["sample_rate"] or 44100, e["scale"], e["norm"], e["channels"], 57, tile + 3, None)
+
+
+EMUL_CASES += [_edge_case(e) for e in ref.EDGES.values()]
+
+
 @pytest.mark.parametrize("case", EMUL_CASES, ids=lambda c: "N%d-H%d-m%d-C%d-s%d" % (c[0], c[1], c[2], c[6], c[7]))
 def test_kernel_arithmetic_on_the_host_against_binary64(case):
     from pdmp3_amd import api
@@ -205,24 +214,30 @@ def test_refusals_of_the_planning_calls():
         api.mel_filterbank(16000, 400, 80, 5000.0, 4000.0)
 
 
+def tile_sweep():
+    """(n_fft, hop, n_mels) of the grid the plan's preconditions are walked over (tests/test_clip_forms_host.py walks it too)"""
+    for n_fft in (16, 18, 398, 400, 512, 1022, 1024):
+        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 128, 160, n_fft // 2, n_fft - 1, n_fft]) & set(range(1, n_fft + 1))):
+            for n_mels in (1, 80, 256):
+                yield n_fft, hop, n_mels
+
+
 def test_the_tile_keeps_the_kernels_preconditions():
     """every (N, H): the span in its padded chunks, the mel tile over it and the powers behind it fit the LDS the product asks
     for, at most 160 KB, 32 frames wherever they fit 64 KB, and hop + row_pad = 2 mod 32"""
     from pdmp3_amd import api
     tiles = {16: 0, 32: 0}
-    for n_fft in (16, 18, 398, 400, 512, 1022, 1024):
-        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 128, 160, n_fft // 2, n_fft - 1, n_fft]) & set(range(1, n_fft + 1))):
-            for n_mels in (1, 80, 256):
-                tile, pad, lds = api.mel_tile(n_fft, hop, n_mels)
-                Kp, Mp, rows = (n_fft // 2 + 1 + 15) // 16 * 16, (n_mels + 15) // 16 * 16, (n_fft + 3) // 4 * 4
-                assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024
-                first = lds // 4 - tile * (Kp + 2)
-                sp = (tile - 1) * hop + rows
-                assert first >= -(-sp // hop) * (hop + pad) and first >= Mp * (tile + 1)
-                if tile == 16:
-                    assert (max(-(-(31 * hop + rows) // hop) * (hop + pad), Mp * 33) + 32 * (Kp + 2)) * 4 > 64 * 1024
-                else:
-                    assert lds <= 64 * 1024
-                tiles[tile] += 1
+    for n_fft, hop, n_mels in tile_sweep():
+        tile, pad, lds = api.mel_tile(n_fft, hop, n_mels)
+        Kp, Mp, rows = (n_fft // 2 + 1 + 15) // 16 * 16, (n_mels + 15) // 16 * 16, (n_fft + 3) // 4 * 4
+        assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024
+        first = lds // 4 - tile * (Kp + 2)
+        sp = (tile - 1) * hop + rows
+        assert first >= -(-sp // hop) * (hop + pad) and first >= Mp * (tile + 1)
+        if tile == 16:
+            assert (max(-(-(31 * hop + rows) // hop) * (hop + pad), Mp * 33) + 32 * (Kp + 2)) * 4 > 64 * 1024
+        else:
+            assert lds <= 64 * 1024
+        tiles[tile] += 1
     assert tiles[16] and tiles[32]
     assert api.mel_tile(400, 160, 80)[0] == 32

@@ -143,6 +143,15 @@ def _expected_tile(nw, n, hop, nm, nc):
     return tile, pad, res[tile]
 
 
+def tile_sweep():
+    """(Nw, N, hop, n_mels, num_ceps) of the grid the plan is walked over (tests/test_clip_forms_host.py walks it too)"""
+    for nw, pow2 in ((2, True), (16, False), (200, True), (400, True), (400, False), (401, True), (1024, True)):
+        n = fref.dft_length(nw, pow2)
+        for hop in sorted(set([1, 3, 4, 33, 80, 160, 450, 480, nw]) & set(range(1, nw + 1))):
+            for nm, nc in ((1, 1), (23, 13), (80, 80), (256, 256), (256, 1)):
+                yield nw, n, hop, nm, nc
+
+
 def test_the_tile_takes_the_larger_of_the_powers_and_the_cepstra():
     from pdmp3_amd import api
     # torchaudio's defaults at 16 kHz: the powers are the larger (258 floats a frame against 17); the same bytes as the
@@ -158,14 +167,11 @@ def test_the_tile_takes_the_larger_of_the_powers_and_the_cepstra():
     t, pad, lds = api.mfcc_tile(1024, 1024, 480, 80, 40)
     assert (t, pad, lds) == _expected_tile(1024, 1024, 480, 80, 40) and t == 16 and 64 * 1024 < lds <= 160 * 1024 - 64
     tiles = {16: 0, 32: 0}
-    for nw, pow2 in ((2, True), (16, False), (200, True), (400, True), (400, False), (401, True), (1024, True)):
-        n = fref.dft_length(nw, pow2)
-        for hop in sorted(set([1, 3, 4, 33, 80, 160, 450, 480, nw]) & set(range(1, nw + 1))):
-            for nm, nc in ((1, 1), (23, 13), (80, 80), (256, 256), (256, 1)):
-                t, pad, lds = api.mfcc_tile(nw, n, hop, nm, nc)
-                assert (t, pad, lds) == _expected_tile(nw, n, hop, nm, nc), (nw, n, hop, nm, nc)
-                assert lds <= 160 * 1024 - 64 and (hop + pad) % 32 == 2
-                tiles[t] += 1
+    for nw, n, hop, nm, nc in tile_sweep():
+        t, pad, lds = api.mfcc_tile(nw, n, hop, nm, nc)
+        assert (t, pad, lds) == _expected_tile(nw, n, hop, nm, nc), (nw, n, hop, nm, nc)
+        assert lds <= 160 * 1024 - 64 and (hop + pad) % 32 == 2
+        tiles[t] += 1
     assert tiles[16] and tiles[32]
     # a tile of 32 for the filterbank kernel, 16 here: 257 floats of cepstra a frame against 18 of powers push it over 64 KB
     assert api.fbank_tile(16, 16, 1, 256)[0] == 32 and api.mfcc_tile(16, 16, 1, 256, 256)[0] == 16
@@ -181,6 +187,18 @@ EMUL_CASES = [
     (1024, 480, True, 80, 40, 22.0, 48000, 2, 300, 18, 6000, dict(window_type="blackman")),   # tile of 16, more than 64 KB
     (16, 16, False, 40, 40, 22.0, 8000, 1, 0, 33, 400, dict(window_type="hamming", low=0.0)),  # the cepstra outgrow the powers
 ]
+
+
+def _edge_case(e):
+    """an entry of clip_mfcc_ref.EDGES as a case: one full tile and a partial one, the row all signal; the own rate: 44.1 kHz"""
+    import test_clip_fbank_host as tfh
+    pow2 = e.get("round_to_power_of_two", True)
+    tile = ref.form(e["win_length"], fref.dft_length(e["win_length"], pow2), e["hop"], e["num_mel_bins"], e["num_ceps"])[0]
+    return (e["win_length"], e["hop"], pow2, e["num_mel_bins"], e["num_ceps"], 22.0, e["sample_rate"] or 44100, e["channels"], 57, tile + 3, None,
+            tfh.edge_options(e))
+
+
+EMUL_CASES += [_edge_case(e) for e in ref.EDGES.values()]
 ENERGIES = [(0, 0, 0.0), (0, 1, 0.0), (1, 0, 0.0), (1, 1, 100.0)]
 
 

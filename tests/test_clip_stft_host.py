@@ -174,24 +174,30 @@ def test_refusals_of_the_planning_calls():
             api.stft_tile(n_fft, hop, mode)
 
 
+def tile_sweep():
+    """(n_fft, hop, mode) of the grid the plan is walked over (tests/test_clip_forms_host.py walks it too)"""
+    for n_fft in (16, 18, 398, 400, 512, 1022, 1024):
+        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 128, 160, 450, 512, 900, n_fft // 2, n_fft - 1, n_fft]) & set(range(1, n_fft + 1))):
+            for mode in range(5):
+                yield n_fft, hop, mode
+
+
 def test_the_tile_is_the_plan_restated_and_keeps_the_kernels_preconditions():
     """every (N, H, mode) of a grid: the call's plan is the restated one, the span in its padded chunks and the four staging
     tiles fit the LDS asked for, at most 160 KB; every launch path is hit"""
     from pdmp3_amd import api
     paths = {"tile32": 0, "tile16": 0, "tile16-static": 0}
-    for n_fft in (16, 18, 398, 400, 512, 1022, 1024):
-        for hop in sorted(set([1, 2, 3, 4, 5, 31, 32, 33, 64, 128, 160, 450, 512, 900, n_fft // 2, n_fft - 1, n_fft]) & set(range(1, n_fft + 1))):
-            for mode in range(5):
-                tile, pad, lds = api.stft_tile(n_fft, hop, mode)
-                want = ref.tile_plan(n_fft, hop, mode)
-                assert (tile, pad, lds) == want[:3], (n_fft, hop, mode)
-                rows = (n_fft + 3) // 4 * 4
-                assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024 - 64
-                stage = 4 * (2 if mode == 0 else 1) * 16 * (tile + 4)
-                first = lds // 4 - stage
-                assert first % 4 == 0 and first >= -(-((tile - 1) * hop + rows) // hop) * (hop + pad)
-                assert (want[3] == "tile32") == (tile == 32) and (want[3] == "tile16-static") == (lds > 64 * 1024)
-                paths[want[3]] += 1
+    for n_fft, hop, mode in tile_sweep():
+        tile, pad, lds = api.stft_tile(n_fft, hop, mode)
+        want = ref.tile_plan(n_fft, hop, mode)
+        assert (tile, pad, lds) == want[:3], (n_fft, hop, mode)
+        rows = (n_fft + 3) // 4 * 4
+        assert tile in (16, 32) and 0 <= pad < 32 and (hop + pad) % 32 == 2 and lds <= 160 * 1024 - 64
+        stage = 4 * (2 if mode == 0 else 1) * 16 * (tile + 4)
+        first = lds // 4 - stage
+        assert first % 4 == 0 and first >= -(-((tile - 1) * hop + rows) // hop) * (hop + pad)
+        assert (want[3] == "tile32") == (tile == 32) and (want[3] == "tile16-static") == (lds > 64 * 1024)
+        paths[want[3]] += 1
     assert all(paths.values()), paths
     assert api.stft_tile(400, 160)[0] == 32 and api.stft_tile(1024, 512)[0] == 16 and api.stft_tile(1024, 512)[2] <= 64 * 1024
     assert api.stft_tile(1024, 1024)[0] == 16 and api.stft_tile(1024, 1024)[2] > 64 * 1024
@@ -212,6 +218,16 @@ EMUL_CASES = [
     (16, 16, 7, True, False, 1, 0, 33, 400),
     (398, 3, 398, False, True, 1, 50, 36, None),                  # N not a multiple of 4, a hop below 4
 ]
+
+
+def _edge_case(e):
+    """an entry of clip_stft_ref.EDGES as a case: one full tile of the mode with the larger tile and a partial one, the row all
+    signal (a caller's window: one of this module's, of the entry's length)"""
+    tile = max(ref.form(e["n_fft"], e["hop"], m)[0] for m in range(5))
+    return (e["n_fft"], e["hop"], e.get("win_length") or e["n_fft"], "window" in e, e.get("normalized", False), e["channels"], 57, tile + 3, None)
+
+
+EMUL_CASES += [_edge_case(e) for e in ref.EDGES.values()]
 
 
 @pytest.mark.parametrize("case", EMUL_CASES, ids=lambda c: "N%d-H%d-Nw%d-C%d-s%d" % (c[0], c[1], c[2], c[5], c[6]))

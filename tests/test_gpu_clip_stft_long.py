@@ -31,6 +31,9 @@ PC = dict(sample_rate=0, n_fft=2048, hop=2048, channels=1)                 # the
 PD = dict(sample_rate=0, n_fft=4096, hop=1024, channels=1)
 PE = dict(sample_rate=0, n_fft=4096, hop=4096, channels=1)
 PF = dict(sample_rate=0, n_fft=2048, hop=1, channels=1)
+W1920 = (np.random.default_rng(1920).random(1920, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
+PG = dict(sample_rate=0, n_fft=4096, hop=1024, channels=2, win_length=1920, window=W1920, normalized=True)
+PH = dict(sample_rate=0, n_fft=4096, hop=4096, channels=2)
 FLOORS = {3: 1e-10, 4: 1e-10}
 
 
@@ -91,6 +94,8 @@ CASES = {
     "d-48k-4096-hop-1024": (PD, "48k", 18, "N4096-tile8"),
     "e-48k-4096-hop-4096": (PE, "48k", 5, "N4096-tile4"),
     "f-32k-2048-hop-1": (PF, "32k", 40, "N2048-tile16"),
+    "g-48k-stereo-4096-hop-1024-own-window-1920": (PG, "48k", 11, "N4096-tile8"),      # 4096: stereo, win_length, a caller's window, normalized
+    "h-48k-stereo-4096-hop-4096": (PH, "48k", 7, "N4096-tile4"),
 }
 
 
