@@ -286,9 +286,10 @@ struct ConstBank {
 // (BankPtr, the pointer to the bank, and PD_LAUNDER: top of the file)
 
 // Large tables in global memory (L2-resident; copied to LDS per chunk where hot).
+constexpr int kNumSfreq = 9;   // sfreq 0..2: MPEG-1; 3..8: MPEG-2 LSF / MPEG-2.5 (host_tables.h)
 struct GlobalTables {
   const float* pow43;       // [8207] (float)pow((float)i, 4.0/3.0), P:979
-  const uint16_t* linetab;  // [3 sfreq][3 kind][576]: for REORDERED line d: source line (10 bits) |
+  const uint16_t* linetab;  // [kNumSfreq][3 kind][576]: for REORDERED line d: source line (10 bits) |
                             //   scale-table index of that source line << 10.
                             //   kind 0 long, 1 short, 2 mixed; index 0..21 long sfb, 22+sfb*3+win short
   const float* win;         // [4][36] g_imdct_win (P:577-603)
@@ -297,7 +298,7 @@ struct GlobalTables {
   const float* frag_short;  // [5 kk][2 nt]   3 x 12-point IMDCT with win[2] folded in, same column map
   const float* frag_mat;    // [2 even/odd][4 k-steps]: 16 x 16 halves of the 32-point DCT-II, rows in register order
   const float* taps;        // [16][64 lanes]: the lane's window coefficients we[0..7], wo[0..7] (g_synth_dtbl, sign folded)
-  const void* tab_image;    // [3 sfreq] images of TabLds (host_tables.h: build_tab_images), copied to LDS as they are
+  const void* tab_image;    // [kNumSfreq] images of TabLds (host_tables.h: build_tab_images), copied to LDS as they are
 };
 
 // LDS.  WaveData is a wave's own working set; TabLds are the hot tables -- one copy per wave in the chunk kernels

@@ -88,15 +88,66 @@ __global__ __launch_bounds__(64, PDMP3_WAVES_PER_EU) void k_decode_rare(DecodeAr
 // an MI355X); W = 8 for the smaller launches: twice as many CUs share the work, two waves per SIMD -- which is also all
 // the occupancy that form is compiled for (a workgroup of 8 waves is one per CU in the launches that take it; asked for
 // four waves per SIMD the compiler could not get there and said so: 217 registers, occupancy 2).
-template <bool F32, int W>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W / 4, W / 4))) void k_decode_g(DecodeArgs a, GlobalTables T) {
+//
+// A launch of 2048 frames is ONE resident round -- 4096 waves on 4096 wave slots -- so nothing hides what a wave does
+// before its first transform instruction, and the kernel keeps every argument in scalar registers for its whole life.
+// GranArgs: its parameters are the twelve values the hot path reads (20 scalar registers, not the 42 of DecodeArgs +
+// GlobalTables); the DecodeArgs / GlobalTables the rest of decode_core.h wants are rebuilt here, what this kernel never
+// has (stage dumps, an LSF launch's granule count, the PCM pointer of the other type, the profile buffer unless PROF) as
+// constants that fold, the tables as constant offsets from the one allocation they share (engine_internal.h kTabOff*).
+// k_decode_g_prof = the development launch with shader-clock stamps (chunk_frames = -2 with a profile buffer:
+// tools/gran_profile.py): the same workgroup code with PROF set, its buffer a second kernel parameter of that kernel alone.
+// Static figures of k_decode_g<false, 16> against DecodeArgs + GlobalTables as parameters: kernarg 168 -> 80 bytes, its
+// s_load 21 -> 15, instructions 5872 -> 5698, spilled SGPRs 82 -> 72 (profiles/gran_entry_ab.txt).
+struct GranArgs {
+  const int16_t* spectra;
+  const pdmp3_gc_side* side;
+  void* pcm;                     // int16 or float by F32
+  const float* state_in;
+  float* state_out;
+  float* chain_state;
+  unsigned* chain_flag;
+  const char* tables;            // the tables' allocation (engine_internal.h kTabOff*)
+  int n_frames;
+  unsigned chain_epoch, debug_flags;
+  int sf_hint;
+};
+
+// (on the host too: launch_decode builds the other kernels' GlobalTables with it)
+__host__ __device__ __forceinline__ GlobalTables tables_at(const char* base) {
+  const float* frag = reinterpret_cast<const float*>(base + kTabOffFrag);
+  return GlobalTables{reinterpret_cast<const float*>(base + kTabOffPow43), reinterpret_cast<const uint16_t*>(base + kTabOffLinetab),
+                      reinterpret_cast<const float*>(base + kTabOffWin), frag, frag + kFragShort, frag + kFragMat, frag + kFragTaps,
+                      base + kTabOffImage};
+}
+
+template <bool F32, int W, bool PROF>
+__device__ __forceinline__ void gran_workgroup(const GranArgs& ga, unsigned long long* prof) {
+  DecodeArgs a;
+  a.spectra = ga.spectra;
+  a.side = ga.side;
+  a.pcm = F32 ? nullptr : static_cast<int16_t*>(ga.pcm);
+  a.pcm_f32 = F32 ? static_cast<float*>(ga.pcm) : nullptr;
+  a.state_in = ga.state_in;
+  a.state_out = ga.state_out;
+  a.stages = nullptr;
+  a.n_frames = ga.n_frames;
+  a.chunk_frames = 1;
+  a.prof = PROF ? prof : nullptr;
+  a.chain_state = ga.chain_state;
+  a.chain_flag = ga.chain_flag;
+  a.chain_epoch = ga.chain_epoch;
+  a.debug_flags = ga.debug_flags;
+  a.sf_hint = ga.sf_hint;
+  a.n_gran = 0;
+  const GlobalTables T = tables_at(ga.tables);
   __shared__ WaveData L[W];
   __shared__ TabLds S;
   __shared__ GranMb mb[W];
   __shared__ unsigned tabs_ready;
   static_assert(sizeof(WaveData) * W + sizeof(TabLds) + sizeof(GranMb) * W + 16 <= 160 * 1024, "one workgroup of 16 waves per CU");
   const int tid = (int)threadIdx.x;
-  const unsigned long long t_entry = a.prof ? PD_CLOCK() : 0ull;
+  const unsigned long long t_entry = PROF ? PD_CLOCK() : 0ull;     // (read before the kernel arguments have arrived: the first phase holds their round trip)
   const int w = tid >> 6;
   const int g = (int)blockIdx.x * W + w;
   const bool valid = g < 2 * a.n_frames;
@@ -114,9 +165,18 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W / 4, W
   __builtin_amdgcn_wave_barrier();
   if ((tid & 63) == 0) atomicAdd(&tabs_ready, 1u);
   if (!valid) return;
-  if (a.prof && (tid & 63) == 0) a.prof[(size_t)g * kProfSlots] = t_entry;
+  if (PROF && (tid & 63) == 0) a.prof[(size_t)g * kProfSlots] = t_entry;
   const GranPos gp{L, mb, w, W, &tabs_ready};
   run_granule_wave<F32>(a, T, (BankPtr)&c_bank, g, L[w], S, gp, pf);
+}
+
+template <bool F32, int W>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W / 4, W / 4))) void k_decode_g(GranArgs ga) {
+  gran_workgroup<F32, W, false>(ga, nullptr);
+}
+template <int W>                         // (development: int16 PCM only)
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(W / 4, W / 4))) void k_decode_g_prof(GranArgs ga, unsigned long long* prof) {
+  gran_workgroup<false, W, true>(ga, prof);
 }
 
 // OPT-IN BUILD (make EXTRA=-DPDMP3_WITH_RING_KERNEL): measured 1.66 x slower than the engine's own choice at every size
@@ -274,11 +334,7 @@ static void chain_free(ChainBuf* b) {                      // (hipFree waits for
 extern "C" void pdmp3_hip_destroy(pdmp3_hip_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  (void)hipFree(c->d_pow43);
-  (void)hipFree(c->d_linetab);
-  (void)hipFree(c->d_win);
-  (void)hipFree(c->d_frag);
-  (void)hipFree(c->d_tab_image);
+  (void)hipFree(c->d_tables);
   (void)hipFree(c->d_rare_flags);
   (void)hipFree(c->d_unpack);
   (void)hipFree(c->d_uprof);
@@ -326,22 +382,24 @@ extern "C" int pdmp3_hip_create(int device, pdmp3_hip_ctx** out) {
   do {
     if (!build_unpack_tables(*U)) { what = "Huffman lookup tables exceed kHuffLutMax"; break; }
     CREATE_STEP(hipMemcpyToSymbol(HIP_SYMBOL(c_bank), &H.cb, sizeof(ConstBank)), "upload const bank")
-    CREATE_STEP(hipMalloc(&c->d_pow43, H.pow43.size() * sizeof(float)), "hipMalloc pow43")
-    CREATE_STEP(hipMalloc(&c->d_linetab, H.linetab.size() * sizeof(uint16_t)), "hipMalloc linetab")
-    CREATE_STEP(hipMalloc(&c->d_win, H.win.size() * sizeof(float)), "hipMalloc win")
-    CREATE_STEP(hipMalloc(&c->d_frag, (10 + 10 + 8 + 16) * 64 * sizeof(float)), "hipMalloc frag")
-    CREATE_STEP(hipMalloc(&c->d_tab_image, kNumSfreq * sizeof(TabLds)), "hipMalloc table images")
+    // the tables GlobalTables points into: one allocation, each at its constant offset (engine_internal.h)
+    if (H.pow43.size() * sizeof(float) != kTabPow43Bytes || H.linetab.size() * sizeof(uint16_t) != kTabLinetabBytes ||
+        H.win.size() * sizeof(float) != kTabWinBytes || H.frag_long.size() != (size_t)kFragShort || H.frag_short.size() != (size_t)(kFragMat - kFragShort) ||
+        H.frag_mat.size() != (size_t)(kFragTaps - kFragMat) || H.taps.size() != (size_t)(kFragFloats - kFragTaps) ||
+        H.tab_image.size() * sizeof(TabLds) != kTabImageBytes) { what = "the host tables do not have the sizes of the device layout"; break; }
+    CREATE_STEP(hipMalloc((void**)&c->d_tables, kTabBytes), "hipMalloc tables")
+    CREATE_STEP(hipMemset(c->d_tables, 0, kTabBytes), "hipMemset tables")
     CREATE_STEP(hipMalloc((void**)&c->d_unpack, sizeof(UnpackTables)), "hipMalloc unpack tables")
     { const char* up = getenv("PDMP3_HIP_UNPACK_PROF");
       if (up && *up == '1') CREATE_STEP(hipMalloc((void**)&c->d_uprof, 2048 * 8 * sizeof(unsigned long long)), "hipMalloc unpack prof") }
-    CREATE_STEP(hipMemcpy(c->d_pow43, H.pow43.data(), H.pow43.size() * sizeof(float), hipMemcpyHostToDevice), "upload pow43")
-    CREATE_STEP(hipMemcpy(c->d_linetab, H.linetab.data(), H.linetab.size() * sizeof(uint16_t), hipMemcpyHostToDevice), "upload linetab")
-    CREATE_STEP(hipMemcpy(c->d_win, H.win.data(), H.win.size() * sizeof(float), hipMemcpyHostToDevice), "upload win")
-    CREATE_STEP(hipMemcpy(c->d_frag, H.frag_long.data(), 10 * 64 * sizeof(float), hipMemcpyHostToDevice), "upload frag_long")
-    CREATE_STEP(hipMemcpy(c->d_frag + 10 * 64, H.frag_short.data(), 10 * 64 * sizeof(float), hipMemcpyHostToDevice), "upload frag_short")
-    CREATE_STEP(hipMemcpy(c->d_frag + 20 * 64, H.frag_mat.data(), 8 * 64 * sizeof(float), hipMemcpyHostToDevice), "upload frag_mat")
-    CREATE_STEP(hipMemcpy(c->d_frag + 28 * 64, H.taps.data(), 16 * 64 * sizeof(float), hipMemcpyHostToDevice), "upload taps")
-    CREATE_STEP(hipMemcpy(c->d_tab_image, H.tab_image.data(), kNumSfreq * sizeof(TabLds), hipMemcpyHostToDevice), "upload table images")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffPow43, H.pow43.data(), kTabPow43Bytes, hipMemcpyHostToDevice), "upload pow43")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffLinetab, H.linetab.data(), kTabLinetabBytes, hipMemcpyHostToDevice), "upload linetab")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffWin, H.win.data(), kTabWinBytes, hipMemcpyHostToDevice), "upload win")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffFrag, H.frag_long.data(), H.frag_long.size() * sizeof(float), hipMemcpyHostToDevice), "upload frag_long")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffFrag + kFragShort * sizeof(float), H.frag_short.data(), H.frag_short.size() * sizeof(float), hipMemcpyHostToDevice), "upload frag_short")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffFrag + kFragMat * sizeof(float), H.frag_mat.data(), H.frag_mat.size() * sizeof(float), hipMemcpyHostToDevice), "upload frag_mat")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffFrag + kFragTaps * sizeof(float), H.taps.data(), H.taps.size() * sizeof(float), hipMemcpyHostToDevice), "upload taps")
+    CREATE_STEP(hipMemcpy(c->d_tables + kTabOffImage, H.tab_image.data(), kTabImageBytes, hipMemcpyHostToDevice), "upload table images")
     CREATE_STEP(hipMalloc((void**)&c->d_rare_flags, kRareSlots * sizeof(unsigned)), "hipMalloc rare flags")
     CREATE_STEP(hipMemset(c->d_rare_flags, 0, kRareSlots * sizeof(unsigned)), "hipMemset rare flags")
     c->rare_epoch.store(1);
@@ -475,14 +533,19 @@ static void launch_ring(const DecodeArgs& a, const GlobalTables& T, const Decode
   else hipLaunchKernelGGL((k_decode_p<false>), dim3(p.n_wgs), dim3(64 * 16), 0, s, a, T, p.frames_per_wg);
 }
 #endif
-static void launch_granules(const DecodeArgs& a, const GlobalTables& T, const DecodePlan& p, bool f32, hipStream_t s) {
+static void launch_granules(pdmp3_hip_ctx* c, const DecodeArgs& a, const DecodePlan& p, bool f32, hipStream_t s) {
   const int W = p.kind;
-  if (W == 8) {
-    if (f32) hipLaunchKernelGGL((k_decode_g<true, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
-    else hipLaunchKernelGGL((k_decode_g<false, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+  const GranArgs ga{a.spectra, a.side, f32 ? (void*)a.pcm_f32 : (void*)a.pcm, a.state_in, a.state_out, a.chain_state, a.chain_flag, c->d_tables,
+                    a.n_frames, a.chain_epoch, a.debug_flags, a.sf_hint};
+  if (a.prof) {                                  // (development: stamps; launch_decode lets no float PCM come here)
+    if (W == 8) hipLaunchKernelGGL((k_decode_g_prof<8>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga, a.prof);
+    else hipLaunchKernelGGL((k_decode_g_prof<16>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga, a.prof);
+  } else if (W == 8) {
+    if (f32) hipLaunchKernelGGL((k_decode_g<true, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga);
+    else hipLaunchKernelGGL((k_decode_g<false, 8>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga);
   } else {
-    if (f32) hipLaunchKernelGGL((k_decode_g<true, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
-    else hipLaunchKernelGGL((k_decode_g<false, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, a, T);
+    if (f32) hipLaunchKernelGGL((k_decode_g<true, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga);
+    else hipLaunchKernelGGL((k_decode_g<false, 16>), dim3(p.n_wgs), dim3(64 * W), 0, s, ga);
   }
 }
 // chunks with halos: the profiling / dumping forms, every chunk to k_decode_rare (LSF), or k_decode with k_decode_rare
@@ -578,6 +641,7 @@ int launch_decode(pdmp3_hip_ctx* c, const DecodeLaunch& q) {
   ring = false;
 #endif
   const bool gran_prof = q.prof && chunk_frames_arg == -2;          // (development: the granule kernel with per-wave stamps)
+  if (gran_prof && q.f32) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_decode_frames: the stamped granule kernel writes int16 PCM only", hipSuccess);
   if (!ring && (plain || gran_prof) && c->chain_mode != 0 && chunk_frames_arg <= 1 && n_frames <= c->gran_max_frames) {
     // one granule per wave (run_granule): tails and matrixing rows are handed from wave to wave, no halo.  Waits for
     // another workgroup are bounded (then: halo), so the launch finishes whatever part of it is resident; up to
@@ -605,12 +669,12 @@ int launch_decode(pdmp3_hip_ctx* c, const DecodeLaunch& q) {
   c->last_kind = p.kind;
 
   // ---- the launch ----
-  GlobalTables T{c->d_pow43, c->d_linetab, c->d_win, c->d_frag, c->d_frag + 10 * 64, c->d_frag + 20 * 64, c->d_frag + 28 * 64, c->d_tab_image};
+  const GlobalTables T = tables_at(c->d_tables);
 #if defined(PDMP3_WITH_RING_KERNEL)
   if (ring) launch_ring(a, T, p, q.f32, s);
   else
 #endif
-  if (gran) launch_granules(a, T, p, q.f32, s);
+  if (gran) launch_granules(c, a, p, q.f32, s);
   else launch_chunks(c, a, T, p, q.f32, q.lsf, s);
   hipError_t e = hipGetLastError();
   const char* what = "launch k_decode";

@@ -15,6 +15,7 @@
 #include <mutex>
 
 #include "../../include/pdmp3_hip.h"
+#include "decode_core.h"        // TabLds, kNumSfreq: the layout of the tables' allocation below
 
 #define PDMP3_LOCAL __attribute__((visibility("hidden")))
 
@@ -53,6 +54,24 @@ struct ChainBuf {
 };
 constexpr int kChainBufs = 32;
 
+// The decode kernels' tables (decode_core.h GlobalTables) share ONE device allocation, each at a constant 256-byte aligned
+// offset: the granule kernel takes the base as its only table parameter and forms the eight pointers from constants; the
+// other kernels get a GlobalTables built on the host from the same offsets.  Sizes as host_tables.h builds them (checked
+// when the engine is created).
+constexpr size_t kTabPow43Bytes = 8207 * sizeof(float);                  // pow43 [8207]
+constexpr size_t kTabLinetabBytes = pdmp3::kNumSfreq * 3 * 576 * sizeof(uint16_t);   // linetab [sfreq][kind][576]
+constexpr size_t kTabWinBytes = 4 * 36 * sizeof(float);                  // win [4][36]
+constexpr int kFragShort = 10 * 64, kFragMat = 20 * 64, kFragTaps = 28 * 64, kFragFloats = 44 * 64;   // frag_long [10][64] | frag_short [10][64] | frag_mat [8][64] | taps [16][64]
+constexpr size_t kTabFragBytes = kFragFloats * sizeof(float);
+constexpr size_t kTabImageBytes = pdmp3::kNumSfreq * sizeof(pdmp3::TabLds);   // [kNumSfreq] TabLds images
+constexpr size_t tab_align(size_t n) { return (n + 255) & ~(size_t)255; }
+constexpr size_t kTabOffPow43 = 0;
+constexpr size_t kTabOffLinetab = tab_align(kTabOffPow43 + kTabPow43Bytes);
+constexpr size_t kTabOffWin = tab_align(kTabOffLinetab + kTabLinetabBytes);
+constexpr size_t kTabOffFrag = tab_align(kTabOffWin + kTabWinBytes);
+constexpr size_t kTabOffImage = tab_align(kTabOffFrag + kTabFragBytes);
+constexpr size_t kTabBytes = tab_align(kTabOffImage + kTabImageBytes);
+
 constexpr int kRareSlots = 4096;      // a flag word per launch, taken round robin: two launches share one only if 4096 others lie between them
 struct pdmp3_hip_ctx {
   int device;
@@ -60,11 +79,7 @@ struct pdmp3_hip_ctx {
   pdmp3::UnpackTables* d_unpack;
   int unpack_n16;                // its used part, in 16-byte units
   unsigned long long* d_uprof;   // development only: PDMP3_HIP_UNPACK_PROF=1
-  float* d_pow43;
-  uint16_t* d_linetab;
-  float* d_win;
-  float* d_frag;            // frag_long [10][64] | frag_short [10][64] | frag_mat [8][64] | taps [16][64]
-  void* d_tab_image;        // [kNumSfreq] TabLds images
+  char* d_tables;           // what GlobalTables points into: one allocation, kTabOff* below
   unsigned* d_rare_flags;   // [kRareSlots] epoch numbers (DecodeArgs::rare_flag): "this launch of chunks holds a chunk for k_decode_rare"
   std::atomic<unsigned> rare_epoch;
   int chain_mode;           // PDMP3_HIP_CHAIN=0: independent chunks with halos everywhere; otherwise launches up to

@@ -29,21 +29,20 @@ constexpr int kT2Size = 312;   // 2^((k-266)/4), k = 0..311
 struct HostTables {
   ConstBank cb;
   std::vector<float> pow43;        // 8207
-  std::vector<uint16_t> linetab;   // 3*3*576: source line | scale index << 10, per reordered line
+  std::vector<uint16_t> linetab;   // kNumSfreq*3*576: source line | scale index << 10, per reordered line
   std::vector<float> win;          // 4*36
   std::vector<float> frag_long, frag_short, frag_mat;   // MFMA B fragments, [fragment][64 lanes]
   std::vector<float> taps;         // [16][64]: per-lane window coefficients (decode_core.h lane_init)
-  std::vector<TabLds> tab_image;   // [3 sfreq]: what the kernels copy to LDS (decode_core.h tab_load_image)
+  std::vector<TabLds> tab_image;   // [kNumSfreq]: what the kernels copy to LDS (decode_core.h tab_load_image)
   // the reference's libm expressions, kept to verify the device's ldexp forms
   // (decode_core.h: pow2_neg_half / pow2_quarter) over their whole index range
   std::vector<float> t1, t2;
   bool ldexp_forms_exact;
 };
 
-// sfreq 0..2: the reference's MPEG-1 tables; 3..8: MPEG-2 LSF / MPEG-2.5 (lsf_tables.h)
+// sfreq 0..2: the reference's MPEG-1 tables; 3..8: MPEG-2 LSF / MPEG-2.5 (lsf_tables.h); kNumSfreq of them (decode_core.h)
 inline const uint16_t* sfb_long_of(int sfreq) { return sfreq >= 3 ? kLsfSfbLong[sfreq - 3] : sfreq == 0 ? kSfbLong0 : (sfreq == 1 ? kSfbLong1 : kSfbLong2); }
 inline const uint16_t* sfb_short_of(int sfreq) { return sfreq >= 3 ? kLsfSfbShort[sfreq - 3] : sfreq == 0 ? kSfbShort0 : (sfreq == 1 ? kSfbShort1 : kSfbShort2); }
-constexpr int kNumSfreq = 9;
 
 inline void build_tab_images(HostTables& H);
 inline void build_host_tables(HostTables& H) {
