@@ -602,6 +602,48 @@ int pdmp3_amd_stft_long_plan(int n_fft, int hop, int out_mode, int* tile, int* r
 int pdmp3_amd_bulk_decode_clips_stft_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_stft_spec* spec,
                                           long long* valid);
 
+/* ---- log-mel features of clips at n_fft 2048 and 4096 ----
+ * The mel spectrogram of the spectrum above without the spectrum leaving the device's compute units: librosa's 2048 / 512
+ * with 128 bands and its like.  Signal, clip, framing, valid[k] and layout are pdmp3_amd_bulk_decode_clips_mel's: frame f of a
+ * clip at `start` reads y[start + f hop - N / 2 + n], no reflection, zeros outside the stream; planar float32
+ * [K, C, n_mels, F], frames innermost, rows of K and C may be strided.  The window is the transform's wt above with s = 1
+ * (there is no `normalized`); P[f][k] = Re^2 + Im^2 of its X, as fma(Im, Im, Re Re); W is pdmp3_amd_mel_filterbank's at
+ * N / 2 + 1 bins; M = W P, each M[f][m] one fused multiply-add chain in one fixed order of the bins, the same for every frame.
+ * out_mode 0 (power), 1 (ln max(M, floor)) and 2 (log10 max(M, floor)).  out_mode 3 (Whisper's normalisation) is refused:
+ * its front end is 400 / 160, and it would bring the row-maximum atomics and the finishing launch for no user at these
+ * lengths.  The Nyquist bin is never computed: f_max <= sr / 2 and the last band's upper edge is f_max itself, so its weight
+ * is exactly 0 in every filterbank the check accepts. */
+typedef struct pdmp3_amd_mel_long_spec {
+  pdmp3_amd_mel_spec mel;     /* pdmp3_amd_mel_spec's fields and meanings; mel.n_fft is 2048 or 4096, mel.hop 1 .. n_fft */
+  int win_length;             /* 0 = n_fft, else 1 .. n_fft, centred as torch.stft centres it */
+  const float* window;        /* NULL: periodic Hann of win_length; else win_length binary32 values of the caller's */
+} pdmp3_amd_mel_long_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: pdmp3_amd_mel_check's limits on n_mels, f_min,
+ * f_max, scale, norm, floor and n_frames, n_fft 2048 or 4096, hop 1 .. n_fft, out_mode 0 .. 2, win_length and the window's
+ * values as pdmp3_amd_stft_long_check takes them. */
+int pdmp3_amd_mel_long_check(const pdmp3_amd_mel_long_spec* spec, long sr);
+/* pdmp3_amd_mel_filterbank on this domain: dense [n_mels][n_fft / 2 + 1], binary64 rounded once.  Returns the floats and
+ * writes min(that, cap); -1 on a bad argument, nothing written. */
+long long pdmp3_amd_mel_long_filterbank(long sr, int n_fft, int n_mels, double f_min, double f_max, int scale, int norm, float* w, size_t cap);
+/* The same weights as the kernel reads them: [n_fft / 2][n_mels rounded up to 16] (*rows, *cols; may be NULL), the row of bin
+ * k = 16 kt + k1l + 64 k2 at 8 N2 kt + slot(k1l, k2) (csrc/mel_long_core.h), zeros in the bands' padding, bin n_fft / 2 left
+ * out.  Returns the floats and writes min(that, cap); -1 on a bad argument, nothing written. */
+long long pdmp3_amd_mel_long_operand(long sr, int n_fft, int n_mels, double f_min, double f_max, int scale, int norm, float* op, size_t cap,
+                                     int* rows, int* cols);
+/* What a workgroup of k_clip_mel_long takes, the function the call itself uses: *tile frames -- 16 where the LDS below fits
+ * PDMP3_MEL_LDS_MAX (include/pdmp3_hip.h), else 8, else 4 -- and all bins.  The LDS bytes: the tile's span,
+ * (tile - 1) hop + n_fft floats rounded up to 4, which stays; Z, tile x N2 x 32 floats; the powers of one tile of k1,
+ * tile x (8 N2 + 2) floats.  *row_pad is 0.  Every plan is above 64 KB and runs on a static array.  0, or -1 on a bad
+ * argument.  Pointers may be NULL. */
+int pdmp3_amd_mel_long_plan(int n_fft, int hop, int n_mels, int* tile, int* row_pad, unsigned* lds_bytes);
+/* pdmp3_amd_bulk_decode_clips_stft_long's course -- rows through the audio call, destinations, the stages, the per-clip
+ * refusals in valid[k], rate 0 / channels 0, the counts, n_clips = 0 and n_frames = 0 -- with the check above and
+ * k_clip_mel_long (csrc/mel_long.hip) writing the rows.  The transform's tables are that call's; the filterbank operand is
+ * made once per (sr, n_fft, n_mels, f_min, f_max, scale, norm) and kept for the decoder's life.  -1 also where
+ * pdmp3_amd_mel_long_check says so. */
+int pdmp3_amd_bulk_decode_clips_mel_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mel_long_spec* spec,
+                                         long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -616,6 +616,29 @@ typedef struct pdmp3_stft_long_params {
 int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                              const pdmp3_stft_long_params* params);
 
+/* Log-mel features of clips at n_fft 2048 and 4096 (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_mel_long; DESIGN.md
+ * section 15).  k_clip_mel_long (mel_long.hip) reads the rows as k_clip_stft_long does (pdmp3_mel_desc) and writes
+ * [n_mels][n_frames] floats per channel, frames innermost.  N = 64 n2; a workgroup of eight waves takes `tile` frames and all
+ * four tiles of k1, one after the other.  Its LDS: span_floats for the tile's span, plain ((tile - 1) hop + n_fft floats, kept
+ * for all four), then Z: tile x n2 x 32 floats, then the powers of one tile of k1: tile x (8 n2 + 2) floats. */
+typedef struct pdmp3_mel_long_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t n_fft, n2;                        /* N: 2048 or 4096; N / 64                                                  */
+  int32_t hop, n_mels;                      /* H; the bands                                                             */
+  int32_t mels16, n_frames;                 /* n_mels rounded up to 16: the operand's columns; F                        */
+  int32_t tile, channels;                   /* frames of a workgroup: 16 or 8 (N 2048), 8 or 4 (N 4096)                 */
+  int32_t out_mode;                         /* 0 power, 1 ln, 2 log10                                                   */
+  float floor;                              /* of the logarithms                                                        */
+  uint32_t span_floats;                     /* LDS floats of the span's region, a multiple of 4                         */
+  uint32_t lds_bytes;
+} pdmp3_mel_long_params;
+/* Uploads the descriptors, the four tables (pdmp3_hip_clip_stft_long's block) and the filterbank operand (n_fft / 2 rows of
+ * mels16 floats in the kernel's order of the bins; csrc/mel_long_core.h has the map) -- host memory -- into one block and runs
+ * k_clip_mel_long on the slot's HIP stream.  lds_bytes <= PDMP3_MEL_LDS_MAX: the kernel has a static array of that size.
+ * Blocks until the rows are written. */
+int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                            const float* operand, const pdmp3_mel_long_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -26,7 +26,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_fbank_tile", "pdmp3_amd_bulk_decode_clips_fbank",
                 "pdmp3_amd_mfcc_check", "pdmp3_amd_mfcc_dct_table", "pdmp3_amd_mfcc_tile", "pdmp3_amd_bulk_decode_clips_mfcc",
                 "pdmp3_amd_stft_check", "pdmp3_amd_stft_table", "pdmp3_amd_stft_tile", "pdmp3_amd_bulk_decode_clips_stft",
-                "pdmp3_amd_stft_long_check", "pdmp3_amd_stft_long_tables", "pdmp3_amd_stft_long_plan", "pdmp3_amd_bulk_decode_clips_stft_long"]
+                "pdmp3_amd_stft_long_check", "pdmp3_amd_stft_long_tables", "pdmp3_amd_stft_long_plan", "pdmp3_amd_bulk_decode_clips_stft_long",
+                "pdmp3_amd_mel_long_check", "pdmp3_amd_mel_long_filterbank", "pdmp3_amd_mel_long_operand", "pdmp3_amd_mel_long_plan",
+                "pdmp3_amd_bulk_decode_clips_mel_long"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -169,6 +171,15 @@ def load_library():
         lib.pdmp3_amd_stft_long_tables.restype = ll
         lib.pdmp3_amd_stft_long_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_stft_long.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_mel_long"):     # (log-mel features at n_fft 2048 and 4096: absent from older builds)
+        lib.pdmp3_amd_mel_long_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_mel_long_filterbank.argtypes = [C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t]
+        lib.pdmp3_amd_mel_long_filterbank.restype = ll
+        lib.pdmp3_amd_mel_long_operand.argtypes = [C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_size_t,
+                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_mel_long_operand.restype = ll
+        lib.pdmp3_amd_mel_long_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_mel_long.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -658,6 +669,72 @@ def stft_long_plan(n_fft, hop, mode="complex"):
     return t.value, p.value, b.value
 
 
+class _MelLongSpec(C.Structure):                   # include/pdmp3_bulk.h pdmp3_amd_mel_long_spec
+    _fields_ = [("mel", _MelSpec), ("win_length", C.c_int), ("window", C.c_void_p)]
+
+
+def _mel_long_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney",
+                   mode="log10", floor=1e-10, win_length=None, window=None, channels=1, width=0, rolloff=0.0):
+    """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
+    w = None
+    if window is not None:
+        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
+        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
+            raise ValueError("mel_long: window must hold win_length values")
+        win_length = w.size
+    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    mel = _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff)
+    return _MelLongSpec(mel, nw, w.ctypes.data if w is not None else None), w
+
+
+def mel_long_check(sample_rate=22050, **kw):
+    """pdmp3_amd_mel_long_check -> True when pdmp3_amd_bulk_decode_clips_mel_long would accept these numbers
+    (decode_clips_mel_long's argument names) at sample_rate"""
+    try:
+        spec, keep = _mel_long_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError):
+        return False
+    return load_library().pdmp3_amd_mel_long_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def _mel_long_bank(sample_rate, n_fft, n_mels, f_min, f_max, scale, norm):
+    sc = MEL_SCALES[scale] if isinstance(scale, str) else int(scale)
+    no = MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm)
+    return int(sample_rate), int(n_fft), int(n_mels), float(f_min), float(f_max), sc, no
+
+
+def mel_long_filterbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney"):
+    """pdmp3_amd_mel_long_filterbank -> float32 numpy [n_mels, n_fft // 2 + 1]"""
+    lib = load_library()
+    a = _mel_long_bank(sample_rate, n_fft, n_mels, f_min, f_max, scale, norm)
+    if lib.pdmp3_amd_mel_long_filterbank(*a, None, 0) < 0:
+        raise ValueError("pdmp3_amd_mel_long_filterbank: bad argument")
+    w = np.full((int(n_mels), int(n_fft) // 2 + 1), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mel_long_filterbank(*a, w.ctypes.data_as(C.c_void_p), w.size)
+    return w
+
+
+def mel_long_operand(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney"):
+    """pdmp3_amd_mel_long_operand -> float32 numpy [n_fft // 2, n_mels rounded up to 16]: the filterbank as k_clip_mel_long
+    reads it, the bins' rows in the kernel's order"""
+    lib = load_library()
+    a = _mel_long_bank(sample_rate, n_fft, n_mels, f_min, f_max, scale, norm)
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_mel_long_operand(*a, None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_mel_long_operand: bad argument")
+    op = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mel_long_operand(*a, op.ctypes.data_as(C.c_void_p), op.size, None, None)
+    return op
+
+
+def mel_long_plan(n_fft, hop, n_mels):
+    """pdmp3_amd_mel_long_plan -> (frames of a workgroup of k_clip_mel_long, 0, LDS bytes of a workgroup)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_mel_long_plan(int(n_fft), int(hop), int(n_mels), C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_mel_long_plan: bad argument")
+    return t.value, p.value, b.value
+
+
 class StreamIndex:
     """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
     built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
@@ -975,6 +1052,52 @@ class BulkDecoder:
             raise e
         if rc != 0:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel failed (a bad argument, a decoder without device Huffman, switches "
+                               "that differ from an index's, or an engine failure)")
+        return out, valid
+
+    def decode_clips_mel_long(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=0.0, scale="slaney",
+                              norm="slaney", mode="log10", floor=1e-10, win_length=None, window=None, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_mel_long: decode_clips_mel in everything -- clips, framing, filterbank, out, valid,
+        exceptions -- at n_fft 2048 or 4096, with decode_clips_stft_long's win_length / window (periodic Hann of win_length when
+        no window is given); mode "power" / "log" / "log10" ("whisper" is refused).  The transform, the powers and the
+        filterbank run in one kernel, k_clip_mel_long: no spectrum is written."""
+        k, f, nm = len(clips), int(n_frames), int(n_mels)
+        c = int(channels)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            if len(cs) > 1:
+                raise ValueError("decode_clips_mel_long: channels=0 and the clips' channel counts differ")
+            c = cs.pop() if cs else 1
+        if out is None:
+            import torch
+            out = torch.zeros((k, c, nm, f), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            torch.cuda.synchronize()
+        if hasattr(out, "data_ptr"):
+            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, nm, f) and out.shape[0] >= k and out.element_size() == 4
+            assert nm * f <= 1 or ((f <= 1 or out.stride(3) == 1) and (nm <= 1 or out.stride(2) == f))
+            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
+        else:
+            assert out.ndim == 4 and out.shape[1:] == (c, nm, f) and out.shape[0] >= k and out.dtype == np.float32
+            assert nm * f <= 1 or ((f <= 1 or out.strides[3] == 4) and (nm <= 1 or out.strides[2] == 4 * f))
+            assert out.strides[1] % 4 == 0
+            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
+        arr = (_AudioClip * max(k, 1))()
+        keep = []
+        for i, (mp3, ix, start) in enumerate(clips):
+            a = _as_u8(mp3)
+            keep.append(a)
+            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
+        spec, keep_window = _mel_long_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, win_length, window, channels, width, rolloff)
+        got = (C.c_longlong * max(k, 1))()
+        rc = self.lib.pdmp3_amd_bulk_decode_clips_mel_long(self.h, arr, k, C.byref(spec), got)
+        valid = np.array(got[:k], dtype=np.int64)
+        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
+            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
+                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
+            e.valid, e.out = valid, out
+            raise e
+        if rc != 0:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel_long failed (a bad argument, a decoder without device Huffman, switches "
                                "that differ from an index's, or an engine failure)")
         return out, valid
 

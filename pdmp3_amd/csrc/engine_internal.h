@@ -169,5 +169,8 @@ hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, in
 // ---- stft_long.hip ----
 hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                        const pdmp3_stft_long_params* params);
+// ---- mel_long.hip ----
+hipError_t pdmp3_launch_clip_mel_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables, const float* operand,
+                                      const pdmp3_mel_long_params* params);
 
 #endif

@@ -735,6 +735,52 @@ extern "C" int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pd
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }
+// ---- log-mel features at n_fft 2048 and 4096 (mel_long.hip) ----
+extern "C" int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                                       const float* operand, const pdmp3_mel_long_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !tables || !operand || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: bad argument", hipSuccess);
+  const pdmp3_mel_long_params& P = *params;
+  // what the kernel's indexing relies on
+  if ((P.n_fft != 2048 && P.n_fft != 4096) || P.n2 != P.n_fft / 64 || P.hop < 1 || P.hop > P.n_fft || P.n_mels < 1 || P.n_mels > 256 ||
+      P.mels16 != ((P.n_mels + 15) & ~15) || (P.tile != 16 && P.tile != 8 && P.tile != 4) || (P.n2 == 32 && P.tile == 4) ||
+      (P.n2 == 64 && P.tile == 16) || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 || P.out_mode > 2 || P.n_frames < 0 || P.n_in < 0 ||
+      !(P.floor > 0.0f) || (P.span_floats & 3u) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: bad parameters", hipSuccess);
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.n_fft;
+    const size_t z = (size_t)P.tile * P.n2 * 32, pw = (size_t)P.tile * (8 * (size_t)P.n2 + 2);
+    if (P.span_floats < span || (size_t)P.lds_bytes < ((size_t)P.span_floats + z + pw) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: a tile's span, Z and powers do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: too many frames", hipSuccess);
+  }
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | the four tables | the filterbank operand: one block (the log-mel call's; the calls never overlap in time),
+  // each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
+  const size_t tab_bytes = ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float);
+  const size_t tab_room = (tab_bytes + 255) & ~(size_t)255;
+  const size_t op_bytes = (size_t)(P.n_fft / 2) * (size_t)P.mels16 * sizeof(float);
+  { void* p = hs->d_mel_args;
+    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_room + op_bytes + 16, "hipMalloc mel tables");
+    hs->d_mel_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_mel_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D mel descriptors");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes, tables, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft tables");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes + tab_room, operand, op_bytes, hipMemcpyHostToDevice, t.stream), "H2D filterbank operand");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_mel_long(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                       reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + tab_room), &P),
+            "launch k_clip_mel_long");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
                                     const pdmp3_fbank_params* params) {

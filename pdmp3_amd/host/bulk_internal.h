@@ -364,6 +364,11 @@ HOST_LOCAL const float* stft_table(struct bulk* b, const pdmp3_amd_stft_spec* s)
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);
 HOST_LOCAL const float* stft_long_tables(struct bulk* b, const pdmp3_amd_stft_spec* s);
+/* clip_mel_long.c: the frame of a log-mel spec at these lengths as the transform's tables take it, the plan of a workgroup of
+ * k_clip_mel_long (0, or -1) and the decoder's filterbank operand of a spec the check accepts (NULL: no memory) */
+HOST_LOCAL void mel_long_stft_spec(const pdmp3_amd_mel_long_spec* s, pdmp3_amd_stft_spec* t);
+HOST_LOCAL int mel_long_plan(int n_fft, int hop, int n_mels, pdmp3_mel_long_params* p);
+HOST_LOCAL const float* mel_long_operand(struct bulk* b, long sr, const pdmp3_amd_mel_spec* s);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

@@ -485,6 +485,117 @@ def clips_stft(args, api, long=False):
     print(json.dumps(res))
 
 
+def clips_mel_long(args, api):
+    """--mel-long: 64 clips of 30 s (--clips / --clip-frames change that) at 44.1 kHz mono as 128 log10-mel bands x 2583 frames
+    (n_fft 2048, hop 512, periodic Hann, Slaney scale and norm) in device memory, four ways, run after run in turn: (a)
+    pdmp3_amd_bulk_decode_clips_audio for the same spans; (b) (a) followed by torch.stft, abs() ** 2, a matmul with the
+    filterbank and log10 (a dense matmul against the direct table where torch.stft cannot run); (c)
+    pdmp3_amd_bulk_decode_clips_mel_long; (d) pdmp3_amd_bulk_decode_clips_stft_long(mode="power") followed by the matmul and
+    log10 -- the route that writes the power batch to memory and reads it back.  (c) is compared once with (b) and (d)
+    (largest difference, printed, not asserted: the tests check (c) against the definition).  Medians and min..max of --runs
+    runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop, n_mels, floor = args.clips, args.clip_frames, 44100, 2048, 512, 128, 1e-10
+    bins = n_fft // 2 + 1
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
+    T = (Fm - 1) * hop + n_fft
+    dev = "cuda:0"
+    mel, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        mel.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - n_fft // 2))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, n_mels, Fm), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, n_mels, Fm), dtype=torch.float32, device=dev)
+    out_d = torch.zeros((K, 1, n_mels, Fm), dtype=torch.float32, device=dev)
+    out_p = torch.zeros((K, 1, bins, Fm), dtype=torch.float32, device=dev)
+    window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32, device=dev)
+    fb = torch.from_numpy(api.mel_long_filterbank(rate, n_fft, n_mels)).to(dev)                        # [n_mels, bins]
+    kp = (bins + 15) // 16 * 16
+    ang = 2.0 * np.pi * ((np.arange(n_fft)[:, None] * np.arange(kp)[None, :]) % n_fft) / n_fft
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft))[:, None]
+    table = torch.from_numpy(np.concatenate([w * np.cos(ang), -w * np.sin(ang)], axis=1).astype(np.float32)).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    how = {"stft": "torch.stft"}
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+        y = out_a[:, 0]
+        p = None
+        if how["stft"] == "torch.stft":
+            try:
+                p = torch.stft(y, n_fft, hop_length=hop, window=window, center=False, return_complex=True).abs() ** 2       # [K, bins, Fm]
+            except Exception as e:                      # noqa: BLE001  (no FFT library on this build)
+                how["stft"] = "dense matmul against the table (torch.stft: %s)" % type(e).__name__
+        if p is None:
+            x = y.unfold(1, n_fft, hop) @ table                                                                          # [K, Fm, 2 Kp]
+            p = (x[:, :, :bins] ** 2 + x[:, :, kp:kp + bins] ** 2).transpose(1, 2)
+        out_b[:, 0] = torch.log10(torch.clamp(torch.matmul(fb, p), min=floor))
+        torch.cuda.synchronize()
+
+    def mel_route():
+        dec.decode_clips_mel_long(mel, Fm, rate, n_fft, hop, n_mels, floor=floor, out=out_c)
+
+    def power_route():
+        dec.decode_clips_stft_long(mel, Fm, rate, n_fft, hop, mode="power", out=out_p)
+        out_d[:, 0] = torch.log10(torch.clamp(torch.matmul(fb, out_p[:, 0]), min=floor))
+        torch.cuda.synchronize()
+
+    routes = [("audio clips", audio_route), ("audio clips + torch.stft + matmul + log10", torch_route), ("mel_long clips", mel_route),
+              ("stft_long power clips + matmul + log10", power_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 4:] + routes[:r % 4]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = {"torch_route": float((out_b - out_c).abs().max()), "power_route": float((out_d - out_c).abs().max())}
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as %d log10-mel bands x %d frames at %d Hz mono (n_fft %d, hop %d): %s" % (
+               K, F, n_mels, Fm, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
+           "power_batch_bytes": K * bins * Fm * 4, "result_bytes": K * n_mels * Fm * 4,
+           "largest_difference_from_mel_long": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    res["mel_long_minus_audio_ms"] = round((med["mel_long clips"] - med["audio clips"]) * 1e3, 3)
+    res["power_route_minus_audio_ms"] = round((med["stft_long power clips + matmul + log10"] - med["audio clips"]) * 1e3, 3)
+    res["torch_route_minus_audio_ms"] = round((med["audio clips + torch.stft + matmul + log10"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(spread * 1e3, 3)
+    res["mel_long_cheaper_than_the_power_route_by_more_than_the_spread"] = bool(
+        med["stft_long power clips + matmul + log10"] - med["mel_long clips"] > spread)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -703,6 +814,10 @@ def main():
     ap.add_argument("--stft-long", action="store_true",
                     help="64 clips of 30 s (or --clips / --clip-frames) as their short-time Fourier transform at 44.1 kHz mono, n_fft 2048, "
                          "hop 512 (pdmp3_amd_bulk_decode_clips_stft_long) against the audio call alone and the audio call followed by torch.stft")
+    ap.add_argument("--mel-long", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as 128 x 2583 log10-mel frames at 44.1 kHz mono, n_fft 2048, hop 512 "
+                         "(pdmp3_amd_bulk_decode_clips_mel_long) against the audio call alone, the audio call followed by torch kernels, and "
+                         "pdmp3_amd_bulk_decode_clips_stft_long's powers followed by a matmul and log10 (see clips_mel_long())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -710,12 +825,14 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long:
+    if args.stft_long or args.mel_long:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
     if args.clips:
         from pdmp3_amd import api
+        if args.mel_long:
+            return clips_mel_long(args, api)
         if args.stft or args.stft_long:
             return clips_stft(args, api, long=args.stft_long)
         if args.mfcc:
