@@ -644,6 +644,83 @@ int pdmp3_amd_mel_long_plan(int n_fft, int hop, int n_mels, int* tile, int* row_
 int pdmp3_amd_bulk_decode_clips_mel_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_mel_long_spec* spec,
                                          long long* valid);
 
+/* ---- The constant-Q transform of clips ----
+ * What music models take besides the mel spectrogram: K clips as one planar float32 batch [K][C][n_bins][F], frames
+ * innermost, complex or as magnitude, power or its logarithm.  New entry points only; nothing above returns anything else.
+ *
+ * Signal, clip, frame position, valid, destinations.  Section 13's: y_c[j] is the binary32 output of
+ * pdmp3_amd_bulk_decode_clips_audio at the requested rate sr and channel count for 0 <= j < J and 0.0 outside; frame f of a
+ * clip at `start` is centred on sample start + f H; NO reflection, samples outside the stream are zeros;
+ * valid[k] = clamp(ceil((J - start) / H), 0, F).  Rows of K and C may be strided.
+ * Bins.  With B = bins_per_octave and k = 0 .. n_bins - 1:
+ *   f_k = fmin 2^(k / B);  Q = filter_scale / (2^(1 / B) - 1);  L_k = Q sr / f_k (real);  h_k = floor(L_k / 2);
+ *   N_k = 2 h_k + 1 (odd: the filter is centred on the frame's centre sample);
+ *   g_k[m] = 0.5 - 0.5 cos(2 pi (m + h_k) / N_k), m = -h_k .. h_k (the periodic Hann window of N_k);
+ *   s_k = n_k a_k;  n_k: norm 0: 1, norm 1: 1 / sum_m g_k[m], norm 2: 1 / sqrt(sum_m g_k[m]^2);
+ *                   a_k: scale 0: 1, scale 1: sqrt(L_k), scale 2: L_k;
+ *   C[f, k] = s_k sum over m = -h_k .. h_k of g_k[m] y[start + f H + m] e^(-2 pi i f_k m / sr).
+ * The phase is referred to the frame's centre.  norm 1, scale 1 is the convention of librosa's cqt(norm=1, scale=True) -- L1
+ * filters times sqrt(length); norm 1, scale 0 gives |C| = a / 2 for a sinusoid of amplitude a at f_k.  The definition is the
+ * formula above, evaluated in full at the one rate sr -- not librosa's multirate approximation of it: no agreement with
+ * librosa is promised beyond the convention.
+ * Output.  out_mode 0 complex: [K][C][n_bins][F][2], Re and Im interleaved -- the memory of a complex64 tensor; 1 magnitude,
+ * the correctly rounded sqrt(Re^2 + Im^2); 2 power fma(Im, Im, Re Re); 3 ln max(power, floor); 4 log10 max(power, floor).
+ * The floor rules are section 13's.
+ * The coefficients s_k g_k[m] cos(2 pi f_k m / sr) and -s_k g_k[m] sin(..) are computed on the host in binary64 and rounded
+ * once to binary32; the angle is reduced first: x = m f_k / sr in binary64 (one product, one quotient), x - floor(x) in
+ * [0, 1), then times 2 pi.  The GPU multiplies and adds in binary32 (v_mfma_f32_16x16x4_f32).
+ * Not offered: windows other than Hann, variable-Q (gamma), fmin per clip, the inverse transform, the multirate form,
+ * reflection at a stream's ends. */
+#define PDMP3_CQT_MAX_LEN 32767       /* N_0, the longest filter, at most */
+#define PDMP3_CQT_SPLIT_ROWS 512      /* a tile of 16 bins with this many rows or more is cut into PDMP3_CQT_SEGMENTS */
+#define PDMP3_CQT_SEGMENTS 8
+#define PDMP3_CQT_TABLES 4
+typedef struct {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec */
+  int hop;
+  double fmin;
+  int n_bins, bins_per_octave;
+  double filter_scale;
+  int norm, scale;                                      /* 0 .. 2 each, above */
+  long long n_frames;
+  int out_mode;                                         /* 0 complex, 1 magnitude, 2 power, 3 ln, 4 log10 */
+  double floor;                                         /* modes 3 and 4: > 0 */
+} pdmp3_amd_cqt_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: n_bins outside 1 .. 512, bins_per_octave
+ * outside 1 .. 96, fmin or filter_scale not finite or not > 0, f_(n_bins - 1) >= sr / 2, N_0 > PDMP3_CQT_MAX_LEN, a shortest
+ * filter of fewer than 3 taps (its Hann window is 0), a table of more than 2^22 floats, hop outside 1 .. 8192, norm or scale
+ * outside 0 .. 2, out_mode unknown, a floor section 13 refuses, n_frames < 0, a spec whose plan finds no tile that fits the LDS. */
+int pdmp3_amd_cqt_check(const pdmp3_amd_cqt_spec* spec, long sr);
+/* f_k into f[] and h_k into half[] (either may be NULL), k < n_bins <= cap.  Returns n_bins; -1 where the check refuses the
+ * spec or cap < n_bins, nothing written. */
+int pdmp3_amd_cqt_lengths(const pdmp3_amd_cqt_spec* spec, long sr, double* f, int* half, size_t cap);
+/* The ragged table.  Bins are taken in tiles of 16, ascending k; tile t has tile_rows[t] = N_(16 t) rounded up to 4 rows --
+ * the support of its lowest, longest bin -- of 32 floats: Re's coefficient of bin 16 t + j at column j, Im's at column
+ * 16 + j.  Row r of tile t stands for m = r - h_(16 t): a shorter bin is centred in its tile, and exact zeros lie outside its
+ * own support, in the padding rows and in the padding bins.  The tiles lie one behind the other; tile_offset[t] is tile t's
+ * first row.  tile_rows / tile_offset hold (n_bins + 15) / 16 entries (either may be NULL).  Returns the floats of the table
+ * and, where table != NULL, writes them all; -1 where the check refuses the spec or table != NULL and cap is short of them,
+ * nothing written. */
+long long pdmp3_amd_cqt_table(const pdmp3_amd_cqt_spec* spec, long sr, float* table, size_t cap, int* tile_rows, int* tile_offset);
+/* What a workgroup of k_clip_cqt takes, the function the call itself uses.  One workgroup of eight waves per (*tile frames,
+ * channel, clip): 16 frames where the LDS below fits PDMP3_MEL_LDS_MAX (include/pdmp3_hip.h), else 8, else 4.  The LDS bytes:
+ * the tile's span, (*tile - 1) hop + tile_rows[0] samples in chunks of hop + *row_pad floats (hop + row_pad = 2 mod 32),
+ * rounded up to 4 floats, then the partial sums, 8 x 2 x 16 x 17 floats.  Up to 64 KB the launch asks for it dynamically,
+ * above that the kernel with a static array runs.  The first *n_split tiles -- those of *split_rows = PDMP3_CQT_SPLIT_ROWS
+ * rows or more -- are cut into *segments = 8 runs of rows, segment s being rows [s q, min((s + 1) q, R)) with q =
+ * ceil(R / 8) rounded up to 4, one a wave, each a chain from +0, the partial sums added as ((p0 + p1) + p2) + ...; every other
+ * tile is one chain from +0 over its rows.  0, or -1 where the check refuses the spec.  Pointers may be NULL. */
+int pdmp3_amd_cqt_plan(const pdmp3_amd_cqt_spec* spec, long sr, int* tile, int* row_pad, unsigned* lds_bytes, int* split_rows, int* segments,
+                       int* n_split);
+/* Row k receives channel c's [n_bins][n_frames] floats (mode 0: [n_bins][n_frames][2]) at dst + c * chan_stride.  Everything
+ * else -- the audio call in front, the stages, host destinations, the per-clip refusals in valid[k], rate 0 / channels 0,
+ * width, rolloff, the counts, n_clips = 0 and n_frames = 0, synchronous -- as pdmp3_amd_bulk_decode_clips_stft; k_clip_cqt
+ * (csrc/cqt.hip) writes the rows.  The decoder keeps the tables of the last PDMP3_CQT_TABLES distinct (sr, fmin, n_bins,
+ * bins_per_octave, filter_scale, norm, scale) and drops the least recently used one for a new one.  -1 also where
+ * pdmp3_amd_cqt_check says so. */
+int pdmp3_amd_bulk_decode_clips_cqt(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
+                                    long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -639,6 +639,35 @@ typedef struct pdmp3_mel_long_params {
 int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                             const float* operand, const pdmp3_mel_long_params* params);
 
+/* The constant-Q transform of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt).
+ * k_clip_cqt (cqt.hip) reads the rows as k_clip_stft does (pdmp3_mel_desc; a frame's span is rows0 samples, its centre the
+ * sample h_0) and writes [n_bins][n_frames] floats per channel, frames innermost; out_mode 0: [n_bins][n_frames][2].  The table
+ * is ragged: tile t of 16 bins has tile_rows[t] rows (a multiple of 4) of 32 floats from row tile_at[t] on, and its row r
+ * multiplies the frame's sample tile_base[t] + r.  A workgroup of eight waves takes `tile` frames.  Its LDS: span_floats for
+ * the tile's span in chunks of hop + row_pad floats, then 8 x 2 x 16 x 17 floats of partial sums. */
+#define PDMP3_CQT_MAX_TILES 32
+#define PDMP3_CQT_PART_FLOATS (8 * 2 * 16 * 17)
+typedef struct pdmp3_cqt_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t rows0, half0;                     /* tile_rows[0]: what a frame reads; h_0: the frame's centre in it          */
+  int32_t hop, row_pad;                     /* H; LDS floats between two hops' worth of the signal                      */
+  int32_t n_bins, n_tiles;                  /* n_tiles = n_bins rounded up to 16, over 16                               */
+  int32_t n_split;                          /* tiles 0 .. n_split - 1 are cut into eight segments of rows, one a wave   */
+  int32_t n_frames, tile;                   /* F; frames of a workgroup: 16, 8 or 4                                     */
+  int32_t channels, out_mode;               /* out_mode 0 complex, 1 magnitude, 2 power, 3 ln, 4 log10                  */
+  float floor;                              /* of the logarithms (modes 3 and 4)                                        */
+  uint32_t span_floats;                     /* LDS floats of the tile's span, a multiple of 4                           */
+  uint32_t lds_bytes;
+  int32_t tile_rows[PDMP3_CQT_MAX_TILES];   /* descending                                                               */
+  int32_t tile_base[PDMP3_CQT_MAX_TILES];   /* h_0 - h_(16 t)                                                           */
+  uint32_t tile_at[PDMP3_CQT_MAX_TILES];    /* the tile's first row in the table                                        */
+} pdmp3_cqt_params;
+/* Uploads the descriptors and the table (table_rows x 32 floats) -- host memory -- and runs k_clip_cqt on the slot's HIP
+ * stream, once per 32 768 clips.  The LDS limits are the log-mel call's (PDMP3_MEL_LDS_SOFT / _MAX).  Blocks until the rows
+ * are written. */
+int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                       const pdmp3_cqt_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

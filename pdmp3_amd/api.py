@@ -28,7 +28,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_stft_check", "pdmp3_amd_stft_table", "pdmp3_amd_stft_tile", "pdmp3_amd_bulk_decode_clips_stft",
                 "pdmp3_amd_stft_long_check", "pdmp3_amd_stft_long_tables", "pdmp3_amd_stft_long_plan", "pdmp3_amd_bulk_decode_clips_stft_long",
                 "pdmp3_amd_mel_long_check", "pdmp3_amd_mel_long_filterbank", "pdmp3_amd_mel_long_operand", "pdmp3_amd_mel_long_plan",
-                "pdmp3_amd_bulk_decode_clips_mel_long"]
+                "pdmp3_amd_bulk_decode_clips_mel_long",
+                "pdmp3_amd_cqt_check", "pdmp3_amd_cqt_lengths", "pdmp3_amd_cqt_table", "pdmp3_amd_cqt_plan", "pdmp3_amd_bulk_decode_clips_cqt"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -180,6 +181,13 @@ def load_library():
         lib.pdmp3_amd_mel_long_operand.restype = ll
         lib.pdmp3_amd_mel_long_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_mel_long.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_cqt"):          # (the constant-Q transform of clips: absent from older builds)
+        lib.pdmp3_amd_cqt_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_cqt_lengths.argtypes = [vp, C.c_long, vp, vp, C.c_size_t]
+        lib.pdmp3_amd_cqt_table.argtypes = [vp, C.c_long, vp, C.c_size_t, vp, vp]
+        lib.pdmp3_amd_cqt_table.restype = ll
+        lib.pdmp3_amd_cqt_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint)] + [C.POINTER(C.c_int)] * 3
+        lib.pdmp3_amd_bulk_decode_clips_cqt.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -628,6 +636,70 @@ def stft_tile(n_fft, hop, mode="complex"):
     if load_library().pdmp3_amd_stft_tile(int(n_fft), int(hop), m, C.byref(t), C.byref(p), C.byref(b)) != 0:
         raise ValueError("pdmp3_amd_stft_tile: bad argument")
     return t.value, p.value, b.value
+
+
+class _CqtSpec(C.Structure):                       # include/pdmp3_bulk.h pdmp3_amd_cqt_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("hop", C.c_int), ("fmin", C.c_double),
+                ("n_bins", C.c_int), ("bins_per_octave", C.c_int), ("filter_scale", C.c_double), ("norm", C.c_int), ("scale", C.c_int),
+                ("n_frames", C.c_longlong), ("out_mode", C.c_int), ("floor", C.c_double)]
+
+
+CQT_FMIN = 32.70319566257483                       # C1
+
+
+def _cqt_spec(n_frames=1, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, filter_scale=1.0, norm=1, scale=1,
+              mode="magnitude", floor=1e-10, channels=1, width=0, rolloff=0.0):
+    return _CqtSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(hop), float(fmin), int(n_bins), int(bins_per_octave),
+                    float(filter_scale), int(norm), int(scale), int(n_frames), STFT_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+
+
+def cqt_check(sample_rate=22050, **kw):
+    """pdmp3_amd_cqt_check -> True when pdmp3_amd_bulk_decode_clips_cqt would accept these numbers (decode_clips_cqt's argument
+    names) at sample_rate"""
+    try:
+        spec = _cqt_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError):
+        return False
+    return load_library().pdmp3_amd_cqt_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def cqt_lengths(sample_rate=22050, **kw):
+    """pdmp3_amd_cqt_lengths -> (f_k float64 [n_bins], h_k int32 [n_bins]): the bins' frequencies and half lengths, N_k = 2 h_k + 1"""
+    spec = _cqt_spec(sample_rate=sample_rate, **kw)
+    n = max(spec.n_bins, 1)
+    f = np.full(n, np.nan, dtype=np.float64)
+    h = np.full(n, -1, dtype=np.int32)
+    if load_library().pdmp3_amd_cqt_lengths(C.byref(spec), int(sample_rate), f.ctypes.data, h.ctypes.data, n) != spec.n_bins:
+        raise ValueError("pdmp3_amd_cqt_lengths: bad argument")
+    return f, h
+
+
+def cqt_table(sample_rate=22050, **kw):
+    """pdmp3_amd_cqt_table -> (float32 numpy [rows, 32] as k_clip_cqt reads it, rows of each tile of 16 bins, first row of each):
+    tile t's row r holds Re's coefficient of bin 16 t + j at sample m = r - h_(16 t) in column j and Im's in column 16 + j"""
+    lib = load_library()
+    spec = _cqt_spec(sample_rate=sample_rate, **kw)
+    nt = (max(spec.n_bins, 1) + 15) // 16
+    rows = np.zeros(nt, dtype=np.int32)
+    at = np.zeros(nt, dtype=np.int32)
+    count = lib.pdmp3_amd_cqt_table(C.byref(spec), int(sample_rate), None, 0, rows.ctypes.data, at.ctypes.data)
+    if count < 0:
+        raise ValueError("pdmp3_amd_cqt_table: bad argument")
+    t = np.full((count // 32, 32), np.nan, dtype=np.float32)
+    if lib.pdmp3_amd_cqt_table(C.byref(spec), int(sample_rate), t.ctypes.data, t.size, None, None) != count:
+        raise ValueError("pdmp3_amd_cqt_table: bad argument")
+    return t, rows, at
+
+
+def cqt_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_cqt_plan -> (frames of a workgroup of k_clip_cqt, LDS floats between two hops, LDS bytes of a workgroup, rows
+    from which a tile is split, segments of a split tile, tiles that are split)"""
+    spec = _cqt_spec(sample_rate=sample_rate, **kw)
+    t, p, sr, sg, ns, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_cqt_plan(C.byref(spec), int(sample_rate), C.byref(t), C.byref(p), C.byref(b), C.byref(sr), C.byref(sg),
+                                         C.byref(ns)) != 0:
+        raise ValueError("pdmp3_amd_cqt_plan: bad argument")
+    return t.value, p.value, b.value, sr.value, sg.value, ns.value
 
 
 def stft_long_check(sample_rate=44100, n_fft=2048, hop=512, **kw):
@@ -1232,8 +1304,24 @@ class BulkDecoder:
         return self._clips_stft("stft_long", clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels,
                                 width, rolloff, out)
 
-    def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out):
-        k, f, nb = len(clips), int(n_frames), int(n_fft) // 2 + 1
+    def decode_clips_cqt(self, clips, n_frames, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, filter_scale=1.0,
+                         norm=1, scale=1, mode="magnitude", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_cqt: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        the constant-Q transform [K, C, n_bins, n_frames], frame f of a clip centred on sample start + f hop of the stream
+        resampled as decode_clips_audio does (width, rolloff), zeros outside the stream and no reflection.  Bin k is at
+        fmin 2^(k / bins_per_octave); its filter is the periodic Hann window of the odd length about
+        filter_scale sample_rate / (f_k (2^(1 / bins_per_octave) - 1)), normalised by norm (0 none, 1 its sum, 2 its Euclidean
+        norm) and scaled by scale (0 none, 1 sqrt(length), 2 length): norm=1, scale=1 is the convention of librosa's
+        cqt(norm=1, scale=True), computed in full at the one rate -- not librosa's multirate approximation.  mode, floor, valid,
+        out, RingReplay / MixedFormat as decode_clips_stft.  Synchronous."""
+        spec = lambda f: _cqt_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, mode, floor, channels, width, rolloff)
+        return self._clips_stft("cqt", clips, n_frames, sample_rate, None, hop, None, None, None, mode, floor, channels, width, rolloff, out,
+                                nb=int(n_bins), spec_of=spec)
+
+    def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
+                    nb=None, spec_of=None):
+        k, f = len(clips), int(n_frames)
+        nb = int(n_fft) // 2 + 1 if nb is None else nb
         m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
         c = int(channels)
         if not c:
@@ -1269,8 +1357,11 @@ class BulkDecoder:
             keep.append(a)
             arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
         try:
-            spec, wkeep = _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
-        except ValueError as e:
+            if spec_of is not None:
+                spec = spec_of(f)
+            else:
+                spec, wkeep = _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
+        except (ValueError, OverflowError) as e:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s: %s" % (call, e))
         got = (C.c_longlong * max(k, 1))()
         rc = getattr(self.lib, "pdmp3_amd_bulk_decode_clips_" + call)(self.h, arr, k, C.byref(spec), got)

@@ -1,0 +1,175 @@
+// cqt.hip -- k_clip_cqt: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's third
+// audio stage) to their constant-Q transform, planar float32 [n_bins][n_frames] per clip and channel -- complex
+// ([n_bins][n_frames][2]), magnitude, power or its logarithm (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt; DESIGN.md
+// section 16).  Launched by stream.hip pdmp3_hip_clip_cqt.  A translation unit of its own, so that every other kernel's code
+// is what it is without it; the span's indexing is mel_core.h's, what is stored stft_core.h's, the segments and the order of
+// the partial sums cqt_core.h's.
+#include <hip/hip_runtime.h>
+
+#include "../../include/pdmp3_hip.h"
+#include "cqt_core.h"
+
+namespace {
+
+using namespace pdmp3;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// a (Re, Im) pair of the output: one 8-byte store; a row may start at any float, and the device stores 8 bytes at 4-byte alignment
+typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
+// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
+// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
+__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// what a wave's lanes wrote to its plane is there for its other lanes (LDS operations of a wave complete in order)
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Rows [r0, r1) of a tile of 16 bins (r0, r1 multiples of 4) times the 16 frames of the workgroup, Re and Im each one chain
+// from +0, rows ascending, into the wave's plane `pw`.  The frames are overlapping rows of the span: the A operand is read at
+// jf hop + base + n and never materialised; the B operand is the tile's rows of the table, read from memory (L2): four rows of
+// 32 floats a step.  Lanes of frames from FT on (tiles of 8 and 4 frames) read frame j mod FT again: nothing of theirs is stored.
+// A shorter tile's padding rows (up to three, exact zeros) may stand behind the span's last sample: the read stops at `last`,
+// the span's last float, and the finite sample there times the zero adds nothing.
+__device__ __forceinline__ void cqt_rows(const float* span, const float* __restrict__ tile_tab, unsigned base, int r0, int r1, unsigned hop,
+                                         unsigned chunk, unsigned last, unsigned jf, int j, int kq, float* pw) {
+  f32x4 re = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, im = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+  const unsigned q = base + (unsigned)r0 + (unsigned)kq;
+  unsigned c = jf + q / hop, rem = q % hop;
+  const float* bp = tile_tab + (size_t)(r0 + kq) * 32 + j;
+  // one step: four rows of the table times the sixteen frames' four samples, on top of the two chains
+  auto step = [&](float b_re, float b_im) {
+    const float a = span[min(c * chunk + rem, last)];
+    re = mfma16(a, b_re, re);
+    im = mfma16(a, b_im, im);
+    rem += 4;
+    if (rem >= hop) {
+      if (hop >= 4) { rem -= hop; c++; }
+      else { c += rem / hop; rem %= hop; }
+    }
+  };
+  // blocks of kU steps: the next block's coefficients are on their way from L2 while this block's matrix instructions run
+  constexpr int kU = 8;
+  const int blocks = (r1 - r0) / (4 * kU);
+  float cre[kU], cim[kU], nre[kU], nim[kU];
+  if (blocks > 0) {
+#pragma unroll
+    for (int u = 0; u < kU; u++) { cre[u] = bp[128 * u]; cim[u] = bp[128 * u + 16]; }
+    bp += 128 * kU;
+  }
+  for (int b = 0; b < blocks; b++) {
+    if (b + 1 < blocks) {
+#pragma unroll
+      for (int u = 0; u < kU; u++) { nre[u] = bp[128 * u]; nim[u] = bp[128 * u + 16]; }
+      bp += 128 * kU;
+    }
+#pragma unroll
+    for (int u = 0; u < kU; u++) step(cre[u], cim[u]);
+#pragma unroll
+    for (int u = 0; u < kU; u++) { cre[u] = nre[u]; cim[u] = nim[u]; }
+  }
+  for (int n = r0 + 4 * kU * blocks; n < r1; n += 4) {
+    step(bp[0], bp[16]);
+    bp += 128;
+  }
+#pragma unroll
+  for (int r = 0; r < 4; r++) {
+    pw[cqt_part_at(j, 4 * kq + r)] = re[r];
+    pw[kCqtPlane + cqt_part_at(j, 4 * kq + r)] = im[r];
+  }
+}
+
+// value i of a tile's 16 bins x 16 frames: the partial sums of `parts` waves added in cqt_reduce's order, turned into what is
+// stored (stft_value; mode 0: the pair); consecutive lanes store consecutive frames of one bin.  Bins from n_bins on and
+// frames from the tile's and from F on are not stored.
+__device__ __forceinline__ void cqt_store(const pdmp3_cqt_params& P, float* out, const float* part, int parts, int t, long long f0, int i) {
+  const int b = i >> 4, fl = i & 15, k = (t << 4) + b;
+  const long long f = f0 + fl;
+  const float re = cqt_reduce(part, cqt_part_at(b, fl), parts);
+  const float im = cqt_reduce(part + kCqtPlane, cqt_part_at(b, fl), parts);
+  if (k >= P.n_bins || fl >= P.tile || f >= P.n_frames) return;
+  const size_t at = (size_t)k * (size_t)P.n_frames + (size_t)f;
+  if (P.out_mode != 0) out[at] = stft_value(re, im, P.floor, P.out_mode);
+  else *reinterpret_cast<f32x2*>(out + 2 * at) = f32x2{re, im};
+}
+
+// One workgroup of eight waves per (tile of P.tile frames, channel, clip).
+//   1. the tile's span -- (tile - 1) hop + rows0 samples, zeros outside the clip's row -- goes to LDS once (mel_lds_at);
+//   2. the first n_split tiles of 16 bins, the long ones: each wave takes one of eight runs of the tile's rows
+//      (cqt_seg_begin) and writes its 16 x 16 partial sums of Re and of Im to its plane; after a barrier the first four waves
+//      add the eight planes in one fixed order and store; a second barrier frees the planes;
+//   3. the other tiles go whole to one wave each, round robin, through the wave's own plane: no workgroup barrier.
+// The order of operations of a value depends on the plan alone: every frame's values come from the same chains whatever its
+// place in a tile, clip or batch.
+__device__ __forceinline__ void cqt_tile(const pdmp3_mel_desc& d, const float* __restrict__ tab, const pdmp3_cqt_params& P, int ch, long long f0,
+                                         float* lds) {
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, j = lane & 15, kq = lane >> 4;
+  const unsigned hop = (unsigned)P.hop, pad = (unsigned)P.row_pad, chunk = hop + pad;
+  const int FT = P.tile;
+  const unsigned jf = (unsigned)(j & (FT - 1));
+  float* const span = lds;
+  float* const part = lds + P.span_floats;
+  float* const pw = part + wave * kCqtPart;
+  const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
+
+  const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows0;
+  const unsigned last = mel_lds_at(n_span - 1, hop, pad);
+  for (unsigned p = tid; p < n_span; p += kCqtThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  __syncthreads();
+
+  float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
+  for (int t = 0; t < P.n_split; t++) {
+    const int R = P.tile_rows[t];
+    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], cqt_seg_begin(R, wave), cqt_seg_begin(R, wave + 1), hop, chunk, last,
+             jf, j, kq, pw);
+    __syncthreads();
+    if (tid < 256) cqt_store(P, out, part, kCqtWaves, t, f0, tid);
+    __syncthreads();                                   // (the next tile's partial sums go to the same planes)
+  }
+  for (int t = P.n_split + wave; t < P.n_tiles; t += kCqtWaves) {
+    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], 0, P.tile_rows[t], hop, chunk, last, jf, j, kq, pw);
+    wave_sync();
+#pragma unroll
+    for (int it = 0; it < 4; it++) cqt_store(P, out, pw, 1, t, f0, 64 * it + lane);
+    wave_sync();
+  }
+}
+
+__global__ __launch_bounds__(kCqtThreads) void k_clip_cqt(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
+                                                          pdmp3_cqt_params P) {
+  extern __shared__ __align__(16) float lds[];
+  const pdmp3_mel_desc d = descs[blockIdx.y];
+  const int ch = blockIdx.x % P.channels;
+  const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
+  if (f0 >= P.n_frames) return;
+  cqt_tile(d, tab, P, ch, f0, lds);
+}
+
+// A plan of more than the 64 KB a launch can ask for dynamically (the low octaves: C1 at 22 050 Hz is 95.5 KB): the same code
+// on a static array of all the LDS a workgroup may have, one workgroup a CU.
+__global__ __launch_bounds__(kCqtThreads) void k_clip_cqt_big(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
+                                                              pdmp3_cqt_params P) {
+  __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
+  const pdmp3_mel_desc d = descs[blockIdx.y];
+  const int ch = blockIdx.x % P.channels;
+  const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
+  if (f0 >= P.n_frames) return;
+  cqt_tile(d, tab, P, ch, f0, lds);
+}
+
+}  // namespace
+
+hipError_t pdmp3_launch_clip_cqt(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_cqt_params* params) {
+  const pdmp3_cqt_params P = *params;
+  if (n_clips <= 0 || P.n_frames <= 0) return hipSuccess;
+  // a plan this file has no kernel for
+  if ((P.tile != 16 && P.tile != 8 && P.tile != 4) || P.lds_bytes > PDMP3_MEL_LDS_MAX || P.n_tiles < 1 || P.n_tiles > PDMP3_CQT_MAX_TILES ||
+      P.n_split < 0 || P.n_split > P.n_tiles)
+    return hipErrorInvalidValue;
+  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
+  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
+  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) hipLaunchKernelGGL(k_clip_cqt_big, grid, dim3(pdmp3::kCqtThreads), 0, s, descs, table, P);
+  else hipLaunchKernelGGL(k_clip_cqt, grid, dim3(pdmp3::kCqtThreads), P.lds_bytes, s, descs, table, P);
+  return hipGetLastError();
+}

@@ -166,6 +166,8 @@ hipError_t pdmp3_launch_clip_mfcc(hipStream_t s, const pdmp3_fbank_desc* descs, 
                                   float* sums, const pdmp3_mfcc_params* params);
 // ---- stft.hip ----
 hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_stft_params* params);
+// ---- cqt.hip ----
+hipError_t pdmp3_launch_clip_cqt(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_cqt_params* params);
 // ---- stft_long.hip ----
 hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                        const pdmp3_stft_long_params* params);

@@ -692,6 +692,54 @@ extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_m
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }
+// ---- the constant-Q transform (cqt.hip) ----
+extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                                  const pdmp3_cqt_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !table || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: bad argument", hipSuccess);
+  const pdmp3_cqt_params& P = *params;
+  // what the kernel's indexing relies on
+  if (P.n_bins < 1 || P.n_bins > 16 * PDMP3_CQT_MAX_TILES || P.n_tiles != (P.n_bins + 15) / 16 || P.n_split < 0 || P.n_split > P.n_tiles ||
+      P.hop < 1 || P.row_pad < 0 || (P.tile != 16 && P.tile != 8 && P.tile != 4) || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 ||
+      P.out_mode > 4 || P.n_frames < 0 || P.n_in < 0 || (P.out_mode >= 3 && !(P.floor > 0.0f)) || (P.span_floats & 3u) ||
+      P.lds_bytes > PDMP3_MEL_LDS_MAX || P.rows0 < 4 || P.rows0 != P.tile_rows[0] || P.rows0 != ((2 * P.half0 + 4) & ~3) || table_rows > (size_t)1 << 24)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: bad parameters", hipSuccess);
+  for (int t = 0; t < P.n_tiles; t++) {
+    // a tile's rows lie inside the table, and what they multiply inside a frame's span but for up to three rows of padding
+    if (P.tile_rows[t] < 4 || (P.tile_rows[t] & 3) || (size_t)P.tile_at[t] + (size_t)P.tile_rows[t] > table_rows || P.tile_base[t] < 0 ||
+        P.tile_base[t] + P.tile_rows[t] > P.rows0 + 3)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: a tile of the table lies outside it or outside the span", hipSuccess);
+  }
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.rows0, chunks = (span + P.hop - 1) / P.hop;
+    if (P.span_floats < chunks * (size_t)(P.hop + P.row_pad) ||
+        (size_t)P.lds_bytes < ((size_t)P.span_floats + PDMP3_CQT_PART_FLOATS) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: a tile's span and partial sums do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: too many frames", hipSuccess);
+  }
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: slot still in flight (wait for it first)", hipSuccess);
+  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  // descriptors | table: one block (the log-mel call's; the calls never overlap in time), each part 256-byte aligned
+  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
+  const size_t tab_bytes = table_rows * 32 * sizeof(float);
+  { void* p = hs->d_mel_args;
+    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc cqt table");
+    hs->d_mel_args = (uint8_t*)p;
+    if (rc != PDMP3_HIP_OK) return rc; }
+  uint8_t* a = hs->d_mel_args;
+  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D cqt descriptors");
+  HIP_TRY(hipMemcpyAsync(a + desc_bytes, table, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D cqt table");
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(pdmp3_launch_clip_cqt(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
+                                  reinterpret_cast<const float*>(a + desc_bytes), &P),
+            "launch k_clip_cqt");
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
 // ---- the short-time Fourier transform at n_fft 2048 and 4096 (stft_long.hip) ----
 extern "C" int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                         const pdmp3_stft_long_params* params) {

@@ -85,6 +85,9 @@ typedef struct mfcc_tab { int n_mels, n_ceps, htk, energy; double lifter; float*
 /* the short-time Fourier transform (clip_stft.c): a folded table per (N, Nw, normalized, the window's values: a copy of the
  * caller's, NULL for the Hann window); a short list, the most recently used first */
 typedef struct stft_tab { int n_fft, win, normalized; float* window; float* t; struct stft_tab* next; } stft_tab;
+/* the constant-Q transform (clip_cqt.c): a ragged folded table per (sr, fmin, n_bins, bins_per_octave, filter_scale, norm,
+ * scale); a short list, the most recently used first */
+typedef struct cqt_tab { long sr; int n_bins, bpo, norm, scale; double fmin, filter_scale; float* t; struct cqt_tab* next; } cqt_tab;
 
 struct bulk {
   pdmp3_handle* id;
@@ -192,6 +195,7 @@ struct bulk {
   struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
   struct mfcc_tab* mfcc_tabs;         /* Kaldi-style MFCC features: the folded DCT tables made so far */
   struct stft_tab* stft_tabs;         /* the short-time Fourier transform: the last PDMP3_STFT_TABLES folded tables */
+  struct cqt_tab* cqt_tabs;           /* the constant-Q transform: the last PDMP3_CQT_TABLES tables */
   float* stft_long_tabs[2];           /* ... at n_fft 2048 and 4096: a call's block of tables, made once; its wt is filled per call */
 };
 
@@ -360,6 +364,11 @@ HOST_LOCAL int mfcc_plan(int win, int n_dft, int hop, int n_mels, int n_ceps, pd
 HOST_LOCAL void stft_table_fill(const pdmp3_amd_stft_spec* s, float* t);
 HOST_LOCAL int stft_plan(int n_fft, int hop, int out_mode, pdmp3_stft_params* p);
 HOST_LOCAL const float* stft_table(struct bulk* b, const pdmp3_amd_stft_spec* s);
+/* clip_cqt.c: the plan of a workgroup of k_clip_cqt with the table's tiles (0, or -1 where the check refuses the spec), the
+ * table of a plan's spec into rows x 32 floats, and the decoder's table of it (NULL: no memory) */
+HOST_LOCAL int cqt_plan(const pdmp3_amd_cqt_spec* s, long sr, pdmp3_cqt_params* p);
+HOST_LOCAL void cqt_table_fill(const pdmp3_amd_cqt_spec* s, long sr, const pdmp3_cqt_params* p, float* t);
+HOST_LOCAL const float* cqt_table(struct bulk* b, const pdmp3_amd_cqt_spec* s, long sr, const pdmp3_cqt_params* p);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

@@ -1356,3 +1356,122 @@ int pdmp3_amd_bulk_decode_clips_mfcc(struct bulk* b, const pdmp3_amd_audio_clip*
   if (!spec) return -1;
   return kaldi_clips(b, clips, n_clips, &spec->fbank, spec, valid);
 }
+
+/* ---- the constant-Q transform of clips ---- */
+/* The short-time Fourier transform's course with another plan, table and launch: the rows through the audio call into stage
+ * 2, k_clip_cqt behind it, host destinations through stage 1. */
+int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
+                                    long long* valid) {
+  if (!b || !b->hs || !b->bits_mode || !spec || n_clips < 0 || (n_clips && (!clips || !valid)) || spec->n_frames < 0) return -1;
+  const long long F = spec->n_frames;
+  int C = spec->channels, rc = 0;
+  long sr = spec->rate;
+  if (C < 0 || C > 2 || sr < 0) return -1;
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    if (!c->index || (!c->mp3 && c->n) || c->n != c->index->n || c->start < 0 || (F && !c->dst)) return -1;
+    if ((c->index->iso & PDMP3_ISO_LSF) != (b->id->iso & PDMP3_ISO_LSF)) return -1;
+    if (c->index->frames < 0 || c->index->mixed) continue;
+    const int cs = c->index->stereo ? 2 : 1;
+    if (!spec->channels) {
+      if (C && C != cs) return -1;                   /* (no channel count asked for, and the clips' differ) */
+      C = cs;
+    }
+    if (!spec->rate && c->index->frames) {
+      if (sr && sr != c->index->rate) return -1;     /* (no rate asked for, and the clips' differ: one time line a call) */
+      sr = c->index->rate;
+    }
+  }
+  if (!C) C = 1;
+  if (!sr) sr = 44100;                               /* (no clip to decode, or only streams without frames) */
+  pdmp3_cqt_params P;
+  if (cqt_plan(spec, sr, &P) != 0) return -1;                         /* (the check's verdict and the plan in one) */
+  /* a frame reads N = N_0 = 2 h_0 + 1 samples, its centre the sample N / 2 = h_0; the table's rows behind them are zeros */
+  const int N = 2 * P.half0 + 1, H = spec->hop;
+  const int per_frame = P.n_bins * (spec->out_mode == 0 ? 2 : 1);     /* floats of a frame */
+  if (F > 0x7fffffffLL / (per_frame > H ? per_frame : H) - 2 * N) return -1;                /* (a row's samples and floats stay inside 31 bits) */
+  const size_t per = (size_t)per_frame * (size_t)F;                   /* floats of a channel's output */
+  for (int k = 0; k < n_clips; k++) if (C == 2 && F && clips[k].chan_stride < per) return -1;
+  const long long T = F ? (F - 1) * H + N : 0;                        /* samples of a row: what F frames read */
+  const size_t Ts = ((size_t)T + 3) & ~(size_t)3;
+  pdmp3_amd_audio_clip* ac = (pdmp3_amd_audio_clip*)calloc((size_t)n_clips + 1, sizeof *ac);
+  long long* av = (long long*)calloc((size_t)n_clips + 1, sizeof *av);
+  pdmp3_mel_desc* ds = (pdmp3_mel_desc*)calloc((size_t)n_clips + 1, sizeof *ds);
+  int* host = (int*)calloc((size_t)n_clips + 1, sizeof *host);       /* per descriptor: its clip, if that one's rows go to host memory, else -1 */
+  int nd = 0;
+  size_t out_floats = 0;
+  if (!ac || !av || !ds || !host) { rc = -1; goto out; }
+  for (int k = 0; k < n_clips; k++) {
+    const pdmp3_amd_audio_clip* c = &clips[k];
+    const pdmp3_amd_index* ix = c->index;
+    if (ix->frames < 0) { valid[k] = PDMP3_BULK_REPLAY; rc = PDMP3_BULK_REPLAY; continue; }
+    if (ix->mixed) { valid[k] = PDMP3_BULK_MIXED_FORMAT; if (rc != PDMP3_BULK_REPLAY) rc = PDMP3_BULK_MIXED_FORMAT; continue; }
+    audio_plan p;
+    if (audio_plan_init(&p, ix->frames ? ix->rate : sr, sr, spec->width, spec->rolloff) != 0) { rc = -1; goto out; }
+    const long long Nin = ix->frames * (ix->frames ? ix->spf : 0);
+    const long long J = (long long)(((__int128)Nin * p.L + p.M - 1) / p.M);
+    const long long left = J - c->start;
+    valid[k] = left <= 0 ? 0 : (left + H - 1) / H < F ? (left + H - 1) / H : F;
+    if (!F) continue;
+    /* the row: the span from max(0, start - N / 2) on, `lead` zeros in front of it */
+    const long long s0 = c->start > N / 2 ? c->start - N / 2 : 0;
+    ac[nd].mp3 = c->mp3; ac[nd].n = c->n; ac[nd].index = ix;
+    ac[nd].start = s0;
+    ac[nd].chan_stride = Ts;
+    ds[nd].lead = (uint32_t)(s0 - (c->start - N / 2));
+    ds[nd].src_chan_stride = Ts;
+    const size_t row_bytes = ((size_t)(C - 1) * c->chan_stride + per) * sizeof(float);
+    if (pdmp3_hip_host_is_pinned(c->dst, row_bytes) == 2) { host[nd] = -1; ds[nd].dst = (uint64_t)(uintptr_t)c->dst; ds[nd].dst_chan_stride = c->chan_stride; }
+    else { host[nd] = k; ds[nd].dst = out_floats; ds[nd].dst_chan_stride = per; out_floats += (size_t)C * per; }
+    nd++;
+  }
+  if (!nd) goto out;
+  const float* table = cqt_table(b, spec, sr, &P);
+  if (!table) { rc = -1; goto out; }
+  if (pdmp3_amd_bulk_wait(b) != 0) { rc = -1; goto out; }
+  float* sig = (float*)pdmp3_hip_stream_audio_stage(b->hs, 2, (size_t)nd * (size_t)C * Ts * sizeof(float));
+  if (!sig) { rc = -1; goto out; }
+  for (int i = 0; i < nd; i++) {
+    ac[i].dst = sig + (size_t)i * (size_t)C * Ts;
+    ds[i].src = (uint64_t)(uintptr_t)ac[i].dst;
+  }
+  /* the rows through the audio call as it is (device destinations: k_clip_audio writes them itself) */
+  {
+    pdmp3_amd_audio_spec as;
+    memset(&as, 0, sizeof as);
+    as.rate = sr; as.channels = C; as.n_samples = T; as.width = spec->width; as.rolloff = spec->rolloff;
+    if (pdmp3_amd_bulk_decode_clips_audio(b, ac, nd, &as, av) != 0) { rc = -1; goto out; }
+  }
+  /* (the audio call may have grown stage 1 for nothing of ours: it is free for the rows of host destinations) */
+  float* out_stage = out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, out_floats * sizeof(float)) : NULL;
+  if (out_floats && !out_stage) { rc = -1; goto out; }
+  for (int i = 0; i < nd; i++) if (host[i] >= 0) ds[i].dst = (uint64_t)(uintptr_t)(out_stage + ds[i].dst);
+  P.n_in = T; P.n_frames = (int32_t)F; P.channels = C; P.floor = spec->out_mode >= 3 ? (float)spec->floor : 0.0f;
+  if (pdmp3_hip_clip_cqt(b->hs, CLIP_SLOT, ds, nd, table, (size_t)P.tile_at[P.n_tiles - 1] + (size_t)P.tile_rows[P.n_tiles - 1], &P) != PDMP3_HIP_OK) {
+    fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
+    rc = -1; goto out;
+  }
+  /* host destinations: rows that lie one behind the other in the caller's memory as they do in the stage leave in one copy */
+  for (int i = 0; i < nd; i++) {
+    if (host[i] < 0) continue;
+    const pdmp3_amd_audio_clip* c = &clips[host[i]];
+    const float* from = (const float*)(uintptr_t)ds[i].dst;
+    if (C == 2 && c->chan_stride != per) {
+      if (pdmp3_hip_copy_from_device(c->dst, from, per * sizeof(float)) != PDMP3_HIP_OK ||
+          pdmp3_hip_copy_from_device(c->dst + c->chan_stride, from + per, per * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+      continue;
+    }
+    size_t floats = (size_t)C * per;
+    int j = i + 1;
+    for (; j < nd && host[j] >= 0; j++) {
+      const pdmp3_amd_audio_clip* n = &clips[host[j]];
+      if (n->dst != c->dst + floats || (C == 2 && n->chan_stride != per)) break;
+      floats += (size_t)C * per;
+    }
+    if (pdmp3_hip_copy_from_device(c->dst, from, floats * sizeof(float)) != PDMP3_HIP_OK) { rc = -1; goto out; }
+    i = j - 1;
+  }
+out:
+  free(ac); free(av); free(ds); free(host);
+  return rc;
+}

@@ -596,6 +596,99 @@ def clips_mel_long(args, api):
     print(json.dumps(res))
 
 
+def clips_cqt(args, api):
+    """--cqt: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as the magnitudes of 84 constant-Q bins
+    (C1, 12 an octave, norm 1, scale 1) x 1292 frames (hop 512) in device memory, three ways, run after run in turn: (a)
+    pdmp3_amd_bulk_decode_clips_audio for the same spans; (b) (a) followed by a dense torch matmul of the unfolded frames with
+    the table as a dense [N_0, 2 x 84] matrix (every bin at the longest filter's length), eight clips at a time, and the
+    magnitude; (c) pdmp3_amd_bulk_decode_clips_cqt.  (c) is compared once with (b) (largest difference, printed, not asserted:
+    the tests check (c) against the definition).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, hop, n_bins = args.clips, args.clip_frames, 22050, 512, 84
+    f_k, half = api.cqt_lengths(rate)
+    h0 = int(half[0])
+    n0 = 2 * h0 + 1
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = 1292 if F == 1149 else (F * 1152 * rate // 44100) // hop + 1
+    T = (Fm - 1) * hop + n0
+    dev = "cuda:0"
+    cq, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), h0)               # (no leading zeros: (a)'s rows start at start - h_0)
+        cq.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - h0))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, n_bins, Fm), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, n_bins, Fm), dtype=torch.float32, device=dev)
+    tab, rows, at = api.cqt_table(rate)
+    dense = np.zeros((n0, 2 * n_bins), dtype=np.float32)
+    for k in range(n_bins):
+        t = k // 16
+        r0, n = h0 - int(half[16 * t]), min(int(rows[t]), n0 - (h0 - int(half[16 * t])))
+        dense[r0:r0 + n, k] = tab[at[t]:at[t] + n, k % 16]
+        dense[r0:r0 + n, n_bins + k] = tab[at[t]:at[t] + n, 16 + k % 16]
+    dense = torch.from_numpy(dense).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+        for k0 in range(0, K, 8):
+            x = out_a[k0:k0 + 8, 0].unfold(1, n0, hop) @ dense                                                           # [8, Fm, 2 x 84]
+            out_b[k0:k0 + 8, 0] = torch.sqrt(x[:, :, :n_bins] ** 2 + x[:, :, n_bins:] ** 2).transpose(1, 2)
+        torch.cuda.synchronize()
+
+    def cqt_route():
+        dec.decode_clips_cqt(cq, Fm, rate, hop, out=out_c)
+
+    routes = [("audio clips", audio_route), ("audio clips + dense torch matmul + magnitude", torch_route), ("cqt clips", cqt_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = {"torch_route": float((out_b - out_c).abs().max()), "largest_magnitude": float(out_c.abs().max())}
+    dec.close()
+    plan = api.cqt_plan(rate, hop=hop)
+    res = {"workload": "%d clips of %d frames' length as %d constant-Q bins x %d frames at %d Hz mono (C1, 12 an octave, hop %d): %s" % (
+               K, F, n_bins, Fm, rate, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "plan": {"tile": plan[0], "lds_bytes": plan[2], "split_tiles": plan[5], "table_rows": int(rows.sum()), "dense_rows": 6 * int(rows[0])},
+           "result_bytes": K * n_bins * Fm * 4, "largest_difference_from_cqt": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["cqt_minus_audio_ms"] = round((med["cqt clips"] - med["audio clips"]) * 1e3, 3)
+    res["torch_route_minus_audio_ms"] = round((med["audio clips + dense torch matmul + magnitude"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -818,6 +911,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as 128 x 2583 log10-mel frames at 44.1 kHz mono, n_fft 2048, hop 512 "
                          "(pdmp3_amd_bulk_decode_clips_mel_long) against the audio call alone, the audio call followed by torch kernels, and "
                          "pdmp3_amd_bulk_decode_clips_stft_long's powers followed by a matmul and log10 (see clips_mel_long())")
+    ap.add_argument("--cqt", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as 84 x 1292 constant-Q magnitudes at 22 050 Hz mono, C1, 12 bins an "
+                         "octave, hop 512 (pdmp3_amd_bulk_decode_clips_cqt) against the audio call alone and the audio call followed by a "
+                         "dense torch matmul over unfolded frames (see clips_cqt())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -825,12 +922,14 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long:
+    if args.stft_long or args.mel_long or args.cqt:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
     if args.clips:
         from pdmp3_amd import api
+        if args.cqt:
+            return clips_cqt(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
