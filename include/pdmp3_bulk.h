@@ -721,6 +721,61 @@ int pdmp3_amd_cqt_plan(const pdmp3_amd_cqt_spec* spec, long sr, int* tile, int* 
 int pdmp3_amd_bulk_decode_clips_cqt(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
                                     long long* valid);
 
+/* ---- Chroma features of clips ----
+ * Pitch-class profiles, what transcription, chord and key models start from: K clips as one planar float32 batch
+ * [K][C][n_chroma][F], frames innermost, straight from MP3 bytes.  New entry points only; nothing above returns anything else.
+ *
+ * Signal, clip, frame position, valid, destinations and strides are section 16's: real neighbours inside the stream, zeros
+ * outside, no reflection.  The bins f_k, the filters g_k, norm, scale and C[f, k] are section 16's, computed by section 16's
+ * table and section 16's chains.
+ *   q_k[f] is what pdmp3_amd_bulk_decode_clips_cqt stores for bin k at out_mode 1 (or 2): the same binary32 value, bit for
+ *     bit, from the same chains.
+ *   class(k) = ((k + r / 2) / r + base_class) mod n_chroma in integer division, r = bins_per_octave / n_chroma.  For r = 3
+ *     class p collects bins 3 p - 1, 3 p, 3 p + 1 of every octave -- the centring of librosa's cq_to_chroma; for r = 1 it is
+ *     k mod n_chroma rotated.
+ *   c_p[f] is the binary32 sum of q_k[f] over the bins of class p, k ascending: it starts from the first term and uses plain
+ *     additions in this order and no other.  A class without a bin is +0.
+ *   The norm d[f] over p = 0 .. n_chroma - 1 ascending: L1 ((c_0 + c_1) + c_2) + ... (no absolute value: every c_p >= 0);
+ *     L2 sqrtf, correctly rounded, of the chain s = c_0 c_0, s = fma(c_p, c_p, s); max the exact maximum.
+ *   The output is c_p / max(d, (float)norm_floor), one correctly rounded binary32 division, or c_p itself at chroma_norm 0.
+ *     A silent frame is exactly +0 in every mode.  There is no threshold and no branch on d other than the max: the result
+ *     is a continuous function of the signal.
+ * As in section 16 the definition is the formula, not librosa's multirate chroma_cqt: no agreement with librosa is promised
+ * beyond the convention.  36 bins an octave from C1 at 22 050 Hz are refused: N_0 = 34 683 > PDMP3_CQT_MAX_LEN, which
+ * pdmp3_amd_cqt_check says already; 36 an octave from C2 (N_0 = 17 341) and 24 an octave from C1 (N_0 = 23 011) fit.
+ * Not offered: octave weighting windows and a caller's fold matrix, thresholds, chroma_stft, harmonic stacks, tuning
+ * estimation. */
+typedef struct {
+  pdmp3_amd_cqt_spec cqt;   /* out_mode: 1 = magnitudes are folded, 2 = powers; cqt.floor is not used */
+  int n_chroma;             /* 1 .. 96, divides cqt.bins_per_octave; r = bins_per_octave / n_chroma */
+  int base_class;           /* 0 .. n_chroma - 1: the class of fmin (0 where fmin is a C) */
+  int chroma_norm;          /* 0 none, 1 L1, 2 L2, 3 max */
+  double norm_floor;        /* > 0, a normal binary32 number; used where chroma_norm != 0 */
+} pdmp3_amd_chroma_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: whatever pdmp3_amd_cqt_check refuses, cqt.out_mode
+ * outside {1, 2}, n_chroma outside 1 .. 96 or not a divisor of bins_per_octave, base_class or chroma_norm out of range, where
+ * chroma_norm != 0 a norm_floor that is not a positive normal binary32 number once rounded, a spec for which the plan below
+ * finds no tile. */
+int pdmp3_amd_chroma_check(const pdmp3_amd_chroma_spec* spec, long sr);
+/* class(k) into cls[k], k < n_bins <= cap, and the bins of each class into count[p], p < n_chroma (either may be NULL).
+ * Returns n_bins; -1 where the check refuses the spec or cls != NULL and cap < n_bins, nothing written. */
+int pdmp3_amd_chroma_map(const pdmp3_amd_chroma_spec* spec, long sr, int* cls, size_t cap, int* count);
+/* What a workgroup of k_clip_chroma takes, the function the call itself uses: pdmp3_amd_cqt_plan's plan -- table, tile rows,
+ * *row_pad, *split_rows, *segments and *n_split are that function's -- with more LDS.  The LDS floats: the tile's span as
+ * there; from *class_at on the eight waves' partial sums, 8 x 2 x 16 x 17; from *q_at = *class_at + 4352 on the plane of the
+ * frame tile's values q, [n_bins rounded up to 16][17].  The folded classes, [n_chroma][17] floats, lie OVER the partial sums,
+ * from *class_at on: they are written behind the workgroup barrier that follows every wave's last read of the sums, and 96 x
+ * 17 <= 4352.  *tile is 16 frames where all of this fits PDMP3_MEL_LDS_MAX, else 8, else 4 -- so it may be smaller than the
+ * constant-Q call's at the same spec; up to 64 KB the launch asks for the LDS dynamically, above that the kernel with a
+ * static array runs.  0, or -1 where the check refuses the spec.  Pointers may be NULL. */
+int pdmp3_amd_chroma_plan(const pdmp3_amd_chroma_spec* spec, long sr, int* tile, int* row_pad, unsigned* lds_bytes, int* split_rows, int* segments,
+                          int* n_split, unsigned* q_at, unsigned* class_at);
+/* Row k receives channel c's [n_chroma][n_frames] floats at dst + c * chan_stride.  Everything else as
+ * pdmp3_amd_bulk_decode_clips_cqt, whose cache of tables this call shares (a chroma call and a constant-Q call of the same
+ * geometry use one table); k_clip_chroma (csrc/chroma.hip) writes the rows.  -1 also where pdmp3_amd_chroma_check says so. */
+int pdmp3_amd_bulk_decode_clips_chroma(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_chroma_spec* spec,
+                                       long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -668,6 +668,24 @@ typedef struct pdmp3_cqt_params {
 int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
                        const pdmp3_cqt_params* params);
 
+/* Chroma features of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_chroma).  k_clip_chroma
+ * (chroma.hip) is k_clip_cqt's tile loop with the values kept in LDS: where that kernel stores bin k of frame fl, this one
+ * writes the same binary32 value to the q plane, [n_tiles x 16][17] floats from LDS float q_at on; after a barrier the classes
+ * are folded into the class plane, [n_chroma][17] floats from class_at on, and after another one normalised and stored as
+ * [n_chroma][n_frames] floats per channel, frames innermost.  The class plane lies over the partial sums (class_at =
+ * cqt.span_floats): the barrier in front of the fold is behind every wave's last read of them.  cqt.out_mode is 1 or 2,
+ * cqt.lds_bytes the whole workgroup's: span, partial sums and q plane. */
+typedef struct pdmp3_chroma_params {
+  pdmp3_cqt_params cqt;
+  int32_t n_chroma, r;                      /* classes; r = bins_per_octave / n_chroma bins of an octave in a class     */
+  int32_t base_class, chroma_norm;          /* the class of bin 0; 0 none, 1 L1, 2 L2, 3 max                            */
+  float norm_floor;                         /* the divisor is max(d, norm_floor)                                        */
+  uint32_t q_at, class_at;                  /* LDS floats in front of the q plane and of the class plane                */
+} pdmp3_chroma_params;
+/* As pdmp3_hip_clip_cqt, with k_clip_chroma / k_clip_chroma_big. */
+int pdmp3_hip_clip_chroma(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                          const pdmp3_chroma_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

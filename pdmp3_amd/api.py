@@ -29,7 +29,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_stft_long_check", "pdmp3_amd_stft_long_tables", "pdmp3_amd_stft_long_plan", "pdmp3_amd_bulk_decode_clips_stft_long",
                 "pdmp3_amd_mel_long_check", "pdmp3_amd_mel_long_filterbank", "pdmp3_amd_mel_long_operand", "pdmp3_amd_mel_long_plan",
                 "pdmp3_amd_bulk_decode_clips_mel_long",
-                "pdmp3_amd_cqt_check", "pdmp3_amd_cqt_lengths", "pdmp3_amd_cqt_table", "pdmp3_amd_cqt_plan", "pdmp3_amd_bulk_decode_clips_cqt"]
+                "pdmp3_amd_cqt_check", "pdmp3_amd_cqt_lengths", "pdmp3_amd_cqt_table", "pdmp3_amd_cqt_plan", "pdmp3_amd_bulk_decode_clips_cqt",
+                "pdmp3_amd_chroma_check", "pdmp3_amd_chroma_map", "pdmp3_amd_chroma_plan", "pdmp3_amd_bulk_decode_clips_chroma"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -188,6 +189,11 @@ def load_library():
         lib.pdmp3_amd_cqt_table.restype = ll
         lib.pdmp3_amd_cqt_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint)] + [C.POINTER(C.c_int)] * 3
         lib.pdmp3_amd_bulk_decode_clips_cqt.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_chroma"):       # (chroma features of clips: absent from older builds)
+        lib.pdmp3_amd_chroma_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_chroma_map.argtypes = [vp, C.c_long, vp, C.c_size_t, vp]
+        lib.pdmp3_amd_chroma_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint)] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_uint)] * 2
+        lib.pdmp3_amd_bulk_decode_clips_chroma.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -700,6 +706,56 @@ def cqt_plan(sample_rate=22050, **kw):
                                          C.byref(ns)) != 0:
         raise ValueError("pdmp3_amd_cqt_plan: bad argument")
     return t.value, p.value, b.value, sr.value, sg.value, ns.value
+
+
+class _ChromaSpec(C.Structure):                    # include/pdmp3_bulk.h pdmp3_amd_chroma_spec
+    _fields_ = [("cqt", _CqtSpec), ("n_chroma", C.c_int), ("base_class", C.c_int), ("chroma_norm", C.c_int), ("norm_floor", C.c_double)]
+
+
+CHROMA_NORMS = {None: 0, "none": 0, "l1": 1, "l2": 2, "max": 3, "inf": 3}
+
+
+def _chroma_spec(n_frames=1, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, n_chroma=12, base_class=0, filter_scale=1.0,
+                 norm=1, scale=1, quantity="magnitude", chroma_norm="max", norm_floor=1e-10, channels=1, width=0, rolloff=0.0):
+    q = STFT_MODES[quantity] if isinstance(quantity, str) else int(quantity)
+    if isinstance(chroma_norm, str) and chroma_norm not in CHROMA_NORMS:
+        raise ValueError("chroma_norm is one of %s" % sorted(k for k in CHROMA_NORMS if k))
+    cn = CHROMA_NORMS[chroma_norm] if isinstance(chroma_norm, str) or chroma_norm is None else int(chroma_norm)
+    cqt = _cqt_spec(n_frames, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, q, 0.0, channels, width, rolloff)
+    return _ChromaSpec(cqt, int(n_chroma), int(base_class), cn, float(norm_floor))
+
+
+def chroma_check(sample_rate=22050, **kw):
+    """pdmp3_amd_chroma_check -> True when pdmp3_amd_bulk_decode_clips_chroma would accept these numbers (decode_clips_chroma's
+    argument names) at sample_rate"""
+    try:
+        spec = _chroma_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError):
+        return False
+    return load_library().pdmp3_amd_chroma_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def chroma_map(sample_rate=22050, **kw):
+    """pdmp3_amd_chroma_map -> (class of every bin int32 [n_bins], bins of every class int32 [n_chroma])"""
+    spec = _chroma_spec(sample_rate=sample_rate, **kw)
+    cls = np.full(max(spec.cqt.n_bins, 1), -1, dtype=np.int32)
+    count = np.full(max(min(spec.n_chroma, 4096), 1), -1, dtype=np.int32)
+    if load_library().pdmp3_amd_chroma_map(C.byref(spec), int(sample_rate), cls.ctypes.data, cls.size, count.ctypes.data) != spec.cqt.n_bins:
+        raise ValueError("pdmp3_amd_chroma_map: bad argument")
+    return cls, count
+
+
+def chroma_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_chroma_plan -> (frames of a workgroup of k_clip_chroma, LDS floats between two hops, LDS bytes of a workgroup,
+    rows from which a tile is split, segments of a split tile, tiles that are split, LDS floats in front of the q plane, LDS
+    floats in front of the class plane)"""
+    spec = _chroma_spec(sample_rate=sample_rate, **kw)
+    t, p, sr, sg, ns = (C.c_int(0) for _ in range(5))
+    b, qa, ca = (C.c_uint(0) for _ in range(3))
+    if load_library().pdmp3_amd_chroma_plan(C.byref(spec), int(sample_rate), C.byref(t), C.byref(p), C.byref(b), C.byref(sr), C.byref(sg),
+                                            C.byref(ns), C.byref(qa), C.byref(ca)) != 0:
+        raise ValueError("pdmp3_amd_chroma_plan: bad argument")
+    return t.value, p.value, b.value, sr.value, sg.value, ns.value, qa.value, ca.value
 
 
 def stft_long_check(sample_rate=44100, n_fft=2048, hop=512, **kw):
@@ -1317,6 +1373,24 @@ class BulkDecoder:
         spec = lambda f: _cqt_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, mode, floor, channels, width, rolloff)
         return self._clips_stft("cqt", clips, n_frames, sample_rate, None, hop, None, None, None, mode, floor, channels, width, rolloff, out,
                                 nb=int(n_bins), spec_of=spec)
+
+    def decode_clips_chroma(self, clips, n_frames, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, n_chroma=12,
+                            base_class=0, filter_scale=1.0, norm=1, scale=1, quantity="magnitude", chroma_norm="max", norm_floor=1e-10, channels=0,
+                            width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_chroma: clips as decode_clips_cqt takes them -> (out, valid): pitch-class profiles
+        [K, C, n_chroma, n_frames] float32.  The constant-Q transform is decode_clips_cqt's at the same arguments, its
+        magnitudes (quantity="magnitude") or powers ("power") bit for bit; bin k goes to class
+        ((k + r // 2) // r + base_class) % n_chroma with r = bins_per_octave // n_chroma (base_class: the class of fmin, 0 where
+        fmin is a C), the bins of a class are added in ascending order, and every frame is divided by
+        max(its norm, norm_floor): chroma_norm "max" (librosa's norm=inf), "l1", "l2" or None.  A silent frame is exactly 0.
+        The definition is this formula at the one rate, not librosa's multirate chroma_cqt.  valid, out, RingReplay /
+        MixedFormat as decode_clips_stft.  Synchronous."""
+        spec = lambda f: _chroma_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, n_chroma, base_class, filter_scale, norm, scale, quantity,
+                                      chroma_norm, norm_floor, channels, width, rolloff)
+        if (STFT_MODES.get(quantity) if isinstance(quantity, str) else quantity) not in (1, 2):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_chroma: quantity is \"magnitude\" or \"power\"")
+        return self._clips_stft("chroma", clips, n_frames, sample_rate, None, hop, None, None, None, quantity, 0.0, channels, width, rolloff, out,
+                                nb=int(n_chroma), spec_of=spec)
 
     def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
                     nb=None, spec_of=None):

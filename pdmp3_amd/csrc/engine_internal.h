@@ -168,6 +168,8 @@ hipError_t pdmp3_launch_clip_mfcc(hipStream_t s, const pdmp3_fbank_desc* descs, 
 hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_stft_params* params);
 // ---- cqt.hip ----
 hipError_t pdmp3_launch_clip_cqt(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_cqt_params* params);
+// ---- chroma.hip ----
+hipError_t pdmp3_launch_clip_chroma(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_chroma_params* params);
 // ---- stft_long.hip ----
 hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                        const pdmp3_stft_long_params* params);

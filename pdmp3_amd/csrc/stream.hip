@@ -693,8 +693,9 @@ extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_m
   return PDMP3_HIP_OK;
 }
 // ---- the constant-Q transform (cqt.hip) ----
-extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
-                                  const pdmp3_cqt_params* params) {
+// k_clip_cqt, or with `chroma` k_clip_chroma, whose LDS holds `extra_floats` more behind the partial sums (chroma.hip)
+static int clip_cqt_run(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                        const pdmp3_cqt_params* params, const pdmp3_chroma_params* chroma, size_t extra_floats) {
   if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !table || !params)
     return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: bad argument", hipSuccess);
   const pdmp3_cqt_params& P = *params;
@@ -713,7 +714,7 @@ extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_me
   {
     const size_t span = (size_t)(P.tile - 1) * P.hop + P.rows0, chunks = (span + P.hop - 1) / P.hop;
     if (P.span_floats < chunks * (size_t)(P.hop + P.row_pad) ||
-        (size_t)P.lds_bytes < ((size_t)P.span_floats + PDMP3_CQT_PART_FLOATS) * sizeof(float))
+        (size_t)P.lds_bytes < ((size_t)P.span_floats + PDMP3_CQT_PART_FLOATS + extra_floats) * sizeof(float))
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: a tile's span and partial sums do not fit the LDS asked for", hipSuccess);
     if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: too many frames", hipSuccess);
@@ -733,12 +734,33 @@ extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_me
   HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D cqt descriptors");
   HIP_TRY(hipMemcpyAsync(a + desc_bytes, table, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D cqt table");
   const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_cqt(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                  reinterpret_cast<const float*>(a + desc_bytes), &P),
-            "launch k_clip_cqt");
+  for (int k = 0; k < n_clips; k += kMaxY) {
+    const pdmp3_mel_desc* dk = reinterpret_cast<const pdmp3_mel_desc*>(a) + k;
+    const int nk = n_clips - k < kMaxY ? n_clips - k : kMaxY;
+    const float* tab = reinterpret_cast<const float*>(a + desc_bytes);
+    if (chroma) HIP_TRY(pdmp3_launch_clip_chroma(t.stream, dk, nk, tab, chroma), "launch k_clip_chroma");
+    else HIP_TRY(pdmp3_launch_clip_cqt(t.stream, dk, nk, tab, &P), "launch k_clip_cqt");
+  }
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
+}
+extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                                  const pdmp3_cqt_params* params) {
+  return clip_cqt_run(hs, slot, descs, n_clips, table, table_rows, params, nullptr, 0);
+}
+// ---- chroma features (chroma.hip): the constant-Q transform's launch with the fold's parameters checked in front of it ----
+extern "C" int pdmp3_hip_clip_chroma(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
+                                     const pdmp3_chroma_params* params) {
+  if (!params) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_chroma: bad argument", hipSuccess);
+  const pdmp3_chroma_params& S = *params;
+  const pdmp3_cqt_params& P = S.cqt;
+  // what the fold's indexing relies on: the planes inside the LDS asked for, the class plane inside the partial sums
+  if (P.n_tiles < 1 || P.n_tiles > PDMP3_CQT_MAX_TILES || (P.out_mode != 1 && P.out_mode != 2) || S.n_chroma < 1 || S.n_chroma > 96 || S.r < 1 ||
+      S.r > 96 || S.base_class < 0 || S.base_class >= S.n_chroma || S.chroma_norm < 0 || S.chroma_norm > 3 ||
+      (S.chroma_norm && !(S.norm_floor > 0.0f)) || S.class_at != P.span_floats || S.q_at != P.span_floats + PDMP3_CQT_PART_FLOATS ||
+      (size_t)S.n_chroma * 17 > PDMP3_CQT_PART_FLOATS)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_chroma: bad parameters", hipSuccess);
+  return clip_cqt_run(hs, slot, descs, n_clips, table, table_rows, &P, &S, (size_t)P.n_tiles * 16 * 17);
 }
 // ---- the short-time Fourier transform at n_fft 2048 and 4096 (stft_long.hip) ----
 extern "C" int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,

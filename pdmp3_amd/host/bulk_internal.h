@@ -369,6 +369,10 @@ HOST_LOCAL const float* stft_table(struct bulk* b, const pdmp3_amd_stft_spec* s)
 HOST_LOCAL int cqt_plan(const pdmp3_amd_cqt_spec* s, long sr, pdmp3_cqt_params* p);
 HOST_LOCAL void cqt_table_fill(const pdmp3_amd_cqt_spec* s, long sr, const pdmp3_cqt_params* p, float* t);
 HOST_LOCAL const float* cqt_table(struct bulk* b, const pdmp3_amd_cqt_spec* s, long sr, const pdmp3_cqt_params* p);
+HOST_LOCAL void cqt_lds(int rows0, int hop, int tile, int row_pad, unsigned* span_floats, unsigned* bytes);
+/* clip_chroma.c: the plan of a workgroup of k_clip_chroma -- cqt_plan's with the q plane behind the partial sums and the tile
+ * chosen for the whole of it (0, or -1 where the check refuses the spec) */
+HOST_LOCAL int chroma_plan(const pdmp3_amd_chroma_spec* s, long sr, pdmp3_chroma_params* p);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

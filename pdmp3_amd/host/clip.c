@@ -1359,9 +1359,10 @@ int pdmp3_amd_bulk_decode_clips_mfcc(struct bulk* b, const pdmp3_amd_audio_clip*
 
 /* ---- the constant-Q transform of clips ---- */
 /* The short-time Fourier transform's course with another plan, table and launch: the rows through the audio call into stage
- * 2, k_clip_cqt behind it, host destinations through stage 1. */
-int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
-                                    long long* valid) {
+ * 2, k_clip_cqt behind it, host destinations through stage 1.  With `chroma` (whose cqt is `spec`) the
+ * plan is chroma_plan's, a frame n_chroma floats and the kernel k_clip_chroma; the table and its cache are the same. */
+static int cqt_clips(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
+                     const pdmp3_amd_chroma_spec* chroma, long long* valid) {
   if (!b || !b->hs || !b->bits_mode || !spec || n_clips < 0 || (n_clips && (!clips || !valid)) || spec->n_frames < 0) return -1;
   const long long F = spec->n_frames;
   int C = spec->channels, rc = 0;
@@ -1385,10 +1386,14 @@ int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* 
   if (!C) C = 1;
   if (!sr) sr = 44100;                               /* (no clip to decode, or only streams without frames) */
   pdmp3_cqt_params P;
-  if (cqt_plan(spec, sr, &P) != 0) return -1;                         /* (the check's verdict and the plan in one) */
+  pdmp3_chroma_params S;
+  if (chroma) {
+    if (chroma_plan(chroma, sr, &S) != 0) return -1;
+    P = S.cqt;
+  } else if (cqt_plan(spec, sr, &P) != 0) return -1;                  /* (the check's verdict and the plan in one) */
   /* a frame reads N = N_0 = 2 h_0 + 1 samples, its centre the sample N / 2 = h_0; the table's rows behind them are zeros */
   const int N = 2 * P.half0 + 1, H = spec->hop;
-  const int per_frame = P.n_bins * (spec->out_mode == 0 ? 2 : 1);     /* floats of a frame */
+  const int per_frame = chroma ? chroma->n_chroma : P.n_bins * (spec->out_mode == 0 ? 2 : 1);     /* floats of a frame */
   if (F > 0x7fffffffLL / (per_frame > H ? per_frame : H) - 2 * N) return -1;                /* (a row's samples and floats stay inside 31 bits) */
   const size_t per = (size_t)per_frame * (size_t)F;                   /* floats of a channel's output */
   for (int k = 0; k < n_clips; k++) if (C == 2 && F && clips[k].chan_stride < per) return -1;
@@ -1447,7 +1452,10 @@ int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* 
   if (out_floats && !out_stage) { rc = -1; goto out; }
   for (int i = 0; i < nd; i++) if (host[i] >= 0) ds[i].dst = (uint64_t)(uintptr_t)(out_stage + ds[i].dst);
   P.n_in = T; P.n_frames = (int32_t)F; P.channels = C; P.floor = spec->out_mode >= 3 ? (float)spec->floor : 0.0f;
-  if (pdmp3_hip_clip_cqt(b->hs, CLIP_SLOT, ds, nd, table, (size_t)P.tile_at[P.n_tiles - 1] + (size_t)P.tile_rows[P.n_tiles - 1], &P) != PDMP3_HIP_OK) {
+  const size_t table_rows = (size_t)P.tile_at[P.n_tiles - 1] + (size_t)P.tile_rows[P.n_tiles - 1];
+  if (chroma) S.cqt = P;
+  if ((chroma ? pdmp3_hip_clip_chroma(b->hs, CLIP_SLOT, ds, nd, table, table_rows, &S)
+              : pdmp3_hip_clip_cqt(b->hs, CLIP_SLOT, ds, nd, table, table_rows, &P)) != PDMP3_HIP_OK) {
     fprintf(stderr, "pdmp3: engine failure: %s\n", pdmp3_hip_last_error());
     rc = -1; goto out;
   }
@@ -1474,4 +1482,15 @@ int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* 
 out:
   free(ac); free(av); free(ds); free(host);
   return rc;
+}
+int pdmp3_amd_bulk_decode_clips_cqt(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_cqt_spec* spec,
+                                    long long* valid) {
+  return cqt_clips(b, clips, n_clips, spec, NULL, valid);
+}
+
+/* ---- chroma features of clips: the constant-Q call's course, the fold inside its kernel ---- */
+int pdmp3_amd_bulk_decode_clips_chroma(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_chroma_spec* spec,
+                                       long long* valid) {
+  if (!spec) return -1;
+  return cqt_clips(b, clips, n_clips, &spec->cqt, spec, valid);
 }

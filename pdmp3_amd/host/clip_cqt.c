@@ -37,7 +37,7 @@ static long long cqt_table_rows(const pdmp3_amd_cqt_spec* s, long sr) {
 }
 
 /* the LDS of a workgroup with `tile` frames: the tile's span in chunks of hop + row_pad floats, then the partial sums */
-static void cqt_lds(int rows0, int hop, int tile, int row_pad, unsigned* span_floats, unsigned* bytes) {
+HOST_LOCAL void cqt_lds(int rows0, int hop, int tile, int row_pad, unsigned* span_floats, unsigned* bytes) {
   const unsigned span = (unsigned)(tile - 1) * (unsigned)hop + (unsigned)rows0;
   const unsigned a = (((span + (unsigned)hop - 1u) / (unsigned)hop) * (unsigned)(hop + row_pad) + 3u) & ~3u;
   *span_floats = a;

@@ -18,6 +18,7 @@
  *   clip.c          stream indices, the halo rule of a frame range, clips (pdmp3_amd_index_*, pdmp3_amd_bulk_decode_clips)
  *   clip_audio.c    clips as float batches: the input span of a clip, the filter table of a pair of sampling frequencies
  *   clip_cqt.c      the constant-Q transform of clips: the check, the bins' lengths, the ragged table, the kernel's plan
+ *   clip_chroma.c   chroma features of clips: the check, the class of every bin, the kernel's plan on top of clip_cqt.c's
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

@@ -689,6 +689,92 @@ def clips_cqt(args, api):
     print(json.dumps(res))
 
 
+def clips_chroma(args, api):
+    """--chroma: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as 12 pitch classes x 1292 frames (the
+    default spec: C1, 84 bins, 12 an octave, hop 512, magnitudes, max norm) in device memory, three ways, run after run in turn:
+    (a) pdmp3_amd_bulk_decode_clips_audio for the same spans; (b) pdmp3_amd_bulk_decode_clips_cqt's magnitudes [K, 1, 84, F]
+    folded over the seven octaves and divided by the frame's maximum in torch; (c) pdmp3_amd_bulk_decode_clips_chroma.  (c) is
+    compared once with (b) (largest difference, printed, not asserted: torch adds the octaves in its own order, and the tests
+    check (c) against the definition and against the sequential fold).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, hop, n_bins, n_chroma, floor = args.clips, args.clip_frames, 22050, 512, 84, 12, 1e-10
+    h0 = int(api.cqt_lengths(rate)[1][0])
+    n0 = 2 * h0 + 1
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = 1292 if F == 1149 else (F * 1152 * rate // 44100) // hop + 1
+    T = (Fm - 1) * hop + n0
+    dev = "cuda:0"
+    cq, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), h0)               # (no leading zeros: (a)'s rows start at start - h_0)
+        cq.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - h0))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_q = torch.zeros((K, 1, n_bins, Fm), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, n_chroma, Fm), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, n_chroma, Fm), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def cqt_route():
+        dec.decode_clips_cqt(cq, Fm, rate, hop, out=out_q)
+        c = out_q.view(K, 1, n_bins // n_chroma, n_chroma, Fm).sum(dim=2)
+        torch.div(c, c.amax(dim=2, keepdim=True).clamp_min(floor), out=out_b)
+        torch.cuda.synchronize()
+
+    def chroma_route():
+        dec.decode_clips_chroma(cq, Fm, rate, hop, channels=1, norm_floor=floor, out=out_c)
+
+    routes = [("audio clips", audio_route), ("cqt clips + fold + max norm in torch", cqt_route), ("chroma clips", chroma_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = {"torch_route": float((out_b - out_c).abs().max()), "largest_value": float(out_c.abs().max()),
+                    "frames_at_one": int((out_c.amax(dim=2) == 1.0).sum()), "frames": K * Fm}
+    dec.close()
+    plan = api.chroma_plan(rate, hop=hop)
+    res = {"workload": "%d clips of %d frames' length as %d pitch classes x %d frames at %d Hz mono (C1, %d bins, 12 an octave, hop %d): %s" % (
+               K, F, n_chroma, Fm, rate, n_bins, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "plan": {"tile": plan[0], "lds_bytes": plan[2], "split_tiles": plan[5]},
+           "result_bytes": K * n_chroma * Fm * 4, "cqt_bytes": K * n_bins * Fm * 4, "largest_difference_from_chroma": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["chroma_minus_audio_ms"] = round((med["chroma clips"] - med["audio clips"]) * 1e3, 3)
+    res["cqt_route_minus_audio_ms"] = round((med["cqt clips + fold + max norm in torch"] - med["audio clips"]) * 1e3, 3)
+    res["chroma_minus_cqt_route_ms"] = round((med["chroma clips"] - med["cqt clips + fold + max norm in torch"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -915,6 +1001,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as 84 x 1292 constant-Q magnitudes at 22 050 Hz mono, C1, 12 bins an "
                          "octave, hop 512 (pdmp3_amd_bulk_decode_clips_cqt) against the audio call alone and the audio call followed by a "
                          "dense torch matmul over unfolded frames (see clips_cqt())")
+    ap.add_argument("--chroma", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as 12 x 1292 chroma features at 22 050 Hz mono, the default spec "
+                         "(pdmp3_amd_bulk_decode_clips_chroma) against the audio call alone and the constant-Q call followed by the fold and "
+                         "the max norm in torch (see clips_chroma())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -922,7 +1012,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -930,6 +1020,8 @@ def main():
         from pdmp3_amd import api
         if args.cqt:
             return clips_cqt(args, api)
+        if args.chroma:
+            return clips_chroma(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
