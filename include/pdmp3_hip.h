@@ -532,7 +532,7 @@ typedef struct pdmp3_fbank_desc {
   uint64_t src, dst;                        /* device addresses: channel 0's first sample, channel 0's first output float */
   uint64_t src_chan_stride, dst_chan_stride; /* floats between the channels                                              */
   uint32_t valid, pad_;
-} pdmp3_fbank_desc;                         /* 40 bytes */
+} pdmp3_fbank_desc;                         /* 40 bytes: pdmp3_mel_desc's layout, `valid` where that has `lead` (the host fills one array) */
 typedef struct pdmp3_fbank_params {
   int64_t n_in;                             /* samples of a row                                                         */
   int32_t win, rows;                        /* Nw; Nw rounded up to 4: the folded table's rows                          */

@@ -932,6 +932,28 @@ class _AudioSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_
     _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("n_samples", C.c_longlong), ("width", C.c_int), ("rolloff", C.c_double)]
 
 
+def _clip_destination(out, k, c, inner, complex_ok=False):
+    """Where the rows of a clip call go: `out` -- a torch tensor or a numpy array -- seen as float32 [>= k, c] + inner (complex64
+    where complex_ok: as [..., 2], inner's last dimension) -> (address of row 0, bytes between rows, floats between channels).
+    Rows and channels may be strided, a channel's floats not; AssertionError for anything else."""
+    if hasattr(out, "data_ptr"):
+        import torch
+        v = torch.view_as_real(out) if out.is_complex() else out
+        assert v.dtype == torch.float32 and (complex_ok or not out.is_complex())
+        shape, strides, base = tuple(v.shape), tuple(v.stride()), v.data_ptr()
+    else:
+        v = out.view(np.float32).reshape(out.shape + (2,)) if out.dtype == np.complex64 else out
+        assert v.dtype == np.float32 and (complex_ok or out.dtype != np.complex64) and all(s % 4 == 0 for s in v.strides)
+        shape, strides, base = v.shape, tuple(s // 4 for s in v.strides), v.ctypes.data
+    inner = tuple(inner)
+    assert len(shape) == 2 + len(inner) and shape[1:] == (c,) + inner and shape[0] >= k
+    want = 1
+    for n, s in zip(reversed(inner), reversed(strides[2:])):                       # (a row's floats are dense)
+        assert n <= 1 or s == want or 0 in shape               # (an array without elements has strides of no meaning)
+        want *= n
+    return base, strides[0] * 4, strides[1]
+
+
 class BulkDecoder:
     """include/pdmp3_bulk.h: whole-stream decode, host Huffman on a thread pool + pipelined GPU batches.
     parse_only=True: host stages only (records out), for machines without a GPU."""
@@ -1096,43 +1118,8 @@ class BulkDecoder:
         strided, the samples not) or a numpy array.  Synchronous.  RingReplay / MixedFormat (with .out and .valid: those
         clips' rows are not written, valid is PDMP3_BULK_REPLAY / PDMP3_BULK_MIXED_FORMAT there) when a clip's stream has no
         finite output / no one format; the other clips are decoded all the same."""
-        k, t = len(clips), int(n_samples)
-        c = int(channels)
-        if not c:
-            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
-            if len(cs) > 1:
-                raise ValueError("decode_clips_audio: channels=0 and the clips' channel counts differ")
-            c = cs.pop() if cs else 1
-        if out is None:
-            import torch
-            out = torch.zeros((k, c, t), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
-            torch.cuda.synchronize()
-        if hasattr(out, "data_ptr"):
-            assert out.dim() == 3 and tuple(out.shape[1:]) == (c, t) and out.shape[0] >= k and out.element_size() == 4 and (t <= 1 or out.stride(2) == 1)
-            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
-        else:
-            assert out.ndim == 3 and out.shape[1:] == (c, t) and out.shape[0] >= k and out.dtype == np.float32 and (t <= 1 or out.strides[2] == 4)
-            assert out.strides[1] % 4 == 0
-            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
-        arr = (_AudioClip * max(k, 1))()
-        keep = []
-        for i, (mp3, ix, start) in enumerate(clips):
-            a = _as_u8(mp3)
-            keep.append(a)
-            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
-        spec = _AudioSpec(int(sample_rate), int(channels), t, int(width), float(rolloff))
-        got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_audio(self.h, arr, k, C.byref(spec), got)
-        valid = np.array(got[:k], dtype=np.int64)
-        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
-            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
-                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
-            e.valid, e.out = valid, out
-            raise e
-        if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_audio failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
-        return out, valid
+        t = int(n_samples)
+        return self._clips_call("audio", clips, (t,), lambda: (_AudioSpec(int(sample_rate), int(channels), t, int(width), float(rolloff)), None), channels, out)
 
     def decode_clips_mel(self, clips, n_frames, sample_rate=16000, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=0.0, scale="slaney",
                          norm="slaney", mode="log10", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
@@ -1143,45 +1130,9 @@ class BulkDecoder:
         valid[k] = frames of row k whose centre lies inside the stream.  out: a float32 torch tensor on the decoder's device (made
         when not given; rows and channels may be strided) or a numpy array.  Synchronous.  RingReplay / MixedFormat (with .out
         and .valid) as decode_clips_audio."""
-        k, f, nm = len(clips), int(n_frames), int(n_mels)
-        c = int(channels)
-        if not c:
-            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
-            if len(cs) > 1:
-                raise ValueError("decode_clips_mel: channels=0 and the clips' channel counts differ")
-            c = cs.pop() if cs else 1
-        if out is None:
-            import torch
-            out = torch.zeros((k, c, nm, f), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
-            torch.cuda.synchronize()
-        if hasattr(out, "data_ptr"):
-            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, nm, f) and out.shape[0] >= k and out.element_size() == 4
-            assert nm * f <= 1 or ((f <= 1 or out.stride(3) == 1) and (nm <= 1 or out.stride(2) == f))
-            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
-        else:
-            assert out.ndim == 4 and out.shape[1:] == (c, nm, f) and out.shape[0] >= k and out.dtype == np.float32
-            assert nm * f <= 1 or ((f <= 1 or out.strides[3] == 4) and (nm <= 1 or out.strides[2] == 4 * f))
-            assert out.strides[1] % 4 == 0
-            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
-        arr = (_AudioClip * max(k, 1))()
-        keep = []
-        for i, (mp3, ix, start) in enumerate(clips):
-            a = _as_u8(mp3)
-            keep.append(a)
-            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
-        spec = _mel_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff)
-        got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_mel(self.h, arr, k, C.byref(spec), got)
-        valid = np.array(got[:k], dtype=np.int64)
-        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
-            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
-                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
-            e.valid, e.out = valid, out
-            raise e
-        if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
-        return out, valid
+        f, nm = int(n_frames), int(n_mels)
+        spec = lambda: (_mel_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff), None)
+        return self._clips_call("mel", clips, (nm, f), spec, channels, out)
 
     def decode_clips_mel_long(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=0.0, scale="slaney",
                               norm="slaney", mode="log10", floor=1e-10, win_length=None, window=None, channels=1, width=0, rolloff=0.0, out=None):
@@ -1189,45 +1140,9 @@ class BulkDecoder:
         exceptions -- at n_fft 2048 or 4096, with decode_clips_stft_long's win_length / window (periodic Hann of win_length when
         no window is given); mode "power" / "log" / "log10" ("whisper" is refused).  The transform, the powers and the
         filterbank run in one kernel, k_clip_mel_long: no spectrum is written."""
-        k, f, nm = len(clips), int(n_frames), int(n_mels)
-        c = int(channels)
-        if not c:
-            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
-            if len(cs) > 1:
-                raise ValueError("decode_clips_mel_long: channels=0 and the clips' channel counts differ")
-            c = cs.pop() if cs else 1
-        if out is None:
-            import torch
-            out = torch.zeros((k, c, nm, f), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
-            torch.cuda.synchronize()
-        if hasattr(out, "data_ptr"):
-            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, nm, f) and out.shape[0] >= k and out.element_size() == 4
-            assert nm * f <= 1 or ((f <= 1 or out.stride(3) == 1) and (nm <= 1 or out.stride(2) == f))
-            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
-        else:
-            assert out.ndim == 4 and out.shape[1:] == (c, nm, f) and out.shape[0] >= k and out.dtype == np.float32
-            assert nm * f <= 1 or ((f <= 1 or out.strides[3] == 4) and (nm <= 1 or out.strides[2] == 4 * f))
-            assert out.strides[1] % 4 == 0
-            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
-        arr = (_AudioClip * max(k, 1))()
-        keep = []
-        for i, (mp3, ix, start) in enumerate(clips):
-            a = _as_u8(mp3)
-            keep.append(a)
-            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
-        spec, keep_window = _mel_long_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, win_length, window, channels, width, rolloff)
-        got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_mel_long(self.h, arr, k, C.byref(spec), got)
-        valid = np.array(got[:k], dtype=np.int64)
-        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
-            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
-                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
-            e.valid, e.out = valid, out
-            raise e
-        if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mel_long failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
-        return out, valid
+        f, nm = int(n_frames), int(n_mels)
+        spec = lambda: _mel_long_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, win_length, window, channels, width, rolloff)
+        return self._clips_call("mel_long", clips, (nm, f), spec, channels, out)
 
     def decode_clips_fbank(self, clips, n_frames, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None,
                            hop=None, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",
@@ -1241,47 +1156,11 @@ class BulkDecoder:
         averages over them).  dither, use_power=False, raw_energy=False, snip_edges=False and vtln_warp are refused.  out: a
         float32 torch tensor on the decoder's device (made when not given; rows and channels may be strided) or a numpy array.
         Synchronous.  RingReplay / MixedFormat (with .out and .valid) as decode_clips_audio."""
-        k, f, d = len(clips), int(n_frames), int(num_mel_bins) + int(bool(use_energy))
-        c = int(channels)
-        if not c:
-            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
-            if len(cs) > 1:
-                raise ValueError("decode_clips_fbank: channels=0 and the clips' channel counts differ")
-            c = cs.pop() if cs else 1
-        if out is None:
-            import torch
-            out = torch.zeros((k, c, f, d), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
-            torch.cuda.synchronize()
-        if hasattr(out, "data_ptr"):
-            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, f, d) and out.shape[0] >= k and out.element_size() == 4
-            assert f * d <= 1 or ((d <= 1 or out.stride(3) == 1) and (f <= 1 or out.stride(2) == d))
-            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
-        else:
-            assert out.ndim == 4 and out.shape[1:] == (c, f, d) and out.shape[0] >= k and out.dtype == np.float32
-            assert f * d <= 1 or ((d <= 1 or out.strides[3] == 4) and (f <= 1 or out.strides[2] == 4 * d))
-            assert out.strides[1] % 4 == 0
-            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
-        arr = (_AudioClip * max(k, 1))()
-        keep = []
-        for i, (mp3, ix, start) in enumerate(clips):
-            a = _as_u8(mp3)
-            keep.append(a)
-            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
-        spec = _fbank_spec(f, sample_rate, frame_length, frame_shift, num_mel_bins, win_length, hop, round_to_power_of_two, remove_dc_offset,
-                           preemphasis_coefficient, window_type, blackman_coeff, low_freq, high_freq, use_log_fbank, use_energy, htk_compat,
-                           energy_floor, subtract_mean, scale, channels, width, rolloff, **not_offered)
-        got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_fbank(self.h, arr, k, C.byref(spec), got)
-        valid = np.array(got[:k], dtype=np.int64)
-        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
-            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
-                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
-            e.valid, e.out = valid, out
-            raise e
-        if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_fbank failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
-        return out, valid
+        f, d = int(n_frames), int(num_mel_bins) + int(bool(use_energy))
+        spec = lambda: (_fbank_spec(f, sample_rate, frame_length, frame_shift, num_mel_bins, win_length, hop, round_to_power_of_two, remove_dc_offset,
+                                   preemphasis_coefficient, window_type, blackman_coeff, low_freq, high_freq, use_log_fbank, use_energy, htk_compat,
+                                   energy_floor, subtract_mean, scale, channels, width, rolloff, **not_offered), None)
+        return self._clips_call("fbank", clips, (f, d), spec, channels, out)
 
     def decode_clips_mfcc(self, clips, n_frames, sample_rate=16000, num_ceps=13, cepstral_lifter=22.0, num_mel_bins=23, frame_length=25.0,
                           frame_shift=10.0, win_length=None, hop=None, round_to_power_of_two=True, remove_dc_offset=True,
@@ -1293,50 +1172,14 @@ class BulkDecoder:
         scale * the stream resampled as decode_clips_audio does: the cepstra of decode_clips_fbank's log filterbank, liftered, with
         C0 or (use_energy) the log energy in its place, in front or (htk_compat) behind the others.  Everything else --
         framing, valid, what is refused, `out`, RingReplay / MixedFormat -- as decode_clips_fbank.  Synchronous."""
-        k, f, d = len(clips), int(n_frames), int(num_ceps)
-        c = int(channels)
-        if not c:
-            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
-            if len(cs) > 1:
-                raise ValueError("decode_clips_mfcc: channels=0 and the clips' channel counts differ")
-            c = cs.pop() if cs else 1
-        if out is None:
-            import torch
-            out = torch.zeros((k, c, f, max(d, 0)), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
-            torch.cuda.synchronize()
-        if hasattr(out, "data_ptr"):
-            assert out.dim() == 4 and tuple(out.shape[1:]) == (c, f, d) and out.shape[0] >= k and out.element_size() == 4
-            assert f * d <= 1 or ((d <= 1 or out.stride(3) == 1) and (f <= 1 or out.stride(2) == d))
-            base, s0, s1 = out.data_ptr(), out.stride(0) * 4, out.stride(1)
-        else:
-            assert out.ndim == 4 and out.shape[1:] == (c, f, d) and out.shape[0] >= k and out.dtype == np.float32
-            assert f * d <= 1 or ((d <= 1 or out.strides[3] == 4) and (f <= 1 or out.strides[2] == 4 * d))
-            assert out.strides[1] % 4 == 0
-            base, s0, s1 = out.ctypes.data, out.strides[0], out.strides[1] // 4
-        arr = (_AudioClip * max(k, 1))()
-        keep = []
-        for i, (mp3, ix, start) in enumerate(clips):
-            a = _as_u8(mp3)
-            keep.append(a)
-            arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
-        spec = _mfcc_spec(num_ceps, cepstral_lifter, n_frames=f, sample_rate=sample_rate, frame_length=frame_length, frame_shift=frame_shift,
-                          num_mel_bins=num_mel_bins, win_length=win_length, hop=hop, round_to_power_of_two=round_to_power_of_two,
-                          remove_dc_offset=remove_dc_offset, preemphasis_coefficient=preemphasis_coefficient, window_type=window_type,
-                          blackman_coeff=blackman_coeff, low_freq=low_freq, high_freq=high_freq, use_energy=use_energy, htk_compat=htk_compat,
-                          energy_floor=energy_floor, subtract_mean=subtract_mean, scale=scale, channels=channels, width=width, rolloff=rolloff,
-                          **not_offered)
-        got = (C.c_longlong * max(k, 1))()
-        rc = self.lib.pdmp3_amd_bulk_decode_clips_mfcc(self.h, arr, k, C.byref(spec), got)
-        valid = np.array(got[:k], dtype=np.int64)
-        if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
-            e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else
-                 MixedFormat("a clip's stream changes its sampling frequency or samples per frame (no time line in samples)"))
-            e.valid, e.out = valid, out
-            raise e
-        if rc != 0:
-            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mfcc failed (a bad argument, a decoder without device Huffman, switches "
-                               "that differ from an index's, or an engine failure)")
-        return out, valid
+        f, d = int(n_frames), int(num_ceps)
+        spec = lambda: (_mfcc_spec(num_ceps, cepstral_lifter, n_frames=f, sample_rate=sample_rate, frame_length=frame_length, frame_shift=frame_shift,
+                                  num_mel_bins=num_mel_bins, win_length=win_length, hop=hop, round_to_power_of_two=round_to_power_of_two,
+                                  remove_dc_offset=remove_dc_offset, preemphasis_coefficient=preemphasis_coefficient, window_type=window_type,
+                                  blackman_coeff=blackman_coeff, low_freq=low_freq, high_freq=high_freq, use_energy=use_energy,
+                                  htk_compat=htk_compat, energy_floor=energy_floor, subtract_mean=subtract_mean, scale=scale, channels=channels,
+                                  width=width, rolloff=rolloff, **not_offered), None)
+        return self._clips_call("mfcc", clips, (f, d), spec, channels, out, made=(f, max(d, 0)))
 
     def decode_clips_stft(self, clips, n_frames, sample_rate=16000, n_fft=400, hop=160, win_length=None, window=None, normalized=False,
                           mode="complex", floor=1e-10, channels=1, width=0, rolloff=0.0, out=None):
@@ -1370,7 +1213,7 @@ class BulkDecoder:
         norm) and scaled by scale (0 none, 1 sqrt(length), 2 length): norm=1, scale=1 is the convention of librosa's
         cqt(norm=1, scale=True), computed in full at the one rate -- not librosa's multirate approximation.  mode, floor, valid,
         out, RingReplay / MixedFormat as decode_clips_stft.  Synchronous."""
-        spec = lambda f: _cqt_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, mode, floor, channels, width, rolloff)
+        spec = lambda f: (_cqt_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, mode, floor, channels, width, rolloff), None)
         return self._clips_stft("cqt", clips, n_frames, sample_rate, None, hop, None, None, None, mode, floor, channels, width, rolloff, out,
                                 nb=int(n_bins), spec_of=spec)
 
@@ -1385,8 +1228,8 @@ class BulkDecoder:
         max(its norm, norm_floor): chroma_norm "max" (librosa's norm=inf), "l1", "l2" or None.  A silent frame is exactly 0.
         The definition is this formula at the one rate, not librosa's multirate chroma_cqt.  valid, out, RingReplay /
         MixedFormat as decode_clips_stft.  Synchronous."""
-        spec = lambda f: _chroma_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, n_chroma, base_class, filter_scale, norm, scale, quantity,
-                                      chroma_norm, norm_floor, channels, width, rolloff)
+        spec = lambda f: (_chroma_spec(f, sample_rate, hop, fmin, n_bins, bins_per_octave, n_chroma, base_class, filter_scale, norm, scale, quantity,
+                                      chroma_norm, norm_floor, channels, width, rolloff), None)
         if (STFT_MODES.get(quantity) if isinstance(quantity, str) else quantity) not in (1, 2):
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_chroma: quantity is \"magnitude\" or \"power\"")
         return self._clips_stft("chroma", clips, n_frames, sample_rate, None, hop, None, None, None, quantity, 0.0, channels, width, rolloff, out,
@@ -1394,9 +1237,23 @@ class BulkDecoder:
 
     def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
                     nb=None, spec_of=None):
-        k, f = len(clips), int(n_frames)
+        """the transform calls: `nb` bins (n_fft // 2 + 1) of n_frames frames, mode "complex" as complex64 or float32 [..., 2]; what
+        the spec's making refuses is a RuntimeError like the library's own refusals"""
+        f = int(n_frames)
         nb = int(n_fft) // 2 + 1 if nb is None else nb
         m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
+        if spec_of is not None:
+            spec = lambda: spec_of(f)
+        else:
+            spec = lambda: _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
+        return self._clips_call(call, clips, (nb, f, 2) if m == 0 else (nb, f), spec, channels, out, complex_ok=m == 0, refused=(ValueError, OverflowError))
+
+    def _clips_call(self, call, clips, inner, spec_of, channels, out, made=None, complex_ok=False, refused=()):
+        """What every decode_clips_<call> does around its spec: the channel count, `out` made when not given (float32
+        [K, C] + `made`, which is `inner` unless given; complex_ok: complex64 without inner's last 2), the destination checked
+        (_clip_destination), the clips' array, the library's call and its refusals as exceptions.  spec_of() -> (the call's spec,
+        what has to stay alive beside it or None); an exception of the types `refused` from it becomes a RuntimeError."""
+        k = len(clips)
         c = int(channels)
         if not c:
             cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
@@ -1405,37 +1262,19 @@ class BulkDecoder:
             c = cs.pop() if cs else 1
         if out is None:
             import torch
-            out = torch.zeros((k, c, nb, f), dtype=torch.complex64 if m == 0 else torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
+            shape = (k, c) + tuple(inner[:-1] if complex_ok else inner if made is None else made)
+            out = torch.zeros(shape, dtype=torch.complex64 if complex_ok else torch.float32, device=torch.device("cuda", torch.cuda.current_device()))
             torch.cuda.synchronize()
-        # the destination as float32 [K, C, bins, F] (mode "complex": [K, C, bins, F, 2]): a view of the caller's memory
-        if hasattr(out, "data_ptr"):
-            import torch
-            v = torch.view_as_real(out) if out.is_complex() else out
-            assert v.dtype == torch.float32
-            shape, strides, base = tuple(v.shape), tuple(v.stride()), v.data_ptr()
-        else:
-            v = out.view(np.float32).reshape(out.shape + (2,)) if out.dtype == np.complex64 else out
-            assert v.dtype == np.float32 and all(s % 4 == 0 for s in v.strides)
-            shape, strides, base = v.shape, tuple(s // 4 for s in v.strides), v.ctypes.data
-        inner = (nb, f, 2) if m == 0 else (nb, f)
-        assert len(shape) == 2 + len(inner) and shape[1:] == (c,) + inner and shape[0] >= k
-        want = 1
-        for n, s in zip(reversed(inner), reversed(strides[2:])):                       # (a row's floats are dense)
-            assert n <= 1 or s == want or nb * f == 0
-            want *= n
-        s0, s1 = strides[0] * 4, strides[1]
+        base, s0, s1 = _clip_destination(out, k, c, inner, complex_ok)
         arr = (_AudioClip * max(k, 1))()
-        keep = []
+        keep = []                                      # (the arrays arr points into; never read: they live until the call is over)
         for i, (mp3, ix, start) in enumerate(clips):
             a = _as_u8(mp3)
             keep.append(a)
             arr[i] = _AudioClip(a.ctypes.data, len(mp3), ix.h, int(start), base + i * s0, max(int(s1), 0))
         try:
-            if spec_of is not None:
-                spec = spec_of(f)
-            else:
-                spec, wkeep = _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
-        except (ValueError, OverflowError) as e:
+            spec, keep_spec = spec_of()                # (keep_spec: memory the spec points into; it lives until the call is over)
+        except refused as e:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s: %s" % (call, e))
         got = (C.c_longlong * max(k, 1))()
         rc = getattr(self.lib, "pdmp3_amd_bulk_decode_clips_" + call)(self.h, arr, k, C.byref(spec), got)

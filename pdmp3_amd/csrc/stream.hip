@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -48,9 +49,8 @@ struct pdmp3_hip_stream {
   int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
   int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
   void* d_audio[3]; size_t audio_cap[3];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call
-  uint8_t* d_audio_args; size_t audio_args_cap;   // ... and a launch's descriptors | frame table | filter tables
-  uint8_t* d_mel_args; size_t mel_args_cap;       // log-mel features: a launch's descriptors | row maxima | DFT table | filterbank; the STFT call: descriptors | folded table
-  uint8_t* d_fbank_args; size_t fbank_args_cap;   // Kaldi-style features (fbank, mfcc): a launch's descriptors | tables | column sums
+  void* d_audio_args; size_t audio_args_cap;      // ... and a launch's descriptors | frame table | filter tables
+  void* d_clip_args; size_t clip_args_cap;        // the feature calls: a launch's descriptors | parts (clip_run)
 };
 
 extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
@@ -68,8 +68,7 @@ extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
   }
   (void)hipFree(hs->d_sfstate);
   (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio[2]); (void)hipFree(hs->d_audio_args);
-  (void)hipFree(hs->d_mel_args);
-  (void)hipFree(hs->d_fbank_args);
+  (void)hipFree(hs->d_clip_args);
   if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
   (void)hipFree(hs->d_state);
   chain_release(hs->ctx, hs);
@@ -586,11 +585,9 @@ extern "C" int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_
   const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_audio_desc) + 255) & ~(size_t)255;
   const size_t frame_bytes = (n_frames * sizeof(uint32_t) + 255) & ~(size_t)255;
   const size_t table_bytes = n_coef * sizeof(float);
-  { void* p = hs->d_audio_args;
-    const int rc = grow_device(&p, &hs->audio_args_cap, desc_bytes + frame_bytes + table_bytes + 16, "hipMalloc audio tables");
-    hs->d_audio_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_audio_args;
+  if (const int rc = grow_device(&hs->d_audio_args, &hs->audio_args_cap, desc_bytes + frame_bytes + table_bytes + 16, "hipMalloc audio tables"); rc != PDMP3_HIP_OK)
+    return rc;
+  uint8_t* a = static_cast<uint8_t*>(hs->d_audio_args);
   HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_audio_desc), hipMemcpyHostToDevice, t.stream), "H2D audio descriptors");
   if (n_frames) HIP_TRY(hipMemcpyAsync(a + desc_bytes, frames, n_frames * sizeof(uint32_t), hipMemcpyHostToDevice, t.stream), "H2D audio frame table");
   if (n_coef) HIP_TRY(hipMemcpyAsync(a + desc_bytes + frame_bytes, tables, table_bytes, hipMemcpyHostToDevice, t.stream), "H2D filter tables");
@@ -603,6 +600,54 @@ extern "C" int pdmp3_hip_clip_audio(pdmp3_hip_stream* hs, int slot, const pdmp3_
   HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
   return PDMP3_HIP_OK;
 }
+
+// ---- the launches of the feature kernels ----
+// A launch's device block is "descriptors | parts", each 256-byte aligned: a part is uploaded from host memory, zero-filled, or
+// scratch that the kernels write before they read it.  One block serves every feature call: they block until their rows are
+// written, so no two overlap in time.
+struct ClipPart {
+  enum Kind { kUpload, kZero, kScratch } kind;
+  const void* src;           // kUpload: the host bytes
+  size_t bytes;
+};
+// What every pdmp3_hip_clip_<feature> does once its arguments and parameters are accepted: the refusal of a busy slot, the
+// empty call's return, the block, the uploads, and a grid per 32768 clips.  launch(dk, nk, k, part): clips [k, k + nk) of the
+// launch, whose descriptors lie at dk on the device; part[i]: the device address of parts[i] (of the whole part: what a part
+// holds per clip is the callable's to offset by k).
+template <class Desc, size_t N, class Launch>
+static int clip_run(pdmp3_hip_stream* hs, int slot, const char* name, const Desc* descs, int n_clips, long long n_frames,
+                    const ClipPart (&parts)[N], Launch launch) {
+  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc or pdmp3_fbank_desc");
+  char what[160];
+  const auto at = [&](const char* step) -> const char* { snprintf(what, sizeof what, "%s: %s", name, step); return what; };
+  StreamSlot& t = hs->s[slot];
+  if (t.busy) return fail(PDMP3_HIP_EINVAL, at("slot still in flight (wait for it first)"), hipSuccess);
+  if (!n_clips || !n_frames) return PDMP3_HIP_OK;
+  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
+  const auto room = [](size_t bytes) { return (bytes + 255) & ~(size_t)255; };
+  const size_t desc_bytes = (size_t)n_clips * sizeof(Desc);
+  size_t total = room(desc_bytes);
+  for (const ClipPart& p : parts) total += room(p.bytes);
+  if (const int rc = grow_device(&hs->d_clip_args, &hs->clip_args_cap, total + 16, at("hipMalloc tables")); rc != PDMP3_HIP_OK) return rc;
+  uint8_t* const a = static_cast<uint8_t*>(hs->d_clip_args);
+  uint8_t* part[N] = {};
+  HIP_TRY(hipMemcpyAsync(a, descs, desc_bytes, hipMemcpyHostToDevice, t.stream), at("H2D descriptors"));
+  size_t off = room(desc_bytes);
+  int i = 0;
+  for (const ClipPart& p : parts) {
+    part[i++] = a + off;
+    if (p.bytes && p.kind == ClipPart::kUpload) HIP_TRY(hipMemcpyAsync(a + off, p.src, p.bytes, hipMemcpyHostToDevice, t.stream), at("H2D tables"));
+    if (p.bytes && p.kind == ClipPart::kZero) HIP_TRY(hipMemsetAsync(a + off, 0, p.bytes, t.stream), at("memset"));
+    off += room(p.bytes);
+  }
+  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
+  for (int k = 0; k < n_clips; k += kMaxY)
+    HIP_TRY(launch(reinterpret_cast<const Desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY, k, part), at("launch"));
+  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
+  return PDMP3_HIP_OK;
+}
+static const float* as_floats(const uint8_t* p) { return reinterpret_cast<const float*>(p); }
+
 // ---- log-mel features (mel.hip) ----
 extern "C" int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dft, const float* fbt,
                                   const pdmp3_mel_params* params) {
@@ -623,32 +668,14 @@ extern "C" int pdmp3_hip_clip_mel(pdmp3_hip_stream* hs, int slot, const pdmp3_me
     if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: too many frames", hipSuccess);
   }
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | row maxima | DFT table | filterbank: one block, each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
-  const size_t max_bytes = ((size_t)n_clips * sizeof(unsigned) + 255) & ~(size_t)255;
-  const size_t dft_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
-  const size_t fb_bytes = (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float);
-  { void* p = hs->d_mel_args;
-    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + max_bytes + dft_bytes + fb_bytes + 16, "hipMalloc mel tables");
-    hs->d_mel_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_mel_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D mel descriptors");
-  HIP_TRY(hipMemsetAsync(a + desc_bytes, 0, max_bytes, t.stream), "memset mel maxima");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + max_bytes, dft, dft_bytes, hipMemcpyHostToDevice, t.stream), "H2D DFT table");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + max_bytes + dft_bytes, fbt, fb_bytes, hipMemcpyHostToDevice, t.stream), "H2D filterbank");
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_mel(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                  reinterpret_cast<const float*>(a + desc_bytes + max_bytes), reinterpret_cast<const float*>(a + desc_bytes + max_bytes + dft_bytes),
-                                  reinterpret_cast<unsigned*>(a + desc_bytes) + k, &P),
-            "launch k_clip_mel");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  // descriptors | row maxima | DFT table | filterbank
+  return clip_run(hs, slot, "pdmp3_hip_clip_mel", descs, n_clips, P.n_frames,
+                  {{ClipPart::kZero, nullptr, (size_t)n_clips * sizeof(unsigned)},
+                   {ClipPart::kUpload, dft, (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float)},
+                   {ClipPart::kUpload, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int k, uint8_t* const* part) {
+                    return pdmp3_launch_clip_mel(hs->s[slot].stream, dk, nk, as_floats(part[1]), as_floats(part[2]), reinterpret_cast<unsigned*>(part[0]) + k, &P);
+                  });
 }
 // ---- the short-time Fourier transform (stft.hip) ----
 extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table,
@@ -670,27 +697,12 @@ extern "C" int pdmp3_hip_clip_stft(pdmp3_hip_stream* hs, int slot, const pdmp3_m
     if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: too many frames", hipSuccess);
   }
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | folded table: one block (the log-mel call's; the two never overlap in time), each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
-  const size_t tab_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
-  { void* p = hs->d_mel_args;
-    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc stft tables");
-    hs->d_mel_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_mel_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D stft descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, table, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft table");
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_stft(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                   reinterpret_cast<const float*>(a + desc_bytes), &P),
-            "launch k_clip_stft");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  // descriptors | folded table
+  return clip_run(hs, slot, "pdmp3_hip_clip_stft", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, table, (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_stft(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
+                  });
 }
 // ---- the constant-Q transform (cqt.hip) ----
 // k_clip_cqt, or with `chroma` k_clip_chroma, whose LDS holds `extra_floats` more behind the partial sums (chroma.hip)
@@ -719,30 +731,12 @@ static int clip_cqt_run(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* de
     if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: too many frames", hipSuccess);
   }
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_cqt: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | table: one block (the log-mel call's; the calls never overlap in time), each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
-  const size_t tab_bytes = table_rows * 32 * sizeof(float);
-  { void* p = hs->d_mel_args;
-    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc cqt table");
-    hs->d_mel_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_mel_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D cqt descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, table, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D cqt table");
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY) {
-    const pdmp3_mel_desc* dk = reinterpret_cast<const pdmp3_mel_desc*>(a) + k;
-    const int nk = n_clips - k < kMaxY ? n_clips - k : kMaxY;
-    const float* tab = reinterpret_cast<const float*>(a + desc_bytes);
-    if (chroma) HIP_TRY(pdmp3_launch_clip_chroma(t.stream, dk, nk, tab, chroma), "launch k_clip_chroma");
-    else HIP_TRY(pdmp3_launch_clip_cqt(t.stream, dk, nk, tab, &P), "launch k_clip_cqt");
-  }
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  // descriptors | table
+  return clip_run(hs, slot, "pdmp3_hip_clip_cqt", descs, n_clips, P.n_frames, {{ClipPart::kUpload, table, table_rows * 32 * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return chroma ? pdmp3_launch_clip_chroma(hs->s[slot].stream, dk, nk, as_floats(part[0]), chroma)
+                                  : pdmp3_launch_clip_cqt(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
+                  });
 }
 extern "C" int pdmp3_hip_clip_cqt(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
                                   const pdmp3_cqt_params* params) {
@@ -783,27 +777,12 @@ extern "C" int pdmp3_hip_clip_stft_long(pdmp3_hip_stream* hs, int slot, const pd
     if (((long long)P.n_frames + P.tile - 1) / P.tile * 4 * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: too many frames", hipSuccess);
   }
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_stft_long: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | the four tables: one block (the log-mel call's; the calls never overlap in time), each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
-  const size_t tab_bytes = ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float);
-  { void* p = hs->d_mel_args;
-    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_bytes + 16, "hipMalloc stft tables");
-    hs->d_mel_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_mel_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D stft descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, tables, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft tables");
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_stft_long(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                        reinterpret_cast<const float*>(a + desc_bytes), &P),
-            "launch k_clip_stft_long");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  // descriptors | the four tables
+  return clip_run(hs, slot, "pdmp3_hip_clip_stft_long", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, tables, ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_stft_long(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
+                  });
 }
 // ---- log-mel features at n_fft 2048 and 4096 (mel_long.hip) ----
 extern "C" int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
@@ -825,31 +804,13 @@ extern "C" int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdm
     if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
       return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: too many frames", hipSuccess);
   }
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mel_long: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | the four tables | the filterbank operand: one block (the log-mel call's; the calls never overlap in time),
-  // each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_mel_desc) + 255) & ~(size_t)255;
-  const size_t tab_bytes = ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float);
-  const size_t tab_room = (tab_bytes + 255) & ~(size_t)255;
-  const size_t op_bytes = (size_t)(P.n_fft / 2) * (size_t)P.mels16 * sizeof(float);
-  { void* p = hs->d_mel_args;
-    const int rc = grow_device(&p, &hs->mel_args_cap, desc_bytes + tab_room + op_bytes + 16, "hipMalloc mel tables");
-    hs->d_mel_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_mel_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_mel_desc), hipMemcpyHostToDevice, t.stream), "H2D mel descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, tables, tab_bytes, hipMemcpyHostToDevice, t.stream), "H2D stft tables");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + tab_room, operand, op_bytes, hipMemcpyHostToDevice, t.stream), "H2D filterbank operand");
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_mel_long(t.stream, reinterpret_cast<const pdmp3_mel_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                       reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + tab_room), &P),
-            "launch k_clip_mel_long");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  // descriptors | the four tables | the filterbank operand
+  return clip_run(hs, slot, "pdmp3_hip_clip_mel_long", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, tables, ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float)},
+                   {ClipPart::kUpload, operand, (size_t)(P.n_fft / 2) * (size_t)P.mels16 * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_mel_long(hs->s[slot].stream, dk, nk, as_floats(part[0]), as_floats(part[1]), &P);
+                  });
 }
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
@@ -875,33 +836,17 @@ extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_
   }
   for (int k = 0; k < n_clips; k++)
     if ((long long)descs[k].valid > (long long)P.n_frames) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_fbank: a clip's valid frames exceed its frames", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_fbank: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | folded table | filterbank | (subtract_mean) column sums [clip][channel][tile][D]: one block, each part 256-byte aligned
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_fbank_desc) + 255) & ~(size_t)255;
-  const size_t dft_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
-  const size_t fb_bytes = ((size_t)P.bins16 * (size_t)P.mels16 * sizeof(float) + 255) & ~(size_t)255;
+  // descriptors | folded table | filterbank | (subtract_mean) column sums [clip][channel][tile][D]
   const size_t clip_sums = (size_t)P.channels * tiles * D;               // (floats)
-  const size_t sum_bytes = P.subtract_mean ? (size_t)n_clips * clip_sums * sizeof(float) : 0;
-  { void* p = hs->d_fbank_args;
-    const int rc = grow_device(&p, &hs->fbank_args_cap, desc_bytes + dft_bytes + fb_bytes + sum_bytes + 16, "hipMalloc fbank tables");
-    hs->d_fbank_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_fbank_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_fbank_desc), hipMemcpyHostToDevice, t.stream), "H2D fbank descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, dft, dft_bytes, hipMemcpyHostToDevice, t.stream), "H2D folded DFT table");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + dft_bytes, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float), hipMemcpyHostToDevice, t.stream), "H2D filterbank");
-  float* const sums = reinterpret_cast<float*>(a + desc_bytes + dft_bytes + fb_bytes);
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_fbank(t.stream, reinterpret_cast<const pdmp3_fbank_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                    reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + dft_bytes),
-                                    P.subtract_mean ? sums + (size_t)k * clip_sums : sums, &P),
-            "launch k_clip_fbank");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  return clip_run(hs, slot, "pdmp3_hip_clip_fbank", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, dft, (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float)},
+                   {ClipPart::kUpload, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float)},
+                   {ClipPart::kScratch, nullptr, P.subtract_mean ? (size_t)n_clips * clip_sums * sizeof(float) : 0}},
+                  [&](const pdmp3_fbank_desc* dk, int nk, int k, uint8_t* const* part) {
+                    float* const sums = reinterpret_cast<float*>(part[2]);
+                    return pdmp3_launch_clip_fbank(hs->s[slot].stream, dk, nk, as_floats(part[0]), as_floats(part[1]),
+                                                   P.subtract_mean ? sums + (size_t)k * clip_sums : sums, &P);
+                  });
 }
 // ---- Kaldi-style MFCC features (mfcc.hip) ----
 extern "C" int pdmp3_hip_clip_mfcc(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
@@ -928,38 +873,18 @@ extern "C" int pdmp3_hip_clip_mfcc(pdmp3_hip_stream* hs, int slot, const pdmp3_f
   }
   for (int k = 0; k < n_clips; k++)
     if ((long long)descs[k].valid > (long long)P.n_frames) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: a clip's valid frames exceed its frames", hipSuccess);
-  StreamSlot& t = hs->s[slot];
-  if (t.busy) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc: slot still in flight (wait for it first)", hipSuccess);
-  if (!n_clips || !P.n_frames) return PDMP3_HIP_OK;
-  HIP_TRY(hipSetDevice(hs->ctx->device), "hipSetDevice");
-  // descriptors | folded table | filterbank | folded DCT table | (subtract_mean) column sums [clip][channel][tile][n_ceps]: one
-  // block, each part 256-byte aligned -- the block of the filterbank call, which has returned before this one starts
-  const size_t desc_bytes = ((size_t)n_clips * sizeof(pdmp3_fbank_desc) + 255) & ~(size_t)255;
-  const size_t dft_bytes = (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float);
-  const size_t fb_bytes = ((size_t)P.bins16 * (size_t)P.mels16 * sizeof(float) + 255) & ~(size_t)255;
-  const size_t dct_bytes = ((size_t)P.mels16 * (size_t)params->ceps16 * sizeof(float) + 255) & ~(size_t)255;
+  // descriptors | folded table | filterbank | folded DCT table | (subtract_mean) column sums [clip][channel][tile][n_ceps]
   const size_t clip_sums = (size_t)P.channels * tiles * D;               // (floats)
-  const size_t sum_bytes = P.subtract_mean ? (size_t)n_clips * clip_sums * sizeof(float) : 0;
-  { void* p = hs->d_fbank_args;
-    const int rc = grow_device(&p, &hs->fbank_args_cap, desc_bytes + dft_bytes + fb_bytes + dct_bytes + sum_bytes + 16, "hipMalloc mfcc tables");
-    hs->d_fbank_args = (uint8_t*)p;
-    if (rc != PDMP3_HIP_OK) return rc; }
-  uint8_t* a = hs->d_fbank_args;
-  HIP_TRY(hipMemcpyAsync(a, descs, (size_t)n_clips * sizeof(pdmp3_fbank_desc), hipMemcpyHostToDevice, t.stream), "H2D mfcc descriptors");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes, dft, dft_bytes, hipMemcpyHostToDevice, t.stream), "H2D folded DFT table");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + dft_bytes, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float), hipMemcpyHostToDevice, t.stream), "H2D filterbank");
-  HIP_TRY(hipMemcpyAsync(a + desc_bytes + dft_bytes + fb_bytes, dct, (size_t)P.mels16 * (size_t)params->ceps16 * sizeof(float), hipMemcpyHostToDevice, t.stream),
-          "H2D folded DCT table");
-  float* const sums = reinterpret_cast<float*>(a + desc_bytes + dft_bytes + fb_bytes + dct_bytes);
-  const int kMaxY = 32768;                     // (a grid's y extent ends at 65535)
-  for (int k = 0; k < n_clips; k += kMaxY)
-    HIP_TRY(pdmp3_launch_clip_mfcc(t.stream, reinterpret_cast<const pdmp3_fbank_desc*>(a) + k, n_clips - k < kMaxY ? n_clips - k : kMaxY,
-                                   reinterpret_cast<const float*>(a + desc_bytes), reinterpret_cast<const float*>(a + desc_bytes + dft_bytes),
-                                   reinterpret_cast<const float*>(a + desc_bytes + dft_bytes + fb_bytes),
-                                   P.subtract_mean ? sums + (size_t)k * clip_sums : sums, params),
-            "launch k_clip_mfcc");
-  HIP_TRY(hipStreamSynchronize(t.stream), "stream sync");
-  return PDMP3_HIP_OK;
+  return clip_run(hs, slot, "pdmp3_hip_clip_mfcc", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, dft, (size_t)P.rows * 2 * (size_t)P.bins16 * sizeof(float)},
+                   {ClipPart::kUpload, fbt, (size_t)P.bins16 * (size_t)P.mels16 * sizeof(float)},
+                   {ClipPart::kUpload, dct, (size_t)P.mels16 * (size_t)params->ceps16 * sizeof(float)},
+                   {ClipPart::kScratch, nullptr, P.subtract_mean ? (size_t)n_clips * clip_sums * sizeof(float) : 0}},
+                  [&](const pdmp3_fbank_desc* dk, int nk, int k, uint8_t* const* part) {
+                    float* const sums = reinterpret_cast<float*>(part[3]);
+                    return pdmp3_launch_clip_mfcc(hs->s[slot].stream, dk, nk, as_floats(part[0]), as_floats(part[1]), as_floats(part[2]),
+                                                  P.subtract_mean ? sums + (size_t)k * clip_sums : sums, params);
+                  });
 }
 extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {
   if (!bytes) return PDMP3_HIP_OK;

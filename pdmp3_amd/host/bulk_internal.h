@@ -186,7 +186,7 @@ struct bulk {
   int slot_arena_n[BULK_SLOTS];
   double t_submit, t_gpuwait, t_poolwait;   /* PDMP3_BULK_TRACE=1: where the scanning thread waits */
   double t_sub_gather, t_sub_call, t_drive, t_subwait, t_tail;          /* ... and what the submitter thread spends on the main-data copies / the engine calls */
-  /* clips (clip.c) */
+  /* clips (clip.c, clip_features.c) */
   void (*ix_note)(struct bulk* b);    /* count-only scan: called for every frame (a stream index being built) */
   struct pdmp3_amd_index* ix;
   long long clip_frames, clip_halo;   /* pdmp3_amd_bulk_clip_stats */
@@ -270,6 +270,27 @@ typedef struct {              /* the scanner's state in front of frame `frame` (
   long long last_ws0[4], last_ws1[4];   /* the last frame before it whose gc g had win_switch_flag 0 / 1 (-1: none) */
   int ready;
 } span_snap;
+
+/* a stream index (clip.c builds and reads it; clip_features.c reads the time line: frames, off, fr, rate, spf, mixed, stereo) */
+struct pdmp3_amd_index {
+  long long frames;                  /* or PDMP3_BULK_REPLAY */
+  size_t n;                          /* bytes of the stream it was built from */
+  unsigned iso;                      /* PDMP3_ISO_LSF or 0 */
+  int spacing;
+  int split;                         /* the pre-pass took the stream: rec / snap are there */
+  int oom;
+  long long cap;                     /* capacity of the per-frame arrays (while building) */
+  long long* off;                    /* [frames + 1] PCM bytes in front of each frame */
+  uint8_t* fr;                       /* [frames] PDMP3_FR mode bits and RESET (what pdmp3_node_halo_start reads) */
+  uint32_t* hb;                      /* [frames] HB_* */
+  int32_t* org;                      /* [frames / spacing + 1][IX_GROUPS]: in front of frame k * spacing, the frame each group's
+                                        value came from (-1: none since the stream's start, the value is 0) */
+  hop_rec* rec;                      /* split: the pre-pass's records */
+  span_snap* snap; long long n_snap; /* split: snap[k] in front of frame k * spacing (k >= 1, where ready) */
+  long rate; int spf;                /* the first frame's sampling frequency and samples per frame and channel ... */
+  int mixed, stereo;                 /* ... a later frame's differ (no time line: DESIGN.md section 9); some frame is stereo */
+};
+#define CLIP_SLOT 0                  /* the engine slot every clip call runs on */
 
 struct par_scan {
   /* ---- set before the threads start, read by all of them (the pre-pass looks at abort / quit once per frame: none of this

@@ -1,6 +1,6 @@
 /* clip_audio.c -- libpdmp3.so: the planning of clips as float batches (include/pdmp3_bulk.h pdmp3_amd_audio_span,
  * pdmp3_amd_audio_table): which input samples a clip reads, and the filter table of a pair of sampling
- * frequencies.  Plain arithmetic, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_audio) is clip.c's. */
+ * frequencies.  Plain arithmetic, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_audio) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <math.h>

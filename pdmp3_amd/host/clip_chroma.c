@@ -1,7 +1,7 @@
 /* clip_chroma.c -- libpdmp3.so: the planning of the chroma features of clips (include/pdmp3_bulk.h pdmp3_amd_chroma_*;
  * DESIGN.md section 17): the check, the class of every bin and the kernel's plan.  The transform under the fold is the
  * constant-Q transform's: its check, table, tile rows, split threshold, segments and cache of tables are clip_cqt.c's, called
- * and not restated.  Plain arithmetic, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_chroma) is clip.c's. */
+ * and not restated.  Plain arithmetic, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_chroma) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

@@ -1,7 +1,7 @@
 /* clip_cqt.c -- libpdmp3.so: the planning of the constant-Q transform of clips (include/pdmp3_bulk.h pdmp3_amd_cqt_*;
  * DESIGN.md section 16): the check, the bins' frequencies and lengths, the ragged folded table (window, normalisation and
  * scale in the coefficients), the kernel's plan and the decoder's small cache of tables.  Plain arithmetic in binary64, no
- * GPU; the call itself (pdmp3_amd_bulk_decode_clips_cqt) is clip.c's. */
+ * GPU; the call itself (pdmp3_amd_bulk_decode_clips_cqt) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

@@ -1,7 +1,7 @@
 /* clip_fbank.c -- libpdmp3.so: the planning of Kaldi-style filterbank features of clips (include/pdmp3_bulk.h
  * pdmp3_amd_fbank_*): the DFT table with DC removal, pre-emphasis, the window and the zero padding
  * folded in, the mel filterbank, the frames wholly inside a stream and the kernel's tile.  Plain arithmetic in binary64, no
- * GPU; the call itself (pdmp3_amd_bulk_decode_clips_fbank) is clip.c's. */
+ * GPU; the call itself (pdmp3_amd_bulk_decode_clips_fbank) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

@@ -1,6 +1,6 @@
 /* clip_mel.c -- libpdmp3.so: the planning of log-mel features of clips (include/pdmp3_bulk.h pdmp3_amd_mel_*; DESIGN.md
  * section 10): the DFT table with the window folded in, the mel filterbank, the samples a clip's frames read and the
- * kernel's tile.  Plain arithmetic in binary64, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_mel) is clip.c's. */
+ * kernel's tile.  Plain arithmetic in binary64, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_mel) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

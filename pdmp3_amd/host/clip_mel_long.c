@@ -1,7 +1,7 @@
 /* clip_mel_long.c -- libpdmp3.so: the planning of log-mel features of clips at n_fft 2048 and 4096 (include/pdmp3_bulk.h
  * pdmp3_amd_mel_long_*): the check, the filterbank on the wider domain, the operand in the order
  * k_clip_mel_long meets the bins, the kernel's tile.  The filterbank's arithmetic is clip_mel.c's (mel_fb_fill), the four
- * transform tables are clip_stft_long.c's; no GPU.  The call itself (pdmp3_amd_bulk_decode_clips_mel_long) is clip.c's. */
+ * transform tables are clip_stft_long.c's; no GPU.  The call itself (pdmp3_amd_bulk_decode_clips_mel_long) is clip_features.c's. */
 #include "bulk_internal.h"
 
 static int mell_fft_ok(int n_fft) { return n_fft == 2048 || n_fft == 4096; }

@@ -1,6 +1,6 @@
 /* clip_mfcc.c -- libpdmp3.so: the planning of Kaldi-style MFCC features of clips (include/pdmp3_bulk.h pdmp3_amd_mfcc_*;
  * DESIGN.md section 12): the check, the DCT table with the lifter, htk_compat's sqrt 2 and the column order folded in, and the
- * kernel's tile.  Plain arithmetic in binary64, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_mfcc) is clip.c's. */
+ * kernel's tile.  Plain arithmetic in binary64, no GPU; the call itself (pdmp3_amd_bulk_decode_clips_mfcc) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <math.h>

@@ -1,7 +1,7 @@
 /* clip_stft.c -- libpdmp3.so: the planning of the short-time Fourier transform of clips (include/pdmp3_bulk.h
  * pdmp3_amd_stft_*): the check, the folded table (window and scale in the DFT's coefficients), the
  * kernel's tile and the decoder's small cache of tables.  Plain arithmetic in binary64, no GPU; the call itself
- * (pdmp3_amd_bulk_decode_clips_stft) is clip.c's. */
+ * (pdmp3_amd_bulk_decode_clips_stft) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

@@ -1,7 +1,7 @@
 /* clip_stft_long.c -- libpdmp3.so: the planning of the short-time Fourier transform of clips at n_fft 2048 and 4096
  * (include/pdmp3_bulk.h pdmp3_amd_stft_long_*): the check, the four tables of the two-stage transform
  * N = 64 N2, the kernel's tile and the decoder's two blocks of tables.  Plain arithmetic in binary64, every angle reduced as
- * an integer modulo its period, rounded once; no GPU.  The call itself (pdmp3_amd_bulk_decode_clips_stft_long) is clip.c's. */
+ * an integer modulo its period, rounded once; no GPU.  The call itself (pdmp3_amd_bulk_decode_clips_stft_long) is clip_features.c's. */
 #include "bulk_internal.h"
 
 #include <float.h>

@@ -70,7 +70,7 @@ ODD_PAIRS = [(44100, 44099, 6, 0.99), (48000, 47999, 6, 0.99), (8000, 44101, 6, 
 
 
 def lds_plan(m, l, taps, channels):
-    """pdmp3_amd/host/clip.c audio_lds restated: (flags, span_cap) of a clip with the ratio M : L and `taps` coefficients a row in a
+    """pdmp3_amd/host/clip_features.c audio_lds restated: (flags, span_cap) of a clip with the ratio M : L and `taps` coefficients a row in a
     call with `channels` channels -- the input span of a tile in LDS if it fits 64 KB, the table behind it if that fits too"""
     span = ((l - 1) + (TILE - 1) * m) // l + taps
     cap = (span + 3) & ~3

@@ -2,7 +2,7 @@
 stream's format, the input span of a clip against brute force over the definition, the filter table against binary64, and the
 kernel's own arithmetic (pdmp3_amd/csrc/resample_core.h, compiled here with g++ into tests/host_emul/resample_emul.cpp's loop)
 against the binary64 restatement of tests/clip_audio_ref.py within the error bound of a binary32 dot product -- with the LDS plan
-the product itself chooses (pdmp3_amd_audio_lds_plan: clip.c audio_lds, held here to its restatement and to the kernel's
+the product itself chooses (pdmp3_amd_audio_lds_plan: clip_features.c audio_lds, held here to its restatement and to the kernel's
 preconditions), to MPEG rates and to odd ones, one table a launch and two."""
 import ctypes as C
 import functools

@@ -1,5 +1,5 @@
 """Clips as float batches on the GPU, every path of k_clip_audio and of its host plumbing (pdmp3_amd/csrc/resample.hip,
-stream.hip pdmp3_hip_clip_audio, host/clip.c pdmp3_amd_bulk_decode_clips_audio): the three resampling
+stream.hip pdmp3_hip_clip_audio, host/clip_features.c pdmp3_amd_bulk_decode_clips_audio): the three resampling
 forms by name -- plan 3: input span and table in LDS, plan 1: the span in LDS and the table from memory, plan 0: every sample
 straight from memory --, output rates that are no MPEG rates, tile edges, host destinations as a loader lays them out, a call of
 more clips than one grid holds, one decoder over many calls, far starts, and seeded random batches.
@@ -176,7 +176,7 @@ def _check_rows(clips, rows, valid, t, rate, channels, skip=()):
 
 @pytest.mark.parametrize("channels", [1, 2])
 def test_contiguous_numpy_destinations(channels):
-    """a dense [K, C, T] numpy array has its rows one behind the other: they leave the device stage in ONE copy (clip.c, the loop
+    """a dense [K, C, T] numpy array has its rows one behind the other: they leave the device stage in ONE copy (clip_features.c, the loop
     behind pdmp3_hip_clip_audio) -- the whole array, the array in front of a guard, and with a refused clip in the middle, around
     which the merged copy must break"""
     from pdmp3_amd import api

@@ -9,11 +9,12 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=${TMPDIR:-/tmp}/pdmp3_sanitize
 mkdir -p $OUT
 HOST=$ROOT/pdmp3_amd/host
-SRCS="$HOST/huffman_lut.c $HOST/frame_parse.c $HOST/stream_api.c $HOST/cpus.c $HOST/bulk.c $HOST/split_scan.c $HOST/bulk_api.c $HOST/clip.c $HOST/corpus.c $HOST/wav_cli.c"
+# the library's sources as pdmp3_amd/host/Makefile lists them
+SRCS=$(sed -n 's/^SRCS *:= *//p' $HOST/Makefile | tr ' ' '\n' | sed "s|^|$HOST/|" | tr '\n' ' ')
 for san in thread address,undefined; do
   for t in stream_threads bulk_threads split_scan clip_ranges; do
     gcc -O1 -g -fsanitize=$san -I$ROOT/include -I$ROOT/pdmp3_amd/csrc -o $OUT/$t $ROOT/tools/sanitize/$t.c $SRCS \
-        -L$ROOT/pdmp3_amd -lpdmp3_hip -lpthread -Wl,-rpath,$ROOT/pdmp3_amd -w     # (warnings off, errors shown: a failed build stops the script with its message)
+        -L$ROOT/pdmp3_amd -lpdmp3_hip -lpthread -lm -Wl,-rpath,$ROOT/pdmp3_amd -w     # (warnings off, errors shown: a failed build stops the script with its message)
     echo "== $san $t"
     ASAN_OPTIONS=detect_leaks=0 $OUT/$t "$1" 2>&1 | tail -4
   done
