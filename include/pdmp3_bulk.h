@@ -776,6 +776,73 @@ int pdmp3_amd_chroma_plan(const pdmp3_amd_chroma_spec* spec, long sr, int* tile,
 int pdmp3_amd_bulk_decode_clips_chroma(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_chroma_spec* spec,
                                        long long* valid);
 
+/* ---- Loudness of clips (ITU-R BS.1770 / EBU R128) ----
+ * The integrated loudness of each clip and its normalisation to a target level, on the GPU while the resampled signal is in
+ * device memory: audio [K][C][T] float32, stats [K][8] float32 and optionally momentary [K][Jmax] float32.  New entry points
+ * only; nothing above returns anything else.  With `target` unset the audio is pdmp3_amd_bulk_decode_clips_audio's bit for bit.
+ * What ffmpeg's ebur128 / loudnorm, libebur128, pyloudnorm and torchaudio.functional.loudness compute.  The definition, to be
+ * evaluated in binary64:
+ *
+ * 1. Signal.  x_c[t], c < C, t < T = n_samples, is the row pdmp3_amd_bulk_decode_clips_audio returns for the same clip, rate,
+ *    channels, width and rolloff: binary32 values with zeros behind the stream's end.  The zeros are measured as the silence
+ *    they are.
+ * 2. K-weighting.  y = H2(H1(x)), two biquads, both from rest at t = 0 of the row: a clip is measured as a file holding just
+ *    that clip would be.  The coefficients at rate fs follow libebur128's parametrisation, with K = tan(pi f0 / fs) and
+ *    a0 = 1 + K/Q + K^2.
+ *    Shelf H1: f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, Vh = 10^(G/20),
+ *      Vb = Vh^0.4996667741545416; b = [(Vh + Vb K/Q + K^2), 2 (K^2 - Vh), (Vh - Vb K/Q + K^2)] / a0,
+ *      a = [1, 2 (K^2 - 1) / a0, (1 - K/Q + K^2) / a0].
+ *    High-pass H2: f0 = 38.13547087602444, Q = 0.5003270373238773; b = [1, -2, 1], a as above.
+ *    At 48 kHz these give the standard's table to 1e-15 (1.53512485958697, -2.69169618940638, 1.19839281085285,
+ *    -1.69065929318241, 0.73248077421585 and -1.99004745483398, 0.99007225036621), and a full-scale 997 Hz sine on one channel
+ *    measures -3.0103 LUFS.  torchaudio's own coefficient formulas (RBJ shelf and high-pass) differ from the table in the
+ *    third decimal of a dB; they are not offered.
+ * 3. Blocks.  q = (fs + 5) / 10 (integer division) samples per 100 ms.  Sub-block sums s_c[i] = sum over i q <= t < (i + 1) q
+ *    of y_c[t]^2 for i < I = T / q: only whole sub-blocks count.  Blocks of 400 ms every 100 ms:
+ *    z_j = (1 / 4q) sum_c G_c (s_c[j] + .. + s_c[j + 3]) for j < J = max(0, I - 3); G_c = 1, and G_0 = 2 when C = 1 and
+ *    dual_mono.  Block loudness l_j = -0.691 + 10 log10 z_j, and -inf at z_j = 0.
+ * 4. Gates.  Absolute gate A = {j : l_j > -70}.  Relative threshold Gamma = -0.691 + 10 log10(mean_A z_j) - 10.  Gated set
+ *    Gt = {j in A : l_j > Gamma}.  Integrated loudness L = -0.691 + 10 log10(mean_Gt z_j), and L = -inf when A is empty.
+ *    Maximum momentary loudness M = max_j l_j, and -inf when J = 0.  Sample peak P = max_{c,t} |x_c[t]|, exact in binary32.
+ * 5. Gain.  g = 1 when target is unset (NaN) or L = -inf.  Otherwise g = 10^((target - L) / 20); if peak_limit > 0 and
+ *    g P > peak_limit, then g = peak_limit / P.  g is rounded once to binary32; audio = fl32(x g).  With g = 1 the row is the
+ *    audio call's bit for bit.
+ * 6. Outputs.  stats[k] = [L, M, P, g, Gamma, J, |A|, |Gt|]; the counts are exact as floats; Gamma = -inf when A is empty.
+ *    momentary[k][j] = l_j for j < J, and -inf from J to Jmax = max(0, T / q - 3).  valid is the audio call's.
+ * 7. Refusals (-1, nothing written): fs < 8000 or fs > 192000; target finite outside [-70, 0] (or infinite); peak_limit
+ *    negative or not finite; dual_mono outside {0, 1}, or set with C = 2; whatever the audio call refuses.
+ * A clip of a replay or mixed-format stream is reported as in the other calls, and its rows of audio, stats and momentary stay
+ * untouched.  A clip wholly behind the end gives [-inf, -inf, 0, 1, -inf, J, 0, 0], audio exactly +0.
+ *
+ * Not offered: short-term (3 s) loudness and loudness range, true peak (4x oversampled), more than two channels, measuring
+ * across clip boundaries with the stream's real history, torchaudio's coefficient variant. */
+typedef struct {
+  long rate; int channels; long long n_samples; int width; double rolloff;      /* pdmp3_amd_audio_spec's */
+  double target;            /* LUFS in [-70, 0]; NaN: no gain */
+  double peak_limit;        /* > 0: g P <= peak_limit; 0: no limit */
+  int dual_mono;            /* 1: a mono clip counts as two channels (G_0 = 2) */
+} pdmp3_amd_loudness_spec;
+/* 0 when the call would accept these numbers at sampling frequency fs and `channels` (1 or 2) channels, else -1 (item 7) */
+int pdmp3_amd_loudness_check(const pdmp3_amd_loudness_spec* spec, long fs, int channels);
+/* The two biquads at fs: coef[12] = H1's b[3], a[3], then H2's b[3], a[3] (a[0] = 1).  0, or -1 (fs outside 8000 .. 192000). */
+int pdmp3_amd_loudness_coefficients(long fs, double* coef);
+/* The tables of the device's filter at fs as the kernels read them (csrc/loudness.hip), for blocks of B = 64 samples and the
+ * state s = (z1, z2 of H1, z1, z2 of H2) of the transposed direct form II:  y_block = Hm u_block + O s_in,
+ * s_out = Phi s_in + R u_block.  Hm [64][64] binary32, lower-triangular Toeplitz of the impulse response (the kernel reads
+ * its column 0); O [64][4] binary32; Phi [4][4] and R [4][64] binary64; pows [70][16] binary64: Phi^k for k = 0 .. 64, then
+ * Phi^(64 2^k), k = 1 .. 5.  All made in binary64, Hm and O rounded once.  Pointers may be NULL.  0, or -1. */
+int pdmp3_amd_loudness_tables(long fs, float* Hm, float* O, double* Phi, double* R, double* pows);
+/* The launch's geometry for rows of n_samples at fs: B (samples of a block), chunk (blocks of a scan chunk), the LDS bytes
+ * of a workgroup of k_loud_blocks, q, the chunks of a row, I and J.  Pointers may be NULL.  0, or -1 (fs as above, n_samples
+ * outside 0 .. 2^31 - 4). */
+int pdmp3_amd_loudness_plan(long fs, long long n_samples, int* B, int* chunk, unsigned* lds_bytes, int* q, long long* n_chunks, long long* I,
+                            long long* J);
+/* Row k receives channel c's n_samples floats x g at dst + c * chan_stride (pdmp3_amd_audio_clip).  stats: [n_clips][8]
+ * floats; momentary: NULL, or [n_clips][Jmax] floats; each host memory or device memory of the decoder's GPU.  Everything else
+ * as pdmp3_amd_bulk_decode_clips_audio; the kernels are csrc/loudness.hip's.  -1 also where pdmp3_amd_loudness_check says so. */
+int pdmp3_amd_bulk_decode_clips_loudness(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
+                                         float* stats, float* momentary, long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

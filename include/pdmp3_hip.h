@@ -686,6 +686,39 @@ typedef struct pdmp3_chroma_params {
 int pdmp3_hip_clip_chroma(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* table, size_t table_rows,
                           const pdmp3_chroma_params* params);
 
+/* Loudness of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_loudness).  The rows are
+ * k_clip_audio's in audio stage 2 (pdmp3_mel_desc with lead = 0: sample t of channel c is src[c * src_chan_stride + t], t <
+ * n_in, src 16-byte aligned and src_chan_stride a multiple of 4); dst receives x * g, dst_chan_stride floats between the
+ * channels.  A row is cut into blocks of PDMP3_LOUD_B samples and chunks of PDMP3_LOUD_CHUNK blocks; the K-weighting of a block
+ * is y = Hm u + O s with s the four-value state of the two biquads at the block's start.  Five kernels (loudness.hip):
+ *   k_loud_states  a wave a chunk: w_b = R u_b and the states from rest at the chunk's start, binary64, a wave-level scan
+ *   k_loud_chain   a wave a row: the states at the chunks' starts, binary64, a wave-level scan over 64 chunks at a time
+ *   k_loud_blocks  four waves a chunk: [Hm | O | O] [U ; S_hi ; S_lo] on v_mfma_f32_16x16x4_f32, y^2 into three partial
+ *                  sub-block sums a wave and |x| into a peak a wave, both in one fixed order, no atomics
+ *   k_loud_gate    a workgroup a clip: sub-block sums, blocks, gates, L, M, P, g in binary64; writes stats and momentary
+ *   k_loud_scale   dst = x * g
+ * The tables are made once per rate on the host (pdmp3_amd/host/clip_loudness.c), in binary64; Hm and O rounded once. */
+#define PDMP3_LOUD_B 64                     /* samples of a block                                                        */
+#define PDMP3_LOUD_CHUNK 64                 /* blocks of a chunk of the scan: 4096 samples                               */
+#define PDMP3_LOUD_POWS 70                  /* Phi^k, k = 0 .. 64, then Phi^(64 * 2^k), k = 1 .. 5                       */
+#define PDMP3_LOUD_LDS_BYTES (64 * 68 * 4)  /* k_loud_blocks: a chunk's samples, a block every 68 floats                 */
+typedef struct pdmp3_loud_tables {
+  double pow[PDMP3_LOUD_POWS][16];          /* powers of Phi [4 x 4], row-major                                          */
+  double R[4][PDMP3_LOUD_B];                /* the state a block's samples leave behind                                  */
+  float Hm[PDMP3_LOUD_B][PDMP3_LOUD_B];     /* lower-triangular Toeplitz of the impulse response: the kernel reads column 0 */
+  float O[PDMP3_LOUD_B][4];                 /* the free response of a block to the state at its start                    */
+} pdmp3_loud_tables;
+typedef struct pdmp3_loud_params {
+  int64_t n_in;                             /* T: samples of a row, < 2^31                                               */
+  int32_t channels, q;                      /* 1 or 2; samples of a sub-block, (fs + 5) / 10                             */
+  int32_t n_chunks, n_sub;                  /* ceil(T / 4096); I = T / q                                                 */
+  int32_t n_mom, dual_mono;                 /* J = max(0, I - 3); G_0 = 2                                                */
+  double target, peak_limit;                /* NaN: no gain; 0: no limit                                                 */
+} pdmp3_loud_params;
+/* stats_dst[i], mom_dst[i]: the device addresses of clip i's 8 floats and (or 0) n_mom floats.  Blocks until all is written. */
+int pdmp3_hip_clip_loudness(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_loud_tables* tables,
+                            const uint64_t* stats_dst, const uint64_t* mom_dst, const pdmp3_loud_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -30,7 +30,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_mel_long_check", "pdmp3_amd_mel_long_filterbank", "pdmp3_amd_mel_long_operand", "pdmp3_amd_mel_long_plan",
                 "pdmp3_amd_bulk_decode_clips_mel_long",
                 "pdmp3_amd_cqt_check", "pdmp3_amd_cqt_lengths", "pdmp3_amd_cqt_table", "pdmp3_amd_cqt_plan", "pdmp3_amd_bulk_decode_clips_cqt",
-                "pdmp3_amd_chroma_check", "pdmp3_amd_chroma_map", "pdmp3_amd_chroma_plan", "pdmp3_amd_bulk_decode_clips_chroma"]
+                "pdmp3_amd_chroma_check", "pdmp3_amd_chroma_map", "pdmp3_amd_chroma_plan", "pdmp3_amd_bulk_decode_clips_chroma",
+                "pdmp3_amd_loudness_check", "pdmp3_amd_loudness_coefficients", "pdmp3_amd_loudness_tables", "pdmp3_amd_loudness_plan",
+                "pdmp3_amd_bulk_decode_clips_loudness"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -194,6 +196,12 @@ def load_library():
         lib.pdmp3_amd_chroma_map.argtypes = [vp, C.c_long, vp, C.c_size_t, vp]
         lib.pdmp3_amd_chroma_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint)] + [C.POINTER(C.c_int)] * 3 + [C.POINTER(C.c_uint)] * 2
         lib.pdmp3_amd_bulk_decode_clips_chroma.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_loudness"):     # (loudness of clips: absent from older builds)
+        lib.pdmp3_amd_loudness_check.argtypes = [vp, C.c_long, C.c_int]
+        lib.pdmp3_amd_loudness_coefficients.argtypes = [C.c_long, vp]
+        lib.pdmp3_amd_loudness_tables.argtypes = [C.c_long, vp, vp, vp, vp, vp]
+        lib.pdmp3_amd_loudness_plan.argtypes = [C.c_long, ll] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint), C.POINTER(C.c_int)] + [C.POINTER(ll)] * 3
+        lib.pdmp3_amd_bulk_decode_clips_loudness.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
     _LIB = lib
     return lib
 
@@ -923,6 +931,56 @@ class _Clip(C.Structure):                          # include/pdmp3_bulk.h pdmp3_
                 ("n_frames", C.c_longlong), ("dst", C.c_void_p), ("dst_cap", C.c_size_t)]
 
 
+class _LoudnessSpec(C.Structure):                  # include/pdmp3_bulk.h pdmp3_amd_loudness_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("n_samples", C.c_longlong), ("width", C.c_int), ("rolloff", C.c_double),
+                ("target", C.c_double), ("peak_limit", C.c_double), ("dual_mono", C.c_int)]
+
+
+def _loudness_spec(n_samples=0, sample_rate=0, channels=0, target=None, peak_limit=0.0, dual_mono=False, width=0, rolloff=0.0):
+    return _LoudnessSpec(int(sample_rate), int(channels), int(n_samples), int(width), float(rolloff),
+                         float("nan") if target is None else float(target), float(peak_limit), int(dual_mono))
+
+
+def loudness_check(sample_rate, channels=1, **kw):
+    """pdmp3_amd_loudness_check -> True when pdmp3_amd_bulk_decode_clips_loudness would accept these numbers (decode_clips_loudness's
+    target, peak_limit, dual_mono) at sample_rate and `channels` channels"""
+    try:
+        spec = _loudness_spec(sample_rate=sample_rate, channels=channels, **kw)
+    except (ValueError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_loudness_check(C.byref(spec), int(sample_rate), int(channels)) == 0
+
+
+def loudness_coefficients(sample_rate):
+    """pdmp3_amd_loudness_coefficients -> float64 [2, 2, 3]: [filter H1 / H2][b / a][3], the K-weighting's two biquads"""
+    c = np.zeros(12, dtype=np.float64)
+    if load_library().pdmp3_amd_loudness_coefficients(int(sample_rate), c.ctypes.data) != 0:
+        raise ValueError("pdmp3_amd_loudness_coefficients: bad argument")
+    return c.reshape(2, 2, 3)
+
+
+def loudness_tables(sample_rate):
+    """pdmp3_amd_loudness_tables -> (Hm float32 [64, 64], O float32 [64, 4], Phi float64 [4, 4], R float64 [4, 64], powers of Phi
+    float64 [70, 4, 4]) as the loudness kernels read them"""
+    hm, o = np.zeros((64, 64), dtype=np.float32), np.zeros((64, 4), dtype=np.float32)
+    phi, r, pw = np.zeros((4, 4), dtype=np.float64), np.zeros((4, 64), dtype=np.float64), np.zeros((70, 4, 4), dtype=np.float64)
+    if load_library().pdmp3_amd_loudness_tables(int(sample_rate), hm.ctypes.data, o.ctypes.data, phi.ctypes.data, r.ctypes.data, pw.ctypes.data) != 0:
+        raise ValueError("pdmp3_amd_loudness_tables: bad argument")
+    return hm, o, phi, r, pw
+
+
+def loudness_plan(sample_rate, n_samples):
+    """pdmp3_amd_loudness_plan -> (samples of a block, blocks of a scan chunk, LDS bytes of a workgroup of k_loud_blocks, q, chunks
+    of a row, I, J)"""
+    b, ch, q = C.c_int(0), C.c_int(0), C.c_int(0)
+    lds = C.c_uint(0)
+    nc, i, j = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+    if load_library().pdmp3_amd_loudness_plan(int(sample_rate), int(n_samples), C.byref(b), C.byref(ch), C.byref(lds), C.byref(q), C.byref(nc),
+                                               C.byref(i), C.byref(j)) != 0:
+        raise ValueError("pdmp3_amd_loudness_plan: bad argument")
+    return b.value, ch.value, lds.value, q.value, nc.value, i.value, j.value
+
+
 class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
                 ("chan_stride", C.c_size_t)]
@@ -1235,6 +1293,50 @@ class BulkDecoder:
         return self._clips_stft("chroma", clips, n_frames, sample_rate, None, hop, None, None, None, quantity, 0.0, channels, width, rolloff, out,
                                 nb=int(n_chroma), spec_of=spec)
 
+    def decode_clips_loudness(self, clips, n_samples, sample_rate=0, channels=0, target=None, peak_limit=0.0, dual_mono=False, width=0,
+                              rolloff=0.0, out=None, momentary=None):
+        """pdmp3_amd_bulk_decode_clips_loudness: clips, n_samples, sample_rate, channels, width, rolloff and out as
+        decode_clips_audio takes them -> (audio, stats, valid).  stats float32 [K, 8] = integrated loudness L (LUFS, ITU-R
+        BS.1770 / EBU R128), maximum momentary loudness M, sample peak P, the gain g, the relative threshold, the 400 ms blocks
+        J, those above the absolute gate, those above both gates -- a torch tensor on the decoder's device, or a numpy array
+        where out is one.  audio = decode_clips_audio's rows times g: g = 1 without a target (bit for bit that call's rows), else
+        10^((target - L) / 20) with target in [-70, 0] LUFS, held to peak_limit / P where peak_limit > 0.  dual_mono: a mono
+        clip counts twice (+3.01 dB).  momentary: None, or a float32 [K, Jmax] destination (torch on the device, or numpy) for
+        the block loudnesses l_j, Jmax = max(0, n_samples // q - 3), q = (rate + 5) // 10.  A clip's filter starts from rest
+        at its first sample.  Rows of stats belonging to clips that raise RingReplay / MixedFormat (.out, .stats, .valid) stay
+        NaN.  With n_samples = 0 nothing is measured: stats stays NaN."""
+        t, k = int(n_samples), len(clips)
+        if out is None or hasattr(out, "data_ptr"):
+            import torch
+            stats = torch.full((k, 8), float("nan"), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
+            torch.cuda.synchronize()
+            sp = stats.data_ptr()
+        else:
+            stats = np.full((k, 8), np.nan, dtype=np.float32)
+            sp = stats.ctypes.data
+        mp = None
+        if momentary is not None:
+            torch_like = hasattr(momentary, "data_ptr")
+            ok = (momentary.is_contiguous() and str(momentary.dtype) == "torch.float32") if torch_like else \
+                (momentary.flags["C_CONTIGUOUS"] and momentary.dtype == np.float32)
+            assert ok and len(momentary.shape) == 2 and momentary.shape[0] >= k, "momentary: float32 [>= K, Jmax], contiguous"
+            rates = set(ix.rate for _, ix, _ in clips if not ix.replay and ix.one_format and ix.frames)
+            fs = int(sample_rate) or (rates.pop() if len(rates) == 1 else 0)
+            if fs and t:                           # (else the library refuses the call, or writes nothing)
+                try:
+                    jmax = loudness_plan(fs, t)[6]
+                except ValueError:
+                    raise RuntimeError("pdmp3_amd_bulk_decode_clips_loudness: bad sample_rate or n_samples")
+                assert momentary.shape[1] == jmax, "momentary: float32 [>= K, %d]" % jmax
+            mp = momentary.data_ptr() if torch_like else momentary.ctypes.data
+        spec = lambda: (_loudness_spec(t, sample_rate, channels, target, peak_limit, dual_mono, width, rolloff), None)
+        try:
+            audio, valid = self._clips_call("loudness", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError), extra=(sp, mp))
+        except (RingReplay, MixedFormat) as e:
+            e.stats = stats
+            raise
+        return audio, stats, valid
+
     def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
                     nb=None, spec_of=None):
         """the transform calls: `nb` bins (n_fft // 2 + 1) of n_frames frames, mode "complex" as complex64 or float32 [..., 2]; what
@@ -1248,11 +1350,12 @@ class BulkDecoder:
             spec = lambda: _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
         return self._clips_call(call, clips, (nb, f, 2) if m == 0 else (nb, f), spec, channels, out, complex_ok=m == 0, refused=(ValueError, OverflowError))
 
-    def _clips_call(self, call, clips, inner, spec_of, channels, out, made=None, complex_ok=False, refused=()):
+    def _clips_call(self, call, clips, inner, spec_of, channels, out, made=None, complex_ok=False, refused=(), extra=()):
         """What every decode_clips_<call> does around its spec: the channel count, `out` made when not given (float32
         [K, C] + `made`, which is `inner` unless given; complex_ok: complex64 without inner's last 2), the destination checked
         (_clip_destination), the clips' array, the library's call and its refusals as exceptions.  spec_of() -> (the call's spec,
-        what has to stay alive beside it or None); an exception of the types `refused` from it becomes a RuntimeError."""
+        what has to stay alive beside it or None); an exception of the types `refused` from it becomes a RuntimeError.  extra: the
+        library call's arguments between its spec and valid."""
         k = len(clips)
         c = int(channels)
         if not c:
@@ -1277,7 +1380,7 @@ class BulkDecoder:
         except refused as e:
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s: %s" % (call, e))
         got = (C.c_longlong * max(k, 1))()
-        rc = getattr(self.lib, "pdmp3_amd_bulk_decode_clips_" + call)(self.h, arr, k, C.byref(spec), got)
+        rc = getattr(self.lib, "pdmp3_amd_bulk_decode_clips_" + call)(self.h, arr, k, C.byref(spec), *extra, got)
         valid = np.array(got[:k], dtype=np.int64)
         if rc in (PDMP3_BULK_REPLAY, PDMP3_BULK_MIXED_FORMAT):
             e = (RingReplay("the reference replays its input ring on a clip's stream (no finite output)") if rc == PDMP3_BULK_REPLAY else

@@ -170,6 +170,11 @@ hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, in
 hipError_t pdmp3_launch_clip_cqt(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_cqt_params* params);
 // ---- chroma.hip ----
 hipError_t pdmp3_launch_clip_chroma(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_chroma_params* params);
+// ---- loudness.hip ----
+// clips [clip0, clip0 + n_clips) of the launch, whose descriptors lie at descs; every other pointer is the whole launch's
+hipError_t pdmp3_launch_clip_loudness(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, int clip0, const pdmp3_loud_tables* tab,
+                                      const uint64_t* stats_dst, const uint64_t* mom_dst, double* states, double* starts, float* part, float* sub,
+                                      float* gains, const pdmp3_loud_params* params);
 // ---- stft_long.hip ----
 hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                        const pdmp3_stft_long_params* params);

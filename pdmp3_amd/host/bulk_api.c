@@ -42,6 +42,7 @@ void pdmp3_amd_bulk_delete(struct bulk* b) {
   while (b->stft_tabs) { stft_tab* t = b->stft_tabs; b->stft_tabs = t->next; free(t->t); free(t->window); free(t); }
   while (b->cqt_tabs) { cqt_tab* t = b->cqt_tabs; b->cqt_tabs = t->next; free(t->t); free(t); }
   free(b->stft_long_tabs[0]); free(b->stft_long_tabs[1]);
+  while (b->loud_tabs) { loud_tab* t = b->loud_tabs; b->loud_tabs = t->next; free(t); }
   free(b->id);
   free(b);
 }

@@ -88,6 +88,7 @@ typedef struct stft_tab { int n_fft, win, normalized; float* window; float* t; s
 /* the constant-Q transform (clip_cqt.c): a ragged folded table per (sr, fmin, n_bins, bins_per_octave, filter_scale, norm,
  * scale); a short list, the most recently used first */
 typedef struct cqt_tab { long sr; int n_bins, bpo, norm, scale; double fmin, filter_scale; float* t; struct cqt_tab* next; } cqt_tab;
+typedef struct loud_tab { long fs; pdmp3_loud_tables t; struct loud_tab* next; } loud_tab;   /* the loudness filter's tables of a rate */
 
 struct bulk {
   pdmp3_handle* id;
@@ -197,6 +198,7 @@ struct bulk {
   struct stft_tab* stft_tabs;         /* the short-time Fourier transform: the last PDMP3_STFT_TABLES folded tables */
   struct cqt_tab* cqt_tabs;           /* the constant-Q transform: the last PDMP3_CQT_TABLES tables */
   float* stft_long_tabs[2];           /* ... at n_fft 2048 and 4096: a call's block of tables, made once; its wt is filled per call */
+  struct loud_tab* loud_tabs;         /* the loudness call: the blocked filter's tables, one per rate */
 };
 
 /* room for a segment start (2064 + 511), a frame's main data (< 2000) and an explicit image (2064) */
@@ -394,6 +396,11 @@ HOST_LOCAL void cqt_lds(int rows0, int hop, int tile, int row_pad, unsigned* spa
 /* clip_chroma.c: the plan of a workgroup of k_clip_chroma -- cqt_plan's with the q plane behind the partial sums and the tile
  * chosen for the whole of it (0, or -1 where the check refuses the spec) */
 HOST_LOCAL int chroma_plan(const pdmp3_amd_chroma_spec* s, long sr, pdmp3_chroma_params* p);
+/* clip_loudness.c: the blocked K-weighting filter's tables at fs, the decoder's kept copy of them (NULL: no memory), and the
+ * launch's geometry for rows of n_samples (0, or -1) */
+HOST_LOCAL void loud_tables_fill(long fs, pdmp3_loud_tables* t);
+HOST_LOCAL const pdmp3_loud_tables* loud_tables(struct bulk* b, long fs);
+HOST_LOCAL int loud_plan(long fs, long long n_samples, pdmp3_loud_params* p);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

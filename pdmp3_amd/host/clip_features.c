@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
- * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma;
- * DESIGN.md sections 9-17).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
+ * _loudness; DESIGN.md sections 9-18).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -577,4 +577,60 @@ int pdmp3_amd_bulk_decode_clips_chroma(struct bulk* b, const pdmp3_amd_audio_cli
                                        long long* valid) {
   if (!spec) return -1;
   return cqt_clips(b, clips, n_clips, &spec->cqt, spec, valid);
+}
+
+/* ---- the loudness of clips ---- */
+/* The call is a feature call whose "frame" is one sample: the rows through the audio call into stage 2, the kernels behind them.
+ * stats and momentary are destinations beside the rows: in device memory the kernel writes clip k's floats itself, for host
+ * memory they lie in stage 1 behind the rows of host destinations and are copied out, the floats of consecutive clips in one
+ * copy.  With n_samples 0 nothing but valid is written. */
+static int copy_floats_out(float* dst, const float* stage, const int* clip_of, int nd, size_t per) {
+  for (int i = 0; i < nd; i++) {
+    int j = i + 1;
+    while (j < nd && clip_of[j] == clip_of[j - 1] + 1) j++;
+    if (pdmp3_hip_copy_from_device(dst + (size_t)clip_of[i] * per, stage + (size_t)i * per, (size_t)(j - i) * per * sizeof(float)) != PDMP3_HIP_OK) return -1;
+    i = j - 1;
+  }
+  return 0;
+}
+
+int pdmp3_amd_bulk_decode_clips_loudness(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
+                                         float* stats, float* momentary, long long* valid) {
+  clip_course cc;
+  if (!spec || course_begin(&cc, b, clips, n_clips, valid, spec->n_samples, spec->channels, spec->rate, spec->width, spec->rolloff) != 0) return -1;
+  if ((n_clips && !stats) || pdmp3_amd_loudness_check(spec, cc.sr, cc.C) != 0) return -1;
+  pdmp3_loud_params P;
+  if (loud_plan(cc.sr, spec->n_samples, &P) != 0) return -1;
+  if (course_rows(&cc, 1, 1, 1, 0) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const size_t J = (size_t)P.n_mom;
+  if (!J) momentary = NULL;
+  const int stats_dev = pdmp3_hip_host_is_pinned(stats, (size_t)n_clips * 8 * sizeof(float)) == 2;
+  const int mom_dev = momentary && pdmp3_hip_host_is_pinned(momentary, (size_t)n_clips * J * sizeof(float)) == 2;
+  const size_t stat_at = cc.out_floats;
+  if (!stats_dev) cc.out_floats += (size_t)cc.nd * 8;
+  const size_t mom_at = cc.out_floats;
+  if (momentary && !mom_dev) cc.out_floats += (size_t)cc.nd * J;
+  const pdmp3_loud_tables* tab = loud_tables(b, cc.sr);
+  int* clip_of = (int*)calloc((size_t)cc.nd, sizeof *clip_of);                 /* the clip of every descriptor */
+  uint64_t* at = (uint64_t*)calloc(2 * (size_t)cc.nd, sizeof *at);             /* where its stats go on the device, where its momentary values */
+  int rc = -1;
+  if (!tab || !clip_of || !at || course_signal(&cc) != 0) goto out;
+  float* const stage = cc.out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, cc.out_floats * sizeof(float)) : NULL;
+  if (cc.out_floats && !stage) goto out;
+  for (int k = 0, i = 0; k < n_clips; k++) {
+    if (clips[k].index->frames < 0 || clips[k].index->mixed) continue;
+    clip_of[i] = k;
+    at[i] = (uint64_t)(uintptr_t)(stats_dev ? stats + (size_t)k * 8 : stage + stat_at + (size_t)i * 8);
+    at[cc.nd + i] = !momentary ? 0 : (uint64_t)(uintptr_t)(mom_dev ? momentary + (size_t)k * J : stage + mom_at + (size_t)i * J);
+    i++;
+  }
+  P.channels = cc.C; P.dual_mono = spec->dual_mono; P.target = spec->target; P.peak_limit = spec->peak_limit;
+  if (course_launched(pdmp3_hip_clip_loudness(b->hs, CLIP_SLOT, cc.ds, cc.nd, tab, at, at + cc.nd, &P)) != 0) goto out;
+  if (!stats_dev && copy_floats_out(stats, stage + stat_at, clip_of, cc.nd, 8) != 0) goto out;
+  if (momentary && !mom_dev && copy_floats_out(momentary, stage + mom_at, clip_of, cc.nd, J) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(clip_of); free(at);
+  return course_finish(&cc, rc);
 }

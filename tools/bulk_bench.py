@@ -775,6 +775,80 @@ def clips_chroma(args, api):
     print(json.dumps(res))
 
 
+def clips_loudness(args, api):
+    """--loudness: 64 clips of 30 s (--clips / --clip-frames change that) at 32 000 Hz stereo in device memory, two ways, run after
+    run in turn: (a) pdmp3_amd_bulk_decode_clips_audio; (b) pdmp3_amd_bulk_decode_clips_loudness for the same clips with target
+    -14 LUFS (audio times the gain, stats, no momentary curve).  There is no torch route to hold against: torch without
+    torchaudio has no recursive filter.  (b) minus (a) is reported, not capped.  The kernels' own times come from a
+    kernel-trace run of this mode (profiles/clip_loudness.txt).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, target = args.clips, args.clip_frames, 32000, -14.0
+    T = 30 * rate if F == 1149 else F * 1152 * rate // 44100
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    clips = []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    dev = "cuda:0"
+    out_a = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    stats = [None]
+
+    def audio_route():
+        dec.decode_clips_audio(clips, T, rate, 2, out=out_a)
+
+    def loudness_route():
+        stats[0] = dec.decode_clips_loudness(clips, T, rate, 2, target=target, out=out_b)[1]
+
+    routes = [("audio clips", audio_route), ("loudness clips", loudness_route)]
+    times = {name: [] for name, _ in routes}
+    seen = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 2:] + routes[:r % 2]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            st = stats[0].cpu().numpy()
+            fin = np.isfinite(st[:, 0])
+            seen = {"audio_is_x_times_g": bool(torch.equal(out_b, out_a * stats[0][:, 3].view(K, 1, 1))), "clips_with_a_loudness": int(fin.sum()),
+                    "L_min": float(st[fin, 0].min()) if fin.any() else None, "L_max": float(st[fin, 0].max()) if fin.any() else None,
+                    "g_min": float(st[:, 3].min()), "g_max": float(st[:, 3].max()), "blocks": int(st[0, 5])}
+    dec.close()
+    plan = api.loudness_plan(rate, T)
+    res = {"workload": "%d clips of %d samples at %d Hz stereo, K-weighted, gated and scaled to %g LUFS: %s" % (
+               K, T, rate, target, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "plan": {"block": plan[0], "chunk_blocks": plan[1], "lds_bytes": plan[2], "q": plan[3], "chunks": plan[4], "I": plan[5], "J": plan[6]},
+           "batch_bytes": K * 2 * T * 4, "seen": seen, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["loudness_minus_audio_ms"] = round((med["loudness clips"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -1005,6 +1079,9 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as 12 x 1292 chroma features at 22 050 Hz mono, the default spec "
                          "(pdmp3_amd_bulk_decode_clips_chroma) against the audio call alone and the constant-Q call followed by the fold and "
                          "the max norm in torch (see clips_chroma())")
+    ap.add_argument("--loudness", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) at 32 000 Hz stereo measured by ITU-R BS.1770 and scaled to -14 LUFS "
+                         "(pdmp3_amd_bulk_decode_clips_loudness) against the audio call alone (see clips_loudness())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1012,7 +1089,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1022,6 +1099,8 @@ def main():
             return clips_cqt(args, api)
         if args.chroma:
             return clips_chroma(args, api)
+        if args.loudness:
+            return clips_loudness(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
