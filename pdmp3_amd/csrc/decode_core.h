@@ -80,6 +80,12 @@ struct ConstBank;
 // against the flag by the wave's own vector-memory counter; nothing else is flushed.  The waiting wave sleeps between polls.
 #define PD_STORE_DEVICE(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 #define PD_LOAD_DEVICE(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// A device-scope (sc1: written through) store of 16 bytes per lane, for bytes that are to be on their way to memory while
+// the kernel still runs instead of staying dirty in L2 until it ends (pcm_emit_through).  Through a buffer descriptor over
+// exactly the bytes the wave may touch: accesses past them are dropped by the hardware.  PD_RANGE16(p, bytes): p
+// wave-uniform and 16-byte aligned; PD_STORE16_DEVICE(range, byte offset, Chunk16).
+#define PD_RANGE16(p, bytes) __builtin_amdgcn_make_buffer_rsrc((void*)PD_UNIFORM_PTR(char*, (p)), (short)0, (int)(bytes), 0x00020000)
+#define PD_STORE16_DEVICE(rs, off, v) __builtin_amdgcn_raw_buffer_store_b128((v), (rs), (int)(off), 0, 16)
 #define PD_VMEM_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 #define PD_SLEEP() __builtin_amdgcn_s_sleep(4)
 #define PD_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
@@ -169,6 +175,14 @@ void permlane32_swap(int* a, int* b);         // v_permlane32_swap_b32 vdst = a,
 // (the host build runs the waves one after the other in frame order: a flag is always set before it is waited for)
 #define PD_STORE_DEVICE(p, v) (*(p) = (v))
 #define PD_LOAD_DEVICE(p) (*(p))
+// (the 16-byte form: a range of bytes; what lies past it is not stored, as on the device)
+namespace pdmp3 {
+struct Range16 { char* p; size_t n; };
+typedef uint32_t Range16Chunk __attribute__((vector_size(16)));
+static inline void range16_store(const Range16& r, size_t off, Range16Chunk v) { if (off + 16 <= r.n) __builtin_memcpy(r.p + off, &v, 16); }
+}  // namespace pdmp3
+#define PD_RANGE16(p, bytes) (::pdmp3::Range16{(char*)(p), (size_t)(bytes)})
+#define PD_STORE16_DEVICE(rs, off, v) ::pdmp3::range16_store((rs), (size_t)(off), (v))
 #define PD_VMEM_DRAIN() ::pdmp3::emu::wave_sync()
 #define PD_SLEEP() ::pdmp3::emu::wave_yield()    /* the other live waves of the workgroup run (a lone wave comes straight back) */
 #define PD_SETPRIO(x) ((void)0)
@@ -214,6 +228,16 @@ static inline void mul18_rtz_32767(const float* x, float* p) {
 // development only (tools/ab_pmc.sh): phases switched off for instruction-count / timing experiments -- results are wrong
 #ifndef PD_EXP_SKIP
 #define PD_EXP_SKIP 0
+#endif
+// A/B switches of the granule kernel's PCM stores (profiles/gran_store_ab.txt; results are the same in every form):
+// -DPD_EXP_PCM_PLAIN: the nine plain dword stores per lane of before; -DPD_EXP_PCM_SC1: those nine as device-scope
+// (write-through) dword stores -- a timing probe; neither: staged in LDS, 16 bytes per lane, write-through
+#if defined(PD_EXP_PCM_PLAIN)
+#define PD_GRAN_PCM_FORM 0
+#elif defined(PD_EXP_PCM_SC1)
+#define PD_GRAN_PCM_FORM 2
+#else
+#define PD_GRAN_PCM_FORM 1
 #endif
 // the VALU columns' coefficients as [m][q] (q fastest): the pair (q, q + 1) of one m is an aligned scalar-register pair, a
 // v_pk_fma_f32 operand as it comes out of the s_load -- as [q][m] every packed FMA needed one or two s_mov_b32 in front of
@@ -1972,8 +1996,41 @@ PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs&
     acc[t] = s;
   }
 }
-// ... and the ones that read the history R.he / R.ho (slots 3..17 of the granule before); PCM
+// PCM of a stereo granule of k_decode_g, written THROUGH to memory in 16-byte pieces.  A launch of up to some thousand
+// frames leaves all its PCM in the L2s (2048 frames: 9.4 MB in 8 x 4 MB), and stored the plain way -- pcm_emit -- it is
+// still dirty there when the last wave ends: whatever comes behind the launch on the stream waits while it is written
+// back.  Written through, it leaves while the other waves of the launch still run.  Write-through stores pay per store, so
+// they are wide ones (2 1/4 per lane instead of 9): the lane's nine sample-frame pairs are 128 bytes apart in the granule,
+// so they are put in PCM order through the wave's own LDS first -- hyb, dead since ph_window_own took its slots and written
+// by no other wave (the mailboxes other waves fill are xr BEFORE ph_overlap_matrix, and spec .. scale) -- and come back
+// as 144 (float: 288) pieces of 16 bytes, lane l pieces l, 64 + l, ...  Same values, same places as pcm_emit<F32, true>.
 template <bool F32>
+PD_FN void pcm_emit_through(int lane, WaveData& L, const float* sum, int16_t* pcm_g, float* pcmf_g) {
+  static_assert(sizeof(L.hyb) >= 4608, "a granule's float PCM staged in hyb");
+  int out[18];
+  if (F32) { PD_UNROLL for (int t = 0; t < 18; t++) out[t] = (int)f2u(sum[t]); }
+  else pcm_convert18_lane(sum, out, pcm_wave_wraps(sum, true));
+  uint32_t* stage = reinterpret_cast<uint32_t*>(&L.hyb[0][0][0]);
+  PD_UNROLL for (int q = 0; q < 9; q++) {
+    int a = out[2 * q], b = out[2 * q + 1];
+    permlane32_swap(a, b);                    // (the pairing of pcm_emit)
+    if (F32) { stage[2 * (64 * q + lane)] = (uint32_t)a; stage[2 * (64 * q + lane) + 1] = (uint32_t)b; }
+    else stage[64 * q + lane] = ((unsigned)a & 0xffffu) | ((unsigned)b << 16);
+  }
+  PD_WAVE_SYNC();
+  constexpr int kBytes = F32 ? 4608 : 2304, kFull = kBytes / 1024, kRest = (kBytes - 1024 * kFull) / 16;
+  const Chunk16* pieces = reinterpret_cast<const Chunk16*>(stage);
+  Chunk16 v[kFull + 1];
+  v[kFull] = (Chunk16){0u, 0u, 0u, 0u};
+  PD_UNROLL for (int k = 0; k < kFull; k++) v[k] = pieces[64 * k + lane];
+  if (lane < kRest) v[kFull] = pieces[64 * kFull + lane];
+  const auto out16 = PD_RANGE16(F32 ? (void*)pcmf_g : (void*)pcm_g, kBytes);
+  PD_UNROLL for (int k = 0; k < kFull; k++) PD_STORE16_DEVICE(out16, 1024 * k + 16 * lane, v[k]);
+  if (lane < kRest) PD_STORE16_DEVICE(out16, 1024 * kFull + 16 * lane, v[kFull]);
+}
+// ... and the ones that read the history R.he / R.ho (slots 3..17 of the granule before); PCM
+// THROUGH: the PCM in 16-byte write-through stores (k_decode_g; the persistent kernel keeps pcm_emit)
+template <bool F32, bool THROUGH = false>
 PD_FN void ph_window_hist(int lane, WaveData& L, const LaneRegs& R, const float* acc, int16_t* pcm_g, float* pcmf_g) {
   float sum[18];
   PD_UNROLL for (int t = 0; t < 18; t++) {
@@ -1984,7 +2041,18 @@ PD_FN void ph_window_hist(int lane, WaveData& L, const LaneRegs& R, const float*
     }
     sum[t] = s;
   }
-  pcm_emit<F32, true>(lane, L, 2, true, sum, pcm_g, pcmf_g);
+  if (THROUGH && PD_GRAN_PCM_FORM == 1) pcm_emit_through<F32>(lane, L, sum, pcm_g, pcmf_g);
+  else if (THROUGH && PD_GRAN_PCM_FORM == 2 && !F32) {
+    // (timing probe: pcm_emit's nine dword stores, device scope)
+    int out[18];
+    pcm_convert18_lane(sum, out, pcm_wave_wraps(sum, true));
+    uint32_t* dst = reinterpret_cast<uint32_t*>(pcm_g);
+    PD_UNROLL for (int q = 0; q < 9; q++) {
+      int a = out[2 * q], b = out[2 * q + 1];
+      permlane32_swap(a, b);
+      PD_STORE_DEVICE(&dst[64 * q + lane], ((unsigned)a & 0xffffu) | ((unsigned)b << 16));
+    }
+  } else pcm_emit<F32, true>(lane, L, 2, true, sum, pcm_g, pcmf_g);
 }
 
 // run_chunk as a CALLED function, for the granule kernel's rare paths (frames that do not go the granule way; the state
@@ -2193,7 +2261,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
   }
   (void)from_chain;
   PD_GT(10)
-  if (PD_EXP_SKIP & 32) { a.pcm[(size_t)f * 2304 + gr * 1152 + lane] = (int16_t)(acc[0] + acc[17] + R.he[0] + R.ho[14]); } else { PD_PHASE(ph_window_hist<F32>(lane, L, R, acc, a.pcm + (size_t)f * 2304 + gr * 1152, F32 ? a.pcm_f32 + (size_t)f * 2304 + gr * 1152 : nullptr)) }
+  if (PD_EXP_SKIP & 32) { a.pcm[(size_t)f * 2304 + gr * 1152 + lane] = (int16_t)(acc[0] + acc[17] + R.he[0] + R.ho[14]); } else { PD_PHASE((ph_window_hist<F32, !RING>(lane, L, R, acc, a.pcm + (size_t)f * 2304 + gr * 1152, F32 ? a.pcm_f32 + (size_t)f * 2304 + gr * 1152 : nullptr))) }
   PD_GT(11)
 #undef PD_GT
 }
