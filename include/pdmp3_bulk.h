@@ -814,8 +814,8 @@ int pdmp3_amd_bulk_decode_clips_chroma(pdmp3_amd_bulk* b, const pdmp3_amd_audio_
  * A clip of a replay or mixed-format stream is reported as in the other calls, and its rows of audio, stats and momentary stay
  * untouched.  A clip wholly behind the end gives [-inf, -inf, 0, 1, -inf, J, 0, 0], audio exactly +0.
  *
- * Not offered: short-term (3 s) loudness and loudness range, true peak (4x oversampled), more than two channels, measuring
- * across clip boundaries with the stream's real history, torchaudio's coefficient variant. */
+ * Not offered: more than two channels, measuring across clip boundaries with the stream's real history, torchaudio's
+ * coefficient variant.  True peak, short-term loudness and loudness range: pdmp3_amd_bulk_decode_clips_r128 below. */
 typedef struct {
   long rate; int channels; long long n_samples; int width; double rolloff;      /* pdmp3_amd_audio_spec's */
   double target;            /* LUFS in [-70, 0]; NaN: no gain */
@@ -842,6 +842,57 @@ int pdmp3_amd_loudness_plan(long fs, long long n_samples, int* B, int* chunk, un
  * as pdmp3_amd_bulk_decode_clips_audio; the kernels are csrc/loudness.hip's.  -1 also where pdmp3_amd_loudness_check says so. */
 int pdmp3_amd_bulk_decode_clips_loudness(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
                                          float* stats, float* momentary, long long* valid);
+
+/* ---- True peak, short-term loudness and loudness range of clips (EBU R128, Tech 3341 / 3342) ----
+ * The other three descriptors of R128 beside the loudness call's, and the gain held to the true peak: audio [K][C][T] float32,
+ * stats [K][16] float32, optionally momentary [K][Jmax] and short_term [K][Jsmax] float32.  New entry points only; the loudness
+ * call and everything above return what they return without them.  The definition, to be evaluated in binary64 on the binary32
+ * row x_c[t] that pdmp3_amd_bulk_decode_clips_audio returns; everything of the loudness call's items 1-4 holds unchanged: q,
+ * s_c[i], I, z_j, l_j, A, Gamma, Gt, L, M, P.
+ *
+ * 1. Interpolator.  49 taps, factor 4 -- libebur128's own formula, the library whose K-weighting parametrisation the loudness
+ *    call follows.  For j = 0 .. 48, m = j - 24: h[j] = sinc4(m) 0.5 (1 - cos(2 pi j / 48)), sinc4(0) = 1, otherwise
+ *    sinc4(m) = sin(m pi / 4) / (m pi / 4).  A coefficient with |h[j]| < 1e-6 is exactly 0.  That leaves 37 coefficients: phase 0
+ *    is h[24] = 1 alone, a pure delay of 6 samples; phases 1-3 have 12 taps each, c_p[d] = h[4 d + p], d = 0 .. 11.  The sums of
+ *    |c_p| are 1, 1.63118, 1.86418, 1.63118; the DC gains 1, 1.00048, 1.00090, 1.00048.  The table of BS.1770-4 Annex 2 is a
+ *    different 48-tap design; it is not offered.  The factor is 4 at every accepted rate: libebur128 drops to 2 from 96 kHz up,
+ *    this call does not.
+ * 2. True peak.  y_c[4 t + p] = sum_d c_p[d] x_c[t - d] for t < T, from rest (x_c[t] = 0 for t < 0), with no flush behind T: a
+ *    clip is measured as a file holding just that clip.  TP = max_{c,t,p} |y_c[4 t + p]|.  Phase 0 only reproduces the samples,
+ *    so the device forms TP = max(P, peak of phases 1-3); TP >= P holds exactly.
+ * 3. Short-term loudness.  w_j = (1 / 30 q) sum_c G_c (s_c[j] + .. + s_c[j + 29]) for j < Js = max(0, I - 29);
+ *    S_j = -0.691 + 10 log10 w_j, and -inf at w_j = 0.  Smax = max_j S_j, and -inf when Js = 0.
+ * 4. Loudness range (Tech 3342, blocks every 1 s as libebur128 takes them).  R = {j = 10 m : j < Js}, Jr = |R| = ceil(Js / 10).
+ *    Ar = {j in R : S_j > -70}.  Gamma_r = -0.691 + 10 log10(mean_Ar w_j) - 20.  Gr = {j in Ar : S_j > Gamma_r}, n = |Gr|.  Sort S_j
+ *    over Gr ascending into v[0 .. n - 1]: LRA = v[(19 (n - 1) + 10) / 20] - v[(n + 4) / 10] with integer divisions, and LRA = 0
+ *    when n = 0.  The indices equal libebur128's (size_t)((n - 1) 0.95 + 0.5) and (size_t)((n - 1) 0.1 + 0.5) for every
+ *    n <= 200 000; the integer forms are used so that no product in binary64 decides an index.
+ * 5. Gain.  The loudness call's item 5 with P replaced by PM: PM = TP when limit_true_peak = 1, else P.
+ * 6. Outputs.  stats[k][16]: fields 0-7 are the loudness call's [L, M, P, g, Gamma, J, |A|, |Gt|], fields 8-15 are
+ *    [TP, Smax, LRA, Gamma_r, Js, Jr, |Ar|, |Gr|].  momentary[k][Jmax] as there.  short_term[k][Jsmax] = S_j, -inf from Js on,
+ *    Jsmax = max(0, T / q - 29).  audio = fl32(x g).  With limit_true_peak = 0, fields 0-7, momentary and audio are the
+ *    loudness call's bit for bit: the same arithmetic in the same order.
+ * 7. Refusals (-1, nothing written): whatever pdmp3_amd_loudness_check refuses; limit_true_peak outside {0, 1}; an n_samples
+ *    whose Jr > 4096 (about 68 minutes: the order statistic is taken inside one workgroup).  Refused, replayed and
+ *    mixed-format clips in a batch as in the loudness call.  A clip wholly behind the end gives that call's eight numbers, then
+ *    [0, -inf, 0, -inf, Js, Jr, 0, 0]. */
+typedef struct {
+  pdmp3_amd_loudness_spec loudness;
+  int limit_true_peak;      /* 1: g PM <= peak_limit with PM the true peak; 0: the sample peak */
+} pdmp3_amd_r128_spec;
+/* 0 when the call would accept these numbers (n_samples among them) at fs and `channels` (1 or 2) channels, else -1 (item 7) */
+int pdmp3_amd_r128_check(const pdmp3_amd_r128_spec* spec, long fs, int channels);
+/* The interpolator: h[49] in binary64, and phases [3][12] binary32, c_p[d] of phases 1 .. 3 as the kernel reads them, rounded
+ * once.  Pointers may be NULL.  0. */
+int pdmp3_amd_r128_taps(double* h, float* phases);
+/* pdmp3_amd_loudness_plan's numbers, then Js, Jr and Jsmax.  Pointers may be NULL.  0, or -1 (there, and where Jr > 4096). */
+int pdmp3_amd_r128_plan(long fs, long long n_samples, int* B, int* chunk, unsigned* lds_bytes, int* q, long long* n_chunks, long long* I,
+                        long long* J, long long* Js, long long* Jr, long long* Jsmax);
+/* As pdmp3_amd_bulk_decode_clips_loudness with stats [n_clips][16] floats and short_term: NULL, or [n_clips][Jsmax] floats, host
+ * memory or device memory of the decoder's GPU.  The kernels are csrc/loudness.hip's, k_loud_blocks and k_loud_gate in their
+ * second instantiation.  -1 also where pdmp3_amd_r128_check says so. */
+int pdmp3_amd_bulk_decode_clips_r128(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_r128_spec* spec,
+                                     float* stats, float* momentary, float* short_term, long long* valid);
 
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the

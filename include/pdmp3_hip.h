@@ -719,6 +719,26 @@ typedef struct pdmp3_loud_params {
 int pdmp3_hip_clip_loudness(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_loud_tables* tables,
                             const uint64_t* stats_dst, const uint64_t* mom_dst, const pdmp3_loud_params* params);
 
+/* True peak, short-term loudness and loudness range of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_r128; DESIGN.md
+ * section 19): the loudness call's five kernels, two of them in their second instantiation (loudness.hip):
+ *   k_loud_blocks<true>  besides the K-weighting, phases 1-3 of the 4x interpolator as banded Toeplitz products on the same
+ *                        operands: 84 more v_mfma_f32_16x16x4_f32 a wave; max |y| into a second maximum a wave (part: 8 floats)
+ *   k_loud_gate<true>    besides L, M, P: TP, the 3 s windows S_j, Smax, the two gates of the range and its two order
+ *                        statistics by counting in LDS (n_rng <= PDMP3_R128_MAX_RANGE); the gain held to TP or P
+ * k_loud_states, k_loud_chain and k_loud_scale are the loudness call's. */
+#define PDMP3_R128_TAPS 12                  /* taps of a phase of the interpolator                                        */
+#define PDMP3_R128_MAX_RANGE 4096           /* 3 s windows a second apart that k_loud_gate<true> ranks in LDS             */
+typedef struct pdmp3_r128_params {
+  pdmp3_loud_params loud;
+  int32_t n_st, n_rng;                      /* Js = max(0, I - 29); Jr = ceil(Js / 10) <= PDMP3_R128_MAX_RANGE            */
+  int32_t limit_true_peak, reserved;        /* 1: the gain is held to TP, 0: to P                                        */
+} pdmp3_r128_params;
+/* taps: [3][PDMP3_R128_TAPS] floats, c_p[d] of phases 1 .. 3.  stats_dst[i], mom_dst[i], st_dst[i]: the device addresses of
+ * clip i's 16 floats, (or 0) n_mom floats and (or 0) n_st floats.  Blocks until all is written. */
+int pdmp3_hip_clip_r128(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_loud_tables* tables,
+                        const float* taps, const uint64_t* stats_dst, const uint64_t* mom_dst, const uint64_t* st_dst,
+                        const pdmp3_r128_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

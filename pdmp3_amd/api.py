@@ -32,7 +32,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_cqt_check", "pdmp3_amd_cqt_lengths", "pdmp3_amd_cqt_table", "pdmp3_amd_cqt_plan", "pdmp3_amd_bulk_decode_clips_cqt",
                 "pdmp3_amd_chroma_check", "pdmp3_amd_chroma_map", "pdmp3_amd_chroma_plan", "pdmp3_amd_bulk_decode_clips_chroma",
                 "pdmp3_amd_loudness_check", "pdmp3_amd_loudness_coefficients", "pdmp3_amd_loudness_tables", "pdmp3_amd_loudness_plan",
-                "pdmp3_amd_bulk_decode_clips_loudness"]
+                "pdmp3_amd_bulk_decode_clips_loudness",
+                "pdmp3_amd_r128_check", "pdmp3_amd_r128_taps", "pdmp3_amd_r128_plan", "pdmp3_amd_bulk_decode_clips_r128"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -202,6 +203,11 @@ def load_library():
         lib.pdmp3_amd_loudness_tables.argtypes = [C.c_long, vp, vp, vp, vp, vp]
         lib.pdmp3_amd_loudness_plan.argtypes = [C.c_long, ll] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint), C.POINTER(C.c_int)] + [C.POINTER(ll)] * 3
         lib.pdmp3_amd_bulk_decode_clips_loudness.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_r128"):         # (true peak, short-term loudness, loudness range: absent from older builds)
+        lib.pdmp3_amd_r128_check.argtypes = [vp, C.c_long, C.c_int]
+        lib.pdmp3_amd_r128_taps.argtypes = [vp, vp]
+        lib.pdmp3_amd_r128_plan.argtypes = [C.c_long, ll] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint), C.POINTER(C.c_int)] + [C.POINTER(ll)] * 6
+        lib.pdmp3_amd_bulk_decode_clips_r128.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
     _LIB = lib
     return lib
 
@@ -981,6 +987,45 @@ def loudness_plan(sample_rate, n_samples):
     return b.value, ch.value, lds.value, q.value, nc.value, i.value, j.value
 
 
+class _R128Spec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_r128_spec
+    _fields_ = [("loudness", _LoudnessSpec), ("limit_true_peak", C.c_int)]
+
+
+def _r128_spec(n_samples=0, sample_rate=0, channels=0, target=None, peak_limit=0.0, limit_true_peak=True, dual_mono=False, width=0, rolloff=0.0):
+    return _R128Spec(_loudness_spec(n_samples, sample_rate, channels, target, peak_limit, dual_mono, width, rolloff), int(limit_true_peak))
+
+
+def r128_check(sample_rate, channels=1, **kw):
+    """pdmp3_amd_r128_check -> True when pdmp3_amd_bulk_decode_clips_r128 would accept these numbers (decode_clips_r128's n_samples,
+    target, peak_limit, limit_true_peak, dual_mono) at sample_rate and `channels` channels"""
+    try:
+        spec = _r128_spec(sample_rate=sample_rate, channels=channels, **kw)
+    except (ValueError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_r128_check(C.byref(spec), int(sample_rate), int(channels)) == 0
+
+
+def r128_taps():
+    """pdmp3_amd_r128_taps -> (h float64 [49], the 4x interpolator; phases float32 [3, 12], c_p[d] = h[4 d + p] of p = 1 .. 3 as
+    the kernel reads them)"""
+    h, ph = np.zeros(49, dtype=np.float64), np.zeros((3, 12), dtype=np.float32)
+    if load_library().pdmp3_amd_r128_taps(h.ctypes.data, ph.ctypes.data) != 0:
+        raise ValueError("pdmp3_amd_r128_taps failed")
+    return h, ph
+
+
+def r128_plan(sample_rate, n_samples):
+    """pdmp3_amd_r128_plan -> loudness_plan's seven numbers, then Js (3 s windows), Jr (those of the range) and Jsmax (floats of a
+    row of short_term)"""
+    b, ch, q = C.c_int(0), C.c_int(0), C.c_int(0)
+    lds = C.c_uint(0)
+    v = [C.c_longlong(0) for _ in range(6)]
+    if load_library().pdmp3_amd_r128_plan(int(sample_rate), int(n_samples), C.byref(b), C.byref(ch), C.byref(lds), C.byref(q),
+                                           *[C.byref(x) for x in v]) != 0:
+        raise ValueError("pdmp3_amd_r128_plan: bad argument")
+    return (b.value, ch.value, lds.value, q.value) + tuple(x.value for x in v)
+
+
 class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
                 ("chan_stride", C.c_size_t)]
@@ -1332,6 +1377,51 @@ class BulkDecoder:
         spec = lambda: (_loudness_spec(t, sample_rate, channels, target, peak_limit, dual_mono, width, rolloff), None)
         try:
             audio, valid = self._clips_call("loudness", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError), extra=(sp, mp))
+        except (RingReplay, MixedFormat) as e:
+            e.stats = stats
+            raise
+        return audio, stats, valid
+
+    def decode_clips_r128(self, clips, n_samples, sample_rate=0, channels=0, target=-23.0, peak_limit=10 ** (-1 / 20), limit_true_peak=True,
+                          dual_mono=False, width=0, rolloff=0.0, out=None, momentary=None, short_term=None):
+        """pdmp3_amd_bulk_decode_clips_r128: decode_clips_loudness with EBU R128's other descriptors and the gain held to the true
+        peak -> (audio, stats, valid).  stats float32 [K, 16]: fields 0-7 as decode_clips_loudness's [L, M, P, g, Gamma, J, |A|,
+        |Gt|], fields 8-15 = true peak TP (4x oversampled, libebur128's 49-tap interpolator), maximum short-term loudness Smax,
+        loudness range LRA (LU), the range's relative threshold, the 3 s windows Js, those a second apart Jr, those above the
+        range's absolute gate, those above both.  g = 10^((target - L) / 20), held to peak_limit / TP where peak_limit > 0 (to
+        peak_limit / P with limit_true_peak=False, which makes fields 0-7, momentary and audio decode_clips_loudness's bit for
+        bit); target=None: no gain.  The defaults are R128's: -23 LUFS under -1 dBTP.  momentary as there; short_term: None, or a
+        float32 [K, Jsmax] destination for the window loudnesses S_j, Jsmax = max(0, n_samples // q - 29).  A clip's filters
+        start from rest at its first sample.  Rows of stats belonging to clips that raise RingReplay / MixedFormat stay NaN."""
+        t, k = int(n_samples), len(clips)
+        if out is None or hasattr(out, "data_ptr"):
+            import torch
+            stats = torch.full((k, 16), float("nan"), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
+            torch.cuda.synchronize()
+            sp = stats.data_ptr()
+        else:
+            stats = np.full((k, 16), np.nan, dtype=np.float32)
+            sp = stats.ctypes.data
+        ptrs = []
+        for name, dst, field in (("momentary", momentary, 6), ("short_term", short_term, 9)):
+            if dst is None:
+                ptrs.append(None)
+                continue
+            torch_like = hasattr(dst, "data_ptr")
+            ok = (dst.is_contiguous() and str(dst.dtype) == "torch.float32") if torch_like else (dst.flags["C_CONTIGUOUS"] and dst.dtype == np.float32)
+            assert ok and len(dst.shape) == 2 and dst.shape[0] >= k, "%s: float32 [>= K, n], contiguous" % name
+            rates = set(ix.rate for _, ix, _ in clips if not ix.replay and ix.one_format and ix.frames)
+            fs = int(sample_rate) or (rates.pop() if len(rates) == 1 else 0)
+            if fs and t:                           # (else the library refuses the call, or writes nothing)
+                try:
+                    n = r128_plan(fs, t)[field]
+                except ValueError:
+                    raise RuntimeError("pdmp3_amd_bulk_decode_clips_r128: bad sample_rate or n_samples")
+                assert dst.shape[1] == n, "%s: float32 [>= K, %d]" % (name, n)
+            ptrs.append(dst.data_ptr() if torch_like else dst.ctypes.data)
+        spec = lambda: (_r128_spec(t, sample_rate, channels, target, peak_limit, limit_true_peak, dual_mono, width, rolloff), None)
+        try:
+            audio, valid = self._clips_call("r128", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError), extra=(sp, ptrs[0], ptrs[1]))
         except (RingReplay, MixedFormat) as e:
             e.stats = stats
             raise

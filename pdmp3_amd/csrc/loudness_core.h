@@ -62,27 +62,32 @@ MEL_FN void loud_square(float y, long long t, long long edge, int bin0, float p[
   p[2] = bin == 2 ? p[2] + sq : p[2];
 }
 
-// s_c[i] of a row from its waves' partial sums part[wave][4] = {bin 0, bin 1, bin 2, peak}: the waves that hold samples of
-// [i q, (i + 1) q) in ascending order, from the first one on by plain additions
-MEL_FN float loud_sub_sum(const float* part, long long i, int q) {
+// s_c[i] of a row from its waves' partial sums part[wave][stride] = {bin 0, bin 1, bin 2, peak, ..}: the waves that hold samples
+// of [i q, (i + 1) q) in ascending order, from the first one on by plain additions
+MEL_FN float loud_sub_sum(const float* part, long long i, int q, int stride = 4) {
   const long long w0 = i * q / kLoudWave, w1 = ((i + 1) * q - 1) / kLoudWave;
   float s = 0.0f;
   for (long long w = w0; w <= w1; w++) {
-    const float v = part[w * 4 + (i - w * kLoudWave / q)];
+    const float v = part[w * stride + (i - w * kLoudWave / q)];
     s = w == w0 ? v : s + v;
   }
   return s;
 }
-// z_j from the sub-block sums sub[c][n_sub], binary64: ((s_j + s_j+1) + s_j+2) + s_j+3 per channel, times G_c, channels added,
-// over 4 q
-MEL_FN double loud_z(const float* sub, int n_sub, int channels, int dual_mono, long long j, int q) {
+// the mean square of the window of n sub-blocks from j on, from the sub-block sums sub[c][n_sub], binary64:
+// (((s_j + s_j+1) + s_j+2) + ..) + s_j+n-1 per channel, times G_c, channels added, over n q
+MEL_FN double loud_zn(const float* sub, int n_sub, int channels, int dual_mono, long long j, int q, int n) {
   double z = 0.0;
   for (int c = 0; c < channels; c++) {
     const float* s = sub + (size_t)c * (size_t)n_sub + j;
-    const double a = (((double)s[0] + (double)s[1]) + (double)s[2]) + (double)s[3];
+    double a = (double)s[0] + (double)s[1];
+    for (int i = 2; i < n; i++) a += (double)s[i];
     z = c == 0 ? (dual_mono ? 2.0 * a : a) : z + a;
   }
-  return z / (4.0 * (double)q);
+  return z / ((double)n * (double)q);
+}
+// z_j: the window of four
+MEL_FN double loud_z(const float* sub, int n_sub, int channels, int dual_mono, long long j, int q) {
+  return loud_zn(sub, n_sub, channels, dual_mono, j, q, 4);
 }
 MEL_FN double loud_l(double z) { return z > 0.0 ? -0.691 + 10.0 * log10(z) : -INFINITY; }
 // g of a clip: 1 without a target or without a loudness; else 10^((target - L) / 20), held to peak_limit / P

@@ -920,6 +920,46 @@ extern "C" int pdmp3_hip_clip_loudness(pdmp3_hip_stream* hs, int slot, const pdm
                                                       reinterpret_cast<float*>(part[7]), &P);
                   });
 }
+// ---- true peak, short-term loudness and loudness range (loudness.hip, the second instantiations) ----
+extern "C" int pdmp3_hip_clip_r128(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_loud_tables* tables,
+                                   const float* taps, const uint64_t* stats_dst, const uint64_t* mom_dst, const uint64_t* st_dst,
+                                   const pdmp3_r128_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && (!descs || !stats_dst || !mom_dst || !st_dst)) || !tables || !taps || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_r128: bad argument", hipSuccess);
+  const pdmp3_loud_params& P = params->loud;
+  // what the kernels' indexing relies on
+  const int n_st = P.n_sub > 29 ? P.n_sub - 29 : 0;
+  if (P.n_in < 0 || P.n_in > 0x7fffffffLL || (P.channels != 1 && P.channels != 2) || P.q < 800 || P.q > 19200 ||
+      P.n_chunks != (P.n_in + PDMP3_LOUD_B * PDMP3_LOUD_CHUNK - 1) / (PDMP3_LOUD_B * PDMP3_LOUD_CHUNK) || P.n_sub != P.n_in / P.q ||
+      P.n_mom != (P.n_sub > 3 ? P.n_sub - 3 : 0) || (P.dual_mono != 0 && (P.dual_mono != 1 || P.channels != 1)) || !(P.peak_limit >= 0.0) ||
+      params->n_st != n_st || params->n_rng != (n_st + 9) / 10 || params->n_rng > PDMP3_R128_MAX_RANGE || (params->limit_true_peak & ~1))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_r128: bad parameters", hipSuccess);
+  for (int k = 0; k < n_clips; k++)
+    if (!descs[k].src || !descs[k].dst || (descs[k].src & 15u) || (descs[k].src_chan_stride & 3u) || !stats_dst[k] ||
+        (P.channels == 2 && (descs[k].src_chan_stride < (uint64_t)P.n_in || descs[k].dst_chan_stride < (uint64_t)P.n_in)))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_r128: a clip's rows are not where the kernels can take them", hipSuccess);
+  // descriptors | tables | taps | destinations of stats, of momentary, of short-term | states | chunk starts | partial results
+  // (8 floats a wave) | sub-block sums | gains
+  const size_t rows = (size_t)n_clips * (size_t)P.channels, chunks = rows * (size_t)P.n_chunks;
+  return clip_run(hs, slot, "pdmp3_hip_clip_r128", descs, n_clips, P.n_in,
+                  {{ClipPart::kUpload, tables, sizeof *tables},
+                   {ClipPart::kUpload, taps, 3 * PDMP3_R128_TAPS * sizeof(float)},
+                   {ClipPart::kUpload, stats_dst, (size_t)n_clips * sizeof(uint64_t)},
+                   {ClipPart::kUpload, mom_dst, (size_t)n_clips * sizeof(uint64_t)},
+                   {ClipPart::kUpload, st_dst, (size_t)n_clips * sizeof(uint64_t)},
+                   {ClipPart::kScratch, nullptr, chunks * PDMP3_LOUD_CHUNK * 4 * sizeof(double)},
+                   {ClipPart::kScratch, nullptr, chunks * 4 * sizeof(double)},
+                   {ClipPart::kScratch, nullptr, chunks * 32 * sizeof(float)},
+                   {ClipPart::kScratch, nullptr, rows * (size_t)P.n_sub * sizeof(float)},
+                   {ClipPart::kScratch, nullptr, (size_t)n_clips * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int k, uint8_t* const* part) {
+                    return pdmp3_launch_clip_r128(hs->s[slot].stream, dk, nk, k, reinterpret_cast<const pdmp3_loud_tables*>(part[0]), as_floats(part[1]),
+                                                  reinterpret_cast<const uint64_t*>(part[2]), reinterpret_cast<const uint64_t*>(part[3]),
+                                                  reinterpret_cast<const uint64_t*>(part[4]), reinterpret_cast<double*>(part[5]),
+                                                  reinterpret_cast<double*>(part[6]), reinterpret_cast<float*>(part[7]),
+                                                  reinterpret_cast<float*>(part[8]), reinterpret_cast<float*>(part[9]), params);
+                  });
+}
 extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {
   if (!bytes) return PDMP3_HIP_OK;
   if (!host_dst || !dev_src) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_copy_from_device: NULL", hipSuccess);

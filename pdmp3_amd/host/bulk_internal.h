@@ -401,6 +401,9 @@ HOST_LOCAL int chroma_plan(const pdmp3_amd_chroma_spec* s, long sr, pdmp3_chroma
 HOST_LOCAL void loud_tables_fill(long fs, pdmp3_loud_tables* t);
 HOST_LOCAL const pdmp3_loud_tables* loud_tables(struct bulk* b, long fs);
 HOST_LOCAL int loud_plan(long fs, long long n_samples, pdmp3_loud_params* p);
+/* clip_r128.c: loud_plan's geometry with the short-term windows and the range's (0, or -1: also where the range has more windows
+ * than k_loud_gate<true> ranks) */
+HOST_LOCAL int r128_plan(long fs, long long n_samples, pdmp3_r128_params* p);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness; DESIGN.md sections 9-18).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128; DESIGN.md sections 9-19).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -594,26 +594,33 @@ static int copy_floats_out(float* dst, const float* stage, const int* clip_of, i
   return 0;
 }
 
-int pdmp3_amd_bulk_decode_clips_loudness(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
-                                         float* stats, float* momentary, long long* valid) {
+/* the loudness call (r128 == NULL) and the true-peak call (spec == &r128->loudness): they differ in the
+ * check and plan, the floats of a row of stats (8 or 16), the short-term destination and the launch */
+static int loud_clips(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
+                      const pdmp3_amd_r128_spec* r128, float* stats, float* momentary, float* short_term, long long* valid) {
   clip_course cc;
   if (!spec || course_begin(&cc, b, clips, n_clips, valid, spec->n_samples, spec->channels, spec->rate, spec->width, spec->rolloff) != 0) return -1;
-  if ((n_clips && !stats) || pdmp3_amd_loudness_check(spec, cc.sr, cc.C) != 0) return -1;
-  pdmp3_loud_params P;
-  if (loud_plan(cc.sr, spec->n_samples, &P) != 0) return -1;
+  if ((n_clips && !stats) || (r128 ? pdmp3_amd_r128_check(r128, cc.sr, cc.C) : pdmp3_amd_loudness_check(spec, cc.sr, cc.C)) != 0) return -1;
+  pdmp3_r128_params Q;
+  pdmp3_loud_params* const P = &Q.loud;
+  if ((r128 ? r128_plan(cc.sr, spec->n_samples, &Q) : loud_plan(cc.sr, spec->n_samples, P)) != 0) return -1;
   if (course_rows(&cc, 1, 1, 1, 0) != 0) return course_finish(&cc, -1);
   if (!cc.nd) return course_finish(&cc, cc.rc);
-  const size_t J = (size_t)P.n_mom;
+  const size_t J = (size_t)P->n_mom, Js = r128 ? (size_t)Q.n_st : 0, S = r128 ? 16 : 8;
   if (!J) momentary = NULL;
-  const int stats_dev = pdmp3_hip_host_is_pinned(stats, (size_t)n_clips * 8 * sizeof(float)) == 2;
+  if (!Js) short_term = NULL;
+  const int stats_dev = pdmp3_hip_host_is_pinned(stats, (size_t)n_clips * S * sizeof(float)) == 2;
   const int mom_dev = momentary && pdmp3_hip_host_is_pinned(momentary, (size_t)n_clips * J * sizeof(float)) == 2;
+  const int st_dev = short_term && pdmp3_hip_host_is_pinned(short_term, (size_t)n_clips * Js * sizeof(float)) == 2;
   const size_t stat_at = cc.out_floats;
-  if (!stats_dev) cc.out_floats += (size_t)cc.nd * 8;
+  if (!stats_dev) cc.out_floats += (size_t)cc.nd * S;
   const size_t mom_at = cc.out_floats;
   if (momentary && !mom_dev) cc.out_floats += (size_t)cc.nd * J;
+  const size_t st_at = cc.out_floats;
+  if (short_term && !st_dev) cc.out_floats += (size_t)cc.nd * Js;
   const pdmp3_loud_tables* tab = loud_tables(b, cc.sr);
   int* clip_of = (int*)calloc((size_t)cc.nd, sizeof *clip_of);                 /* the clip of every descriptor */
-  uint64_t* at = (uint64_t*)calloc(2 * (size_t)cc.nd, sizeof *at);             /* where its stats go on the device, where its momentary values */
+  uint64_t* at = (uint64_t*)calloc(3 * (size_t)cc.nd, sizeof *at);             /* where its stats go on the device, its momentary, its short-term values */
   int rc = -1;
   if (!tab || !clip_of || !at || course_signal(&cc) != 0) goto out;
   float* const stage = cc.out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, cc.out_floats * sizeof(float)) : NULL;
@@ -621,16 +628,36 @@ int pdmp3_amd_bulk_decode_clips_loudness(struct bulk* b, const pdmp3_amd_audio_c
   for (int k = 0, i = 0; k < n_clips; k++) {
     if (clips[k].index->frames < 0 || clips[k].index->mixed) continue;
     clip_of[i] = k;
-    at[i] = (uint64_t)(uintptr_t)(stats_dev ? stats + (size_t)k * 8 : stage + stat_at + (size_t)i * 8);
+    at[i] = (uint64_t)(uintptr_t)(stats_dev ? stats + (size_t)k * S : stage + stat_at + (size_t)i * S);
     at[cc.nd + i] = !momentary ? 0 : (uint64_t)(uintptr_t)(mom_dev ? momentary + (size_t)k * J : stage + mom_at + (size_t)i * J);
+    at[2 * cc.nd + i] = !short_term ? 0 : (uint64_t)(uintptr_t)(st_dev ? short_term + (size_t)k * Js : stage + st_at + (size_t)i * Js);
     i++;
   }
-  P.channels = cc.C; P.dual_mono = spec->dual_mono; P.target = spec->target; P.peak_limit = spec->peak_limit;
-  if (course_launched(pdmp3_hip_clip_loudness(b->hs, CLIP_SLOT, cc.ds, cc.nd, tab, at, at + cc.nd, &P)) != 0) goto out;
-  if (!stats_dev && copy_floats_out(stats, stage + stat_at, clip_of, cc.nd, 8) != 0) goto out;
+  P->channels = cc.C; P->dual_mono = spec->dual_mono; P->target = spec->target; P->peak_limit = spec->peak_limit;
+  if (r128) {
+    float taps[3 * PDMP3_R128_TAPS];
+    pdmp3_amd_r128_taps(NULL, taps);
+    Q.limit_true_peak = r128->limit_true_peak;
+    if (course_launched(pdmp3_hip_clip_r128(b->hs, CLIP_SLOT, cc.ds, cc.nd, tab, taps, at, at + cc.nd, at + 2 * cc.nd, &Q)) != 0) goto out;
+  } else if (course_launched(pdmp3_hip_clip_loudness(b->hs, CLIP_SLOT, cc.ds, cc.nd, tab, at, at + cc.nd, P)) != 0) goto out;
+  if (!stats_dev && copy_floats_out(stats, stage + stat_at, clip_of, cc.nd, S) != 0) goto out;
   if (momentary && !mom_dev && copy_floats_out(momentary, stage + mom_at, clip_of, cc.nd, J) != 0) goto out;
+  if (short_term && !st_dev && copy_floats_out(short_term, stage + st_at, clip_of, cc.nd, Js) != 0) goto out;
   rc = cc.rc;
 out:
   free(clip_of); free(at);
   return course_finish(&cc, rc);
+}
+
+int pdmp3_amd_bulk_decode_clips_loudness(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_loudness_spec* spec,
+                                         float* stats, float* momentary, long long* valid) {
+  return loud_clips(b, clips, n_clips, spec, NULL, stats, momentary, NULL, valid);
+}
+
+/* ---- true peak, short-term loudness and loudness range of clips: the loudness call's course with the
+ * short-term values a third destination beside the rows ---- */
+int pdmp3_amd_bulk_decode_clips_r128(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_r128_spec* spec,
+                                     float* stats, float* momentary, float* short_term, long long* valid) {
+  if (!spec) return -1;
+  return loud_clips(b, clips, n_clips, &spec->loudness, spec, stats, momentary, short_term, valid);
 }

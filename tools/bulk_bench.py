@@ -775,8 +775,11 @@ def clips_chroma(args, api):
     print(json.dumps(res))
 
 
-def clips_loudness(args, api):
-    """--loudness: 64 clips of 30 s (--clips / --clip-frames change that) at 32 000 Hz stereo in device memory, two ways, run after
+def clips_loudness(args, api, r128=False):
+    """--r128: --loudness's batch and routes with a third one in the rotation, (c) pdmp3_amd_bulk_decode_clips_r128 for the same
+    clips with the same target under -1 dBTP (audio times the gain, stats of 16, no curves): true peak, short-term loudness
+    and loudness range on top of (b).  (c) minus (b) is reported, not capped (profiles/clip_r128.txt).
+    --loudness: 64 clips of 30 s (--clips / --clip-frames change that) at 32 000 Hz stereo in device memory, two ways, run after
     run in turn: (a) pdmp3_amd_bulk_decode_clips_audio; (b) pdmp3_amd_bulk_decode_clips_loudness for the same clips with target
     -14 LUFS (audio times the gain, stats, no momentary curve).  There is no torch route to hold against: torch without
     torchaudio has no recursive filter.  (b) minus (a) is reported, not capped.  The kernels' own times come from a
@@ -805,9 +808,10 @@ def clips_loudness(args, api):
     dev = "cuda:0"
     out_a = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
     out_b = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 2, T), dtype=torch.float32, device=dev) if r128 else None
     dec = api.BulkDecoder(threads=args.clip_threads)
     torch.cuda.synchronize()
-    stats = [None]
+    stats = [None, None]
 
     def audio_route():
         dec.decode_clips_audio(clips, T, rate, 2, out=out_a)
@@ -815,11 +819,14 @@ def clips_loudness(args, api):
     def loudness_route():
         stats[0] = dec.decode_clips_loudness(clips, T, rate, 2, target=target, out=out_b)[1]
 
-    routes = [("audio clips", audio_route), ("loudness clips", loudness_route)]
+    def r128_route():
+        stats[1] = dec.decode_clips_r128(clips, T, rate, 2, target=target, out=out_c)[1]
+
+    routes = [("audio clips", audio_route), ("loudness clips", loudness_route)] + ([("r128 clips", r128_route)] if r128 else [])
     times = {name: [] for name, _ in routes}
     seen = None
     for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 2:] + routes[:r % 2]:
+        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
             t0 = time.perf_counter()
             fn()
             dt = time.perf_counter() - t0
@@ -831,6 +838,13 @@ def clips_loudness(args, api):
             seen = {"audio_is_x_times_g": bool(torch.equal(out_b, out_a * stats[0][:, 3].view(K, 1, 1))), "clips_with_a_loudness": int(fin.sum()),
                     "L_min": float(st[fin, 0].min()) if fin.any() else None, "L_max": float(st[fin, 0].max()) if fin.any() else None,
                     "g_min": float(st[:, 3].min()), "g_max": float(st[:, 3].max()), "blocks": int(st[0, 5])}
+            if r128:
+                sr = stats[1].cpu().numpy()
+                seen.update({"r128_audio_is_x_times_g": bool(torch.equal(out_c, out_a * stats[1][:, 3].view(K, 1, 1))),
+                             "r128_first_three_are_the_loudness_calls": bool((sr[:, :3].view(np.uint32) == st[:, :3].view(np.uint32)).all()),
+                             "clips_held_to_the_true_peak": int((sr[:, 3] < st[:, 3]).sum()), "TP_over_P_max": float((sr[:, 8] / np.maximum(sr[:, 2], 1e-30)).max()),
+                             "TP_max": float(sr[:, 8].max()), "LRA_min": float(sr[:, 10].min()), "LRA_max": float(sr[:, 10].max()),
+                             "windows": int(sr[0, 12]), "range_windows": int(sr[0, 13])})
     dec.close()
     plan = api.loudness_plan(rate, T)
     res = {"workload": "%d clips of %d samples at %d Hz stereo, K-weighted, gated and scaled to %g LUFS: %s" % (
@@ -843,6 +857,8 @@ def clips_loudness(args, api):
                      "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["loudness_minus_audio_ms"] = round((med["loudness clips"] - med["audio clips"]) * 1e3, 3)
+    if r128:
+        res["r128_minus_loudness_ms"] = round((med["r128 clips"] - med["loudness clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
     for ix in ixs:
         ix.close()
@@ -1082,6 +1098,9 @@ def main():
     ap.add_argument("--loudness", action="store_true",
                     help="64 clips of 30 s (or --clips / --clip-frames) at 32 000 Hz stereo measured by ITU-R BS.1770 and scaled to -14 LUFS "
                          "(pdmp3_amd_bulk_decode_clips_loudness) against the audio call alone (see clips_loudness())")
+    ap.add_argument("--r128", action="store_true",
+                    help="--loudness's batch with pdmp3_amd_bulk_decode_clips_r128 (true peak, short-term loudness, loudness range, the gain "
+                         "held to -1 dBTP) as a third route beside the loudness call and the audio call (see clips_loudness())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1089,7 +1108,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1099,8 +1118,8 @@ def main():
             return clips_cqt(args, api)
         if args.chroma:
             return clips_chroma(args, api)
-        if args.loudness:
-            return clips_loudness(args, api)
+        if args.loudness or args.r128:
+            return clips_loudness(args, api, r128=args.r128)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
