@@ -894,6 +894,62 @@ int pdmp3_amd_r128_plan(long fs, long long n_samples, int* B, int* chunk, unsign
 int pdmp3_amd_bulk_decode_clips_r128(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_r128_spec* spec,
                                      float* stats, float* momentary, float* short_term, long long* valid);
 
+/* ---- Pitch of clips (YIN, de Cheveigne and Kawahara 2002, with librosa.yin's parameters) ----
+ * K clips as one planar float32 batch, frames innermost: f0, aperiodicity and lag [K][C][3][F], or the cumulative-mean-normalised
+ * difference curve [K][C][tmax + 1][F] that pYIN-style trackers start from.  New entry points only.  The definition is
+ * evaluated in binary64 on the binary32 row x_c[t] that pdmp3_amd_bulk_decode_clips_audio returns at the call's rate and
+ * channels (sections 13-19's convention).  N = frame_length, W = win_length (0: N / 2), H = hop (0: N / 4).
+ * 1. Framing, centred as the transform's: frame f of clip k is z[j] = x[start + f H - N / 2 + j], j = 0 .. N - 1; real
+ *    neighbours inside the stream, zeros outside, no reflection; valid[k] = clamp(ceil((J - start) / H), 0, F).
+ * 2. Lags.  tmin = max(1, floor(sr / fmax)), tmax = min(ceil(sr / fmin), N - W - 1), from integer arithmetic on the binary64
+ *    quotient q: where |q - round(q)| < 1e-9 the quotient must be that integer exactly (the divisor times it is sr without a
+ *    rounding error), else the spec is refused.
+ * 3. Difference function, tau = 0 .. tmax: r(tau) = sum over j < W of z[j] z[j + tau], e(tau) = sum over j < W of
+ *    z[j + tau]^2, d(tau) = e(0) + e(tau) - 2 r(tau) = sum over j < W of (z[j] - z[j + tau])^2  (r(0) = e(0)).
+ * 4. S(tau) = d(1) + .. + d(tau); d'(0) = 1; d'(tau) = d(tau) tau / S(tau) where S(tau) > 0, else 1.
+ * 5. Decision (librosa's) on [tmin, tmax]: tau is a trough when d'(tau) < d'(tau - 1) and d'(tau) <= d'(tau + 1); at tmin:
+ *    d'(tmin) < d'(tmin + 1); tmax is never one.  tau* = the smallest trough with d'(tau*) < threshold; if there is none, the
+ *    smallest tau of [tmin, tmax] that attains the minimum of d'.
+ * 6. With a = d'(tau* - 1), b = d'(tau*), c = d'(tau* + 1), D = a - 2 b + c: delta = (a - c) / (2 D) when tmin < tau* < tmax
+ *    and D > 0, else 0; f0 = sr / (tau* + delta).  A frame whose N samples are all zero gives f0 = 0, aperiodicity 1,
+ *    tau* = 0 exactly; its curve is 1 everywhere.
+ * 7. out_mode 0: [K][C][3][F], plane 0 f0, plane 1 d'(tau*), plane 2 tau*.  out_mode 1: [K][C][tmax + 1][F], d'(tau).  The
+ *    device takes decision and refinement on the binary32 curve values it stores in mode 1: plane 2 is rule 5 applied to the
+ *    mode-1 output of the same arguments, plane 1 is that curve at tau* bit for bit, plane 0 is rule 6 in binary64 on those
+ *    three binary32 values, rounded once (a frame of zeros excepted: rule 6's last sentence).
+ * Arithmetic.  r^ is a binary32 fused multiply-add chain over j ascending (v_mfma_f32_16x16x4_f32); e is a difference of two
+ * binary64 prefix sums of the exact squares; d, S (one fixed order) and d tau / S are binary64, d' is rounded once.  With
+ * u = 2^-24 and n = 4 ceil((W + 15) / 4): |r^ - r| <= (n u / (1 - n u)) sum |z[j] z[j + tau]|; section 20 derives the bounds
+ * of d, S, d' and f0 from it and says when a frame's decision is undecided against the binary64 definition.
+ * 8. Refusals (-1, nothing written): N odd or outside 64 .. 2048, W outside 4 .. N - 2, H outside 1 .. N, fmin <= 0,
+ *    fmax <= fmin, fmax > sr / 2, tmin >= tmax, threshold outside (0, 1], out_mode not 0 or 1, rule 2's, n_frames < 0, and
+ *    whatever the audio call refuses.  N = 4096 is left to a follow-up. */
+typedef struct {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec */
+  long long n_frames;
+  int frame_length, win_length, hop;                    /* N (2048); W, 0 = N / 2; H, 0 = N / 4 */
+  double fmin, fmax;                                    /* Hz */
+  double threshold;                                     /* 0.1 */
+  int out_mode;                                         /* 0: f0, aperiodicity, lag; 1: the curve */
+} pdmp3_amd_pitch_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1 (item 8) */
+int pdmp3_amd_pitch_check(const pdmp3_amd_pitch_spec* spec, long sr);
+/* *tmin, *tmax (item 2) and *tiles = ceil((tmax + 1) / 256), the lag tiles of a frame.  Pointers may be NULL.  0, or -1 where
+ * the check refuses the spec. */
+int pdmp3_amd_pitch_lags(const pdmp3_amd_pitch_spec* spec, long sr, int* tmin, int* tmax, int* tiles);
+/* What a workgroup of k_clip_pitch takes, the function the call itself uses: *frames (one a wave: 8, or 4, 2, 1 where the LDS
+ * below would pass 160 KB - 64), *span_floats (the span with its zeros around it, skewed by 2 floats every 16), *lds_bytes
+ * (the span, (frames - 1) H + N + 1 binary64 prefix sums, 64 frames + 64 binary64 scratch values, 256 tiles + 8 floats a
+ * frame for its curve, 4 a frame for its result) and *ksteps = ceil((W + 15) / 4), the matrix instructions a lag tile.  More
+ * than 64 KB runs in a kernel with a static array (k_clip_pitch_big).  Pointers may be NULL.  0, or -1 as the check. */
+int pdmp3_amd_pitch_plan(const pdmp3_amd_pitch_spec* spec, long sr, int* frames, unsigned* span_floats, unsigned* lds_bytes, int* ksteps);
+/* Row k receives channel c's [3][n_frames] (out_mode 1: [tmax + 1][n_frames]) floats at dst + c * chan_stride.  Everything
+ * else -- the audio call in front, the stages, host destinations, the per-clip refusals in valid[k], rate 0 / channels 0,
+ * width, rolloff, the counts, n_clips = 0 and n_frames = 0, synchronous -- as pdmp3_amd_bulk_decode_clips_stft; k_clip_pitch
+ * (csrc/pitch.hip) writes the rows and reads no table.  -1 also where pdmp3_amd_pitch_check says so. */
+int pdmp3_amd_bulk_decode_clips_pitch(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pitch_spec* spec,
+                                      long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

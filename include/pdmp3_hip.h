@@ -739,6 +739,30 @@ int pdmp3_hip_clip_r128(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* de
                         const float* taps, const uint64_t* stats_dst, const uint64_t* mom_dst, const uint64_t* st_dst,
                         const pdmp3_r128_params* params);
 
+/* Pitch of clips (YIN) (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_pitch).  k_clip_pitch (pitch.hip)
+ * reads the rows as k_clip_stft does (pdmp3_mel_desc) and writes [3][n_frames] (out_mode 0: f0, d'(tau*), tau*) or
+ * [tmax + 1][n_frames] (out_mode 1: the curve d') floats per channel, frames innermost.  A workgroup of frames_wg waves takes
+ * frames_wg consecutive frames of one (clip, channel), one frame a wave.  Its LDS, in this order (csrc/pitch_core.h has the
+ * indexing): span_floats floats for the span -- position x = p + 16 of it (p = 0: the first sample of the workgroup's first
+ * frame; 16 zeros in front, zeros behind the span up to `ext` positions) lies at x + 2 (x >> 4) --, q_doubles binary64 prefix
+ * sums of squares, 64 binary64 scratch values a wave, 256 tiles floats a wave for its curve, 4 floats a wave for its result. */
+typedef struct pdmp3_pitch_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  double sr, threshold;                     /* the call's sampling frequency; the trough threshold                      */
+  int32_t n, win, hop;                      /* N, W, H                                                                  */
+  int32_t tmin, tmax;                       /* the lag range                                                            */
+  int32_t tiles, ksteps;                    /* lag tiles of 256: ceil((tmax + 1) / 256) <= 8; ceil((W + 15) / 4)         */
+  int32_t n_frames, frames_wg;              /* F; frames (waves) of a workgroup: 8, 4, 2 or 1                           */
+  int32_t channels, out_mode;
+  uint32_t ext;                             /* positions of the span region that are written: 16 + the span + its padding */
+  uint32_t span_floats;                     /* LDS floats of the span region, a multiple of 4                           */
+  uint32_t q_doubles;                       /* (frames_wg - 1) H + N + 1                                                */
+  uint32_t lds_bytes;
+} pdmp3_pitch_params;
+/* Uploads the descriptors -- host memory -- and runs k_clip_pitch on the slot's HIP stream.  The LDS limits are the log-mel
+ * call's (PDMP3_MEL_LDS_SOFT / _MAX).  Blocks until the rows are written. */
+int pdmp3_hip_clip_pitch(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_pitch_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -33,7 +33,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_chroma_check", "pdmp3_amd_chroma_map", "pdmp3_amd_chroma_plan", "pdmp3_amd_bulk_decode_clips_chroma",
                 "pdmp3_amd_loudness_check", "pdmp3_amd_loudness_coefficients", "pdmp3_amd_loudness_tables", "pdmp3_amd_loudness_plan",
                 "pdmp3_amd_bulk_decode_clips_loudness",
-                "pdmp3_amd_r128_check", "pdmp3_amd_r128_taps", "pdmp3_amd_r128_plan", "pdmp3_amd_bulk_decode_clips_r128"]
+                "pdmp3_amd_r128_check", "pdmp3_amd_r128_taps", "pdmp3_amd_r128_plan", "pdmp3_amd_bulk_decode_clips_r128",
+                "pdmp3_amd_pitch_check", "pdmp3_amd_pitch_lags", "pdmp3_amd_pitch_plan", "pdmp3_amd_bulk_decode_clips_pitch"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -208,6 +209,11 @@ def load_library():
         lib.pdmp3_amd_r128_taps.argtypes = [vp, vp]
         lib.pdmp3_amd_r128_plan.argtypes = [C.c_long, ll] + [C.POINTER(C.c_int)] * 2 + [C.POINTER(C.c_uint), C.POINTER(C.c_int)] + [C.POINTER(ll)] * 6
         lib.pdmp3_amd_bulk_decode_clips_r128.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_pitch"):        # (pitch of clips: absent from older builds)
+        lib.pdmp3_amd_pitch_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_pitch_lags.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 3
+        lib.pdmp3_amd_pitch_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_bulk_decode_clips_pitch.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -1026,6 +1032,53 @@ def r128_plan(sample_rate, n_samples):
     return (b.value, ch.value, lds.value, q.value) + tuple(x.value for x in v)
 
 
+class _PitchSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_pitch_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("n_frames", C.c_longlong),
+                ("frame_length", C.c_int), ("win_length", C.c_int), ("hop", C.c_int), ("fmin", C.c_double), ("fmax", C.c_double),
+                ("threshold", C.c_double), ("out_mode", C.c_int)]
+
+
+PITCH_MODES = {"pitch": 0, "curve": 1}
+PITCH_FMIN, PITCH_FMAX = 65.406, 2093.0            # C2 and C7, librosa's note_to_hz to the digits its examples print
+
+
+def _pitch_spec(n_frames=1, sample_rate=22050, frame_length=2048, win_length=None, hop=None, fmin=PITCH_FMIN, fmax=PITCH_FMAX, threshold=0.1,
+                out_mode="pitch", channels=1, width=0, rolloff=0.0):
+    """(None means 0 to the library: win_length frame_length / 2, hop frame_length / 4)"""
+    return _PitchSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_frames), int(frame_length),
+                      0 if win_length is None else int(win_length), 0 if hop is None else int(hop), float(fmin), float(fmax), float(threshold),
+                      PITCH_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode))
+
+
+def pitch_check(sample_rate=22050, **kw):
+    """pdmp3_amd_pitch_check -> True when pdmp3_amd_bulk_decode_clips_pitch would accept these numbers (decode_clips_pitch's
+    argument names) at sample_rate"""
+    try:
+        spec = _pitch_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_pitch_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def pitch_lags(sample_rate=22050, **kw):
+    """pdmp3_amd_pitch_lags -> (tmin, tmax, lag tiles of 256 a frame)"""
+    spec = _pitch_spec(sample_rate=sample_rate, **kw)
+    a, b, t = C.c_int(0), C.c_int(0), C.c_int(0)
+    if load_library().pdmp3_amd_pitch_lags(C.byref(spec), int(sample_rate), C.byref(a), C.byref(b), C.byref(t)) != 0:
+        raise ValueError("pdmp3_amd_pitch_lags: bad argument")
+    return a.value, b.value, t.value
+
+
+def pitch_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_pitch_plan -> (frames of a workgroup of k_clip_pitch, LDS floats of its span, LDS bytes, matrix instructions a
+    lag tile)"""
+    spec = _pitch_spec(sample_rate=sample_rate, **kw)
+    f, k, sp, b = C.c_int(0), C.c_int(0), C.c_uint(0), C.c_uint(0)
+    if load_library().pdmp3_amd_pitch_plan(C.byref(spec), int(sample_rate), C.byref(f), C.byref(sp), C.byref(b), C.byref(k)) != 0:
+        raise ValueError("pdmp3_amd_pitch_plan: bad argument")
+    return f.value, sp.value, b.value, k.value
+
+
 class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
                 ("chan_stride", C.c_size_t)]
@@ -1426,6 +1479,27 @@ class BulkDecoder:
             e.stats = stats
             raise
         return audio, stats, valid
+
+    def decode_clips_pitch(self, clips, n_frames, sample_rate=22050, frame_length=2048, hop=512, fmin=PITCH_FMIN, fmax=PITCH_FMAX, threshold=0.1,
+                           out_mode="pitch", win_length=None, channels=1, width=0, rolloff=0.0, out=None):
+        """pdmp3_amd_bulk_decode_clips_pitch: clips = sequence of (mp3, StreamIndex, first sample at sample_rate) -> (out, valid):
+        YIN with librosa.yin's parameters on frames centred on sample start + f hop of the stream resampled as decode_clips_audio
+        does (width, rolloff), zeros outside the stream and no reflection.  out_mode "pitch": float32 [K, C, 3, n_frames] -- f0 in
+        Hz, the aperiodicity d'(tau*), the lag tau*; a frame of zeros is (0, 1, 0).  out_mode "curve": [K, C, tmax + 1, n_frames],
+        the cumulative-mean-normalised difference d'(tau), tau = 0 .. tmax (pitch_lags gives tmax).  win_length None:
+        frame_length // 2; hop None: frame_length // 4.  valid, out, RingReplay / MixedFormat as decode_clips_stft.  Synchronous."""
+        f = int(n_frames)
+        m = PITCH_MODES.get(out_mode) if isinstance(out_mode, str) else int(out_mode)
+        spec = lambda: (_pitch_spec(f, sample_rate, frame_length, win_length, hop, fmin, fmax, threshold, m, channels, width, rolloff), None)
+        if m not in (0, 1):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_pitch: out_mode is \"pitch\" or \"curve\"")
+        rows = 3
+        if m != 0:
+            try:
+                rows = pitch_lags(sample_rate, frame_length=frame_length, win_length=win_length, hop=hop, fmin=fmin, fmax=fmax)[1] + 1
+            except (ValueError, OverflowError, TypeError):
+                raise RuntimeError("pdmp3_amd_bulk_decode_clips_pitch: bad sample_rate, frame_length, win_length, hop, fmin or fmax")
+        return self._clips_call("pitch", clips, (rows, f), spec, channels, out, refused=(ValueError, OverflowError, TypeError))
 
     def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
                     nb=None, spec_of=None):

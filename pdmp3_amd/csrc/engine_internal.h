@@ -178,6 +178,8 @@ hipError_t pdmp3_launch_clip_loudness(hipStream_t s, const pdmp3_mel_desc* descs
 hipError_t pdmp3_launch_clip_r128(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, int clip0, const pdmp3_loud_tables* tab, const float* taps,
                                   const uint64_t* stats_dst, const uint64_t* mom_dst, const uint64_t* st_dst, double* states, double* starts,
                                   float* part, float* sub, float* gains, const pdmp3_r128_params* params);
+// ---- pitch.hip ----
+hipError_t pdmp3_launch_clip_pitch(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_pitch_params* params);
 // ---- stft_long.hip ----
 hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                        const pdmp3_stft_long_params* params);

@@ -11,6 +11,7 @@
 #include "engine_internal.h"
 #include "unpack_core.h"
 #include "resample_core.h"
+#include "pitch_core.h"
 
 using namespace pdmp3;
 
@@ -959,6 +960,32 @@ extern "C" int pdmp3_hip_clip_r128(pdmp3_hip_stream* hs, int slot, const pdmp3_m
                                                   reinterpret_cast<double*>(part[6]), reinterpret_cast<float*>(part[7]),
                                                   reinterpret_cast<float*>(part[8]), reinterpret_cast<float*>(part[9]), params);
                   });
+}
+// ---- pitch (pitch.hip) ----
+extern "C" int pdmp3_hip_clip_pitch(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_pitch_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pitch: bad argument", hipSuccess);
+  const pdmp3_pitch_params& P = *params;
+  // what the kernel's indexing relies on
+  if (P.n < 64 || P.n > 2048 || (P.n & 1) || P.win < 4 || P.win > P.n - 2 || P.hop < 1 || P.hop > P.n || P.tmin < 1 || P.tmin >= P.tmax ||
+      P.tmax > P.n - P.win - 1 || P.tiles != (P.tmax + 256) / 256 || P.tiles > 8 || P.ksteps != (P.win + 18) / 4 ||
+      (P.frames_wg != 1 && P.frames_wg != 2 && P.frames_wg != 4 && P.frames_wg != 8) || (P.channels != 1 && P.channels != 2) ||
+      (P.out_mode != 0 && P.out_mode != 1) || P.n_frames < 0 || P.n_in < 0 || !(P.sr > 0.0) || !(P.threshold > 0.0) || (P.span_floats & 3u) ||
+      P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pitch: bad parameters", hipSuccess);
+  {
+    // (the A operand of the k-step behind the last, which the kernel reads ahead: row 15 of the last tile)
+    const size_t reach = (size_t)4 * (P.ksteps + 1) + 240 + (size_t)256 * (P.tiles - 1), first = (size_t)(P.frames_wg - 1) * P.hop;
+    const size_t ext = pdmp3::kPitchFront + first + (reach > (size_t)P.n ? reach : (size_t)P.n);
+    if (P.q_doubles != first + P.n + 1 || P.ext < ext || P.ext > 0x100000u || P.span_floats < pdmp3::pitch_at(P.ext) ||
+        (size_t)P.lds_bytes < (size_t)pdmp3::pitch_lds(P).total_f * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pitch: a workgroup's span, sums and curves do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.frames_wg - 1) / P.frames_wg * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pitch: too many frames", hipSuccess);
+  }
+  // descriptors alone: the kernel reads no table
+  return clip_run(hs, slot, "pdmp3_hip_clip_pitch", descs, n_clips, P.n_frames, {{ClipPart::kScratch, nullptr, 0}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const*) { return pdmp3_launch_clip_pitch(hs->s[slot].stream, dk, nk, &P); });
 }
 extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {
   if (!bytes) return PDMP3_HIP_OK;

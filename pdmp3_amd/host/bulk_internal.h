@@ -404,6 +404,9 @@ HOST_LOCAL int loud_plan(long fs, long long n_samples, pdmp3_loud_params* p);
 /* clip_r128.c: loud_plan's geometry with the short-term windows and the range's (0, or -1: also where the range has more windows
  * than k_loud_gate<true> ranks) */
 HOST_LOCAL int r128_plan(long fs, long long n_samples, pdmp3_r128_params* p);
+/* clip_pitch.c: the check, the lag range and the geometry of a workgroup of k_clip_pitch for the spec at sr; n_in, n_frames and
+ * channels are left to the call (0, or -1 where the check refuses the spec) */
+HOST_LOCAL int pitch_plan(const pdmp3_amd_pitch_spec* s, long sr, pdmp3_pitch_params* p);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

@@ -403,6 +403,23 @@ int pdmp3_amd_bulk_decode_clips_stft(struct bulk* b, const pdmp3_amd_audio_clip*
   return course_finish(&cc, cc.rc);
 }
 
+/* ---- the pitch of clips ---- */
+int pdmp3_amd_bulk_decode_clips_pitch(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pitch_spec* spec,
+                                      long long* valid) {
+  clip_course cc;
+  if (!spec || course_begin(&cc, b, clips, n_clips, valid, spec->n_frames, spec->channels, spec->rate, spec->width, spec->rolloff) != 0) return -1;
+  pdmp3_pitch_params P;
+  memset(&P, 0, sizeof P);
+  if (pitch_plan(spec, cc.sr, &P) != 0) return -1;                      /* (the check is its first step) */
+  const int per_frame = spec->out_mode == 0 ? 3 : P.tmax + 1;            /* floats of a frame */
+  if (course_rows(&cc, P.n, P.hop, per_frame, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  if (course_signal(&cc) != 0) return course_finish(&cc, -1);
+  P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_pitch(b->hs, CLIP_SLOT, cc.ds, cc.nd, &P)) != 0) return course_finish(&cc, -1);
+  return course_finish(&cc, cc.rc);
+}
+
 /* ---- the short-time Fourier transform of clips at n_fft 2048 and 4096 ---- */
 int pdmp3_amd_bulk_decode_clips_stft_long(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_stft_spec* spec,
                                           long long* valid) {

@@ -25,6 +25,7 @@
  *   clip_chroma.c   chroma features of clips: the check, the class of every bin, the kernel's plan on top of clip_cqt.c's
  *   clip_loudness.c loudness of clips: the check, the K-weighting's coefficients, the blocked filter's tables, the geometry
  *   clip_r128.c     true peak, short-term loudness and loudness range of clips: the check, the interpolator's taps, the geometry
+ *   clip_pitch.c    pitch of clips (YIN): the check, the lag range, the geometry of a workgroup
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

@@ -865,6 +865,126 @@ def clips_loudness(args, api, r128=False):
     print(json.dumps(res))
 
 
+def torch_yin(x, rate, N, W, H, tmin, tmax, thr):
+    """YIN as include/pdmp3_bulk.h defines it (items 3-6), for rows x [K, T] whose first sample is the first frame's first, with
+    torch's own kernels in binary32 -> [K, 3, F]: f0, d'(tau*), tau*"""
+    import torch
+    lag = torch.arange(tmax + 1, dtype=torch.float32, device=x.device)
+    fr = x.unfold(-1, N, H)                                        # [K, F, N]
+    r = torch.fft.irfft(torch.fft.rfft(fr, n=N) * torch.fft.rfft(fr[..., :W], n=N).conj(), n=N)[..., :tmax + 1]
+    cs = torch.nn.functional.pad(torch.cumsum(fr * fr, -1), (1, 0))
+    e = cs[..., W:W + tmax + 1] - cs[..., :tmax + 1]
+    d = e[..., :1] + e - 2.0 * r
+    S = torch.cumsum(d[..., 1:], -1)
+    dp = torch.ones_like(d)
+    dp[..., 1:] = torch.where(S > 0, d[..., 1:] * lag[1:] / S, torch.ones_like(S))
+    c = dp[..., tmin:tmax + 1]
+    trough = torch.zeros_like(c, dtype=torch.bool)
+    trough[..., 1:-1] = (c[..., 1:-1] < c[..., :-2]) & (c[..., 1:-1] <= c[..., 2:])
+    trough[..., 0] = c[..., 0] < c[..., 1]
+    under = trough & (c < thr)
+    first = torch.argmax(under.to(torch.int8), -1)
+    best = torch.where(under.any(-1), first, torch.argmin(c, -1))
+    i0 = best.unsqueeze(-1)
+    b = torch.gather(c, -1, i0)
+    a = torch.gather(c, -1, (i0 - 1).clamp(min=0))
+    cc = torch.gather(c, -1, (i0 + 1).clamp(max=tmax - tmin))
+    D = a - 2.0 * b + cc
+    inner = (i0 > 0) & (i0 < tmax - tmin) & (D > 0)
+    delta = torch.where(inner, (a - cc) / (2.0 * torch.where(inner, D, torch.ones_like(D))), torch.zeros_like(D))
+    tau = (best + tmin).to(torch.float32)
+    silent = ~(fr != 0).any(-1)
+    return torch.stack([torch.where(silent, torch.zeros_like(tau), rate / (tau + delta.squeeze(-1))),
+                        torch.where(silent, torch.ones_like(tau), b.squeeze(-1)), torch.where(silent, torch.zeros_like(tau), tau)], 1)
+
+
+def clips_pitch(args, api):
+    """--pitch: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as YIN pitch [K, 1, 3, 1292] with
+    librosa.yin's defaults (frame 2048, window 1024, hop 512, C2 .. C7, threshold 0.1) in device memory, three ways, run after
+    run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the same spans (the call the feature call makes itself); (b) (a)
+    followed by the same algorithm in torch on the device -- unfold, torch.fft.rfft / irfft for r, cumulative sums for e and S,
+    the decision with argmax / argmin, the parabola --; (c) pdmp3_amd_bulk_decode_clips_pitch.  (b) and (c) are compared once
+    (share of frames with the same lag and the largest f0 difference among them, printed, not asserted: the tests check (c)
+    against the definition).  k_clip_pitch's own time comes from a kernel-trace run of this mode (profiles/clip_pitch.txt).
+    Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, Fm, rate, N, W, H, thr = args.clips, args.clip_frames, 22050, 2048, 1024, 512, 0.1
+    span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
+    F = span // H + 1
+    T = (F - 1) * H + N
+    tmin, tmax, tiles = api.pitch_lags(rate)
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(2, max(3, ixs[i].frames - Fm - 4))))
+    clips, spans = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = -((-a * ixs[i].frame_samples * l) // m)
+        clips.append((files[i], ixs[i], start))
+        spans.append((files[i], ixs[i], start - N // 2))
+    dev = "cuda:0"
+    sig = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, 3, F), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, 3, F), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(spans, T, rate, 1, out=sig)
+
+    def torch_route():
+        dec.decode_clips_audio(spans, T, rate, 1, out=sig)
+        out_b[:, 0] = torch_yin(sig[:, 0], rate, N, W, H, tmin, tmax, thr)
+        torch.cuda.synchronize()
+
+    def pitch_route():
+        dec.decode_clips_pitch(clips, F, rate, N, H, out=out_c)
+
+    routes = [("audio clips", audio_route), ("audio clips + torch yin", torch_route), ("pitch clips", pitch_route)]
+    times = {name: [] for name, _ in routes}
+    seen = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            same = out_b[:, 0, 2] == out_c[:, 0, 2]
+            seen = {"frames": int(same.numel()), "frames_with_torchs_lag": int(same.sum()),
+                    "largest_f0_difference_among_them_hz": float((out_b[:, 0, 0] - out_c[:, 0, 0])[same].abs().max()) if bool(same.any()) else None,
+                    "voiced_frames": int((out_c[:, 0, 1] < thr).sum()), "frames_of_zeros": int((out_c[:, 0, 2] == 0).sum())}
+    dec.close()
+    plan = api.pitch_plan(rate)
+    res = {"workload": "%d clips of %d frames (%d samples) at %d Hz mono, YIN, frame %d window %d hop %d, lags %d .. %d: %s" % (
+               K, F, T, rate, N, W, H, tmin, tmax, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "plan": {"frames_a_workgroup": plan[0], "span_floats": plan[1], "lds_bytes": plan[2], "matrix_instructions_a_tile": plan[3], "lag_tiles": tiles},
+           "matrix_instructions": K * F * tiles * plan[3], "seen": seen, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["pitch_minus_audio_ms"] = round((med["pitch clips"] - med["audio clips"]) * 1e3, 3)
+    res["torch_minus_audio_ms"] = round((med["audio clips + torch yin"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -1101,6 +1221,10 @@ def main():
     ap.add_argument("--r128", action="store_true",
                     help="--loudness's batch with pdmp3_amd_bulk_decode_clips_r128 (true peak, short-term loudness, loudness range, the gain "
                          "held to -1 dBTP) as a third route beside the loudness call and the audio call (see clips_loudness())")
+    ap.add_argument("--pitch", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as YIN pitch [3, 1292] at 22 050 Hz mono with librosa.yin's defaults "
+                         "(pdmp3_amd_bulk_decode_clips_pitch) against the audio call alone and the audio call followed by the same algorithm "
+                         "in torch on the device (see clips_pitch())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1108,7 +1232,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1120,6 +1244,8 @@ def main():
             return clips_chroma(args, api)
         if args.loudness or args.r128:
             return clips_loudness(args, api, r128=args.r128)
+        if args.pitch:
+            return clips_pitch(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
