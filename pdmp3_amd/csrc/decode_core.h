@@ -239,6 +239,27 @@ static inline void mul18_rtz_32767(const float* x, float* p) {
 #else
 #define PD_GRAN_PCM_FORM 1
 #endif
+// A/B switches of the granule kernel's instruction diet (profiles/gran_diet_ab.txt; results are the same in every form).
+// -DPD_EXP_SCALES_COMPUTED: the band scales computed per granule (ph_scales), as before -- otherwise looked up (ph_scales_tab);
+// -DPD_EXP_TAPS_ROWS: TabLds::taps as [tap][lane], read one dword at a time with an address each, as before -- otherwise
+// per lane in 16-byte pieces, four reads from one address; -DPD_EXP_IMDCT_COPY: ph_imdct hands the transform's B fragments
+// to the matrix instructions through a second set of registers whatever the block type, as before -- otherwise a granule
+// without short blocks feeds them from where they are
+#if defined(PD_EXP_SCALES_COMPUTED)
+#define PD_GRAN_SCALE_TABS 0
+#else
+#define PD_GRAN_SCALE_TABS 1
+#endif
+#if defined(PD_EXP_TAPS_ROWS)
+#define PD_GRAN_TAPS_WIDE 0
+#else
+#define PD_GRAN_TAPS_WIDE 1
+#endif
+#if defined(PD_EXP_IMDCT_COPY)
+#define PD_GRAN_IMDCT_SPLIT 0
+#else
+#define PD_GRAN_IMDCT_SPLIT 1
+#endif
 // the VALU columns' coefficients as [m][q] (q fastest): the pair (q, q + 1) of one m is an aligned scalar-register pair, a
 // v_pk_fma_f32 operand as it comes out of the s_load -- as [q][m] every packed FMA needed one or two s_mov_b32 in front of
 // it and the block two more scalar loads (131072 frames 1.037 -> 1.005 ms, round 5; 0 = the old layout, for A/B)
@@ -322,7 +343,8 @@ struct GlobalTables {
   const float* frag_short;  // [5 kk][2 nt]   3 x 12-point IMDCT with win[2] folded in, same column map
   const float* frag_mat;    // [2 even/odd][4 k-steps]: 16 x 16 halves of the 32-point DCT-II, rows in register order
   const float* taps;        // [16][64 lanes]: the lane's window coefficients we[0..7], wo[0..7] (g_synth_dtbl, sign folded)
-  const void* tab_image;    // [kNumSfreq] images of TabLds (host_tables.h: build_tab_images), copied to LDS as they are
+  const void* tab_image;    // [kNumSfreq] images of TabLds (host_tables.h: build_tab_images), copied to LDS as they are;
+                            //   behind them the image of ScaleTabs (the granule kernel's: scale_tabs_load)
 };
 
 // LDS.  WaveData is a wave's own working set; TabLds are the hot tables -- one copy per wave in the chunk kernels
@@ -350,10 +372,26 @@ struct alignas(16) TabLds {
   int pad_[3];
   // the window taps of lane i = lane & 31 (GlobalTables::taps holds them per lane; both channels' are alike): the granule
   // kernel reads them from here -- its sixteen waves took 16 x 256 B each through the CU's L1 at their entry, 64 KB per
-  // workgroup; as part of the table image that is 2 KB per workgroup
-  alignas(16) float taps[16][32];
+  // workgroup; as part of the table image that is 2 KB per workgroup.  Tap t = 0..15 (we[0..7], wo[0..7]) of lane i is
+  // taps[tab_tap_index(t, i)]: four taps to a 16-byte piece, the 32 lanes' pieces p = t >> 2 side by side -- lane i's four
+  // pieces are 512 bytes apart, one address and four offsets (ph_window_own), and the sixteen lanes one ds_read_b128 cycle
+  // serves ({0-3, 12-15, 20-27}, ...: i mod 16 all different) are in 64 different banks
+  alignas(16) float taps[16 * 32];
 };
+PD_HD int tab_tap_index(int t, int i) { return PD_GRAN_TAPS_WIDE ? ((t >> 2) * 32 + i) * 4 + (t & 3) : t * 32 + i; }
 static_assert(sizeof(TabLds) % 16 == 0, "copied in 16-byte pieces");
+// The band scales' tables of the granule kernel (ph_scales_tab), one copy per workgroup beside its TabLds -- not part of it:
+// the chunk kernels hold a TabLds per wave and compute their scales (ph_scales).  Built on the host with ph_scales' own
+// functions (host_tables.h), copied as they are (scale_tabs_load).
+constexpr int kScaleT1Max = 300;         // pow2_neg_half(n) = 0 from here on
+constexpr int kScaleT2Min = -266, kScaleT2Max = 45;      // k = global_gain - 210 - 8 subblock_gain
+struct alignas(16) ScaleTabs {
+  float t1[kScaleT1Max + 4];                       // [min(n, 300)] = pow2_neg_half(n) (301 entries, padded)
+  float t2[kScaleT2Max - kScaleT2Min + 1];         // [k + 266] = pow2_quarter(k)
+  uint32_t lane[64];                               // what ph_scales derives from the lane number: scale_lane_const()
+};
+static_assert(sizeof(ScaleTabs) % 16 == 0, "copied in 16-byte pieces");
+constexpr int kScaleTabImages = (int)((sizeof(ScaleTabs) + sizeof(TabLds) - 1) / sizeof(TabLds));   // its image's room behind GlobalTables::tab_image, in TabLds
 struct WaveLds : WaveData {
   TabLds tab;
 };
@@ -487,6 +525,12 @@ PD_FN void tab_load_image(int tid, int nthr, TabLds& S, const GlobalTables& T, i
   Chunk16* dst = reinterpret_cast<Chunk16*>(&S);
   for (int k = tid; k < (int)(sizeof(TabLds) / 16); k += nthr) dst[k] = src[k];
 }
+// ... and the granule kernel's ScaleTabs, whose image lies behind the kNumSfreq images of TabLds
+PD_FN void scale_tabs_load(int tid, int nthr, ScaleTabs& G, const GlobalTables& T) {
+  const Chunk16* src = reinterpret_cast<const Chunk16*>(reinterpret_cast<const char*>(T.tab_image) + (size_t)kNumSfreq * sizeof(TabLds));
+  Chunk16* dst = reinterpret_cast<Chunk16*>(&G);
+  for (int k = tid; k < (int)(sizeof(ScaleTabs) / 16); k += nthr) dst[k] = src[k];
+}
 PD_FN void load_linetab(int lane, TabLds& S, const GlobalTables& T, int sfreq) { tab_load_image(lane, 64, S, T, sfreq); }
 
 // state layout (opaque to callers): float ovl[kOvlRegs][64 lanes]; float he[15][64]; float ho[15][64]
@@ -584,6 +628,45 @@ PD_FN void ph_scales(int lane, WaveData& L) {
     const uint32_t x = is_long ? sl + ((flags & PDMP3_GC_PREFLAG) ? (uint32_t)pre : 0u) : sf_short;
     const float t1 = pow2_neg_half(sfscale ? 2 * x : x);
     const float t2 = pow2_quarter(gg - 210 - (is_long ? 0 : 8 * (int)sbg));
+    res[ch] = t1 * t2;
+  }
+  if (lane < 61) { L.scale[0][lane] = res[0]; L.scale[1][lane] = res[1]; }
+}
+// ScaleTabs::lane[lane]: everything ph_scales works out from the lane number, in one dword --
+//   bits 0-6 the side record's byte with the lane's scalefactor (8 + ll, or 30 + q), 7-9 the one with its subblock_gain
+//   (4 + win), 10-11 pre (0 for a short band: nothing is added there), 12 sfb == 12 (the H5 band), 13 is_long, 14-15 win,
+//   16-20 ll, 21-26 q
+PD_HD uint32_t scale_lane_const(int lane) {
+  const bool is_long = lane < 22;
+  const int ll = is_long ? lane : 21;
+  const int q = is_long ? 0 : (lane < 61 ? lane - 22 : 38);
+  const int sfb = q / 3, win = q - 3 * sfb;
+  const int pre = is_long ? (int)((0x2fe95400000ull >> (2 * ll)) & 3) : 0;
+  return (uint32_t)(is_long ? 8 + ll : 30 + q) | (uint32_t)(4 + win) << 7 | (uint32_t)pre << 10 | (sfb == 12 ? 1u << 12 : 0u) |
+         (is_long ? 1u << 13 : 0u) | (uint32_t)win << 14 | (uint32_t)ll << 16 | (uint32_t)q << 21;
+}
+// ph_scales from tables (the granule kernel): the same t1 * t2 per band -- t1 and t2 looked up where ph_scales computes
+// them, the lane's constants from one dword, ONE scalefactor byte read (the lane's own kind) instead of both kinds' and a
+// select.  A long band's byte is at most 255, so the clamp at 400 that ph_scales gives a short band's value changes
+// nothing there; its pre is 0 for a short band.
+PD_FN void ph_scales_tab(int lane, WaveData& L, const ScaleTabs& G) {
+  const uint32_t c = G.lane[lane];
+  const uint32_t sf_at = c & 127u, sbg_at = (c >> 7) & 7u, pre = (c >> 10) & 3u, win = (c >> 14) & 3u;
+  const bool h5 = (c & (1u << 12)) != 0u, is_long = (c & (1u << 13)) != 0u;
+  const float pk = L.peek[win];
+  float res[2];
+  PD_UNROLL for (int ch = 0; ch < 2; ch++) {
+    const uint8_t* s = L.side[ch];
+    const int gg = s[2], flags = s[3];
+    const uint32_t sf = s[sf_at], mark = s[30 + 36], sbg = s[sbg_at];
+    const bool sfscale = flags & PDMP3_GC_SCALEFAC_SCALE;
+    uint32_t v = (h5 && mark == PDMP3_SF_PEEK) ? f2u(pk) : sf;                                // H5
+    v = v > 400u ? 400u : v;
+    const uint32_t x = v + ((flags & PDMP3_GC_PREFLAG) ? pre : 0u);
+    const uint32_t n = sfscale ? 2 * x : x;
+    const float t1 = G.t1[n < (uint32_t)kScaleT1Max ? n : (uint32_t)kScaleT1Max];
+    const uint32_t k = (uint32_t)(gg - 210 - kScaleT2Min - (is_long ? 0 : 8 * (int)sbg));
+    const float t2 = G.t2[k < (uint32_t)(kScaleT2Max - kScaleT2Min) ? k : (uint32_t)(kScaleT2Max - kScaleT2Min)];    // (in the table whatever the record holds)
     res[ch] = t1 * t2;
   }
   if (lane < 61) { L.scale[0][lane] = res[0]; L.scale[1][lane] = res[1]; }
@@ -739,7 +822,7 @@ PD_FN void ph_stereo_is(int lane, WaveData* Lp, const TabLds* Sp, BankPtr cb, co
   }
 }
 
-template <bool TG, bool SCALES> PD_FN void ph_requant_long(int lane, WaveData& L, const TabLds& S, const GlobalTables& T, const GranuleInfo& g);   // (below)
+template <bool TG, bool SCALES, bool SCTAB> PD_FN void ph_requant_long(int lane, WaveData& L, const TabLds& S, const GlobalTables& T, const GranuleInfo& g, const ScaleTabs* sc);   // (below)
 PD_FN void ph_scales(int lane, WaveData& L);
 
 // NI = 9: the whole granule.  NI = 1: only the reordered lines 0..63 (the peek-only halo granule, see run_chunk).
@@ -747,9 +830,10 @@ PD_FN void ph_scales(int lane, WaveData& L);
 // the granule's (granule kernel: one table block per workgroup) -- then the line table is read from global memory.
 // SCALES: the band scales (ph_scales) are computed in here -- in the fast path while the loads from the full |is|^(4/3)
 // table are in flight (straight-line callers, which have nothing else to put there).
-template <bool DUMP, int NI = 9, bool FAST = false, bool TG = false, bool SCALES = false, bool RARE = true>
+// SCTAB (with SCALES): from the tables `sc` (ph_scales_tab: the granule kernel).
+template <bool DUMP, int NI = 9, bool FAST = false, bool TG = false, bool SCALES = false, bool RARE = true, bool SCTAB = false>
 PD_FN void ph_requant(int lane, WaveData& L, const TabLds& S, BankPtr cb, const GlobalTables& T, float* dump0, float* dump1,
-                      const GranuleInfo* gi = nullptr) {
+                      const GranuleInfo* gi = nullptr, const ScaleTabs* sc = nullptr) {
   // (gi: the granule's facts, read once by the caller -- every granule_info() is an LDS round trip and four
   //  v_readfirstlane at the head of a phase, and the phase fences keep the compiler from sharing one between phases)
   const GranuleInfo g = gi ? *gi : granule_info<RARE>(L);
@@ -762,11 +846,11 @@ PD_FN void ph_requant(int lane, WaveData& L, const TabLds& S, BankPtr cb, const 
   const int kind0 = g.kind(0), kind1 = g.kind(1);
   if (FAST && !DUMP && NI == 9) {
     if (kind0 == 0 && (g.nch == 1 || kind1 == 0) && !is && g.ver == 0) {     // wave-uniform (the fast path's band addresses are MPEG-1's)
-      ph_requant_long<TG, SCALES>(lane, L, S, T, g);
+      ph_requant_long<TG, SCALES, SCTAB>(lane, L, S, T, g, sc);
       return;
     }
   }
-  if (SCALES) { ph_scales(lane, L); PD_WAVE_SYNC(); }
+  if (SCALES) { if (SCTAB) ph_scales_tab(lane, L, *sc); else ph_scales(lane, L); PD_WAVE_SYNC(); }
   float x0[NI], x1[NI];
 #define PD_LINE(i) (lane + 64 * (i))
   {
@@ -877,8 +961,8 @@ PD_FN float ms_scale(float x) { return (float)((double)x * 0.7071067811865475244
 // the lanes that hold one fetch theirs from the full table under their own execution mask (a skipped block for
 // everybody else: one compare and a scalar branch per pair of lines) -- all of a granule's loads are issued before
 // anything waits for one, the scales are computed under them, the results are picked up afterwards.
-template <bool TG, bool SCALES>
-PD_FN void ph_requant_long(int lane, WaveData& L, const TabLds& S, const GlobalTables& T, const GranuleInfo& g) {
+template <bool TG, bool SCALES, bool SCTAB>
+PD_FN void ph_requant_long(int lane, WaveData& L, const TabLds& S, const GlobalTables& T, const GranuleInfo& g, const ScaleTabs* sc) {
   const bool two = g.nch == 2;
   const bool ms = two && (g.mode == 1) && (g.mode_ext & 2);
   const int cmin = (g.iso & PDMP3_GC_ISO_MS_ALL) ? 576 : (g.count1_0 > g.count1_1 ? g.count1_1 : g.count1_0);   // P:1920 (H2): the smaller; ISO switch: every line
@@ -916,7 +1000,7 @@ PD_FN void ph_requant_long(int lane, WaveData& L, const TabLds& S, const GlobalT
   const bool bigs0 = (unsigned)(v0s + kPow43Small) >= 2u * kPow43Small, bigs1 = (unsigned)(v1s + kPow43Small) >= 2u * kPow43Small;
   if (bigs0) { int ia = pow43_big_index(v0s); PD_PIN(ia); gs0 = T.pow43[ia]; }
   if (bigs1) { int ia = pow43_big_index(v1s); PD_PIN(ia); gs1 = T.pow43[ia]; }
-  if (SCALES) { ph_scales(lane, L); PD_WAVE_SYNC(); }       // (the loads above are in flight)
+  if (SCALES) { if (SCTAB) ph_scales_tab(lane, L, *sc); else ph_scales(lane, L); PD_WAVE_SYNC(); }       // (the loads above are in flight)
   PD_UNROLL for (int i = 0; i < 5; i++) {
     const float s0 = *reinterpret_cast<const float*>(sc0 + ba[i]);
     const float s1 = *reinterpret_cast<const float*>(sc1 + ba[i]);
@@ -1694,6 +1778,7 @@ struct GranPos {
   // receiving granule's number in the range + 1 instead of 0 / 1; nothing is handed on beyond g_end
   int ring;              // 0: one granule per wave, flags 0 -> 1 (k_decode_g)
   int g_base, g_end;
+  const ScaleTabs* sc;   // LDS: the workgroup's band-scale tables, complete with the others (tabs_ready); read by run_granule<.., SCTAB = true> alone
 };
 PD_FN int gran_next_place(const GranPos& gp) { return (gp.ring && gp.w + 1 == gp.wpw) ? 0 : gp.w + 1; }
 PD_FN unsigned gran_tag(const GranPos& gp, int g) { return gp.ring ? (unsigned)(g - gp.g_base + 1) : 1u; }
@@ -1847,10 +1932,11 @@ PD_FN bool gran_far_wait(const DecodeArgs& a, int g, int k, bool bounded) {
 
 // ---- ph_mfma in two stages (stereo granules).  ph_imdct: everything up to the windowed IMDCT outputs, indexed like
 // R.ovl: y1 = first halves (what the overlap is added to), y2 = tails (the next granule's overlap).  xr is dead after it.
+template <bool SHORT>
+PD_FN void ph_imdct_tiles(int lane, const WaveData& L, const TabLds& S, const LaneRegs& R, const GlobalTables& T, const GranuleInfo& g, float* y1, float* y2);
 PD_FN void ph_imdct(int lane, const WaveData& L, const TabLds& S, const LaneRegs& R, BankPtr cb, const GlobalTables& T, float* y1, float* y2,
                     const GranuleInfo* gi = nullptr) {
   const GranuleInfo g = gi ? *gi : granule_info(L);
-  const int j = lane & 15, kq = lane >> 4;
   const bool any_short = g.is_short(0) || g.is_short(1);
   {   // IMDCT outputs p = 16, 17, 34, 35 on the VALU: lane = (cl, sb), scalar-broadcast coefficients
     const int cl = lane >> 5, sb = lane & 31;
@@ -1873,9 +1959,19 @@ PD_FN void ph_imdct(int lane, const WaveData& L, const TabLds& S, const LaneRegs
     }
     y1[16] = y[0]; y1[17] = y[1]; y2[16] = y[2]; y2[17] = y[3];
   }
+  // one branch per wave: a granule without short blocks (most are) takes the copy of the tiles' code in which the long
+  // transform's fragments R.bi ARE the matrix instructions' B operands; with the short blocks' loads behind a branch per
+  // channel in the one copy, both paths met in a second set of ten registers, which the long one filled with ten moves
+  if (PD_GRAN_IMDCT_SPLIT && !any_short) ph_imdct_tiles<false>(lane, L, S, R, T, g, y1, y2);
+  else ph_imdct_tiles<true>(lane, L, S, R, T, g, y1, y2);
+}
+// the 16 x 16 tiles of ph_imdct on the matrix pipe.  SHORT = false: the caller knows that neither channel has short blocks
+template <bool SHORT>
+PD_FN void ph_imdct_tiles(int lane, const WaveData& L, const TabLds& S, const LaneRegs& R, const GlobalTables& T, const GranuleInfo& g, float* y1, float* y2) {
+  const int j = lane & 15, kq = lane >> 4;
   PD_UNROLL for (int cc = 0; cc < 2; cc++) {
     const int ch = 1 - cc;
-    const bool shrt = g.is_short(ch);
+    const bool shrt = SHORT && g.is_short(ch);
     const bool wsf = (g.flags(ch) & PDMP3_GC_WIN_SWITCH) != 0;
     const bool mixrows = wsf && g.is_mixed(ch);        // subbands 0, 1 use window/transform 0 (P:1769-1771)
     const int bt = g.block_type(ch);
@@ -1984,7 +2080,15 @@ PD_FN void ph_overlap_matrix(int lane, WaveData& L, const LaneRegs& R, const flo
 // the terms that read the granule's own slots ...
 PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs& R, float* acc) {
   const int ch = lane >> 5;
-  PD_UNROLL for (int k = 0; k < 8; k++) { R.we[k] = S.taps[k][lane & 31]; R.wo[k] = S.taps[8 + k][lane & 31]; }
+  if (PD_GRAN_TAPS_WIDE) {               // (TabLds::taps: the lane's piece p at 16 (32 p + i) bytes)
+    const Chunk16* tp = reinterpret_cast<const Chunk16*>(S.taps) + (lane & 31);
+    PD_UNROLL for (int p = 0; p < 4; p++) {
+      const Chunk16 v = tp[32 * p];
+      PD_UNROLL for (int r = 0; r < 4; r++) { if (p < 2) R.we[4 * p + r] = u2f(v[r]); else R.wo[4 * (p - 2) + r] = u2f(v[r]); }
+    }
+  } else {
+    PD_UNROLL for (int k = 0; k < 8; k++) { R.we[k] = S.taps[tab_tap_index(k, lane & 31)]; R.wo[k] = S.taps[tab_tap_index(8 + k, lane & 31)]; }
+  }
   float E[18], O[18];
   PD_UNROLL for (int t = 0; t < 18; t++) { E[t] = L.hyb[ch][t][R.idx_e]; O[t] = L.hyb[ch][t][R.idx_o]; }
   PD_UNROLL for (int t = 0; t < 18; t++) {
@@ -2079,7 +2183,8 @@ PD_SLOW_FN void gran_slow_chunk(DecodeArgs a, GlobalTables T, BankPtr cb, int f,
 // halo_in: the range's first granule when no halo frame can be run in front of it (mono frames there): the state at
 // its start is derived by this wave the independent way (run_chunk's halo as a called function);
 // g_pf: the granule whose input is asked for while this one is windowed (this wave's next), -1: none.
-template <bool F32, bool RING = false>
+// SCTAB: the band scales of the wave's own granule from the workgroup's tables (GranPos::sc, ph_scales_tab)
+template <bool F32, bool RING = false, bool SCTAB = false>
 PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, int g, WaveData& L, TabLds& S, const GranPos& gp,
                        bool fresh, bool h5, bool next_takes, const LaneRegs& pf, LaneRegs* Rp = nullptr, bool emit = true,
                        bool zero_in = false, bool halo_in = false, int g_pf = -1) {
@@ -2123,7 +2228,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
       R1.ovl[0] = 0.0f;
       PD_PHASE(ph_prefetch(lane, R1, a.spectra + (size_t)(g - 1) * 1152, a.side + (size_t)(g - 1) * 2))
       PD_PHASE(ph_commit(lane, L, R1))
-      PD_PHASE(ph_scales(lane, L))
+      PD_PHASE(if (SCTAB) ph_scales_tab(lane, L, *gp.sc); else ph_scales(lane, L))
       PD_PHASE((ph_requant<false, 1, false, true, false, false>(lane, L, S, cb, T, nullptr, nullptr)))
       PD_PHASE(ph_antialias(lane, L, cb, true))
       PD_PHASE(ph_peek_tail(lane, L, S, R1, T))
@@ -2138,7 +2243,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
       PD_PHASE(ph_prefetch(lane, R0, a.spectra + (size_t)(g - 1) * 1152, a.side + (size_t)(g - 1) * 2))
       if (fresh && f == 0 && a.state_in && !(reinterpret_cast<const uint8_t*>(a.side)[7] & PDMP3_FR_RESET) && lane < 3) tail = a.state_in[lane];
       PD_PHASE(ph_commit(lane, L, R0))
-      PD_PHASE(ph_scales(lane, L))
+      PD_PHASE(if (SCTAB) ph_scales_tab(lane, L, *gp.sc); else ph_scales(lane, L))
       PD_PHASE((ph_requant<false, 1, false, true, false, false>(lane, L, S, cb, T, nullptr, nullptr)))
       PD_PHASE(ph_antialias(lane, L, cb, true))
       const float head = ph_peek_head(lane, L, S, T);
@@ -2160,7 +2265,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
   PD_LAUNDER(cb);
   const GranuleInfo gi = granule_info<false>(L);  // (the granule's facts, read once for the three phases that want them; frames that are
                                                   //  frame_is_rare() do not come this way: run_granule_wave)
-  if (!(PD_EXP_SKIP & 1)) { PD_PHASE((ph_requant<false, 9, true, true, true, false>(lane, L, S, cb, T, nullptr, nullptr, &gi))) }
+  if (!(PD_EXP_SKIP & 1)) { PD_PHASE((ph_requant<false, 9, true, true, true, false, SCTAB>(lane, L, S, cb, T, nullptr, nullptr, &gi, gp.sc))) }
   PD_GT(3)
   // A SIMD issues from its OLDEST wave first: of the four waves that share one -- places w, w + 4, w + 8, w + 12 of the
   // workgroup -- the first gets through requantisation in 5 k ticks and the last in 12 k (profiles/r04_gran_profile.txt),
@@ -2269,7 +2374,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
 // The wave of granule g: which way its frame goes (wave-uniform facts from the side records; both waves of a frame
 // decide alike).  gp = this granule's place; pf = its input, prefetched.
 // RING: see run_granule; g_emit = the range's first granule proper (granules before it are its halo frame).
-template <bool F32, bool RING = false>
+template <bool F32, bool RING = false, bool SCTAB = false>
 PD_FN void run_granule_wave(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, int g, WaveData& L, TabLds& S, const GranPos& gp,
                             const LaneRegs& pf, LaneRegs* Rp = nullptr, int g_emit = 0, bool halo_by_wave = false, int g_pf = -1) {
   const int f = g >> 1, gr = g & 1;
@@ -2296,9 +2401,9 @@ PD_FN void run_granule_wave(const DecodeArgs& a, const GlobalTables& T, BankPtr 
     if (RING) {
       if (g + 1 >= gp.g_end) next_takes = false;          // (the next range derives its opening state itself)
       const bool halo_frame = g < g_emit;                 // (then this frame is chained or fresh: run_granule_ring chose it so)
-      run_granule<F32, true>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf, Rp, !halo_frame, halo_frame && gr == 0 && !fresh,
+      run_granule<F32, true, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf, Rp, !halo_frame, halo_frame && gr == 0 && !fresh,
                              halo_by_wave && g == g_emit && !fresh, g_pf);
-    } else run_granule<F32, false>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf);
+    } else run_granule<F32, false, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf);
     return;
   }
   if (gr == 0) {                                             // the frame is decoded by the wave of its first granule

@@ -145,7 +145,8 @@ __device__ __forceinline__ void gran_workgroup(const GranArgs& ga, unsigned long
   __shared__ TabLds S;
   __shared__ GranMb mb[W];
   __shared__ unsigned tabs_ready;
-  static_assert(sizeof(WaveData) * W + sizeof(TabLds) + sizeof(GranMb) * W + 16 <= 160 * 1024, "one workgroup of 16 waves per CU");
+  __shared__ ScaleTabs G;                // (the band scales' tables: decode_core.h ph_scales_tab)
+  static_assert(sizeof(WaveData) * W + sizeof(TabLds) + sizeof(GranMb) * W + sizeof(ScaleTabs) + 16 <= 160 * 1024, "one workgroup of 16 waves per CU");
   const int tid = (int)threadIdx.x;
   const unsigned long long t_entry = PROF ? PD_CLOCK() : 0ull;     // (read before the kernel arguments have arrived: the first phase holds their round trip)
   const int w = tid >> 6;
@@ -161,13 +162,14 @@ __device__ __forceinline__ void gran_workgroup(const GranArgs& ga, unsigned long
   // one read the global line table).  No barrier behind the loads: each wave counts itself in when its part is
   // stored (GranPos::tabs_ready) and whoever needs the tables waits for the count -- by then it is long there
   tab_load_image(tid, 64 * W, S, T, a.sf_hint);
+  if (PD_GRAN_SCALE_TABS) scale_tabs_load(tid, 64 * W, G, T);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   if ((tid & 63) == 0) atomicAdd(&tabs_ready, 1u);
   if (!valid) return;
   if (PROF && (tid & 63) == 0) a.prof[(size_t)g * kProfSlots] = t_entry;
-  const GranPos gp{L, mb, w, W, &tabs_ready};
-  run_granule_wave<F32>(a, T, (BankPtr)&c_bank, g, L[w], S, gp, pf);
+  const GranPos gp{L, mb, w, W, &tabs_ready, 0, 0, 0, &G};
+  run_granule_wave<F32, false, PD_GRAN_SCALE_TABS != 0>(a, T, (BankPtr)&c_bank, g, L[w], S, gp, pf);
 }
 
 template <bool F32, int W>
@@ -386,7 +388,7 @@ extern "C" int pdmp3_hip_create(int device, pdmp3_hip_ctx** out) {
     if (H.pow43.size() * sizeof(float) != kTabPow43Bytes || H.linetab.size() * sizeof(uint16_t) != kTabLinetabBytes ||
         H.win.size() * sizeof(float) != kTabWinBytes || H.frag_long.size() != (size_t)kFragShort || H.frag_short.size() != (size_t)(kFragMat - kFragShort) ||
         H.frag_mat.size() != (size_t)(kFragTaps - kFragMat) || H.taps.size() != (size_t)(kFragFloats - kFragTaps) ||
-        H.tab_image.size() * sizeof(TabLds) != kTabImageBytes) { what = "the host tables do not have the sizes of the device layout"; break; }
+        H.tab_image.size() * sizeof(TabLds) < kTabImageBytes || H.tab_image.size() != (size_t)kNumSfreq + kScaleTabImages) { what = "the host tables do not have the sizes of the device layout"; break; }
     CREATE_STEP(hipMalloc((void**)&c->d_tables, kTabBytes), "hipMalloc tables")
     CREATE_STEP(hipMemset(c->d_tables, 0, kTabBytes), "hipMemset tables")
     CREATE_STEP(hipMalloc((void**)&c->d_unpack, sizeof(UnpackTables)), "hipMalloc unpack tables")

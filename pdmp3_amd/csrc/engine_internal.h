@@ -63,7 +63,7 @@ constexpr size_t kTabLinetabBytes = pdmp3::kNumSfreq * 3 * 576 * sizeof(uint16_t
 constexpr size_t kTabWinBytes = 4 * 36 * sizeof(float);                  // win [4][36]
 constexpr int kFragShort = 10 * 64, kFragMat = 20 * 64, kFragTaps = 28 * 64, kFragFloats = 44 * 64;   // frag_long [10][64] | frag_short [10][64] | frag_mat [8][64] | taps [16][64]
 constexpr size_t kTabFragBytes = kFragFloats * sizeof(float);
-constexpr size_t kTabImageBytes = pdmp3::kNumSfreq * sizeof(pdmp3::TabLds);   // [kNumSfreq] TabLds images
+constexpr size_t kTabImageBytes = pdmp3::kNumSfreq * sizeof(pdmp3::TabLds) + sizeof(pdmp3::ScaleTabs);   // [kNumSfreq] TabLds images | the ScaleTabs image
 constexpr size_t tab_align(size_t n) { return (n + 255) & ~(size_t)255; }
 constexpr size_t kTabOffPow43 = 0;
 constexpr size_t kTabOffLinetab = tab_align(kTabOffPow43 + kTabPow43Bytes);

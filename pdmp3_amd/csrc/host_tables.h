@@ -33,7 +33,8 @@ struct HostTables {
   std::vector<float> win;          // 4*36
   std::vector<float> frag_long, frag_short, frag_mat;   // MFMA B fragments, [fragment][64 lanes]
   std::vector<float> taps;         // [16][64]: per-lane window coefficients (decode_core.h lane_init)
-  std::vector<TabLds> tab_image;   // [kNumSfreq]: what the kernels copy to LDS (decode_core.h tab_load_image)
+  std::vector<TabLds> tab_image;   // [kNumSfreq]: what the kernels copy to LDS (decode_core.h tab_load_image); behind them,
+                                   //   in kScaleTabImages more, the image of ScaleTabs (scale_tabs_load)
   // the reference's libm expressions, kept to verify the device's ldexp forms
   // (decode_core.h: pow2_neg_half / pow2_quarter) over their whole index range
   std::vector<float> t1, t2;
@@ -162,7 +163,25 @@ inline void build_tab_images(HostTables& H) {
       H.taps[(8 + k) * 64 + lane] = -kSynthD[64 * k + 32 + i];
     }
   }
-  H.tab_image.resize(kNumSfreq);
+  // the band scales' tables of the granule kernel (decode_core.h ScaleTabs) behind the kNumSfreq images: ph_scales' own
+  // functions over their whole index range, held against the reference's libm expressions like the functions themselves
+  H.tab_image.resize(kNumSfreq + kScaleTabImages);
+  memset(&H.tab_image[kNumSfreq], 0, kScaleTabImages * sizeof(TabLds));
+  {
+    ScaleTabs G;
+    memset(&G, 0, sizeof G);
+    for (int n = 0; n <= kScaleT1Max; n++) {
+      G.t1[n] = pow2_neg_half((uint32_t)n);
+      if (f2u(G.t1[n]) != f2u(H.t1[n])) H.ldexp_forms_exact = false;
+    }
+    if (f2u(G.t1[kScaleT1Max]) != 0u) H.ldexp_forms_exact = false;         // (what every n beyond reads)
+    for (int k = kScaleT2Min; k <= kScaleT2Max; k++) {
+      G.t2[k - kScaleT2Min] = pow2_quarter(k);
+      if (f2u(G.t2[k - kScaleT2Min]) != f2u(H.t2[k + 266])) H.ldexp_forms_exact = false;
+    }
+    for (int lane = 0; lane < 64; lane++) G.lane[lane] = scale_lane_const(lane);
+    memcpy(&H.tab_image[kNumSfreq], &G, sizeof G);
+  }
   for (int sf = 0; sf < kNumSfreq; sf++) {
     TabLds& S = H.tab_image[sf];
     memset(&S, 0, sizeof S);
@@ -179,7 +198,7 @@ inline void build_tab_images(HostTables& H) {
           S.bandaddr[f][i][lane] = (uint8_t)((H.linetab[(size_t)f * 3 * 576 + fast_line(lane, i)] >> 10) << 2);
     S.sfreq = sf;
     for (int k = 0; k < 16; k++)
-      for (int i = 0; i < 32; i++) S.taps[k][i] = H.taps[k * 64 + i];
+      for (int i = 0; i < 32; i++) S.taps[tab_tap_index(k, i)] = H.taps[k * 64 + i];
   }
 }
 
