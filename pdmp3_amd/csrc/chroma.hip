@@ -1,8 +1,8 @@
 // chroma.hip -- k_clip_chroma: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's
 // third audio stage) to pitch-class profiles, planar float32 [n_chroma][n_frames] per clip and channel
 // (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_chroma).  Launched by stream.hip
-// pdmp3_hip_clip_chroma.  A translation unit of its own, so that every other kernel's code -- k_clip_cqt's too -- is what it
-// is without it.  The tile loop is cqt.hip's cqt_tile: the same rows, segments and order of the partial sums (cqt_core.h) and
+// pdmp3_hip_clip_chroma.  A translation unit of its own.  The span's load is clip_tile.h's and the tile loop cqt_rows.h's
+// cqt_tiles, one source for this kernel and k_clip_cqt: the same rows, segments and order of the partial sums (cqt_core.h) and
 // the same stft_value (stft_core.h), so a bin's value of a frame is the binary32 number k_clip_cqt stores; it goes to LDS,
 // and the fold, the norms and the quotient behind it are chroma_core.h's.
 #include <hip/hip_runtime.h>
@@ -27,8 +27,9 @@ __device__ __forceinline__ void chroma_keep(const pdmp3_cqt_params& P, float* q,
 }
 
 // One workgroup of eight waves per (tile of P.tile frames, channel, clip).
-//   1. - 3. cqt.hip's cqt_tile: the span to LDS once, the split tiles over the eight waves' segments of rows and their planes
-//      added in one fixed order, the other tiles whole to one wave each, round robin -- every value to the q plane;
+//   1. - 3. as cqt.hip's cqt_tile (cqt_tiles with chroma_keep for the sink): the span to LDS once, the split tiles over the
+//      eight waves' segments of rows and their planes added in one fixed order, the other tiles whole to one wave each,
+//      round robin -- every value to the q plane;
 //   4. a barrier; value i = 16 p + fl of the n_chroma x 16: the bins of class p of frame fl added in ascending k
 //      (chroma_fold), into the class plane, which lies over the partial sums: nobody reads those behind the barrier;
 //   5. a barrier; each lane forms its frame's d over the classes in ascending order (chroma_norm_of) and stores
@@ -50,24 +51,11 @@ __device__ __forceinline__ void chroma_tile(const pdmp3_mel_desc& d, const float
 
   const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows0;
   const unsigned last = mel_lds_at(n_span - 1, hop, pad);
-  for (unsigned p = tid; p < n_span; p += kCqtThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load<kCqtThreads>(span, row, P.n_in, f0, P.hop, pad, d.lead, n_span, tid);
   __syncthreads();
 
-  for (int t = 0; t < P.n_split; t++) {
-    const int R = P.tile_rows[t];
-    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], cqt_seg_begin(R, wave), cqt_seg_begin(R, wave + 1), hop, chunk, last,
-             jf, j, kq, pw);
-    __syncthreads();
-    if (tid < 256) chroma_keep(P, q, part, kCqtWaves, t, tid);
-    __syncthreads();                                   // (the next tile's partial sums go to the same planes)
-  }
-  for (int t = P.n_split + wave; t < P.n_tiles; t += kCqtWaves) {
-    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], 0, P.tile_rows[t], hop, chunk, last, jf, j, kq, pw);
-    wave_sync();
-#pragma unroll
-    for (int it = 0; it < 4; it++) chroma_keep(P, q, pw, 1, t, 64 * it + lane);
-    wave_sync();
-  }
+  cqt_tiles(span, tab, P, hop, chunk, last, jf, tid, wave, lane, j, kq, part, pw,
+            [&](const float* planes, int parts, int t, int i) { chroma_keep(P, q, planes, parts, t, i); });
   __syncthreads();                                     // the q plane is whole, the partial sums are free
 
   const int n_val = S.n_chroma << 4, fl = tid & 15;    // (512 is a multiple of 16: a lane's values are all of frame fl)
@@ -84,9 +72,9 @@ __device__ __forceinline__ void chroma_tile(const pdmp3_mel_desc& d, const float
   }
 }
 
-__global__ __launch_bounds__(kCqtThreads) void k_clip_chroma(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
-                                                             pdmp3_chroma_params S) {
-  extern __shared__ __align__(16) float lds[];
+// a workgroup's (tile, channel, clip)
+__device__ __forceinline__ void chroma_entry(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab, const pdmp3_chroma_params& S,
+                                             float* lds) {
   const pdmp3_mel_desc d = descs[blockIdx.y];
   const int ch = blockIdx.x % S.cqt.channels;
   const long long f0 = (long long)(blockIdx.x / S.cqt.channels) * S.cqt.tile;
@@ -94,16 +82,18 @@ __global__ __launch_bounds__(kCqtThreads) void k_clip_chroma(const pdmp3_mel_des
   chroma_tile(d, tab, S, ch, f0, lds);
 }
 
+__global__ __launch_bounds__(kCqtThreads) void k_clip_chroma(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
+                                                             pdmp3_chroma_params S) {
+  extern __shared__ __align__(16) float lds[];
+  chroma_entry(descs, tab, S, lds);
+}
+
 // A plan of more than the 64 KB a launch can ask for dynamically: the same code on a static array of all the LDS a workgroup
 // may have, one workgroup a CU.
 __global__ __launch_bounds__(kCqtThreads) void k_clip_chroma_big(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
                                                                  pdmp3_chroma_params S) {
   __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
-  const pdmp3_mel_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % S.cqt.channels;
-  const long long f0 = (long long)(blockIdx.x / S.cqt.channels) * S.cqt.tile;
-  if (f0 >= S.cqt.n_frames) return;
-  chroma_tile(d, tab, S, ch, f0, lds);
+  chroma_entry(descs, tab, S, lds);
 }
 
 }  // namespace
@@ -116,9 +106,6 @@ hipError_t pdmp3_launch_clip_chroma(hipStream_t s, const pdmp3_mel_desc* descs, 
   if ((P.tile != 16 && P.tile != 8 && P.tile != 4) || P.lds_bytes > PDMP3_MEL_LDS_MAX || P.n_tiles < 1 || P.n_tiles > PDMP3_CQT_MAX_TILES ||
       P.n_split < 0 || P.n_split > P.n_tiles || (P.out_mode != 1 && P.out_mode != 2) || S.n_chroma < 1 || S.r < 1)
     return hipErrorInvalidValue;
-  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
-  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
-  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) hipLaunchKernelGGL(k_clip_chroma_big, grid, dim3(pdmp3::kCqtThreads), 0, s, descs, table, S);
-  else hipLaunchKernelGGL(k_clip_chroma, grid, dim3(pdmp3::kCqtThreads), P.lds_bytes, s, descs, table, S);
-  return hipGetLastError();
+  return pdmp3::launch_clip_pair(k_clip_chroma, k_clip_chroma_big, s, pdmp3::kCqtThreads, P.n_frames, P.tile, P.channels, n_clips, P.lds_bytes,
+                                 descs, table, S);
 }

@@ -1,9 +1,10 @@
 // cqt.hip -- k_clip_cqt: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's third
 // audio stage) to their constant-Q transform, planar float32 [n_bins][n_frames] per clip and channel -- complex
 // ([n_bins][n_frames][2]), magnitude, power or its logarithm (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt; DESIGN.md
-// section 16).  Launched by stream.hip pdmp3_hip_clip_cqt.  A translation unit of its own, so that every other kernel's code
-// is what it is without it; the span's indexing is mel_core.h's, what is stored stft_core.h's, the segments and the order of
-// the partial sums cqt_core.h's, the rows of a tile cqt_rows.h's (shared with chroma.hip).
+// section 16).  Launched by stream.hip pdmp3_hip_clip_cqt.  A translation unit of its own; the span's load is clip_tile.h's,
+// the rows of a tile and the loop over the tiles cqt_rows.h's (one source for this kernel and k_clip_chroma, which keeps the
+// values this one stores); the span's indexing is mel_core.h's, what is stored stft_core.h's, the segments and the order of
+// the partial sums cqt_core.h's.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
@@ -13,8 +14,6 @@ namespace {
 
 using namespace pdmp3;
 
-// a (Re, Im) pair of the output: one 8-byte store; a row may start at any float, and the device stores 8 bytes at 4-byte alignment
-typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
 // value i of a tile's 16 bins x 16 frames: the partial sums of `parts` waves added in cqt_reduce's order, turned into what is
 // stored (stft_value; mode 0: the pair); consecutive lanes store consecutive frames of one bin.  Bins from n_bins on and
 // frames from the tile's and from F on are not stored.
@@ -35,6 +34,7 @@ __device__ __forceinline__ void cqt_store(const pdmp3_cqt_params& P, float* out,
 //      (cqt_seg_begin) and writes its 16 x 16 partial sums of Re and of Im to its plane; after a barrier the first four waves
 //      add the eight planes in one fixed order and store; a second barrier frees the planes;
 //   3. the other tiles go whole to one wave each, round robin, through the wave's own plane: no workgroup barrier.
+// (2 and 3 are cqt_rows.h's cqt_tiles with cqt_store for the sink.)
 // The order of operations of a value depends on the plan alone: every frame's values come from the same chains whatever its
 // place in a tile, clip or batch.
 __device__ __forceinline__ void cqt_tile(const pdmp3_mel_desc& d, const float* __restrict__ tab, const pdmp3_cqt_params& P, int ch, long long f0,
@@ -50,35 +50,28 @@ __device__ __forceinline__ void cqt_tile(const pdmp3_mel_desc& d, const float* _
 
   const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows0;
   const unsigned last = mel_lds_at(n_span - 1, hop, pad);
-  for (unsigned p = tid; p < n_span; p += kCqtThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load<kCqtThreads>(span, row, P.n_in, f0, P.hop, pad, d.lead, n_span, tid);
   __syncthreads();
 
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
-  for (int t = 0; t < P.n_split; t++) {
-    const int R = P.tile_rows[t];
-    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], cqt_seg_begin(R, wave), cqt_seg_begin(R, wave + 1), hop, chunk, last,
-             jf, j, kq, pw);
-    __syncthreads();
-    if (tid < 256) cqt_store(P, out, part, kCqtWaves, t, f0, tid);
-    __syncthreads();                                   // (the next tile's partial sums go to the same planes)
-  }
-  for (int t = P.n_split + wave; t < P.n_tiles; t += kCqtWaves) {
-    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], 0, P.tile_rows[t], hop, chunk, last, jf, j, kq, pw);
-    wave_sync();
-#pragma unroll
-    for (int it = 0; it < 4; it++) cqt_store(P, out, pw, 1, t, f0, 64 * it + lane);
-    wave_sync();
-  }
+  cqt_tiles(span, tab, P, hop, chunk, last, jf, tid, wave, lane, j, kq, part, pw,
+            [&](const float* planes, int parts, int t, int i) { cqt_store(P, out, planes, parts, t, f0, i); });
 }
 
-__global__ __launch_bounds__(kCqtThreads) void k_clip_cqt(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
-                                                          pdmp3_cqt_params P) {
-  extern __shared__ __align__(16) float lds[];
+// a workgroup's (tile, channel, clip)
+__device__ __forceinline__ void cqt_entry(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab, const pdmp3_cqt_params& P,
+                                          float* lds) {
   const pdmp3_mel_desc d = descs[blockIdx.y];
   const int ch = blockIdx.x % P.channels;
   const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
   if (f0 >= P.n_frames) return;
   cqt_tile(d, tab, P, ch, f0, lds);
+}
+
+__global__ __launch_bounds__(kCqtThreads) void k_clip_cqt(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
+                                                          pdmp3_cqt_params P) {
+  extern __shared__ __align__(16) float lds[];
+  cqt_entry(descs, tab, P, lds);
 }
 
 // A plan of more than the 64 KB a launch can ask for dynamically (the low octaves: C1 at 22 050 Hz is 95.5 KB): the same code
@@ -86,11 +79,7 @@ __global__ __launch_bounds__(kCqtThreads) void k_clip_cqt(const pdmp3_mel_desc* 
 __global__ __launch_bounds__(kCqtThreads) void k_clip_cqt_big(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
                                                               pdmp3_cqt_params P) {
   __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
-  const pdmp3_mel_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
-  if (f0 >= P.n_frames) return;
-  cqt_tile(d, tab, P, ch, f0, lds);
+  cqt_entry(descs, tab, P, lds);
 }
 
 }  // namespace
@@ -102,9 +91,6 @@ hipError_t pdmp3_launch_clip_cqt(hipStream_t s, const pdmp3_mel_desc* descs, int
   if ((P.tile != 16 && P.tile != 8 && P.tile != 4) || P.lds_bytes > PDMP3_MEL_LDS_MAX || P.n_tiles < 1 || P.n_tiles > PDMP3_CQT_MAX_TILES ||
       P.n_split < 0 || P.n_split > P.n_tiles)
     return hipErrorInvalidValue;
-  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
-  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
-  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) hipLaunchKernelGGL(k_clip_cqt_big, grid, dim3(pdmp3::kCqtThreads), 0, s, descs, table, P);
-  else hipLaunchKernelGGL(k_clip_cqt, grid, dim3(pdmp3::kCqtThreads), P.lds_bytes, s, descs, table, P);
-  return hipGetLastError();
+  return pdmp3::launch_clip_pair(k_clip_cqt, k_clip_cqt_big, s, pdmp3::kCqtThreads, P.n_frames, P.tile, P.channels, n_clips, P.lds_bytes, descs,
+                                 table, P);
 }

@@ -1,25 +1,13 @@
-// cqt_rows.h -- device code shared by k_clip_cqt (cqt.hip) and k_clip_chroma (chroma.hip): the matrix instruction, the wave's
-// own synchronisation and the rows of a tile of 16 bins times the workgroup's 16 frames.  One source, so that a bin's value of a
-// frame is the same binary32 number in both kernels (DESIGN.md sections 16 and 17).  HIP only; the indexing and the arithmetic
-// that the host build shares are cqt_core.h's.
+// cqt_rows.h -- device code shared by k_clip_cqt (cqt.hip) and k_clip_chroma (chroma.hip): the rows of a tile of 16 bins times
+// the workgroup's 16 frames, and the loop over a plan's tiles with its barriers.  One source, so that a bin's value of a frame
+// is the same binary32 number in both kernels (DESIGN.md sections 16 and 17).  HIP only; the matrix instruction and the wave's
+// own synchronisation are clip_tile.h's, the indexing and the arithmetic that the host build shares cqt_core.h's.
 #ifndef PDMP3_CQT_ROWS_H
 #define PDMP3_CQT_ROWS_H
-#include <hip/hip_runtime.h>
-
+#include "clip_tile.h"
 #include "cqt_core.h"
 
 namespace pdmp3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// what a wave's lanes wrote to its plane is there for its other lanes (LDS operations of a wave complete in order)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Rows [r0, r1) of a tile of 16 bins (r0, r1 multiples of 4) times the 16 frames of the workgroup, Re and Im each one chain
 // from +0, rows ascending, into the wave's plane `pw`.  The frames are overlapping rows of the span: the A operand is read at
@@ -72,6 +60,33 @@ __device__ __forceinline__ void cqt_rows(const float* span, const float* __restr
   for (int r = 0; r < 4; r++) {
     pw[cqt_part_at(j, 4 * kq + r)] = re[r];
     pw[kCqtPlane + cqt_part_at(j, 4 * kq + r)] = im[r];
+  }
+}
+
+// The tiles of a plan, the span being in LDS.
+//   - the first n_split tiles of 16 bins, the long ones: each wave takes one of eight runs of the tile's rows (cqt_seg_begin)
+//     and writes its 16 x 16 partial sums of Re and of Im to its plane `pw` of `part`; after a barrier the first four waves
+//     hand the eight planes' 256 values to the sink; a second barrier frees the planes;
+//   - the other tiles go whole to one wave each, round robin, through the wave's own plane: no workgroup barrier.
+// sink(planes, parts, t, i): value i of tile t's 16 bins x 16 frames, to be added over `parts` planes in cqt_reduce's order.
+template <class Sink>
+__device__ __forceinline__ void cqt_tiles(const float* span, const float* __restrict__ tab, const pdmp3_cqt_params& P, unsigned hop, unsigned chunk,
+                                          unsigned last, unsigned jf, int tid, int wave, int lane, int j, int kq, float* part, float* pw,
+                                          Sink sink) {
+  for (int t = 0; t < P.n_split; t++) {
+    const int R = P.tile_rows[t];
+    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], cqt_seg_begin(R, wave), cqt_seg_begin(R, wave + 1), hop, chunk, last,
+             jf, j, kq, pw);
+    __syncthreads();
+    if (tid < 256) sink(part, kCqtWaves, t, tid);
+    __syncthreads();                                   // (the next tile's partial sums go to the same planes)
+  }
+  for (int t = P.n_split + wave; t < P.n_tiles; t += kCqtWaves) {
+    cqt_rows(span, tab + (size_t)P.tile_at[t] * 32, (unsigned)P.tile_base[t], 0, P.tile_rows[t], hop, chunk, last, jf, j, kq, pw);
+    wave_sync();
+#pragma unroll
+    for (int it = 0; it < 4; it++) sink(pw, 1, t, 64 * it + lane);
+    wave_sync();
   }
 }
 

@@ -1,44 +1,34 @@
 // fbank.hip -- k_clip_fbank: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's
 // third audio stage) to Kaldi-style filterbank features, planar float32 [n_frames][D] per clip and channel, coefficients
 // innermost (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_fbank).  Launched by stream.hip
-// pdmp3_hip_clip_fbank.  A translation unit of its own, so that every other kernel's code is what it is without it; the two
-// matrix stages are k_clip_mel's (mel.hip), restated here rather than shared through a header for the same reason; the
-// indexing and pointwise arithmetic are mel_core.h's and fbank_core.h's.
+// pdmp3_hip_clip_fbank.  A translation unit of its own; the span's load and the two matrix stages are k_clip_mel's, the energy
+// stage, the column sums and the finishing pass k_clip_mfcc's too: all of them clip_tile.h's, one source inlined here, so that
+// a change to a stage is made once and k_clip_mfcc's stages 1 .. 4 stay these bit for bit; the indexing and pointwise
+// arithmetic are mel_core.h's and fbank_core.h's.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
-#include "fbank_core.h"
+#include "clip_tile.h"
 
 namespace {
 
 using namespace pdmp3;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// every lane of the wave gets the sum of the 64 values, added pairwise in one fixed order
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = kFbankWave / 2; off; off >>= 1) v = v + __shfl_xor(v, off, kFbankWave);
-  return v;
-}
-
 // One workgroup of four waves per (tile of P.tile = 16 RT frames, channel, clip).
 //   1. the tile's span -- (tile - 1) hop + rows samples from the clip's row, zeros behind it -- goes to LDS once (mel_lds_at);
-//   2. energy (use_energy): a wave per frame, the mean and then sum (s - mean)^2 in a fixed lane and shuffle order; a frame's
-//      value does not depend on its place.  It waits in the spare float behind the frame's row of powers;
-//   3. DFT: the frames are overlapping rows of the span; the B operand is the folded table (DC removal, pre-emphasis, window
-//      and zero padding in it) from memory, `rows` rows of it.  Re^2 + Im^2 goes to LDS [frame][bin];
-//   4. filterbank: A = the powers, B = the transposed padded filterbank from memory; the mel tile goes to LDS [band][frames + 1]
-//      over the span, which nobody reads any more;
+//   2. energy (use_energy; tile_energy): a wave per frame, the mean and then sum (s - mean)^2 in a fixed lane and shuffle
+//      order; a frame's value does not depend on its place.  It waits in the spare float behind the frame's row of powers;
+//   3. DFT (tile_dft_power): the frames are overlapping rows of the span; the B operand is the folded table (DC removal,
+//      pre-emphasis, window and zero padding in it) from memory, `rows` rows of it.  Re^2 + Im^2 goes to LDS [frame][bin];
+//   4. filterbank (tile_filterbank): A = the powers, B = the transposed padded filterbank from memory; the mel tile goes to LDS
+//      [band][frames + 1] over the span, which nobody reads any more;
 //   5. floor, logarithm, stores: consecutive lanes write consecutive coefficients of one frame (the odd stride of the mel tile
 //      keeps those LDS reads free of bank conflicts); the energy goes into its column;
-//   6. subtract_mean: the stored values go back to LDS, and a lane per column adds those of the frames f < valid, in frame order,
-//      into the tile's row of `tile_sums`; k_clip_fbank_finish does the rest.
+//   6. subtract_mean: the stored values go back to LDS, and a lane per column adds those of the frames f < valid, in frame
+//      order, into the tile's row `ts` of the launch's scratch (tile_sums); k_clip_fbank_finish does the rest.
 template <int RT>
 __device__ __forceinline__ void fbank_tile(const pdmp3_fbank_desc& d, const float* __restrict__ dft, const float* __restrict__ fbt,
-                                           const pdmp3_fbank_params& P, int ch, long long f0, float* __restrict__ tile_sums, float* lds) {
+                                           const pdmp3_fbank_params& P, int ch, long long f0, float* __restrict__ ts, float* lds) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, kq = lane >> 4;
   const unsigned hop = (unsigned)P.hop, pad = (unsigned)P.row_pad, chunk = hop + pad;
   const int Kp = P.bins16, Mp = P.mels16, PS = Kp + 2, FT = 16 * RT, FTS = FT + 1;
@@ -46,63 +36,15 @@ __device__ __forceinline__ void fbank_tile(const pdmp3_fbank_desc& d, const floa
   float* const pw = lds + P.span_floats;
   const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
 
-  const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows;
-  for (unsigned p = tid; p < n_span; p += kMelThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, 0u, p);
+  span_load<kMelThreads>(span, row, P.n_in, f0, P.hop, pad, 0u, (unsigned)(FT - 1) * hop + (unsigned)P.rows, tid);
   __syncthreads();
 
-  if (P.use_energy) {
-    for (int fl = wave; fl < FT; fl += 4) {
-      const unsigned p0 = (unsigned)fl * hop;
-      float mean = 0.0f;
-      if (P.remove_dc) mean = fbank_mean(wave_sum(fbank_lane_sum(span, p0, P.win, hop, pad, P.scale, lane)), P.win);
-      const float e = wave_sum(fbank_lane_squares(span, p0, P.win, hop, pad, P.scale, mean, lane));
-      if (lane == 0) pw[fl * PS + Kp] = e;
-    }
-  }
-
-  const int ld = 2 * Kp;
-  for (int bt = wave; bt < (Kp >> 4); bt += 4) {
-    f32x4 re[RT], im[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) { re[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; im[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
-    // lane (j, kq) reads frame j's sample n + kq: position j hop + n + kq = c hop + rem
-    unsigned c = (unsigned)j + (unsigned)kq / hop, rem = (unsigned)kq % hop;
-    const float* bp = dft + (size_t)kq * ld + (bt << 4) + j;
-#pragma unroll 2
-    for (int n = 0; n < P.rows; n += 4) {
-      const float b_re = bp[0], b_im = bp[Kp];
-      bp += 4 * ld;
-      const float* ap = span + c * chunk + rem;
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const float a = ap[(unsigned)(16 * rt) * chunk];
-        re[rt] = mfma16(a, b_re, re[rt]);
-        im[rt] = mfma16(a, b_im, im[rt]);
-      }
-      rem += 4;
-      if (rem >= hop) {
-        if (hop >= 4) { rem -= hop; c++; }
-        else { c += rem / hop; rem %= hop; }
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) pw[(16 * rt + 4 * kq + r) * PS + (bt << 4) + j] = mel_power(re[rt][r], im[rt][r]);
-  }
+  tile_energy(span, P, FT, hop, pad, wave, lane, pw, PS, Kp);
+  tile_dft_power<RT>(span, dft, P.rows, Kp, hop, chunk, wave, j, kq, pw, PS);
   __syncthreads();
 
   float* const mt = lds;                               // [Mp][FTS]
-  for (int t = wave; t < RT * (Mp >> 4); t += 4) {
-    const int rt = t % RT, m0 = (t / RT) << 4;
-    f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* ap = pw + (16 * rt + j) * PS + kq;
-    const float* bp = fbt + (size_t)kq * Mp + m0 + j;
-#pragma unroll 4
-    for (int k = 0; k < Kp; k += 4) acc = mfma16(ap[k], bp[(size_t)k * Mp], acc);
-#pragma unroll
-    for (int r = 0; r < 4; r++) mt[(m0 + j) * FTS + 16 * rt + 4 * kq + r] = acc[r];
-  }
+  tile_filterbank<RT>(pw, PS, fbt, Kp, Mp, wave, j, kq, mt, FTS);
   __syncthreads();
 
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
@@ -119,34 +61,30 @@ __device__ __forceinline__ void fbank_tile(const pdmp3_fbank_desc& d, const floa
   }
   if (!P.subtract_mean) return;
   __syncthreads();
-  long long cnt = (long long)d.valid - f0;             // (valid <= n_frames)
-  cnt = cnt < 0 ? 0 : cnt > FT ? FT : cnt;
-  for (int dc = tid; dc < D; dc += kMelThreads) {
+  tile_sums(ts, D, d.valid, f0, FT, tid, [&](int dc, int* step) -> const float* {
     const int m = fbank_column_band(dc, P.n_mels, P.use_energy, P.htk_compat);
-    const float* const at = m < 0 ? pw + Kp : mt + m * FTS;
-    const int step = m < 0 ? PS : 1;
-    float s = 0.0f;
-    for (int fl = 0; fl < (int)cnt; fl++) s = s + at[fl * step];
-    tile_sums[dc] = s;
-  }
+    *step = m < 0 ? PS : 1;
+    return m < 0 ? pw + Kp : mt + m * FTS;
+  });
 }
 
-// the place of a (clip, channel, tile)'s column sums in the launch's scratch
-__device__ __forceinline__ float* sums_at(float* sums, const pdmp3_fbank_params& P, unsigned clip, int ch, unsigned tile, unsigned tiles) {
-  return sums + (((size_t)clip * (size_t)P.channels + (size_t)ch) * tiles + tile) * (size_t)(P.n_mels + P.use_energy);
+// a workgroup's (tile, channel, clip), its tile of `tile` frames and its row of the column sums
+__device__ __forceinline__ void fbank_entry(const pdmp3_fbank_desc* __restrict__ descs, const float* __restrict__ dft, const float* __restrict__ fbt,
+                                            float* __restrict__ sums, const pdmp3_fbank_params& P, int tile, float* lds) {
+  const pdmp3_fbank_desc d = descs[blockIdx.y];
+  const int ch = blockIdx.x % P.channels;
+  const unsigned t = blockIdx.x / P.channels, tiles = gridDim.x / P.channels;
+  const long long f0 = (long long)t * tile;
+  if (f0 >= P.n_frames) return;
+  float* const ts = sums_at(sums, P.channels, P.n_mels + P.use_energy, blockIdx.y, ch, t, tiles);
+  if (tile == 32) fbank_tile<2>(d, dft, fbt, P, ch, f0, ts, lds);
+  else fbank_tile<1>(d, dft, fbt, P, ch, f0, ts, lds);
 }
 
 __global__ __launch_bounds__(kMelThreads) void k_clip_fbank(const pdmp3_fbank_desc* __restrict__ descs, const float* __restrict__ dft,
                                                             const float* __restrict__ fbt, float* __restrict__ sums, pdmp3_fbank_params P) {
   extern __shared__ __align__(16) float lds[];
-  const pdmp3_fbank_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const unsigned t = blockIdx.x / P.channels, tiles = gridDim.x / P.channels;
-  const long long f0 = (long long)t * P.tile;
-  if (f0 >= P.n_frames) return;
-  float* const ts = sums_at(sums, P, blockIdx.y, ch, t, tiles);
-  if (P.tile == 32) fbank_tile<2>(d, dft, fbt, P, ch, f0, ts, lds);
-  else fbank_tile<1>(d, dft, fbt, P, ch, f0, ts, lds);
+  fbank_entry(descs, dft, fbt, sums, P, P.tile, lds);
 }
 
 // A tile of 16 frames that needs more than the 64 KB a launch can ask for dynamically (Nw = 1024 at hops above 450): the same
@@ -154,36 +92,13 @@ __global__ __launch_bounds__(kMelThreads) void k_clip_fbank(const pdmp3_fbank_de
 __global__ __launch_bounds__(kMelThreads) void k_clip_fbank_big(const pdmp3_fbank_desc* __restrict__ descs, const float* __restrict__ dft,
                                                                 const float* __restrict__ fbt, float* __restrict__ sums, pdmp3_fbank_params P) {
   __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
-  const pdmp3_fbank_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const unsigned t = blockIdx.x / P.channels, tiles = gridDim.x / P.channels;
-  const long long f0 = (long long)t * 16;
-  if (f0 >= P.n_frames) return;
-  fbank_tile<1>(d, dft, fbt, P, ch, f0, sums_at(sums, P, blockIdx.y, ch, t, tiles), lds);
+  fbank_entry(descs, dft, fbt, sums, P, 16, lds);
 }
 
-// subtract_mean, behind k_clip_fbank: every column's tile sums added in ascending order, divided by valid, and the mean
-// subtracted from every frame of the row.  No atomics: the result does not depend on the order the workgroups ran in.
+// subtract_mean, behind k_clip_fbank (tile_sums_finish)
 __global__ __launch_bounds__(kMelThreads) void k_clip_fbank_finish(const pdmp3_fbank_desc* __restrict__ descs, const float* __restrict__ sums,
                                                                    unsigned tiles, pdmp3_fbank_params P) {
-  __shared__ float mean[256 + 1];
-  const pdmp3_fbank_desc d = descs[blockIdx.y];
-  if (!d.valid) return;
-  const int D = P.n_mels + P.use_energy;
-  const long long per = (long long)D * P.n_frames;
-  for (int ch = 0; ch < P.channels; ch++) {
-    const float* const ts = sums + ((size_t)blockIdx.y * (size_t)P.channels + (size_t)ch) * tiles * (size_t)D;
-    for (int dc = threadIdx.x; dc < D; dc += kMelThreads) {
-      float s = 0.0f;
-      for (unsigned t = 0; t < tiles; t++) s = s + ts[(size_t)t * D + dc];
-      mean[dc] = fbank_column_mean(s, d.valid);
-    }
-    __syncthreads();
-    float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
-    for (long long i = (long long)blockIdx.x * kMelThreads + threadIdx.x; i < per; i += (long long)gridDim.x * kMelThreads)
-      out[i] = out[i] - mean[(int)(i % D)];
-    __syncthreads();
-  }
+  tile_sums_finish(descs, sums, tiles, P.n_mels + P.use_energy, P.channels, P.n_frames);
 }
 
 }  // namespace
@@ -192,19 +107,14 @@ hipError_t pdmp3_launch_clip_fbank(hipStream_t s, const pdmp3_fbank_desc* descs,
                                    const pdmp3_fbank_params* params) {
   const pdmp3_fbank_params P = *params;
   if (n_clips <= 0 || P.n_frames <= 0) return hipSuccess;
-  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
-  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
-  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) {
-    if (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_clip_fbank_big, grid, dim3(pdmp3::kMelThreads), 0, s, descs, dft, fbt, sums, P);
-  } else {
-    hipLaunchKernelGGL(k_clip_fbank, grid, dim3(pdmp3::kMelThreads), P.lds_bytes, s, descs, dft, fbt, sums, P);
-  }
-  hipError_t e = hipGetLastError();
+  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT && (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX)) return hipErrorInvalidValue;
+  const hipError_t e = pdmp3::launch_clip_pair(k_clip_fbank, k_clip_fbank_big, s, pdmp3::kMelThreads, P.n_frames, P.tile, P.channels, n_clips,
+                                               P.lds_bytes, descs, dft, fbt, sums, P);
   if (e != hipSuccess || !P.subtract_mean) return e;
   const long long per = (long long)(P.n_mels + P.use_energy) * P.n_frames;
   long long blocks = (per + 16 * pdmp3::kMelThreads - 1) / (16 * pdmp3::kMelThreads);
   if (blocks > 256) blocks = 256;
-  hipLaunchKernelGGL(k_clip_fbank_finish, dim3((unsigned)blocks, (unsigned)n_clips), dim3(pdmp3::kMelThreads), 0, s, descs, sums, tiles, P);
+  hipLaunchKernelGGL(k_clip_fbank_finish, dim3((unsigned)blocks, (unsigned)n_clips), dim3(pdmp3::kMelThreads), 0, s, descs, sums,
+                     pdmp3::clip_tiles(P.n_frames, P.tile), P);
   return hipGetLastError();
 }

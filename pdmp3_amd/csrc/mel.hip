@@ -1,29 +1,26 @@
 // mel.hip -- k_clip_mel: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's
 // third audio stage) to log-mel features, planar float32 [n_mels][n_frames] per clip and channel
 // (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_mel).  Launched by stream.hip pdmp3_hip_clip_mel.
-// A translation unit of its own, so that every other kernel's code is what it is without it; its indexing and pointwise
-// arithmetic are mel_core.h's.
+// A translation unit of its own; the span's load and the two matrix stages are clip_tile.h's, one source for this kernel,
+// k_clip_fbank and k_clip_mfcc (k_clip_stft has the first two), inlined here; the indexing and pointwise arithmetic are
+// mel_core.h's.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
-#include "mel_core.h"
+#include "clip_tile.h"
 
 namespace {
 
 using namespace pdmp3;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // One workgroup of four waves per (tile of P.tile = 16 RT frames, channel, clip).
 //   1. the tile's span -- (tile - 1) hop + rows samples, zeros outside the clip's row -- goes to LDS once (mel_lds_at);
-//   2. DFT: the frames are overlapping rows of the span, the A operand is read at f hop + n and never materialised; the B
-//      operand is the table (window folded in), read from memory (L2: every workgroup reads the same table).  A wave takes
-//      every fourth tile of 16 bins, Re and Im of all RT row tiles in registers; Re^2 + Im^2 goes to LDS [frame][bin];
-//   3. filterbank: A = the powers, B = the transposed padded filterbank from memory; the mel tile goes to LDS [band][frame]
-//      over the span, which nobody reads any more;
+//   2. DFT (tile_dft_power): the frames are overlapping rows of the span, the A operand is read at f hop + n and never
+//      materialised; the B operand is the table (window folded in), read from memory (L2: every workgroup reads the same
+//      table).  A wave takes every fourth tile of 16 bins, Re and Im of all RT row tiles in registers; Re^2 + Im^2 goes to LDS
+//      [frame][bin];
+//   3. filterbank (tile_filterbank): A = the powers, B = the transposed padded filterbank from memory; the mel tile goes to LDS
+//      [band][frame] over the span, which nobody reads any more;
 //   4. floor, logarithm, stores: consecutive lanes write consecutive frames of one band.  Mode 3 stores M and takes the
 //      row's maximum as an integer maximum of the floats' bits (M >= 0): one LDS atomic a lane, one global atomic a workgroup.
 // Every frame's values come from the same chains of operations whatever its place in the tile.
@@ -38,54 +35,15 @@ __device__ __forceinline__ void mel_tile(const pdmp3_mel_desc& d, const float* _
   float* const pw = lds + P.span_floats;
   const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
 
-  const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows;
-  for (unsigned p = tid; p < n_span; p += kMelThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load<kMelThreads>(span, row, P.n_in, f0, P.hop, pad, d.lead, (unsigned)(FT - 1) * hop + (unsigned)P.rows, tid);
   if (tid == 0) *smax = 0u;
   __syncthreads();
 
-  const int ld = 2 * Kp;
-  for (int bt = wave; bt < (Kp >> 4); bt += 4) {
-    f32x4 re[RT], im[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) { re[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; im[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
-    // lane (j, kq) reads frame j's sample n + kq: position j hop + n + kq = c hop + rem
-    unsigned c = (unsigned)j + (unsigned)kq / hop, rem = (unsigned)kq % hop;
-    const float* bp = dft + (size_t)kq * ld + (bt << 4) + j;
-#pragma unroll 2
-    for (int n = 0; n < P.rows; n += 4) {
-      const float b_re = bp[0], b_im = bp[Kp];
-      bp += 4 * ld;
-      const float* ap = span + c * chunk + rem;
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const float a = ap[(unsigned)(16 * rt) * chunk];
-        re[rt] = mfma16(a, b_re, re[rt]);
-        im[rt] = mfma16(a, b_im, im[rt]);
-      }
-      rem += 4;
-      if (rem >= hop) {
-        if (hop >= 4) { rem -= hop; c++; }
-        else { c += rem / hop; rem %= hop; }
-      }
-    }
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) pw[(16 * rt + 4 * kq + r) * PS + (bt << 4) + j] = mel_power(re[rt][r], im[rt][r]);
-  }
+  tile_dft_power<RT>(span, dft, P.rows, Kp, hop, chunk, wave, j, kq, pw, PS);
   __syncthreads();
 
   float* const mt = lds;                               // [Mp][FTS]
-  for (int t = wave; t < RT * (Mp >> 4); t += 4) {
-    const int rt = t % RT, m0 = (t / RT) << 4;
-    f32x4 acc = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* ap = pw + (16 * rt + j) * PS + kq;
-    const float* bp = fbt + (size_t)kq * Mp + m0 + j;
-#pragma unroll 4
-    for (int k = 0; k < Kp; k += 4) acc = mfma16(ap[k], bp[(size_t)k * Mp], acc);
-#pragma unroll
-    for (int r = 0; r < 4; r++) mt[(m0 + j) * FTS + 16 * rt + 4 * kq + r] = acc[r];
-  }
+  tile_filterbank<RT>(pw, PS, fbt, Kp, Mp, wave, j, kq, mt, FTS);
   __syncthreads();
 
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
@@ -105,16 +63,22 @@ __device__ __forceinline__ void mel_tile(const pdmp3_mel_desc& d, const float* _
   }
 }
 
-__global__ __launch_bounds__(kMelThreads) void k_clip_mel(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ dft,
-                                                          const float* __restrict__ fbt, unsigned* __restrict__ row_max, pdmp3_mel_params P) {
-  extern __shared__ __align__(16) float lds[];
+// a workgroup's (tile, channel, clip) and its tile of `tile` frames
+__device__ __forceinline__ void mel_entry(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ dft, const float* __restrict__ fbt,
+                                          unsigned* __restrict__ row_max, const pdmp3_mel_params& P, int tile, float* lds) {
   __shared__ unsigned smax;
   const pdmp3_mel_desc d = descs[blockIdx.y];
   const int ch = blockIdx.x % P.channels;
-  const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
+  const long long f0 = (long long)(blockIdx.x / P.channels) * tile;
   if (f0 >= P.n_frames) return;
-  if (P.tile == 32) mel_tile<2>(d, dft, fbt, P, ch, f0, row_max + blockIdx.y, lds, &smax);
+  if (tile == 32) mel_tile<2>(d, dft, fbt, P, ch, f0, row_max + blockIdx.y, lds, &smax);
   else mel_tile<1>(d, dft, fbt, P, ch, f0, row_max + blockIdx.y, lds, &smax);
+}
+
+__global__ __launch_bounds__(kMelThreads) void k_clip_mel(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ dft,
+                                                          const float* __restrict__ fbt, unsigned* __restrict__ row_max, pdmp3_mel_params P) {
+  extern __shared__ __align__(16) float lds[];
+  mel_entry(descs, dft, fbt, row_max, P, P.tile, lds);
 }
 
 // A tile of 16 frames that needs more than the 64 KB a launch can ask for dynamically (n_fft = 1024 at hops above 450): the
@@ -122,12 +86,7 @@ __global__ __launch_bounds__(kMelThreads) void k_clip_mel(const pdmp3_mel_desc* 
 __global__ __launch_bounds__(kMelThreads) void k_clip_mel_big(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ dft,
                                                               const float* __restrict__ fbt, unsigned* __restrict__ row_max, pdmp3_mel_params P) {
   __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
-  __shared__ unsigned smax;
-  const pdmp3_mel_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const long long f0 = (long long)(blockIdx.x / P.channels) * 16;
-  if (f0 >= P.n_frames) return;
-  mel_tile<1>(d, dft, fbt, P, ch, f0, row_max + blockIdx.y, lds, &smax);
+  mel_entry(descs, dft, fbt, row_max, P, 16, lds);
 }
 
 // mode 3, behind k_clip_mel: every M of a row to (max(log10 max(M, floor), g - 8) + 4) / 4 with the row's maximum
@@ -149,15 +108,9 @@ hipError_t pdmp3_launch_clip_mel(hipStream_t s, const pdmp3_mel_desc* descs, int
                                  const pdmp3_mel_params* params) {
   const pdmp3_mel_params P = *params;
   if (n_clips <= 0 || P.n_frames <= 0) return hipSuccess;
-  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
-  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
-  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) {
-    if (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_clip_mel_big, grid, dim3(pdmp3::kMelThreads), 0, s, descs, dft, fbt, row_max, P);
-  } else {
-    hipLaunchKernelGGL(k_clip_mel, grid, dim3(pdmp3::kMelThreads), P.lds_bytes, s, descs, dft, fbt, row_max, P);
-  }
-  hipError_t e = hipGetLastError();
+  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT && (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX)) return hipErrorInvalidValue;
+  const hipError_t e = pdmp3::launch_clip_pair(k_clip_mel, k_clip_mel_big, s, pdmp3::kMelThreads, P.n_frames, P.tile, P.channels, n_clips,
+                                               P.lds_bytes, descs, dft, fbt, row_max, P);
   if (e != hipSuccess || P.out_mode != 3) return e;
   const long long per = (long long)P.n_mels * P.n_frames;
   long long blocks = (per + pdmp3::kMelThreads - 1) / pdmp3::kMelThreads;

@@ -3,29 +3,26 @@
 // bin and the mel filterbank in one workgroup, the spectrum never leaving the CU.  Rows in are k_clip_stft_long's, the layout
 // out and the pointwise arithmetic k_clip_mel's (mel_core.h); the transform's index maps, Z's layout and the twiddle step are
 // stft_long_core.h's, the order of the bins and the power tile's layout mel_long_core.h's.  Launched by stream.hip
-// pdmp3_hip_clip_mel_long.  A translation unit of its own, so that every other kernel's code is what it is without it.
+// pdmp3_hip_clip_mel_long.  A translation unit of its own; the two stages are stft_long_stages.h's, one source for this
+// kernel and k_clip_stft_long, inlined here.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
 #include "mel_long_core.h"
+#include "stft_long_stages.h"
 
 namespace {
 
 using namespace pdmp3;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // One workgroup of eight waves per (tile of FT frames, channel, clip); n = N2 n1 + n2, k = k1 + 64 k2.  A band's sum runs over
 // all bins, so the four tiles of k1 cannot go to four workgroups as in k_clip_stft_long (floating-point atomics between them
 // would make a value depend on scheduling): this workgroup takes kt = 0 .. 3 one after the other.
 //   0. the tile's span -- (FT - 1) hop + N samples, zeros outside the clip's row -- goes to LDS once, plain, and stays;
 //   then for each kt:
-//   1. stage 1 as in k_clip_stft_long: the window product, the 64-term chains, the twiddle, into Z;
-//   2. stage 2 as there: the chains of 2 N2 terms; what a lane holds of X goes through mel_power into the power tile, at the
-//      slot mel_long_core.h gives the bin;
+//   1. stage 1 as in k_clip_stft_long (stftl_stage1): the window product, the 64-term chains, the twiddle, into Z;
+//   2. stage 2 as there (stftl_stage2_operand, stftl_stage2_chains): the chains of 2 N2 terms; what a lane holds of X goes
+//      through mel_power into the power tile, at the slot mel_long_core.h gives the bin;
 //   3. the filterbank: M^T = W^T P^T on the matrix instruction, rows the bands of one tile of 16, columns the frames, k the
 //      slots ascending -- A from the operand in memory (its rows are in slot order: 16 consecutive floats a row and band
 //      tile), B from the power tile.  A wave takes the band tiles wave and wave + 8 and carries their accumulators in
@@ -41,7 +38,7 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __bu
 template <int N2, int FT>
 __device__ __forceinline__ void mel_long_tile(const pdmp3_mel_desc& d, const float* __restrict__ tab, const float* __restrict__ op,
                                               const pdmp3_mel_long_params& P, int ch, long long f0, float* lds) {
-  constexpr int N = 64 * N2, K2 = N2 / 2, NT = N2 / 16, NCT = K2 / 16, SLOTS = 8 * N2;
+  constexpr int N = 64 * N2, NCT = N2 / 32, SLOTS = 8 * N2;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, kq = lane >> 4;
   const int mp = P.mels16, nbt = mp >> 4;
   float* const span = lds;
@@ -50,66 +47,21 @@ __device__ __forceinline__ void mel_long_tile(const pdmp3_mel_desc& d, const flo
   const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
 
-  const unsigned n_span = stftl_span(FT, P.hop, N);
-  for (unsigned p = tid; p < n_span; p += kMelLongThreads) span[p] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load_plain<kMelLongThreads>(span, row, P.n_in, f0, P.hop, d.lead, stftl_span(FT, P.hop, N), tid);
   __syncthreads();
 
   f32x4 acc0 = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, acc1 = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
   for (int kt = 0; kt < 4; kt++) {
-    {
-      const int t = wave % NT;
-      const float* const d64 = tab + stftl_tab_d64(N) + 16 * kt + j;
-      const float* const tw = tab + stftl_tab_tw(N) + 16 * kt + j;
-      float w[16], b_re[16], b_im[16], t_re[4], t_im[4];
-#pragma unroll
-      for (int s = 0; s < 16; s++) {
-        w[s] = tab[N2 * (4 * s + kq) + 16 * t + j];
-        b_re[s] = d64[(4 * s + kq) * 128];
-        b_im[s] = d64[(4 * s + kq) * 128 + 64];
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        t_re[r] = tw[(16 * t + 4 * kq + r) * 128];
-        t_im[r] = tw[(16 * t + 4 * kq + r) * 128 + 64];
-      }
-      for (int fl = wave / NT; fl < FT; fl += 8 / NT) {
-        f32x4 re = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, im = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        const float* const ap = span + (unsigned)fl * (unsigned)P.hop + N2 * kq + 16 * t + j;
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-          const float a = stftl_window(w[s], ap[4 * N2 * s]);
-          re = mfma16(a, b_re[s], re);
-          im = mfma16(a, b_im[s], im);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int n2 = 16 * t + 4 * kq + r;
-          float zr, zi;
-          stftl_twiddle(re[r], im[r], t_re[r], t_im[r], &zr, &zi);
-          z[stftl_z_at(fl, n2, 0, j, N2)] = zr;
-          z[stftl_z_at(fl, n2, 1, j, N2)] = zi;
-        }
-      }
-    }
+    stftl_stage1<N2, FT>(span, tab, (unsigned)P.hop, kt, wave, j, kq, z);
     __syncthreads();
 
     {
       const int ct = wave % NCT;
-      const float* const h2 = tab + stftl_tab_h2(N) + 16 * ct + j;
       float b_re[N2 / 2], b_im[N2 / 2];
-#pragma unroll
-      for (int s = 0; s < N2 / 2; s++) {
-        b_re[s] = h2[(4 * s + kq) * N2];
-        b_im[s] = h2[(4 * s + kq) * N2 + K2];
-      }
+      stftl_stage2_operand<N2>(tab, ct, j, kq, b_re, b_im);
       for (int fl = wave / NCT; fl < FT; fl += 8 / NCT) {
-        f32x4 re = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, im = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int s = 0; s < N2 / 2; s++) {
-          const float a = z[stftl_z_at(fl, 2 * s + (kq >> 1), kq & 1, j, N2)];
-          re = mfma16(a, b_re[s], re);
-          im = mfma16(a, b_im[s], im);
-        }
+        f32x4 re, im;
+        stftl_stage2_chains<N2>(z, fl, j, kq, b_re, b_im, re, im);
 #pragma unroll
         for (int r = 0; r < 4; r++) pw[mell_p_at(fl, mell_slot(4 * kq + r, 16 * ct + j, N2), N2)] = mel_power(re[r], im[r]);
       }

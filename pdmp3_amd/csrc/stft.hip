@@ -1,35 +1,24 @@
 // stft.hip -- k_clip_stft: rows of the resampled signal of a batch of clips (k_clip_audio's output in the stream object's
 // third audio stage) to their short-time Fourier transform, planar float32 [bins][n_frames] per clip and channel -- complex
 // ([bins][n_frames][2]), magnitude, power or its logarithm (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_stft; DESIGN.md
-// section 13).  Launched by stream.hip pdmp3_hip_clip_stft.  A translation unit of its own, so that every other kernel's code
-// is what it is without it; the span's indexing is mel_core.h's, the pointwise arithmetic and the staging layout stft_core.h's.
+// section 13).  Launched by stream.hip pdmp3_hip_clip_stft.  A translation unit of its own; the span's load and the DFT are
+// k_clip_mel's: clip_tile.h's, one source inlined here, which leaves a tile of bins' Re and Im in registers; the span's indexing
+// is mel_core.h's, the pointwise arithmetic and the staging layout stft_core.h's.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
+#include "clip_tile.h"
 #include "stft_core.h"
 
 namespace {
 
 using namespace pdmp3;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// a (Re, Im) pair of the output: one 8-byte store; a row may start at any float, and the device stores 8 bytes at 4-byte alignment
-typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// what a wave's lanes wrote to its staging tile is there for its other lanes (LDS operations of a wave complete in order)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One workgroup of four waves per (tile of 16 RT frames, channel, clip).
 //   1. the tile's span -- (tile - 1) hop + rows samples, zeros outside the clip's row -- goes to LDS once (mel_lds_at);
-//   2. DFT, as k_clip_mel's: the frames are overlapping rows of the span, the A operand is read at f hop + n and never
-//      materialised; the B operand is the folded table (window and scale in it), read from memory (L2).  A wave takes every
-//      fourth tile of 16 bins, Re and Im of all RT row tiles in registers;
+//   2. DFT, as k_clip_mel's (tile_dft, a tile of 16 bins a call): the frames are overlapping rows of the span, the A operand is
+//      read at f hop + n and never materialised; the B operand is the folded table (window and scale in it), read from memory
+//      (L2).  A wave takes every fourth tile of 16 bins, Re and Im of all RT row tiles in registers;
 //   3. the wave turns them into what is stored (stft_value; mode 0: the pair) in registers and transposes its 16 bins x
 //      tile frames through its own staging tile (stft_core.h has the layout and its banks): no workgroup barrier;
 //   4. consecutive lanes store consecutive frames of one bin, mode 0 consecutive (Re, Im) pairs.  Bins from K on and frames
@@ -46,36 +35,13 @@ __device__ __forceinline__ void stft_tile(const pdmp3_mel_desc& d, const float* 
   float* const st = lds + P.span_floats + wave * stft_stage_floats(FT, mode);
   const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
 
-  const unsigned n_span = (unsigned)(FT - 1) * hop + (unsigned)P.rows;
-  for (unsigned p = tid; p < n_span; p += kStftThreads) span[mel_lds_at(p, hop, pad)] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load<kStftThreads>(span, row, P.n_in, f0, P.hop, pad, d.lead, (unsigned)(FT - 1) * hop + (unsigned)P.rows, tid);
   __syncthreads();
 
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
-  const int ld = 2 * Kp;
   for (int bt = wave; bt < (Kp >> 4); bt += 4) {
     f32x4 re[RT], im[RT];
-#pragma unroll
-    for (int rt = 0; rt < RT; rt++) { re[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; im[rt] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
-    // lane (j, kq) reads frame j's sample n + kq: position j hop + n + kq = c hop + rem
-    unsigned c = (unsigned)j + (unsigned)kq / hop, rem = (unsigned)kq % hop;
-    const float* bp = tab + (size_t)kq * ld + (bt << 4) + j;
-#pragma unroll 2
-    for (int n = 0; n < P.rows; n += 4) {
-      const float b_re = bp[0], b_im = bp[Kp];
-      bp += 4 * ld;
-      const float* ap = span + c * chunk + rem;
-#pragma unroll
-      for (int rt = 0; rt < RT; rt++) {
-        const float a = ap[(unsigned)(16 * rt) * chunk];
-        re[rt] = mfma16(a, b_re, re[rt]);
-        im[rt] = mfma16(a, b_im, im[rt]);
-      }
-      rem += 4;
-      if (rem >= hop) {
-        if (hop >= 4) { rem -= hop; c++; }
-        else { c += rem / hop; rem %= hop; }
-      }
-    }
+    tile_dft<RT>(span, tab, P.rows, Kp, hop, chunk, bt, j, kq, re, im);
     // the lane's four frames of bin j, rt by rt: one 16-byte store a plane
     float* const sp = st + j * S + 4 * kq;
 #pragma unroll
@@ -106,15 +72,21 @@ __device__ __forceinline__ void stft_tile(const pdmp3_mel_desc& d, const float* 
   }
 }
 
+// a workgroup's (tile, channel, clip) and its tile of `tile` frames
+__device__ __forceinline__ void stft_entry(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab, const pdmp3_stft_params& P,
+                                           int tile, float* lds) {
+  const pdmp3_mel_desc d = descs[blockIdx.y];
+  const int ch = blockIdx.x % P.channels;
+  const long long f0 = (long long)(blockIdx.x / P.channels) * tile;
+  if (f0 >= P.n_frames) return;
+  if (tile == 32) stft_tile<2>(d, tab, P, ch, f0, lds);
+  else stft_tile<1>(d, tab, P, ch, f0, lds);
+}
+
 __global__ __launch_bounds__(kStftThreads) void k_clip_stft(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
                                                             pdmp3_stft_params P) {
   extern __shared__ __align__(16) float lds[];
-  const pdmp3_mel_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const long long f0 = (long long)(blockIdx.x / P.channels) * P.tile;
-  if (f0 >= P.n_frames) return;
-  if (P.tile == 32) stft_tile<2>(d, tab, P, ch, f0, lds);
-  else stft_tile<1>(d, tab, P, ch, f0, lds);
+  stft_entry(descs, tab, P, P.tile, lds);
 }
 
 // A tile of 16 frames that needs more than the 64 KB a launch can ask for dynamically (n_fft = 1024 at hops from about 900
@@ -122,11 +94,7 @@ __global__ __launch_bounds__(kStftThreads) void k_clip_stft(const pdmp3_mel_desc
 __global__ __launch_bounds__(kStftThreads) void k_clip_stft_big(const pdmp3_mel_desc* __restrict__ descs, const float* __restrict__ tab,
                                                                 pdmp3_stft_params P) {
   __shared__ __align__(16) float lds[PDMP3_MEL_LDS_MAX / sizeof(float)];
-  const pdmp3_mel_desc d = descs[blockIdx.y];
-  const int ch = blockIdx.x % P.channels;
-  const long long f0 = (long long)(blockIdx.x / P.channels) * 16;
-  if (f0 >= P.n_frames) return;
-  stft_tile<1>(d, tab, P, ch, f0, lds);
+  stft_entry(descs, tab, P, 16, lds);
 }
 
 }  // namespace
@@ -134,13 +102,7 @@ __global__ __launch_bounds__(kStftThreads) void k_clip_stft_big(const pdmp3_mel_
 hipError_t pdmp3_launch_clip_stft(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* table, const pdmp3_stft_params* params) {
   const pdmp3_stft_params P = *params;
   if (n_clips <= 0 || P.n_frames <= 0) return hipSuccess;
-  const unsigned tiles = (unsigned)((P.n_frames + P.tile - 1) / P.tile);
-  const dim3 grid(tiles * (unsigned)P.channels, (unsigned)n_clips);
-  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT) {
-    if (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_clip_stft_big, grid, dim3(pdmp3::kStftThreads), 0, s, descs, table, P);
-  } else {
-    hipLaunchKernelGGL(k_clip_stft, grid, dim3(pdmp3::kStftThreads), P.lds_bytes, s, descs, table, P);
-  }
-  return hipGetLastError();
+  if (P.lds_bytes > PDMP3_MEL_LDS_SOFT && (P.tile != 16 || P.lds_bytes > PDMP3_MEL_LDS_MAX)) return hipErrorInvalidValue;
+  return pdmp3::launch_clip_pair(k_clip_stft, k_clip_stft_big, s, pdmp3::kStftThreads, P.n_frames, P.tile, P.channels, n_clips, P.lds_bytes,
+                                 descs, table, P);
 }

@@ -2,42 +2,32 @@
 // transform N = 64 N2 (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_stft_long).  Rows in, layouts
 // out and the pointwise arithmetic are k_clip_stft's (stft.hip, stft_core.h); the index maps, the LDS layouts with their
 // banks, the twiddle step and the Nyquist bin's chain are stft_long_core.h's.  Launched by stream.hip
-// pdmp3_hip_clip_stft_long.  A translation unit of its own, so that every other kernel's code is what it is without it.
+// pdmp3_hip_clip_stft_long.  A translation unit of its own; the two stages are stft_long_stages.h's, one source for this
+// kernel and k_clip_mel_long, inlined here.
 #include <hip/hip_runtime.h>
 
 #include "../../include/pdmp3_hip.h"
-#include "stft_long_core.h"
+#include "stft_long_stages.h"
 
 namespace {
 
 using namespace pdmp3;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// a (Re, Im) pair of the output: one 8-byte store; a row may start at any float, and the device stores 8 bytes at 4-byte alignment
-typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
-// v_mfma_f32_16x16x4_f32: lane l = (j = l & 15, kq = l >> 4) holds A[row j][k = kq], B[k = kq][col j] and
-// D[row 4 kq + r][col j], r = 0..3; each D element is a fused multiply-add chain over k = 0..3 on top of C
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // One workgroup of eight waves per (tile of FT frames, 16 values k1 = 16 kt .. 16 kt + 15, channel, clip); n = N2 n1 + n2,
 // k = k1 + 64 k2.
 //   0. the tile's span -- (FT - 1) hop + N samples, zeros outside the clip's row -- goes to LDS once, plain;
-//   1. stage 1, rows (frame, n2), columns k1: a wave keeps one tile of 16 n2 -- its sixteen window values wt[N2 n1 + n2], the
-//      64-point DFT's B operands and its twiddles in registers -- and takes every (8 N2 / 16)-th frame of it: the A operand is
-//      wt times the span at fl hop + N2 n1 + n2, n1 = 4 s + kq ascending over sixteen steps; the result times the twiddle goes
-//      to Z in LDS.  The two kq of a 32-lane group read addresses N2 floats apart, the same banks: a two-way conflict on one
-//      4-byte read per two matrix instructions, taken (a padding that removes it costs half of the span again);
+//   1. stage 1 (stftl_stage1), rows (frame, n2), columns k1: the window product, the 64-term chains and the twiddle, into Z
+//      in LDS;
 //   2. the Nyquist bin, in the workgroups with kt = 0: lane fl of wave 0 runs the chain over Z[fl][.][k1 = 0] and stores it;
-//   3. stage 2, rows (frame, k1), columns k2 < N2 / 2: a wave keeps one tile of 16 columns of the half DFT in registers and
-//      takes every (8 / column tiles)-th frame: N2 / 2 steps over the 2 N2 terms (n2, part); what is stored (stft_value; mode
-//      0: the pair) goes to the workgroup's staging tile, which lies where the span lay;
+//   3. stage 2 (stftl_stage2_operand, stftl_stage2_chains), rows (frame, k1), columns k2 < N2 / 2: the chains of 2 N2 terms out
+//      of Z; what is stored (stft_value; mode 0: the pair) goes to the workgroup's staging tile, which lies where the span lay;
 //   4. consecutive lanes store consecutive frames of one bin, mode 0 consecutive (Re, Im) pairs.  Frames from F on are not
 //      stored; the bins are exactly 0 .. N / 2.
 // Every frame's values come from the same chains of operations whatever its place in the tile.
 template <int N2, int FT>
 __device__ __forceinline__ void stft_long_tile(const pdmp3_mel_desc& d, const float* __restrict__ tab, const pdmp3_stft_long_params& P,
                                                int ch, int kt, long long f0, float* lds) {
-  constexpr int N = 64 * N2, K2 = N2 / 2, NT = N2 / 16, NCT = K2 / 16;
+  constexpr int N = 64 * N2, K2 = N2 / 2, NCT = K2 / 16;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 15, kq = lane >> 4;
   const int mode = P.out_mode;
   float* const span = lds;
@@ -46,45 +36,10 @@ __device__ __forceinline__ void stft_long_tile(const pdmp3_mel_desc& d, const fl
   const float* const row = reinterpret_cast<const float*>(static_cast<uintptr_t>(d.src)) + (size_t)ch * d.src_chan_stride;
   float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(d.dst)) + (size_t)ch * d.dst_chan_stride;
 
-  const unsigned n_span = stftl_span(FT, P.hop, N);
-  for (unsigned p = tid; p < n_span; p += kStftLongThreads) span[p] = mel_sample(row, P.n_in, f0, P.hop, d.lead, p);
+  span_load_plain<kStftLongThreads>(span, row, P.n_in, f0, P.hop, d.lead, stftl_span(FT, P.hop, N), tid);
   __syncthreads();
 
-  {
-    const int t = wave % NT;
-    const float* const d64 = tab + stftl_tab_d64(N) + 16 * kt + j;
-    const float* const tw = tab + stftl_tab_tw(N) + 16 * kt + j;
-    float w[16], b_re[16], b_im[16], t_re[4], t_im[4];
-#pragma unroll
-    for (int s = 0; s < 16; s++) {
-      w[s] = tab[N2 * (4 * s + kq) + 16 * t + j];
-      b_re[s] = d64[(4 * s + kq) * 128];
-      b_im[s] = d64[(4 * s + kq) * 128 + 64];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      t_re[r] = tw[(16 * t + 4 * kq + r) * 128];
-      t_im[r] = tw[(16 * t + 4 * kq + r) * 128 + 64];
-    }
-    for (int fl = wave / NT; fl < FT; fl += 8 / NT) {
-      f32x4 re = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, im = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      const float* const ap = span + (unsigned)fl * (unsigned)P.hop + N2 * kq + 16 * t + j;
-#pragma unroll
-      for (int s = 0; s < 16; s++) {
-        const float a = stftl_window(w[s], ap[4 * N2 * s]);
-        re = mfma16(a, b_re[s], re);
-        im = mfma16(a, b_im[s], im);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int n2 = 16 * t + 4 * kq + r;
-        float zr, zi;
-        stftl_twiddle(re[r], im[r], t_re[r], t_im[r], &zr, &zi);
-        z[stftl_z_at(fl, n2, 0, j, N2)] = zr;
-        z[stftl_z_at(fl, n2, 1, j, N2)] = zi;
-      }
-    }
-  }
+  stftl_stage1<N2, FT>(span, tab, (unsigned)P.hop, kt, wave, j, kq, z);
   __syncthreads();
 
   if (kt == 0 && tid < FT && f0 + tid < P.n_frames) {
@@ -97,21 +52,11 @@ __device__ __forceinline__ void stft_long_tile(const pdmp3_mel_desc& d, const fl
 
   {
     const int ct = wave % NCT;
-    const float* const h2 = tab + stftl_tab_h2(N) + 16 * ct + j;
     float b_re[N2 / 2], b_im[N2 / 2];
-#pragma unroll
-    for (int s = 0; s < N2 / 2; s++) {
-      b_re[s] = h2[(4 * s + kq) * N2];
-      b_im[s] = h2[(4 * s + kq) * N2 + K2];
-    }
+    stftl_stage2_operand<N2>(tab, ct, j, kq, b_re, b_im);
     for (int fl = wave / NCT; fl < FT; fl += 8 / NCT) {
-      f32x4 re = f32x4{0.0f, 0.0f, 0.0f, 0.0f}, im = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-      for (int s = 0; s < N2 / 2; s++) {
-        const float a = z[stftl_z_at(fl, 2 * s + (kq >> 1), kq & 1, j, N2)];
-        re = mfma16(a, b_re[s], re);
-        im = mfma16(a, b_im[s], im);
-      }
+      f32x4 re, im;
+      stftl_stage2_chains<N2>(z, fl, j, kq, b_re, b_im, re, im);
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         if (mode == 0) {
