@@ -950,6 +950,73 @@ int pdmp3_amd_pitch_plan(const pdmp3_amd_pitch_spec* spec, long sr, int* frames,
 int pdmp3_amd_bulk_decode_clips_pitch(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pitch_spec* spec,
                                       long long* valid);
 
+/* ---- Onset strength, tempogram and tempo of clips (librosa.onset.onset_strength, librosa.feature.tempogram and
+ * librosa.feature.tempo with their parameters) ----
+ * K clips as one planar float32 batch: the onset envelope [K][C][F], the autocorrelation tempogram [K][C][Wt][F], frames
+ * innermost, or the tempo estimate [K][C][4].  New entry points only.  The definition is evaluated in binary64 on binary32
+ * values that the product itself can return, so every stage can be held against its predecessor.  N = n_fft, H = hop,
+ * Wt = win_length of the tempogram (even), Wh = Wt / 2, F = n_frames.
+ * 1. Log-mel.  l[m][f] is the binary32 value that pdmp3_amd_bulk_decode_clips_mel_long stores at out_mode 2 (log10 max(M,
+ *    floor)) for band m of the frame centred on sample start + f H, with the same mel fields (spec.mel; its out_mode is not
+ *    read).  f runs from -(lag + Wh) to F - 1 + Wh - 1 in modes 1 and 2, from -lag to F - 1 in mode 0.  Frames in front of the
+ *    clip and behind it see the stream's real neighbours, zeros outside the stream, no reflection.  The value is that call's bit
+ *    for bit: the kernel is the same.
+ * 2. Reference spectrum (librosa's max_size; SuperFlux at 3): ref[m][f] = max of l[m'][f] over |m' - m| <= (max_size - 1) / 2,
+ *    m' clamped to 0 .. n_mels - 1 (scipy's reflecting maximum filter gives the same).
+ * 3. Onset strength: o[f] = (10 / n_mels) * sum over m ascending of max(0, l[m][f] - ref[m][f - lag]), rounded once to
+ *    binary32: the mean over the bands of the half-wave rectified dB difference, librosa.onset.onset_strength(lag, max_size,
+ *    aggregate=mean) on power_to_db(S, top_db=None), without librosa's shift by n_fft // (2 hop) frames and with the real
+ *    history in place of its zero padding.  top_db is not offered: it makes every value depend on the clip's loudest frame, so
+ *    a clip would no longer be the slice of a longer one; a caller who wants a fixed range sets `floor`.
+ * 4. Windowed frame: x_f[n] = fl32(w[n] * o[f - Wh + n]), n = 0 .. Wt - 1, w[n] = 0.5 - 0.5 cos(2 pi n / Wt) in binary64
+ *    rounded once (scipy's get_window("hann", fftbins=True)).
+ * 5. Autocorrelation: r_f(tau) = sum over n < Wt - tau of x_f[n] x_f[n + tau], tau = 0 .. Wt - 1; T[tau][f] = r_f(tau) / r_f(0)
+ *    where r_f(0) > 0, else exactly 0 (librosa's norm=inf: |r(tau)| <= r(0)).
+ * 6. Tempo (librosa.feature.tempo, static, aggregate=mean): A[tau] = (sum over f < F ascending of T[tau][f]) / F on the
+ *    binary32 T of mode 1; bpm(tau) = 60 sr / (H tau); prior[tau] = -0.5 ((log2 bpm(tau) - log2 start_bpm) / std_bpm)^2, and
+ *    -inf for tau = 0 and wherever bpm(tau) >= max_tempo; s[tau] = log1p(1e6 A[tau]) + prior[tau]; tau* = the smallest argmax.
+ * 7. out_mode 0 "onset": [K][C][F], o.  1 "tempogram": [K][C][Wt][F], T.  2 "tempo": [K][C][4] = bpm(tau*), tau*, s[tau*], and
+ *    the margin s[tau*] minus the largest s at any other lag (+inf where no other lag is admissible).  The o that mode 1 windows
+ *    is mode 0's output bit for bit, for the clip widened by Wh frames on both sides (start - Wh H, F + Wt - 1 frames); the T
+ *    that mode 2 averages is mode 1's output bit for bit.
+ * Arithmetic.  o is a binary64 sum rounded once; r^ is a binary32 fused multiply-add chain over n ascending
+ * (v_mfma_f32_16x16x4_f32), T = r^(tau) / r^(0) in binary64 rounded once; A, log1p and s are binary64.  Section 21 derives
+ * the bounds and says when a clip's tempo is decided against the binary64 definition.
+ * 8. valid[k] is the centred calls': clamp(ceil((J - start) / H), 0, F).
+ * 9. Refusals (-1, nothing written): whatever pdmp3_amd_mel_long_check refuses with out_mode 2; lag outside 1 .. 16; max_size
+ *    even or outside 1 .. 9; win_length odd or outside 16 .. 1024; start_bpm, std_bpm, max_tempo not finite and positive; a prior
+ *    that is -inf at every lag; out_mode not 0, 1 or 2; n_frames < 0; a row of a clip (the output's, the log-mel's) beyond
+ *    2^31 - 1 floats; and whatever the audio call refuses. */
+typedef struct {
+  pdmp3_amd_mel_long_spec mel;                          /* the log-mel of item 1; mel.n_frames = F; mel.out_mode is not read */
+  int lag, max_size;                                    /* 1; 1 */
+  int win_length;                                       /* Wt (384) */
+  double start_bpm, std_bpm, max_tempo;                 /* 120, 1, 320 */
+  int out_mode;                                         /* 0 onset, 1 tempogram, 2 tempo */
+} pdmp3_amd_tempogram_spec;
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1 (item 9) */
+int pdmp3_amd_tempogram_check(const pdmp3_amd_tempogram_spec* spec, long sr);
+/* w[0 .. Wt - 1] of item 4 as the kernel reads it.  Returns Wt, or -1 (win_length refused, or cap < Wt); w may be NULL with
+ * cap 0 to ask for the count. */
+int pdmp3_amd_tempogram_window(int win_length, float* w, size_t cap);
+/* prior[0 .. Wt - 1] of item 6 in binary64 and *first, the smallest admissible lag.  Pointers may be NULL.  0, or -1 as the
+ * check. */
+int pdmp3_amd_tempogram_prior(const pdmp3_amd_tempogram_spec* spec, long sr, double* prior, size_t cap, int* first);
+/* What the call launches, the function the call itself uses: *front and *back, the log-mel frames in front of frame 0 and
+ * behind frame F - 1 (lag + Wh and Wh - 1; mode 0: lag and 0), *tiles = ceil(Wt / 256), *ksteps = ceil((Wt + 15) / 4), the
+ * matrix instructions a lag tile, *frames (one a wave: 8, or 4, 2, 1 where the LDS would pass 160 KB - 64) and *lds_bytes of a
+ * workgroup of k_clip_tempogram: per frame the skewed span (16 zeros, Wt values, zeros as far as the operands reach) and
+ * 256 tiles + 8 floats for its curve.  Pointers may be NULL.  0, or -1 as the check. */
+int pdmp3_amd_tempogram_plan(const pdmp3_amd_tempogram_spec* spec, long sr, int* front, int* back, int* tiles, int* ksteps, int* frames,
+                             unsigned* lds_bytes);
+/* Row k receives channel c's [F] (mode 0), [Wt][F] (mode 1) or [4] (mode 2) floats at dst + c * chan_stride.  The log-mel
+ * batch, (modes 1, 2) the envelope and (mode 2) the tempogram go to a stage of the decoder, not to the caller.  Everything else
+ * -- the audio call in front, host destinations, the per-clip refusals in valid[k], rate 0 / channels 0, width, rolloff, the
+ * counts, n_clips = 0 and n_frames = 0, synchronous -- as pdmp3_amd_bulk_decode_clips_stft.  k_clip_mel_long writes the
+ * log-mel; k_clip_onset, k_clip_tempogram and k_clip_tempo (csrc/tempogram.hip) the rest. */
+int pdmp3_amd_bulk_decode_clips_tempogram(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_tempogram_spec* spec,
+                                          long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

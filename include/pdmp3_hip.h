@@ -484,7 +484,8 @@ typedef struct pdmp3_audio_desc {
 } pdmp3_audio_desc;                         /* 96 bytes */
 /* The stream object's audio stages: device memory (hipMalloc, kept and grown on demand; call with nothing of the audio
  * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory; 2: the
- * resampled signal the log-mel call reads (below).  NULL on failure. */
+ * resampled signal the log-mel call reads (below); 3: what the tempogram call keeps between its kernels (log-mel, envelope,
+ * tempogram).  NULL on failure. */
 void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes);
 /* Uploads the launch's tables (descs, frames, tables: host memory) and runs k_clip_audio on the slot's HIP stream, behind
  * whatever the slot ran last (the last clip window's k_clip_pack); n_samples output samples per row, channels = 1 or 2.
@@ -762,6 +763,43 @@ typedef struct pdmp3_pitch_params {
 /* Uploads the descriptors -- host memory -- and runs k_clip_pitch on the slot's HIP stream.  The LDS limits are the log-mel
  * call's (PDMP3_MEL_LDS_SOFT / _MAX).  Blocks until the rows are written. */
 int pdmp3_hip_clip_pitch(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_pitch_params* params);
+
+/* Onset strength, tempogram and tempo of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_tempogram; DESIGN.md section
+ * 21).  Three kernels (tempogram.hip), each reading what the one before wrote:
+ *   k_clip_onset      a lane a frame: the log-mel [n_mels][n_mel_frames] that k_clip_mel_long wrote (frame 0 of it lies `lag`
+ *                     frames in front of envelope frame 0) to the envelope [n_env], a binary64 sum over the bands
+ *   k_clip_tempogram  (modes 1, 2) a wave a frame, frames_wg waves a workgroup: the windowed envelope x_f into the wave's own
+ *                     skewed LDS span (csrc/pitch_core.h pitch_at; 16 zeros in front, zeros behind as far as the operands
+ *                     reach: ext positions, span_floats floats), its autocorrelation on v_mfma_f32_16x16x4_f32 as
+ *                     k_clip_pitch's with W = win, divided by r^(0) into the wave's curve (256 tiles + 8 floats), stored
+ *                     [win][n_frames], frames innermost
+ *   k_clip_tempo      (mode 2) a workgroup a (clip, channel), a thread a lag: the mean over the frames, log1p, the prior, the
+ *                     argmax and the margin, in binary64
+ * Envelope frame e is o[e - win / 2] in modes 1 and 2 (n_env = n_frames + win - 1), o[e] in mode 0 (n_env = n_frames). */
+typedef struct pdmp3_tempogram_desc {
+  uint64_t mel;                             /* device address of channel 0's log-mel; channels n_mels n_mel_frames apart        */
+  uint64_t env;                             /* ... of channel 0's envelope; mode 0: the destination                             */
+  uint64_t tg;                              /* ... of channel 0's tempogram (modes 1, 2); mode 1: the destination               */
+  uint64_t dst;                             /* ... of channel 0's four floats (mode 2)                                          */
+  uint64_t dst_chan_stride;                 /* floats between the channels of the destination                                   */
+} pdmp3_tempogram_desc;                     /* 40 bytes */
+typedef struct pdmp3_tempogram_params {
+  double sr;                                /* the call's sampling frequency                                            */
+  int32_t n_mels, lag, half;                /* half = (max_size - 1) / 2                                                */
+  int32_t hop, win;                         /* H; Wt                                                                    */
+  int32_t tiles, ksteps;                    /* lag tiles of 256: ceil(Wt / 256) <= 4; ceil((Wt + 15) / 4)               */
+  int32_t n_frames, frames_wg;              /* F; frames (waves) of a workgroup: 8, 4, 2 or 1                           */
+  int32_t n_mel_frames, n_env;              /* frames of the log-mel batch: n_env + lag; of the envelope                */
+  int32_t channels, out_mode;
+  uint32_t env_stride;                      /* floats between the channels of the envelope stage (modes 1, 2)           */
+  uint32_t ext;                             /* positions of a wave's span that are written                              */
+  uint32_t span_floats;                     /* LDS floats of a wave's span, a multiple of 4                             */
+  uint32_t lds_bytes;
+} pdmp3_tempogram_params;
+/* Uploads the descriptors, the window (win floats) and the prior (win doubles) -- host memory -- and runs the kernels of
+ * out_mode on the slot's HIP stream.  The LDS limits are the log-mel call's.  Blocks until the rows are written. */
+int pdmp3_hip_clip_tempogram(pdmp3_hip_stream* hs, int slot, const pdmp3_tempogram_desc* descs, int n_clips, const float* window,
+                             const double* prior, const pdmp3_tempogram_params* params);
 
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);

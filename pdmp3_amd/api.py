@@ -34,7 +34,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_loudness_check", "pdmp3_amd_loudness_coefficients", "pdmp3_amd_loudness_tables", "pdmp3_amd_loudness_plan",
                 "pdmp3_amd_bulk_decode_clips_loudness",
                 "pdmp3_amd_r128_check", "pdmp3_amd_r128_taps", "pdmp3_amd_r128_plan", "pdmp3_amd_bulk_decode_clips_r128",
-                "pdmp3_amd_pitch_check", "pdmp3_amd_pitch_lags", "pdmp3_amd_pitch_plan", "pdmp3_amd_bulk_decode_clips_pitch"]
+                "pdmp3_amd_pitch_check", "pdmp3_amd_pitch_lags", "pdmp3_amd_pitch_plan", "pdmp3_amd_bulk_decode_clips_pitch",
+                "pdmp3_amd_tempogram_check", "pdmp3_amd_tempogram_window", "pdmp3_amd_tempogram_prior", "pdmp3_amd_tempogram_plan",
+                "pdmp3_amd_bulk_decode_clips_tempogram"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -214,6 +216,12 @@ def load_library():
         lib.pdmp3_amd_pitch_lags.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 3
         lib.pdmp3_amd_pitch_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]
         lib.pdmp3_amd_bulk_decode_clips_pitch.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_tempogram"):    # (onset strength, tempogram, tempo: absent from older builds)
+        lib.pdmp3_amd_tempogram_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_tempogram_window.argtypes = [C.c_int, vp, C.c_size_t]
+        lib.pdmp3_amd_tempogram_prior.argtypes = [vp, C.c_long, vp, C.c_size_t, C.POINTER(C.c_int)]
+        lib.pdmp3_amd_tempogram_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_tempogram.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -1079,6 +1087,65 @@ def pitch_plan(sample_rate=22050, **kw):
     return f.value, sp.value, b.value, k.value
 
 
+class _TempogramSpec(C.Structure):                 # include/pdmp3_bulk.h pdmp3_amd_tempogram_spec
+    _fields_ = [("mel", _MelLongSpec), ("lag", C.c_int), ("max_size", C.c_int), ("win_length", C.c_int), ("start_bpm", C.c_double),
+                ("std_bpm", C.c_double), ("max_tempo", C.c_double), ("out_mode", C.c_int)]
+
+
+TEMPOGRAM_MODES = {"onset": 0, "tempogram": 1, "tempo": 2}
+
+
+def _tempogram_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384, start_bpm=120.0,
+                    std_bpm=1.0, max_tempo=320.0, out_mode="tempogram", f_min=0.0, f_max=0.0, scale="slaney", norm="slaney", floor=1e-10,
+                    fft_win_length=None, fft_window=None, channels=1, width=0, rolloff=0.0):
+    """-> (spec, what its window points to).  win_length is the tempogram's; the transform's window is fft_win_length /
+    fft_window (decode_clips_mel_long's win_length / window)"""
+    mel, keep = _mel_long_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, "log10", floor, fft_win_length, fft_window,
+                               channels, width, rolloff)
+    return _TempogramSpec(mel, int(lag), int(max_size), int(win_length), float(start_bpm), float(std_bpm), float(max_tempo),
+                          TEMPOGRAM_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)), keep
+
+
+def tempogram_check(sample_rate=22050, **kw):
+    """pdmp3_amd_tempogram_check -> True when pdmp3_amd_bulk_decode_clips_tempogram would accept these numbers
+    (decode_clips_tempogram's argument names) at sample_rate"""
+    try:
+        spec, keep = _tempogram_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_tempogram_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def tempogram_window(win_length=384):
+    """pdmp3_amd_tempogram_window -> float32 numpy [win_length]: the periodic Hann window k_clip_tempogram reads"""
+    w = np.full(max(int(win_length), 1), np.nan, dtype=np.float32)
+    if load_library().pdmp3_amd_tempogram_window(int(win_length), w.ctypes.data_as(C.c_void_p), w.size) != int(win_length):
+        raise ValueError("pdmp3_amd_tempogram_window: win_length must be even, 16 .. 1024")
+    return w
+
+
+def tempogram_prior(sample_rate=22050, **kw):
+    """pdmp3_amd_tempogram_prior -> (float64 numpy [win_length]: the log-normal prior of every lag, -inf where a lag is not
+    admissible; the smallest admissible lag)"""
+    spec, keep = _tempogram_spec(sample_rate=sample_rate, **kw)
+    p = np.full(max(spec.win_length, 1), np.nan, dtype=np.float64)
+    first = C.c_int(0)
+    if load_library().pdmp3_amd_tempogram_prior(C.byref(spec), int(sample_rate), p.ctypes.data_as(C.c_void_p), p.size, C.byref(first)) != 0:
+        raise ValueError("pdmp3_amd_tempogram_prior: bad argument")
+    return p, first.value
+
+
+def tempogram_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_tempogram_plan -> (log-mel frames in front of frame 0, behind the last frame, lag tiles of 256, matrix
+    instructions a lag tile, frames of a workgroup of k_clip_tempogram, its LDS bytes)"""
+    spec, keep = _tempogram_spec(sample_rate=sample_rate, **kw)
+    v = [C.c_int(0) for _ in range(5)]
+    b = C.c_uint(0)
+    if load_library().pdmp3_amd_tempogram_plan(C.byref(spec), int(sample_rate), *[C.byref(x) for x in v], C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_tempogram_plan: bad argument")
+    return tuple(x.value for x in v) + (b.value,)
+
+
 class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
                 ("chan_stride", C.c_size_t)]
@@ -1513,6 +1580,27 @@ class BulkDecoder:
         else:
             spec = lambda: _stft_spec(f, sample_rate, n_fft, hop, win_length, window, normalized, m, floor, channels, width, rolloff)
         return self._clips_call(call, clips, (nb, f, 2) if m == 0 else (nb, f), spec, channels, out, complex_ok=m == 0, refused=(ValueError, OverflowError))
+
+    def decode_clips_tempogram(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384,
+                               start_bpm=120.0, std_bpm=1.0, max_tempo=320.0, out_mode="tempogram", out=None, f_min=0.0, f_max=0.0, scale="slaney",
+                               norm="slaney", floor=1e-10, fft_win_length=None, fft_window=None, channels=1, width=0, rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_tempogram: clips as decode_clips_mel_long takes them -> (out, valid).  out_mode "onset":
+        float32 [K, C, n_frames], librosa.onset.onset_strength(lag, max_size) of decode_clips_mel_long's log10 mel in dB, frame f
+        centred on sample start + f hop, the frames in front of the clip the stream's own (no shift, no zero padding, no top_db:
+        set floor for a fixed range); "tempogram": [K, C, win_length, n_frames], librosa.feature.tempogram's autocorrelation of
+        the Hann-windowed envelope around every frame, normalised by lag 0; "tempo": [K, C, 4] -- librosa.feature.tempo's bpm
+        (start_bpm, std_bpm, max_tempo), its lag in frames, the lag's score and the score's margin over every other lag.
+        fft_win_length / fft_window are decode_clips_mel_long's win_length / window.  valid, out, the exceptions: as
+        decode_clips_mel_long."""
+        f, wt = int(n_frames), int(win_length)
+        spec = lambda: _tempogram_spec(f, sample_rate, n_fft, hop, n_mels, lag, max_size, wt, start_bpm, std_bpm, max_tempo, out_mode, f_min, f_max,
+                                       scale, norm, floor, fft_win_length, fft_window, channels, width, rolloff)
+        if out_mode not in TEMPOGRAM_MODES:
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_tempogram: out_mode is \"onset\", \"tempogram\" or \"tempo\"")
+        inner = {"onset": (f,), "tempogram": (wt, f), "tempo": (4,)}[out_mode]
+        if out_mode == "tempogram" and out is None and not tempogram_check(sample_rate, win_length=wt):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_tempogram: bad win_length")
+        return self._clips_call("tempogram", clips, inner, spec, channels, out, refused=(ValueError, KeyError, OverflowError, TypeError))
 
     def _clips_call(self, call, clips, inner, spec_of, channels, out, made=None, complex_ok=False, refused=(), extra=()):
         """What every decode_clips_<call> does around its spec: the channel count, `out` made when not given (float32

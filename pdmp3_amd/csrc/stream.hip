@@ -12,6 +12,7 @@
 #include "unpack_core.h"
 #include "resample_core.h"
 #include "pitch_core.h"
+#include "tempogram_core.h"
 
 using namespace pdmp3;
 
@@ -49,7 +50,7 @@ struct pdmp3_hip_stream {
   int have_bits;
   int f32;                   // PCM as float (pdmp3_hip_stream_set_f32): the slots' PCM buffers hold 9216 bytes per frame
   int lsf;                   // the records of the submits are LSF frames (pdmp3_hip_stream_set_lsf): pdmp3_hip_decode_lsf_frames' layout
-  void* d_audio[3]; size_t audio_cap[3];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call
+  void* d_audio[4]; size_t audio_cap[4];   // clips as float batches (allocated on first use, grown on demand): the clips' int16 PCM, float rows for host destinations, the signal of the log-mel call, the tempogram call's stages
   void* d_audio_args; size_t audio_args_cap;      // ... and a launch's descriptors | frame table | filter tables
   void* d_clip_args; size_t clip_args_cap;        // the feature calls: a launch's descriptors | parts (clip_run)
 };
@@ -68,7 +69,7 @@ extern "C" void pdmp3_hip_stream_destroy(pdmp3_hip_stream* hs) {
     (void)hipHostFree(t.h_pieces); (void)hipFree(t.d_pieces); (void)hipFree(t.d_stage);
   }
   (void)hipFree(hs->d_sfstate);
-  (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio[2]); (void)hipFree(hs->d_audio_args);
+  (void)hipFree(hs->d_audio[0]); (void)hipFree(hs->d_audio[1]); (void)hipFree(hs->d_audio[2]); (void)hipFree(hs->d_audio[3]); (void)hipFree(hs->d_audio_args);
   (void)hipFree(hs->d_clip_args);
   if (hs->ev_state) (void)hipEventDestroy(hs->ev_state);
   (void)hipFree(hs->d_state);
@@ -557,7 +558,7 @@ static int grow_device(void** p, size_t* cap, size_t bytes, const char* what) {
   return PDMP3_HIP_OK;
 }
 extern "C" void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes) {
-  if (!hs || which < 0 || which > 2) return nullptr;
+  if (!hs || which < 0 || which > 3) return nullptr;
   if (hipSetDevice(hs->ctx->device) != hipSuccess) return nullptr;
   if (grow_device(&hs->d_audio[which], &hs->audio_cap[which], bytes ? bytes : 16, "hipMalloc audio stage") != PDMP3_HIP_OK) return nullptr;
   return hs->d_audio[which];
@@ -618,7 +619,7 @@ struct ClipPart {
 template <class Desc, size_t N, class Launch>
 static int clip_run(pdmp3_hip_stream* hs, int slot, const char* name, const Desc* descs, int n_clips, long long n_frames,
                     const ClipPart (&parts)[N], Launch launch) {
-  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc or pdmp3_fbank_desc");
+  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc, pdmp3_fbank_desc or pdmp3_tempogram_desc");
   char what[160];
   const auto at = [&](const char* step) -> const char* { snprintf(what, sizeof what, "%s: %s", name, step); return what; };
   StreamSlot& t = hs->s[slot];
@@ -986,6 +987,33 @@ extern "C" int pdmp3_hip_clip_pitch(pdmp3_hip_stream* hs, int slot, const pdmp3_
   // descriptors alone: the kernel reads no table
   return clip_run(hs, slot, "pdmp3_hip_clip_pitch", descs, n_clips, P.n_frames, {{ClipPart::kScratch, nullptr, 0}},
                   [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const*) { return pdmp3_launch_clip_pitch(hs->s[slot].stream, dk, nk, &P); });
+}
+// ---- onset strength, tempogram, tempo (tempogram.hip) ----
+extern "C" int pdmp3_hip_clip_tempogram(pdmp3_hip_stream* hs, int slot, const pdmp3_tempogram_desc* descs, int n_clips, const float* window,
+                                        const double* prior, const pdmp3_tempogram_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !window || !prior || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_tempogram: bad argument", hipSuccess);
+  const pdmp3_tempogram_params& P = *params;
+  // what the kernels' indexing relies on
+  if (P.n_mels < 1 || P.n_mels > 256 || P.lag < 1 || P.lag > 16 || P.half < 0 || P.half > 4 || P.hop < 1 || P.win < 16 || P.win > pdmp3::kTempoMaxWin ||
+      (P.win & 1) || P.tiles != (P.win + 255) / 256 || P.ksteps != (P.win + 18) / 4 ||
+      (P.frames_wg != 1 && P.frames_wg != 2 && P.frames_wg != 4 && P.frames_wg != 8) || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 ||
+      P.out_mode > 2 || P.n_frames < 0 || P.n_env != (P.out_mode == 0 ? (long long)P.n_frames : (long long)P.n_frames + P.win - 1) ||
+      P.n_mel_frames != (long long)P.n_env + P.lag || (long long)P.n_mels * P.n_mel_frames > 0x7fffffffLL ||
+      (long long)P.win * P.n_frames > 0x7fffffffLL || (P.out_mode != 0 && P.env_stride < (unsigned)P.n_env) || !(P.sr > 0.0) || (P.span_floats & 3u) ||
+      P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_tempogram: bad parameters", hipSuccess);
+  if (P.ext < pdmp3::tempogram_ext(P.win, P.tiles, P.ksteps) || P.ext > 0x10000u || P.span_floats < pdmp3::pitch_at(P.ext) ||
+      (size_t)P.lds_bytes < (size_t)pdmp3::tempogram_lds(P).total_f * sizeof(float))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_tempogram: a workgroup's spans and curves do not fit the LDS asked for", hipSuccess);
+  if (((long long)P.n_env + pdmp3::kOnsetThreads - 1) / pdmp3::kOnsetThreads * P.channels > 0x7fffffffLL)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_tempogram: too many frames", hipSuccess);
+  // descriptors | the window | the prior
+  return clip_run(hs, slot, "pdmp3_hip_clip_tempogram", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, window, (size_t)P.win * sizeof(float)}, {ClipPart::kUpload, prior, (size_t)P.win * sizeof(double)}},
+                  [&](const pdmp3_tempogram_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_tempogram(hs->s[slot].stream, dk, nk, as_floats(part[0]), reinterpret_cast<const double*>(part[1]), &P);
+                  });
 }
 extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {
   if (!bytes) return PDMP3_HIP_OK;

@@ -407,6 +407,10 @@ HOST_LOCAL int r128_plan(long fs, long long n_samples, pdmp3_r128_params* p);
 /* clip_pitch.c: the check, the lag range and the geometry of a workgroup of k_clip_pitch for the spec at sr; n_in, n_frames and
  * channels are left to the call (0, or -1 where the check refuses the spec) */
 HOST_LOCAL int pitch_plan(const pdmp3_amd_pitch_spec* s, long sr, pdmp3_pitch_params* p);
+/* clip_tempogram.c: the check and the geometry of the launches of the tempogram call for the spec at sr, *front and *back the
+ * log-mel frames a row needs in front of frame 0 and behind frame F - 1; the frame counts, env_stride and channels are left to the
+ * call (0, or -1 where the check refuses the spec) */
+HOST_LOCAL int tempogram_plan(const pdmp3_amd_tempogram_spec* s, long sr, pdmp3_tempogram_params* p, int* front, int* back);
 /* clip_stft_long.c: the plan of a workgroup of k_clip_stft_long (0, or -1) and the decoder's block of tables of a spec the
  * check accepts -- wt | 64-point DFT | half DFT | twiddles as pdmp3_hip_clip_stft_long takes them (NULL: no memory) */
 HOST_LOCAL int stft_long_plan(int n_fft, int hop, int out_mode, pdmp3_stft_long_params* p);

@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128; DESIGN.md sections 9-19).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram; DESIGN.md sections 9-21).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -219,6 +219,11 @@ typedef struct {
   int* host;                         /* per descriptor: its clip, if that one's rows go to host memory, else -1 */
   int nd;
   size_t out_floats;                 /* floats of stage 1 the host destinations' rows take */
+  /* the tempogram call's extension, zero for every other call: a row is read for `front` frames in front of frame 0 and `back`
+   * frames behind frame F - 1 as well (valid[] stays relative to `start` and F); per_fixed: floats of a channel's output where
+   * they are not per_frame F */
+  int front, back;
+  size_t per_fixed;
 } clip_course;
 
 /* the arguments, and the call's channels and sampling frequency from the clips (0, or -1: nothing is allocated yet) */
@@ -254,15 +259,17 @@ static int course_begin(clip_course* cc, struct bulk* b, const pdmp3_amd_audio_c
 
 /* The rows of the call: a frame reads N samples, the next one H further on, and writes per_frame floats.  centred: frame f's
  * centre is the sample start + f H -- the row is the span from max(0, start - N / 2) on, `lead` zeros in front of it, and valid
- * counts the frames whose centres lie inside the stream.  Else frame f begins there -- the row is the span from `start` on, and
+ * counts the frames whose centres lie inside the stream (with cc->front / cc->back the row begins `front` frames earlier and ends
+ * `back` frames later; lead counts the zeros in front of that span).  Else frame f begins there -- the row is the span from `start` on, and
  * valid, pdmp3_amd_fbank_valid's, goes into the descriptor too.  Fills valid[], the descriptors and host[] (0, or -1). */
 static int course_rows(clip_course* cc, int N, int H, int per_frame, int centred) {
   const long long F = cc->F;
   const int C = cc->C;
-  if (F > 0x7fffffffLL / (per_frame > H ? per_frame : H) - 2 * N) return -1;                /* (a row's samples and floats stay inside 31 bits) */
-  const size_t per = cc->per = (size_t)per_frame * (size_t)F;
+  const long long Fr = F ? F + cc->front + cc->back : 0;                                     /* frames a row is read for */
+  if (Fr > 0x7fffffffLL / (per_frame > H ? per_frame : H) - 2 * N) return -1;               /* (a row's samples and floats stay inside 31 bits) */
+  const size_t per = cc->per = cc->per_fixed ? cc->per_fixed : (size_t)per_frame * (size_t)F;
   for (int k = 0; k < cc->n_clips; k++) if (C == 2 && F && cc->clips[k].chan_stride < per) return -1;
-  cc->T = F ? (F - 1) * H + N : 0;
+  cc->T = F ? (Fr - 1) * H + N : 0;
   const size_t Ts = cc->Ts = ((size_t)cc->T + 3) & ~(size_t)3;
   cc->ac = (pdmp3_amd_audio_clip*)calloc((size_t)cc->n_clips + 1, sizeof *cc->ac);
   cc->av = (long long*)calloc((size_t)cc->n_clips + 1, sizeof *cc->av);
@@ -281,13 +288,14 @@ static int course_rows(clip_course* cc, int N, int H, int per_frame, int centred
     const long long left = J - c->start;
     cc->valid[k] = !centred ? pdmp3_amd_fbank_valid(J, c->start, N, H, F) : left <= 0 ? 0 : (left + H - 1) / H < F ? (left + H - 1) / H : F;
     if (!F) continue;
-    const long long s0 = !centred ? c->start : c->start > N / 2 ? c->start - N / 2 : 0;
+    const long long c0 = c->start - (long long)cc->front * H;                      /* the centre of the row's first frame */
+    const long long s0 = !centred ? c->start : c0 > N / 2 ? c0 - N / 2 : 0;
     pdmp3_amd_audio_clip* a = &cc->ac[cc->nd];
     pdmp3_mel_desc* d = &cc->ds[cc->nd];
     a->mp3 = c->mp3; a->n = c->n; a->index = ix;
     a->start = s0;
     a->chan_stride = Ts;
-    d->lead = centred ? (uint32_t)(s0 - (c->start - N / 2)) : (uint32_t)cc->valid[k];
+    d->lead = centred ? (uint32_t)(s0 - (c0 - N / 2)) : (uint32_t)cc->valid[k];
     d->src_chan_stride = Ts;
     const size_t row_bytes = ((size_t)(C - 1) * c->chan_stride + per) * sizeof(float);
     if (pdmp3_hip_host_is_pinned(c->dst, row_bytes) == 2) { cc->host[cc->nd] = -1; d->dst = (uint64_t)(uintptr_t)c->dst; d->dst_chan_stride = c->chan_stride; }
@@ -461,6 +469,64 @@ int pdmp3_amd_bulk_decode_clips_mel_long(struct bulk* b, const pdmp3_amd_audio_c
   P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C; P.out_mode = m->out_mode; P.floor = (float)m->floor;
   if (course_launched(pdmp3_hip_clip_mel_long(b->hs, CLIP_SLOT, cc.ds, cc.nd, table, operand, &P)) != 0) return course_finish(&cc, -1);
   return course_finish(&cc, cc.rc);
+}
+
+/* ---- onset strength, tempogram and tempo of clips ---- */
+/* The log-mel call's course on rows widened by the frames the flux and the tempogram's window reach, its kernel writing into
+ * audio stage 3 instead of the destination; the envelope (modes 1, 2) and the tempogram (mode 2) lie behind the log-mel there. */
+int pdmp3_amd_bulk_decode_clips_tempogram(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_tempogram_spec* spec,
+                                          long long* valid) {
+  clip_course cc;
+  if (!spec) return -1;
+  const pdmp3_amd_mel_spec* m = &spec->mel.mel;
+  if (course_begin(&cc, b, clips, n_clips, valid, m->n_frames, m->channels, m->rate, m->width, m->rolloff) != 0) return -1;
+  pdmp3_tempogram_params Q;
+  pdmp3_mel_long_params P;
+  memset(&Q, 0, sizeof Q);
+  memset(&P, 0, sizeof P);
+  if (tempogram_plan(spec, cc.sr, &Q, &cc.front, &cc.back) != 0) return -1;  /* (the check is its first step) */
+  if (mel_long_plan(m->n_fft, m->hop, m->n_mels, &P) != 0) return -1;
+  const int mode = spec->out_mode, Wt = spec->win_length;
+  if (mode == 2) cc.per_fixed = 4;
+  if (course_rows(&cc, m->n_fft, m->hop, mode == 1 ? Wt : 1, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const long long F = cc.F, Fe = mode == 0 ? F : F + Wt - 1, Fm = Fe + spec->lag;
+  const size_t mel_floats = (size_t)m->n_mels * (size_t)Fm, env_stride = ((size_t)Fe + 3) & ~(size_t)3;
+  const size_t env_floats = mode == 0 ? 0 : env_stride, tg_floats = mode == 2 ? (size_t)Wt * (size_t)F : 0;
+  pdmp3_amd_mel_long_spec ms = spec->mel;
+  ms.mel.out_mode = 2;
+  pdmp3_amd_stft_spec frame;
+  mel_long_stft_spec(&ms, &frame);
+  const float* table = stft_long_tables(b, &frame);
+  const float* operand = mel_long_operand(b, cc.sr, m);
+  pdmp3_mel_desc* md = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *md);
+  pdmp3_tempogram_desc* td = (pdmp3_tempogram_desc*)calloc((size_t)cc.nd, sizeof *td);
+  float* w = (float*)malloc((size_t)Wt * sizeof *w);
+  double* prior = (double*)malloc((size_t)Wt * sizeof *prior);
+  int rc = -1;
+  if (!table || !operand || !md || !td || !w || !prior || course_signal(&cc) != 0) goto out;
+  if (pdmp3_amd_tempogram_window(Wt, w, (size_t)Wt) != Wt || pdmp3_amd_tempogram_prior(spec, cc.sr, prior, (size_t)Wt, NULL) != 0) goto out;
+  float* const stage = (float*)pdmp3_hip_stream_audio_stage(b->hs, 3, (size_t)cc.nd * (size_t)cc.C * (mel_floats + env_floats + tg_floats) * sizeof(float));
+  if (!stage) goto out;
+  float* const env_stage = stage + (size_t)cc.nd * (size_t)cc.C * mel_floats;
+  float* const tg_stage = env_stage + (size_t)cc.nd * (size_t)cc.C * env_floats;
+  for (int i = 0; i < cc.nd; i++) {
+    md[i] = cc.ds[i];
+    md[i].dst = (uint64_t)(uintptr_t)(stage + (size_t)i * (size_t)cc.C * mel_floats);
+    md[i].dst_chan_stride = mel_floats;
+    td[i].mel = md[i].dst;
+    td[i].dst = cc.ds[i].dst; td[i].dst_chan_stride = cc.ds[i].dst_chan_stride;
+    td[i].env = mode == 0 ? td[i].dst : (uint64_t)(uintptr_t)(env_stage + (size_t)i * (size_t)cc.C * env_floats);
+    td[i].tg = mode == 1 ? td[i].dst : mode == 2 ? (uint64_t)(uintptr_t)(tg_stage + (size_t)i * (size_t)cc.C * tg_floats) : 0;
+  }
+  P.n_in = cc.T; P.n_frames = (int32_t)Fm; P.channels = cc.C; P.out_mode = 2; P.floor = (float)m->floor;
+  if (course_launched(pdmp3_hip_clip_mel_long(b->hs, CLIP_SLOT, md, cc.nd, table, operand, &P)) != 0) goto out;
+  Q.n_frames = (int32_t)F; Q.n_env = (int32_t)Fe; Q.n_mel_frames = (int32_t)Fm; Q.env_stride = (uint32_t)env_stride; Q.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_tempogram(b->hs, CLIP_SLOT, td, cc.nd, w, prior, &Q)) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(md); free(td); free(w); free(prior);
+  return course_finish(&cc, rc);
 }
 
 /* ---- Kaldi-style filterbank features of clips ---- */

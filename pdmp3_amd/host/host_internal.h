@@ -26,6 +26,7 @@
  *   clip_loudness.c loudness of clips: the check, the K-weighting's coefficients, the blocked filter's tables, the geometry
  *   clip_r128.c     true peak, short-term loudness and loudness range of clips: the check, the interpolator's taps, the geometry
  *   clip_pitch.c    pitch of clips (YIN): the check, the lag range, the geometry of a workgroup
+ *   clip_tempogram.c onset strength, tempogram and tempo of clips: the check, the window, the prior, the launches' geometry
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

@@ -985,6 +985,137 @@ def clips_pitch(args, api):
     print(json.dumps(res))
 
 
+def torch_tempogram(l, lag, wt, f, window, prior, rate, hop, mode):
+    """the definition of DESIGN.md section 21 (max_size 1) in torch on the device: l [K, n_mels, n_env + lag] log10 mel ->
+    mode 0 [K, n_env], 1 [K, wt, f], 2 [K, 4]"""
+    import torch
+    o = 10.0 * torch.relu(l[..., lag:] - l[..., :-lag]).mean(dim=1)
+    if mode == 0:
+        return o
+    x = o.unfold(-1, wt, 1) * window                                            # [K, f, wt]
+    r = torch.fft.irfft(torch.fft.rfft(x, 2 * wt).abs() ** 2, 2 * wt)[..., :wt]
+    r0 = r[..., :1]
+    t = torch.where(r0 > 0, r / r0.clamp_min(1e-30), torch.zeros_like(r)).transpose(1, 2)
+    if mode == 1:
+        return t
+    s = torch.log1p(1e6 * t.to(torch.float64).mean(-1).clamp_min(0.0)) + prior
+    top = torch.topk(s, 2, dim=-1)
+    tau = top.indices[:, 0].to(torch.float64)
+    return torch.stack([60.0 * rate / (hop * tau), tau, top.values[:, 0], top.values[:, 0] - top.values[:, 1]], 1).to(torch.float32)
+
+
+def clips_tempogram(args, api):
+    """--tempogram: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as onset envelope [K, 1, 1292],
+    tempogram [K, 1, 384, 1292] and tempo [K, 1, 4] with librosa's defaults (n_fft 2048, hop 512, 128 bands, lag 1, max_size 1,
+    window 384, prior 120 bpm) in device memory, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the spans of the
+    widened clips; (b) pdmp3_amd_bulk_decode_clips_mel_long for the widened clips; (c) per mode, (b) -- for mode 0 on the clips
+    widened by the lag alone -- followed by the same algorithm in torch on the device: diff, relu, mean, unfold, window,
+    torch.fft autocorrelation, normalise, mean, log1p, prior, topk; (d) per mode, pdmp3_amd_bulk_decode_clips_tempogram.  (c) and
+    (d) are compared once (largest differences and the share of clips with the same lag, printed, not asserted: the tests check
+    (d) against the definition).  The kernels' own times come from a kernel-trace run of this mode
+    (profiles/clip_tempogram.txt).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, Fm, rate, N, H, nm, lag, wt = args.clips, args.clip_frames, 22050, 2048, 512, 128, 1, 384
+    span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
+    F = span // H + 1
+    front, back, tiles, ksteps, frames_wg, lds = api.tempogram_plan(rate)
+    Fw = F + front + back                                                       # frames of the widened clips
+    T = (Fw - 1) * H + N
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(400, max(401, ixs[i].frames - Fm - 4))))
+    clips, wide, wide0, spans = [], [], [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = -((-a * ixs[i].frame_samples * l) // m)
+        assert start - front * H - N // 2 >= 0
+        clips.append((files[i], ixs[i], start))
+        wide.append((files[i], ixs[i], start - front * H))
+        wide0.append((files[i], ixs[i], start - lag * H))
+        spans.append((files[i], ixs[i], start - front * H - N // 2))
+    dev = "cuda:0"
+    sig = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    mel = torch.zeros((K, 1, nm, Fw), dtype=torch.float32, device=dev)
+    mel0 = torch.zeros((K, 1, nm, F + lag), dtype=torch.float32, device=dev)
+    shapes = {"onset": (F,), "tempogram": (wt, F), "tempo": (4,)}
+    out_t = {}
+    out_p = {m: torch.zeros((K, 1) + sh, dtype=torch.float32, device=dev) for m, sh in shapes.items()}
+    window = torch.from_numpy(api.tempogram_window(wt)).to(dev)
+    prior = torch.from_numpy(api.tempogram_prior(rate)[0]).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(spans, T, rate, 1, out=sig)
+
+    def mel_route():
+        dec.decode_clips_mel_long(wide, Fw, rate, N, H, nm, out=mel)
+
+    def torch_route(mode):
+        def run():
+            if mode == "onset":
+                dec.decode_clips_mel_long(wide0, F + lag, rate, N, H, nm, out=mel0)
+                out_t[mode] = torch_tempogram(mel0[:, 0], lag, wt, F, window, prior, rate, H, 0)
+            else:
+                dec.decode_clips_mel_long(wide, Fw, rate, N, H, nm, out=mel)
+                out_t[mode] = torch_tempogram(mel[:, 0], lag, wt, F, window, prior, rate, H, 1 if mode == "tempogram" else 2)
+            torch.cuda.synchronize()
+        return run
+
+    def product_route(mode):
+        return lambda: dec.decode_clips_tempogram(clips, F, rate, N, H, nm, lag, 1, wt, out_mode=mode, out=out_p[mode])
+
+    routes = [("audio clips", audio_route), ("mel_long clips", mel_route)]
+    for m in shapes:
+        routes += [("mel_long clips + torch " + m, torch_route(m)), ("tempogram clips, " + m, product_route(m))]
+    times = {name: [] for name, _ in routes}
+    seen = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            same = out_t["tempo"][:, 1] == out_p["tempo"][:, 0, 1]
+            seen = {"largest_onset_difference": float((out_t["onset"] - out_p["onset"][:, 0]).abs().max()),
+                    "largest_onset": float(out_p["onset"].max()),
+                    "largest_tempogram_difference": float((out_t["tempogram"] - out_p["tempogram"][:, 0]).abs().max()),
+                    "clips": K, "clips_with_torchs_lag": int(same.sum()),
+                    "bpm": sorted(set(round(float(v), 2) for v in out_p["tempo"][:, 0, 0].cpu()))[:8]}
+    dec.close()
+    res = {"workload": "%d clips of %d frames at %d Hz mono, n_fft %d hop %d, %d bands, lag %d, tempogram window %d (%d log-mel frames a clip): %s" % (
+               K, F, rate, N, H, nm, lag, wt, Fw, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "plan": {"frames_in_front": front, "frames_behind": back, "lag_tiles": tiles, "matrix_instructions_a_tile": ksteps,
+                    "frames_a_workgroup": frames_wg, "lds_bytes": lds},
+           "matrix_instructions": K * F * tiles * ksteps, "stage_bytes": {"log_mel": K * nm * Fw * 4, "envelope": K * (F + wt - 1) * 4, "tempogram": K * wt * F * 4},
+           "seen": seen, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    for m in shapes:
+        res[m + "_minus_mel_long_ms"] = round((med["tempogram clips, " + m] - med["mel_long clips"]) * 1e3, 3)
+        res[m + "_torch_minus_mel_long_ms"] = round((med["mel_long clips + torch " + m] - med["mel_long clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_fbank(args, api):
     """--clips K --clip-frames F --fbank: the clips of clips() (same seed, same places), the whole seconds of F MPEG-1 frames'
     length each, as Kaldi-style filterbank features [K, 1, frames, 80] at 16 kHz mono (25 ms povey frames every 10 ms, N = 512,
@@ -1225,6 +1356,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as YIN pitch [3, 1292] at 22 050 Hz mono with librosa.yin's defaults "
                          "(pdmp3_amd_bulk_decode_clips_pitch) against the audio call alone and the audio call followed by the same algorithm "
                          "in torch on the device (see clips_pitch())")
+    ap.add_argument("--tempogram", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as onset envelope, tempogram [384, 1292] and tempo at 22 050 Hz mono with "
+                         "librosa's defaults (pdmp3_amd_bulk_decode_clips_tempogram, all three modes) against the audio call alone, the log-mel "
+                         "call alone and that call followed by the same algorithm in torch on the device (see clips_tempogram())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1232,7 +1367,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1246,6 +1381,8 @@ def main():
             return clips_loudness(args, api, r128=args.r128)
         if args.pitch:
             return clips_pitch(args, api)
+        if args.tempogram:
+            return clips_tempogram(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
         if args.stft or args.stft_long:
