@@ -227,3 +227,47 @@ def check_stats(m, stats, momentary=None):
     else:
         near(stats[3], m.g, m.dg, "g")
     return worst
+
+
+def curve_gates(row, every=1, relative=-10.0):
+    """The two gates on a curve as a call stores it: row holds binary32 values l'_j = fl32(l_j) in dB (-inf: silence) of which
+    every `every`-th takes part; the absolute gate is -70, the relative one `relative` dB under the level of the mean of what
+    passes the absolute one.  All in binary64 -> a Measured with n_abs, gamma / dgamma, n_rel, level / dlevel (the level of the
+    mean of what passes both), inside (the mask of those, over row[::every]), dv (the bound of each of row[::every]),
+    undecided and margin_bounds.
+
+    Bounds, from the row's own rounding alone.  The call gates and sums its binary64 l_j and z_j and stores fl32(l_j), so
+    |l'_j - l_j| <= d_j = 2^-24 |l'_j| / (1 - 2^-24) (round to nearest, |l_j| <= |l'_j| / (1 - 2^-24)).  The power behind a
+    value is z = 10^((l + 0.691) / 10), so dz / z = (ln 10 / 10) dl to first order and, without dropping a term,
+    |z'_j / z_j - 1| <= r_j = exp((ln 10 / 10) d_j) - 1.  A mean of positive z_j over a fixed set moves by no more than the
+    largest r_j of the set, relatively, so its level moves by no more than 10 log10(1 / (1 - r)) dB: that is dgamma (r over
+    the set behind the absolute gate) and dlevel (r over the set behind both).  The sets are fixed only where no value lies
+    within its rounding of a gate: |l'_j + 70| <= d_j, or |l'_j - gamma| <= d_j + dgamma for a value behind the absolute
+    gate, makes the clip undecided, as in measure().  margin_bounds is the smallest such distance over its bound."""
+    v = np.asarray(row, dtype=np.float64)[::every]
+    g = Measured()
+    d = np.where(np.isfinite(v), U * np.abs(np.where(np.isfinite(v), v, 0.0)) / (1.0 - U), 0.0)
+    r = np.expm1(math.log(10.0) / 10.0 * d)
+    z = np.where(np.isfinite(v), 10.0 ** ((np.where(np.isfinite(v), v, 0.0) + 0.691) / 10.0), 0.0)
+    g.dv = d
+    in_a = v > -70.0
+    g.n_abs = int(in_a.sum())
+    near = np.isfinite(v) & (np.abs(v + 70.0) <= d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        bounds = [np.inf] + list(np.abs(v + 70.0)[np.isfinite(v)] / np.maximum(d[np.isfinite(v)], 1e-300))
+    g.undecided = bool(near.any())
+    g.inside = np.zeros(v.shape, dtype=bool)
+    g.n_rel, g.gamma, g.dgamma, g.level, g.dlevel = 0, -np.inf, 0.0, -np.inf, 0.0
+    if g.n_abs:
+        g.gamma = float(_l(z[in_a].mean()) + relative)
+        g.dgamma = float(-10.0 * np.log10(1.0 - r[in_a].max()))
+        g.undecided |= bool((np.abs(v[in_a] - g.gamma) <= d[in_a] + g.dgamma).any())
+        bounds += list(np.abs(v[in_a] - g.gamma) / (d[in_a] + g.dgamma))
+        g.inside = in_a & (v > g.gamma)
+        g.n_rel = int(g.inside.sum())
+        if g.n_rel:
+            g.level = float(_l(z[g.inside].mean()))
+            g.dlevel = float(-10.0 * np.log10(1.0 - r[g.inside].max()))
+    g.values = v
+    g.margin_bounds = float(min(bounds))
+    return g

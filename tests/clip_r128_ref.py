@@ -232,3 +232,92 @@ def check_stats(m, stats, momentary=None, short_term=None):
     near(stats[11], m.gamma_r, m.dgamma_r, "Gamma_r")
     near(stats[10], m.LRA, m.dLRA, "LRA")
     return worst
+
+
+LEAD_SECONDS = 2
+
+
+def measure_from(x, fs, t0, lead=LEAD_SECONDS, dual_mono=False):
+    """measure()'s momentary and short-term values and their bounds for the windows that begin at or behind sample t0 of
+    x [C, T], from x[:, a:] alone with the filters started from rest at a = the last multiple of q at least `lead` seconds in
+    front of the first such window (0 where the row is shorter).  The K-weighting's memory decays: at 8 kHz a start from rest
+    0.5 s before is bit-equal in binary64 to the full run, at 48 kHz it agrees to 2e-13 of max |y| after 0.5 s and is
+    bit-equal after 2 s (tests/test_clip_r128_host.py holds this helper to 1e-12 of measure() behind a loud history).  The
+    bounds are the cut row's: all of measure()'s terms but the states' binary64 chain are local to a block, and that one is
+    proportional to max |x| of the cut row alone -- a rounding committed in front of the cut decays as the states do.
+    -> (j0, m): the first window is number j0 of the whole row's, m.l / m.dl / m.z / m.ez and m.S / m.dS / m.w / m.ew are cut
+    to the windows j0, j0 + 1, ... of the whole row (m.J, m.Js: how many); the other fields of m speak of the cut row"""
+    x = np.asarray(x)
+    q = (fs + 5) // 10
+    j0 = (int(t0) + q - 1) // q
+    a = max(0, j0 - (int(lead * fs) + q - 1) // q) * q
+    m = measure(x[:, a:], fs, dual_mono)
+    k = j0 - a // q
+    m.l, m.dl, m.z, m.ez = m.l[k:], m.dl[k:], m.z[k:], m.ez[k:]
+    m.S, m.dS, m.w, m.ew = m.S[k:], m.dS[k:], m.w[k:], m.ew[k:]
+    m.J, m.Js = len(m.l), len(m.S)
+    return j0, m
+
+
+def check_curves_from(j0, m, momentary, short_term):
+    """the tails of a call's momentary and short-term rows from window j0 on against measure_from's m, as check_stats holds the
+    whole rows -> the worst error / bound met"""
+    worst = 0.0
+    for name, row, val, dval, z, ez in (("l", momentary, m.l, m.dl, m.z, m.ez), ("S", short_term, m.S, m.dS, m.w, m.ew)):
+        got = np.asarray(row, dtype=np.float64)[j0:]
+        assert got.shape == val.shape, (name, got.shape, val.shape)
+        for j in range(len(val)):
+            if ez[j] < 0.5 * z[j]:
+                b = dval[j] + abs(val[j]) * 2.0 ** -23
+                assert abs(got[j] - val[j]) <= b, ("%s[%d]" % (name, j0 + j), got[j], val[j], b)
+                worst = max(worst, abs(got[j] - val[j]) / b)
+            else:
+                assert got[j] <= float(lref._l(z[j] + ez[j])) + 1e-5, ("%s[%d]" % (name, j0 + j), got[j], z[j], ez[j])
+    return worst
+
+
+def gates_on_curves(momentary, short_term):
+    """The gated numbers of a call from its own curves: the momentary row and the short-term row as the call stores them
+    (binary32 dB values) -> a Measured with L / dL, gamma / dgamma, nA, nGt, undecided (clip_loudness_ref.curve_gates on the
+    momentary row: relative gate -10) and gamma_r / dgamma_r, nAr, nGr, LRA / dLRA, r_undecided, Jr (the same on every tenth
+    short-term value: relative gate -20), margin_bounds.  What a call's stats must be where the curves are right: it is the
+    check of a clip too long for measure().
+
+    The bounds of L, Gamma and Gamma_r are curve_gates' (derived there from the rows' rounding alone, |dl| <= 2^-24 |l|).
+    LRA = v_(hi) - v_(lo), two order statistics of the gated values v_i, of which the row holds v'_i with |v'_i - v_i| <= d_i.
+    An order statistic is monotone in every value, so the k-th smallest of the v_i lies between the k-th smallest of the
+    v'_i - d_i and the k-th smallest of the v'_i + d_i -- the spread of the values whose rank can change, and d_k itself where
+    no neighbour is that near.  dLRA is the sum of the two statistics' largest distances from v'_(hi) and v'_(lo)."""
+    g = lref.curve_gates(momentary)
+    m = lref.Measured()
+    m.L, m.dL, m.gamma, m.dgamma, m.nA, m.nGt, m.undecided = g.level, g.dlevel, g.gamma, g.dgamma, g.n_abs, g.n_rel, g.undecided
+    r = lref.curve_gates(short_term, every=EVERY, relative=-20.0)
+    m.Jr = len(r.values)
+    m.gamma_r, m.dgamma_r, m.nAr, m.nGr, m.r_undecided = r.gamma, r.dgamma, r.n_abs, r.n_rel, r.undecided
+    m.LRA, m.dLRA = 0.0, 0.0
+    if m.nGr:
+        v, d = r.values[r.inside], r.dv[r.inside]
+        mid, dn, up = np.sort(v), np.sort(v - d), np.sort(v + d)
+        hi, lo = hi_index(m.nGr), lo_index(m.nGr)
+        m.LRA = float(mid[hi] - mid[lo])
+        m.dLRA = float(max(up[hi] - mid[hi], mid[hi] - dn[hi]) + max(up[lo] - mid[lo], mid[lo] - dn[lo]))
+    m.margin_bounds = min(g.margin_bounds, r.margin_bounds)
+    return m
+
+
+def check_stats_on_curves(g, stats):
+    """the call's stats row [16] against gates_on_curves' g -> the worst error / bound met; the counts are exact"""
+    stats = np.asarray(stats, dtype=np.float64)
+    assert not g.undecided and not g.r_undecided
+    assert (stats[6], stats[7], stats[13], stats[14], stats[15]) == (g.nA, g.nGt, g.Jr, g.nAr, g.nGr), (stats[[6, 7, 13, 14, 15]], g.nA, g.nGt, g.Jr, g.nAr, g.nGr)
+    worst = 0.0
+    for got, want, bound, what in ((stats[0], g.L, g.dL, "L"), (stats[4], g.gamma, g.dgamma, "Gamma"), (stats[11], g.gamma_r, g.dgamma_r, "Gamma_r"),
+                                   (stats[10], g.LRA, g.dLRA, "LRA")):
+        if not np.isfinite(want):
+            assert got == want, (what, got, want)
+            continue
+        b = bound + abs(want) * 2.0 ** -23            # (the value's own rounding to binary32)
+        assert abs(got - want) <= b, (what, got, want, b)
+        if b > 0.0:
+            worst = max(worst, abs(got - want) / b)
+    return worst

@@ -199,6 +199,46 @@ def test_shapes_within_the_bound(fs):
                 assert abs(float(stats[0]) - (mono.L + 10.0 * math.log10(2.0))) <= m.dL + 2e-6 * abs(m.L)
 
 
+def chain_signal(T, fs, seed):
+    """mono noise with two level steps inside: 0.1 rms over the first quarter, 30 dB less from there on, an offset of 0.25
+    under the last two chunks in front of chunk 64 (it loads the high-pass's slow poles), and exact zeros from seven samples
+    in front of chunk 64 on.  What the rows behind the 64th chunk hold is then the decay of the state that k_loud_chain
+    carried out of lane 63, and nothing else: a wrong carry is wrong by the size of the values themselves"""
+    x = _signal("noise", 1, T, fs, seed)
+    x[:, T // 4:] *= np.float32(10.0 ** (-30.0 / 20.0))
+    x[:, 62 * 4096:] += np.float32(0.25)
+    x[:, 64 * 4096 - 7:] = 0.0
+    return x
+
+
+@pytest.mark.parametrize("fs,T", [(48000, 64 * 4096), (48000, 64 * 4096 + 1), (48000, 128 * 4096), (48000, 128 * 4096 + 1), (192000, 128 * 4096 + 1)])
+def test_the_chain_at_the_edges_of_its_steps(fs, T):
+    """k_loud_chain takes 64 chunks a step: exactly one step, one step and a chunk of a single sample (the guards of a step
+    whose other lanes lie behind n_chunks), two steps, two and a sample.  The signal ends in front of chunk 64, so the first
+    sub-blocks behind it are the carried state's decay.  At 48 000 Hz that state is gone a chunk later (4096 samples are 20
+    time constants of the high-pass), and the carry's way into the step's other lanes, Phi^64 times it, moves nothing; at
+    192 000 Hz a chunk is 5 time constants and sub-block 14, which begins inside chunk 65, is held by that path alone.
+    L, Gamma, the counts and the whole momentary curve against the binary64 definition (its sample loop run by scipy's
+    lfilter, which test_the_sample_loop_is_scipys_lfilter holds to 1e-12: the rows are half a million samples long)"""
+    pytest.importorskip("scipy.signal")
+    import clip_r128_ref
+    q = (fs + 5) // 10
+    n_chunks = _api().loudness_plan(fs, T)[4]
+    assert n_chunks == (T + 4095) // 4096 and n_chunks in (64, 65, 128, 129)
+    x = chain_signal(T, fs, 640 + n_chunks)
+    m = clip_r128_ref._loudness_measure(x, fs)
+    audio, stats, mom = emulate(x, fs)
+    worst = ref.check_stats(m, stats, mom)
+    print("fs %d T %d, %d chunks: L %.4f J %d |A| %d |Gt| %d worst error / bound %.3g, margin %.3g dB" % (fs, T, n_chunks, m.L, m.J, m.nA, m.nGt, worst, m.margin))
+    assert not m.undecided and 0 < m.nGt < m.nA <= m.J and 0.0 < worst <= 1.0
+    if n_chunks > 65:
+        # the windows that begin behind the signal's end: the state's decay, well above the bound's floor, and held two-sidedly
+        j = (64 * 4096 + q - 1) // q
+        k = (65 * 4096 + q - 1) // q if fs == 192000 else j
+        assert m.nA < m.J and np.isfinite(m.l[k]) and m.ez[k] < 1e-3 * m.z[k] and m.l[j - 4] > m.l[k] + 20.0
+    assert (audio.view(np.uint32) == x.view(np.uint32)).all() and stats[3] == 1.0
+
+
 # ---- 6. gain ----
 def test_gain():
     fs = 8000

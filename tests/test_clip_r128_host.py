@@ -235,6 +235,117 @@ def test_a_silent_tail_is_gated_out_of_the_range():
     assert m.S[-1] < -100.0 and stats[14] == m.Jr - 1     # (the filters' decay alone is in the last window)
 
 
+# ---- 3b. more than 256 blocks, windows and range values: every stride loop of k_loud_gate makes a second trip ----
+DRAWN_DB = (-12, -18, -24, -30, -36, -42, -80)         # of noise with sigma 0.5: the last one lies under the absolute gate
+LONG = {
+    # name: (seconds, channels, seed) at 8000 Hz -- the seeds were chosen on the reference alone (both gates of the range bite,
+    # nothing undecided, every window of the range more than 10 bounds from its gates)
+    "27s-mono": (27.0, 1, 2705),
+    "27s-stereo": (27.0, 2, 2751),
+    "300s-mono": (300.05, 1, 30005),
+}
+
+
+def _drawn_segments(fs, seconds, Cn, seed):
+    """noise in segments of 3 .. 5 s end to end, each at a level drawn from DRAWN_DB"""
+    rng = np.random.default_rng(seed)
+    T = int(round(seconds * fs))
+    x = 0.5 * rng.standard_normal((Cn, T))
+    t = 0
+    while t < T:
+        n, db = int(rng.integers(3 * fs, 5 * fs + 1)), DRAWN_DB[int(rng.integers(len(DRAWN_DB)))]
+        x[:, t:t + n] *= 10.0 ** (db / 20.0)
+        t += n
+    return np.clip(x, -1.0, 1.0).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def _long_case(name):
+    """(x, the reference, the emulation's (audio, stats, momentary, short-term)) -- made once"""
+    seconds, Cn, seed = LONG[name]
+    x = _drawn_segments(8000, seconds, Cn, seed)
+    return x, ref.measure(x, 8000), emulate(x, 8000)
+
+
+@pytest.mark.parametrize("name", sorted(LONG))
+def test_more_than_256_blocks_windows_and_range_values(name):
+    """27 s: J = 267 and Js = 241, n_sub = 270 -- the loops over the sub-blocks and the momentary blocks (both passes) make a
+    second trip, in threads 0 .. 13 alone; 300.05 s: Jr = 298 and 586 chunks, so the loops over the waves' partial peaks, the
+    short-term windows (twelve trips), the gated range values and the ranking do too, and the chain takes ten steps.  Every
+    field and both curves against the binary64 definition"""
+    x, m, (audio, stats, mom, st) = _long_case(name)
+    worst = ref.check_stats(m, stats, mom, st)
+    print("%s: J %d Js %d Jr %d |A| %d |Gt| %d |Ar| %d |Gr| %d L %.3f LRA %.3f worst error / bound %.3g, range margin %.3g dB = %.3g bounds" %
+          (name, m.J, m.Js, m.Jr, m.nA, m.nGt, m.nAr, m.nGr, m.L, m.LRA, worst, m.r_margin, m.r_margin_bounds))
+    n_chunks = ref.plan(8000, x.shape[1])["n_chunks"]
+    assert m.J > 256 and ((m.Jr > 256 and m.Js > 256 and n_chunks > 64 * 9) if name.startswith("300s") else (m.J, m.Js) == (267, 241))
+    assert 0 < m.nGr < m.nAr < m.Jr and 0 < m.nGt < m.nA < m.J
+    assert 0.0 < worst <= 1.0 and not m.undecided and not m.r_undecided and m.r_margin_bounds > 10.0
+    assert (audio.view(np.uint32) == (x * np.float32(stats[3])).astype(np.float32).view(np.uint32)).all()
+    assert stats[8] >= stats[2] == np.abs(x).max()
+
+
+def test_a_shorter_clip_is_a_prefix_of_the_longer_one():
+    """the 300 s signal cut to 27 s and five samples: its momentary and short-term rows are the first values of the long
+    clip's rows, bit for bit -- every sum has one fixed order, nothing behind a block enters it, and the scans hand states
+    upwards only"""
+    x, m, (audio, stats, mom, st) = _long_case("300s-mono")
+    _, s2, mom2, st2 = emulate(x[:, :27 * 8000 + 5], 8000)
+    assert (len(mom2), len(st2)) == (267, 241) and np.isfinite(mom2).any() and s2[13] == 25
+    assert (mom2.view(np.uint32) == mom[:267].view(np.uint32)).all() and (st2.view(np.uint32) == st[:241].view(np.uint32)).all()
+
+
+# ---- 3c. the helpers of the device tests of long clips ----
+def test_measure_from_is_measure_behind_a_loud_history():
+    """12 s at 8000 and 48 000 Hz stereo: 6 s near full scale, then 40 dB less.  The windows from 8 s on (t0 not a multiple of
+    q), from a restart 2 s in front of them, against the whole run's: 1e-12 relative, the bar of the lfilter pin"""
+    for fs in (8000, 48000):
+        q = (fs + 5) // 10
+        x = tlh._signal("noise", 2, 12 * fs + 77, fs, 12)
+        x[:, :6 * fs] *= np.float32(8.0)
+        x[:, 6 * fs:] *= np.float32(0.08)
+        m = ref.measure(x, fs)
+        t0 = 8 * fs - q // 3
+        j0, c = ref.measure_from(x, fs, t0)
+        assert j0 == 80 and (j0 - 1) * q < t0 <= j0 * q and c.J == m.J - j0 > 30 and c.Js == m.Js - j0 > 5
+        for got, want in ((c.z, m.z[j0:]), (c.w, m.w[j0:])):
+            assert got.shape == want.shape and (np.abs(got - want) <= 1e-12 * np.abs(want)).all()
+        for got, want in ((c.ez, m.ez[j0:]), (c.ew, m.ew[j0:])):     # (the bounds: the cut row's peak in the states' term, not the history's)
+            assert got.shape == want.shape and (got <= want * (1.0 + 1e-12)).all() and (got >= 0.5 * want).all()
+        assert np.abs(c.l - m.l[j0:]).max() <= 1e-11 and np.abs(c.S - m.S[j0:]).max() <= 1e-11
+        assert m.z[:40].min() > 1000.0 * m.z[j0:].max()              # (the history is loud)
+        # the emulation's own rows, held from j0 on
+        _, stats, mom, st = emulate(x, fs)
+        worst = ref.check_curves_from(j0, c, mom, st)
+        assert 0.0 < worst <= 1.0
+    j0, c = ref.measure_from(x, fs, 5)                                # (a start nearer to the row's than the lead: the whole run)
+    assert j0 == 1 and c.J == m.J - 1 and (c.z == m.z[1:]).all()
+
+
+def test_the_gates_on_the_calls_own_curves():
+    """the 300 s signal: L, Gamma, Gamma_r, LRA and the counts from the emulation's stored rows alone, against measure() within
+    the two bounds together and against the emulation's stats within the rows' own rounding"""
+    x, m, (audio, stats, mom, st) = _long_case("300s-mono")
+    g = ref.gates_on_curves(mom, st)
+    assert not g.undecided and not g.r_undecided and g.margin_bounds > 10.0
+    assert (g.nA, g.nGt, g.Jr, g.nAr, g.nGr) == (m.nA, m.nGt, m.Jr, m.nAr, m.nGr) and 0 < g.nGr < g.nAr < g.Jr
+    for got, dgot, want, dwant in ((g.L, g.dL, m.L, m.dL), (g.gamma, g.dgamma, m.gamma, m.dgamma), (g.gamma_r, g.dgamma_r, m.gamma_r, m.dgamma_r),
+                                   (g.LRA, g.dLRA, m.LRA, m.dLRA)):
+        assert abs(got - want) <= dgot + dwant and 0.0 < dgot < 1e-4, (got, dgot, want, dwant)
+    worst = ref.check_stats_on_curves(g, stats)
+    print("gates on the curves: worst error / bound %.3g; dL %.3g dGamma_r %.3g dLRA %.3g; margin %.3g bounds" % (worst, g.dL, g.dgamma_r, g.dLRA, g.margin_bounds))
+    assert 0.0 <= worst <= 1.0
+    # a value moved across a gate moves a count, and one put within its rounding of a gate makes the clip undecided
+    moved = st.copy()
+    moved[10 * int(np.argmax(st[::10] > g.gamma_r))] = np.float32(-71.0)
+    h = ref.gates_on_curves(mom, moved)
+    assert h.nAr == g.nAr - 1
+    moved[0] = np.float32(-70.0)
+    assert ref.gates_on_curves(mom, moved).r_undecided
+    with pytest.raises(AssertionError):
+        ref.check_stats_on_curves(h, stats)
+
+
 # ---- 4. the loudness call, bit for bit ----
 @pytest.mark.parametrize("kw", [dict(), dict(target=-14.0), dict(target=-14.0, peak_limit=0.3), dict(dual_mono=True)])
 def test_without_the_true_peak_limit_the_first_eight_are_the_loudness_calls(kw):

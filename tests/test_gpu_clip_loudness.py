@@ -32,9 +32,12 @@ def _gate_stream():
     return mp3, api.StreamIndex(mp3, ISO_LSF)
 
 
+STREAMS = {"gate": _gate_stream}                   # name -> maker of (mp3, index); the other loudness test files add theirs
+
+
 def _source(name):
-    if name == "gate":
-        return _gate_stream()
+    if name in STREAMS:
+        return STREAMS[name]()
     return tga._streams()[name], tga._ref(name)[0]
 
 
