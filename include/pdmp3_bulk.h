@@ -1017,6 +1017,58 @@ int pdmp3_amd_tempogram_plan(const pdmp3_amd_tempogram_spec* spec, long sr, int*
 int pdmp3_amd_bulk_decode_clips_tempogram(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_tempogram_spec* spec,
                                           long long* valid);
 
+/* ---- Spectral descriptors of clips at n_fft 2048 and 4096 ----
+ * The per-frame scalars of librosa.feature -- RMS energy, zero-crossing rate, spectral centroid, bandwidth, roll-off and
+ * flatness -- of K clips as one planar float32 batch [K][C][6][F], frames innermost, rows of K and C may be strided; the
+ * spectrum they are made of never leaves the device's compute units.  New entry points only.
+ * Frame and signal are the two-stage transform's above: n_fft = N is 2048 or 4096, hop 1 .. N, win_length 0 (= N) or 1 .. N
+ * centred as torch.stft centres it, window NULL (periodic Hann of win_length) or the caller's binary32 values; there is no
+ * `normalized`.  x[n] = y[start + f hop - N / 2 + n], n < N: real neighbours inside the stream, zeros outside, no reflection;
+ * valid[k], rate 0 and channels 0 as pdmp3_amd_bulk_decode_clips_mel.
+ * X is that transform's spectrum bit for bit (the same chains), P_k = fma(Im, Im, Re Re), S_k = sqrtf(P_k) -- what its modes 2
+ * and 1 store -- for all k = 0 .. N / 2, the Nyquist bin included; f_k = k sr / N.  The rows:
+ *   0 rms        sqrt((1 / N) sum_n x[n]^2) over the unwindowed frame (librosa.feature.rms, frame_length = N)
+ *   1 zcr        (1 / N) #{n = 1 .. N - 1: neg(x[n]) != neg(x[n - 1])}, neg(v) = v < -t, t = zcr_threshold rounded to binary32
+ *                (librosa's zero_pos = True, pad = False): exact
+ *   2 centroid   sum f_k S_k / sum S_k
+ *   3 bandwidth  sqrt(sum S_k (f_k - centroid)^2 / sum S_k)                  (librosa's p = 2, norm = True)
+ *   4 rolloff    the least f_k with S_0 + .. + S_k >= roll_percent sum S
+ *   5 flatness   exp(mean_k ln max(amin, P_k)) / mean_k max(amin, P_k)       (librosa's power = 2)
+ * A frame whose samples are all zero gives rows 0 .. 4 exactly 0; row 5 is what its formula gives.
+ * Arithmetic.  The sums of rows 0 and 2 .. 5 are binary64 sums in one fixed order (csrc/spectral_core.h) that does not depend on
+ * the frame's place in a tile, clip or batch, each value rounded once to binary32; x^2 is exact in binary64; ln is binary32 logf
+ * of fmaxf(P, amin).  The cumulative sum of row 4 runs in ascending k: each of 64 lanes sums its run of N / 128 consecutive
+ * bins (the last one's ends with bin N / 2), a scan adds the lanes' totals in ascending order -- its last value is the one
+ * sum S that rows 2 .. 4 use -- and a lane's bins are compared as prefix + (the run's sum so far).  No atomics: two runs are
+ * bit-equal.
+ * Not offered: spectral contrast (its per-band quantiles are a ranking of their own), p != 2, subsets of the rows,
+ * n_fft <= 1024. */
+typedef struct pdmp3_amd_spectral_spec {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec (rolloff: the resampling filter's) */
+  int n_fft, hop, win_length;                           /* N: 2048 or 4096; 1 .. N; 0 = N, else 1 .. N */
+  const float* window;                                  /* win_length values, NULL = periodic Hann */
+  long long n_frames;
+  double roll_percent;                                  /* inside (0, 1); librosa's default is 0.85 */
+  double amin;                                          /* > 0 as binary32; librosa's default is 1e-10 */
+  double zcr_threshold;                                 /* >= 0; librosa's default is 1e-10 */
+} pdmp3_amd_spectral_spec;
+#define PDMP3_SPECTRAL_ROWS 6
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: any other n_fft, hop outside 1 .. n_fft, a bad
+ * win_length or window value (pdmp3_amd_stft_long_check's rules), roll_percent outside (0, 1), amin that is not positive and
+ * finite as binary32, a negative or non-finite zcr_threshold, n_frames < 0, sr <= 0. */
+int pdmp3_amd_spectral_check(const pdmp3_amd_spectral_spec* spec, long sr);
+/* What a workgroup of k_clip_spectral takes, the function the call itself uses: *tile frames -- 8 at n_fft 2048, 4 at 4096, at
+ * every hop -- and all bins.  The LDS bytes: the tile's span, (tile - 1) hop + n_fft floats rounded up to 4, which stays; Z,
+ * tile x N2 x 32 floats; the plane, tile x (n_fft / 2 + 1) floats; 8 x tile floats of results; rounded up to 16 bytes.
+ * *row_pad is 0.  Every plan is above 64 KB and runs on a static array.  0, or -1 on a bad argument.  Pointers may be NULL. */
+int pdmp3_amd_spectral_plan(int n_fft, int hop, int* tile, int* row_pad, unsigned* lds_bytes);
+/* pdmp3_amd_bulk_decode_clips_stft_long's course -- rows through the audio call, destinations, the stages, the per-clip
+ * refusals in valid[k], rate 0 / channels 0, the counts, n_clips = 0 and n_frames = 0 -- with the check above and
+ * k_clip_spectral (csrc/spectral.hip) writing the rows: row k receives channel c's [6][n_frames] floats at
+ * dst + c * chan_stride.  The transform's tables are that call's.  -1 also where pdmp3_amd_spectral_check says so. */
+int pdmp3_amd_bulk_decode_clips_spectral(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_spectral_spec* spec,
+                                         long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

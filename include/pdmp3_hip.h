@@ -640,6 +640,29 @@ typedef struct pdmp3_mel_long_params {
 int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                             const float* operand, const pdmp3_mel_long_params* params);
 
+/* Spectral descriptors of clips at n_fft 2048 and 4096 (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_spectral; DESIGN.md
+ * section 22).  k_clip_spectral (spectral.hip) reads the rows as k_clip_stft_long does (pdmp3_mel_desc) and writes [6][n_frames]
+ * floats per channel, frames innermost: rms, zcr, centroid, bandwidth, rolloff, flatness.  N = 64 n2; a workgroup of eight
+ * waves takes `tile` frames and all four tiles of k1, one after the other.  Its LDS: span_floats for the tile's span, plain
+ * ((tile - 1) hop + n_fft floats, kept), then Z: tile x n2 x 32 floats, then the plane: tile x (n_fft / 2 + 1) floats, then
+ * 8 x tile floats of results; csrc/spectral_core.h has the layouts. */
+typedef struct pdmp3_spectral_params {
+  int64_t n_in;                             /* samples of a row                                                         */
+  int32_t n_fft, n2;                        /* N: 2048 or 4096; N / 64                                                  */
+  int32_t hop, n_frames;                    /* H; F                                                                     */
+  int32_t tile, channels;                   /* frames of a workgroup: 8 (N 2048) or 4 (N 4096)                          */
+  double bin_hz;                            /* sr / N                                                                   */
+  double roll_percent;                      /* inside (0, 1)                                                            */
+  float amin, zcr_threshold;                /* the floor of the flatness' powers (> 0); the zero crossings' dead band (>= 0) */
+  uint32_t span_floats;                     /* LDS floats of the span's region, a multiple of 4                         */
+  uint32_t lds_bytes;
+} pdmp3_spectral_params;
+/* Uploads the descriptors and the four tables (pdmp3_hip_clip_stft_long's block) -- host memory -- and runs k_clip_spectral on
+ * the slot's HIP stream, one launch per 32 768 clips.  lds_bytes <= PDMP3_MEL_LDS_MAX: the kernel has a static array of that
+ * size.  Blocks until the rows are written. */
+int pdmp3_hip_clip_spectral(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                            const pdmp3_spectral_params* params);
+
 /* The constant-Q transform of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt).
  * k_clip_cqt (cqt.hip) reads the rows as k_clip_stft does (pdmp3_mel_desc; a frame's span is rows0 samples, its centre the
  * sample h_0) and writes [n_bins][n_frames] floats per channel, frames innermost; out_mode 0: [n_bins][n_frames][2].  The table

@@ -36,7 +36,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_r128_check", "pdmp3_amd_r128_taps", "pdmp3_amd_r128_plan", "pdmp3_amd_bulk_decode_clips_r128",
                 "pdmp3_amd_pitch_check", "pdmp3_amd_pitch_lags", "pdmp3_amd_pitch_plan", "pdmp3_amd_bulk_decode_clips_pitch",
                 "pdmp3_amd_tempogram_check", "pdmp3_amd_tempogram_window", "pdmp3_amd_tempogram_prior", "pdmp3_amd_tempogram_plan",
-                "pdmp3_amd_bulk_decode_clips_tempogram"]
+                "pdmp3_amd_bulk_decode_clips_tempogram",
+                "pdmp3_amd_spectral_check", "pdmp3_amd_spectral_plan", "pdmp3_amd_bulk_decode_clips_spectral"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -222,6 +223,10 @@ def load_library():
         lib.pdmp3_amd_tempogram_prior.argtypes = [vp, C.c_long, vp, C.c_size_t, C.POINTER(C.c_int)]
         lib.pdmp3_amd_tempogram_plan.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_tempogram.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_spectral"):     # (spectral descriptors at n_fft 2048 and 4096: absent from older builds)
+        lib.pdmp3_amd_spectral_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_spectral_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_spectral.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -891,6 +896,48 @@ def mel_long_plan(n_fft, hop, n_mels):
     return t.value, p.value, b.value
 
 
+class _SpectralSpec(C.Structure):                  # include/pdmp3_bulk.h pdmp3_amd_spectral_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("win_length", C.c_int), ("window", C.c_void_p), ("n_frames", C.c_longlong), ("roll_percent", C.c_double), ("amin", C.c_double),
+                ("zcr_threshold", C.c_double)]
+
+
+SPECTRAL_ROWS = ("rms", "zcr", "centroid", "bandwidth", "rolloff", "flatness")
+
+
+def _spectral_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, roll_percent=0.85, amin=1e-10, zcr_threshold=1e-10, channels=1,
+                   win_length=None, window=None, width=0, rolloff=0.0):
+    """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
+    w = None
+    if window is not None:
+        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
+        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
+            raise ValueError("spectral: window must hold win_length values")
+        win_length = w.size
+    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    spec = _SpectralSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw,
+                         w.ctypes.data if w is not None else None, int(n_frames), float(roll_percent), float(amin), float(zcr_threshold))
+    return spec, w
+
+
+def spectral_check(sample_rate=22050, **kw):
+    """pdmp3_amd_spectral_check -> True when pdmp3_amd_bulk_decode_clips_spectral would accept these numbers
+    (decode_clips_spectral's argument names) at sample_rate"""
+    try:
+        spec, keep = _spectral_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, TypeError, OverflowError):
+        return False
+    return load_library().pdmp3_amd_spectral_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def spectral_plan(n_fft, hop):
+    """pdmp3_amd_spectral_plan -> (frames of a workgroup of k_clip_spectral, 0, LDS bytes of a workgroup)"""
+    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
+    if load_library().pdmp3_amd_spectral_plan(int(n_fft), int(hop), C.byref(t), C.byref(p), C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_spectral_plan: bad argument")
+    return t.value, p.value, b.value
+
+
 class StreamIndex:
     """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
     built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
@@ -1366,6 +1413,18 @@ class BulkDecoder:
         f, nm = int(n_frames), int(n_mels)
         spec = lambda: _mel_long_spec(f, sample_rate, n_fft, hop, nm, f_min, f_max, scale, norm, mode, floor, win_length, window, channels, width, rolloff)
         return self._clips_call("mel_long", clips, (nm, f), spec, channels, out)
+
+    def decode_clips_spectral(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, roll_percent=0.85, amin=1e-10, zcr_threshold=1e-10,
+                              channels=0, win_length=None, window=None, out=None, width=0, rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_spectral: clips as decode_clips_stft_long takes them -> (out, valid): out float32
+        [K, C, 6, n_frames], the rows SPECTRAL_ROWS -- librosa.feature's rms (frame_length = n_fft), zero_crossing_rate
+        (threshold = zcr_threshold, pad = False), spectral_centroid, spectral_bandwidth (p = 2), spectral_rolloff (roll_percent) and
+        spectral_flatness (amin, power = 2) -- of frame f centred on sample start + f hop, the stream's own neighbours around the
+        clip, zeros outside the stream and no reflection.  n_fft 2048 or 4096; win_length / window as decode_clips_stft_long.
+        One kernel, k_clip_spectral: no spectrum is written.  valid, out, the exceptions: as decode_clips_mel_long."""
+        f = int(n_frames)
+        spec = lambda: _spectral_spec(f, sample_rate, n_fft, hop, roll_percent, amin, zcr_threshold, channels, win_length, window, width, rolloff)
+        return self._clips_call("spectral", clips, (len(SPECTRAL_ROWS), f), spec, channels, out, refused=(ValueError, OverflowError, TypeError))
 
     def decode_clips_fbank(self, clips, n_frames, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None,
                            hop=None, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",

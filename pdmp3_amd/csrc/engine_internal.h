@@ -189,5 +189,8 @@ hipError_t pdmp3_launch_clip_stft_long(hipStream_t s, const pdmp3_mel_desc* desc
 // ---- mel_long.hip ----
 hipError_t pdmp3_launch_clip_mel_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables, const float* operand,
                                       const pdmp3_mel_long_params* params);
+// ---- spectral.hip ----
+hipError_t pdmp3_launch_clip_spectral(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                                      const pdmp3_spectral_params* params);
 
 #endif

@@ -814,6 +814,32 @@ extern "C" int pdmp3_hip_clip_mel_long(pdmp3_hip_stream* hs, int slot, const pdm
                     return pdmp3_launch_clip_mel_long(hs->s[slot].stream, dk, nk, as_floats(part[0]), as_floats(part[1]), &P);
                   });
 }
+// ---- spectral descriptors at n_fft 2048 and 4096 (spectral.hip) ----
+extern "C" int pdmp3_hip_clip_spectral(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
+                                       const pdmp3_spectral_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !tables || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_spectral: bad argument", hipSuccess);
+  const pdmp3_spectral_params& P = *params;
+  // what the kernel's indexing relies on: one of its two (n2, tile) paths, and the four regions inside the LDS asked for
+  if ((P.n_fft != 2048 && P.n_fft != 4096) || P.n2 != P.n_fft / 64 || P.hop < 1 || P.hop > P.n_fft || P.tile != (P.n2 == 32 ? 8 : 4) ||
+      (P.channels != 1 && P.channels != 2) || P.n_frames < 0 || P.n_in < 0 || !(P.bin_hz > 0.0) || !(P.roll_percent > 0.0 && P.roll_percent < 1.0) ||
+      !(P.amin > 0.0f) || !(P.zcr_threshold >= 0.0f) || (P.span_floats & 3u) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_spectral: bad parameters", hipSuccess);
+  {
+    const size_t span = (size_t)(P.tile - 1) * P.hop + P.n_fft;
+    const size_t z = (size_t)P.tile * P.n2 * 32, plane = (size_t)P.tile * (size_t)(P.n_fft / 2 + 1), res = (size_t)8 * P.tile;
+    if (P.span_floats < span || (size_t)P.lds_bytes < ((size_t)P.span_floats + z + plane + res) * sizeof(float))
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_spectral: a tile's span, Z, plane and results do not fit the LDS asked for", hipSuccess);
+    if (((long long)P.n_frames + P.tile - 1) / P.tile * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_spectral: too many frames", hipSuccess);
+  }
+  // descriptors | the four tables
+  return clip_run(hs, slot, "pdmp3_hip_clip_spectral", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, tables, ((size_t)P.n_fft + 64 * 128 + 2 * (size_t)P.n2 * P.n2 + (size_t)P.n2 * 128) * sizeof(float)}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_spectral(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
+                  });
+}
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,
                                     const pdmp3_fbank_params* params) {

@@ -31,7 +31,7 @@ EXPORTS = [
     "pdmp3_hip_stream_create", "pdmp3_hip_stream_destroy", "pdmp3_hip_stream_reset", "pdmp3_hip_stream_spectra",
     "pdmp3_hip_stream_side", "pdmp3_hip_stream_pcm", "pdmp3_hip_stream_decode",
     "pdmp3_hip_stream_audio_stage", "pdmp3_hip_clip_audio", "pdmp3_hip_copy_from_device", "pdmp3_hip_clip_mel", "pdmp3_hip_clip_fbank",
-    "pdmp3_hip_clip_mfcc", "pdmp3_hip_clip_stft", "pdmp3_hip_clip_stft_long", "pdmp3_hip_clip_mel_long",
+    "pdmp3_hip_clip_mfcc", "pdmp3_hip_clip_stft", "pdmp3_hip_clip_stft_long", "pdmp3_hip_clip_mel_long", "pdmp3_hip_clip_spectral",
     "pdmp3_hip_clip_cqt", "pdmp3_hip_clip_chroma", "pdmp3_hip_clip_loudness", "pdmp3_hip_clip_r128",
     "pdmp3_hip_clip_pitch", "pdmp3_hip_clip_tempogram",
 ]

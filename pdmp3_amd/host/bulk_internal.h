@@ -420,6 +420,10 @@ HOST_LOCAL const float* stft_long_tables(struct bulk* b, const pdmp3_amd_stft_sp
 HOST_LOCAL void mel_long_stft_spec(const pdmp3_amd_mel_long_spec* s, pdmp3_amd_stft_spec* t);
 HOST_LOCAL int mel_long_plan(int n_fft, int hop, int n_mels, pdmp3_mel_long_params* p);
 HOST_LOCAL const float* mel_long_operand(struct bulk* b, long sr, const pdmp3_amd_mel_spec* s);
+/* clip_spectral.c: the frame of a spectral spec as the transform's tables take it, and the check with the plan of a workgroup of
+ * k_clip_spectral for the spec at sr; n_in, n_frames and channels are left to the call (0, or -1 where the check refuses the spec) */
+HOST_LOCAL void spectral_stft_spec(const pdmp3_amd_spectral_spec* s, pdmp3_amd_stft_spec* t);
+HOST_LOCAL int spectral_plan(const pdmp3_amd_spectral_spec* s, long sr, pdmp3_spectral_params* p);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

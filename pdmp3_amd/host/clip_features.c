@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128, _pitch, _tempogram; DESIGN.md sections 9-21).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram, _spectral; DESIGN.md sections 9-22).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -468,6 +468,25 @@ int pdmp3_amd_bulk_decode_clips_mel_long(struct bulk* b, const pdmp3_amd_audio_c
   if (!table || !operand || course_signal(&cc) != 0) return course_finish(&cc, -1);
   P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C; P.out_mode = m->out_mode; P.floor = (float)m->floor;
   if (course_launched(pdmp3_hip_clip_mel_long(b->hs, CLIP_SLOT, cc.ds, cc.nd, table, operand, &P)) != 0) return course_finish(&cc, -1);
+  return course_finish(&cc, cc.rc);
+}
+
+/* ---- spectral descriptors of clips at n_fft 2048 and 4096 ---- */
+int pdmp3_amd_bulk_decode_clips_spectral(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_spectral_spec* spec,
+                                         long long* valid) {
+  clip_course cc;
+  if (!spec || course_begin(&cc, b, clips, n_clips, valid, spec->n_frames, spec->channels, spec->rate, spec->width, spec->rolloff) != 0) return -1;
+  pdmp3_spectral_params P;
+  memset(&P, 0, sizeof P);
+  if (spectral_plan(spec, cc.sr, &P) != 0) return -1;                    /* (the check is its first step) */
+  if (course_rows(&cc, spec->n_fft, spec->hop, PDMP3_SPECTRAL_ROWS, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  pdmp3_amd_stft_spec frame;
+  spectral_stft_spec(spec, &frame);
+  const float* table = stft_long_tables(b, &frame);
+  if (!table || course_signal(&cc) != 0) return course_finish(&cc, -1);
+  P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_spectral(b->hs, CLIP_SLOT, cc.ds, cc.nd, table, &P)) != 0) return course_finish(&cc, -1);
   return course_finish(&cc, cc.rc);
 }
 

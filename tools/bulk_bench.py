@@ -596,6 +596,136 @@ def clips_mel_long(args, api):
     print(json.dumps(res))
 
 
+def clips_spectral(args, api):
+    """--spectral: 64 clips of 30 s (--clips / --clip-frames change that) at 44.1 kHz mono as the six spectral descriptors x 2583
+    frames (n_fft 2048, hop 512, periodic Hann; rms, zcr, centroid, bandwidth, roll-off 0.85, flatness) in device memory, four
+    ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the same spans; (b) (a) followed by torch.stft and the
+    reductions in torch (a dense matmul against the direct table where torch.stft cannot run); (c)
+    pdmp3_amd_bulk_decode_clips_spectral; (d) pdmp3_amd_bulk_decode_clips_stft_long(mode="magnitude") followed by the reductions
+    of rows 2 .. 5 in torch -- the route that writes the magnitude batch to memory and reads it back (rows 0 and 1 need the signal,
+    which (d) does not have: it computes four rows, and is the cheaper for it).  (c) is compared once with (b) and (d) (largest
+    relative difference per row, printed, not asserted: the tests check (c) against the definition).  Medians and min..max of
+    --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop, roll, amin, zt = args.clips, args.clip_frames, 44100, 2048, 512, 0.85, 1e-10, 1e-10
+    bins = n_fft // 2 + 1
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
+    T = (Fm - 1) * hop + n_fft
+    dev = "cuda:0"
+    clips, audio = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        clips.append((files[i], ixs[i], start))
+        audio.append((files[i], ixs[i], start - n_fft // 2))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, 6, Fm), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, 6, Fm), dtype=torch.float32, device=dev)
+    out_d = torch.zeros((K, 1, 6, Fm), dtype=torch.float32, device=dev)
+    out_s = torch.zeros((K, 1, bins, Fm), dtype=torch.float32, device=dev)
+    window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32, device=dev)
+    freq = (torch.arange(bins, dtype=torch.float32, device=dev) * (rate / n_fft))[None, :, None]
+    kp = (bins + 15) // 16 * 16
+    ang = 2.0 * np.pi * ((np.arange(n_fft)[:, None] * np.arange(kp)[None, :]) % n_fft) / n_fft
+    w = (0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n_fft) / n_fft))[:, None]
+    table = torch.from_numpy(np.concatenate([w * np.cos(ang), -w * np.sin(ang)], axis=1).astype(np.float32)).to(dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    how = {"stft": "torch.stft"}
+
+    def reductions(s, out):                              # s [K, bins, Fm] magnitudes -> rows 2 .. 5 of out [K, 6, Fm]
+        total = s.sum(dim=1)
+        safe = torch.clamp(total, min=1e-30)
+        c = (freq * s).sum(dim=1) / safe
+        out[:, 2] = c
+        out[:, 3] = torch.sqrt((s * (freq - c[:, None, :]) ** 2).sum(dim=1) / safe)
+        k = (torch.cumsum(s, dim=1) < (roll * total)[:, None, :]).sum(dim=1)
+        out[:, 4] = torch.clamp(k, max=bins - 1).to(torch.float32) * (rate / n_fft)
+        pm = torch.clamp(s * s, min=amin)
+        out[:, 5] = torch.exp(torch.log(pm).mean(dim=1)) / pm.mean(dim=1)
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def torch_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+        y = out_a[:, 0]
+        s = None
+        if how["stft"] == "torch.stft":
+            try:
+                s = torch.stft(y, n_fft, hop_length=hop, window=window, center=False, return_complex=True).abs()            # [K, bins, Fm]
+            except Exception as e:                      # noqa: BLE001  (no FFT library on this build)
+                how["stft"] = "dense matmul against the table (torch.stft: %s)" % type(e).__name__
+        fr = y.unfold(1, n_fft, hop)                                                                                      # [K, Fm, N]
+        if s is None:
+            x = fr @ table                                                                                                # [K, Fm, 2 Kp]
+            s = torch.sqrt(x[:, :, :bins] ** 2 + x[:, :, kp:kp + bins] ** 2).transpose(1, 2)
+        out_b[:, 0, 0] = torch.sqrt((fr * fr).mean(dim=2))
+        neg = fr < -zt
+        out_b[:, 0, 1] = (neg[:, :, 1:] != neg[:, :, :-1]).sum(dim=2).to(torch.float32) / n_fft
+        reductions(s, out_b[:, 0])
+        torch.cuda.synchronize()
+
+    def spectral_route():
+        dec.decode_clips_spectral(clips, Fm, rate, n_fft, hop, roll, amin, zt, channels=1, out=out_c)
+
+    def magnitude_route():
+        dec.decode_clips_stft_long(clips, Fm, rate, n_fft, hop, mode="magnitude", out=out_s)
+        reductions(out_s[:, 0], out_d[:, 0])
+        torch.cuda.synchronize()
+
+    routes = [("audio clips", audio_route), ("audio clips + torch.stft + reductions", torch_route), ("spectral clips", spectral_route),
+              ("stft_long magnitude clips + reductions", magnitude_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 4:] + routes[:r % 4]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            rel = lambda o, rows: [float(((o[:, 0, i] - out_c[:, 0, i]).abs() / torch.clamp(out_c[:, 0, i].abs(), min=1e-3)).max()) for i in rows]
+            diff = {"torch_route_rows_0_to_5": rel(out_b, range(6)), "magnitude_route_rows_2_to_5": rel(out_d, range(2, 6))}
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as 6 spectral descriptors x %d frames at %d Hz mono (n_fft %d, hop %d): %s" % (
+               K, F, Fm, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
+           "magnitude_batch_bytes": K * bins * Fm * 4, "result_bytes": K * 6 * Fm * 4,
+           "largest_relative_difference_from_spectral": diff, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    res["spectral_minus_audio_ms"] = round((med["spectral clips"] - med["audio clips"]) * 1e3, 3)
+    res["magnitude_route_minus_audio_ms"] = round((med["stft_long magnitude clips + reductions"] - med["audio clips"]) * 1e3, 3)
+    res["torch_route_minus_audio_ms"] = round((med["audio clips + torch.stft + reductions"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(spread * 1e3, 3)
+    res["spectral_cheaper_than_the_magnitude_route_by_more_than_the_spread"] = bool(
+        med["stft_long magnitude clips + reductions"] - med["spectral clips"] > spread)
+    res["spectral_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(
+        med["audio clips + torch.stft + reductions"] - med["spectral clips"] > spread)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_cqt(args, api):
     """--cqt: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as the magnitudes of 84 constant-Q bins
     (C1, 12 an octave, norm 1, scale 1) x 1292 frames (hop 512) in device memory, three ways, run after run in turn: (a)
@@ -1360,6 +1490,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as onset envelope, tempogram [384, 1292] and tempo at 22 050 Hz mono with "
                          "librosa's defaults (pdmp3_amd_bulk_decode_clips_tempogram, all three modes) against the audio call alone, the log-mel "
                          "call alone and that call followed by the same algorithm in torch on the device (see clips_tempogram())")
+    ap.add_argument("--spectral", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as 6 x 2583 spectral descriptors at 44.1 kHz mono, n_fft 2048, hop 512 "
+                         "(pdmp3_amd_bulk_decode_clips_spectral) against the audio call alone, the audio call followed by torch kernels, and "
+                         "pdmp3_amd_bulk_decode_clips_stft_long's magnitudes followed by the reductions in torch (see clips_spectral())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1367,7 +1501,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1385,6 +1519,8 @@ def main():
             return clips_tempogram(args, api)
         if args.mel_long:
             return clips_mel_long(args, api)
+        if args.spectral:
+            return clips_spectral(args, api)
         if args.stft or args.stft_long:
             return clips_stft(args, api, long=args.stft_long)
         if args.mfcc:
