@@ -1069,6 +1069,68 @@ int pdmp3_amd_spectral_plan(int n_fft, int hop, int* tile, int* row_pad, unsigne
 int pdmp3_amd_bulk_decode_clips_spectral(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_spectral_spec* spec,
                                          long long* valid);
 
+/* ---- Harmonic-percussive separation of clips at n_fft 2048 and 4096 ----
+ * Median-filter separation of the magnitude spectrogram (librosa.decompose.hpss, librosa.effects.harmonic / percussive) of K
+ * clips as one planar float32 batch, frames innermost, rows of K and C may be strided.  New entry points only.
+ * Frame and signal are the two-stage transform's above: n_fft = N is 2048 or 4096, hop = H 1 .. N, win_length 0 (= N) or 1 .. N
+ * centred as torch.stft centres it, window NULL (periodic Hann of win_length) or the caller's binary32 values; there is no
+ * `normalized`; real neighbours inside the stream, zeros outside, no reflection; rate, channels, width, rolloff, valid[k], rate 0
+ * and channels 0 as pdmp3_amd_bulk_decode_clips_stft_long.
+ * K = N / 2 + 1 bins, F = n_frames; Lh = kernel_harm (frames) and Lp = kernel_perc (bins) are odd, 3 .. 31 (librosa: 31 / 31);
+ * rh = (Lh - 1) / 2, rp = (Lp - 1) / 2.
+ *   1. S[k][f] is the binary32 value pdmp3_amd_bulk_decode_clips_stft_long stores at out_mode 1 for bin k of the frame centred
+ *      on sample start + f H, bit for bit (the same kernel), f = -rh .. F - 1 + rh.  In mode 2 Re and Im are that call's
+ *      out_mode 0 values and S = sqrtf(fma(Im, Im, Re Re)), that kernel's expression.
+ *   2. Hm[k][f] is the (rh + 1)-th smallest of S[k][f - rh .. f + rh]: along time over the stream's real frames (librosa
+ *      reflects at a clip's edge; here a clip stays the slice of a longer one).
+ *   3. Pm[k][f] is the (rp + 1)-th smallest of S[rho(i)][f], i = k - rp .. k + rp; rho(i) = -1 - i for i < 0, 2 K - 1 - i for
+ *      i >= K, else i: scipy.ndimage.median_filter(mode = "reflect"), numpy's "symmetric", as librosa along frequency.
+ *      A median of an odd count is one of its elements and every S is +0 or positive and finite: Hm and Pm are exact.
+ *   4. Masks (librosa.util.softmask): (X, R) = (Hm, margin_harm Pm) for the harmonic mask, (Pm, margin_perc Hm) for the
+ *      percussive one, the product one binary64 multiplication.  power is exactly 1, 2 or +inf.  Finite power: where
+ *      max(X, R) < 2^-126 the mask is 0.5 if both margins are 1, else 0; otherwise m = X^p / (X^p + R^p) in binary64, rounded
+ *      once to binary32.  power = +inf: m = 1 if X > R, else 0.
+ *   5. out_mode, component 0 harmonic, 1 percussive:
+ *        0 mask       [K][C][2][bins][F]     m
+ *        1 magnitude  [K][C][2][bins][F]     fl32(S m), one binary32 multiplication with mode 0's m
+ *        2 complex    [K][C][2][bins][F][2]  (fl32(Re m), fl32(Im m)): what torch.istft takes
+ *        3 median     [K][C][2][bins][F]     Hm and Pm themselves
+ *      The modes agree bit for bit: mode 1 is mode 0 times the spectrum call's magnitude, mode 2 mode 0 times its complex
+ *      output, mode 0 the stated function of mode 3.
+ * Every element comes from the same operations whatever its tile, clip or batch; no atomics: two runs are bit-equal.
+ * Not offered: any other power, kernels above 31, reflection along time, n_fft <= 1024. */
+typedef struct pdmp3_amd_hpss_spec {
+  long rate; int channels; int width; double rolloff;   /* as pdmp3_amd_mel_spec (rolloff: the resampling filter's) */
+  int n_fft, hop, win_length;                           /* N: 2048 or 4096; 1 .. N; 0 = N, else 1 .. N */
+  const float* window;                                  /* win_length values, NULL = periodic Hann */
+  long long n_frames;
+  int kernel_harm, kernel_perc;                         /* odd, 3 .. 31: frames; bins */
+  double margin_harm, margin_perc;                      /* >= 1, finite; librosa's default is 1 */
+  double power;                                         /* 1, 2 or +inf; librosa's default is 2 */
+  int out_mode;                                         /* 0 mask, 1 magnitude, 2 complex, 3 median */
+} pdmp3_amd_hpss_spec;
+#define PDMP3_HPSS_MAX_KERNEL 31
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: whatever pdmp3_amd_stft_long_check refuses (any
+ * other n_fft, hop outside 1 .. n_fft, a bad win_length or window value, sr <= 0), a kernel size that is even or outside
+ * 3 .. 31, a margin below 1 or not finite, a power other than 1, 2 and +inf, out_mode outside 0 .. 3, n_frames < 0, a channel's
+ * row of the output (2 bins n_frames floats, twice that in mode 2) or of the stage (bins (n_frames + kernel_harm - 1)) beyond
+ * 2^31 - 1 floats. */
+int pdmp3_amd_hpss_check(const pdmp3_amd_hpss_spec* spec, long sr);
+/* What the call launches, the function the call itself uses: *front and *back, the frames of the spectrum in front of frame 0
+ * and behind frame F - 1 (both kernel_harm / 2); *tile_bins x *tile_frames, the elements of a workgroup of k_clip_hpss
+ * (64 x 64 for every pair of sizes); *pitch, the floats between two rows of its tile in LDS (64 + 30), and *lds_bytes
+ * ((64 + 30) x pitch x 4: the layout has room for 15 bins and 15 frames around the tile, of which kernel_perc / 2 and
+ * kernel_harm / 2 are loaded).  Pointers may be NULL.  0, or -1 on a bad kernel size. */
+int pdmp3_amd_hpss_plan(int kernel_harm, int kernel_perc, int* front, int* back, int* tile_bins, int* tile_frames, int* pitch,
+                        unsigned* lds_bytes);
+/* Row k receives channel c's [2][bins][F] floats (mode 2: [2][bins][F][2]) at dst + c * chan_stride.  Three steps: the audio
+ * call for the clips widened to start - rh H and F + 2 rh frames; k_clip_stft_long, unchanged, into a stage of the decoder
+ * (magnitudes; mode 2: complex values); k_clip_hpss (csrc/hpss.hip) writes the rows.  Everything else -- host destinations, the
+ * per-clip refusals in valid[k], rate 0 / channels 0, width, rolloff, the counts, n_clips = 0 and n_frames = 0, synchronous --
+ * as pdmp3_amd_bulk_decode_clips_stft_long.  -1, nothing written, also where pdmp3_amd_hpss_check says so. */
+int pdmp3_amd_bulk_decode_clips_hpss(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_hpss_spec* spec,
+                                     long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

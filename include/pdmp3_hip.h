@@ -485,7 +485,7 @@ typedef struct pdmp3_audio_desc {
 /* The stream object's audio stages: device memory (hipMalloc, kept and grown on demand; call with nothing of the audio
  * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory; 2: the
  * resampled signal the log-mel call reads (below); 3: what the tempogram call keeps between its kernels (log-mel, envelope,
- * tempogram).  NULL on failure. */
+ * tempogram), or the separation call its spectrum.  NULL on failure. */
 void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes);
 /* Uploads the launch's tables (descs, frames, tables: host memory) and runs k_clip_audio on the slot's HIP stream, behind
  * whatever the slot ran last (the last clip window's k_clip_pack); n_samples output samples per row, channels = 1 or 2.
@@ -662,6 +662,27 @@ typedef struct pdmp3_spectral_params {
  * size.  Blocks until the rows are written. */
 int pdmp3_hip_clip_spectral(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                             const pdmp3_spectral_params* params);
+
+/* Median-filter harmonic-percussive separation of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_hpss; DESIGN.md
+ * section 23).  k_clip_hpss (hpss.hip) reads what k_clip_stft_long wrote into audio stage 3 -- a descriptor's src: channel 0's
+ * [bins][n_stage] magnitudes (out_mode 2: [bins][n_stage][2], Re and Im), src_chan_stride floats between the channels; stage
+ * frame j is the clip's frame j - kernel_harm / 2 -- and writes [2][bins][n_frames] floats per channel at dst (out_mode 2:
+ * [2][bins][n_frames][2]), component 0 harmonic, 1 percussive, frames innermost; lead is not read.  A workgroup of four waves
+ * takes tile_bins x tile_frames elements; its LDS is the tile with 15 bins and 15 frames around it, of which kernel_perc / 2 and
+ * kernel_harm / 2 are loaded, rows `pitch` floats apart (csrc/hpss_core.h). */
+typedef struct pdmp3_hpss_params {
+  int32_t n_fft, bins;                      /* N: 2048 or 4096; K = N / 2 + 1                                           */
+  int32_t n_frames, n_stage;                /* F; F + kernel_harm - 1: the frames of a row of the stage                 */
+  int32_t kernel_harm, kernel_perc;         /* odd, 3 .. 31: frames; bins                                               */
+  int32_t tile_bins, tile_frames;           /* 64 x 64                                                                  */
+  int32_t pitch, channels;                  /* tile_frames + 30                                                         */
+  int32_t out_mode, power;                  /* 0 mask, 1 magnitude, 2 complex, 3 median; 1, 2, or 0 for +inf            */
+  double margin_harm, margin_perc;          /* >= 1                                                                     */
+  uint32_t lds_bytes, pad_;
+} pdmp3_hpss_params;
+/* Uploads the descriptors -- host memory -- and runs k_clip_hpss on the slot's HIP stream, one launch per 32 768 clips.  The
+ * tile, the pitch and lds_bytes must be csrc/hpss_core.h's (pdmp3_amd_hpss_plan's), and lds_bytes <= PDMP3_MEL_LDS_MAX.  Blocks until the rows are written. */
+int pdmp3_hip_clip_hpss(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_hpss_params* params);
 
 /* The constant-Q transform of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt).
  * k_clip_cqt (cqt.hip) reads the rows as k_clip_stft does (pdmp3_mel_desc; a frame's span is rows0 samples, its centre the

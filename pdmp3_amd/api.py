@@ -37,7 +37,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_pitch_check", "pdmp3_amd_pitch_lags", "pdmp3_amd_pitch_plan", "pdmp3_amd_bulk_decode_clips_pitch",
                 "pdmp3_amd_tempogram_check", "pdmp3_amd_tempogram_window", "pdmp3_amd_tempogram_prior", "pdmp3_amd_tempogram_plan",
                 "pdmp3_amd_bulk_decode_clips_tempogram",
-                "pdmp3_amd_spectral_check", "pdmp3_amd_spectral_plan", "pdmp3_amd_bulk_decode_clips_spectral"]
+                "pdmp3_amd_spectral_check", "pdmp3_amd_spectral_plan", "pdmp3_amd_bulk_decode_clips_spectral",
+                "pdmp3_amd_hpss_check", "pdmp3_amd_hpss_plan", "pdmp3_amd_bulk_decode_clips_hpss"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -227,6 +228,10 @@ def load_library():
         lib.pdmp3_amd_spectral_check.argtypes = [vp, C.c_long]
         lib.pdmp3_amd_spectral_plan.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_spectral.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_hpss"):         # (harmonic-percussive separation: absent from older builds)
+        lib.pdmp3_amd_hpss_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_hpss_plan.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_hpss.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -938,6 +943,55 @@ def spectral_plan(n_fft, hop):
     return t.value, p.value, b.value
 
 
+class _HpssSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_hpss_spec
+    _fields_ = [("rate", C.c_long), ("channels", C.c_int), ("width", C.c_int), ("rolloff", C.c_double), ("n_fft", C.c_int), ("hop", C.c_int),
+                ("win_length", C.c_int), ("window", C.c_void_p), ("n_frames", C.c_longlong), ("kernel_harm", C.c_int), ("kernel_perc", C.c_int),
+                ("margin_harm", C.c_double), ("margin_perc", C.c_double), ("power", C.c_double), ("out_mode", C.c_int)]
+
+
+HPSS_MODES = {"mask": 0, "magnitude": 1, "complex": 2, "median": 3}
+
+
+def _hpss_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, kernel_size=31, power=2.0, margin=1.0, mode="mask", channels=1,
+               win_length=None, window=None, width=0, rolloff=0.0):
+    """-> (spec, the float32 array its window points to, to be kept while the spec is in use); kernel_size and margin: one
+    number or (harmonic, percussive), as librosa takes them"""
+    w = None
+    if window is not None:
+        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
+        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
+            raise ValueError("hpss: window must hold win_length values")
+        win_length = w.size
+    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    kh, kp = kernel_size if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
+    mh, mp = margin if isinstance(margin, (tuple, list)) else (margin, margin)
+    if int(kh) != kh or int(kp) != kp:
+        raise ValueError("hpss: kernel sizes are integers")
+    spec = _HpssSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, w.ctypes.data if w is not None else None,
+                     int(n_frames), int(kh), int(kp), float(mh), float(mp), float(power), HPSS_MODES[mode] if isinstance(mode, str) else int(mode))
+    return spec, w
+
+
+def hpss_check(sample_rate=22050, **kw):
+    """pdmp3_amd_hpss_check -> True when pdmp3_amd_bulk_decode_clips_hpss would accept these numbers (decode_clips_hpss's
+    argument names) at sample_rate"""
+    try:
+        spec, keep = _hpss_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, TypeError, OverflowError):
+        return False
+    return load_library().pdmp3_amd_hpss_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def hpss_plan(kernel_harm=31, kernel_perc=31):
+    """pdmp3_amd_hpss_plan -> (frames in front, frames behind, bins of a workgroup of k_clip_hpss, its frames, the floats between
+    two rows of its tile in LDS, its LDS bytes)"""
+    v = [C.c_int(0) for _ in range(5)]
+    b = C.c_uint(0)
+    if load_library().pdmp3_amd_hpss_plan(int(kernel_harm), int(kernel_perc), *[C.byref(x) for x in v], C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_hpss_plan: bad argument")
+    return tuple(x.value for x in v) + (b.value,)
+
+
 class StreamIndex:
     """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
     built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
@@ -1425,6 +1479,25 @@ class BulkDecoder:
         f = int(n_frames)
         spec = lambda: _spectral_spec(f, sample_rate, n_fft, hop, roll_percent, amin, zcr_threshold, channels, win_length, window, width, rolloff)
         return self._clips_call("spectral", clips, (len(SPECTRAL_ROWS), f), spec, channels, out, refused=(ValueError, OverflowError, TypeError))
+
+    def decode_clips_hpss(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, kernel_size=31, power=2.0, margin=1.0, mode="mask",
+                          channels=0, win_length=None, window=None, out=None, width=0, rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_hpss: clips as decode_clips_stft_long takes them -> (out, valid): median-filter
+        harmonic-percussive separation (librosa.decompose.hpss) of the magnitudes decode_clips_stft_long gives for frame f centred
+        on sample start + f hop.  out[:, :, 0] is the harmonic component, out[:, :, 1] the percussive one; mode "mask": float32
+        [K, C, 2, n_fft / 2 + 1, n_frames], the soft masks (power 1, 2 or inf; margin >= 1); "magnitude": the masked magnitudes;
+        "complex": complex64 of the same shape, the masked spectrum, which torch.istft takes; "median": the two median-filtered
+        spectrograms.  kernel_size and margin: one number or (harmonic, percussive); sizes odd, 3 .. 31.  The harmonic median
+        runs over the stream's own frames in front of and behind the clip (zeros outside the stream, no reflection along time),
+        the percussive one reflects at bins 0 and n_fft / 2 as scipy's "reflect" does.  n_fft 2048 or 4096; win_length / window
+        as decode_clips_stft_long.  valid, out, the exceptions: as decode_clips_mel_long."""
+        f, nb = int(n_frames), int(n_fft) // 2 + 1
+        m = HPSS_MODES.get(mode) if isinstance(mode, str) else mode
+        if m not in (0, 1, 2, 3):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_hpss: mode is \"mask\", \"magnitude\", \"complex\" or \"median\"")
+        spec = lambda: _hpss_spec(f, sample_rate, n_fft, hop, kernel_size, power, margin, m, channels, win_length, window, width, rolloff)
+        return self._clips_call("hpss", clips, (2, nb, f, 2) if m == 2 else (2, nb, f), spec, channels, out, complex_ok=m == 2,
+                                refused=(ValueError, OverflowError, TypeError))
 
     def decode_clips_fbank(self, clips, n_frames, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None,
                            hop=None, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",

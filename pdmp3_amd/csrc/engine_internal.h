@@ -192,5 +192,7 @@ hipError_t pdmp3_launch_clip_mel_long(hipStream_t s, const pdmp3_mel_desc* descs
 // ---- spectral.hip ----
 hipError_t pdmp3_launch_clip_spectral(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* tables,
                                       const pdmp3_spectral_params* params);
+// ---- hpss.hip ----
+hipError_t pdmp3_launch_clip_hpss(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_hpss_params* params);
 
 #endif

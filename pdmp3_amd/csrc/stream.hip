@@ -13,6 +13,7 @@
 #include "resample_core.h"
 #include "pitch_core.h"
 #include "tempogram_core.h"
+#include "hpss_core.h"
 
 using namespace pdmp3;
 
@@ -839,6 +840,31 @@ extern "C" int pdmp3_hip_clip_spectral(pdmp3_hip_stream* hs, int slot, const pdm
                   [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
                     return pdmp3_launch_clip_spectral(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
                   });
+}
+// ---- harmonic-percussive separation (hpss.hip) ----
+extern "C" int pdmp3_hip_clip_hpss(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_hpss_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_hpss: bad argument", hipSuccess);
+  const pdmp3_hpss_params& P = *params;
+  const auto kernel_ok = [](int l) { return l >= 3 && l <= pdmp3::kHpssMaxKernel && (l & 1); };
+  // what the kernel's indexing relies on: the one tile and layout of hpss_core.h, the stage's frames, rows inside 31 bits
+  if ((P.n_fft != 2048 && P.n_fft != 4096) || P.bins != P.n_fft / 2 + 1 || !kernel_ok(P.kernel_harm) || !kernel_ok(P.kernel_perc) || P.n_frames < 0 ||
+      P.n_stage != (long long)P.n_frames + P.kernel_harm - 1 || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 || P.out_mode > 3 ||
+      (P.power != 0 && P.power != 1 && P.power != 2) || !(P.margin_harm >= 1.0 && P.margin_harm <= 1.7976931348623157e308) ||
+      !(P.margin_perc >= 1.0 && P.margin_perc <= 1.7976931348623157e308))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_hpss: bad parameters", hipSuccess);
+  if (P.tile_bins != pdmp3::kHpssBins || P.tile_frames != pdmp3::kHpssFrames || P.pitch != pdmp3::kHpssPitch ||
+      P.lds_bytes != pdmp3::kHpssLdsFloats * sizeof(float) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_hpss: not the plan's tile, pitch and LDS", hipSuccess);
+  {
+    const long long e = P.out_mode == 2 ? 2 : 1, tiles = ((long long)P.n_frames + pdmp3::kHpssFrames - 1) / pdmp3::kHpssFrames;
+    if (e * P.bins * (long long)P.n_stage > 0x7fffffffLL || 2 * e * P.bins * (long long)P.n_frames > 0x7fffffffLL ||
+        tiles * pdmp3::hpss_bin_tiles(P.bins) * P.channels > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_hpss: too many frames", hipSuccess);
+  }
+  // descriptors alone: the kernel reads no table
+  return clip_run(hs, slot, "pdmp3_hip_clip_hpss", descs, n_clips, P.n_frames, {{ClipPart::kScratch, nullptr, 0}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const*) { return pdmp3_launch_clip_hpss(hs->s[slot].stream, dk, nk, &P); });
 }
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,

@@ -424,6 +424,11 @@ HOST_LOCAL const float* mel_long_operand(struct bulk* b, long sr, const pdmp3_am
  * k_clip_spectral for the spec at sr; n_in, n_frames and channels are left to the call (0, or -1 where the check refuses the spec) */
 HOST_LOCAL void spectral_stft_spec(const pdmp3_amd_spectral_spec* s, pdmp3_amd_stft_spec* t);
 HOST_LOCAL int spectral_plan(const pdmp3_amd_spectral_spec* s, long sr, pdmp3_spectral_params* p);
+/* clip_hpss.c: the frame of a separation spec as the transform's tables take it (out_mode: what the stage holds), and the check
+ * with the plan of k_clip_hpss for the spec at sr and the frames a clip is widened by; n_frames, n_stage and channels are left
+ * to the call (0, or -1 where the check refuses the spec) */
+HOST_LOCAL void hpss_stft_spec(const pdmp3_amd_hpss_spec* s, pdmp3_amd_stft_spec* t);
+HOST_LOCAL int hpss_plan(const pdmp3_amd_hpss_spec* s, long sr, pdmp3_hpss_params* p, int* front, int* back);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

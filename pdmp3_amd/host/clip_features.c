@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128, _pitch, _tempogram, _spectral; DESIGN.md sections 9-22).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss; DESIGN.md sections 9-23).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -219,7 +219,7 @@ typedef struct {
   int* host;                         /* per descriptor: its clip, if that one's rows go to host memory, else -1 */
   int nd;
   size_t out_floats;                 /* floats of stage 1 the host destinations' rows take */
-  /* the tempogram call's extension, zero for every other call: a row is read for `front` frames in front of frame 0 and `back`
+  /* the tempogram and separation calls' extension, zero for every other call: a row is read for `front` frames in front of frame 0 and `back`
    * frames behind frame F - 1 as well (valid[] stays relative to `start` and F); per_fixed: floats of a channel's output where
    * they are not per_frame F */
   int front, back;
@@ -545,6 +545,50 @@ int pdmp3_amd_bulk_decode_clips_tempogram(struct bulk* b, const pdmp3_amd_audio_
   rc = cc.rc;
 out:
   free(md); free(td); free(w); free(prior);
+  return course_finish(&cc, rc);
+}
+
+/* ---- harmonic-percussive separation of clips ---- */
+/* The two-stage transform's course on rows widened by the frames the harmonic median reaches, its kernel writing into audio
+ * stage 3 instead of the destination: magnitudes, or (mode 2) complex values; k_clip_hpss reads them there. */
+int pdmp3_amd_bulk_decode_clips_hpss(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_hpss_spec* spec,
+                                     long long* valid) {
+  clip_course cc;
+  if (!spec || course_begin(&cc, b, clips, n_clips, valid, spec->n_frames, spec->channels, spec->rate, spec->width, spec->rolloff) != 0) return -1;
+  pdmp3_hpss_params Q;
+  pdmp3_stft_long_params P;
+  memset(&Q, 0, sizeof Q);
+  memset(&P, 0, sizeof P);
+  if (hpss_plan(spec, cc.sr, &Q, &cc.front, &cc.back) != 0) return -1;       /* (the check is its first step) */
+  pdmp3_amd_stft_spec frame;
+  hpss_stft_spec(spec, &frame);
+  if (stft_long_plan(frame.n_fft, frame.hop, frame.out_mode, &P) != 0) return -1;
+  const int e = spec->out_mode == 2 ? 2 : 1;                                  /* floats of a value */
+  if (course_rows(&cc, spec->n_fft, spec->hop, 2 * e * P.bins, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const long long F = cc.F, Fs = F + cc.front + cc.back;
+  const size_t spec_floats = (size_t)e * (size_t)P.bins * (size_t)Fs;         /* of a channel in the stage */
+  const float* table = stft_long_tables(b, &frame);
+  pdmp3_mel_desc* sd = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *sd);
+  pdmp3_mel_desc* hd = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *hd);
+  int rc = -1;
+  if (!table || !sd || !hd || course_signal(&cc) != 0) goto out;
+  float* const stage = (float*)pdmp3_hip_stream_audio_stage(b->hs, 3, (size_t)cc.nd * (size_t)cc.C * spec_floats * sizeof(float));
+  if (!stage) goto out;
+  for (int i = 0; i < cc.nd; i++) {
+    sd[i] = cc.ds[i];
+    sd[i].dst = (uint64_t)(uintptr_t)(stage + (size_t)i * (size_t)cc.C * spec_floats);
+    sd[i].dst_chan_stride = spec_floats;
+    hd[i].src = sd[i].dst; hd[i].src_chan_stride = spec_floats;
+    hd[i].dst = cc.ds[i].dst; hd[i].dst_chan_stride = cc.ds[i].dst_chan_stride;
+  }
+  P.n_in = cc.T; P.n_frames = (int32_t)Fs; P.channels = cc.C; P.floor = 0.0f;
+  if (course_launched(pdmp3_hip_clip_stft_long(b->hs, CLIP_SLOT, sd, cc.nd, table, &P)) != 0) goto out;
+  Q.n_frames = (int32_t)F; Q.n_stage = (int32_t)Fs; Q.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_hpss(b->hs, CLIP_SLOT, hd, cc.nd, &Q)) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(sd); free(hd);
   return course_finish(&cc, rc);
 }
 

@@ -726,6 +726,119 @@ def clips_spectral(args, api):
     print(json.dumps(res))
 
 
+def clips_hpss(args, api):
+    """--hpss: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as the soft masks of median-filter
+    harmonic-percussive separation [2, 1025, 1292] (n_fft 2048, hop 512, kernels 31 / 31, power 2, margins 1) in device memory,
+    four ways, run after run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the widened spans; (b)
+    pdmp3_amd_bulk_decode_clips_stft_long(mode="magnitude") of the widened clips; (c) pdmp3_amd_bulk_decode_clips_hpss; (d) (b)
+    followed by the same algorithm in torch -- unfold + median along both axes, then the mask.  (c) is compared once with (d)
+    (largest difference, printed, not asserted: the tests check (c) against the definition).  Also timed with device events: a
+    plain copy of two planes, the bytes k_clip_hpss writes.  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop, lh, lp = args.clips, args.clip_frames, 22050, 2048, 512, 31, 31
+    bins, rh, rp = n_fft // 2 + 1, lh // 2, lp // 2
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
+    Fw = Fm + 2 * rh
+    T = (Fw - 1) * hop + n_fft
+    dev = "cuda:0"
+    clips, wide, audio = [], [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2 + rh * hop)      # (no leading zeros in the widened clip)
+        clips.append((files[i], ixs[i], start))
+        wide.append((files[i], ixs[i], start - rh * hop))
+        audio.append((files[i], ixs[i], start - rh * hop - n_fft // 2))
+    out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    out_s = torch.zeros((K, 1, bins, Fw), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, 2, bins, Fm), dtype=torch.float32, device=dev)
+    out_d = torch.zeros((K, 1, 2, bins, Fm), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def audio_route():
+        dec.decode_clips_audio(audio, T, rate, 1, out=out_a)
+
+    def magnitude_route():
+        dec.decode_clips_stft_long(wide, Fw, rate, n_fft, hop, mode="magnitude", out=out_s)
+
+    def hpss_route():
+        dec.decode_clips_hpss(clips, Fm, rate, n_fft, hop, (lh, lp), 2.0, 1.0, "mask", channels=1, out=out_c)
+
+    def torch_route():
+        dec.decode_clips_stft_long(wide, Fw, rate, n_fft, hop, mode="magnitude", out=out_s)
+        for k in range(K):                               # (a clip at a time: the unfolded windows of one are 31 x its spectrogram)
+            s = out_s[k, 0]                                                                   # [bins, Fw]
+            hm = s.unfold(1, lh, 1).median(dim=2).values                                      # [bins, Fm]
+            c = s[:, rh:rh + Fm]
+            sym = torch.cat([c[:rp].flip(0), c, c[bins - rp:].flip(0)], dim=0)                # numpy's "symmetric"
+            pm = sym.unfold(0, lp, 1).median(dim=2).values                                    # [bins, Fm]
+            h2, p2 = hm.double() ** 2, pm.double() ** 2
+            tot = h2 + p2
+            silent = torch.maximum(hm, pm) < 2.0 ** -126
+            safe = torch.where(silent, torch.ones_like(tot), tot)
+            out_d[k, 0, 0] = torch.where(silent, 0.5, h2 / safe).float()
+            out_d[k, 0, 1] = torch.where(silent, 0.5, p2 / safe).float()
+        torch.cuda.synchronize()
+
+    routes = [("audio clips", audio_route), ("stft_long magnitude clips", magnitude_route), ("hpss clips", hpss_route),
+              ("stft_long magnitude clips + torch medians and masks", torch_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 4:] + routes[:r % 4]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = float((out_d - out_c).abs().max())
+    copies = []
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for r in range(args.warmup_runs + args.runs):
+        e0.record()
+        out_d.copy_(out_c)
+        e1.record()
+        torch.cuda.synchronize()
+        if r >= args.warmup_runs:
+            copies.append(e0.elapsed_time(e1))
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as harmonic and percussive masks [2, %d, %d] at %d Hz mono (n_fft %d, hop %d, kernels %d / %d, "
+                       "power 2): %s" % (K, F, bins, Fm, rate, n_fft, hop, lh, lp,
+                                         "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "stage_bytes": K * bins * Fw * 4, "result_bytes": K * 2 * bins * Fm * 4, "largest_difference_of_the_torch_route_from_hpss": diff,
+           "plain_copy_of_the_result_ms": {"median": round(statistics.median(copies), 4), "min": round(min(copies), 4), "max": round(max(copies), 4)},
+           "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    res["hpss_minus_magnitude_ms"] = round((med["hpss clips"] - med["stft_long magnitude clips"]) * 1e3, 3)
+    res["torch_route_minus_magnitude_ms"] = round((med["stft_long magnitude clips + torch medians and masks"] - med["stft_long magnitude clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(spread * 1e3, 3)
+    res["hpss_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(
+        med["stft_long magnitude clips + torch medians and masks"] - med["hpss clips"] > spread)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_cqt(args, api):
     """--cqt: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as the magnitudes of 84 constant-Q bins
     (C1, 12 an octave, norm 1, scale 1) x 1292 frames (hop 512) in device memory, three ways, run after run in turn: (a)
@@ -1494,6 +1607,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as 6 x 2583 spectral descriptors at 44.1 kHz mono, n_fft 2048, hop 512 "
                          "(pdmp3_amd_bulk_decode_clips_spectral) against the audio call alone, the audio call followed by torch kernels, and "
                          "pdmp3_amd_bulk_decode_clips_stft_long's magnitudes followed by the reductions in torch (see clips_spectral())")
+    ap.add_argument("--hpss", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as harmonic and percussive soft masks [2, 1025, 1292] at 22 050 Hz mono, "
+                         "n_fft 2048, hop 512, kernels 31 / 31, power 2 (pdmp3_amd_bulk_decode_clips_hpss) against the audio call alone, "
+                         "pdmp3_amd_bulk_decode_clips_stft_long's magnitudes alone and those followed by the same algorithm in torch (see clips_hpss())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1501,7 +1618,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral or args.hpss:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1521,6 +1638,8 @@ def main():
             return clips_mel_long(args, api)
         if args.spectral:
             return clips_spectral(args, api)
+        if args.hpss:
+            return clips_hpss(args, api)
         if args.stft or args.stft_long:
             return clips_stft(args, api, long=args.stft_long)
         if args.mfcc:
