@@ -1131,6 +1131,77 @@ int pdmp3_amd_hpss_plan(int kernel_harm, int kernel_perc, int* front, int* back,
 int pdmp3_amd_bulk_decode_clips_hpss(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_hpss_spec* spec,
                                      long long* valid);
 
+/* ---- MFCC, deltas and dB mel of clips at n_fft 2048 and 4096 ----
+ * librosa.feature.mfcc with librosa.feature.delta stacked under it, and librosa.power_to_db(melspectrogram) with top_db, of K
+ * clips as one planar float32 batch, frames innermost, rows of K and C may be strided.  New entry points only; the Kaldi
+ * call above (section 12) is a different definition.  The log-mel's parameters are pdmp3_amd_mel_long_spec's (mel.mel.floor is
+ * librosa's amin; mel.mel.out_mode is not read); F = mel.mel.n_frames.
+ * h = (delta_width - 1) / 2 if deltas > 0 and out_mode is 0, else 0.
+ *   1. Log-mel.  l[m][t], t = -h .. F - 1 + h, is the binary32 value pdmp3_amd_bulk_decode_clips_mel_long stores at out_mode 2
+ *      (log10 max(M, floor)) for the clip (start - h hop, F + 2 h), bit for bit (the same kernel): real neighbours inside the
+ *      stream, zeros outside it, no reflection.  valid[k] is that call's count for the clip (start, F).
+ *   2. dB.  d0[m][t] = fl32(10 l[m][t]), one binary32 product.  top_db >= 0: Mx = max d0[m][t] over all m and the clip's own
+ *      frames t = 0 .. F - 1 -- the halo does not count --, per clip AND channel; thr = fl32(Mx - fl32(top_db));
+ *      d = max(d0, thr).  top_db < 0: d = d0.  Mono is librosa.power_to_db(S, ref = 1.0, amin, top_db); for a stereo clip
+ *      librosa takes one maximum over both channels, this call one per channel.  Every operation is one binary32 rounding and
+ *      max is exact: d is reproducible bit for bit in binary32 from the log-mel call's values.
+ *   3. Cepstra.  c[q][t] = sum_m T[q][m] d[m][t], q < n_mfcc <= n_mels;
+ *      T[q][m] = s_q cos(pi q (2 m + 1) / (2 n_mels)) (1 + (lifter / 2) sin(pi (q + 1) / lifter)), s_0 = sqrt(1 / n_mels),
+ *      s_q = sqrt(2 / n_mels) for q > 0, the lifter's factor 1 at lifter = 0: scipy.fft.dct(type = 2, norm = "ortho") and
+ *      librosa's lifter.  T is formed in binary64 and rounded once; a cepstrum is one chain of binary32 fused multiply-adds
+ *      over the bands in ascending order, the same for every frame wherever its tile starts.
+ *   4. Deltas.  j = -h .. h, w = delta_width, S2 = sum j^2, S4 = sum j^4:
+ *        D1[q][t] = sum_j (j / S2) c[q][t + j]
+ *        D2[q][t] = sum_j 2 (j^2 - S2 / w) / (S4 - S2^2 / w) c[q][t + j]
+ *      both on c (librosa.feature.delta(order = 2) is not the delta of the delta); at w = 9 the taps are j / 60 and
+ *      (3 j^2 - 20) / 462.  These are the interior coefficients of scipy.signal.savgol_coeffs(w, order, deriv = order).  The
+ *      formula holds at EVERY frame of the clip because the neighbours exist: librosa.feature.delta fits polynomials at a
+ *      batch's edges (mode = "interp"), this call has no edges.  Each value is a chain of binary64 fused multiply-adds, j
+ *      ascending, on the binary32 c, rounded once to binary32.
+ *   5. Output.  out_mode 0 ("mfcc"): [K][C][(1 + deltas) n_mfcc][F], rows 0 .. n_mfcc - 1 c, then D1, then D2: the memory of
+ *      np.concatenate([mfcc, delta, delta2], axis = -2).  out_mode 1 ("db"): [K][C][n_mels][F] = d; n_mfcc, lifter and the
+ *      delta fields are not read.  F = 0 writes nothing but valid.
+ * No atomics, one fixed order: two runs are bit-equal, and at top_db < 0 a clip is the slice of a longer one bit for bit.
+ * Not offered: DCT types 1 and 3, norm = None, one maximum over the channels, delta's edge modes. */
+typedef struct pdmp3_amd_mfcc_long_spec {
+  pdmp3_amd_mel_long_spec mel;  /* the log-mel of item 1 */
+  double top_db;                /* librosa's default is 80; negative: no clamp */
+  int n_mfcc;                   /* 1 .. min(n_mels, 128); librosa's default is 20 */
+  double lifter;                /* >= 0, finite; 0: none */
+  int deltas, delta_width;      /* 0, 1 or 2; odd, 3 .. 17 (librosa: 9), read when deltas > 0 */
+  int out_mode;                 /* 0 mfcc, 1 db */
+} pdmp3_amd_mfcc_long_spec;
+#define PDMP3_MFCC_LONG_MAX_WIDTH 17
+#define PDMP3_MFCC_LONG_MAX_CEPS 128
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1: whatever pdmp3_amd_mel_long_check refuses at
+ * out_mode 2, top_db NaN or +inf, an out_mode other than 0 and 1; at out_mode 0 also n_mfcc outside 1 .. min(n_mels, 128), a
+ * lifter that is negative or not finite, deltas outside 0 .. 2, with deltas > 0 a delta_width that is even or outside 3 .. 17;
+ * a channel's row of the output ((1 + deltas) n_mfcc F, or n_mels F) or of the stage (n_mels (F + 2 h)) beyond 2^31 - 1 floats. */
+int pdmp3_amd_mfcc_long_check(const pdmp3_amd_mfcc_long_spec* spec, long sr);
+/* T of item 3 as k_clip_mfcc_long reads it: [n_mfcc rounded up to 16][n_mels rounded up to 16] (*rows, *cols; may be NULL),
+ * zeros in the padding.  Returns the floats and writes min(that, cap); -1 on a bad argument (n_mels outside 1 .. 256, n_mfcc
+ * outside 1 .. min(n_mels, 128), a bad lifter), nothing written. */
+long long pdmp3_amd_mfcc_long_dct_table(int n_mels, int n_mfcc, double lifter, float* table, size_t cap, int* rows, int* cols);
+/* Item 4's taps in binary64: taps[j + h] for D1, taps[w + j + h] for D2.  Returns w = delta_width; -1, nothing written, on a
+ * width that is even or outside 3 .. 17 or where cap < 2 w.  taps NULL with cap 0: the count alone. */
+int pdmp3_amd_mfcc_long_delta_taps(int delta_width, double* taps, size_t cap);
+/* What the call launches, the function the call itself uses: *front and *back, the frames of the log-mel in front of frame 0
+ * and behind frame F - 1 (both h); *tile, the frames of a workgroup of k_clip_mfcc_long (64); *d_pitch and *c_pitch, the
+ * floats between two rows of its two LDS planes (80: the tile with the widest halo; 84); *lds_bytes = (mels16 d_pitch +
+ * ceps16 c_pitch) x 4, at most 124 928: every shape fits PDMP3_MEL_LDS_MAX at 64 frames, so there is one tile.  out_mode 1:
+ * no halo, *tile the 1024 elements of a workgroup of k_clip_db, no LDS.  Pointers may be NULL.  0, or -1 on a bad argument. */
+int pdmp3_amd_mfcc_long_plan(int n_mels, int n_mfcc, int deltas, int delta_width, int out_mode, int* front, int* back, int* tile,
+                             int* d_pitch, int* c_pitch, unsigned* lds_bytes);
+/* Row k receives channel c's [(1 + deltas) n_mfcc][F] (out_mode 1: [n_mels][F]) floats at dst + c * chan_stride.  The audio
+ * call for the clips widened to start - h hop and F + 2 h frames; k_clip_mel_long, unchanged, into a stage of the decoder;
+ * k_clip_db_max (top_db >= 0: a plane's threshold, behind the clip's log-mel in the stage); k_clip_mfcc_long or k_clip_db
+ * (csrc/mfcc_long.hip) write the rows.  T is made once per (n_mels, n_mfcc, lifter) and kept for the decoder's life.
+ * Everything else -- host destinations, the per-clip refusals in valid[k], rate 0 / channels 0, width, rolloff, the counts,
+ * n_clips = 0 and n_frames = 0, synchronous -- as pdmp3_amd_bulk_decode_clips_mel_long.  -1, nothing written, also where
+ * pdmp3_amd_mfcc_long_check says so. */
+int pdmp3_amd_bulk_decode_clips_mfcc_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips,
+                                          const pdmp3_amd_mfcc_long_spec* spec, long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -485,7 +485,7 @@ typedef struct pdmp3_audio_desc {
 /* The stream object's audio stages: device memory (hipMalloc, kept and grown on demand; call with nothing of the audio
  * path in flight).  which = 0: the clips' int16 PCM; 1: float rows of clips whose destination is host memory; 2: the
  * resampled signal the log-mel call reads (below); 3: what the tempogram call keeps between its kernels (log-mel, envelope,
- * tempogram), or the separation call its spectrum.  NULL on failure. */
+ * tempogram), the separation call its spectrum, or the long MFCC call its log-mel and thresholds.  NULL on failure. */
 void* pdmp3_hip_stream_audio_stage(pdmp3_hip_stream* hs, int which, size_t bytes);
 /* Uploads the launch's tables (descs, frames, tables: host memory) and runs k_clip_audio on the slot's HIP stream, behind
  * whatever the slot ran last (the last clip window's k_clip_pack); n_samples output samples per row, channels = 1 or 2.
@@ -683,6 +683,32 @@ typedef struct pdmp3_hpss_params {
 /* Uploads the descriptors -- host memory -- and runs k_clip_hpss on the slot's HIP stream, one launch per 32 768 clips.  The
  * tile, the pitch and lds_bytes must be csrc/hpss_core.h's (pdmp3_amd_hpss_plan's), and lds_bytes <= PDMP3_MEL_LDS_MAX.  Blocks until the rows are written. */
 int pdmp3_hip_clip_hpss(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_hpss_params* params);
+
+/* MFCC, deltas and dB mel of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_mfcc_long).  The
+ * kernels of mfcc_long.hip read what k_clip_mel_long wrote into audio stage 3 -- a descriptor's src: channel 0's
+ * [n_mels][n_stage] log10 mel, src_chan_stride floats between the channels, and behind the last channel's one float per
+ * channel, the plane's threshold (written by k_clip_db_max, read by the others; only with use_top); stage frame j is the
+ * clip's frame j - halo -- and write [(1 + deltas) n_mfcc][n_frames] floats per channel at dst (out_mode 1:
+ * [n_mels][n_frames]), frames innermost; lead is not read.  A workgroup of k_clip_mfcc_long, four waves, takes `tile` frames:
+ * its LDS is a plane [mels16][d_pitch] of dB values and a plane [ceps16][c_pitch] of cepstra (csrc/mfcc_long_core.h). */
+typedef struct pdmp3_mfcc_long_params {
+  int32_t n_mels, mels16;                   /* <= 256; rounded up to 16                                                  */
+  int32_t n_mfcc, ceps16;                   /* <= 128; rounded up to 16 (out_mode 1: 0, 0)                               */
+  int32_t n_frames, n_stage;                /* F; F + 2 halo: the frames of a row of the stage                           */
+  int32_t halo, deltas;                     /* (delta_width - 1) / 2 with deltas > 0, else 0; 0 .. 2                     */
+  int32_t tile, channels;                   /* 64                                                                        */
+  int32_t d_pitch, c_pitch;                 /* 80, 84                                                                    */
+  int32_t out_mode, use_top;                /* 0 mfcc, 1 db; 1: clamp at the plane's maximum - top_db                    */
+  float top_db;                             /* fl32(top_db), >= 0, with use_top                                          */
+  uint32_t lds_bytes;
+  double taps[2][17];                       /* [order - 1][j + halo], binary64                                           */
+} pdmp3_mfcc_long_params;
+/* Uploads the descriptors and the table T [ceps16][mels16] -- host memory; dct may be NULL at out_mode 1 -- and runs, on the
+ * slot's HIP stream and per 32 768 clips, k_clip_db_max (use_top) and then k_clip_mfcc_long or k_clip_db.  The tile, the
+ * pitches and lds_bytes must be csrc/mfcc_long_core.h's (pdmp3_amd_mfcc_long_plan's), lds_bytes <= PDMP3_MEL_LDS_MAX.
+ * Blocks until the rows are written. */
+int pdmp3_hip_clip_mfcc_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dct,
+                             const pdmp3_mfcc_long_params* params);
 
 /* The constant-Q transform of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_cqt).
  * k_clip_cqt (cqt.hip) reads the rows as k_clip_stft does (pdmp3_mel_desc; a frame's span is rows0 samples, its centre the

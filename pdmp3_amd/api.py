@@ -38,7 +38,9 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_tempogram_check", "pdmp3_amd_tempogram_window", "pdmp3_amd_tempogram_prior", "pdmp3_amd_tempogram_plan",
                 "pdmp3_amd_bulk_decode_clips_tempogram",
                 "pdmp3_amd_spectral_check", "pdmp3_amd_spectral_plan", "pdmp3_amd_bulk_decode_clips_spectral",
-                "pdmp3_amd_hpss_check", "pdmp3_amd_hpss_plan", "pdmp3_amd_bulk_decode_clips_hpss"]
+                "pdmp3_amd_hpss_check", "pdmp3_amd_hpss_plan", "pdmp3_amd_bulk_decode_clips_hpss",
+                "pdmp3_amd_mfcc_long_check", "pdmp3_amd_mfcc_long_dct_table", "pdmp3_amd_mfcc_long_delta_taps", "pdmp3_amd_mfcc_long_plan",
+                "pdmp3_amd_bulk_decode_clips_mfcc_long"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -232,6 +234,13 @@ def load_library():
         lib.pdmp3_amd_hpss_check.argtypes = [vp, C.c_long]
         lib.pdmp3_amd_hpss_plan.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_uint)]
         lib.pdmp3_amd_bulk_decode_clips_hpss.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_mfcc_long"):    # (librosa-style MFCC, deltas, dB mel: absent from older builds)
+        lib.pdmp3_amd_mfcc_long_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_mfcc_long_dct_table.argtypes = [C.c_int, C.c_int, C.c_double, vp, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        lib.pdmp3_amd_mfcc_long_dct_table.restype = ll
+        lib.pdmp3_amd_mfcc_long_delta_taps.argtypes = [C.c_int, vp, C.c_size_t]
+        lib.pdmp3_amd_mfcc_long_plan.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)] * 5 + [C.POINTER(C.c_uint)]
+        lib.pdmp3_amd_bulk_decode_clips_mfcc_long.argtypes = [vp, vp, C.c_int, vp, vp]
     _LIB = lib
     return lib
 
@@ -992,6 +1001,73 @@ def hpss_plan(kernel_harm=31, kernel_perc=31):
     return tuple(x.value for x in v) + (b.value,)
 
 
+class _MfccLongSpec(C.Structure):                  # include/pdmp3_bulk.h pdmp3_amd_mfcc_long_spec
+    _fields_ = [("mel", _MelLongSpec), ("top_db", C.c_double), ("n_mfcc", C.c_int), ("lifter", C.c_double), ("deltas", C.c_int),
+                ("delta_width", C.c_int), ("out_mode", C.c_int)]
+
+
+MFCC_LONG_MODES = {"mfcc": 0, "db": 1}
+
+
+def _mfcc_long_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, n_mfcc=20, lifter=0.0, top_db=80.0, amin=1e-10, deltas=0,
+                    delta_width=9, out_mode="mfcc", f_min=0.0, f_max=0.0, scale="slaney", norm="slaney", win_length=None, window=None, channels=1,
+                    width=0, rolloff=0.0):
+    """-> (spec, what its window points to).  top_db None: no clamp (a negative value to the library)"""
+    mel, keep = _mel_long_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, "log10", amin, win_length, window, channels,
+                               width, rolloff)
+    mode = MFCC_LONG_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)
+    if mode == 1:                                          # (the dB mode reads none of the cepstral fields)
+        n_mfcc, lifter, deltas, delta_width = 0, 0.0, 0, 0
+    elif int(n_mfcc) != n_mfcc or int(deltas) != deltas or int(delta_width) != delta_width:
+        raise ValueError("mfcc_long: n_mfcc, deltas and delta_width are integers")
+    if top_db is not None and float(top_db) < 0.0:
+        raise ValueError("mfcc_long: top_db is None or not negative")
+    top = -1.0 if top_db is None else float(top_db)
+    return _MfccLongSpec(mel, top, int(n_mfcc), float(lifter), int(deltas), int(delta_width), mode), keep
+
+
+def mfcc_long_check(sample_rate=22050, **kw):
+    """pdmp3_amd_mfcc_long_check -> True when pdmp3_amd_bulk_decode_clips_mfcc_long would accept these numbers
+    (decode_clips_mfcc_long's argument names) at sample_rate"""
+    try:
+        spec, keep = _mfcc_long_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_mfcc_long_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def mfcc_long_dct_table(n_mels=128, n_mfcc=20, lifter=0.0):
+    """pdmp3_amd_mfcc_long_dct_table -> float32 numpy [n_mfcc rounded up to 16, n_mels rounded up to 16]: the orthonormal
+    DCT-II with librosa's lifter folded in as k_clip_mfcc_long reads it, zeros in the padding"""
+    lib = load_library()
+    rows, cols = C.c_int(0), C.c_int(0)
+    if lib.pdmp3_amd_mfcc_long_dct_table(int(n_mels), int(n_mfcc), float(lifter), None, 0, C.byref(rows), C.byref(cols)) < 0:
+        raise ValueError("pdmp3_amd_mfcc_long_dct_table: bad argument")
+    t = np.full((rows.value, cols.value), np.nan, dtype=np.float32)
+    lib.pdmp3_amd_mfcc_long_dct_table(int(n_mels), int(n_mfcc), float(lifter), t.ctypes.data_as(C.c_void_p), t.size, None, None)
+    return t
+
+
+def mfcc_long_delta_taps(delta_width=9):
+    """pdmp3_amd_mfcc_long_delta_taps -> float64 numpy [2, delta_width]: the taps of the first and the second delta, j ascending"""
+    w = int(delta_width)
+    t = np.full((2, max(w, 1)), np.nan, dtype=np.float64)
+    if load_library().pdmp3_amd_mfcc_long_delta_taps(w, t.ctypes.data_as(C.c_void_p), t.size) != w:
+        raise ValueError("pdmp3_amd_mfcc_long_delta_taps: delta_width must be odd, 3 .. 17")
+    return t
+
+
+def mfcc_long_plan(n_mels=128, n_mfcc=20, deltas=0, delta_width=9, out_mode="mfcc"):
+    """pdmp3_amd_mfcc_long_plan -> (log-mel frames in front of frame 0, behind the last frame, frames of a workgroup of
+    k_clip_mfcc_long, the floats between two rows of its plane of dB values, of its plane of cepstra, its LDS bytes)"""
+    v = [C.c_int(0) for _ in range(5)]
+    b = C.c_uint(0)
+    m = MFCC_LONG_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)
+    if load_library().pdmp3_amd_mfcc_long_plan(int(n_mels), int(n_mfcc), int(deltas), int(delta_width), m, *[C.byref(x) for x in v], C.byref(b)) != 0:
+        raise ValueError("pdmp3_amd_mfcc_long_plan: bad argument")
+    return tuple(x.value for x in v) + (b.value,)
+
+
 class StreamIndex:
     """include/pdmp3_bulk.h pdmp3_amd_index: what a stream's frames are and where their PCM lies in the whole-stream output,
     built once, for BulkDecoder.decode_range / decode_clips.  .frames (PDMP3_BULK_REPLAY when the scan ends in a ring replay),
@@ -1498,6 +1574,29 @@ class BulkDecoder:
         spec = lambda: _hpss_spec(f, sample_rate, n_fft, hop, kernel_size, power, margin, m, channels, win_length, window, width, rolloff)
         return self._clips_call("hpss", clips, (2, nb, f, 2) if m == 2 else (2, nb, f), spec, channels, out, complex_ok=m == 2,
                                 refused=(ValueError, OverflowError, TypeError))
+
+    def decode_clips_mfcc_long(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, n_mfcc=20, lifter=0.0, top_db=80.0,
+                               amin=1e-10, deltas=0, delta_width=9, out_mode="mfcc", out=None, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney",
+                               win_length=None, window=None, channels=1, width=0, rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_mfcc_long: clips as decode_clips_mel_long takes them -> (out, valid).  out_mode "mfcc":
+        float32 [K, C, (1 + deltas) n_mfcc, n_frames] -- librosa.feature.mfcc (orthonormal DCT-II of
+        power_to_db(melspectrogram, ref=1.0, amin, top_db), lifter) of frame f centred on sample start + f hop, with deltas = 1 or 2
+        librosa.feature.delta(width=delta_width) of order 1 and 2 stacked under it, as np.concatenate([mfcc, delta, delta2],
+        axis=-2); the deltas read the stream's own frames in front of and behind the clip (zeros outside the stream), so the
+        interior formula holds at every frame and there is no mode="interp" edge.  "db": [K, C, n_mels, n_frames], the dB mel
+        itself.  top_db clamps at the largest value of the clip's own frames, per clip and channel (librosa takes one maximum
+        over a stereo clip's channels); None: no clamp.  n_fft 2048 or 4096; the filterbank's and the window's arguments, valid,
+        out, the exceptions: as decode_clips_mel_long."""
+        f, nm, nc, nd = int(n_frames), int(n_mels), int(n_mfcc), int(deltas)
+        m = MFCC_LONG_MODES.get(out_mode) if isinstance(out_mode, str) else out_mode
+        if m not in (0, 1):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mfcc_long: out_mode is \"mfcc\" or \"db\"")
+        spec = lambda: _mfcc_long_spec(f, sample_rate, n_fft, hop, nm, n_mfcc, lifter, top_db, amin, deltas, delta_width, m, f_min, f_max, scale, norm,
+                                       win_length, window, channels, width, rolloff)
+        inner = (nm, f) if m == 1 else ((1 + nd) * nc, f)
+        if nm < 1 or (m == 0 and (nd not in (0, 1, 2) or nc < 1)):        # (no shape to check a destination against)
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_mfcc_long: bad n_mels, n_mfcc or deltas")
+        return self._clips_call("mfcc_long", clips, inner, spec, channels, out, refused=(ValueError, KeyError, OverflowError, TypeError))
 
     def decode_clips_fbank(self, clips, n_frames, sample_rate=16000, frame_length=25.0, frame_shift=10.0, num_mel_bins=23, win_length=None,
                            hop=None, round_to_power_of_two=True, remove_dc_offset=True, preemphasis_coefficient=0.97, window_type="povey",

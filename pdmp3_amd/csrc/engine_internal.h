@@ -194,5 +194,8 @@ hipError_t pdmp3_launch_clip_spectral(hipStream_t s, const pdmp3_mel_desc* descs
                                       const pdmp3_spectral_params* params);
 // ---- hpss.hip ----
 hipError_t pdmp3_launch_clip_hpss(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_hpss_params* params);
+// ---- mfcc_long.hip ----
+hipError_t pdmp3_launch_clip_mfcc_long(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const float* dct,
+                                       const pdmp3_mfcc_long_params* params);
 
 #endif

@@ -14,6 +14,7 @@
 #include "pitch_core.h"
 #include "tempogram_core.h"
 #include "hpss_core.h"
+#include "mfcc_long_core.h"
 
 using namespace pdmp3;
 
@@ -865,6 +866,35 @@ extern "C" int pdmp3_hip_clip_hpss(pdmp3_hip_stream* hs, int slot, const pdmp3_m
   // descriptors alone: the kernel reads no table
   return clip_run(hs, slot, "pdmp3_hip_clip_hpss", descs, n_clips, P.n_frames, {{ClipPart::kScratch, nullptr, 0}},
                   [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const*) { return pdmp3_launch_clip_hpss(hs->s[slot].stream, dk, nk, &P); });
+}
+// ---- MFCC, deltas and dB mel at n_fft 2048 and 4096 (mfcc_long.hip) ----
+extern "C" int pdmp3_hip_clip_mfcc_long(pdmp3_hip_stream* hs, int slot, const pdmp3_mel_desc* descs, int n_clips, const float* dct,
+                                        const pdmp3_mfcc_long_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc_long: bad argument", hipSuccess);
+  const pdmp3_mfcc_long_params& P = *params;
+  // what the kernels' indexing relies on: the bands, the stage's frames, rows inside 31 bits
+  if (P.n_mels < 1 || P.n_mels > 256 || P.mels16 != ((P.n_mels + 15) & ~15) || P.n_frames < 0 || (P.channels != 1 && P.channels != 2) ||
+      (P.out_mode != 0 && P.out_mode != 1) || (P.use_top != 0 && P.use_top != 1) || (P.use_top && !(P.top_db >= 0.0f)) ||
+      P.halo < 0 || P.halo > pdmp3::kMfccLongMaxHalo || P.n_stage != (long long)P.n_frames + 2 * P.halo ||
+      (long long)P.n_mels * P.n_stage > 0x7fffffffLL)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc_long: bad parameters", hipSuccess);
+  size_t dct_bytes = 0;
+  if (P.out_mode == 1) {
+    if (P.halo != 0) return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc_long: the dB mode has no halo", hipSuccess);
+  } else {
+    if ((n_clips && !dct) || P.n_mfcc < 1 || P.n_mfcc > P.n_mels || P.n_mfcc > 128 || P.ceps16 != ((P.n_mfcc + 15) & ~15) || P.deltas < 0 ||
+        P.deltas > 2 || (P.deltas == 0) != (P.halo == 0) || (long long)(1 + P.deltas) * P.n_mfcc * P.n_frames > 0x7fffffffLL)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc_long: bad parameters", hipSuccess);
+    if (P.tile != pdmp3::kMfccLongFrames || P.d_pitch != pdmp3::kMfccLongDPitch || P.c_pitch != pdmp3::kMfccLongCPitch ||
+        P.lds_bytes != pdmp3::mfcc_long_lds_floats(P.mels16, P.ceps16) * sizeof(float) || P.lds_bytes > PDMP3_MEL_LDS_MAX)
+      return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_mfcc_long: not the plan's tile, pitches and LDS", hipSuccess);
+    dct_bytes = (size_t)P.ceps16 * (size_t)P.mels16 * sizeof(float);
+  }
+  return clip_run(hs, slot, "pdmp3_hip_clip_mfcc_long", descs, n_clips, P.n_frames, {{ClipPart::kUpload, dct, dct_bytes}},
+                  [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_mfcc_long(hs->s[slot].stream, dk, nk, as_floats(part[0]), &P);
+                  });
 }
 // ---- Kaldi-style filterbank features (fbank.hip) ----
 extern "C" int pdmp3_hip_clip_fbank(pdmp3_hip_stream* hs, int slot, const pdmp3_fbank_desc* descs, int n_clips, const float* dft, const float* fbt,

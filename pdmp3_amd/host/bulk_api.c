@@ -39,6 +39,7 @@ void pdmp3_amd_bulk_delete(struct bulk* b) {
   while (b->mel_tabs) { mel_tab* t = b->mel_tabs; b->mel_tabs = t->next; free(t->t); free(t); }
   while (b->fbank_tabs) { fbank_tab* t = b->fbank_tabs; b->fbank_tabs = t->next; free(t->t); free(t); }
   while (b->mfcc_tabs) { mfcc_tab* t = b->mfcc_tabs; b->mfcc_tabs = t->next; free(t->t); free(t); }
+  while (b->mfcc_long_tabs) { mfcc_long_tab* t = b->mfcc_long_tabs; b->mfcc_long_tabs = t->next; free(t->t); free(t); }
   while (b->stft_tabs) { stft_tab* t = b->stft_tabs; b->stft_tabs = t->next; free(t->t); free(t->window); free(t); }
   while (b->cqt_tabs) { cqt_tab* t = b->cqt_tabs; b->cqt_tabs = t->next; free(t->t); free(t); }
   free(b->stft_long_tabs[0]); free(b->stft_long_tabs[1]);

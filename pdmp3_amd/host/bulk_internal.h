@@ -82,6 +82,8 @@ typedef struct fbank_tab {
 /* Kaldi-style MFCC features (clip_mfcc.c): a folded DCT table as k_clip_mfcc reads it ([mels16][ceps16]) per (n_mels,
  * num_ceps, cepstral_lifter, htk_compat, use_energy) */
 typedef struct mfcc_tab { int n_mels, n_ceps, htk, energy; double lifter; float* t; struct mfcc_tab* next; } mfcc_tab;
+/* librosa-style MFCC (clip_mfcc_long.c): a DCT table [ceps16][mels16] per (n_mels, n_mfcc, lifter) */
+typedef struct mfcc_long_tab { int n_mels, n_mfcc; double lifter; float* t; struct mfcc_long_tab* next; } mfcc_long_tab;
 /* the short-time Fourier transform (clip_stft.c): a folded table per (N, Nw, normalized, the window's values: a copy of the
  * caller's, NULL for the Hann window); a short list, the most recently used first */
 typedef struct stft_tab { int n_fft, win, normalized; float* window; float* t; struct stft_tab* next; } stft_tab;
@@ -195,6 +197,7 @@ struct bulk {
   struct mel_tab* mel_tabs;           /* log-mel features: the DFT tables and filterbanks made so far */
   struct fbank_tab* fbank_tabs;       /* Kaldi-style filterbank features: the folded tables and filterbanks made so far */
   struct mfcc_tab* mfcc_tabs;         /* Kaldi-style MFCC features: the folded DCT tables made so far */
+  struct mfcc_long_tab* mfcc_long_tabs; /* librosa-style MFCC features: the DCT tables made so far */
   struct stft_tab* stft_tabs;         /* the short-time Fourier transform: the last PDMP3_STFT_TABLES folded tables */
   struct cqt_tab* cqt_tabs;           /* the constant-Q transform: the last PDMP3_CQT_TABLES tables */
   float* stft_long_tabs[2];           /* ... at n_fft 2048 and 4096: a call's block of tables, made once; its wt is filled per call */
@@ -429,6 +432,11 @@ HOST_LOCAL int spectral_plan(const pdmp3_amd_spectral_spec* s, long sr, pdmp3_sp
  * to the call (0, or -1 where the check refuses the spec) */
 HOST_LOCAL void hpss_stft_spec(const pdmp3_amd_hpss_spec* s, pdmp3_amd_stft_spec* t);
 HOST_LOCAL int hpss_plan(const pdmp3_amd_hpss_spec* s, long sr, pdmp3_hpss_params* p, int* front, int* back);
+/* clip_mfcc_long.c: the check with the geometry of the kernels of mfcc_long.hip for the spec at sr, the taps and the frames a
+ * clip is widened by; n_frames, n_stage and channels are left to the call (0, or -1 where the check refuses the spec); the
+ * decoder's DCT table of (n_mels, n_mfcc, lifter) (NULL: no memory) */
+HOST_LOCAL int mfcc_long_plan(const pdmp3_amd_mfcc_long_spec* s, long sr, pdmp3_mfcc_long_params* p, int* front, int* back);
+HOST_LOCAL const float* mfcc_long_table(struct bulk* b, int n_mels, int n_mfcc, double lifter);
 /* cpus.c */
 HOST_LOCAL int gpu_local_cpus(pdmp3_hip_ctx* ctx, cpu_set_t* out);
 HOST_LOCAL void bind_thread(pthread_t t, const cpu_set_t* set);

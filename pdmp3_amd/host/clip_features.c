@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss; DESIGN.md sections 9-23).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss, _mfcc_long; DESIGN.md sections 9-24).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -589,6 +589,56 @@ int pdmp3_amd_bulk_decode_clips_hpss(struct bulk* b, const pdmp3_amd_audio_clip*
   rc = cc.rc;
 out:
   free(sd); free(hd);
+  return course_finish(&cc, rc);
+}
+
+/* ---- MFCC, deltas and dB mel of clips at n_fft 2048 and 4096 ---- */
+/* The log-mel call's course on rows widened by the frames the delta stencil reaches, its kernel writing into audio stage 3
+ * instead of the destination; behind a clip's log-mel there lies one float per channel, the plane's threshold. */
+int pdmp3_amd_bulk_decode_clips_mfcc_long(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips,
+                                          const pdmp3_amd_mfcc_long_spec* spec, long long* valid) {
+  clip_course cc;
+  if (!spec) return -1;
+  const pdmp3_amd_mel_spec* m = &spec->mel.mel;
+  if (course_begin(&cc, b, clips, n_clips, valid, m->n_frames, m->channels, m->rate, m->width, m->rolloff) != 0) return -1;
+  pdmp3_mfcc_long_params Q;
+  pdmp3_mel_long_params P;
+  memset(&P, 0, sizeof P);
+  if (mfcc_long_plan(spec, cc.sr, &Q, &cc.front, &cc.back) != 0) return -1;   /* (the check is its first step) */
+  if (mel_long_plan(m->n_fft, m->hop, m->n_mels, &P) != 0) return -1;
+  const int rows = spec->out_mode == 1 ? m->n_mels : (1 + spec->deltas) * spec->n_mfcc;
+  if (course_rows(&cc, m->n_fft, m->hop, rows, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const long long F = cc.F, Fs = F + cc.front + cc.back;
+  const size_t mel_floats = (size_t)m->n_mels * (size_t)Fs;                    /* of a channel in the stage */
+  const size_t clip_floats = ((size_t)cc.C * mel_floats + (size_t)cc.C + 3) & ~(size_t)3;
+  pdmp3_amd_mel_long_spec ms = spec->mel;
+  ms.mel.out_mode = 2;
+  pdmp3_amd_stft_spec frame;
+  mel_long_stft_spec(&ms, &frame);
+  const float* table = stft_long_tables(b, &frame);
+  const float* operand = mel_long_operand(b, cc.sr, m);
+  const float* dct = spec->out_mode == 0 ? mfcc_long_table(b, m->n_mels, spec->n_mfcc, spec->lifter) : NULL;
+  pdmp3_mel_desc* md = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *md);
+  pdmp3_mel_desc* qd = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *qd);
+  int rc = -1;
+  if (!table || !operand || (spec->out_mode == 0 && !dct) || !md || !qd || course_signal(&cc) != 0) goto out;
+  float* const stage = (float*)pdmp3_hip_stream_audio_stage(b->hs, 3, (size_t)cc.nd * clip_floats * sizeof(float));
+  if (!stage) goto out;
+  for (int i = 0; i < cc.nd; i++) {
+    md[i] = cc.ds[i];
+    md[i].dst = (uint64_t)(uintptr_t)(stage + (size_t)i * clip_floats);
+    md[i].dst_chan_stride = mel_floats;
+    qd[i].src = md[i].dst; qd[i].src_chan_stride = mel_floats;
+    qd[i].dst = cc.ds[i].dst; qd[i].dst_chan_stride = cc.ds[i].dst_chan_stride;
+  }
+  P.n_in = cc.T; P.n_frames = (int32_t)Fs; P.channels = cc.C; P.out_mode = 2; P.floor = (float)m->floor;
+  if (course_launched(pdmp3_hip_clip_mel_long(b->hs, CLIP_SLOT, md, cc.nd, table, operand, &P)) != 0) goto out;
+  Q.n_frames = (int32_t)F; Q.n_stage = (int32_t)Fs; Q.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_mfcc_long(b->hs, CLIP_SLOT, qd, cc.nd, dct, &Q)) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(md); free(qd);
   return course_finish(&cc, rc);
 }
 

@@ -17,7 +17,7 @@
  *   bulk_api.c      whole-stream decoder: pdmp3_amd_bulk_* entry points (new / delete / decode / wait / parse hooks)
  *   clip.c          stream indices, the halo rule of a frame range, clips (pdmp3_amd_index_*, pdmp3_amd_bulk_decode_clips)
  *   clip_features.c clips as float batches and the feature calls on them (pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank,
- *                   _mfcc, _stft, _stft_long, _cqt, _chroma, _loudness, _spectral, _hpss): their one course and the decoder's tables; the checks, plans and
+ *                   _mfcc, _stft, _stft_long, _cqt, _chroma, _loudness, _spectral, _hpss, _mfcc_long): their one course and the decoder's tables; the checks, plans and
  *                   tables' contents are the clip_*.c files below and their like (clip_mel.c, clip_fbank.c, clip_mfcc.c, clip_stft.c,
  *                   clip_stft_long.c, clip_mel_long.c)
  *   clip_audio.c    clips as float batches: the input span of a clip, the filter table of a pair of sampling frequencies
@@ -29,6 +29,7 @@
  *   clip_tempogram.c onset strength, tempogram and tempo of clips: the check, the window, the prior, the launches' geometry
  *   clip_spectral.c spectral descriptors of clips (rms, zcr, centroid, bandwidth, roll-off, flatness): the check, the kernel's plan
  *   clip_hpss.c     harmonic-percussive separation of clips: the check, the widening, the kernel's plan
+ *   clip_mfcc_long.c librosa-style MFCC, deltas and dB mel of clips: the check, the DCT table, the delta taps, the kernel's plan
  *   corpus.c        a corpus of files dealt over the GPUs of a node
  *   wav_cli.c       pdmp3() -- the reference's CLI contract -- and the .raw / .wav sinks
  *

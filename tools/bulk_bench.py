@@ -839,6 +839,97 @@ def clips_hpss(args, api):
     print(json.dumps(res))
 
 
+def clips_mfcc_long(args, api):
+    """--mfcc-long: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as librosa's MFCC with both deltas
+    [60, 1292] (n_fft 2048, hop 512, 128 bands, 20 cepstra, top_db 80, delta width 9) in device memory, three ways, run after run
+    in turn: (a) pdmp3_amd_bulk_decode_clips_mel_long (log10) of the widened clips alone; (b) pdmp3_amd_bulk_decode_clips_mfcc_long;
+    (c) (a) followed by the same chain in torch -- amax, clamp, matmul, conv1d.  (b) is compared once with (c) (largest
+    difference, printed, not asserted: the tests check (b) against the definition).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, F, rate, n_fft, hop, nm, nc, w, top = args.clips, args.clip_frames, 22050, 2048, 512, 128, 20, 9, 80.0
+    h = (w - 1) // 2
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
+    Fw = Fm + 2 * h
+    dev = "cuda:0"
+    clips, wide = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2 + h * hop)
+        clips.append((files[i], ixs[i], start))
+        wide.append((files[i], ixs[i], start - h * hop))
+    out_l = torch.zeros((K, 1, nm, Fw), dtype=torch.float32, device=dev)
+    out_b = torch.zeros((K, 1, 3 * nc, Fm), dtype=torch.float32, device=dev)
+    out_c = torch.zeros((K, 1, 3 * nc, Fm), dtype=torch.float32, device=dev)
+    table = torch.from_numpy(api.mfcc_long_dct_table(nm, nc, 0.0)[:nc, :nm].copy()).to(dev)
+    taps = torch.from_numpy(api.mfcc_long_delta_taps(w).astype(np.float32)).to(dev).reshape(2, 1, w)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+
+    def mel_route():
+        dec.decode_clips_mel_long(wide, Fw, rate, n_fft, hop, nm, mode="log10", floor=1e-10, out=out_l)
+
+    def mfcc_route():
+        dec.decode_clips_mfcc_long(clips, Fm, rate, n_fft, hop, nm, nc, 0.0, top, 1e-10, 2, w, "mfcc", out=out_b)
+
+    def torch_route():
+        dec.decode_clips_mel_long(wide, Fw, rate, n_fft, hop, nm, mode="log10", floor=1e-10, out=out_l)
+        d = out_l[:, 0] * 10.0                                                            # [K, nm, Fw]
+        d = torch.maximum(d, d[:, :, h:h + Fm].amax(dim=(1, 2), keepdim=True) - top)
+        c = torch.matmul(table, d)                                                        # [K, nc, Fw]
+        dl = torch.nn.functional.conv1d(c.reshape(K * nc, 1, Fw), taps).reshape(K, nc, 2, Fm)
+        out_c[:, 0, :nc] = c[:, :, h:h + Fm]
+        out_c[:, 0, nc:2 * nc] = dl[:, :, 0]
+        out_c[:, 0, 2 * nc:] = dl[:, :, 1]
+        torch.cuda.synchronize()
+
+    routes = [("mel_long log10 clips", mel_route), ("mfcc_long clips", mfcc_route), ("mel_long log10 clips + torch amax, clamp, matmul, conv1d", torch_route)]
+    times = {name: [] for name, _ in routes}
+    diff = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % 3:] + routes[:r % 3]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            diff = float((out_c - out_b).abs().max())
+    dec.close()
+    res = {"workload": "%d clips of %d frames' length as MFCC, delta and delta-delta [%d, %d] at %d Hz mono (n_fft %d, hop %d, %d bands, %d cepstra, "
+                       "top_db %g, width %d): %s" % (K, F, 3 * nc, Fm, rate, n_fft, hop, nm, nc, top, w,
+                                                     "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
+           "stage_bytes": K * nm * Fw * 4, "result_bytes": K * 3 * nc * Fm * 4, "largest_difference_of_the_torch_route_from_mfcc_long": diff,
+           "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = max(max(ts) - min(ts) for ts in times.values())
+    res["mfcc_long_minus_mel_long_ms"] = round((med["mfcc_long clips"] - med["mel_long log10 clips"]) * 1e3, 3)
+    res["torch_route_minus_mel_long_ms"] = round((med[routes[2][0]] - med["mel_long log10 clips"]) * 1e3, 3)
+    res["mfcc_long_over_mel_long"] = round(med["mfcc_long clips"] / med["mel_long log10 clips"], 4)
+    res["largest_spread_ms"] = round(spread * 1e3, 3)
+    res["mfcc_long_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(med[routes[2][0]] - med["mfcc_long clips"] > spread)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def clips_cqt(args, api):
     """--cqt: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono as the magnitudes of 84 constant-Q bins
     (C1, 12 an octave, norm 1, scale 1) x 1292 frames (hop 512) in device memory, three ways, run after run in turn: (a)
@@ -1611,6 +1702,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as harmonic and percussive soft masks [2, 1025, 1292] at 22 050 Hz mono, "
                          "n_fft 2048, hop 512, kernels 31 / 31, power 2 (pdmp3_amd_bulk_decode_clips_hpss) against the audio call alone, "
                          "pdmp3_amd_bulk_decode_clips_stft_long's magnitudes alone and those followed by the same algorithm in torch (see clips_hpss())")
+    ap.add_argument("--mfcc-long", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) as librosa's MFCC with delta and delta-delta [60, 1292] at 22 050 Hz mono, "
+                         "n_fft 2048, hop 512, 128 bands, top_db 80 (pdmp3_amd_bulk_decode_clips_mfcc_long) against "
+                         "pdmp3_amd_bulk_decode_clips_mel_long alone and that call followed by the same chain in torch (see clips_mfcc_long())")
     ap.add_argument("--fbank", action="store_true",
                     help="--clips: the clips as Kaldi-style filterbank features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_fbank) against "
                          "the audio call for the same spans and against that call followed by torch kernels (see clips_fbank())")
@@ -1618,7 +1713,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral or args.hpss:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral or args.hpss or args.mfcc_long:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1640,6 +1735,8 @@ def main():
             return clips_spectral(args, api)
         if args.hpss:
             return clips_hpss(args, api)
+        if args.mfcc_long:
+            return clips_mfcc_long(args, api)
         if args.stft or args.stft_long:
             return clips_stft(args, api, long=args.stft_long)
         if args.mfcc:
