@@ -3,6 +3,7 @@ configurations of fuzz_gpu.random_cfg with fixed seeds (MPEG-1 and LSF), streams
 rule that look far back (granule 1 copying scalefactors that granule 0, a short block, did not
 write -- non-strict streams, whose scfsi the packer draws at random; granules coded empty at low bit rates, H6), MPEG-1
 streams with bit flips whose index the one-thread scan builds, and a stream the scan calls a ring replay."""
+import functools
 import random
 
 from fuzz_gpu import random_cfg
@@ -94,3 +95,14 @@ def mixed_streams(frames):
               packer.generate(n_frames=k, seed=69, version=2, sfreq=1, mode=3, bitrate_index=6, iso_strict=True),
               packer.generate(n_frames=k, seed=70, version=1, sfreq=1, mode=0, bitrate_index=9, iso_strict=True)]
     return [("mixed/mono-stereo", mixed_mode, 0), ("mixed/mpeg1-lsf", b"".join(vparts), ISO_LSF)]
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_streams():
+    """(name, mp3, iso): the 18 streams of the clip tests on the GPU -- every family above and one of the C3 configuration (320 kbps
+    joint stereo, 9600 frames: longer than the decoder's 8192-frame window)"""
+    s = random_streams(range(1, 9), (200, 420))
+    s += scfsi_streams(400) + h6_streams(400)
+    s += corrupted_streams(range(3), 360) + mixed_streams(400)
+    s.append(("c3-config", packer.generate(n_frames=9600, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14), 0))
+    return s

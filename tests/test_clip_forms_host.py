@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import clip_fbank_ref as fref
+import clip_forms_cases as cases
 import clip_mel_ref as mref
 import clip_mfcc_ref as cref
 import clip_stft_ref as sref
@@ -24,10 +25,6 @@ import test_clip_fbank_host as tfh
 import test_clip_mel_host as tmh
 import test_clip_mfcc_host as tch
 import test_clip_stft_host as tsh
-import test_gpu_clip_fbank as tgf
-import test_gpu_clip_mel as tgm
-import test_gpu_clip_mfcc as tgc
-import test_gpu_clip_stft as tgs
 
 
 def _fb_geometry(p):
@@ -59,10 +56,10 @@ def stft_classes(p):
 
 # what the suite ran on the device before the EDGES tables: the cases of the four modules' comparisons with the definition
 DEVICE = {
-    "mel": [p for p, _, _ in tgm.CASES.values()],
-    "fbank": [p for p, _, _ in tgf.CASES.values()] + [dict(tgf.P16, **v) for v in tgf.VARIANTS.values()],
-    "mfcc": [p for p, _, _, _ in tgc.CASES.values()],
-    "stft": [p for p, _, _ in tgs.CASES.values()],
+    "mel": [p for p, _, _ in cases.MEL_CASES.values()],
+    "fbank": [p for p, _, _ in cases.FBANK_CASES.values()] + [dict(cases.FBANK_P16, **v) for v in cases.FBANK_VARIANTS.values()],
+    "mfcc": [p for p, _, _, _ in cases.MFCC_CASES.values()],
+    "stft": [p for p, _, _ in cases.STFT_CASES.values()],
 }
 CALLS = {"mel": (mel_classes, mref), "fbank": (fbank_classes, fref), "mfcc": (mfcc_classes, cref), "stft": (stft_classes, sref)}
 

@@ -11,108 +11,19 @@ the error bound of a length-T_j binary32 dot product with once-rounded coefficie
 one coefficient rounding, one more for second-order terms; x is exact).  It holds for any summation order, with or without FMA,
 and is 0 on digital silence.  Destinations are filled with a sentinel first: nothing outside [k, :, :T] may change.
 
-Streams: those of test_gpu_clips.py (mono runs inside stereo, MPEG-1 and LSF in one stream, the 9600-frame C3 configuration
+Streams (tests/clip_gpu.py): those of test_gpu_clips.py (mono runs inside stereo, MPEG-1 and LSF in one stream, the 9600-frame C3 configuration
 among them) plus one each at 48 and 32 kHz and LSF ones at 22.05, 16 and 8 kHz."""
-import functools
-
 import numpy as np
 import pytest
 
 import clip_audio_ref as ref
+import clip_gpu as cg
 import clip_streams
-import test_gpu_clips as tgc
+from clip_gpu import SENT
+from clip_gpu_calls import audio_check as _check, audio_run as _run
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT = np.float32(-1234.5)
-GUARD = 24
-
-
-@functools.lru_cache(maxsize=None)
-def _streams():
-    from pdmp3_amd.packer import packer
-    s = {name: mp3 for name, mp3, _ in tgc._streams()}
-    s["48k"] = packer.generate(n_frames=300, seed=481, sfreq=1, mode=1, mode_ext=2, bitrate_index=10, block_pct=(40, 20, 20, 20))
-    s["32k"] = packer.generate(n_frames=300, seed=321, sfreq=2, mode=0, bitrate_index=9, block_pct=(40, 20, 20, 20))
-    s["44k-mono"] = packer.generate(n_frames=300, seed=441, sfreq=0, mode=3, bitrate_index=7)
-    s["22k"] = packer.generate(n_frames=400, seed=221, version=1, sfreq=0, mode=1, mode_ext=2, bitrate_index=8, iso_strict=True)
-    s["16k-mono"] = packer.generate(n_frames=400, seed=161, version=1, sfreq=2, mode=3, bitrate_index=6, iso_strict=True)
-    s["8k"] = packer.generate(n_frames=400, seed=81, version=2, sfreq=2, mode=0, bitrate_index=6, iso_strict=True)
-    return s
-
-
-@functools.lru_cache(maxsize=None)
-def _ref(name):
-    """(index, the stream on its time line as int64 [Cs, N]) from the whole-stream decode"""
-    from pdmp3_amd import api
-    mp3 = _streams()[name]
-    ix = api.StreamIndex(mp3, ISO_LSF)
-    b = api.BulkDecoder(threads=2)
-    try:
-        b.set_quirks(ISO_LSF)
-        whole = b.decode(mp3)
-    finally:
-        b.close()
-    assert whole.nbytes == ix.pcm_offsets[-1]
-    if not ix.one_format:
-        return ix, None
-    return ix, ref.timeline(whole, ix.pcm_offsets, ix.frame_samples, ix.channels == 2)
-
-
-def _decoder():
-    from pdmp3_amd import api
-    dec = api.BulkDecoder(threads=2)
-    dec.set_quirks(ISO_LSF)
-    return dec
-
-
-def _destination(kind, k, c, t):
-    """a sentinel-filled [k, c, t + GUARD] buffer and its [:, :, :t] view (rows and channels strided)"""
-    if kind == "device":
-        import torch
-        big = torch.full((k, c, t + GUARD), float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-    else:
-        big = np.full((k, c, t + GUARD), SENT, dtype=np.float32)
-    return big, big[:, :, :t]
-
-
-def _host(big):
-    if hasattr(big, "cpu"):
-        import torch
-        torch.cuda.synchronize()
-        return big.cpu().numpy()
-    return big
-
-
-def _run(dec, kind, clips, t, rate=0, channels=0, width=0, rolloff=0.0, c_out=None):
-    """clips: (stream name, start) -> (host copy of the whole sentinel buffer, valid)"""
-    c = c_out or channels
-    big, view = _destination(kind, len(clips), c, t)
-    out, valid = dec.decode_clips_audio([(_streams()[n], _ref(n)[0], s) for n, s in clips], t, rate, channels, width, rolloff, out=view)
-    assert out is view
-    host = _host(big)
-    assert (host[:, :, t:] == SENT).all(), "written behind a row's samples"
-    return host[:, :, :t], valid
-
-
-def _check(name, start, got, valid, t, rate, channels, width=6, rolloff=0.99):
-    """one row against the definition; -> worst error / bound"""
-    ix, lr = _ref(name)
-    rate = rate or ix.rate
-    x = ref.channels64(lr, ix.channels, channels)
-    j_all = ref.out_length(ix.samples, ix.rate, rate)
-    assert valid == min(max(j_all - start, 0), t), (name, start, valid)
-    assert (got[:, valid:] == 0).all(), (name, start)
-    y64, bound = ref.resample64(x, ix.rate, rate, width, rolloff, start, t)
-    err = np.abs(got.astype(np.float64) - y64)
-    if rate == ix.rate:
-        assert np.array_equal(got.astype(np.float64), y64), "%s at %d: not the whole-stream decode bit for bit" % (name, start)
-        return 0.0
-    assert (err <= bound).all(), "%s at %d -> %d Hz: error beyond the bound by %g at %s" % (
-        name, start, rate, float((err - bound).max()), np.unravel_index(np.argmax(err - bound), err.shape))
-    nz = bound > 0
-    return float((err[nz] / bound[nz]).max(initial=0.0))
 
 
 @pytest.mark.parametrize("kind", ["device", "numpy"])
@@ -120,17 +31,17 @@ def test_own_rate_is_the_whole_stream_decode_bit_for_bit(kind):
     """C = Cs (channels = 0), rate = 0: clips at sample 0, across the stream's end, wholly behind it, at starts that are no
     multiples of the frame length; mono frames inside a stereo stream come out doubled"""
     t = 30000
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         for names in (["mixed/mono-stereo", "48k", "32k", "22k", "8k", "scfsi/joint"], ["44k-mono", "16k-mono"]):
             clips = []
             for n in names:
-                ix, _ = _ref(n)
+                ix, _ = cg.ref(n)
                 clips += [(n, 0), (n, ix.samples - t // 3), (n, ix.samples + 17), (n, 1152 * 5 + 331), (n, ix.samples // 2 + 1)]
-            got, valid = _run(dec, kind, clips, t, c_out=_ref(names[0])[0].channels)
+            got, valid = _run(dec, kind, clips, t, c_out=cg.ref(names[0])[0].channels)
             for i, (n, s) in enumerate(clips):
-                _check(n, s, got[i], int(valid[i]), t, 0, _ref(n)[0].channels)
-        ix, lr = _ref("mixed/mono-stereo")
+                _check(n, s, got[i], int(valid[i]), t, 0, cg.ref(n)[0].channels)
+        ix, lr = cg.ref("mixed/mono-stereo")
         mono_frames = np.flatnonzero(np.diff(ix.pcm_offsets) == 2304)
         assert mono_frames.size and (lr[0] != lr[1]).any()        # (the stream does mix mono frames into stereo)
     finally:
@@ -139,7 +50,7 @@ def test_own_rate_is_the_whole_stream_decode_bit_for_bit(kind):
 
 def test_a_clip_longer_than_a_window():
     """8400 frames of the C3-configuration stream from a start inside a frame: a call of its own, device memory"""
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         t = 8400 * 1152
         start = 1000 * 1152 + 37
@@ -153,14 +64,14 @@ def test_a_clip_longer_than_a_window():
 @pytest.mark.parametrize("kind", ["device", "numpy"])
 def test_downmix_and_doubling_at_the_own_rate_are_exact(kind):
     t = 20000
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         clips = [("mixed/mono-stereo", 1152 * 60 + 5), ("48k", 7), ("22k", 576 * 398), ("44k-mono", 100), ("16k-mono", 0), ("8k", 576 * 400 - 1)]
         for channels in (1, 2):
             got, valid = _run(dec, kind, clips, t, 0, channels)
             for i, (n, s) in enumerate(clips):
                 _check(n, s, got[i], int(valid[i]), t, 0, channels)
-        ix, lr = _ref("mixed/mono-stereo")
+        ix, lr = cg.ref("mixed/mono-stereo")
         a = 1152 * 60 + 5
         assert (lr[0, a:a + t] != lr[1, a:a + t]).any() and ((lr[0, a:a + t] + lr[1, a:a + t]) % 2 != 0).any()
     finally:
@@ -174,13 +85,13 @@ RESAMPLE_SOURCES = ["mixed/mono-stereo", "48k", "32k", "22k", "16k-mono", "8k", 
 def test_resampling_a_batch_of_mixed_rates_against_binary64(rate, width, kind):
     """one batch of 44.1 / 48 / 32 kHz MPEG-1 and 22.05 / 16 / 8 kHz LSF sources to one rate, stereo and downmixed"""
     t = 24000 if rate == 16000 else 40000
-    dec = _decoder()
+    dec = cg.decoder()
     try:
-        rates = set(_ref(n)[0].rate for n in RESAMPLE_SOURCES)
+        rates = set(cg.ref(n)[0].rate for n in RESAMPLE_SOURCES)
         assert rates >= {44100, 48000, 32000, 22050, 16000, 8000}
         clips = []
         for n in RESAMPLE_SOURCES:
-            ix, _ = _ref(n)
+            ix, _ = cg.ref(n)
             j_all = ref.out_length(ix.samples, ix.rate, rate)
             clips += [(n, 0), (n, j_all // 3 + 11), (n, max(j_all - t // 2, 0)), (n, j_all + 3)]
         for channels in (2, 1):
@@ -201,20 +112,20 @@ def test_refusals():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix, _ = _ref("mixed/mpeg1-lsf")
+    mix, _ = cg.ref("mixed/mpeg1-lsf")
     assert not mix.one_format
-    good, _ = _ref("48k")
-    s = _streams()
-    dec = _decoder()
+    good, _ = cg.ref("48k")
+    s = cg.streams()
+    dec = cg.decoder()
     try:
         for kind in ("device", "numpy"):
             # a mixed-format clip inside a batch; with a replay clip as well the replay wins
             for clips, exc, codes in (([("48k", good, 100), ("mixed/mpeg1-lsf", mix, 0), ("48k", good, 3000)], api.MixedFormat, [None, -3, None]),
                                       ([("mixed/mpeg1-lsf", mix, 50), ("48k", good, 100), (None, bix, 10)], api.RingReplay, [-3, None, -2])):
-                big, view = _destination(kind, 3, 2, t)
+                big, view = cg.destination(kind, 3, 2, (t,))
                 with pytest.raises(exc) as e:
                     dec.decode_clips_audio([(bad if n is None else s[n], ix, st) for n, ix, st in clips], t, 16000, 2, out=view)
-                host = _host(big)
+                host = cg.host(big)
                 for i, (n, ix, st) in enumerate(clips):
                     if codes[i] is None:
                         _check(n, st, host[i, :, :t], int(e.value.valid[i]), t, 16000, 2)
@@ -222,7 +133,7 @@ def test_refusals():
                     else:
                         assert e.value.valid[i] == codes[i] and (host[i] == SENT).all()
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 2, t)
+        big, view = cg.destination("device", 1, 2, (t,))
         with pytest.raises(RuntimeError):
             dec.decode_clips_audio([(s["48k"], good, -1)], t, 16000, 2, out=view)
         with pytest.raises(RuntimeError):
@@ -230,28 +141,28 @@ def test_refusals():
         with pytest.raises(RuntimeError):
             dec.decode_clips_audio([(s["48k"], good, 0)], t, 16000, 2, rolloff=1.5, out=view)
         with pytest.raises(ValueError):
-            dec.decode_clips_audio([(s["48k"], good, 0), (s["44k-mono"], _ref("44k-mono")[0], 0)], t, 16000, 0)
-        assert (_host(big) == SENT).all()
+            dec.decode_clips_audio([(s["48k"], good, 0), (s["44k-mono"], cg.ref("44k-mono")[0], 0)], t, 16000, 0)
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
     # a decoder without PDMP3_ISO_LSF on an LSF index, and a host-Huffman decoder
-    lsf, _ = _ref("22k")
+    lsf, _ = cg.ref("22k")
     plain = api.BulkDecoder(threads=2)
     try:
-        big, view = _destination("device", 1, 2, t)
+        big, view = cg.destination("device", 1, 2, (t,))
         with pytest.raises(RuntimeError):
             plain.decode_clips_audio([(s["22k"], lsf, 0)], t, 16000, 2, out=view)
-        assert (_host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         plain.close()
     hh = api.BulkDecoder(threads=2, host_huffman=True)
     try:
         hh.set_quirks(ISO_LSF)
-        big, view = _destination("device", 1, 2, t)
+        big, view = cg.destination("device", 1, 2, (t,))
         with pytest.raises(RuntimeError):
             hh.decode_clips_audio([(s["48k"], good, 0)], t, 16000, 2, out=view)
-        assert (_host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         hh.close()
     torch.cuda.synchronize()
@@ -266,17 +177,17 @@ def test_clip_stats_count_audio_clips_and_plain_clips_still_work():
     par.set_quirks(ISO_LSF)
     try:
         for n, st in clips:
-            ix, _ = _ref(n)
+            ix, _ = cg.ref(n)
             first, count = api.audio_span(ix.rate, rate, st, t)
             lo, hi = max(first, 0), min(first + count, ix.samples)
             a, e = lo // ix.frame_samples, (hi - 1) // ix.frame_samples + 1
             assert e > a
-            f0, _, _ = par.parse_range(_streams()[n], ix, a, e - a)
+            f0, _, _ = par.parse_range(cg.streams()[n], ix, a, e - a)
             kept += e - a
             halo += a - f0
     finally:
         par.close()
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         assert dec.clip_stats() == (0, 0)
         got, valid = _run(dec, "device", clips, t, rate, 1)
@@ -284,28 +195,28 @@ def test_clip_stats_count_audio_clips_and_plain_clips_still_work():
             _check(n, st, got[i], int(valid[i]), t, rate, 1)
         assert dec.clip_stats() == (kept, halo)
         # the stage and the tables do not disturb the slots: plain clips on the same decoder, then audio again
-        k = next(i for i, x in enumerate(tgc._streams()) if x[0] == "mixed/mono-stereo")
-        ix, whole = tgc._ref(k)
-        plain = dec.decode_range(tgc._streams()[k][1], ix, 33, 50)
+        k = next(i for i, x in enumerate(clip_streams.gpu_streams()) if x[0] == "mixed/mono-stereo")
+        ix, whole = cg.frames_ref(k)
+        plain = dec.decode_range(clip_streams.gpu_streams()[k][1], ix, 33, 50)
         assert np.array_equal(plain, whole[int(ix.pcm_offsets[33]) // 2:int(ix.pcm_offsets[83]) // 2])
         got, valid = _run(dec, "numpy", clips, t, rate, 2)
         for i, (n, st) in enumerate(clips):
             _check(n, st, got[i], int(valid[i]), t, rate, 2)
-        assert dec.clip_stats() == (2 * kept + 50, 2 * halo + 33 - tgc._halo(k, 33, 50))
+        assert dec.clip_stats() == (2 * kept + 50, 2 * halo + 33 - cg.halo(k, 33, 50))
     finally:
         dec.close()
 
 
 def test_made_output_and_empty_calls():
     """out=None: a tensor on the decoder's device; n_samples 0 and no clips are fine"""
-    dec = _decoder()
+    dec = cg.decoder()
     try:
-        out, valid = dec.decode_clips_audio([(_streams()["32k"], _ref("32k")[0], 1000)], 8000, 16000, 1)
+        out, valid = dec.decode_clips_audio([(cg.streams()["32k"], cg.ref("32k")[0], 1000)], 8000, 16000, 1)
         assert tuple(out.shape) == (1, 1, 8000) and out.is_cuda
-        _check("32k", 1000, _host(out)[0], int(valid[0]), 8000, 16000, 1)
+        _check("32k", 1000, cg.host(out)[0], int(valid[0]), 8000, 16000, 1)
         out, valid = dec.decode_clips_audio([], 100, 16000, 1)
         assert tuple(out.shape) == (0, 1, 100) and valid.size == 0
-        out, valid = dec.decode_clips_audio([(_streams()["32k"], _ref("32k")[0], 1000)], 0, 16000, 1)
+        out, valid = dec.decode_clips_audio([(cg.streams()["32k"], cg.ref("32k")[0], 1000)], 0, 16000, 1)
         assert tuple(out.shape) == (1, 1, 0) and valid[0] == 0
     finally:
         dec.close()

@@ -4,7 +4,7 @@ forms by name -- plan 3: input span and table in LDS, plan 1: the span in LDS an
 straight from memory --, output rates that are no MPEG rates, tile edges, host destinations as a loader lays them out, a call of
 more clips than one grid holds, one decoder over many calls, far starts, and seeded random batches.
 
-Every value is checked as in test_gpu_clip_audio.py (its helpers are used): at the stream's own rate bit for bit against the
+Every value is checked as in test_gpu_clip_audio.py (the same helpers): at the stream's own rate bit for bit against the
 whole-stream decode, at another rate against clip_audio_ref.resample64 within its bound (T_j + 2) 2^-24 sum |h| |x|.  No other
 tolerance.  The plan of a case is asserted from the product (api.audio_lds_plan) before the call: a change of audio_lds that
 moves a case to another form fails here by name.
@@ -18,8 +18,10 @@ import numpy as np
 import pytest
 
 import clip_audio_ref as ref
-import test_gpu_clips as tgc
-from test_gpu_clip_audio import GUARD, SENT, _check, _decoder, _destination, _host, _ref, _run, _streams
+import clip_gpu as cg
+import clip_streams
+from clip_gpu import GUARD, SENT
+from clip_gpu_calls import audio_check as _check, audio_run as _run
 
 pytestmark = pytest.mark.gpu
 PLAN0_WORK = 1 << 27
@@ -28,7 +30,7 @@ PLAN0_WORK = 1 << 27
 def _plan(name, rate, channels, width=0, rolloff=0.0):
     """the form of k_clip_audio a clip of this stream takes: "own" (no filter), else the product's LDS flags 0, 1 or 3"""
     from pdmp3_amd import api
-    ix, _ = _ref(name)
+    ix, _ = cg.ref(name)
     if not rate or rate == ix.rate:
         return "own"
     return api.audio_lds_plan(ix.rate, rate, channels, width, rolloff)[0]
@@ -38,7 +40,7 @@ def _cap_ok(name, rate, channels, t, width=0, rolloff=0.0):
     from pdmp3_amd import api
     if _plan(name, rate, channels, width, rolloff) != 0:
         return True
-    return t * channels * api.audio_table(_ref(name)[0].rate, rate, width, rolloff)[0].shape[1] <= PLAN0_WORK
+    return t * channels * api.audio_table(cg.ref(name)[0].rate, rate, width, rolloff)[0].shape[1] <= PLAN0_WORK
 
 
 def _run_checked(dec, kind, clips, t, rate, channels, width=0, rolloff=0.0):
@@ -54,7 +56,7 @@ def _run_checked(dec, kind, clips, t, rate, channels, width=0, rolloff=0.0):
 
 
 def _j(name, rate):
-    ix, _ = _ref(name)
+    ix, _ = cg.ref(name)
     return ref.out_length(ix.samples, ix.rate, rate or ix.rate)
 
 
@@ -88,7 +90,7 @@ PLAN_CASES = [
 def test_every_plan_by_name(case):
     from pdmp3_amd import api
     name, rate, width, rolloff, channels, t, plan = PLAN_CASES[case]
-    ix, lr = _ref(name)
+    ix, lr = cg.ref(name)
     assert api.audio_lds_plan(ix.rate, rate, channels, width, rolloff)[0] == plan, "%s: the LDS plan of this case has moved" % (PLAN_CASES[case],)
     clips = [(name, s) for s in _starts(name, rate, t)]
     if name == "mixed/mono-stereo" and rate == 16000:
@@ -99,7 +101,7 @@ def test_every_plan_by_name(case):
         assert first <= loud < first + count and ix.channels == 2 and (lr[0, first:first + count] != lr[1, first:first + count]).any()
         assert ((lr[0, first:first + count] + lr[1, first:first + count]) % 2 != 0).any()
         clips.append((name, start))
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         for kind in ("device", "numpy"):
             worst, got, valid = _run_checked(dec, kind, clips, t, rate, channels, width, rolloff)
@@ -120,7 +122,7 @@ def test_all_forms_in_one_launch(kind):
     names = ["48k", "16k-mono", "22k", "8k", "48k", "16k-mono"]
     assert [_plan(n, rate, channels, width, rolloff) for n in names[:4]] == [0, 3, 1, "own"]
     clips = [(n, _starts(n, rate, t)[1 + i % 2]) for i, n in enumerate(names)]
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         worst, got, valid = _run_checked(dec, kind, clips, t, rate, channels, width, rolloff)
         print("plans 0, 1, 3 and the own rate in one launch, %s: worst error / bound %s" % (kind, sorted(worst.items(), key=str)))
@@ -136,10 +138,10 @@ EDGE_T = [1, 2, 255, 256, 257, 1023, 1024, 1025, 2048, 2049]
 @pytest.mark.parametrize("name,rate", [("32k", 16000), ("44k-mono", 0)])
 def test_tile_edges(name, rate, kind):
     """T and J - start on and around the tile length: what nt, nv and the branch of a tile wholly behind the stream's end store"""
-    ix, _ = _ref(name)
+    ix, _ = cg.ref(name)
     j = _j(name, rate)
     assert ix.samples * (rate or ix.rate) % ix.rate == 0          # (J is N L / M exactly)
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         for t in EDGE_T:
             left = sorted(set(d for d in (0, 1, 2, 1023, 1024, 1025, t - 1, t, t + 1) if d >= 0))
@@ -161,7 +163,7 @@ def _host_clips(rate, t):
 
 
 def _decode_into(dec, clips, view, t, rate, channels):
-    out, valid = dec.decode_clips_audio([(_streams()[n], _ref(n)[0], s) for n, s in clips], t, rate, channels, out=view)
+    out, valid = dec.decode_clips_audio(cg.src(clips), t, rate, channels, out=view)
     assert out is view
     return valid
 
@@ -183,8 +185,8 @@ def test_contiguous_numpy_destinations(channels):
     rate, t = 16000, 3001
     clips = _host_clips(rate, t)
     k = len(clips)
-    assert k == 7 and len(set(_ref(n)[0].rate for n, _ in clips)) >= 6
-    dec = _decoder()
+    assert k == 7 and len(set(cg.ref(n)[0].rate for n, _ in clips)) >= 6
+    dec = cg.decoder()
     try:
         dense = np.full((k, channels, t), SENT, dtype=np.float32)
         assert dense.flags["C_CONTIGUOUS"]
@@ -200,7 +202,7 @@ def test_contiguous_numpy_destinations(channels):
         assert (flat[k * channels * t:] == SENT).all(), "written behind the last row"
         assert np.array_equal(view, dense)
         # a refused clip in the middle
-        mix, _ = _ref("mixed/mpeg1-lsf")
+        mix, _ = cg.ref("mixed/mpeg1-lsf")
         assert not mix.one_format
         holed = clips[:3] + [("mixed/mpeg1-lsf", 100)] + clips[4:]
         flat[:] = SENT
@@ -218,7 +220,7 @@ def test_stereo_rows_with_dense_channels_and_a_guard_between_rows():
     rate, t, channels = 16000, 3001, 2
     clips = _host_clips(rate, t)
     k = len(clips)
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         big = np.full((k, 2 * t + GUARD), SENT, dtype=np.float32)
         view = np.lib.stride_tricks.as_strided(big, shape=(k, 2, t), strides=(big.strides[0], 4 * t, 4), writeable=True)
@@ -240,7 +242,7 @@ def test_pinned_host_destination(channels):
     clips = _host_clips(rate, t)
     k = len(clips)
     pin = api.PinnedPCM(2 * k * channels * (t + GUARD))
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         big = pin.array.view(np.float32).reshape(k, channels, t + GUARD)
         hip = pdmp3_amd.load_library()
@@ -269,21 +271,21 @@ def test_more_clips_than_one_grid(rate):
     """32 768 + 5 clips of one stream in one call: pdmp3_hip_clip_audio launches the kernel twice (a grid's y extent), the second
     time from descriptor 32 768 on"""
     name, t, k, base = "32k", 8, 32768 + 5, 50000
-    ix, lr = _ref(name)
+    ix, lr = cg.ref(name)
     offs = (np.arange(k, dtype=np.int64) * 37) % 4000
     assert base + 4000 + t < _j(name, rate) and np.unique(offs).size == 4000
     x = ref.channels64(lr, ix.channels, 1)
     y64, bound = ref.resample64(x, ix.rate, rate or ix.rate, 6, 0.99, base, 4000 + t)
     at = offs[:, None] + np.arange(t)[None, :]
     want, bnd = y64[0][at], bound[0][at]
-    dec = _decoder()
+    dec = cg.decoder()
     try:
-        big, view = _destination("device", k, 1, t)
-        mp3 = _streams()[name]
+        big, view = cg.destination("device", k, 1, (t,))
+        mp3 = cg.streams()[name]
         t0 = time.perf_counter()
         out, valid = dec.decode_clips_audio([(mp3, ix, int(base + o)) for o in offs], t, rate, 1, out=view)
         wall = time.perf_counter() - t0
-        host = _host(big)
+        host = cg.host(big)
         assert (host[:, :, t:] == SENT).all(), "written behind a row's samples"
         assert (valid == t).all()
         err = np.abs(host[:, 0, :t].astype(np.float64) - want)
@@ -303,7 +305,7 @@ def test_more_clips_than_one_grid(rate):
 def test_one_decoder_over_many_calls():
     """a small call, a large one (both stages and the argument block are freed and allocated again), the small one again; twelve
     tables on one decoder, then the first again; plain frame ranges afterwards"""
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         small = [("mixed/mono-stereo", 40000), ("48k", 7)]
         w1, first, v1 = _run_checked(dec, "numpy", small, 500, 16000, 2)
@@ -327,9 +329,9 @@ def test_one_decoder_over_many_calls():
         for kind in ("numpy", "device"):                                     # the first key again: its table is still the decoder's
             w, got, valid = _run_checked(dec, kind, small, 500, 16000, 2)
             assert np.array_equal(got, first)
-        k = next(i for i, x in enumerate(tgc._streams()) if x[0] == "mixed/mono-stereo")
-        ix, whole = tgc._ref(k)
-        plain = dec.decode_range(tgc._streams()[k][1], ix, 33, 50)
+        k = next(i for i, x in enumerate(clip_streams.gpu_streams()) if x[0] == "mixed/mono-stereo")
+        ix, whole = cg.frames_ref(k)
+        plain = dec.decode_range(clip_streams.gpu_streams()[k][1], ix, 33, 50)
         assert np.array_equal(plain, whole[int(ix.pcm_offsets[33]) // 2:int(ix.pcm_offsets[83]) // 2])
     finally:
         dec.close()
@@ -338,9 +340,9 @@ def test_one_decoder_over_many_calls():
 def test_far_starts_and_refusals():
     from pdmp3_amd import api
     t = 3000
-    s = _streams()
-    good, _ = _ref("48k")
-    dec = _decoder()
+    s = cg.streams()
+    good, _ = cg.ref("48k")
+    dec = cg.decoder()
     try:
         for kind in ("device", "numpy"):
             for rate in (16000, 0):
@@ -350,17 +352,17 @@ def test_far_starts_and_refusals():
                 assert valid[0] == 0 and (got == 0).all() and dec.clip_stats() == stats
                 _, got, valid = _run_checked(dec, kind, [("48k", 2 ** 40), ("48k", 100), ("48k", 2 ** 40 + 1)], t, rate, 2)
                 assert list(valid) == [0, t, 0] and (got[0] == 0).all() and (got[2] == 0).all()
-            big, view = _destination(kind, 2, 2, t)
+            big, view = cg.destination(kind, 2, 2, (t,))
             m, _ = ref.ratio(48000, 16000)
             limit = (2 ** 63 - 1) // 2 // m - t
             with pytest.raises(RuntimeError):
                 dec.decode_clips_audio([(s["48k"], good, 100), (s["48k"], good, limit + 1)], t, 16000, 2, out=view)
             with pytest.raises(RuntimeError):
                 dec.decode_clips_audio([(s["48k"], good, 100), (s["48k"], good, 0)], t, 2 ** 31 - 1, 2, out=view)
-            assert (_host(big) == SENT).all()
+            assert (cg.host(big) == SENT).all()
             # at the limit itself: far behind the stream, zeros
             out, valid = dec.decode_clips_audio([(s["48k"], good, 100), (s["48k"], good, limit)], t, 16000, 2, out=view)
-            host = _host(big)
+            host = cg.host(big)
             assert list(valid) == [t, 0] and (host[1, :, :t] == 0).all() and (host[:, :, t:] == SENT).all()
     finally:
         dec.close()
@@ -375,7 +377,7 @@ def _fuzz_batches(index_of):
     index_of(name) -> StreamIndex; needs no GPU (the seed is chosen where there is none)"""
     from pdmp3_amd import api
     rng = np.random.default_rng(FUZZ_SEED)
-    names = sorted(n for n in _streams() if index_of(n).one_format)
+    names = sorted(n for n in cg.streams() if index_of(n).one_format)
     out = []
     for b in range(24):
         rate = int(rng.choice(FUZZ_RATES))
@@ -408,10 +410,10 @@ def _fuzz_batches(index_of):
 
 
 def test_seeded_random_batches():
-    batches = _fuzz_batches(lambda n: _ref(n)[0])
+    batches = _fuzz_batches(lambda n: cg.ref(n)[0])
     assert sum(b is None for b in batches) <= 4
     assert set().union(*[b["plans"] for b in batches if b]) == {0, 1, 3, "own"}
-    dec = _decoder()
+    dec = cg.decoder()
     try:
         for i, b in enumerate(batches):
             if b is None:
@@ -422,7 +424,7 @@ def test_seeded_random_batches():
                 assert _cap_ok(n, rate, channels, t, width, rolloff)
             if b["kind"] == "numpy-contiguous":
                 dense = np.full((len(clips), channels, t), SENT, dtype=np.float32)
-                out, valid = dec.decode_clips_audio([(_streams()[n], _ref(n)[0], s) for n, s in clips], t, rate, channels, width, rolloff, out=dense)
+                out, valid = dec.decode_clips_audio(cg.src(clips), t, rate, channels, width, rolloff, out=dense)
                 got = dense
             else:
                 got, valid = _run(dec, b["kind"], clips, t, rate, channels, width, rolloff)

@@ -17,15 +17,15 @@ import pytest
 import clip_audio_ref as aref
 import clip_chroma_ref as ref
 import clip_cqt_ref as cref
+import clip_forms_cases as cases
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_cqt as tgq
-import test_gpu_clip_mel as tgm
-import test_gpu_clip_stft as tgs
+from clip_gpu import GUARD, SENT
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD, U = tgs.SENT, tgs.GUARD, ref.U
+U = ref.U
 C1, C3 = ref.FMIN_C1, ref.FMIN_C3
 QUANTITIES = ["magnitude", "power"]
 NORMS = [None, "l1", "l2", "max"]
@@ -47,7 +47,7 @@ PM = dict(sample_rate=0, hop=1, channels=1, fmin=500.0, n_bins=6, bins_per_octav
 
 def _hop_for(tile, sr=44100):
     """the smallest multiple of 64 at which the plan of (e) at 44.1 kHz takes `tile` frames"""
-    return next(h for h in range(64, 8193, 64) if ref.plan(sr, h, **tgq._shape(PE))[0] == tile)
+    return next(h for h in range(64, 8193, 64) if ref.plan(sr, h, **calls.cqt_shape(PE))[0] == tile)
 
 
 PE8, PE4 = dict(PE, hop=_hop_for(8)), dict(PE, hop=_hop_for(4))
@@ -57,30 +57,19 @@ def _cqt_args(p):
     return {k: v for k, v in p.items() if k not in FOLD}
 
 
-def _src(clips):
-    return [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-
-
 def _run(dec, kind, clips, f, p, quantity, norm, floor=1e-10):
     """clips: (stream name, start) -> (host copy [k, c, n_chroma, f], valid)"""
-    k, c, nc = len(clips), p["channels"], p["n_chroma"]
-    per = nc * f
-    big, view = tgs._destination(kind, k, c, nc, f, "magnitude")
-    out, valid = dec.decode_clips_chroma(_src(clips), f, quantity=quantity, chroma_norm=norm, norm_floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big).reshape(k, c, per + GUARD)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :per].reshape(k, c, nc, f), valid
+    return cg.run(dec, "decode_clips_chroma", kind, clips, f, p["channels"], (p["n_chroma"], f), quantity=quantity, chroma_norm=norm, norm_floor=floor, **p)
 
 
 def _reference(dec, clips, f, p):
     """per clip and quantity the constant-Q transform of the product's own signal in binary64 with its bounds -- computed once a
     case and left unchanged"""
-    sig = tgq._signal(dec, clips, f, p)
+    sig = calls.cqt_signal(dec, clips, f, p)
     out = []
     for (n, s), (s0, y) in zip(clips, sig):
-        rate = tgm._rate(p, n)
-        out.append({q: cref.cqt(y, s0, s, f, rate, p["hop"], cref.MODES[q], **tgq._geo(p)) for q in QUANTITIES} | {"signal": float(np.abs(y).sum())})
+        rate = cg.rate(p, n)
+        out.append({q: cref.cqt(y, s0, s, f, rate, p["hop"], cref.MODES[q], **calls.cqt_geo(p)) for q in QUANTITIES} | {"signal": float(np.abs(y).sum())})
     return out
 
 
@@ -88,8 +77,8 @@ def _check(clips, refs, got, valid, f, p, quantity, norm, floor=1e-10):
     """every row against the definition; -> worst error / bound over the rows that hold signal"""
     worst = 0.0
     for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, tgm._rate(p, n))
+        ix = cg.ref(n)[0]
+        j_all = aref.out_length(ix.samples, ix.rate, cg.rate(p, n))
         assert int(valid[i]) == ref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
         want, bound = ref.from_cqt(*refs[i][quantity], p["bins_per_octave"], p["n_chroma"], p["base_class"], ref.NORMS[norm], floor)
         assert want.shape == got[i].shape
@@ -121,27 +110,27 @@ CASES = {
 def test_against_binary64_and_against_the_fold_of_the_cqt_call(case):
     from pdmp3_amd import api
     p, names, f, path, n_split, n_tiles = CASES[case]
-    rate = tgm._rate(p, names[0])
-    assert all(tgm._rate(p, n) == rate for n in names)
+    rate = cg.rate(p, names[0])
+    assert all(cg.rate(p, n) == rate for n in names)
     # the launch path and the tile, from the plan function and from its restatement
-    plan = api.chroma_plan(rate, hop=p["hop"], n_chroma=p["n_chroma"], base_class=p["base_class"], **tgq._shape(p))
-    want = ref.plan(rate, p["hop"], **tgq._shape(p))
+    plan = api.chroma_plan(rate, hop=p["hop"], n_chroma=p["n_chroma"], base_class=p["base_class"], **calls.cqt_shape(p))
+    want = ref.plan(rate, p["hop"], **calls.cqt_shape(p))
     assert plan == want[:8] and want[8] == path and plan[5] == n_split and (p["n_bins"] + 15) // 16 == n_tiles
     tile = plan[0]
     assert f > tile                                                          # (a tile edge inside the clip)
     if case == "e-44k-tile-4":
-        assert api.cqt_plan(rate, hop=p["hop"], **tgq._shape(p))[0] == 8     # (the q plane costs this spec a tile size)
+        assert api.cqt_plan(rate, hop=p["hop"], **calls.cqt_shape(p))[0] == 8     # (the q plane costs this spec a tile size)
     cls, count = ref.class_map(p["n_bins"], p["bins_per_octave"], p["n_chroma"], p["base_class"])
     if case[0] == "c":
         assert cls[0] == cls[1] == p["base_class"] and cls[2] == p["base_class"] + 1 and cls[107] == p["base_class"] and list(count) == [9] * 12
     if case[0] == "d":
         assert sorted(set(count)) == [1, 2]
-    clips = [(n, s) for n in names for s in tgq._starts(n, p, f)]
-    dec = tga._decoder()
+    clips = [(n, s) for n in names for s in calls.centred_starts(n, p, f)]
+    dec = cg.decoder()
     try:
         refs = _reference(dec, clips, f, p)
         for quantity in QUANTITIES:
-            q32, qv = tgq._run(dec, "device", clips, f, _cqt_args(p), quantity)
+            q32, qv = calls.cqt_run(dec, "device", clips, f, _cqt_args(p), quantity)
             folded = ref.fold32(q32, cls, p["n_chroma"])
             for norm in NORMS:
                 floor = 1e-10 if norm != "l1" else 0.5       # (L1 against a floor that some frames' sums reach and some do not)
@@ -165,10 +154,10 @@ def test_against_binary64_and_against_the_fold_of_the_cqt_call(case):
 
 def test_clips_wholly_behind_the_end_are_exactly_zero():
     p, f, name = PB, 18, "32k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, 16000)
-    h0 = int(cref.lengths(16000, **tgq._shape(p))[2][0])
-    dec = tga._decoder()
+    h0 = int(cref.lengths(16000, **calls.cqt_shape(p))[2][0])
+    dec = cg.decoder()
     try:
         stats = dec.clip_stats()
         clips = [(name, j_all + h0), (name, j_all + 10 ** 6), (name, 2 ** 40)]
@@ -187,8 +176,8 @@ def test_frames_are_frames_and_slices_of_a_batch_are_slices():
     from pdmp3_amd import api
     p = dict(PA, channels=1)
     name, start = "48k", 4321
-    tile = api.chroma_plan(22050, hop=p["hop"], **tgq._shape(p))[0]
-    dec = tga._decoder()
+    tile = api.chroma_plan(22050, hop=p["hop"], **calls.cqt_shape(p))[0]
+    dec = cg.decoder()
     try:
         fs = [0, 1, tile - 1, tile, tile + 1, tile + 4]
         for norm in ("l2", "max"):
@@ -212,28 +201,28 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         refs = _reference(dec, good, f, p)
         per = nc * f
         for kind, norm in (("device", "max"), ("numpy", "l2")):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tgs._destination(kind, 3, 1, nc, f, "magnitude")
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, (nc, f))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_chroma(src, f, chroma_norm=norm, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape(2, 1, nc, f)
                 assert 0.0 < _check(good, refs, got, e.value.valid[[0, 2]], f, p, "magnitude", norm) <= 1.0
         # bad arguments: nothing is written
-        big, view = tgs._destination("device", 1, 1, nc, f, "magnitude")
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, (nc, f))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         for bad_p in (dict(n_chroma=0), dict(n_chroma=5), dict(n_chroma=24), dict(base_class=12), dict(base_class=-1), dict(chroma_norm=4),
                       dict(chroma_norm="l3"), dict(norm_floor=0.0), dict(norm_floor=1e-46), dict(norm_floor=float("nan")), dict(quantity="complex"),
                       dict(quantity="log10"), dict(hop=0), dict(fmin=0.0), dict(fmin=7600.0), dict(bins_per_octave=0), dict(norm=3), dict(width=65)):
@@ -241,12 +230,12 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
             out = view if args["n_chroma"] == nc else None
             with pytest.raises(RuntimeError):
                 dec.decode_clips_chroma(src, f, out=out, **args)
-            assert (tga._host(big) == SENT).all(), bad_p
+            assert (cg.host(big) == SENT).all(), bad_p
         with pytest.raises(RuntimeError):
-            dec.decode_clips_chroma([(s["48k"], tga._ref("48k")[0], -1)], f, out=view, **p)
+            dec.decode_clips_chroma([(s["48k"], cg.ref("48k")[0], -1)], f, out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_chroma(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_chroma(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -257,17 +246,17 @@ def test_more_clips_than_one_grid():
     descriptor 32 768 on.  Sixty-four distinct clips are held against the definition, every row is bit-equal to its twin among
     them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k, f, p = "8k", 32768 + 5, 40, PM
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     assert ix.rate == 8000
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
-    h0 = int(cref.lengths(8000, **tgq._shape(p))[2][0])
+    h0 = int(cref.lengths(8000, **calls.cqt_shape(p))[2][0])
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + h0 + 9, j_all - 5]
     assert starts[61] + f + h0 + 16 < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         refs = _reference(dec, first, f, p)
@@ -275,10 +264,10 @@ def test_more_clips_than_one_grid():
         assert 0.0 < _check(first, refs, base, valid64, f, p, "magnitude", "max") <= 1.0
         assert list(valid64[61:]) == [f, 0, 5] and (base[62] == 0.0).all()
         nc = p["n_chroma"]
-        big, view = tgs._destination("device", k, 1, nc, f, "magnitude")
+        big, view = cg.destination("device", k, 1, (nc, f))
         out, valid = dec.decode_clips_chroma([(mp3, ix, int(starts[t])) for t in twin], f, out=view, **p)
         per = nc * f
-        host = tga._host(big).reshape(k, per + GUARD)
+        host = cg.host(big).reshape(k, per + GUARD)
         assert (host[:, per:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 5, f, f, f]
         same = (host[:, :per].view(np.uint32) == base[twin].reshape(k, per).view(np.uint32)).all(axis=1)
@@ -294,19 +283,19 @@ def test_one_decoder_through_this_call_the_cqt_call_and_the_mel_call_twice():
     tables, decode_clips_mel, this call with other fold arguments -- and all of it again: every call is bit-equal to its first
     answer"""
     small = [("48k", 500), ("22k", 1234)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         def round_():
             out = []
             out.append(_run(dec, "device", small, 9, PB, "magnitude", "max"))
-            out.append(tgq._run(dec, "device", small, 9, _cqt_args(PB), "magnitude"))
+            out.append(calls.cqt_run(dec, "device", small, 9, _cqt_args(PB), "magnitude"))
             for i in range(5):                                                   # (more tables than the decoder keeps)
-                out.append(tgq._run(dec, "device", small, 3, dict(_cqt_args(PB), fmin=1000.0 + 10.0 * i), "power"))
+                out.append(calls.cqt_run(dec, "device", small, 3, dict(_cqt_args(PB), fmin=1000.0 + 10.0 * i), "power"))
                 out.append(_run(dec, "device", small, 3, dict(PB, fmin=1005.0 + 10.0 * i), "power", "l1"))
-            out.append(tgm._run(dec, "device", small, 9, tgm.P16, "log10"))
+            out.append(calls.mel_run(dec, "device", small, 9, cases.MEL_P16, "log10"))
             out.append(_run(dec, "device", small, 9, dict(PB, n_chroma=6, base_class=2), "magnitude", "l2"))
             out.append(_run(dec, "numpy", small, 9, PB, "magnitude", "max"))
-            return [(tga._host(a), v) for a, v in out]
+            return [(cg.host(a), v) for a, v in out]
         one, two = round_(), round_()
         assert len(one) == len(two)
         for (a, va), (b, vb) in zip(one, two):
@@ -324,13 +313,13 @@ def test_one_decoder_through_this_call_the_cqt_call_and_the_mel_call_twice():
 
 def test_return_types_and_empty_calls():
     import torch
-    src = [(tga._streams()["22k"], tga._ref("22k")[0], 1000)]
-    dec = tga._decoder()
+    src = [(cg.streams()["22k"], cg.ref("22k")[0], 1000)]
+    dec = cg.decoder()
     try:
         out, valid = dec.decode_clips_chroma(src, 17)          # the defaults: 22 050 Hz, C1, 84 bins, 12 classes, magnitudes, max; the stream's channels
         assert tuple(out.shape) == (1, 2, 12, 17) and out.is_cuda and out.dtype == torch.float32 and valid[0] == 17
         plain, _ = _run(dec, "device", [("22k", 1000)], 17, PA, "magnitude", "max")
-        assert np.array_equal(tga._host(out).view(np.uint32), plain.view(np.uint32)) and (plain.max(axis=2) == 1.0).all()
+        assert np.array_equal(cg.host(out).view(np.uint32), plain.view(np.uint32)) and (plain.max(axis=2) == 1.0).all()
         out, valid = dec.decode_clips_chroma([], 10, channels=1)
         assert tuple(out.shape) == (0, 1, 12, 10) and valid.size == 0
         out, valid = dec.decode_clips_chroma(src, 0, n_chroma=6, channels=1)

@@ -7,7 +7,7 @@ output has to agree within the binary32 bound derived there -- every value of ev
 output exactly 0 on silence in modes 0 - 2.  Destinations are filled with a sentinel first: nothing outside a row's floats may
 change.  Each device step runs once.
 
-Streams and helpers: those of test_gpu_clip_audio.py, test_gpu_clip_mel.py and test_gpu_clip_stft.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import math
 
 import numpy as np
@@ -15,17 +15,18 @@ import pytest
 
 import clip_audio_ref as aref
 import clip_cqt_ref as ref
+import clip_forms_cases as cases
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
-import test_gpu_clip_stft as tgs
+from clip_gpu import GUARD, SENT
+from clip_gpu_calls import centred_starts as _starts, cqt_geo as _geo, cqt_run as _run, cqt_shape as _shape, cqt_signal as _signal
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD, U = tgs.SENT, tgs.GUARD, ref.U
+U = ref.U
 MODES = ["complex", "magnitude", "power", "log", "log10"]
 C1 = ref.FMIN_C1
-GEO = ("fmin", "n_bins", "bins_per_octave", "filter_scale", "norm", "scale")
 SEEN = {"im": False, "swap": False}
 
 # (a) split and unsplit tiles, a last tile of 4 bins, a tile edge inside the clip (20 frames); (b) every tile split, N_0 = 29 783,
@@ -38,14 +39,6 @@ PD = dict(sample_rate=0, hop=1, channels=1, fmin=500.0, n_bins=3, bins_per_octav
 PE = dict(sample_rate=0, channels=1, fmin=C1, n_bins=24, bins_per_octave=12, norm=1, scale=0)
 
 
-def _geo(p):
-    return {k: p[k] for k in GEO if k in p}
-
-
-def _shape(p):
-    return {k: p[k] for k in ("fmin", "n_bins", "bins_per_octave", "filter_scale") if k in p}
-
-
 def _hop_for(tile, sr=44100):
     """the smallest multiple of 64 at which the plan of (e) at 44.1 kHz takes `tile` frames"""
     return next(h for h in range(64, 8193, 64) if ref.plan(sr, h, **_shape(PE))[0] == tile)
@@ -54,37 +47,13 @@ def _hop_for(tile, sr=44100):
 PE8, PE4 = dict(PE, hop=_hop_for(8)), dict(PE, hop=_hop_for(4))
 
 
-def _q(p, name):
-    """p with the n_fft that test_gpu_clip_mel's helpers read: N_0, whose half is h_0"""
-    h0 = int(ref.lengths(tgm._rate(p, name), **_shape(p))[2][0])
-    return dict(p, n_fft=2 * h0 + 1)
-
-
-def _run(dec, kind, clips, f, p, mode, floor=1e-10, offset=0):
-    """clips: (stream name, start) -> (host copy [k, c, n_bins, f(, 2)], valid)"""
-    k, c, nb = len(clips), p["channels"], p["n_bins"]
-    per = nb * f * (2 if mode == "complex" else 1)
-    big, view = tgs._destination(kind, k, c, nb, f, mode, offset=offset)
-    out, valid = dec.decode_clips_cqt([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, mode=mode, floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:offset] == SENT).all()
-    host = host[offset:].reshape(k, c, per + GUARD)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :per].reshape((k, c, nb, f, 2) if mode == "complex" else (k, c, nb, f)), valid
-
-
-def _signal(dec, clips, f, p):
-    return tgm._signal(dec, clips, f, _q(p, clips[0][0]))
-
-
 def _check(clips, sig, got, valid, f, p, mode, floor=1e-10):
     """every row against the definition on `sig`; -> worst error / bound over the rows that hold signal"""
     worst = 0.0
     m = MODES.index(mode)
     for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        rate = tgm._rate(p, n)
+        ix = cg.ref(n)[0]
+        rate = cg.rate(p, n)
         j_all = aref.out_length(ix.samples, ix.rate, rate)
         assert int(valid[i]) == ref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
         s0, y = sig[i]
@@ -108,13 +77,6 @@ def _check(clips, sig, got, valid, f, p, mode, floor=1e-10):
     return worst
 
 
-def _starts(name, p, f):
-    """at 0, a small odd number, mid-stream, across the end and behind it"""
-    ix = tga._ref(name)[0]
-    j_all = aref.out_length(ix.samples, ix.rate, tgm._rate(p, name))
-    return [0, 57, j_all // 3 + 11, max(j_all - (f // 2) * p["hop"] - 3, 0), j_all + 3]
-
-
 CASES = {
     "a-22k-c1-84-stereo": (PA, ["22k", "48k", "mixed/mono-stereo"], 20, "tile16-static", 4, 6),
     "b-48k-own-rate-96-bins": (PB, ["48k"], 18, "tile16-static", 6, 6),
@@ -129,10 +91,10 @@ CASES = {
 def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, names, f, path, n_split, n_tiles = CASES[case]
-    rate = tgm._rate(p, names[0])
-    assert all(tgm._rate(p, n) == rate for n in names)
+    rate = cg.rate(p, names[0])
+    assert all(cg.rate(p, n) == rate for n in names)
     if case[0] == "a":
-        assert tga._ref("22k")[0].rate == 22050 and tga._ref("48k")[0].rate == 48000
+        assert cg.ref("22k")[0].rate == 22050 and cg.ref("48k")[0].rate == 48000
     if case[0] == "b":
         assert rate == 48000 and 2 * api.cqt_lengths(rate, **_shape(p))[1][0] + 1 == 29783 and api.cqt_plan(rate, hop=p["hop"], **_shape(p))[2] == 153632
     if case[0] == "d":
@@ -145,7 +107,7 @@ def test_against_binary64_on_the_products_own_signal(case):
     assert f > tile                                                          # (a tile edge inside the clip)
     clips = [(n, s) for n in names for s in _starts(n, p, f)]
     SEEN.update(im=False, swap=False)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         for mode in MODES:
@@ -165,7 +127,7 @@ def test_mode_0_rederives_the_others_bit_for_bit():
     1's, bit for bit: a transposed frame, a swapped bin or a mixed pair would show"""
     import clip_stft_ref as sref
     f, clips = 19, [("48k", 4321), ("22k", 0)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         z, _ = _run(dec, "device", clips, f, PA, "complex")
         power, _ = _run(dec, "device", clips, f, PA, "power")
@@ -186,7 +148,7 @@ def test_frames_are_frames_and_slices_of_a_batch_are_slices():
     name, start = "48k", 4321
     assert start % p["hop"] != 0
     tile = api.cqt_plan(22050, hop=p["hop"], **_shape(p))[0]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         fs = [0, 1, tile - 1, tile, tile + 1, tile + 4]
         f_long = tile + 6
@@ -209,10 +171,10 @@ def test_frames_are_frames_and_slices_of_a_batch_are_slices():
 
 def test_clips_wholly_behind_the_end():
     p, f, name = PC, 18, "32k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, 16000)
     h0 = int(ref.lengths(16000, **_shape(p))[2][0])
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         stats = dec.clip_stats()
         clips = [(name, j_all + h0), (name, j_all + 10 ** 6), (name, 2 ** 40)]
@@ -237,40 +199,40 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         for kind, mode in (("device", "complex"), ("numpy", "log10")):
             per = nb * f * (2 if mode == "complex" else 1)
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tgs._destination(kind, 3, 1, nb, f, mode)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, calls.stft_inner(nb, f, mode))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_cqt(src, f, mode=mode, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape((2, 1, nb, f, 2) if mode == "complex" else (2, 1, nb, f))
                 _check(good, sig, got, e.value.valid[[0, 2]], f, p, mode)
         # bad arguments: nothing is written
-        big, view = tgs._destination("device", 1, 1, nb, f, "log10")
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, calls.stft_inner(nb, f, "log10"))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         for bad_p in (dict(hop=0), dict(hop=8193), dict(fmin=0.0), dict(fmin=7600.0), dict(fmin=5.0), dict(bins_per_octave=0), dict(bins_per_octave=97),
                       dict(filter_scale=0.0), dict(filter_scale=float("nan")), dict(norm=3), dict(scale=-1), dict(floor=0.0), dict(width=65)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_cqt(src, f, mode="log10", out=view, **dict(p, **bad_p))
-            assert (tga._host(big) == SENT).all(), bad_p
+            assert (cg.host(big) == SENT).all(), bad_p
         with pytest.raises(RuntimeError):
             dec.decode_clips_cqt(src, f, mode=7, out=view, **p)
         with pytest.raises(RuntimeError):
-            dec.decode_clips_cqt([(s["48k"], tga._ref("48k")[0], -1)], f, mode="log10", out=view, **p)
+            dec.decode_clips_cqt([(s["48k"], cg.ref("48k")[0], -1)], f, mode="log10", out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_cqt(src + [(s["32k"], tga._ref("32k")[0], 0)], f, mode="log10", **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_cqt(src + [(s["32k"], cg.ref("32k")[0], 0)], f, mode="log10", **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -281,25 +243,25 @@ def test_more_clips_than_one_grid():
     time from descriptor 32 768 on.  Sixty-four distinct clips are held against the definition, every row is bit-equal to its
     twin among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k, f, p = "8k", 32768 + 5, 40, PD
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 9, j_all - 5]
     assert starts[61] + f + 16 < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         sig = _signal(dec, first, f, p)
         base, valid64 = _run(dec, "device", first, f, p, "magnitude")
         assert 0.0 < _check(first, sig, base, valid64, f, p, "magnitude") <= 1.0
         assert list(valid64[61:]) == [f, 0, 5]
-        big, view = tgs._destination("device", k, 1, p["n_bins"], f, "magnitude")
+        big, view = cg.destination("device", k, 1, (p["n_bins"], f))
         out, valid = dec.decode_clips_cqt([(mp3, ix, int(starts[t])) for t in twin], f, mode="magnitude", out=view, **p)
         per = p["n_bins"] * f
-        host = tga._host(big).reshape(k, per + GUARD)
+        host = cg.host(big).reshape(k, per + GUARD)
         assert (host[:, per:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 5, f, f, f]
         same = (host[:, :per].view(np.uint32) == base[twin].reshape(k, per).view(np.uint32)).all(axis=1)
@@ -314,20 +276,20 @@ def test_one_decoder_through_this_call_the_other_calls_and_this_call_again():
     """this call, decode_clips_stft, decode_clips_mel_long, decode_clips_audio, this call with another spec and with more specs
     than the decoder keeps tables -- and all of it again: every call is bit-equal to its first answer"""
     small = [("48k", 500), ("22k", 1234)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         def round_():
             out = []
             out.append(_run(dec, "device", small, 9, PC, "complex"))
-            out.append(tgs._run(dec, "device", small, 9, tgs.P16, "complex"))
+            out.append(calls.stft_run(dec, "device", small, 9, cases.STFT_P16, "complex"))
             pl = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=64, scale="slaney", norm="slaney", channels=1)
-            out.append(dec.decode_clips_mel_long([(tga._streams()[n], tga._ref(n)[0], s) for n, s in small], 9, mode="log10", **pl))
-            out.append(tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1))
+            out.append(dec.decode_clips_mel_long([(cg.streams()[n], cg.ref(n)[0], s) for n, s in small], 9, mode="log10", **pl))
+            out.append(calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1))
             out.append(_run(dec, "device", small, 9, dict(PC, norm=1, scale=1), "complex"))
             for i in range(5):                                                   # (more tables than the decoder keeps)
                 out.append(_run(dec, "device", small, 3, dict(PC, fmin=1000.0 + 10.0 * i), "power"))
             out.append(_run(dec, "numpy", small, 9, PC, "complex"))
-            return [(tga._host(a), v) for a, v in out]
+            return [(cg.host(a), v) for a, v in out]
         one, two = round_(), round_()
         assert len(one) == len(two)
         for (a, va), (b, vb) in zip(one, two):
@@ -344,18 +306,18 @@ def test_one_decoder_through_this_call_the_other_calls_and_this_call_again():
 
 def test_return_types_and_empty_calls():
     import torch
-    src = [(tga._streams()["22k"], tga._ref("22k")[0], 1000)]
-    dec = tga._decoder()
+    src = [(cg.streams()["22k"], cg.ref("22k")[0], 1000)]
+    dec = cg.decoder()
     try:
         out, valid = dec.decode_clips_cqt(src, 17)                              # the defaults: 22 050 Hz, C1, 84 bins, magnitude
         assert tuple(out.shape) == (1, 1, 84, 17) and out.is_cuda and out.dtype == torch.float32 and valid[0] == 17
         p = dict(PA, channels=1)
         sig = _signal(dec, [("22k", 1000)], 17, p)
-        _check([("22k", 1000)], sig, tga._host(out), valid, 17, p, "magnitude")
+        _check([("22k", 1000)], sig, cg.host(out), valid, 17, p, "magnitude")
         z, _ = dec.decode_clips_cqt(src, 17, mode="complex")
         assert tuple(z.shape) == (1, 1, 84, 17) and z.dtype == torch.complex64
         plain, _ = _run(dec, "device", [("22k", 1000)], 17, p, "complex")
-        assert np.array_equal(tga._host(torch.view_as_real(z)).view(np.uint32), plain.view(np.uint32))
+        assert np.array_equal(cg.host(torch.view_as_real(z)).view(np.uint32), plain.view(np.uint32))
         # a row at an odd float: the pairs' 8-byte stores are 4-byte aligned there, the values the same
         odd, _ = _run(dec, "device", [("22k", 1000)], 17, p, "complex", offset=1)
         assert np.array_equal(odd.view(np.uint32), plain.view(np.uint32))

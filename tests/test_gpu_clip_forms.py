@@ -4,7 +4,7 @@ grid launch of all five feature calls; DESIGN.md section 10, "launch forms").
 The shapes are the EDGES tables of tests/clip_*_ref.py -- the geometries whose launch form, LDS layout or lane walk no speech
 front end reaches; tests/test_clip_forms_host.py holds their classes without a GPU -- and twelve seeded draws a call
 (tests/clip_forms_draws.py).  Every comparison is the one of test_gpu_clip_mel.py, _fbank.py, _mfcc.py and _stft.py, through
-their own helpers: the binary64 definition on the product's own decode_clips_audio signal, every value within the derived
+the same helpers: the binary64 definition on the product's own decode_clips_audio signal, every value within the derived
 binary32 bound, sentinel-filled destinations with guards, `valid` compared, and the worst error / bound over the rows that
 hold signal inside (0, 1].  No tolerance is introduced here.  Each device step runs once; the shapes at the plan's exact 64 KB
 edge run last in the file."""
@@ -17,18 +17,14 @@ import pytest
 import clip_audio_ref as aref
 import clip_fbank_ref as fref
 import clip_forms_draws as draws
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_mel_ref as mref
 import clip_mfcc_ref as cref
 import clip_stft_ref as sref
-import test_gpu_clip_audio as tga
-import test_gpu_clip_fbank as tgf
-import test_gpu_clip_mel as tgm
-import test_gpu_clip_mfcc as tgc
-import test_gpu_clip_stft as tgs
-import test_gpu_clip_stft_long as tgl
+from clip_gpu import GUARD, SENT
 
 pytestmark = pytest.mark.gpu
-SENT = tgm.SENT
 NOT_ARGUMENTS = ("stream", "modes", "mode")
 
 
@@ -37,7 +33,7 @@ def _arguments(e):
 
 
 def _j(name, rate):
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     return aref.out_length(ix.samples, ix.rate, rate or ix.rate)
 
 
@@ -54,19 +50,19 @@ def _whole_frame_starts(name, p, f):
 
 
 # ---- one call's edge shape, all its modes: (name of the case, frames) -> {label: worst error / bound} ----
-def _mel_case(dec, e, kinds=("device",), modes=tgm.MODES, n_clips=3):
+def _mel_case(dec, e, kinds=("device",), modes=calls.MEL_MODES, n_clips=3):
     from pdmp3_amd import api
     p, name = _arguments(e), e["stream"]
     tile, _, lds, classes = mref.form(p["n_fft"], p["hop"], p["n_mels"])
     assert api.mel_tile(p["n_fft"], p["hop"], p["n_mels"]) == (tile, (2 - p["hop"]) % 32, lds)
     f = tile + 3
     clips = [(name, s) for s in _centred_starts(name, p, f)[:n_clips]]
-    sig = tgm._signal(dec, clips, f, p)
+    sig = cg.signal(dec, clips, f, p)
     out = {}
     for mode in modes:
         for kind in kinds:
-            got, valid = tgm._run(dec, kind, clips, f, p, mode)
-            worst = tgm._check(clips, sig, got, valid, f, p, mode)
+            got, valid = calls.mel_run(dec, kind, clips, f, p, mode)
+            worst = calls.mel_check(clips, sig, got, valid, f, p, mode)
             print("mel N %d H %d mels %d C %d (tile %d, LDS %d, %s), mode %s, %s: worst error / bound %.4f over %d clips of %d frames"
                   % (p["n_fft"], p["hop"], p["n_mels"], p["channels"], tile, lds, " ".join(sorted(classes)), mode, kind, worst, len(clips), f))
             assert 0.0 < worst <= 1.0
@@ -79,18 +75,18 @@ def _mel_case(dec, e, kinds=("device",), modes=tgm.MODES, n_clips=3):
 def _fbank_case(dec, e, kinds=("device",), variants=({}, fref.WITH_EVERYTHING), n_clips=3):
     from pdmp3_amd import api
     p0, name = _arguments(e), e["stream"]
-    nw, n, hop, nm = p0["win_length"], tgf._n(p0), p0["hop"], p0["num_mel_bins"]
+    nw, n, hop, nm = p0["win_length"], calls.fbank_n(p0), p0["hop"], p0["num_mel_bins"]
     tile, _, lds, classes = fref.form(nw, n, hop, nm)
     assert api.fbank_tile(nw, n, hop, nm) == (tile, (2 - hop) % 32, lds)
     f = tile + 3
     clips = [(name, s) for s in _whole_frame_starts(name, p0, f)[:n_clips]]
-    sig = tgf._signal(dec, clips, f, p0)
+    sig = calls.fbank_signal(dec, clips, f, p0)
     out = {}
     for extra in variants:
         p = dict(p0, **extra)
         for kind in kinds:
-            got, valid = tgf._run(dec, kind, clips, f, p)
-            worst = tgf._check(clips, sig, got, valid, f, p)
+            got, valid = calls.fbank_run(dec, kind, clips, f, p)
+            worst = calls.fbank_check(clips, sig, got, valid, f, p)
             print("fbank Nw %d N %d H %d mels %d C %d (tile %d, LDS %d, %s), %s, %s: worst error / bound %.4f over %d clips of %d frames"
                   % (nw, n, hop, nm, p["channels"], tile, lds, " ".join(sorted(classes)), "plain" if not extra else "energy mean htk", kind, worst,
                      len(clips), f))
@@ -104,16 +100,16 @@ def _fbank_case(dec, e, kinds=("device",), variants=({}, fref.WITH_EVERYTHING), 
 def _mfcc_case(dec, e, kinds=("device",), n_clips=3):
     from pdmp3_amd import api
     p, name = _arguments(e), e["stream"]
-    nw, n, hop, nm, nc = p["win_length"], tgf._n(p), p["hop"], p["num_mel_bins"], p["num_ceps"]
+    nw, n, hop, nm, nc = p["win_length"], calls.fbank_n(p), p["hop"], p["num_mel_bins"], p["num_ceps"]
     tile, _, lds, classes = cref.form(nw, n, hop, nm, nc)
     assert api.mfcc_tile(nw, n, hop, nm, nc) == (tile, (2 - hop) % 32, lds)
     f = tile + 3
     clips = [(name, s) for s in _whole_frame_starts(name, p, f)[:n_clips]]
-    sig = tgf._signal(dec, clips, f, p)
+    sig = calls.fbank_signal(dec, clips, f, p)
     out = {}
     for kind in kinds:
-        got, valid = tgc._run(dec, kind, clips, f, p)
-        worst = tgc._check(clips, sig, got, valid, f, p)
+        got, valid = calls.mfcc_run(dec, kind, clips, f, p)
+        worst = calls.mfcc_check(clips, sig, got, valid, f, p)
         print("mfcc Nw %d N %d H %d mels %d ceps %d C %d (tile %d, LDS %d, %s), %s: worst error / bound %.4f over %d clips of %d frames"
               % (nw, n, hop, nm, nc, p["channels"], tile, lds, " ".join(sorted(classes)), kind, worst, len(clips), f))
         assert 0.0 < worst <= 1.0
@@ -123,20 +119,20 @@ def _mfcc_case(dec, e, kinds=("device",), n_clips=3):
     return out
 
 
-def _stft_case(dec, e, kinds=("device",), modes=tgs.MODES, n_clips=3):
+def _stft_case(dec, e, kinds=("device",), modes=calls.STFT_MODES, n_clips=3):
     from pdmp3_amd import api
     p, name = _arguments(e), e["stream"]
     forms = {m: sref.form(p["n_fft"], p["hop"], sref.MODES[m]) for m in modes}
     f = max(t for t, _, _, _ in forms.values()) + 3                        # (one signal for all modes: the larger tile's frames)
     clips = [(name, s) for s in _centred_starts(name, p, f)[:n_clips]]
-    sig = tgm._signal(dec, clips, f, p)
+    sig = cg.signal(dec, clips, f, p)
     out = {}
     for mode in modes:
         tile, pad, lds, classes = forms[mode]
         assert api.stft_tile(p["n_fft"], p["hop"], mode) == (tile, pad, lds)
         for kind in kinds:
-            got, valid = tgs._run(dec, kind, clips, f, p, mode)
-            worst = tgs._check(clips, sig, got, valid, f, p, mode)
+            got, valid = calls.stft_run(dec, kind, clips, f, p, mode)
+            worst = calls.stft_check(clips, sig, got, valid, f, p, mode)
             print("stft N %d H %d Nw %s C %d (tile %d, LDS %d, %s), mode %s, %s: worst error / bound %.4f over %d clips of %d frames"
                   % (p["n_fft"], p["hop"], p.get("win_length"), p["channels"], tile, lds, " ".join(sorted(classes)), mode, kind, worst, len(clips), f))
             assert 0.0 < worst <= 1.0
@@ -163,7 +159,7 @@ def test_the_tables_are_run_whole():
 @pytest.mark.parametrize("call,name", EDGE_IDS, ids=["%s-%s" % i for i in EDGE_IDS])
 def test_edge_shapes_against_binary64_on_the_products_own_signal(call, name):
     run, module = RUNNERS[call]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         run(dec, module.EDGES[name], ("device", "numpy") if NUMPY_TOO[call] == name else ("device",))
     finally:
@@ -190,19 +186,19 @@ def test_frames_are_frames_across_the_edges_of_a_tile_of_16_in_dynamic_lds(call)
     fs = _frames(tile)
     f_long = 2 * tile + 1
     shorts = [(name, start + f * p["hop"]) for f in fs]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         if call == "mel":
-            pairs = [(tgm._run(dec, "device", [(name, start)], f_long, p, m)[0], tgm._run(dec, "device", shorts, 1, p, m)[0]) for m in tgm.MODES[:3]]
+            pairs = [(calls.mel_run(dec, "device", [(name, start)], f_long, p, m)[0], calls.mel_run(dec, "device", shorts, 1, p, m)[0]) for m in calls.MEL_MODES[:3]]
             pick = lambda a, f: a[:, :, f]                                  # [c, n_mels, f]
         elif call == "stft":
             pairs = []
-            for m in tgs.MODES[:3]:
+            for m in calls.STFT_MODES[:3]:
                 assert sref.form(p["n_fft"], p["hop"], sref.MODES[m])[:1] == (16,)
-                pairs.append((tgs._run(dec, "device", [(name, start)], f_long, p, m)[0], tgs._run(dec, "device", shorts, 1, p, m)[0]))
+                pairs.append((calls.stft_run(dec, "device", [(name, start)], f_long, p, m)[0], calls.stft_run(dec, "device", shorts, 1, p, m)[0]))
             pick = lambda a, f: a[:, :, f]                                  # [c, bins, f(, 2)]
         else:
-            run = tgf._run if call == "fbank" else tgc._run
+            run = calls.fbank_run if call == "fbank" else calls.mfcc_run
             pairs = [(run(dec, "device", [(name, start)], f_long, p)[0], run(dec, "device", shorts, 1, p)[0])]
             pick = lambda a, f: a[:, f]                                     # [c, f, d]
         for long, short in pairs:
@@ -221,11 +217,11 @@ def test_stft_mode_0_rederives_the_others_across_two_launch_forms():
     assert [sref.form(1024, 352, m)[0] for m in range(3)] == [16, 32, 32]
     f = 37
     clips = [(name, 4321), (name, 0)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        z, _ = tgs._run(dec, "device", clips, f, p, "complex")
-        power, _ = tgs._run(dec, "device", clips, f, p, "power")
-        mag, _ = tgs._run(dec, "device", clips, f, p, "magnitude")
+        z, _ = calls.stft_run(dec, "device", clips, f, p, "complex")
+        power, _ = calls.stft_run(dec, "device", clips, f, p, "power")
+        mag, _ = calls.stft_run(dec, "device", clips, f, p, "magnitude")
         want = sref.power_as_the_product(z[..., 0], z[..., 1])
         assert np.array_equal(want.view(np.uint32), power.view(np.uint32))
         assert np.array_equal(np.sqrt(want).view(np.uint32), mag.view(np.uint32))
@@ -241,10 +237,10 @@ def test_a_seeded_sweep(call):
     filterbank holds no bin is skipped and counted: at most 2 of 12"""
     run = RUNNERS[call][0]
     skipped = 0
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for p in draws.draw(call):
-            own = tga._ref(p["stream"])[0].rate
+            own = cg.ref(p["stream"])[0].rate
             if call != "stft" and draws.no_band_holds_a_bin(call, p, own):
                 skipped += 1
                 continue
@@ -277,11 +273,11 @@ def _audio_grid_wall():
     own rate: the same clips in a call of its own, not that test's own time (which has its reference in it)"""
     name, t, base = GRID_STREAM, 8, 50000
     offs = (np.arange(K_GRID, dtype=np.int64) * 37) % 4000
-    ix = tga._ref(name)[0]
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    ix = cg.ref(name)[0]
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
-        view = tga._destination("device", K_GRID, 1, t)[1]
+        view = cg.destination("device", K_GRID, 1, (t,))[1]
         t0 = time.perf_counter()
         dec.decode_clips_audio([(mp3, ix, int(base + o)) for o in offs], t, 0, 1, out=view)
         return time.perf_counter() - t0
@@ -302,14 +298,14 @@ def _grid(call, p, f, per, starts, first_rows, valid_of, mode=None):
     first_rows(clips, host rows [64, C, per], valid).  The five clips of the second launch have valid 0, 1 (the partial count of
     two frames) and f, and stand where the first launch had clips wholly inside the stream."""
     import torch
-    name, c, guard = GRID_STREAM, p["channels"], tgm.GUARD
+    name, c, guard = GRID_STREAM, p["channels"], GUARD
     assert len(starts) == PERIOD
     index = np.array([_grid_index(i) for i in range(K_GRID)])
     assert (index[:PERIOD] == np.arange(PERIOD)).all() and index[FIRST_GRID:].tolist() == list(range(SHIFT, SHIFT + K_GRID - FIRST_GRID))
     clips = [(name, starts[k]) for k in index]
-    mp3, ix = tga._streams()[name], tga._ref(name)[0]
+    mp3, ix = cg.streams()[name], cg.ref(name)[0]
     src = [(mp3, ix, s) for _, s in clips]
-    dec = tga._decoder()
+    dec = cg.decoder()
     t_all = time.perf_counter()
     try:
         big = torch.full((K_GRID, c, per + guard), float(SENT), dtype=torch.float32, device="cuda")
@@ -356,8 +352,8 @@ def test_more_clips_than_one_grid_mel():
     starts = _grid_starts([j - 17, j - 16, j - 1, j, j + 5, j + 1000])
 
     def check(dec, clips, host, valid, f):
-        sig = tgm._signal(dec, clips, f, p)
-        return tgm._check(clips, sig, host.reshape(PERIOD, 1, nm, f), valid, f, p, "whisper")
+        sig = cg.signal(dec, clips, f, p)
+        return calls.mel_check(clips, sig, host.reshape(PERIOD, 1, nm, f), valid, f, p, "whisper")
     _grid("mel", p, f, nm * f, starts, _Rows(lambda v, f: v.unflatten(2, (nm, f)), check), lambda s: mref.valid(j, s, 16, f), mode="whisper")
 
 
@@ -372,8 +368,8 @@ def test_more_clips_than_one_grid_fbank_and_mfcc(call):
     starts = _grid_starts([j - 33, j - 32, j - 31, j - 16, j - 15, j, j + 1000])
 
     def check(dec, clips, host, valid, f):
-        sig = tgf._signal(dec, clips, f, p)
-        return (tgf._check if call == "fbank" else tgc._check)(clips, sig, host.reshape(PERIOD, 1, f, d), valid, f, p)
+        sig = calls.fbank_signal(dec, clips, f, p)
+        return (calls.fbank_check if call == "fbank" else calls.mfcc_check)(clips, sig, host.reshape(PERIOD, 1, f, d), valid, f, p)
     _grid(call, p, f, f * d, starts, _Rows(lambda v, f: v.unflatten(2, (f, d)), check), lambda s: fref.valid(j, s, 16, 16, f))
 
 
@@ -384,8 +380,8 @@ def test_more_clips_than_one_grid_stft():
     starts = _grid_starts([j - 17, j - 16, j - 1, j, j + 5, j + 1000])
 
     def check(dec, clips, host, valid, f):
-        sig = tgm._signal(dec, clips, f, p)
-        return tgs._check(clips, sig, host.reshape(PERIOD, 1, nb, f, 2), valid, f, p, "complex")
+        sig = cg.signal(dec, clips, f, p)
+        return calls.stft_check(clips, sig, host.reshape(PERIOD, 1, nb, f, 2), valid, f, p, "complex")
     _grid("stft", p, f, nb * f * 2, starts, _Rows(lambda v, f: v.unflatten(2, (nb, f, 2)), check), lambda s: sref.valid(j, s, 16, f), mode="complex")
 
 
@@ -396,9 +392,9 @@ def test_more_clips_than_one_grid_stft_long():
     starts = _grid_starts([j - 1, j, j + 5, j + 5000])
 
     def check(dec, clips, host, valid, f):
-        sig = tgm._signal(dec, clips, f, p)
-        wants = tgl._wants(clips, sig, f, p)
-        return tgl._check(clips, sig, wants, host.reshape(PERIOD, 1, nb, f), valid, f, p, "power")
+        sig = cg.signal(dec, clips, f, p)
+        wants = calls.stft_long_wants(clips, sig, f, p)
+        return calls.stft_long_check(clips, sig, wants, host.reshape(PERIOD, 1, nb, f), valid, f, p, "power")
     _grid("stft_long", p, f, nb * f, starts, _Rows(lambda v, f: v.unflatten(2, (nb, f)), check), lambda s: sref.valid(j, s, 2048, f), mode="power")
 
 
@@ -409,7 +405,7 @@ def test_the_exact_64k_edge_of_the_plan(call, name):
     runtime refuses is an error return of the call, which the test reports; nothing is tried twice."""
     run, module = RUNNERS[call]
     e = module.EDGES[name]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         run(dec, e)
     finally:

@@ -9,22 +9,22 @@ transform's error remains: the medians bit for bit against np.sort on decode_cli
 clip, the masks on those medians within one rounding, the masked magnitudes and the masked spectrum bit for bit.
 Destinations are filled with a sentinel first.  Each device step runs once; a clip's reference is computed once.
 
-Streams and helpers: those of test_gpu_clip_audio.py and test_gpu_clip_mel.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import math
 
 import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_hpss_ref as href
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
+from clip_gpu import GUARD, SENT
+from clip_gpu_calls import mel_starts as _starts
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD = tgm.SENT, tgm.GUARD
-_starts, _rate = tgm._starts, tgm._rate
 INF = float("inf")
 FT = href.TILE_FRAMES
 
@@ -42,47 +42,16 @@ def _margins(p):
     return m if isinstance(m, tuple) else (m, m)
 
 
-def _destination(kind, k, c, inner):
-    """a sentinel-filled [k, c, floats of inner + GUARD] buffer and its [k, c] + inner view (rows and channels strided)"""
-    per = int(np.prod(inner))
-    strides = [1]
-    for n in reversed(inner[1:]):
-        strides.insert(0, strides[0] * n)
-    if kind == "device":
-        import torch
-        big = torch.full((k, c, per + GUARD), float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        return big, big.as_strided((k, c) + tuple(inner), (c * (per + GUARD), per + GUARD) + tuple(strides))
-    big = np.full((k, c, per + GUARD), SENT, dtype=np.float32)
-    return big, np.lib.stride_tricks.as_strided(big, (k, c) + tuple(inner), tuple(4 * s for s in (c * (per + GUARD), per + GUARD) + tuple(strides)))
-
-
-def _src(clips):
-    return [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-
-
 def _run(dec, kind, clips, f, p, mode="mask"):
     """clips: (stream name, start) -> (host copy [k, c, 2, K, f] (complex: [.., 2]), valid)"""
-    k, c, nb = len(clips), p["channels"], p["n_fft"] // 2 + 1
-    inner = (2, nb, f, 2) if mode == "complex" else (2, nb, f)
-    per = int(np.prod(inner))
-    big, view = _destination(kind, k, c, inner)
-    out, valid = dec.decode_clips_hpss(_src(clips), f, mode=mode, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :per].reshape((k, c) + inner), valid
+    nb = p["n_fft"] // 2 + 1
+    return cg.run(dec, "decode_clips_hpss", kind, clips, f, p["channels"], (2, nb, f, 2) if mode == "complex" else (2, nb, f), mode=mode, **p)
 
 
 def _signal(dec, clips, f, p):
     """the binary32 samples the widened clips' frames read, from the product's own audio call: per clip (s0, y [C, T])"""
-    n_fft, hop, c, rh = p["n_fft"], p["hop"], p["channels"], p["kernel_size"][0] // 2
-    t = (f + 2 * rh - 1) * hop + n_fft
-    rate = _rate(p, clips[0][0])
-    s0 = [max(0, s - rh * hop - n_fft // 2) for _, s in clips]
-    y = np.full((len(clips), c, t), SENT, dtype=np.float32)
-    dec.decode_clips_audio([(tga._streams()[n], tga._ref(n)[0], a) for (n, _), a in zip(clips, s0)], t, rate, c, out=y)
-    return list(zip(s0, y))
+    rh = p["kernel_size"][0] // 2
+    return cg.signal(dec, clips, f, p, front=rh, back=rh)
 
 
 def _wants(clips, sig, f, p):
@@ -96,8 +65,8 @@ def _check(clips, wants, got, valid, f, p):
     """every mask against the definition -> (worst error / bound, loose elements, elements)"""
     worst, loose, total = 0.0, 0, 0
     for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
+        ix = cg.ref(n)[0]
+        j_all = aref.out_length(ix.samples, ix.rate, cg.rate(p, n))
         assert int(valid[i]) == href.sref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
         w, l, t = href.check_masks(got[i], wants[i], p["power"])
         print("  %s at %d: worst error / bound %.4f, %d of %d elements %s" % (n, s, w, l, t, "undecided" if math.isinf(p["power"]) else "with the trivial bound"))
@@ -120,7 +89,7 @@ def test_against_binary64_on_the_products_own_signal(case):
     p, name, f = CASES[case]
     assert FT < f < 2 * FT and api.hpss_plan(*p["kernel_size"])[2:4] == (64, FT) and (p["n_fft"] // 2 + 1) % 64 == 1
     clips = [(name, s) for s in _starts(name, p, f)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         wants = _wants(clips, sig, f, p)
@@ -143,14 +112,14 @@ def test_the_sharp_check_on_the_spectrum_calls_own_output(p):
     complex output, bit for bit.  The starts are rh hop and later: the spectrum call takes no clip that begins before the stream"""
     name, f = "48k", 96
     (lh, lp), rh, hop = p["kernel_size"], p["kernel_size"][0] // 2, p["hop"]
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     clips = [(name, s) for s in (rh * hop, rh * hop + 57, ix.samples // 3 + 11, ix.samples - 40 * hop - 3, ix.samples + rh * hop + 3)]
-    wide = _src([(n, s - rh * hop) for n, s in clips])
+    wide = cg.src([(n, s - rh * hop) for n, s in clips])
     long = dict(sample_rate=0, n_fft=p["n_fft"], hop=hop, channels=p["channels"])
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        mag = tga._host(dec.decode_clips_stft_long(wide, f + 2 * rh, mode="magnitude", **long)[0])              # [k, c, K, f + 2 rh]
-        cplx = tga._host(dec.decode_clips_stft_long(wide, f + 2 * rh, mode="complex", **long)[0])
+        mag = cg.host(dec.decode_clips_stft_long(wide, f + 2 * rh, mode="magnitude", **long)[0])              # [k, c, K, f + 2 rh]
+        cplx = cg.host(dec.decode_clips_stft_long(wide, f + 2 * rh, mode="complex", **long)[0])
         cplx = np.ascontiguousarray(cplx).view(np.float32).reshape(cplx.shape + (2,))
         med, valid = _run(dec, "device", clips, f, p, "median")
         hm, pm = href.medians(mag, lh, lp)
@@ -187,7 +156,7 @@ def test_frames_are_frames(p):
     fs = [0, 1, FT - 1, FT, FT + 1, 2 * FT - 1, 2 * FT, 2 * FT + 2]
     f_long = 2 * FT + 4
     q = dict(p, power=2.0)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         long, _ = _run(dec, "device", [(name, start)], f_long, q)
         short, _ = _run(dec, "device", [(name, start + f * p["hop"]) for f in fs], 2, q)
@@ -202,7 +171,7 @@ def test_frames_are_frames(p):
 def test_slices_of_a_batch_are_the_batchs_slices():
     p, f = dict(PB, sample_rate=16000), 11
     clips = [(n, s) for n in ("48k", "22k", "16k-mono") for s in (0, 5000, 23457)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         whole, valid = _run(dec, "device", clips, f, p)
         for a, b in ((0, 1), (2, 5), (4, 9), (8, 9)):
@@ -219,31 +188,31 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
     nb = p["n_fft"] // 2 + 1
     per = 2 * nb * f
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         wants = _wants(good, sig, f, p)
         for kind in ("device", "numpy"):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, (2, nb, f))
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, (2, nb, f))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_hpss(src, f, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape(2, 1, 2, nb, f)
                 worst, loose, total = _check(good, wants, got, e.value.valid[[0, 2]], f, p)
                 assert loose <= href.CAP * total
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, (2, nb, f))
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, (2, nb, f))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         nan_window = np.ones(2048, dtype=np.float32)
         nan_window[123] = np.nan
         nan = float("nan")
@@ -260,25 +229,25 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
             else:
                 with pytest.raises(RuntimeError):
                     dec.decode_clips_hpss(src, f, out=view, **q)
-            assert (tga._host(big) == SENT).all(), bad_p
+            assert (cg.host(big) == SENT).all(), bad_p
         for bad_mode in (4, -1, "power"):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_hpss(src, f, out=view, mode=bad_mode, **p)
         with pytest.raises(RuntimeError):
             dec.decode_clips_hpss(src, -1, **p)
         with pytest.raises(RuntimeError):
-            dec.decode_clips_hpss([(s["48k"], tga._ref("48k")[0], -1)], f, out=view, **p)
+            dec.decode_clips_hpss([(s["48k"], cg.ref("48k")[0], -1)], f, out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_hpss(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+            dec.decode_clips_hpss(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
         # a row of the output beyond 2^31 - 1 floats, straight at the library: refused, nothing written
         import ctypes as C
         a8 = api._as_u8(s["48k"])
-        arr = (api._AudioClip * 1)(api._AudioClip(a8.ctypes.data, len(s["48k"]), tga._ref("48k")[0].h, 0, view.data_ptr(), 0))
+        arr = (api._AudioClip * 1)(api._AudioClip(a8.ctypes.data, len(s["48k"]), cg.ref("48k")[0].h, 0, view.data_ptr(), 0))
         got = (C.c_longlong * 1)()
         for mode, frames in ((0, 2 ** 31 // 2050 + 1), (2, 2 ** 31 // 4100 + 1), (3, 2 ** 40)):
             spec, keep = api._hpss_spec(frames, 16000, channels=1, mode=mode)
             assert dec.lib.pdmp3_amd_bulk_decode_clips_hpss(dec.h, arr, 1, C.byref(spec), got) == -1, (mode, frames)
-        assert (tga._host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -288,11 +257,11 @@ def test_clips_wholly_behind_the_end_return_types_and_empty_calls():
     import torch
     p, f = PA, 5
     name = "48k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     clips = [(name, j_all + 5 * p["n_fft"] + 15 * p["hop"]), (name, j_all + 1000000)]
     nb = p["n_fft"] // 2 + 1
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, p)
         assert (valid == 0).all() and (got == np.float32(0.5)).all()                 # margins 1, a finite power: exactly 0.5
@@ -303,13 +272,13 @@ def test_clips_wholly_behind_the_end_return_types_and_empty_calls():
         for mode in ("magnitude", "complex", "median"):
             got, valid = _run(dec, "numpy", clips, f, p, mode)
             assert (valid == 0).all() and (got.view(np.uint32) == 0).all(), mode
-        out, valid = dec.decode_clips_hpss(_src(clips), f, sample_rate=0)
+        out, valid = dec.decode_clips_hpss(cg.src(clips), f, sample_rate=0)
         assert tuple(out.shape) == (2, 2, 2, nb, f) and out.is_cuda and out.dtype == torch.float32 and (valid == 0).all()
-        out, valid = dec.decode_clips_hpss(_src(clips), f, sample_rate=0, mode="complex")
+        out, valid = dec.decode_clips_hpss(cg.src(clips), f, sample_rate=0, mode="complex")
         assert tuple(out.shape) == (2, 2, 2, nb, f) and out.is_cuda and out.dtype == torch.complex64 and (valid == 0).all()
         out, valid = dec.decode_clips_hpss([], 10)
         assert tuple(out.shape) == (0, 1, 2, nb, 10) and valid.size == 0
-        out, valid = dec.decode_clips_hpss(_src(clips), 0, sample_rate=0, n_fft=4096, channels=1)
+        out, valid = dec.decode_clips_hpss(cg.src(clips), 0, sample_rate=0, n_fft=4096, channels=1)
         assert tuple(out.shape) == (2, 1, 2, 2049, 0) and (valid == 0).all()
     finally:
         dec.close()
@@ -323,26 +292,26 @@ def test_more_clips_than_one_grid():
     name, k = "32k", 32768 + 5
     p = dict(sample_rate=0, n_fft=2048, hop=2048, channels=1, kernel_size=(3, 3), power=2.0)
     nb = 1025
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     starts = [3000 + 3001 * i for i in range(62)] + [j_all + 7, j_all - 1]
     assert starts[61] + 2 * 2048 < j_all and starts[0] >= 2048
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         base, valid64 = _run(dec, "device", first, 1, p, "median")
-        mag = tga._host(dec.decode_clips_stft_long(_src([(n, s - 2048) for n, s in first]), 3, mode="magnitude", sample_rate=0, n_fft=2048, hop=2048,
+        mag = cg.host(dec.decode_clips_stft_long(cg.src([(n, s - 2048) for n, s in first]), 3, mode="magnitude", sample_rate=0, n_fft=2048, hop=2048,
                                                    channels=1)[0])
         hm, pm = href.medians(mag, 3, 3)
         assert np.array_equal(base[:, :, 0].view(np.uint32), hm.view(np.uint32)) and np.array_equal(base[:, :, 1].view(np.uint32), pm.view(np.uint32))
         assert list(valid64[61:]) == [1, 0, 1]
-        big, view = _destination("device", k, 1, (2, nb, 1))
+        big, view = cg.destination("device", k, 1, (2, nb, 1))
         out, valid = dec.decode_clips_hpss([(mp3, ix, int(starts[t])) for t in twin], 1, mode="median", out=view, **p)
-        host = tga._host(big)
+        host = cg.host(big)
         assert (host[:, :, 2 * nb:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 1, 1, 1, 1]
         bad = np.flatnonzero((host[:, 0, :2 * nb].view(np.uint32) != base[twin, 0].reshape(k, 2 * nb).view(np.uint32)).any(axis=1))
@@ -356,19 +325,17 @@ def test_one_decoder_through_this_call_the_other_calls_and_this_call_again():
     """the new call, decode_clips_stft_long, decode_clips_mel_long, decode_clips_audio, the new call with other parameters and
     with the other n_fft -- and all of it again: every call is bit-equal to its first answer; the transform's tables are shared
     with the spectrum and the log-mel call, the stage with the tempogram call"""
-    import test_gpu_clip_mel_long as tgml
-    import test_gpu_clip_stft_long as tgl
     small = [("32k", 500), ("8k", 1234)]
     pa = dict(PA, sample_rate=16000, channels=1)
     pb = dict(pa, kernel_size=(5, 17), power=1.0, margin=(1.5, 1.0), win_length=1764, window=W1764)
     pc = dict(PC, sample_rate=16000)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         def once():
             return [_run(dec, "device", small, 9, pa),
-                    tgl._run(dec, "device", small, 9, dict(tgl.PA, sample_rate=16000, channels=1), "complex"),
-                    tgml._run(dec, "device", small, 9, dict(tgml.PA, sample_rate=16000, channels=1), "log10"),
-                    tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
+                    calls.stft_long_run(dec, "device", small, 9, dict(calls.STFT_LONG_PA, sample_rate=16000, channels=1), "complex"),
+                    calls.mel_long_run(dec, "device", small, 9, dict(calls.MEL_LONG_PA, sample_rate=16000, channels=1), "log10"),
+                    calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
                     _run(dec, "device", small, 9, pb, "complex"),
                     _run(dec, "numpy", small, 5, pc, "magnitude")]
         a, b = once(), once()

@@ -3,7 +3,7 @@ sections 18 and 19): k_loud_chain at the edges of its steps of 64 chunks, every 
 trip (more than 256 sub-blocks, waves, momentary blocks, short-term windows and range values), the ranking over thousands of
 values, and one clip of Jr = 4096.
 
-References as in tests/test_gpu_clip_loudness.py and tests/test_gpu_clip_r128.py, whose helpers run the calls here: the audio
+References as in tests/test_gpu_clip_loudness.py and tests/test_gpu_clip_r128.py, through the same helpers (tests/clip_gpu_calls.py): the audio
 call's rows measured in binary64 with the derived bounds.  The clip at the limit is 68 minutes long and is not measured whole:
 its first 300 s are held bit for bit to the same clip cut to 300 s (which is measured whole), its last 60 s to a reference
 restarted 2 s in front of them (clip_r128_ref.measure_from), and its gated numbers to the gates evaluated on its own curves
@@ -14,15 +14,14 @@ import functools
 import numpy as np
 import pytest
 
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_loudness_ref as lref
 import clip_r128_ref as ref
-import test_gpu_clip_audio as tga
-import test_gpu_clip_loudness as tgl
-import test_gpu_clip_r128 as tgr
+from clip_gpu import SENT
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT = tga.SENT
 FS, Q = 8000, 800
 GAINS = (152, 149, 146, 143, 140, 128, 90)          # global_gain of a segment: loud ones 4.5 dB apart, one 36 dB down, one under -70 LUFS
 R128 = dict(target=-23.0, peak_limit=10 ** (-1 / 20))
@@ -64,8 +63,8 @@ def _limit_stream():
     return _drawn_stream(56960, 3, 4096)
 
 
-tgl.STREAMS["long300"] = _long300_stream
-tgl.STREAMS["limit"] = _limit_stream
+cg.STREAMS["long300"] = _long300_stream
+cg.STREAMS["limit"] = _limit_stream
 
 
 @contextlib.contextmanager
@@ -86,7 +85,7 @@ def _sample_loop_in_c():
 
 
 def _same(a, b):
-    return np.array_equal(tgr._bits(a), tgr._bits(b))
+    return np.array_equal(cg.bits(a), cg.bits(b))
 
 
 def _moved_without_the_state(x, fs, at, m):
@@ -114,20 +113,20 @@ def test_the_chain_at_the_edges_of_its_steps(fs, t):
     stream gives: tests/test_clip_loudness_host.py holds it at 192 000 Hz with an offset in the signal.)  Every number
     against binary64"""
     import clip_audio_ref
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        ix = tgl._source("48k")[1]
+        ix = cg.source("48k")[1]
         n_all = clip_audio_ref.out_length(int(ix.samples), 48000, fs)
         assert ix.rate == 48000 and n_all > 64 * 4096
         end = 64 * 4096 - 1
         clips = [("48k", 0), ("48k", n_all - end)]
         q, n_chunks = lref.plan(fs, t)["q"], lref.plan(fs, t)["n_chunks"]
         assert n_chunks == {64 * 4096: 64, 64 * 4096 + 1: 65, 128 * 4096 + 1: 129}[t]
-        x, valid = tgl._signal(dec, clips, t, fs, 1, 1)
+        x, valid = calls.audio_rows(dec, clips, t, fs, 1, 1)
         assert valid[1] == end and (x[1, :, end:] == 0).all() and valid[0] == min(t, n_all)
-        got = tgl._run(dec, "device", clips, t, fs, 1)
+        got = calls.loudness_run(dec, "device", clips, t, fs, 1)
         with _sample_loop_in_c():
-            refs, worst, margin, undecided = tgl._check(x, valid, got, fs)
+            refs, worst, margin, undecided = calls.loudness_check(x, valid, got, fs)
         m = refs[1]
         print("chain edges: fs %d t %d, %d chunks, J %d, valid %s, worst error / bound %.3g" % (fs, t, n_chunks, m.J, list(valid), worst))
         assert 0.0 < worst <= 1.0 and not undecided and all(0 < r.nGt <= r.nA for r in refs) and m.J == t // q - 3
@@ -160,11 +159,11 @@ def test_more_than_256_blocks_windows_and_range_values(channels, length):
     starts = [0, 40 * FS + 333] if t < all_t else [0, 40 * FS + 333, all_t - 27 * FS - 5, all_t - 3 * FS // 2]
     clips = [("long300", s) for s in starts]
     p = ref.plan(FS, t)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        x, valid = tgr._signal(dec, clips, t, 0, channels, channels)
-        got = tgr._run(dec, "device", clips, t, 0, channels, **R128)
-        refs, worst, margin, undecided = tgr._check(x, valid, got, FS, **R128)
+        x, valid = calls.audio_rows(dec, clips, t, 0, channels, channels)
+        got = calls.r128_run(dec, "device", clips, t, 0, channels, **R128)
+        refs, worst, margin, undecided = calls.r128_check(x, valid, got, FS, **R128)
         m = refs[0]
         print("long300 c=%d t=%d: J %d Js %d Jr %d chunks %d |A| %d |Gt| %d |Ar| %d |Gr| %d LRA %.2f worst error / bound %.3g margin %.3g bounds" %
               (channels, t, m.J, m.Js, m.Jr, p["n_chunks"], m.nA, m.nGt, m.nAr, m.nGr, m.LRA, worst, m.r_margin_bounds))
@@ -176,12 +175,12 @@ def test_more_than_256_blocks_windows_and_range_values(channels, length):
         if length == "whole":
             assert m.Js > 256 and m.Jr > 256 and p["n_chunks"] > 9 * 64 and 0 < m.nGr < m.nAr < m.Jr and 0 < m.nGt < m.nA < m.J
             assert list(valid) == [all_t, all_t - 40 * FS - 333, 27 * FS + 5, 3 * FS // 2]
-        host = tgr._run(dec, "numpy", clips, t, 0, channels, **R128)
+        host = calls.r128_run(dec, "numpy", clips, t, 0, channels, **R128)
         for a, b in zip(got, host):
             assert _same(a, b)
         kw = dict(target=-14.0, peak_limit=0.5)
-        audio, stats, mom, st, v = tgr._run(dec, "device", clips, t, 0, channels, limit_true_peak=False, **kw)
-        want = tgl._run(dec, "device", clips, t, 0, channels, **kw)
+        audio, stats, mom, st, v = calls.r128_run(dec, "device", clips, t, 0, channels, limit_true_peak=False, **kw)
+        want = calls.loudness_run(dec, "device", clips, t, 0, channels, **kw)
         assert _same(audio, want[0]) and _same(stats[:, :8], want[1]) and _same(mom, want[2]) and np.array_equal(v, want[3])
         assert _same(mom, got[2]) and _same(st, got[3]) and (stats[:, 3] != 1.0).any()
     finally:
@@ -193,11 +192,11 @@ def test_a_shorter_clip_is_a_prefix_of_the_longer_one():
     rows, bit for bit -- every sum has one fixed order and nothing behind a block enters it (the host build shows the same:
     tests/test_clip_r128_host.py)"""
     all_t = _long300_length()
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for start in (0, 40 * FS + 333):
-            short = tgr._run(dec, "device", [("long300", start)], 27 * FS + 5, c=2, **R128)
-            whole = tgr._run(dec, "device", [("long300", start)], all_t, c=2, **R128)
+            short = calls.r128_run(dec, "device", [("long300", start)], 27 * FS + 5, c=2, **R128)
+            whole = calls.r128_run(dec, "device", [("long300", start)], all_t, c=2, **R128)
             J, Js = short[2].shape[1], short[3].shape[1]
             assert (J, Js) == (267, 241) and whole[2].shape[1] > 2900 and whole[3].shape[1] > 2900
             assert _same(short[2], whole[2][:, :J]) and _same(short[3], whole[3][:, :Js])
@@ -211,13 +210,13 @@ def test_windows_behind_the_streams_end_do_not_count():
     skipped by the ranking, whose loop still walks them.  |Ar| is the reference's, every field within its bound"""
     all_t = _long300_length()
     start = 40 * FS + 123
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         clips = [("long300", start)]
-        x, valid = tgr._signal(dec, clips, all_t, 0, 0, 2)
+        x, valid = calls.audio_rows(dec, clips, all_t, 0, 0, 2)
         assert valid[0] == all_t - start and (x[0, :, valid[0]:] == 0).all()
-        got = tgr._run(dec, "device", clips, all_t, c=2, **R128)
-        refs, worst, margin, undecided = tgr._check(x, valid, got, FS, **R128)
+        got = calls.r128_run(dec, "device", clips, all_t, c=2, **R128)
+        refs, worst, margin, undecided = calls.r128_check(x, valid, got, FS, **R128)
         m = refs[0]
         silent = int((got[3][0, ::10] < -150.0).sum())
         print("ties: Jr %d |Ar| %d |Gr| %d, %d windows of the range in silence, worst error / bound %.3g" % (m.Jr, m.nAr, m.nGr, silent, worst))
@@ -253,12 +252,12 @@ def _run_the_limit():
     r128 call with both curves.  Of the two rows of 131 MB only what the tests below look at is kept"""
     t = LIMIT_T
     clips = [("limit", 0)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         ix = _limit_stream()[1]
         assert ix.rate == FS and ix.channels == 1 and int(ix.samples) >= t
-        x, valid = tgr._signal(dec, clips, t, 0, 0, 1)
-        audio, stats, mom, st, v = tgr._run(dec, "device", clips, t, c=1, **R128)
+        x, valid = calls.audio_rows(dec, clips, t, 0, 0, 1)
+        audio, stats, mom, st, v = calls.r128_run(dec, "device", clips, t, c=1, **R128)
     finally:
         dec.close()
     c = _Limit()
@@ -294,12 +293,12 @@ def test_the_limits_first_300_s_are_the_clip_cut_there():
     once more, over 126 steps of the chain against 10); the cut clip is held to binary64 whole"""
     c = _limit_case()
     cut = c.head.shape[2]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        got = tgr._run(dec, "device", [("limit", 0)], cut, c=1, **R128)
+        got = calls.r128_run(dec, "device", [("limit", 0)], cut, c=1, **R128)
     finally:
         dec.close()
-    refs, worst, margin, undecided = tgr._check(c.head, np.array([cut]), got, FS, **R128)
+    refs, worst, margin, undecided = calls.r128_check(c.head, np.array([cut]), got, FS, **R128)
     m = refs[0]
     print("limit, cut to 300 s: Jr %d |Ar| %d |Gr| %d LRA %.2f worst error / bound %.3g margin %.3g bounds" % (m.Jr, m.nAr, m.nGr, m.LRA, worst, m.r_margin_bounds))
     assert 0.0 < worst <= 1.0 and not undecided and m.Jr > 256 and 0 < m.nGr < m.nAr < m.Jr and m.r_margin_bounds > 10.0
@@ -335,12 +334,12 @@ def test_the_limits_gated_numbers_are_the_gates_on_its_own_curves():
 def test_one_sample_more_than_the_limit_is_refused():
     t = LIMIT_T + 1
     p = ref.plan(FS, LIMIT_T)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         import torch
-        big, view = tga._destination("device", 1, 1, t)
-        mom, st = tgr._filled("device", (1, p["J"])), tgr._filled("device", (1, p["Js"]))
-        src = tgr._src([("limit", 0)])
+        big, view = cg.destination("device", 1, 1, (t,))
+        mom, st = cg.filled("device", (1, p["J"])), cg.filled("device", (1, p["Js"]))
+        src = cg.src([("limit", 0)])
         with pytest.raises(RuntimeError):
             dec.decode_clips_r128(src, t, 0, 1, out=view, momentary=mom, short_term=st, **R128)
         with pytest.raises(RuntimeError):

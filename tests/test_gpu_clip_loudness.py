@@ -12,13 +12,14 @@ import functools
 import numpy as np
 import pytest
 
+import clip_gpu as cg
 import clip_loudness_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
+from clip_gpu import GUARD, SENT
+from clip_gpu_calls import LOUDNESS_CASES as CASES, audio_rows as _signal, loud_rate as _fs, loudness_check as _check, loudness_run as _run
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD = tga.SENT, tga.GUARD
 BIG = 5 * ref.B * ref.CHUNK + ref.B + 5            # five scan chunks, a block and five samples: J >= 1 at every rate used
 
 
@@ -32,77 +33,7 @@ def _gate_stream():
     return mp3, api.StreamIndex(mp3, ISO_LSF)
 
 
-STREAMS = {"gate": _gate_stream}                   # name -> maker of (mp3, index); the other loudness test files add theirs
-
-
-def _source(name):
-    if name in STREAMS:
-        return STREAMS[name]()
-    return tga._streams()[name], tga._ref(name)[0]
-
-
-def _src(clips):
-    return [_source(n) + (s,) for n, s in clips]
-
-
-def _fs(clips, rate):
-    return rate or _source(clips[0][0])[1].rate
-
-
-def _run(dec, kind, clips, t, rate=0, channels=0, c=None, momentary=True, **kw):
-    """clips: (stream name, start) -> (audio [k, c, t], stats [k, 8], momentary [k, J] or None, valid), host copies"""
-    k = len(clips)
-    c = c or channels
-    J = ref.plan(_fs(clips, rate), t)["J"]
-    big, view = tga._destination(kind, k, c, t)
-    if kind == "device":
-        import torch
-        mom = torch.full((k + 1, J), float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-    else:
-        mom = np.full((k + 1, J), SENT, dtype=np.float32)
-    audio, stats, valid = dec.decode_clips_loudness(_src(clips), t, rate, channels, out=view, momentary=mom if momentary else None, **kw)
-    assert audio is view and tuple(stats.shape) == (k, 8) and hasattr(stats, "data_ptr") == (kind == "device")
-    host = tga._host(big)
-    assert (host[:, :, t:] == SENT).all(), "written behind a row's samples"
-    m = tga._host(mom)
-    assert (m[k] == SENT).all() and (momentary or (m == SENT).all()), "written behind the momentary rows"
-    return host[:, :, :t].copy(), np.array(tga._host(stats)), m[:k].copy() if momentary else None, valid
-
-
-def _signal(dec, clips, t, rate, channels, c):
-    big, view = tga._destination("device", len(clips), c, t)
-    out, valid = dec.decode_clips_audio(_src(clips), t, rate, channels, out=view)
-    return tga._host(big)[:, :, :t].copy(), valid
-
-
-def _check(x, want_valid, got, fs, **kw):
-    """rows x [k, c, t] of the audio call against the loudness call's (audio, stats, momentary, valid) -> (the references, worst
-    error / bound, smallest margin in dB, undecided clips)"""
-    audio, stats, mom, valid = got
-    assert np.array_equal(valid, want_valid)
-    refs, worst, margin, undecided = [], 0.0, np.inf, 0
-    for i in range(x.shape[0]):
-        m = ref.measure(x[i], fs, **kw)
-        refs.append(m)
-        worst = max(worst, ref.check_stats(m, stats[i], None if mom is None else mom[i]))
-        margin = min(margin, m.margin)
-        undecided += m.undecided
-        want = (x[i] * np.float32(stats[i, 3])).astype(np.float32)
-        assert np.array_equal(audio[i].view(np.uint32), want.view(np.uint32)), "clip %d: audio is not x * g" % i
-        assert np.float32(stats[i, 2]) == np.abs(x[i]).max()
-    assert undecided * 10 <= x.shape[0], "%d of %d clips undecided" % (undecided, x.shape[0])
-    print("worst error / bound %.3g, smallest gate margin %.3g dB, %d undecided of %d" % (worst, margin, undecided, x.shape[0]))
-    return refs, worst, margin, undecided
-
-
-CASES = {
-    # streams, rate, channels
-    "48k-32k-stereo-at-32000": (["48k", "32k"], 32000, 2),
-    "44k-mono-own-rate": (["44k-mono"], 0, 1),
-    "8k-own-rate": (["8k"], 0, 2),
-    "22k-at-16000-mono": (["22k"], 16000, 1),
-}
+cg.STREAMS["gate"] = _gate_stream
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -110,13 +41,13 @@ def test_against_binary64(case):
     """1.5 s and a length of five chunks, a block and five samples; starts 0, mid-stream and with the stream's end inside the
     clip; device and numpy destinations -- the reference of a length made once for both"""
     names, rate, channels = CASES[case]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         fs = _fs([(names[0], 0)], rate)
         for t in (fs * 3 // 2, BIG):
             clips = []
             for n in names:
-                ix = _source(n)[1]
+                ix = cg.source(n)[1]
                 j_all = ix.samples * fs // ix.rate
                 clips += [(n, 0), (n, j_all // 2 + 331), (n, j_all - t // 3)]
             x, valid = _signal(dec, clips, t, rate, channels, channels)
@@ -134,7 +65,7 @@ def test_against_binary64(case):
 @functools.lru_cache(maxsize=None)
 def _gate_case():
     """the whole gate stream at its own rate: (t, the audio call's rows, valid) -- made once"""
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         ix = _gate_stream()[1]
         t = int(ix.samples)
@@ -146,7 +77,7 @@ def _gate_case():
 
 def test_both_gates_bite():
     t, x, valid = _gate_case()
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         got = _run(dec, "device", [("gate", 0)], t, c=2)
         refs, worst, margin, undecided = _check(x, valid, got, 48000)
@@ -163,7 +94,7 @@ def test_no_target_is_the_audio_call_and_the_gain_is_in_stats():
     fs = 48000
     t = fs * 3 // 2
     clips = [("gate", 0), ("48k", 0), ("48k", 8 * fs)]       # (the last one: behind the stream's end)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         x, valid = _signal(dec, clips, t, 0, 0, 2)
         audio, stats, mom, v = _run(dec, "device", clips, t, c=2)
@@ -183,7 +114,7 @@ def test_order_and_batch_independence():
     fs, q = 32000, 3200
     t = 9 * q + 77
     clips = [("32k", 4321), ("48k", 100), ("32k", 150000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         one = _run(dec, "device", clips, t, fs, 2, target=-20.0)
         two = _run(dec, "device", clips, t, fs, 2, target=-20.0)
@@ -216,25 +147,25 @@ def test_behind_the_end_refusals_and_a_refused_clip_in_the_middle_of_a_batch():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("48k", 30000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         x, valid = _signal(dec, good, t, fs, 2, 2)
         for kind in ("device", "numpy"):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tga._destination(kind, 3, 2, t)
+                big, view = cg.destination(kind, 3, 2, (t,))
                 mom = np.full((3, J), SENT, dtype=np.float32)
                 if kind == "device":
                     import torch
                     mom = torch.full((3, J), float(SENT), dtype=torch.float32, device="cuda")
-                src = [_src(good)[0], mid, _src(good)[1]]
+                src = [cg.src(good)[0], mid, cg.src(good)[1]]
                 c0, h0 = dec.clip_stats()
                 with pytest.raises(exc) as e:
                     dec.decode_clips_loudness(src, t, fs, 2, target=-23.0, out=view, momentary=mom)
-                host, m, st = tga._host(big), tga._host(mom), np.array(tga._host(e.value.stats))
+                host, m, st = cg.host(big), cg.host(mom), np.array(cg.host(e.value.stats))
                 assert e.value.valid[1] == code and (host[1] == SENT).all() and (m[1] == SENT).all() and np.isnan(st[1]).all()
                 assert (host[:, :, t:] == SENT).all()
                 got = (host[[0, 2], :, :t], st[[0, 2]], m[[0, 2]], e.value.valid[[0, 2]])
@@ -250,19 +181,19 @@ def test_behind_the_end_refusals_and_a_refused_clip_in_the_middle_of_a_batch():
         c2, h2 = dec.clip_stats()
         assert (c2 - c1, h2 - h1) == (c1 - c0, h1 - h0)
         # bad arguments: nothing is written
-        big, view = tga._destination("device", 1, 2, t)
-        src = _src(good[:1])
+        big, view = cg.destination("device", 1, 2, (t,))
+        src = cg.src(good[:1])
         for kw in (dict(target=-70.5), dict(target=0.5), dict(target=float("inf")), dict(peak_limit=-1.0), dict(peak_limit=float("inf")),
                    dict(peak_limit=float("nan")), dict(dual_mono=True), dict(dual_mono=2), dict(width=65), dict(sample_rate=7999),
                    dict(sample_rate=192001)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_loudness(src, t, **dict(dict(sample_rate=fs, channels=2, out=view), **kw))
-            assert (tga._host(big) == SENT).all(), kw
+            assert (cg.host(big) == SENT).all(), kw
         with pytest.raises(RuntimeError):
-            dec.decode_clips_loudness([(s["48k"], tga._ref("48k")[0], -1)], t, fs, 2, out=view)
+            dec.decode_clips_loudness([(s["48k"], cg.ref("48k")[0], -1)], t, fs, 2, out=view)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_loudness(src + _src([("32k", 0)]), t)
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_loudness(src + cg.src([("32k", 0)]), t)
+        assert (cg.host(big) == SENT).all()
         # dual mono on a mono call: + 3.01 dB
         xm, vm = _signal(dec, good[:1], t, fs, 1, 1)
         got = _run(dec, "device", good[:1], t, fs, 1, dual_mono=True)
@@ -279,14 +210,14 @@ def test_more_clips_than_one_grid():
     extent), the second time from descriptor 32 768 on.  Sixty-four distinct clips are held against the definition, every row is
     bit-equal to its twin among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k, t = "8k", 32768 + 5, 3200
-    mp3, ix = _source(name)
+    mp3, ix = cg.source(name)
     assert ix.rate == 8000
     j_all = int(ix.samples)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 9, j_all - 5]
     assert starts[61] + t < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         x, valid64 = _signal(dec, first, t, 0, 1, 1)
@@ -313,8 +244,8 @@ def test_more_clips_than_one_grid():
 
 def test_return_types_defaults_and_empty_calls():
     import torch
-    src = _src([("48k", 1000)])
-    dec = tga._decoder()
+    src = cg.src([("48k", 1000)])
+    dec = cg.decoder()
     try:
         audio, stats, valid = dec.decode_clips_loudness(src, 30000)          # the stream's rate and channels, no target, no momentary
         assert tuple(audio.shape) == (1, 2, 30000) and audio.is_cuda and audio.dtype == torch.float32 and valid[0] == 30000
@@ -322,7 +253,7 @@ def test_return_types_defaults_and_empty_calls():
         plain, _ = dec.decode_clips_audio(src, 30000)
         assert torch.equal(audio.view(torch.int32), plain.view(torch.int32))
         got = _run(dec, "numpy", [("48k", 1000)], 30000, c=2)
-        assert np.array_equal(got[1].view(np.uint32), tga._host(stats).view(np.uint32)) and got[1][0, 5] == 3
+        assert np.array_equal(got[1].view(np.uint32), cg.host(stats).view(np.uint32)) and got[1][0, 5] == 3
         audio, stats, valid = dec.decode_clips_loudness([], 10, channels=1)
         assert tuple(audio.shape) == (0, 1, 10) and tuple(stats.shape) == (0, 8) and valid.size == 0
         audio, stats, valid = dec.decode_clips_loudness(src, 0, channels=1)

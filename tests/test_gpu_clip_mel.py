@@ -7,7 +7,7 @@ call's output has to agree within the binary32 bound derived there -- every valu
 in mode 0.  Destinations are filled with a sentinel first: nothing outside a row's n_mels * F floats may change.  Each device
 step runs once.
 
-Streams and helpers: those of test_gpu_clip_audio.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import ctypes as C
 import math
 
@@ -15,98 +15,17 @@ import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_mel_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
+from clip_forms_cases import MEL_CASES as CASES, MEL_P16 as P16, MEL_P24 as P24, MEL_P48 as P48
+from clip_gpu import GUARD, SENT, signal as _signal
+from clip_gpu_calls import MEL_MODES as MODES, mel_check as _check, mel_filterbank as _filterbank, mel_run as _run, mel_starts as _starts
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT = np.float32(-1234.5)
-GUARD = 24
 U = ref.U
-
-P16 = dict(sample_rate=16000, n_fft=400, hop=160, n_mels=80, scale="slaney", norm="slaney", channels=1)
-P24 = dict(sample_rate=24000, n_fft=512, hop=128, n_mels=128, scale="htk", norm=None, channels=2)
-P48 = dict(sample_rate=0, n_fft=1024, hop=1024, n_mels=40, scale="slaney", norm="slaney", channels=2)      # the own rate (the 48 kHz stream)
-MODES = ["power", "log", "log10", "whisper"]
-
-
-def _rate(p, name):
-    return p["sample_rate"] or tga._ref(name)[0].rate
-
-
-def _filterbank(p, name):
-    return ref.filterbank(_rate(p, name), p["n_fft"], p["n_mels"], p.get("f_min", 0.0), p.get("f_max", 0.0), p["scale"], p["norm"])
-
-
-def _destination(kind, k, c, nm, f, guard=GUARD):
-    """a sentinel-filled [k, c, nm * f + guard] buffer and its [k, c, nm, f] view (rows and channels strided)"""
-    per = nm * f
-    if kind == "device":
-        import torch
-        big = torch.full((k, c, per + guard), float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        return big, big.as_strided((k, c, nm, f), (c * (per + guard), per + guard, f, 1))
-    big = np.full((k, c, per + guard), SENT, dtype=np.float32)
-    return big, np.lib.stride_tricks.as_strided(big, (k, c, nm, f), (4 * c * (per + guard), 4 * (per + guard), 4 * f, 4))
-
-
-def _run(dec, kind, clips, f, p, mode, floor=1e-10):
-    """clips: (stream name, start) -> (host copy [k, c, nm, f], valid)"""
-    k, c, nm = len(clips), p["channels"], p["n_mels"]
-    big, view = _destination(kind, k, c, nm, f)
-    out, valid = dec.decode_clips_mel([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, mode=mode, floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:, :, nm * f:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :nm * f].reshape(k, c, nm, f), valid
-
-
-def _signal(dec, clips, f, p):
-    """the binary32 samples the clips' frames read, from the product's own audio call: per clip (s0, y [C, T])"""
-    n_fft, hop, c = p["n_fft"], p["hop"], p["channels"]
-    t = (f - 1) * hop + n_fft
-    rate = _rate(p, clips[0][0])
-    s0 = [max(0, s - n_fft // 2) for _, s in clips]
-    y = np.full((len(clips), c, t), SENT, dtype=np.float32)
-    dec.decode_clips_audio([(tga._streams()[n], tga._ref(n)[0], a) for (n, _), a in zip(clips, s0)], t, rate, c, out=y)
-    return list(zip(s0, y))
-
-
-def _check(clips, sig, got, valid, f, p, mode, floor=1e-10):
-    """every row against the definition on `sig`; -> worst error / bound over the rows that hold signal"""
-    worst = 0.0
-    m = MODES.index(mode)
-    for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
-        assert int(valid[i]) == ref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
-        s0, y = sig[i]
-        want, bound = ref.mel(y, s0, s, f, p["n_fft"], p["hop"], _filterbank(p, n), m, floor)
-        err = np.abs(got[i].astype(np.float64) - want)
-        assert (err <= bound).all(), "%s at %d, mode %s: error beyond the bound by %g at %s" % (
-            n, s, mode, float((err - bound).max()), np.unravel_index(np.argmax(err - bound), err.shape))
-        nz = bound > 0
-        if m == 0:
-            assert (got[i][~nz] == 0.0).all()
-        if np.abs(y).sum() > 0 and nz.any():        # (a start inside the first N / 2 samples: the span's last samples belong to no frame)
-            r = float((err[nz] / bound[nz]).max())
-            assert 0.0 < r <= 1.0, (n, s, mode, r)
-            worst = max(worst, r)
-    return worst
-
-
-def _starts(name, p, f):
-    ix = tga._ref(name)[0]
-    j_all = aref.out_length(ix.samples, ix.rate, _rate(p, name))
-    return [0, 57, j_all // 3 + 11, max(j_all - (f // 2) * p["hop"] - 3, 0), j_all + 3, j_all + 5 * p["n_fft"]]
-
-
-CASES = {
-    "16k-mono-batch": (P16, ["mixed/mono-stereo", "48k", "32k", "22k", "16k-mono", "8k"], 70),
-    "24k-stereo-htk": (P24, ["48k", "22k", "mixed/mono-stereo"], 45),
-    "own-rate-1024": (P48, ["48k"], 21),
-}
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
@@ -114,10 +33,10 @@ def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, names, f = CASES[case]
     if case == "16k-mono-batch":
-        assert set(tga._ref(n)[0].rate for n in names) == {44100, 48000, 32000, 22050, 16000, 8000}
+        assert set(cg.ref(n)[0].rate for n in names) == {44100, 48000, 32000, 22050, 16000, 8000}
     clips = [(n, s) for n in names for s in _starts(n, p, f)]
     tile = api.mel_tile(p["n_fft"], p["hop"], p["n_mels"])[0]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         for mode in MODES:
@@ -139,7 +58,7 @@ def test_slices_are_slices(p):
     assert start % p["hop"] != 0
     fs = [0, 1, tile - 1, tile, tile + 1, 2 * tile - 1, 2 * tile, 2 * tile + 1, 2 * tile + 5]
     f_long = 2 * tile + 7
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in MODES[:3]:
             long, _ = _run(dec, "device", [(name, start)], f_long, p, mode)
@@ -158,9 +77,9 @@ def test_edges_of_the_tile_and_of_the_stream():
     p = P16
     tile = api.mel_tile(p["n_fft"], p["hop"], p["n_mels"])[0]
     name = "32k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, 16000)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for f in (1, tile - 1, tile, tile + 1):
             clips = [(name, 777), (name, 0)]
@@ -209,10 +128,10 @@ def test_host_destinations():
     p, f = P16, 37
     clips = _host_clips(p, f)
     k, nm = len(clips), p["n_mels"]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
-        src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
+        src = cg.src(clips)
         flat = np.full(k * nm * f + GUARD, SENT, dtype=np.float32)
         dense = flat[:k * nm * f].reshape(k, 1, nm, f)
         out, valid = dec.decode_clips_mel(src, f, out=dense, **p)
@@ -244,35 +163,35 @@ def test_a_refused_clip_in_the_middle_of_a_batch():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         for kind in ("device", "numpy"):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, p["n_mels"], f)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, (p["n_mels"], f))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_mel(src, f, out=view, **p)
-                host = tga._host(big)
+                host = cg.host(big)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, p["n_mels"] * f:] == SENT).all()
                 got = host[[0, 2], :, :p["n_mels"] * f].reshape(2, 1, p["n_mels"], f)
                 _check(good, sig, got, e.value.valid[[0, 2]], f, p, "log10")
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, p["n_mels"], f)
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, (p["n_mels"], f))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         for bad_p in (dict(n_fft=401), dict(n_fft=2048), dict(hop=0), dict(hop=401), dict(f_max=8000.5), dict(floor=0.0), dict(width=65)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_mel(src, f, out=view, **dict(p, **bad_p))
         with pytest.raises(RuntimeError):
-            dec.decode_clips_mel([(s["48k"], tga._ref("48k")[0], -1)], f, out=view, **p)
+            dec.decode_clips_mel([(s["48k"], cg.ref("48k")[0], -1)], f, out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_mel(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_mel(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -282,14 +201,14 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_after_it():
     p = P16
     small = [("32k", 500), ("8k", 1234)]
     large = [(n, s) for n in ("mixed/mono-stereo", "48k", "32k", "22k", "16k-mono", "8k") for s in (0, 999, 20001)]
-    fresh = tga._decoder()
+    fresh = cg.decoder()
     try:
-        audio_before, av = tga._run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
-        ix = tga._ref("48k")[0]
-        plain_before = fresh.decode_range(tga._streams()["48k"], ix, 33, 50).copy()
+        audio_before, av = calls.audio_run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        ix = cg.ref("48k")[0]
+        plain_before = fresh.decode_range(cg.streams()["48k"], ix, 33, 50).copy()
     finally:
         fresh.close()
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         a, va = _run(dec, "device", small, 9, p, "log10")
         sig = _signal(dec, large, 300, p)
@@ -302,9 +221,9 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_after_it():
         _run(dec, "device", [("48k", 10)], 17, P48, "whisper")
         c, vc = _run(dec, "numpy", small, 9, p, "log10")
         assert np.array_equal(a.view(np.uint32), c.view(np.uint32))
-        audio_after, av2 = tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        audio_after, av2 = calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
         assert np.array_equal(audio_before.view(np.uint32), audio_after.view(np.uint32)) and np.array_equal(av, av2)
-        plain_after = dec.decode_range(tga._streams()["48k"], tga._ref("48k")[0], 33, 50)
+        plain_after = dec.decode_range(cg.streams()["48k"], cg.ref("48k")[0], 33, 50)
         assert np.array_equal(plain_before, plain_after)
     finally:
         dec.close()
@@ -313,17 +232,17 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_after_it():
 def test_4099_clips_of_3_frames_in_one_call():
     p, f, k = P16, 3, 4099
     name = "mixed/mono-stereo"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, 16000)
     rng = np.random.default_rng(4099)
     starts = [0, 1, 199, 200, 201, j_all - 1, j_all, j_all + 999] + [int(x) for x in rng.integers(0, j_all + 400, k - 8)]
     clips = [(name, s) for s in starts]
     w = _filterbank(p, name)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         # the whole stream at 16 kHz, once: every clip's samples are slices of it (the audio call's rows are)
         whole = np.zeros((1, 1, j_all + 2048), dtype=np.float32)
-        dec.decode_clips_audio([(tga._streams()[name], ix, 0)], j_all + 2048, 16000, 1, out=whole)
+        dec.decode_clips_audio([(cg.streams()[name], ix, 0)], j_all + 2048, 16000, 1, out=whole)
         got, valid = _run(dec, "device", clips, f, p, "log10")
         worst = 0.0
         for i, s in enumerate(starts):
@@ -339,15 +258,15 @@ def test_4099_clips_of_3_frames_in_one_call():
 
 
 def test_made_output_and_empty_calls():
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        out, valid = dec.decode_clips_mel([(tga._streams()["32k"], tga._ref("32k")[0], 1000)], 50)
+        out, valid = dec.decode_clips_mel([(cg.streams()["32k"], cg.ref("32k")[0], 1000)], 50)
         assert tuple(out.shape) == (1, 1, 80, 50) and out.is_cuda and valid[0] == 50
         sig = _signal(dec, [("32k", 1000)], 50, P16)
-        _check([("32k", 1000)], sig, tga._host(out), valid, 50, P16, "log10")
+        _check([("32k", 1000)], sig, cg.host(out), valid, 50, P16, "log10")
         out, valid = dec.decode_clips_mel([], 10)
         assert tuple(out.shape) == (0, 1, 80, 10) and valid.size == 0
-        out, valid = dec.decode_clips_mel([(tga._streams()["32k"], tga._ref("32k")[0], 1000)], 0)
+        out, valid = dec.decode_clips_mel([(cg.streams()["32k"], cg.ref("32k")[0], 1000)], 0)
         assert tuple(out.shape) == (1, 1, 80, 0) and valid[0] == 0
     finally:
         dec.close()

@@ -7,46 +7,32 @@ call's output has to agree within the bound derived in tests/clip_mel_long_ref.p
 the bound is 0 and the output exactly 0 on silence in mode 0.  Destinations are filled with a sentinel first.  Each device step
 runs once; a clip's reference is computed once and shared by the modes.
 
-Streams and helpers: those of test_gpu_clip_audio.py and test_gpu_clip_mel.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import math
 
 import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_forms_cases as cases
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_mel_long_ref as mlref
 import clip_mel_ref as mref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
+from clip_gpu import GUARD, SENT, signal as _signal
+from clip_gpu_calls import MEL_LONG_PA as PA, mel_filterbank as _filterbank, mel_long_run as _run, mel_starts as _starts
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD, MODES, U = tgm.SENT, tgm.GUARD, mlref.MODES, mref.U
-_signal, _starts, _rate, _destination = tgm._signal, tgm._starts, tgm._rate, tgm._destination
+MODES, U = mlref.MODES, mref.U
 
 W1764 = (np.random.default_rng(1764).random(1764, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
-PA = dict(sample_rate=0, n_fft=2048, hop=512, n_mels=128, scale="slaney", norm="slaney", channels=2)     # the 48 kHz stream at its own rate
 PB = dict(sample_rate=22050, n_fft=2048, hop=441, n_mels=128, scale="htk", norm=None, channels=1, win_length=1764, window=W1764)
 PC = dict(sample_rate=0, n_fft=2048, hop=2048, n_mels=17, scale="slaney", norm="slaney", channels=1)
 PD = dict(sample_rate=0, n_fft=4096, hop=1024, n_mels=128, scale="slaney", norm="slaney", channels=1)
 PE = dict(sample_rate=0, n_fft=4096, hop=4096, n_mels=1, scale="slaney", norm="slaney", channels=2)
 PF = dict(sample_rate=0, n_fft=2048, hop=1, n_mels=256, scale="slaney", norm="slaney", channels=1)
-
-
-def _filterbank(p, name):
-    return mref.filterbank(_rate(p, name), p["n_fft"], p["n_mels"], p.get("f_min", 0.0), p.get("f_max", 0.0), p["scale"], p["norm"])
-
-
-def _run(dec, kind, clips, f, p, mode, floor=1e-10):
-    """clips: (stream name, start) -> (host copy [k, c, nm, f], valid)"""
-    k, c, nm = len(clips), p["channels"], p["n_mels"]
-    big, view = _destination(kind, k, c, nm, f)
-    out, valid = dec.decode_clips_mel_long([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, mode=mode, floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:, :, nm * f:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :nm * f].reshape(k, c, nm, f), valid
 
 
 def _wants(clips, sig, f, p, floor=1e-10):
@@ -61,8 +47,8 @@ def _check(clips, sig, wants, got, valid, f, p, mode):
     worst = 0.0
     m = MODES.index(mode)
     for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
+        ix = cg.ref(n)[0]
+        j_all = aref.out_length(ix.samples, ix.rate, cg.rate(p, n))
         assert int(valid[i]) == mref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
         want, bound = wants[i][m]
         assert want.shape == got[i].shape
@@ -104,11 +90,11 @@ def test_the_cases_cover_every_launch_path():
 def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, name, f, path = CASES[case]
-    assert _rate(p, name) == RATES[name]
+    assert cg.rate(p, name) == RATES[name]
     clips = [(name, s) for s in _starts(name, p, f)]
     tile = api.mel_long_plan(p["n_fft"], p["hop"], p["n_mels"])[0]
     assert mlref.plan(p["n_fft"], p["hop"], p["n_mels"])[3] == path and path.endswith("tile%d" % tile)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         wants = _wants(clips, sig, f, p)
@@ -132,7 +118,7 @@ def test_frames_are_frames(p):
     tile = api.mel_long_plan(p["n_fft"], p["hop"], p["n_mels"])[0]
     fs = [0, 1, tile - 1, tile, tile + 1, 2 * tile - 1, 2 * tile, 2 * tile + 2]
     f_long = 2 * tile + 4
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in MODES:
             long, _ = _run(dec, "device", [(name, start)], f_long, p, mode)
@@ -152,13 +138,13 @@ def test_mode_0_is_the_filterbank_of_the_spectrum_calls_powers(p, f):
     second part of dM alone"""
     name = "48k"
     clips = [(name, s) for s in (0, 57, 30011)]
-    src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-    dec = tga._decoder()
+    src = cg.src(clips)
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, p, "power")
         power, v2 = dec.decode_clips_stft_long(src, f, sample_rate=0, n_fft=p["n_fft"], hop=p["hop"], channels=p["channels"], mode="power")
         assert np.array_equal(valid, v2)
-        pw = tga._host(power).astype(np.float64)                             # [k, c, K, f]
+        pw = cg.host(power).astype(np.float64)                             # [k, c, K, f]
         want, bound = mlref.gemm_bound(_filterbank(p, name), pw)
         err = np.abs(got.astype(np.float64) - want)
         assert want.shape == got.shape and (err <= bound).all(), float((err - bound).max())
@@ -172,7 +158,7 @@ def test_mode_0_is_the_filterbank_of_the_spectrum_calls_powers(p, f):
 def test_slices_of_a_batch_are_the_batchs_slices():
     p, f = dict(PB, sample_rate=16000), 19
     clips = [(n, s) for n in ("48k", "22k", "16k-mono") for s in (0, 5000, 23457)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in ("power", "log10"):
             whole, valid = _run(dec, "device", clips, f, p, mode)
@@ -191,29 +177,29 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         wants = _wants(good, sig, f, p)
         for kind, mode in (("device", "power"), ("numpy", "log10")):
             per = nm * f
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, nm, f)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, (nm, f))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_mel_long(src, f, mode=mode, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape(2, 1, nm, f)
                 _check(good, sig, wants, got, e.value.valid[[0, 2]], f, p, mode)
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, nm, f)
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, (nm, f))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         nan_window = np.ones(2048, dtype=np.float32)
         nan_window[123] = np.nan
         for bad_p in (dict(n_fft=1024), dict(n_fft=8192), dict(n_fft=400), dict(hop=0), dict(hop=2049), dict(win_length=2049), dict(window=nan_window),
@@ -221,16 +207,16 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
             q = dict(dict(p, mode="log10"), **bad_p)
             with pytest.raises(RuntimeError):
                 dec.decode_clips_mel_long(src, f, out=view, **q)
-            assert (tga._host(big) == SENT).all()
+            assert (cg.host(big) == SENT).all()
         with pytest.raises(RuntimeError):
-            dec.decode_clips_mel_long([(s["48k"], tga._ref("48k")[0], -1)], f, out=view, **p)
+            dec.decode_clips_mel_long([(s["48k"], cg.ref("48k")[0], -1)], f, out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_mel_long(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_mel_long(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
         # the call of section 10 keeps refusing this length
         with pytest.raises(RuntimeError):
             dec.decode_clips_mel(src, f, mode="log10", out=view, **p)
-        assert (tga._host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -240,11 +226,11 @@ def test_clips_wholly_behind_the_end_return_types_and_empty_calls():
     import torch
     p, f, floor = PA, 5, 1e-7
     name = "48k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     clips = [(name, j_all + 5 * p["n_fft"]), (name, j_all + 1000000)]
-    src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-    dec = tga._decoder()
+    src = cg.src(clips)
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, p, "power", floor)
         assert (valid == 0).all() and (got.view(np.uint32) == 0).all()        # exactly +0.0
@@ -268,15 +254,15 @@ def test_more_clips_than_one_grid():
     every row is bit-equal to its twin among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k = "32k", 32768 + 5
     p = dict(sample_rate=0, n_fft=2048, hop=2048, n_mels=1, scale="slaney", norm="slaney", channels=1)
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 7, j_all - 1]
     assert starts[61] + 2048 < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         sig = _signal(dec, first, 1, p)
@@ -284,9 +270,9 @@ def test_more_clips_than_one_grid():
         base, valid64 = _run(dec, "device", first, 1, p, "log10")
         assert 0.0 < _check(first, sig, wants, base, valid64, 1, p, "log10") <= 1.0
         assert list(valid64[61:]) == [1, 0, 1]
-        big, view = _destination("device", k, 1, 1, 1)
+        big, view = cg.destination("device", k, 1, (1, 1))
         out, valid = dec.decode_clips_mel_long([(mp3, ix, int(starts[t])) for t in twin], 1, mode="log10", out=view, **p)
-        host = tga._host(big)
+        host = cg.host(big)
         assert (host[:, :, 1:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 1, 1, 1, 1]
         bad = np.flatnonzero(host[:, 0, 0].view(np.uint32) != base[twin, 0, 0, 0].view(np.uint32))
@@ -300,19 +286,18 @@ def test_one_decoder_through_this_call_the_other_calls_and_this_call_again():
     """the new call, decode_clips_stft_long, decode_clips_mel, decode_clips_audio, decode_range, the new call with another
     filterbank and with the other n_fft -- and all of it again: every call is bit-equal to its first answer, the filterbank
     operands live side by side and the transform's tables are shared with the spectrum call"""
-    import test_gpu_clip_stft_long as tgl
     small = [("32k", 500), ("8k", 1234)]
     pa = dict(PA, sample_rate=16000, channels=1)
     pb = dict(pa, n_mels=40, scale="htk", norm=None, f_min=50.0, f_max=7000.0)
     pd = dict(PD, sample_rate=16000, n_mels=17)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         def once():
             r = [_run(dec, "device", small, 9, pa, "log10"),
-                 tgl._run(dec, "device", small, 9, dict(tgl.PA, sample_rate=16000, channels=1), "complex"),
-                 tgm._run(dec, "device", small, 9, tgm.P16, "log10"),
-                 tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
-                 (dec.decode_range(tga._streams()["48k"], tga._ref("48k")[0], 33, 50).copy(), np.zeros(0)),
+                 calls.stft_long_run(dec, "device", small, 9, dict(calls.STFT_LONG_PA, sample_rate=16000, channels=1), "complex"),
+                 calls.mel_run(dec, "device", small, 9, cases.MEL_P16, "log10"),
+                 calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
+                 (dec.decode_range(cg.streams()["48k"], cg.ref("48k")[0], 33, 50).copy(), np.zeros(0)),
                  _run(dec, "device", small, 9, pb, "log10"),
                  _run(dec, "numpy", small, 5, pd, "power")]
             return r

@@ -9,14 +9,13 @@ import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_gpu as cg
 import clip_pitch_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_stft as tgs
+from clip_gpu import GUARD, SENT, signal as _signal
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD = tgs.SENT, tgs.GUARD
 CAP = 0.1                                          # the share of a test's frames that may be undecided
 
 
@@ -46,14 +45,7 @@ def _periodic():
     return mp3, api.StreamIndex(mp3, ISO_LSF)
 
 
-def _source(name):
-    if name == "periodic":
-        return _periodic()
-    return tga._streams()[name], tga._ref(name)[0]
-
-
-def _src(clips):
-    return [_source(n) + (s,) for n, s in clips]
+cg.STREAMS["periodic/16k"] = _periodic
 
 
 def _lags(g):
@@ -63,24 +55,8 @@ def _lags(g):
 
 def _run(dec, kind, clips, f, g, out_mode):
     """clips: (stream name, start) -> (host copy [k, c, rows, f], valid)"""
-    k, c = len(clips), g["channels"]
     rows = 3 if out_mode == "pitch" else _lags(g)[1] + 1
-    big, view = tgs._destination(kind, k, c, rows, f, "power")
-    out, valid = dec.decode_clips_pitch(_src(clips), f, out_mode=out_mode, out=view, **g)
-    assert out is view
-    host = tga._host(big).reshape(k, c, rows * f + GUARD)
-    assert (host[:, :, rows * f:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :rows * f].reshape(k, c, rows, f).copy(), valid
-
-
-def _signal(dec, clips, f, g):
-    """the binary32 samples the clips' frames read, from the product's own audio call: per clip (s0, y [C, T])"""
-    n, hop, c = g["frame_length"], g["hop"], g["channels"]
-    t = (f - 1) * hop + n
-    s0 = [max(0, s - n // 2) for _, s in clips]
-    y = np.full((len(clips), c, t), SENT, dtype=np.float32)
-    dec.decode_clips_audio([_source(nm) + (a,) for (nm, _), a in zip(clips, s0)], t, g["sample_rate"], c, out=y)
-    return list(zip(s0, y))
+    return cg.run(dec, "decode_clips_pitch", kind, clips, f, g["channels"], (rows, f), out_mode=out_mode, **g)
 
 
 def _check(clips, sig, pitch, curve, valid, f, g):
@@ -91,7 +67,7 @@ def _check(clips, sig, pitch, curve, valid, f, g):
     tmin, tmax, _ = _lags(g)
     worst, und, live, ulps = 0.0, 0, 0, 0
     for i, (name, s) in enumerate(clips):
-        ix = _source(name)[1]
+        ix = cg.source(name)[1]
         j_all = aref.out_length(ix.samples, ix.rate, sr)
         assert int(valid[i]) == ref.valid(j_all, s, hop, f), (name, s, valid[i])
         s0, y = sig[i]
@@ -105,7 +81,7 @@ def _check(clips, sig, pitch, curve, valid, f, g):
 
 def _starts(name, g, f):
     """a positive lead, the middle of the stream, frames past its end"""
-    ix = _source(name)[1]
+    ix = cg.source(name)[1]
     j_all = aref.out_length(ix.samples, ix.rate, g["sample_rate"])
     return [g["frame_length"] // 2 - 7, j_all // 3 + 11, j_all - (f // 2) * g["hop"] - 3]
 
@@ -124,8 +100,8 @@ def test_against_binary64_on_the_products_own_signal(case):
     make, name, f = CASES[case]
     assert f % 8 != 0
     if case == "defaults-22k-from-44k":
-        assert _source(name)[1].rate == 44100 and _lags(make(1)) == (10, 338, 2)
-    dec = tga._decoder()
+        assert cg.source(name)[1].rate == 44100 and _lags(make(1)) == (10, 338, 2)
+    dec = cg.decoder()
     try:
         for channels in (1, 2):
             g = make(channels)
@@ -155,8 +131,8 @@ def test_a_periodic_stream_runs_the_threshold_branch():
     tmin, tmax, tiles = _lags(g)
     assert (tmin, tmax, tiles) == (4, 1535, 6)
     f, start = 11, 4608
-    clips = [("periodic", start)]
-    dec = tga._decoder()
+    clips = [("periodic/16k", start)]
+    dec = cg.decoder()
     try:
         (s0, y), = _signal(dec, clips, f, g)
         row = y[0]
@@ -190,7 +166,7 @@ def test_twice_the_same_and_alone_as_in_a_batch():
     f = 9
     name = "22k"
     batch = [(name, s) for s in (1000, 50000, 7, 123456, 90000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in ("pitch", "curve"):
             a, va = _run(dec, "device", batch, f, g, mode)
@@ -211,11 +187,11 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, g)
         want_p, _ = _run(dec, "device", good, f, g, "pitch")
@@ -224,31 +200,31 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
         for kind, mode, want in (("device", "pitch", want_p), ("numpy", "curve", want_c)):
             rows = want.shape[2]
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tgs._destination(kind, 3, 1, rows, f, "power")
-                src = [_source("48k") + (100,), mid, _source("22k") + (3000,)]
+                big, view = cg.destination(kind, 3, 1, (rows, f))
+                src = [cg.source("48k") + (100,), mid, cg.source("22k") + (3000,)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_pitch(src, f, out_mode=mode, out=view, **g)
-                host = tga._host(big).reshape(3, 1, rows * f + GUARD)
+                host = cg.host(big).reshape(3, 1, rows * f + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all() and (host[:, :, rows * f:] == SENT).all()
                 got = host[[0, 2], :, :rows * f].reshape(2, 1, rows, f)
                 assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(e.value.valid[[0, 2]], valid)
         # bad arguments: nothing is written
-        big, view = tgs._destination("device", 1, 1, 3, f, "power")
-        src = [_source("48k") + (0,)]
+        big, view = cg.destination("device", 1, 1, (3, f))
+        src = [cg.source("48k") + (0,)]
         for bad_g in (dict(frame_length=1023), dict(frame_length=4096), dict(frame_length=62), dict(win_length=3), dict(win_length=1023),
                       dict(hop=1025), dict(hop=-2), dict(fmin=0.0), dict(fmax=g["fmin"]), dict(fmax=8000.5), dict(threshold=0.0),
                       dict(threshold=1.01), dict(fmin=100.0 * (1 + 1e-13), fmax=4000.0), dict(width=65)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_pitch(src, f, out=view, **dict(g, **bad_g))
-            assert (tga._host(big) == SENT).all(), bad_g
+            assert (cg.host(big) == SENT).all(), bad_g
         for mode in ("contour", 2, -1):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_pitch(src, f, out_mode=mode, out=view, **g)
         with pytest.raises(RuntimeError):
-            dec.decode_clips_pitch([_source("48k") + (-1,)], f, out=view, **g)
+            dec.decode_clips_pitch([cg.source("48k") + (-1,)], f, out=view, **g)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_pitch(src + [_source("32k") + (0,)], f, **dict(g, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_pitch(src + [cg.source("32k") + (0,)], f, **dict(g, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -260,7 +236,7 @@ def test_more_clips_than_one_grid():
     to its twin among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     g = geometry(8000, 64, 32, 16, 2, 31)
     name, k, f = "8k", 32768 + 5, 1
-    mp3, ix = _source(name)
+    mp3, ix = cg.source(name)
     assert ix.rate == 8000
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 64 + 9, j_all - 5]
@@ -268,7 +244,7 @@ def test_more_clips_than_one_grid():
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         sig = _signal(dec, first, f, g)
@@ -278,9 +254,9 @@ def test_more_clips_than_one_grid():
         print("sixty-four one-frame clips: worst error / bound %.4f, %d of %d frames undecided" % (worst, und, live))
         assert 0.0 < worst <= 1.0 and und <= CAP * live and ulps == 0 and live >= 40
         assert list(valid64[61:]) == [1, 0, 1] and base[62, 0, :, 0].tolist() == [0.0, 1.0, 0.0]
-        big, view = tgs._destination("device", k, 1, 3, f, "power")
+        big, view = cg.destination("device", k, 1, (3, f))
         out, valid = dec.decode_clips_pitch([(mp3, ix, int(starts[t])) for t in twin], f, out=view, **g)
-        host = tga._host(big).reshape(k, 3 * f + GUARD)
+        host = cg.host(big).reshape(k, 3 * f + GUARD)
         assert (host[:, 3 * f:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 1, 1, 1, 1]
         same = (host[:, :3 * f].view(np.uint32) == base[twin].reshape(k, 3 * f).view(np.uint32)).all(axis=1)
@@ -293,17 +269,17 @@ def test_more_clips_than_one_grid():
 
 def test_return_types_defaults_and_empty_calls():
     import torch
-    src = [_source("22k") + (30000,)]
-    dec = tga._decoder()
+    src = [cg.source("22k") + (30000,)]
+    dec = cg.decoder()
     try:
         out, valid = dec.decode_clips_pitch(src, 20)
         assert tuple(out.shape) == (1, 1, 3, 20) and out.is_cuda and out.dtype == torch.float32 and valid[0] == 20 and valid.dtype == np.int64
         plain, _ = _run(dec, "device", [("22k", 30000)], 20, DEFAULTS, "pitch")       # (the defaults, spelled out)
-        assert np.array_equal(tga._host(out).view(np.uint32), plain.view(np.uint32))
-        lag = tga._host(out)[0, 0, 2]
-        assert ((lag >= 10) & (lag <= 338)).all() and (tga._host(out)[0, 0, 0] > 0).all()
+        assert np.array_equal(cg.host(out).view(np.uint32), plain.view(np.uint32))
+        lag = cg.host(out)[0, 0, 2]
+        assert ((lag >= 10) & (lag <= 338)).all() and (cg.host(out)[0, 0, 0] > 0).all()
         out, valid = dec.decode_clips_pitch(src, 20, out_mode="curve", channels=2)
-        assert tuple(out.shape) == (1, 2, 339, 20) and out.dtype == torch.float32 and (tga._host(out)[0, :, 0] == 1.0).all()
+        assert tuple(out.shape) == (1, 2, 339, 20) and out.dtype == torch.float32 and (cg.host(out)[0, :, 0] == 1.0).all()
         out, valid = dec.decode_clips_pitch(src, 5, sample_rate=0, frame_length=1024, hop=None, win_length=None, fmin=100.0, fmax=2000.0)
         assert tuple(out.shape) == (1, 1, 3, 5) and valid[0] == 5
         out, valid = dec.decode_clips_pitch([], 10)

@@ -12,15 +12,15 @@ import functools
 import numpy as np
 import pytest
 
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_r128_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_loudness as tgl
+from clip_gpu import GUARD, SENT
+from clip_gpu_calls import LOUDNESS_CASES as CASES, audio_rows as _signal, loud_rate as _fs, r128_check as _check, r128_run as _run
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD = tga.SENT, tga.GUARD
-CASES = tgl.CASES
 
 
 @functools.lru_cache(maxsize=None)
@@ -36,82 +36,13 @@ def _range_stream():
     return mp3, api.StreamIndex(mp3, ISO_LSF)
 
 
-def _source(name):
-    if name == "range":
-        return _range_stream()
-    return tgl._source(name)
-
-
-def _src(clips):
-    return [_source(n) + (s,) for n, s in clips]
-
-
-def _fs(clips, rate):
-    return rate or _source(clips[0][0])[1].rate
-
-
-def _filled(kind, shape):
-    if kind == "device":
-        import torch
-        a = torch.full(shape, float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        return a
-    return np.full(shape, SENT, dtype=np.float32)
-
-
-def _run(dec, kind, clips, t, rate=0, channels=0, c=None, curves=True, **kw):
-    """clips: (stream name, start) -> (audio [k, c, t], stats [k, 16], momentary [k, J], short-term [k, Js], valid), host copies"""
-    k = len(clips)
-    c = c or channels
-    p = ref.plan(_fs(clips, rate), t)
-    big, view = tga._destination(kind, k, c, t)
-    mom, st = _filled(kind, (k + 1, p["J"])), _filled(kind, (k + 1, p["Jsmax"]))
-    audio, stats, valid = dec.decode_clips_r128(_src(clips), t, rate, channels, out=view, momentary=mom if curves else None,
-                                                short_term=st if curves else None, **kw)
-    assert audio is view and tuple(stats.shape) == (k, 16) and hasattr(stats, "data_ptr") == (kind == "device")
-    host = tga._host(big)
-    assert (host[:, :, t:] == SENT).all(), "written behind a row's samples"
-    m, s = tga._host(mom), tga._host(st)
-    assert (m[k] == SENT).all() and (s[k] == SENT).all() and (curves or ((m == SENT).all() and (s == SENT).all())), "written behind the curves' rows"
-    return host[:, :, :t].copy(), np.array(tga._host(stats)), m[:k].copy(), s[:k].copy(), valid
-
-
-def _signal(dec, clips, t, rate, channels, c):
-    big, view = tga._destination("device", len(clips), c, t)
-    out, valid = dec.decode_clips_audio(_src(clips), t, rate, channels, out=view)
-    return tga._host(big)[:, :, :t].copy(), valid
-
-
-def _check(x, want_valid, got, fs, curves=True, **kw):
-    """rows x [k, c, t] of the audio call against the call's (audio, stats, momentary, short-term, valid) -> (the references,
-    worst error / bound, smallest range-gate margin in bounds, undecided clips)"""
-    audio, stats, mom, st, valid = got
-    assert np.array_equal(valid, want_valid)
-    refs, worst, margin, margin_db, undecided = [], 0.0, np.inf, np.inf, 0
-    for i in range(x.shape[0]):
-        m = ref.measure(x[i], fs, **kw)
-        refs.append(m)
-        worst = max(worst, ref.check_stats(m, stats[i], mom[i] if curves else None, st[i] if curves else None))
-        margin, margin_db = min(margin, m.r_margin_bounds), min(margin_db, m.r_margin)
-        undecided += m.undecided or m.r_undecided
-        want = (x[i] * np.float32(stats[i, 3])).astype(np.float32)
-        assert np.array_equal(audio[i].view(np.uint32), want.view(np.uint32)), "clip %d: audio is not x * g" % i
-        assert np.float32(stats[i, 2]) == np.abs(x[i]).max() and stats[i, 8] >= stats[i, 2]
-    assert undecided * 10 <= x.shape[0], "%d of %d clips undecided" % (undecided, x.shape[0])
-    print("r128: worst error / bound %.3g, smallest range-gate margin %.3g dB = %.3g bounds, %d undecided of %d" %
-          (worst, margin_db, margin, undecided, x.shape[0]))
-    return refs, worst, margin, undecided
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
+cg.STREAMS["range"] = _range_stream
 
 
 def _case_clips(names, fs, t):
     clips = []
     for n in names:
-        ix = _source(n)[1]
+        ix = cg.source(n)[1]
         j_all = ix.samples * fs // ix.rate
         clips += [(n, 0), (n, j_all // 2 + 331), (n, j_all - t // 3)]
     return clips
@@ -126,7 +57,7 @@ def test_against_binary64(case):
     """3 s (the first length with a short-term window) and 14 s, a block and five samples; starts 0, mid-stream and with the
     stream's end inside the clip; device and numpy destinations -- the reference of a length made once for both"""
     names, rate, channels = CASES[case]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         fs = _fs([(names[0], 0)], rate)
         for t in _lengths(fs):
@@ -137,7 +68,7 @@ def test_against_binary64(case):
             assert 0.0 < worst <= 1.0 and refs[0].Js >= 1 and any(np.isfinite(m.Smax) for m in refs) and any(m.TP > m.P for m in refs)
             host = _run(dec, "numpy", clips, t, rate, channels)
             for a, b in zip(got, host):
-                assert np.array_equal(_bits(a), _bits(b))
+                assert np.array_equal(cg.bits(a), cg.bits(b))
     finally:
         dec.close()
 
@@ -145,16 +76,16 @@ def test_against_binary64(case):
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_without_the_limit_the_first_eight_are_the_loudness_calls(case):
     names, rate, channels = CASES[case]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         fs = _fs([(names[0], 0)], rate)
         for t in _lengths(fs):
             clips = _case_clips(names, fs, t)
             for kw in (dict(target=None, peak_limit=0.0), dict(target=-14.0, peak_limit=0.5)):
                 audio, stats, mom, st, valid = _run(dec, "device", clips, t, rate, channels, limit_true_peak=False, **kw)
-                want = tgl._run(dec, "device", clips, t, rate, channels, **kw)
-                assert np.array_equal(_bits(audio), _bits(want[0])) and np.array_equal(_bits(stats[:, :8]), _bits(want[1]))
-                assert np.array_equal(_bits(mom), _bits(want[2])) and np.array_equal(valid, want[3])
+                want = calls.loudness_run(dec, "device", clips, t, rate, channels, **kw)
+                assert np.array_equal(cg.bits(audio), cg.bits(want[0])) and np.array_equal(cg.bits(stats[:, :8]), cg.bits(want[1]))
+                assert np.array_equal(cg.bits(mom), cg.bits(want[2])) and np.array_equal(valid, want[3])
             assert (stats[:, 3] != 1.0).any()
     finally:
         dec.close()
@@ -163,7 +94,7 @@ def test_without_the_limit_the_first_eight_are_the_loudness_calls(case):
 @functools.lru_cache(maxsize=None)
 def _range_case():
     """the whole range stream at its own rate: (t, the audio call's rows, valid) -- made once"""
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         t = int(_range_stream()[1].samples)
         x, valid = _signal(dec, [("range", 0)], t, 0, 0, 2)
@@ -175,7 +106,7 @@ def _range_case():
 def test_both_gates_of_the_range_bite():
     t, x, valid = _range_case()
     assert _range_stream()[1].rate == 8000 and t == 158976
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         got = _run(dec, "device", [("range", 0)], t, c=2)
         refs, worst, margin, undecided = _check(x, valid, got, 8000, target=-23.0, peak_limit=10 ** (-1 / 20))
@@ -197,9 +128,9 @@ def test_the_history_across_waves_and_chunks():
     offs = [b + d for b in (1024, 3072, 4096) for d in (0, 5, 11)]
     t = max(offs) + 64 + 6
     assert t % 4
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
-        n_all = int(_source(name)[1].samples)
+        n_all = int(cg.source(name)[1].samples)
         whole, _ = _signal(dec, [(name, 0)], n_all, 0, 0, 2)
         y = np.abs(ref.oversample(whole[0])[0][:, :, 1:]).max(axis=(0, 2))       # per sample, phases 1 .. 3, both channels
         p = None
@@ -231,12 +162,12 @@ def test_the_gain_is_held_to_the_true_peak():
     m0 = ref.measure(x[0], 8000, target=-20.0)
     assert m0.TP > 1.05 * m0.P and not m0.tp_limited
     between, above = m0.g * (m0.P * m0.TP) ** 0.5, m0.g * m0.TP * 1.2
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         got = _run(dec, "device", [("range", 0)], t, c=2, curves=False, target=-20.0, peak_limit=between)
         refs, _, _, undecided = _check(x, valid, got, 8000, curves=False, target=-20.0, peak_limit=between)
-        big, view = tga._destination("device", 1, 2, t)
-        plain = float(dec.decode_clips_loudness(_src([("range", 0)]), t, target=-20.0, peak_limit=between, out=view)[1][0, 3])
+        big, view = cg.destination("device", 1, 2, (t,))
+        plain = float(dec.decode_clips_loudness(cg.src([("range", 0)]), t, target=-20.0, peak_limit=between, out=view)[1][0, 3])
         g, tp = float(got[1][0, 3]), float(got[1][0, 8])
         assert refs[0].tp_limited and not undecided and g < plain and abs(plain - m0.g) <= m0.dg + 2.0 ** -23 * m0.g      # (the sample peak holds nothing)
         assert g * tp <= between * (1.0 + 2.0 ** -22) + g * refs[0].dTP
@@ -251,15 +182,15 @@ def test_order_and_batch_independence():
     fs, q = 32000, 3200
     t = 41 * q + 77
     clips = [("32k", 4321), ("48k", 100), ("32k", 150000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         one = _run(dec, "device", clips, t, fs, 2)
         two = _run(dec, "device", clips, t, fs, 2)
         for a, b in zip(one, two):
-            assert np.array_equal(_bits(a), _bits(b))
+            assert np.array_equal(cg.bits(a), cg.bits(b))
         alone = _run(dec, "device", [clips[2]], t, fs, 2)
         for a, b in zip(one[:4], alone[:4]):
-            assert np.array_equal(_bits(a[2]), _bits(b[0])), "a clip's numbers depend on its batch"
+            assert np.array_equal(cg.bits(a[2]), cg.bits(b[0])), "a clip's numbers depend on its batch"
         assert np.isfinite(one[1][:, 9]).all() and (one[1][:, 12] == 12).all() and (one[1][:, 13] == 2).all()
     finally:
         dec.close()
@@ -272,22 +203,22 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("48k", 30000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         x, valid = _signal(dec, good, t, fs, 2, 2)
         for kind in ("device", "numpy"):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tga._destination(kind, 3, 2, t)
-                mom, st = _filled(kind, (3, p["J"])), _filled(kind, (3, p["Jsmax"]))
-                src = [_src(good)[0], mid, _src(good)[1]]
+                big, view = cg.destination(kind, 3, 2, (t,))
+                mom, st = cg.filled(kind, (3, p["J"])), cg.filled(kind, (3, p["Jsmax"]))
+                src = [cg.src(good)[0], mid, cg.src(good)[1]]
                 c0, h0 = dec.clip_stats()
                 with pytest.raises(exc) as e:
                     dec.decode_clips_r128(src, t, fs, 2, out=view, momentary=mom, short_term=st)
-                host, m, sh, stt = tga._host(big), tga._host(mom), tga._host(st), np.array(tga._host(e.value.stats))
+                host, m, sh, stt = cg.host(big), cg.host(mom), cg.host(st), np.array(cg.host(e.value.stats))
                 assert e.value.valid[1] == code and (host[1] == SENT).all() and (m[1] == SENT).all() and (sh[1] == SENT).all() and np.isnan(stt[1]).all()
                 assert (host[:, :, t:] == SENT).all() and stt.shape == (3, 16)
                 got = (host[[0, 2], :, :t], stt[[0, 2]], m[[0, 2]], sh[[0, 2]], e.value.valid[[0, 2]])
@@ -303,19 +234,19 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
         c2, h2 = dec.clip_stats()
         assert (c2 - c1, h2 - h1) == (c1 - c0, h1 - h0)
         # bad arguments: nothing is written
-        big, view = tga._destination("device", 1, 2, t)
-        src = _src(good[:1])
+        big, view = cg.destination("device", 1, 2, (t,))
+        src = cg.src(good[:1])
         for kw in (dict(target=-70.5), dict(target=0.5), dict(target=float("inf")), dict(peak_limit=-1.0), dict(peak_limit=float("inf")),
                    dict(peak_limit=float("nan")), dict(dual_mono=True), dict(dual_mono=2), dict(limit_true_peak=2), dict(limit_true_peak=-1),
                    dict(width=65), dict(sample_rate=7999), dict(sample_rate=192001)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_r128(src, t, **dict(dict(sample_rate=fs, channels=2, out=view), **kw))
-            assert (tga._host(big) == SENT).all(), kw
+            assert (cg.host(big) == SENT).all(), kw
         with pytest.raises(RuntimeError):
-            dec.decode_clips_r128([(s["48k"], tga._ref("48k")[0], -1)], t, fs, 2, out=view)
+            dec.decode_clips_r128([(s["48k"], cg.ref("48k")[0], -1)], t, fs, 2, out=view)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_r128(src + _src([("32k", 0)]), t)
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_r128(src + cg.src([("32k", 0)]), t)
+        assert (cg.host(big) == SENT).all()
         # a clip wholly behind the end
         got = _run(dec, "device", [("48k", 8 * fs)], t, fs, 2)
         want = [-np.inf, -np.inf, 0, 1, -np.inf, p["J"], 0, 0, 0, -np.inf, 0, -np.inf, p["Js"], p["Jr"], 0, 0]
@@ -330,14 +261,14 @@ def test_more_clips_than_one_grid():
     from descriptor 32 768 on.  Sixty-four distinct clips are held against the definition, every row is bit-equal to its twin
     among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k, t = "8k", 32768 + 5, 3200
-    mp3, ix = _source(name)
+    mp3, ix = cg.source(name)
     assert ix.rate == 8000
     j_all = int(ix.samples)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 9, j_all - 5]
     assert starts[61] + t < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         x, valid64 = _signal(dec, first, t, 0, 1, 1)
@@ -364,8 +295,8 @@ def test_more_clips_than_one_grid():
 
 def test_return_types_defaults_and_empty_calls():
     import torch
-    src = _src([("48k", 1000)])
-    dec = tga._decoder()
+    src = cg.src([("48k", 1000)])
+    dec = cg.decoder()
     try:
         c0, _ = dec.clip_stats()
         audio, stats, valid = dec.decode_clips_r128(src, 30000)             # the stream's rate and channels, R128's target and limit, no curves
@@ -380,7 +311,7 @@ def test_return_types_defaults_and_empty_calls():
         plain, _ = dec.decode_clips_audio(src, 30000)
         assert torch.equal(audio.view(torch.int32), plain.view(torch.int32)) and float(stats[0, 3]) == 1.0
         got = _run(dec, "numpy", [("48k", 1000)], 30000, c=2, target=None)
-        assert np.array_equal(got[1].view(np.uint32), tga._host(stats).view(np.uint32)) and got[1][0, 5] == 3
+        assert np.array_equal(got[1].view(np.uint32), cg.host(stats).view(np.uint32)) and got[1][0, 5] == 3
         audio, stats, valid = dec.decode_clips_r128([], 10, channels=1)
         assert tuple(audio.shape) == (0, 1, 10) and tuple(stats.shape) == (0, 16) and valid.size == 0
         audio, stats, valid = dec.decode_clips_r128(src, 0, channels=1)

@@ -11,20 +11,21 @@ CPU before relying on it; roll_percent 0.85 is held exactly, bin for bin, agains
 magnitudes (test_rows_2_to_5_are_the_reductions_of_the_spectrum_calls_output).  Destinations are filled with a sentinel first.
 Each device step runs once; a clip's reference is computed once.
 
-Streams and helpers: those of test_gpu_clip_audio.py and test_gpu_clip_mel.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_spectral_ref as spref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
+from clip_gpu import GUARD, SENT, signal as _signal
+from clip_gpu_calls import mel_starts as _starts
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD, U = tgm.SENT, tgm.GUARD, spref.U
-_signal, _starts, _rate, _destination = tgm._signal, tgm._starts, tgm._rate, tgm._destination
+U = spref.U
 ROWS = len(spref.ROWS)
 
 W1764 = (np.random.default_rng(1764).random(1764, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
@@ -38,18 +39,12 @@ PF = dict(sample_rate=0, n_fft=2048, hop=1, channels=1, roll_percent=0.005)     
 
 def _run(dec, kind, clips, f, p):
     """clips: (stream name, start) -> (host copy [k, c, 6, f], valid)"""
-    k, c = len(clips), p["channels"]
-    big, view = _destination(kind, k, c, ROWS, f)
-    out, valid = dec.decode_clips_spectral([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:, :, ROWS * f:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :ROWS * f].reshape(k, c, ROWS, f), valid
+    return cg.run(dec, "decode_clips_spectral", kind, clips, f, p["channels"], (ROWS, f), **p)
 
 
 def _wants(clips, sig, f, p):
     """per clip clip_spectral_ref.spectral's result: the definition on the product's own signal"""
-    return [spref.spectral(y, s0, s, f, p["n_fft"], p["hop"], _rate(p, n), p.get("roll_percent", 0.85), p.get("amin", 1e-10),
+    return [spref.spectral(y, s0, s, f, p["n_fft"], p["hop"], cg.rate(p, n), p.get("roll_percent", 0.85), p.get("amin", 1e-10),
                            p.get("zcr_threshold", 1e-10), p.get("win_length"), p.get("window")) for (n, s), (s0, y) in zip(clips, sig)]
 
 
@@ -58,8 +53,8 @@ def _check(clips, wants, got, valid, f, p):
     worst = np.zeros(ROWS)
     und = frames = 0
     for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
+        ix = cg.ref(n)[0]
+        j_all = aref.out_length(ix.samples, ix.rate, cg.rate(p, n))
         assert int(valid[i]) == spref.sref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
         res = wants[i]
         want, bound, signal = res["want"], res["bound"], res["signal"]
@@ -72,7 +67,7 @@ def _check(clips, wants, got, valid, f, p):
             if nz.any():
                 worst[r] = max(worst[r], float((err[:, r][nz] / bound[:, r][nz]).max()))
         assert np.array_equal(got[i][:, 1], want[:, 1].astype(np.float32)), (n, s, "zcr")
-        u, fr = spref.check_rolloff(got[i][:, 4], res, _rate(p, n), p["n_fft"])
+        u, fr = spref.check_rolloff(got[i][:, 4], res, cg.rate(p, n), p["n_fft"])
         und, frames = und + u, frames + fr
         assert (got[i][:, :5].transpose(0, 2, 1)[~signal].view(np.uint32) == 0).all(), (n, s, "a silent frame")
         assert (got[i][:, 5] > 0).all() and (got[i][:, 5] <= 1.0 + 1e-5).all()
@@ -101,11 +96,11 @@ def test_the_cases_cover_both_launch_paths():
 def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, name, f, path = CASES[case]
-    assert _rate(p, name) == RATES[name]
+    assert cg.rate(p, name) == RATES[name]
     clips = [(name, s) for s in _starts(name, p, f)]
     tile = api.spectral_plan(p["n_fft"], p["hop"])[0]
     assert spref.plan(p["n_fft"], p["hop"])[3] == path and path.endswith("tile%d" % tile)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         wants = _wants(clips, sig, f, p)
@@ -130,16 +125,16 @@ def test_rows_2_to_5_are_the_reductions_of_the_spectrum_calls_output(p, f):
     name = "48k"
     q = dict(p, roll_percent=0.85)
     clips = [(name, s) for s in (0, 57, 30011)]
-    src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-    dec = tga._decoder()
+    src = cg.src(clips)
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, q)
         long = dict(sample_rate=0, n_fft=p["n_fft"], hop=p["hop"], channels=p["channels"])
         mag, v1 = dec.decode_clips_stft_long(src, f, mode="magnitude", **long)
         power, v2 = dec.decode_clips_stft_long(src, f, mode="power", **long)
         assert np.array_equal(valid, v1) and np.array_equal(valid, v2)
-        s32 = np.moveaxis(tga._host(mag), 2, 3)                              # [k, c, f, K]
-        p32 = np.moveaxis(tga._host(power), 2, 3)
+        s32 = np.moveaxis(cg.host(mag), 2, 3)                              # [k, c, f, K]
+        p32 = np.moveaxis(cg.host(power), 2, 3)
         assert s32.shape[-1] == p["n_fft"] // 2 + 1 and (s32[..., -1] > 0).any()
         want, bound = spref.from_spectrum(s32, p32, RATES[name], p["n_fft"], 0.85, 1e-10)
         mine = np.moveaxis(got[:, :, 2:6, :], 2, 3).astype(np.float64)       # [k, c, f, 4]
@@ -165,7 +160,7 @@ def test_frames_are_frames(p):
     tile = api.spectral_plan(p["n_fft"], p["hop"])[0]
     fs = [0, 1, tile - 1, tile, tile + 1, 2 * tile - 1, 2 * tile, 2 * tile + 2]
     f_long = 2 * tile + 4
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         long, _ = _run(dec, "device", [(name, start)], f_long, p)
         short, _ = _run(dec, "device", [(name, start + f * p["hop"]) for f in fs], 2, p)
@@ -180,7 +175,7 @@ def test_frames_are_frames(p):
 def test_slices_of_a_batch_are_the_batchs_slices():
     p, f = dict(PB, sample_rate=16000), 11
     clips = [(n, s) for n in ("48k", "22k", "16k-mono") for s in (0, 5000, 23457)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         whole, valid = _run(dec, "device", clips, f, p)
         for a, b in ((0, 1), (2, 5), (4, 9), (8, 9)):
@@ -197,29 +192,29 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         wants = _wants(good, sig, f, p)
         per = ROWS * f
         for kind in ("device", "numpy"):
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, ROWS, f)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, (ROWS, f))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_spectral(src, f, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape(2, 1, ROWS, f)
                 _check(good, wants, got, e.value.valid[[0, 2]], f, p)
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, ROWS, f)
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, (ROWS, f))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         nan_window = np.ones(2048, dtype=np.float32)
         nan_window[123] = np.nan
         for bad_p in (dict(n_fft=1024), dict(n_fft=8192), dict(n_fft=400), dict(hop=0), dict(hop=2049), dict(win_length=2049), dict(window=nan_window),
@@ -227,12 +222,12 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
                       dict(amin=float("inf")), dict(zcr_threshold=-1e-3), dict(zcr_threshold=float("nan")), dict(width=65)):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_spectral(src, f, out=view, **dict(p, **bad_p))
-            assert (tga._host(big) == SENT).all(), bad_p
+            assert (cg.host(big) == SENT).all(), bad_p
         with pytest.raises(RuntimeError):
-            dec.decode_clips_spectral([(s["48k"], tga._ref("48k")[0], -1)], f, out=view, **p)
+            dec.decode_clips_spectral([(s["48k"], cg.ref("48k")[0], -1)], f, out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_spectral(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_spectral(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -242,11 +237,11 @@ def test_clips_wholly_behind_the_end_return_types_and_empty_calls():
     import torch
     p, f = PA, 5
     name = "48k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     clips = [(name, j_all + 5 * p["n_fft"]), (name, j_all + 1000000)]
-    src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
-    dec = tga._decoder()
+    src = cg.src(clips)
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, p)
         assert (valid == 0).all() and (got[:, :, :5].view(np.uint32) == 0).all()     # rows 0 .. 4 exactly +0.0
@@ -268,15 +263,15 @@ def test_more_clips_than_one_grid():
     bit-equal to its twin among them; the last five are other clips than rows 0 .. 4, one of them behind the end"""
     name, k = "32k", 32768 + 5
     p = dict(PC, roll_percent=0.005)
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, ix.rate)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 7, j_all - 1]
     assert starts[61] + 2048 < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    mp3 = tga._streams()[name]
-    dec = tga._decoder()
+    mp3 = cg.streams()[name]
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         sig = _signal(dec, first, 1, p)
@@ -285,9 +280,9 @@ def test_more_clips_than_one_grid():
         worst, und, frames = _check(first, wants, base, valid64, 1, p)
         assert 0.0 < worst[0] <= 1.0 and und <= spref.UNDECIDED_CAP * frames
         assert list(valid64[61:]) == [1, 0, 1]
-        big, view = _destination("device", k, 1, ROWS, 1)
+        big, view = cg.destination("device", k, 1, (ROWS, 1))
         out, valid = dec.decode_clips_spectral([(mp3, ix, int(starts[t])) for t in twin], 1, out=view, **p)
-        host = tga._host(big)
+        host = cg.host(big)
         assert (host[:, :, ROWS:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 1, 1, 1, 1]
         bad = np.flatnonzero((host[:, 0, :ROWS].view(np.uint32) != base[twin, 0, :, 0].view(np.uint32)).any(axis=1))
@@ -301,19 +296,17 @@ def test_one_decoder_through_this_call_the_other_calls_and_this_call_again():
     """the new call, decode_clips_stft_long, decode_clips_mel_long, decode_clips_audio, the new call with other parameters and
     with the other n_fft -- and all of it again: every call is bit-equal to its first answer; the transform's tables are shared
     with the spectrum and the log-mel call"""
-    import test_gpu_clip_mel_long as tgml
-    import test_gpu_clip_stft_long as tgl
     small = [("32k", 500), ("8k", 1234)]
     pa = dict(PA, sample_rate=16000, channels=1)
     pb = dict(pa, roll_percent=0.5, amin=1e-6, zcr_threshold=1e-3, win_length=1764, window=W1764)
     pd = dict(PD, sample_rate=16000)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         def once():
             return [_run(dec, "device", small, 9, pa),
-                    tgl._run(dec, "device", small, 9, dict(tgl.PA, sample_rate=16000, channels=1), "complex"),
-                    tgml._run(dec, "device", small, 9, dict(tgml.PA, sample_rate=16000, channels=1), "log10"),
-                    tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
+                    calls.stft_long_run(dec, "device", small, 9, dict(calls.STFT_LONG_PA, sample_rate=16000, channels=1), "complex"),
+                    calls.mel_long_run(dec, "device", small, 9, dict(calls.MEL_LONG_PA, sample_rate=16000, channels=1), "log10"),
+                    calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1),
                     _run(dec, "device", small, 9, pb),
                     _run(dec, "numpy", small, 5, pd)]
         a, b = once(), once()

@@ -7,7 +7,7 @@ call's output has to agree within the binary32 bound derived there -- every valu
 and the output exactly 0 on silence in modes 0 - 2.  Destinations are filled with a sentinel first: nothing outside a row's
 floats may change.  Each device step runs once.
 
-Streams and helpers: those of test_gpu_clip_audio.py and test_gpu_clip_mel.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import ctypes as C
 import math
 
@@ -15,98 +15,18 @@ import numpy as np
 import pytest
 
 import clip_audio_ref as aref
+import clip_forms_cases as cases
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_stft_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
+from clip_forms_cases import STFT_CASES as CASES, STFT_P16 as P16, STFT_P24 as P24, STFT_P48 as P48, STFT_P48H as P48H
+from clip_gpu import GUARD, SENT, signal as _signal
+from clip_gpu_calls import STFT_MODES as MODES, mel_starts as _starts, stft_check as _check, stft_per as _per, stft_run as _run
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT = np.float32(-1234.5)
-GUARD = 24
 U = ref.U
-MODES = ["complex", "magnitude", "power", "log", "log10"]
-
-_signal, _starts, _rate = tgm._signal, tgm._starts, tgm._rate
-
-W301 = (np.random.default_rng(301).random(301, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
-P16 = dict(sample_rate=16000, n_fft=400, hop=160, channels=1)
-P24 = dict(sample_rate=24000, n_fft=512, hop=128, channels=2, win_length=301, window=W301, normalized=True)
-P48 = dict(sample_rate=0, n_fft=1024, hop=1024, channels=2)               # the own rate (the 48 kHz stream); the static array
-P48H = dict(sample_rate=0, n_fft=1024, hop=512, channels=1)               # a tile of 16 frames inside 64 KB
-P8 = dict(sample_rate=16000, n_fft=16, hop=1, channels=1)
-
-
-def _per(p, mode):
-    return (p["n_fft"] // 2 + 1) * (2 if mode == "complex" else 1)
-
-
-def _destination(kind, k, c, nb, f, mode, guard=GUARD, offset=0):
-    """a sentinel-filled [k, c, floats of a row + guard] buffer and its view [k, c, nb, f] (mode complex: [k, c, nb, f, 2]);
-    rows and channels strided"""
-    two = mode == "complex"
-    per = nb * f * (2 if two else 1)
-    shape = (k, c, nb, f, 2) if two else (k, c, nb, f)
-    strides = (c * (per + guard), per + guard) + ((2 * f, 2, 1) if two else (f, 1))
-    if kind == "device":
-        import torch
-        big = torch.full((k * c * (per + guard) + offset,), float(SENT), dtype=torch.float32, device="cuda")
-        torch.cuda.synchronize()
-        return big, big.as_strided(shape, strides, offset)
-    big = np.full(k * c * (per + guard) + offset, SENT, dtype=np.float32)
-    return big, np.lib.stride_tricks.as_strided(big[offset:], shape, tuple(4 * s for s in strides))
-
-
-def _run(dec, kind, clips, f, p, mode, floor=1e-10, offset=0):
-    """clips: (stream name, start) -> (host copy [k, c, nb, f(, 2)], valid)"""
-    k, c, nb = len(clips), p["channels"], p["n_fft"] // 2 + 1
-    per = _per(p, mode) * f
-    big, view = _destination(kind, k, c, nb, f, mode, offset=offset)
-    out, valid = dec.decode_clips_stft([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, mode=mode, floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:offset] == SENT).all()
-    host = host[offset:].reshape(k, c, per + GUARD)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :per].reshape((k, c, nb, f, 2) if mode == "complex" else (k, c, nb, f)), valid
-
-
-def _check(clips, sig, got, valid, f, p, mode, floor=1e-10):
-    """every row against the definition on `sig`; -> worst error / bound over the rows that hold signal"""
-    worst = 0.0
-    m = MODES.index(mode)
-    for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
-        assert int(valid[i]) == ref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
-        s0, y = sig[i]
-        want, bound = ref.stft(y, s0, s, f, p["n_fft"], p["hop"], m, floor, p.get("win_length"), p.get("window"), p.get("normalized", False))
-        assert want.shape == got[i].shape
-        err = np.abs(got[i].astype(np.float64) - want)
-        assert (err <= bound).all(), "%s at %d, mode %s: error beyond the bound by %g at %s" % (
-            n, s, mode, float((err - bound).max()), np.unravel_index(np.argmax(err - bound), err.shape))
-        nz = bound > 0
-        if m <= 2:
-            assert (got[i][~nz] == 0.0).all()
-        if np.abs(y).sum() > 0 and nz.any():        # (a start inside the first N / 2 samples: the span's last samples belong to no frame)
-            r = float((err[nz] / bound[nz]).max())
-            assert 0.0 < r <= 1.0, (n, s, mode, r)
-            worst = max(worst, r)
-            if m == 0:
-                # the signal is no even function of n about any frame's centre: Im is far above the bound, so its sign (and a
-                # swap with Re) shows in the comparison above
-                assert (np.abs(want[..., 1]) > 100.0 * bound[..., 1])[nz[..., 1]].any()
-                assert (np.abs(want[..., 0] - want[..., 1]) > 100.0 * bound[..., 0])[nz[..., 0]].any()
-    return worst
-
-
-CASES = {
-    "16k-mono-batch": (P16, ["mixed/mono-stereo", "48k", "32k", "22k", "16k-mono", "8k"], 70),
-    "24k-stereo-own-window": (P24, ["48k", "22k", "mixed/mono-stereo"], 45),
-    "own-rate-1024": (P48, ["48k"], 21),
-    "own-rate-1024-hop-512": (P48H, ["48k"], 21),
-    "n16-hop1": (P8, ["32k"], 40),
-}
 PATHS = {"16k-mono-batch": "tile32", "24k-stereo-own-window": "tile32", "own-rate-1024": "tile16-static", "own-rate-1024-hop-512": "tile16",
          "n16-hop1": "tile32"}
 
@@ -116,9 +36,9 @@ def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, names, f = CASES[case]
     if case == "16k-mono-batch":
-        assert set(tga._ref(n)[0].rate for n in names) == {44100, 48000, 32000, 22050, 16000, 8000}
+        assert set(cg.ref(n)[0].rate for n in names) == {44100, 48000, 32000, 22050, 16000, 8000}
     clips = [(n, s) for n in names for s in _starts(n, p, f)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         for mode in MODES:
@@ -140,7 +60,7 @@ def test_mode_0_rederives_the_others_bit_for_bit(p):
     mode 1's, bit for bit: a transposed frame, a swapped bin or a mixed pair would show"""
     f = 37
     clips = [("48k", 4321), ("22k", 0)] if p["sample_rate"] else [("48k", 4321)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         z, _ = _run(dec, "device", clips, f, p, "complex")
         power, _ = _run(dec, "device", clips, f, p, "power")
@@ -159,7 +79,7 @@ def test_slices_are_slices(p):
     from pdmp3_amd import api
     name, start = "48k", 4321
     assert start % p["hop"] != 0
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in MODES[:3]:
             tile = api.stft_tile(p["n_fft"], p["hop"], mode)[0]
@@ -182,10 +102,10 @@ def test_edges_of_the_tile_and_of_the_stream():
     tile = api.stft_tile(p["n_fft"], p["hop"], "complex")[0]
     assert tile == api.stft_tile(p["n_fft"], p["hop"], "log10")[0]
     name = "32k"
-    ix = tga._ref(name)[0]
+    ix = cg.ref(name)[0]
     j_all = aref.out_length(ix.samples, ix.rate, 16000)
     nb = p["n_fft"] // 2 + 1
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for f in (1, tile - 1, tile, tile + 1):
             clips = [(name, 777), (name, 0)]
@@ -228,10 +148,10 @@ def test_host_destinations():
     p, f = P16, 37
     clips = [(n, s) for n in ("48k", "22k", "16k-mono") for s in _starts(n, p, f)[1:4]]
     k, nb = len(clips), p["n_fft"] // 2 + 1
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
-        src = [(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips]
+        src = cg.src(clips)
         for mode in ("complex", "log10"):
             per = _per(p, mode) * f
             shape = (k, 1, nb, f, 2) if mode == "complex" else (k, 1, nb, f)
@@ -275,42 +195,42 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         for kind, mode in (("device", "complex"), ("numpy", "log10")):
             per = _per(p, mode) * f
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, nb, f, mode)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, calls.stft_inner(nb, f, mode))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_stft(src, f, mode=mode, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape((2, 1, nb, f, 2) if mode == "complex" else (2, 1, nb, f))
                 _check(good, sig, got, e.value.valid[[0, 2]], f, p, mode)
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, nb, f, "log10")
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, calls.stft_inner(nb, f, "log10"))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         nan_window = np.ones(400, dtype=np.float32)
         nan_window[123] = np.nan
         for bad_p in (dict(n_fft=401), dict(n_fft=2048), dict(hop=0), dict(hop=401), dict(win_length=401), dict(window=nan_window),
                       dict(floor=0.0), dict(width=65)):
             q = dict(p, **bad_p)
-            bb, bv = (big, view) if q["n_fft"] == 400 else _destination("device", 1, 1, q["n_fft"] // 2 + 1, f, "log10")
+            bb, bv = (big, view) if q["n_fft"] == 400 else cg.destination("device", 1, 1, calls.stft_inner(q["n_fft"] // 2 + 1, f, "log10"))
             with pytest.raises(RuntimeError):
                 dec.decode_clips_stft(src, f, mode="log10", out=bv, **q)
-            assert (tga._host(bb) == SENT).all()
+            assert (cg.host(bb) == SENT).all()
         with pytest.raises(RuntimeError):
-            dec.decode_clips_stft([(s["48k"], tga._ref("48k")[0], -1)], f, mode="log10", out=view, **p)
+            dec.decode_clips_stft([(s["48k"], cg.ref("48k")[0], -1)], f, mode="log10", out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_stft(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_stft(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -326,16 +246,16 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_around_it():
     pa, pb = dict(P16, window=wa), dict(P16, window=wb)
     small = [("32k", 500), ("8k", 1234)]
     large = [(n, s) for n in ("mixed/mono-stereo", "48k", "32k", "22k", "16k-mono", "8k") for s in (0, 999, 20001)]
-    fresh = tga._decoder()
+    fresh = cg.decoder()
     try:
-        audio_before, av = tga._run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
-        mel_before, mv = tgm._run(fresh, "device", small, 9, tgm.P16, "log10")
-        ix = tga._ref("48k")[0]
-        plain_before = fresh.decode_range(tga._streams()["48k"], ix, 33, 50).copy()
+        audio_before, av = calls.audio_run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        mel_before, mv = calls.mel_run(fresh, "device", small, 9, cases.MEL_P16, "log10")
+        ix = cg.ref("48k")[0]
+        plain_before = fresh.decode_range(cg.streams()["48k"], ix, 33, 50).copy()
         a_fresh, _ = _run(fresh, "device", small, 9, pa, "complex")
     finally:
         fresh.close()
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         a, va = _run(dec, "device", small, 9, pa, "complex")
         b, vb = _run(dec, "device", small, 9, pb, "complex")
@@ -358,11 +278,11 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_around_it():
         _run(dec, "device", [("48k", 10)], 17, P48, "log10")
         c, vc = _run(dec, "numpy", small, 9, pa, "complex")
         assert np.array_equal(a.view(np.uint32), c.view(np.uint32)) and np.array_equal(va, vc)
-        audio_after, av2 = tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        audio_after, av2 = calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
         assert np.array_equal(audio_before.view(np.uint32), audio_after.view(np.uint32)) and np.array_equal(av, av2)
-        mel_after, mv2 = tgm._run(dec, "device", small, 9, tgm.P16, "log10")
+        mel_after, mv2 = calls.mel_run(dec, "device", small, 9, cases.MEL_P16, "log10")
         assert np.array_equal(mel_before.view(np.uint32), mel_after.view(np.uint32)) and np.array_equal(mv, mv2)
-        plain_after = dec.decode_range(tga._streams()["48k"], tga._ref("48k")[0], 33, 50)
+        plain_after = dec.decode_range(cg.streams()["48k"], cg.ref("48k")[0], 33, 50)
         assert np.array_equal(plain_before, plain_after)
     finally:
         dec.close()
@@ -370,13 +290,13 @@ def test_one_decoder_through_small_large_small_and_the_other_calls_around_it():
 
 def test_return_types_and_empty_calls():
     import torch
-    src = [(tga._streams()["32k"], tga._ref("32k")[0], 1000)]
-    dec = tga._decoder()
+    src = [(cg.streams()["32k"], cg.ref("32k")[0], 1000)]
+    dec = cg.decoder()
     try:
         out, valid = dec.decode_clips_stft(src, 50)
         assert tuple(out.shape) == (1, 1, 201, 50) and out.is_cuda and out.dtype == torch.complex64 and valid[0] == 50
         sig = _signal(dec, [("32k", 1000)], 50, P16)
-        as_real = tga._host(torch.view_as_real(out))
+        as_real = cg.host(torch.view_as_real(out))
         _check([("32k", 1000)], sig, as_real, valid, 50, P16, "complex")
         plain, _ = _run(dec, "device", [("32k", 1000)], 50, P16, "complex")
         assert np.array_equal(as_real.view(np.uint32), plain.view(np.uint32))
@@ -386,7 +306,7 @@ def test_return_types_and_empty_calls():
         # a complex64 destination of the caller's
         z = torch.full((1, 1, 201, 50), complex(float(SENT), float(SENT)), dtype=torch.complex64, device="cuda")
         got, _ = dec.decode_clips_stft(src, 50, out=z)
-        assert got is z and np.array_equal(tga._host(torch.view_as_real(z)).view(np.uint32), plain.view(np.uint32))
+        assert got is z and np.array_equal(cg.host(torch.view_as_real(z)).view(np.uint32), plain.view(np.uint32))
         out, valid = dec.decode_clips_stft(src, 50, mode="magnitude", channels=2)
         assert tuple(out.shape) == (1, 2, 201, 50) and out.dtype == torch.float32
         out, valid = dec.decode_clips_stft([], 10)

@@ -7,25 +7,23 @@ within the two-stage bound derived in tests/clip_stft_long_ref.py -- every value
 and the output exactly 0 on silence in modes 0 - 2.  Destinations are filled with a sentinel first.  Each device step runs
 once; a clip's reference is computed once and shared by the modes.
 
-Streams and helpers: those of test_gpu_clip_audio.py, test_gpu_clip_mel.py and test_gpu_clip_stft.py."""
+Streams and helpers: tests/clip_gpu.py and tests/clip_gpu_calls.py."""
 import numpy as np
 import pytest
 
-import clip_audio_ref as aref
+import clip_forms_cases as cases
+import clip_gpu as cg
+import clip_gpu_calls as calls
 import clip_stft_long_ref as lref
 import clip_stft_ref as ref
 import clip_streams
-import test_gpu_clip_audio as tga
-import test_gpu_clip_mel as tgm
-import test_gpu_clip_stft as tgs
+from clip_gpu import GUARD, SENT, signal as _signal
+from clip_gpu_calls import STFT_LONG_PA as PA, STFT_MODES as MODES, mel_starts as _starts, stft_long_check as _check, stft_long_run as _run, stft_long_wants as _wants, stft_per as _per
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD, MODES = tgs.SENT, tgs.GUARD, tgs.MODES
-_signal, _starts, _rate, _destination, _per = tgm._signal, tgm._starts, tgm._rate, tgs._destination, tgs._per
 
 W1764 = (np.random.default_rng(1764).random(1764, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
-PA = dict(sample_rate=0, n_fft=2048, hop=512, channels=2)                  # the 48 kHz stream at its own rate, stereo
 PB = dict(sample_rate=22050, n_fft=2048, hop=441, channels=1, win_length=1764, window=W1764, normalized=True)
 PC = dict(sample_rate=0, n_fft=2048, hop=2048, channels=1)                 # the reduced tile
 PD = dict(sample_rate=0, n_fft=4096, hop=1024, channels=1)
@@ -34,59 +32,6 @@ PF = dict(sample_rate=0, n_fft=2048, hop=1, channels=1)
 W1920 = (np.random.default_rng(1920).random(1920, dtype=np.float32) * np.float32(1.5) - np.float32(0.25)).astype(np.float32)
 PG = dict(sample_rate=0, n_fft=4096, hop=1024, channels=2, win_length=1920, window=W1920, normalized=True)
 PH = dict(sample_rate=0, n_fft=4096, hop=4096, channels=2)
-FLOORS = {3: 1e-10, 4: 1e-10}
-
-
-def _run(dec, kind, clips, f, p, mode, floor=1e-10, offset=0, call="decode_clips_stft_long"):
-    """clips: (stream name, start) -> (host copy [k, c, nb, f(, 2)], valid)"""
-    k, c, nb = len(clips), p["channels"], p["n_fft"] // 2 + 1
-    per = _per(p, mode) * f
-    big, view = _destination(kind, k, c, nb, f, mode, offset=offset)
-    out, valid = getattr(dec, call)([(tga._streams()[n], tga._ref(n)[0], s) for n, s in clips], f, mode=mode, floor=floor, out=view, **p)
-    assert out is view
-    host = tga._host(big)
-    assert (host[:offset] == SENT).all()
-    host = host[offset:].reshape(k, c, per + GUARD)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    return host[:, :, :per].reshape((k, c, nb, f, 2) if mode == "complex" else (k, c, nb, f)), valid
-
-
-def _wants(clips, sig, f, p):
-    """per clip {mode: (out, bound)}: the definition on the product's own signal, once for all modes"""
-    return [lref.stft_all(y, s0, s, f, p["n_fft"], p["hop"], FLOORS, p.get("win_length"), p.get("window"), p.get("normalized", False))
-            for (n, s), (s0, y) in zip(clips, sig)]
-
-
-def _check(clips, sig, wants, got, valid, f, p, mode):
-    """every row against the definition; -> worst error / bound over the rows that hold signal"""
-    worst = 0.0
-    m = MODES.index(mode)
-    K = p["n_fft"] // 2 + 1
-    for i, (n, s) in enumerate(clips):
-        ix = tga._ref(n)[0]
-        j_all = aref.out_length(ix.samples, ix.rate, _rate(p, n))
-        assert int(valid[i]) == ref.valid(j_all, s, p["hop"], f), (n, s, valid[i])
-        want, bound = wants[i][m]
-        assert want.shape == got[i].shape
-        err = np.abs(got[i].astype(np.float64) - want)
-        assert (err <= bound).all(), "%s at %d, mode %s: error beyond the bound by %g at %s" % (
-            n, s, mode, float((err - bound).max()), np.unravel_index(np.argmax(err - bound), err.shape))
-        nz = bound > 0
-        if m <= 2:
-            assert (got[i][~nz] == 0.0).all()
-        if m == 0:
-            assert (got[i][:, 0, :, 1] == 0.0).all() and (got[i][:, K - 1, :, 1] == 0.0).all()     # Im of bins 0 and N / 2
-        if np.abs(sig[i][1]).sum() > 0 and nz.any():
-            r = float((err[nz] / bound[nz]).max())
-            assert 0.0 < r <= 1.0, (n, s, mode, r)
-            worst = max(worst, r)
-            if m == 0:
-                # Im is far above the bound somewhere, so its sign (and a swap with Re) shows in the comparison above
-                assert (np.abs(want[..., 1]) > 100.0 * bound[..., 1])[nz[..., 1]].any()
-                assert (np.abs(want[..., 0] - want[..., 1]) > 100.0 * bound[..., 0])[nz[..., 0]].any()
-    return worst
-
-
 CASES = {
     "a-48k-stereo-2048-hop-512": (PA, "48k", 21, "N2048-tile16"),       # one full tile and a partial one
     "b-22k-2048-hop-441-own-window": (PB, "22k", 19, "N2048-tile16"),
@@ -108,7 +53,7 @@ def test_against_binary64_on_the_products_own_signal(case):
     from pdmp3_amd import api
     p, name, f, path = CASES[case]
     clips = [(name, s) for s in _starts(name, p, f)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, clips, f, p)
         wants = _wants(clips, sig, f, p)
@@ -136,7 +81,7 @@ def test_frames_are_frames_and_mode_0_rederives_the_others_bit_for_bit(p):
     tile = api.stft_long_plan(p["n_fft"], p["hop"], "complex")[0]
     fs = [0, 1, tile - 1, tile, tile + 1, 2 * tile - 1, 2 * tile, 2 * tile + 2]
     f_long = 2 * tile + 4
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         outs = {}
         for mode in MODES[:3]:
@@ -159,7 +104,7 @@ def test_frames_are_frames_and_mode_0_rederives_the_others_bit_for_bit(p):
 def test_slices_of_a_batch_are_the_batchs_slices():
     p, f = dict(PB, sample_rate=16000), 19
     clips = [(n, s) for n in ("48k", "22k", "16k-mono") for s in (0, 5000, 23457)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in ("complex", "log10"):
             whole, valid = _run(dec, "device", clips, f, p, mode)
@@ -178,47 +123,47 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 100), ("22k", 3000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         sig = _signal(dec, good, f, p)
         wants = _wants(good, sig, f, p)
         for kind, mode in (("device", "complex"), ("numpy", "log10")):
             per = _per(p, mode) * f
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = _destination(kind, 3, 1, nb, f, mode)
-                src = [(s["48k"], tga._ref("48k")[0], 100), mid, (s["22k"], tga._ref("22k")[0], 3000)]
+                big, view = cg.destination(kind, 3, 1, calls.stft_inner(nb, f, mode))
+                src = [(s["48k"], cg.ref("48k")[0], 100), mid, (s["22k"], cg.ref("22k")[0], 3000)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_stft_long(src, f, mode=mode, out=view, **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all()
                 assert (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape((2, 1, nb, f, 2) if mode == "complex" else (2, 1, nb, f))
                 _check(good, sig, wants, got, e.value.valid[[0, 2]], f, p, mode)
         # bad arguments: nothing is written
-        big, view = _destination("device", 1, 1, nb, f, "log10")
-        src = [(s["48k"], tga._ref("48k")[0], 0)]
+        big, view = cg.destination("device", 1, 1, calls.stft_inner(nb, f, "log10"))
+        src = [(s["48k"], cg.ref("48k")[0], 0)]
         nan_window = np.ones(2048, dtype=np.float32)
         nan_window[123] = np.nan
         for bad_p in (dict(n_fft=1024), dict(n_fft=8192), dict(n_fft=400), dict(hop=0), dict(hop=2049), dict(win_length=2049), dict(window=nan_window),
                       dict(floor=0.0), dict(width=65)):
             q = dict(p, **bad_p)
-            bb, bv = (big, view) if q["n_fft"] == 2048 else _destination("device", 1, 1, q["n_fft"] // 2 + 1, f, "log10")
+            bb, bv = (big, view) if q["n_fft"] == 2048 else cg.destination("device", 1, 1, calls.stft_inner(q["n_fft"] // 2 + 1, f, "log10"))
             with pytest.raises(RuntimeError):
                 dec.decode_clips_stft_long(src, f, mode="log10", out=bv, **q)
-            assert (tga._host(bb) == SENT).all()
+            assert (cg.host(bb) == SENT).all()
         with pytest.raises(RuntimeError):
-            dec.decode_clips_stft_long([(s["48k"], tga._ref("48k")[0], -1)], f, mode="log10", out=view, **p)
+            dec.decode_clips_stft_long([(s["48k"], cg.ref("48k")[0], -1)], f, mode="log10", out=view, **p)
         with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-            dec.decode_clips_stft_long(src + [(s["32k"], tga._ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
-        assert (tga._host(big) == SENT).all()
+            dec.decode_clips_stft_long(src + [(s["32k"], cg.ref("32k")[0], 0)], f, **dict(p, sample_rate=0))
+        assert (cg.host(big) == SENT).all()
         # the call of section 13 keeps refusing this length
         with pytest.raises(RuntimeError):
             dec.decode_clips_stft(src, f, mode="log10", out=view, **p)
-        assert (tga._host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -228,8 +173,8 @@ def test_an_odd_float_destination_return_types_and_empty_calls():
     import torch
     p, f = PD, 10
     clips = [("48k", 1000)]
-    src = [(tga._streams()["48k"], tga._ref("48k")[0], 1000)]
-    dec = tga._decoder()
+    src = [(cg.streams()["48k"], cg.ref("48k")[0], 1000)]
+    dec = cg.decoder()
     try:
         plain, _ = _run(dec, "device", clips, f, p, "complex")
         # a row at an odd float: the pairs' 8-byte stores are 4-byte aligned there, the values the same
@@ -237,7 +182,7 @@ def test_an_odd_float_destination_return_types_and_empty_calls():
         assert np.array_equal(odd.view(np.uint32), plain.view(np.uint32)) and np.abs(plain).sum() > 0
         out, valid = dec.decode_clips_stft_long(src, f, **p)
         assert tuple(out.shape) == (1, 1, 2049, f) and out.is_cuda and out.dtype == torch.complex64 and valid[0] == f
-        assert np.array_equal(tga._host(torch.view_as_real(out)).view(np.uint32), plain.view(np.uint32))
+        assert np.array_equal(cg.host(torch.view_as_real(out)).view(np.uint32), plain.view(np.uint32))
         out, valid = dec.decode_clips_stft_long(src, f, mode="magnitude", channels=2)
         assert tuple(out.shape) == (1, 2, 1025, f) and out.dtype == torch.float32
         out, valid = dec.decode_clips_stft_long([], 10)
@@ -259,24 +204,24 @@ def test_one_decoder_through_the_long_call_the_other_calls_and_the_long_call_aga
     small = [("32k", 500), ("8k", 1234)]
     p16 = dict(pa, sample_rate=16000)
     p16b = dict(pb, sample_rate=16000)
-    fresh = tga._decoder()
+    fresh = cg.decoder()
     try:
-        stft_before, sv = tgs._run(fresh, "device", small, 9, tgs.P16, "complex")
-        mel_before, mv = tgm._run(fresh, "device", small, 9, tgm.P16, "log10")
-        audio_before, av = tga._run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
-        plain_before = fresh.decode_range(tga._streams()["48k"], tga._ref("48k")[0], 33, 50).copy()
+        stft_before, sv = calls.stft_run(fresh, "device", small, 9, cases.STFT_P16, "complex")
+        mel_before, mv = calls.mel_run(fresh, "device", small, 9, cases.MEL_P16, "log10")
+        audio_before, av = calls.audio_run(fresh, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        plain_before = fresh.decode_range(cg.streams()["48k"], cg.ref("48k")[0], 33, 50).copy()
     finally:
         fresh.close()
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         a, va = _run(dec, "device", small, 9, p16, "complex")
-        stft_after, sv2 = tgs._run(dec, "device", small, 9, tgs.P16, "complex")
+        stft_after, sv2 = calls.stft_run(dec, "device", small, 9, cases.STFT_P16, "complex")
         assert np.array_equal(stft_before.view(np.uint32), stft_after.view(np.uint32)) and np.array_equal(sv, sv2)
-        mel_after, mv2 = tgm._run(dec, "device", small, 9, tgm.P16, "log10")
+        mel_after, mv2 = calls.mel_run(dec, "device", small, 9, cases.MEL_P16, "log10")
         assert np.array_equal(mel_before.view(np.uint32), mel_after.view(np.uint32)) and np.array_equal(mv, mv2)
-        audio_after, av2 = tga._run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
+        audio_after, av2 = calls.audio_run(dec, "device", [("48k", 700), ("22k", 9000)], 6000, 16000, 1)
         assert np.array_equal(audio_before.view(np.uint32), audio_after.view(np.uint32)) and np.array_equal(av, av2)
-        plain_after = dec.decode_range(tga._streams()["48k"], tga._ref("48k")[0], 33, 50)
+        plain_after = dec.decode_range(cg.streams()["48k"], cg.ref("48k")[0], 33, 50)
         assert np.array_equal(plain_before, plain_after)
         b, vb = _run(dec, "device", small, 9, p16b, "complex")
         assert not np.array_equal(a, b) and np.array_equal(va, vb)

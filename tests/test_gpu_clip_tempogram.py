@@ -11,17 +11,15 @@ import functools
 import numpy as np
 import pytest
 
-import clip_audio_ref as aref
+import clip_gpu as cg
 import clip_mel_long_ref as mlref
 import clip_mel_ref as mref
 import clip_streams
 import clip_tempogram_ref as ref
-import test_gpu_clip_audio as tga
-import test_gpu_clip_stft as tgs
+from clip_gpu import GUARD, SENT
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-SENT, GUARD = tgs.SENT, tgs.GUARD
 MODES = ("onset", "tempogram", "tempo")
 P0 = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384, channels=1)      # the defaults, spelled out
 
@@ -39,23 +37,7 @@ def _periodic():
     return mp3, api.StreamIndex(mp3, ISO_LSF)
 
 
-def _source(name):
-    if name == "periodic":
-        return _periodic()
-    return tga._streams()[name], tga._ref(name)[0]
-
-
-def _src(clips):
-    return [_source(n) + (s,) for n, s in clips]
-
-
-def _rate(p, name):
-    return p["sample_rate"] or _source(name)[1].rate
-
-
-def _j_all(p, name):
-    ix = _source(name)[1]
-    return aref.out_length(ix.samples, ix.rate, _rate(p, name))
+cg.STREAMS["periodic/44k"] = _periodic
 
 
 def _shape(p, f, mode):
@@ -67,12 +49,12 @@ def _run(dec, kind, clips, f, p, mode, **kw):
     row are looked at"""
     k, c = len(clips), p["channels"]
     nb, inner = _shape(p, f, mode)
-    big, view = tgs._destination(kind, k, c, nb, inner, "power")
+    big, view = cg.destination(kind, k, c, (nb, inner))
     dst = view if mode == "tempogram" else view[:, :, 0]
-    out, valid = dec.decode_clips_tempogram(_src(clips), f, out_mode=mode, out=dst, **dict(p, **kw))
+    out, valid = dec.decode_clips_tempogram(cg.src(clips), f, out_mode=mode, out=dst, **dict(p, **kw))
     assert out is dst
     per = nb * inner
-    host = tga._host(big).reshape(k, c, per + GUARD)
+    host = cg.host(big).reshape(k, c, per + GUARD)
     assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
     got = host[:, :, :per].copy()
     return (got.reshape(k, c, nb, inner) if mode == "tempogram" else got), valid
@@ -81,13 +63,13 @@ def _run(dec, kind, clips, f, p, mode, **kw):
 def _mel(dec, clips, f, p, floor=1e-10):
     """decode_clips_mel_long's log10 values of the clips -> [k, c, n_mels, f]"""
     q = {a: p[a] for a in ("sample_rate", "n_fft", "hop", "n_mels", "channels")}
-    out, valid = dec.decode_clips_mel_long(_src(clips), f, mode="log10", floor=floor, **q)
-    return tga._host(out)
+    out, valid = dec.decode_clips_mel_long(cg.src(clips), f, mode="log10", floor=floor, **q)
+    return cg.host(out)
 
 
 def _valid(clips, valid, f, p):
     for i, (name, s) in enumerate(clips):
-        assert int(valid[i]) == ref.valid(_j_all(p, name), s, p["hop"], f), (name, s, valid[i])
+        assert int(valid[i]) == ref.valid(cg.j_all(p, name), s, p["hop"], f), (name, s, valid[i])
 
 
 # ---- mode 0 against the definition on decode_clips_mel_long's own output ----
@@ -103,9 +85,9 @@ ONSET_CASES = {
 def test_onset_against_binary64_on_the_log_mel_calls_own_values(case):
     name, p = ONSET_CASES[case]
     f, lag, hop = 261, p["lag"], p["hop"]              # (a workgroup of 256 lanes and five more)
-    j_all = _j_all(p, name)
+    j_all = cg.j_all(p, name)
     clips = [(name, s) for s in (lag * hop, 12345, j_all - 200 * hop - 3)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         l = _mel(dec, [(n, s - lag * hop) for n, s in clips], f + lag, p)
         worst = 0.0
@@ -131,10 +113,10 @@ def test_onset_against_binary64_on_the_log_mel_calls_own_values(case):
 def test_onset_against_the_full_chain_at_a_streams_start_and_end(case):
     name, p = ONSET_CASES[case]
     f, lag, hop, n, c, floor = 11, p["lag"], p["hop"], p["n_fft"], p["channels"], 1e-6
-    j_all = _j_all(p, name)
+    j_all = cg.j_all(p, name)
     clips = [(name, 0), (name, hop - 1), (name, j_all - 4 * hop - 7)]
-    w = mref.filterbank(_rate(p, name), n, p["n_mels"], 0.0, 0.0, "slaney", "slaney")
-    dec = tga._decoder()
+    w = mref.filterbank(cg.rate(p, name), n, p["n_mels"], 0.0, 0.0, "slaney", "slaney")
+    dec = cg.decoder()
     try:
         got, valid = _run(dec, "device", clips, f, p, "onset", floor=floor)
         _valid(clips, valid, f, p)
@@ -145,7 +127,7 @@ def test_onset_against_the_full_chain_at_a_streams_start_and_end(case):
             first = s - lag * hop                        # the centre of the first log-mel frame: before sample 0 in clips 0 and 1
             s0 = max(0, first - n // 2)
             y = np.full((1, c, t), SENT, dtype=np.float32)
-            dec.decode_clips_audio([_source(nm) + (s0,)], t, p["sample_rate"], c, out=y)
+            dec.decode_clips_audio([cg.source(nm) + (s0,)], t, p["sample_rate"], c, out=y)
             l, dl = mlref.mel_all(y[0], s0, first, f + lag, n, hop, w, floor, modes=(2,))[2]
             for ch in range(c):
                 want, bound = ref.onset(l[ch], lag, p["max_size"])
@@ -168,8 +150,8 @@ def test_tempogram_against_binary64_on_the_onset_modes_own_values(wt, hop):
     name = "44k-mono"
     p = dict(P0, win_length=wt, hop=hop, n_mels=40, channels=2, lag=2, max_size=3)
     wh = wt // 2
-    j_all = _j_all(p, name)
-    dec = tga._decoder()
+    j_all = cg.j_all(p, name)
+    dec = cg.decoder()
     try:
         worst, dead = 0.0, 0
         for f in (7, 9, 17):
@@ -204,7 +186,7 @@ def test_a_clip_is_the_slice_of_a_longer_one():
     name, f = "44k-mono", 13
     p = dict(P0, win_length=272, n_mels=40, channels=1, max_size=3)
     hop = p["hop"]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for s, a in ((20000, 1), (20000, 9), (200 * hop + 5, 16), (136 * hop, 3)):
             short, long = [(name, s)], [(name, s - a * hop)]
@@ -222,10 +204,10 @@ def test_a_clip_is_the_slice_of_a_longer_one():
 def test_tempo_of_a_periodic_stream_is_its_period():
     p = dict(P0, sample_rate=0)
     f, start = 200, 250 * 512
-    clips = [("periodic", start)]
-    assert _source("periodic")[1].rate == 44100
+    clips = [("periodic/44k", start)]
+    assert cg.source("periodic/44k")[1].rate == 44100
     pr, first = ref.prior(44100, 512, 384)
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         tg, valid = _run(dec, "device", clips, f, p, "tempogram")
         got, v2 = _run(dec, "device", clips, f, p, "tempo")
@@ -246,12 +228,12 @@ def test_tempo_of_a_periodic_stream_is_its_period():
 def test_tempo_is_the_definition_on_the_tempogram_modes_own_values():
     """noise streams: no tempo is claimed; plane by plane the four floats are the definition's on mode 1's output, the lag exact
     where the margin decides it and within the bound of the maximum elsewhere"""
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for p, name, f in ((dict(P0, channels=2, sample_rate=0), "48k", 57), (dict(P0, win_length=16, n_mels=40, lag=2, max_size=3), "22k", 9),
                            (dict(P0, win_length=1024, hop=64, n_mels=40, start_bpm=300.0, std_bpm=2.0, max_tempo=4000.0), "44k-mono", 17)):
-            wt, hop, sr = p["win_length"], p["hop"], _rate(p, name)
-            clips = [(name, s) for s in ((wt // 2 + 16) * hop, (wt // 2) * hop + 60001, _j_all(p, name) - 5 * hop)]
+            wt, hop, sr = p["win_length"], p["hop"], cg.rate(p, name)
+            clips = [(name, s) for s in ((wt // 2 + 16) * hop, (wt // 2) * hop + 60001, cg.j_all(p, name) - 5 * hop)]
             kw = {a: p[a] for a in ("start_bpm", "std_bpm", "max_tempo") if a in p}
             pr, first = ref.prior(sr, hop, wt, **kw)
             tg, valid = _run(dec, "device", clips, f, p, "tempogram")
@@ -280,7 +262,7 @@ def test_twice_the_same_and_alone_as_in_a_batch():
     p = dict(P0, channels=2, win_length=272, n_mels=40)
     f = 9
     batch = [("22k", s) for s in (136 * 512 + 1000, 100000, 136 * 512, 123456, 90000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for mode in MODES:
             a, va = _run(dec, "device", batch, f, p, mode)
@@ -302,50 +284,50 @@ def test_a_refused_clip_in_the_middle_of_a_batch_and_bad_arguments():
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
-    mix = tga._ref("mixed/mpeg1-lsf")[0]
+    mix = cg.ref("mixed/mpeg1-lsf")[0]
     assert not mix.one_format
-    s = tga._streams()
+    s = cg.streams()
     good = [("48k", 9000), ("22k", 30000)]
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         for kind, mode in (("device", "onset"), ("numpy", "tempogram"), ("device", "tempo")):
             want, valid = _run(dec, "device", good, f, p, mode)
             nb, inner = _shape(p, f, mode)
             per = nb * inner
             for mid, exc, code in (((s["mixed/mpeg1-lsf"], mix, 0), api.MixedFormat, -3), ((bad, bix, 10), api.RingReplay, -2)):
-                big, view = tgs._destination(kind, 3, 1, nb, inner, "power")
-                src = [_source("48k") + (9000,), mid, _source("22k") + (30000,)]
+                big, view = cg.destination(kind, 3, 1, (nb, inner))
+                src = [cg.source("48k") + (9000,), mid, cg.source("22k") + (30000,)]
                 with pytest.raises(exc) as e:
                     dec.decode_clips_tempogram(src, f, out_mode=mode, out=view if mode == "tempogram" else view[:, :, 0], **p)
-                host = tga._host(big).reshape(3, 1, per + GUARD)
+                host = cg.host(big).reshape(3, 1, per + GUARD)
                 assert e.value.valid[1] == code and (host[1] == SENT).all() and (host[:, :, per:] == SENT).all()
                 got = host[[0, 2], :, :per].reshape(want.shape)
                 assert np.array_equal(got.view(np.uint32), want.view(np.uint32)) and np.array_equal(e.value.valid[[0, 2]], valid)
         # bad arguments: nothing is written
-        src = [_source("48k") + (9000,)]
+        src = [cg.source("48k") + (9000,)]
         for mode in MODES:
             nb, inner = _shape(p, f, mode)
-            big, view = tgs._destination("device", 1, 1, nb, inner, "power")
+            big, view = cg.destination("device", 1, 1, (nb, inner))
             dst = view if mode == "tempogram" else view[:, :, 0]
             for bad_p in (dict(lag=0), dict(lag=17), dict(max_size=2), dict(max_size=11), dict(start_bpm=0.0), dict(std_bpm=float("nan")),
                           dict(max_tempo=float("inf")), dict(max_tempo=1.0), dict(n_fft=1024), dict(hop=0), dict(n_mels=0), dict(floor=0.0),
                           dict(f_max=12000.0), dict(width=65)):
                 with pytest.raises(RuntimeError):
                     dec.decode_clips_tempogram(src, f, out_mode=mode, out=dst, **dict(p, **bad_p))
-                assert (tga._host(big) == SENT).all(), (mode, bad_p)
+                assert (cg.host(big) == SENT).all(), (mode, bad_p)
             with pytest.raises(RuntimeError):
-                dec.decode_clips_tempogram([_source("48k") + (-1,)], f, out_mode=mode, out=dst, **p)
+                dec.decode_clips_tempogram([cg.source("48k") + (-1,)], f, out_mode=mode, out=dst, **p)
             with pytest.raises(RuntimeError):            # (rate 0 and clips of different rates)
-                dec.decode_clips_tempogram(src + [_source("32k") + (0,)], f, out_mode=mode, **dict(p, sample_rate=0))
-            assert (tga._host(big) == SENT).all()
-        big, view = tgs._destination("device", 1, 1, 1, f, "power")
+                dec.decode_clips_tempogram(src + [cg.source("32k") + (0,)], f, out_mode=mode, **dict(p, sample_rate=0))
+            assert (cg.host(big) == SENT).all()
+        big, view = cg.destination("device", 1, 1, (1, f))
         for mode in ("bpm", 3, -1):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_tempogram(src, f, out_mode=mode, out=view[:, :, 0], **p)
         for wt in (14, 17, 1026):
             with pytest.raises(RuntimeError):
                 dec.decode_clips_tempogram(src, f, out_mode="onset", out=view[:, :, 0], **dict(p, win_length=wt))
-        assert (tga._host(big) == SENT).all()
+        assert (cg.host(big) == SENT).all()
     finally:
         dec.close()
         bix.close()
@@ -358,14 +340,14 @@ def test_more_clips_than_one_grid():
     than rows 0 .. 4, one of them behind the end"""
     name, k, f = "32k", 32768 + 5, 1
     p = dict(P0, sample_rate=0, hop=64, n_mels=8, lag=1, max_size=3)
-    mp3, ix = _source(name)
-    j_all = _j_all(p, name)
+    mp3, ix = cg.source(name)
+    j_all = cg.j_all(p, name)
     starts = [1000 + 3001 * i for i in range(62)] + [j_all + 2048 + 9, j_all - 5]
     assert starts[61] + 2048 < j_all
     twin = (np.arange(k, dtype=np.int64) * 7) % 62
     twin[32768:] = [62, 63, 61, 60, 59]
     assert not np.any(twin[32768:] == twin[:5])
-    dec = tga._decoder()
+    dec = cg.decoder()
     try:
         first = [(name, s) for s in starts]
         l = _mel(dec, [(n, s - 64) for n, s in first], 2, p)
@@ -374,9 +356,9 @@ def test_more_clips_than_one_grid():
             want, bound = ref.onset(l[i, 0], 1, 3)
             assert abs(float(base[i, 0, 0]) - want[0]) <= bound[0], i
         assert list(valid64[61:]) == [1, 0, 1] and base[62, 0, 0] == 0.0 and np.unique(base[:62, 0, 0]).size > 8
-        big, view = tgs._destination("device", k, 1, 1, f, "power")
+        big, view = cg.destination("device", k, 1, (1, f))
         out, valid = dec.decode_clips_tempogram([(mp3, ix, int(starts[t])) for t in twin], f, out_mode="onset", out=view[:, :, 0], **p)
-        host = tga._host(big).reshape(k, f + GUARD)
+        host = cg.host(big).reshape(k, f + GUARD)
         assert (host[:, f:] == SENT).all(), "written behind a row's floats"
         assert np.array_equal(valid, valid64[twin]) and list(valid[32768:]) == [0, 1, 1, 1, 1]
         bad = np.flatnonzero(host[:, 0].view(np.uint32) != base[twin, 0, 0].view(np.uint32))
@@ -387,28 +369,28 @@ def test_more_clips_than_one_grid():
 
 def test_return_types_defaults_and_empty_calls():
     import torch
-    src = [_source("22k") + (120000,)]
-    dec = tga._decoder()
+    src = [cg.source("22k") + (120000,)]
+    dec = cg.decoder()
     try:
         out, valid = dec.decode_clips_tempogram(src, 20)
         assert tuple(out.shape) == (1, 1, 384, 20) and out.is_cuda and out.dtype == torch.float32 and valid[0] == 20 and valid.dtype == np.int64
         plain, _ = _run(dec, "device", [("22k", 120000)], 20, P0, "tempogram")        # (the defaults, spelled out)
-        assert np.array_equal(tga._host(out).view(np.uint32), plain.view(np.uint32)) and (plain[0, 0, 0] == 1.0).all()
+        assert np.array_equal(cg.host(out).view(np.uint32), plain.view(np.uint32)) and (plain[0, 0, 0] == 1.0).all()
         out, valid = dec.decode_clips_tempogram(src, 20, out_mode="onset", channels=2)
-        assert tuple(out.shape) == (1, 2, 20) and (tga._host(out) >= 0).all()
+        assert tuple(out.shape) == (1, 2, 20) and (cg.host(out) >= 0).all()
         out, valid = dec.decode_clips_tempogram(src, 20, out_mode="tempo")
-        assert tuple(out.shape) == (1, 1, 4) and 8 < tga._host(out)[0, 0, 1] < 384
+        assert tuple(out.shape) == (1, 1, 4) and 8 < cg.host(out)[0, 0, 1] < 384
         pinned = torch.full((1, 1, 4), float(SENT)).pin_memory()
         out2, _ = dec.decode_clips_tempogram(src, 20, out_mode="tempo", out=pinned)
-        assert np.array_equal(pinned.numpy().view(np.uint32), tga._host(out).view(np.uint32))
+        assert np.array_equal(pinned.numpy().view(np.uint32), cg.host(out).view(np.uint32))
         for mode, shape in (("onset", (0, 1, 10)), ("tempogram", (0, 1, 384, 10)), ("tempo", (0, 1, 4))):
             out, valid = dec.decode_clips_tempogram([], 10, out_mode=mode)
             assert tuple(out.shape) == shape and valid.size == 0
         for mode, shape in (("onset", (1, 1, 0)), ("tempogram", (1, 1, 384, 0))):
             out, valid = dec.decode_clips_tempogram(src, 0, out_mode=mode)
             assert tuple(out.shape) == shape and valid[0] == 0
-        big, view = tgs._destination("device", 1, 1, 1, 4, "power")
+        big, view = cg.destination("device", 1, 1, (1, 4))
         out, valid = dec.decode_clips_tempogram(src, 0, out_mode="tempo", out=view[:, :, 0])
-        assert valid[0] == 0 and (tga._host(big) == SENT).all()                       # (no frames: nothing but valid is written)
+        assert valid[0] == 0 and (cg.host(big) == SENT).all()                       # (no frames: nothing but valid is written)
     finally:
         dec.close()

@@ -12,44 +12,17 @@ LSF; non-strict short-heavy streams for the scfsi case; low bit rates for H6; bi
 one-thread scan builds; mono runs inside stereo; MPEG-1 and LSF frames in one stream) and one clip of 8400 frames, longer
 than the decoder's 8192-frame window, from a stream of the C3 configuration (320 kbps joint stereo, 9600 frames: as long as
 the oracle's restatement, 0.5 ms a frame on the host, can be run here) -- goes to pageable, pinned and device memory."""
-import functools
 import zlib
 
 import numpy as np
 import pytest
 
+import clip_gpu as cg
 import clip_streams
 from clip_streams import ISO_LSF
-from util import SENTINEL
+from util import GUARD, SENTINEL
 
 pytestmark = pytest.mark.gpu
-GUARD = 64                                        # sentinel values behind every clip's place
-
-
-@functools.lru_cache(maxsize=None)
-def _streams():
-    from pdmp3_amd.packer import packer
-    s = clip_streams.random_streams(range(1, 9), (200, 420))
-    s += clip_streams.scfsi_streams(400) + clip_streams.h6_streams(400)
-    s += clip_streams.corrupted_streams(range(3), 360) + clip_streams.mixed_streams(400)
-    s.append(("c3-config", packer.generate(n_frames=9600, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14), 0))
-    return s
-
-
-@functools.lru_cache(maxsize=None)
-def _ref(k):
-    """(index, whole-stream decode) of stream k, every switch but PDMP3_ISO_LSF off (one decoder takes the whole batch)"""
-    from pdmp3_amd import api
-    name, mp3, _ = _streams()[k]
-    ix = api.StreamIndex(mp3, ISO_LSF)
-    b = api.BulkDecoder(threads=2)
-    try:
-        b.set_quirks(ISO_LSF)
-        whole = b.decode(mp3)
-    finally:
-        b.close()
-    assert whole.nbytes == ix.pcm_offsets[-1]
-    return ix, whole
 
 
 _ORACLE = {}
@@ -58,11 +31,11 @@ _ORACLE = {}
 def _oracle(oracle, k):
     """the oracle's whole-stream output of stream k and what to make of a difference (fuzz_gpu.py's exemptions)"""
     if k not in _ORACLE:
-        name, mp3, _ = _streams()[k]
+        name, mp3, _ = clip_streams.gpu_streams()[k]
         want = np.frombuffer(oracle.decode_buffer_like_cli_iso(mp3, ISO_LSF), dtype=np.int16)
         undefined = oracle.last_undefined
         peak = None
-        ix, whole = _ref(k)
+        ix, whole = cg.frames_ref(k)
         if not undefined and want.shape == whole.shape and np.abs(want.astype(np.int32) - whole.astype(np.int32)).max(initial=0) > 1:
             _, sp_t, sd_t = oracle.decode_buffer_like_cli_iso(mp3, ISO_LSF, tap_frames=ix.frames + 8)
             _, f32 = oracle.decode_f32(sp_t, sd_t)
@@ -75,9 +48,9 @@ def _clips():
     """(stream, first, count): four per stream -- two at random places, and at the start, at the last frame, past the end
     and empty ones spread over the streams -- and the long one"""
     out = []
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     for k, (name, mp3, _) in enumerate(streams[:-1]):
-        ix, _ = _ref(k)
+        ix, _ = cg.frames_ref(k)
         rs = np.random.RandomState(zlib.crc32(name.encode()))
         edge = [(0, 30), (ix.frames - 1, 5), (ix.frames + 10, 5), (ix.frames // 3, 0)][k % 4]
         out += [(k, int(rs.randint(0, ix.frames)), int(rs.randint(1, 120))) for _ in range(3)] + [(k,) + edge]
@@ -85,24 +58,9 @@ def _clips():
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def _halo(k, first, count):
-    """the first frame the host hook decodes the clip from (pdmp3_amd_bulk_parse_range: the same index and halo rule)"""
-    from pdmp3_amd import api
-    name, mp3, _ = _streams()[k]
-    ix, _ = _ref(k)
-    b = api.BulkDecoder(threads=2, parse_only=True)
-    try:
-        b.set_quirks(ISO_LSF)
-        f0, _, _ = b.parse_range(mp3, ix, first, count)
-    finally:
-        b.close()
-    return f0
-
-
 def _check_clip(oracle, k, first, count, got_bytes, seg, what):
     """seg: the clip's place and the guard behind it (int16 numpy)"""
-    ix, whole = _ref(k)
+    ix, whole = cg.frames_ref(k)
     a, b = ix.clamp(first, count)
     lo, hi = int(ix.pcm_offsets[a]) // 2, int(ix.pcm_offsets[b]) // 2
     assert got_bytes == 2 * (hi - lo), (what, k, first, count)
@@ -140,20 +98,20 @@ def _sentinel_segments(kind, sizes):
 @pytest.mark.parametrize("kind", ["pageable", "pinned", "device"])
 def test_a_batch_of_clips_is_the_whole_stream_sliced(oracle, kind):
     from pdmp3_amd import api
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     clips = _clips()
     assert len(clips) >= 64 and len(set(k for k, _, _ in clips)) >= 16
     sizes = []
     for k, first, count in clips:
-        ix, _ = _ref(k)
+        ix, _ = cg.frames_ref(k)
         a, b = ix.clamp(first, count)
         sizes.append(int(ix.pcm_offsets[b] - ix.pcm_offsets[a]) // 2)
-    assert max(b - a for (k, f, c) in clips for a, b in [_ref(k)[0].clamp(f, c)]) > 8192
+    assert max(b - a for (k, f, c) in clips for a, b in [cg.frames_ref(k)[0].clamp(f, c)]) > 8192
     owner, views, starts = _sentinel_segments(kind, sizes)
     dec = api.BulkDecoder(threads=2)
     try:
         dec.set_quirks(ISO_LSF)
-        got = dec.decode_clips([(streams[k][1], _ref(k)[0], first, count) for k, first, count in clips], views)
+        got = dec.decode_clips([(streams[k][1], cg.frames_ref(k)[0], first, count) for k, first, count in clips], views)
         stats = dec.clip_stats()
     finally:
         dec.close()
@@ -168,8 +126,8 @@ def test_a_batch_of_clips_is_the_whole_stream_sliced(oracle, kind):
         seg = host[starts[i]:starts[i] + sizes[i] + GUARD]
         r = _check_clip(oracle, k, first, count, int(got[i]), seg, kind)
         seen[r] = seen.get(r, 0) + 1
-    kept = sum(b - a for (k, f, c) in clips for a, b in [_ref(k)[0].clamp(f, c)])
-    halo = sum(_ref(k)[0].clamp(f, c)[0] - _halo(k, f, c) for k, f, c in clips if _ref(k)[0].clamp(f, c)[1] > _ref(k)[0].clamp(f, c)[0])
+    kept = sum(b - a for (k, f, c) in clips for a, b in [cg.frames_ref(k)[0].clamp(f, c)])
+    halo = sum(cg.frames_ref(k)[0].clamp(f, c)[0] - cg.halo(k, f, c) for k, f, c in clips if cg.frames_ref(k)[0].clamp(f, c)[1] > cg.frames_ref(k)[0].clamp(f, c)[0])
     print("%s: %d clips, %s; clip_stats %s, kept %d, halo %d" % (kind, len(clips), seen, stats, kept, halo))
     assert stats == (kept, halo)
     assert seen.get("ok", 0) >= 50
@@ -181,9 +139,9 @@ def test_a_batch_of_clips_is_the_whole_stream_sliced(oracle, kind):
 def test_rows_of_one_array(oracle, kind):
     """out = one [K, stride] array whose rows are not 16-byte aligned (stride odd): the rows' gaps stay the sentinel"""
     from pdmp3_amd import api
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     clips = _clips()[:-1]
-    stride = 1 + GUARD + max(int(_ref(k)[0].pcm_offsets[_ref(k)[0].clamp(f, c)[1]] - _ref(k)[0].pcm_offsets[_ref(k)[0].clamp(f, c)[0]]) // 2
+    stride = 1 + GUARD + max(int(cg.frames_ref(k)[0].pcm_offsets[cg.frames_ref(k)[0].clamp(f, c)[1]] - cg.frames_ref(k)[0].pcm_offsets[cg.frames_ref(k)[0].clamp(f, c)[0]]) // 2
                              for k, f, c in clips)
     if kind == "device":
         import torch
@@ -194,7 +152,7 @@ def test_rows_of_one_array(oracle, kind):
     dec = api.BulkDecoder(threads=2)
     try:
         dec.set_quirks(ISO_LSF)
-        got = dec.decode_clips([(streams[k][1], _ref(k)[0], first, count) for k, first, count in clips], out)
+        got = dec.decode_clips([(streams[k][1], cg.frames_ref(k)[0], first, count) for k, first, count in clips], out)
     finally:
         dec.close()
     host = out.cpu().numpy() if kind == "device" else out
@@ -207,9 +165,9 @@ def test_short_destinations_take_what_fits():
     frame), on the device and in host memory"""
     import torch
     from pdmp3_amd import api
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     k = next(i for i, s in enumerate(streams) if s[0] == "mixed/mono-stereo")
-    ix, whole = _ref(k)
+    ix, whole = cg.frames_ref(k)
     dec = api.BulkDecoder(threads=2)
     try:
         dec.set_quirks(ISO_LSF)
@@ -227,12 +185,12 @@ def test_short_destinations_take_what_fits():
 
 def test_ring_replay_clips_fail_and_the_decoder_goes_on():
     from pdmp3_amd import api
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     bad = clip_streams.replay_stream()
     bix = api.StreamIndex(bad, ISO_LSF)
     assert bix.replay
     k = 3
-    ix, whole = _ref(k)
+    ix, whole = cg.frames_ref(k)
     dec = api.BulkDecoder(threads=2)
     try:
         dec.set_quirks(ISO_LSF)
@@ -256,9 +214,9 @@ def test_ring_replay_clips_fail_and_the_decoder_goes_on():
 def test_switches_that_differ_from_the_index_are_refused():
     """an index built with PDMP3_ISO_LSF and a decoder without it: -1 (RuntimeError), nothing written; then right"""
     from pdmp3_amd import api
-    streams = _streams()
+    streams = clip_streams.gpu_streams()
     k = next(i for i, s in enumerate(streams) if s[0] == "mixed/mpeg1-lsf")
-    ix, whole = _ref(k)
+    ix, whole = cg.frames_ref(k)
     dec = api.BulkDecoder(threads=2)
     try:
         out = np.full((1, 50000), SENTINEL, dtype=np.int16)
