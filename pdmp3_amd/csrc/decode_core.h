@@ -58,6 +58,9 @@ struct ConstBank;
 // pins a VGPR value at this program point (keeps IR passes from sinking the
 // arithmetic that produced it past the scheduling fences)
 #define PD_PIN(x) asm volatile("" : "+v"(x))
+// a pair of binary32 values as ONE value in an aligned register pair from here on: the compiler does not look through it
+// to the wider value its halves came from, nor share what is computed from it with code in front of this point
+#define PD_PAIR(x) asm("" : "+v"(x))
 #define PD_ANY(c) (__builtin_amdgcn_ballot_w64(c) != 0ull)     // wave-uniform: any lane
 #define PD_LANE() ((int)(threadIdx.x & 63))
 // a value every lane holds alike, moved to a scalar register: conditions on it become scalar branches instead of
@@ -167,6 +170,7 @@ void permlane32_swap(int* a, int* b);         // v_permlane32_swap_b32 vdst = a,
 #define PD_NOUNROLL
 #define PD_SCHED_FENCE() ((void)0)
 #define PD_PIN(x) ((void)0)
+#define PD_PAIR(x) ((void)0)
 #define PD_ANY(c) (::pdmp3::emu::any(c))
 #define PD_LANE() (::pdmp3::emu::lane())
 #define PD_UNIFORM(x) ((int)(x))
@@ -259,6 +263,14 @@ static inline void mul18_rtz_32767(const float* x, float* p) {
 #define PD_GRAN_IMDCT_SPLIT 0
 #else
 #define PD_GRAN_IMDCT_SPLIT 1
+#endif
+// A/B switch of the granule kernel's window sums (profiles/gran_pairs_ab.txt; results are the same in either form).
+// -DPD_EXP_WINDOW_SCALAR: the window sums of a granule as eighteen scalar chains, paired by the compiler where it finds
+// pairs, as before -- otherwise written on register pairs (ph_window_own / ph_window_hist on f32x2)
+#if defined(PD_EXP_WINDOW_SCALAR)
+#define PD_GRAN_WINDOW_PAIRS 0
+#else
+#define PD_GRAN_WINDOW_PAIRS 1
 #endif
 // the VALU columns' coefficients as [m][q] (q fastest): the pair (q, q + 1) of one m is an aligned scalar-register pair, a
 // v_pk_fma_f32 operand as it comes out of the s_load -- as [q][m] every packed FMA needed one or two s_mov_b32 in front of
@@ -2076,10 +2088,8 @@ PD_FN void ph_overlap_matrix(int lane, WaveData& L, const LaneRegs& R, const flo
     }
   }
 }
-// the window sums of a stereo granule in two parts (same chain of 16 FMAs per sum as ph_window, newest slot first):
-// the terms that read the granule's own slots ...
-PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs& R, float* acc) {
-  const int ch = lane >> 5;
+// the window taps of the lane, from the workgroup's tables
+PD_FN void ph_window_taps(int lane, const TabLds& S, LaneRegs& R) {
   if (PD_GRAN_TAPS_WIDE) {               // (TabLds::taps: the lane's piece p at 16 (32 p + i) bytes)
     const Chunk16* tp = reinterpret_cast<const Chunk16*>(S.taps) + (lane & 31);
     PD_UNROLL for (int p = 0; p < 4; p++) {
@@ -2089,6 +2099,12 @@ PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs&
   } else {
     PD_UNROLL for (int k = 0; k < 8; k++) { R.we[k] = S.taps[tab_tap_index(k, lane & 31)]; R.wo[k] = S.taps[tab_tap_index(8 + k, lane & 31)]; }
   }
+}
+// the window sums of a stereo granule in two parts (same chain of 16 FMAs per sum as ph_window, newest slot first):
+// the terms that read the granule's own slots ...
+PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs& R, float* acc) {
+  const int ch = lane >> 5;
+  ph_window_taps(lane, S, R);
   float E[18], O[18];
   PD_UNROLL for (int t = 0; t < 18; t++) { E[t] = L.hyb[ch][t][R.idx_e]; O[t] = L.hyb[ch][t][R.idx_o]; }
   PD_UNROLL for (int t = 0; t < 18; t++) {
@@ -2098,6 +2114,56 @@ PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, LaneRegs&
       if (t - 2 * k - 1 >= 0) s = PD_FMA(R.wo[k], O[t - 2 * k - 1], s);
     }
     acc[t] = s;
+  }
+}
+// The same terms, in the same order per sum, on PAIRS (as ph_window_emit is, and for its reasons): acc[q] = (sum[2 q],
+// sum[2 q + 1]), whose we[k] term reads Ee[q - k] = (E[2 (q - k)], E[2 (q - k) + 1]) and whose wo[k] term reads
+// Oo[q - k] = (O[2 (q - k) - 1], O[2 (q - k)]) -- one v_pk_fma_f32 per two FMAs, 80 of them; only the term k = q of wo
+// straddles the history (O[-1] is ho[14]: ph_window_hist's), its own half, O[0], is one scalar FMA on the odd sum, q = 0..7.
+// The slot pairs are loaded as the pairs they are used as; O's start at an odd slot, so slot 0 is read through a base
+// register of its own (see ph_window_emit).  O[17] is not read here.  Three sum pairs at a time, so that no packed FMA reads
+// the result of the one before it.
+// The taps stay in the registers they were read into, tw[p] = taps (2 p, 2 p + 1): we[0..7] then wo[0..7]; a packed FMA takes
+// either half of an aligned pair as its broadcast factor.  They are the caller's own values, not LaneRegs::we / wo: the
+// compiler holds LaneRegs in memory until late and, reading the taps from there, formed the factor of tap k from "taps k,
+// k + 1" -- for odd k no register pair, so the taps went through the stack inside this phase.
+#define PD_TAP(tw, t) ((tw)[(t) >> 1][(t) & 1])
+#define PD_TAP2(tw, t) ((f32x2){PD_TAP(tw, t), PD_TAP(tw, t)})
+PD_FN void ph_window_own(int lane, const WaveData& L, const TabLds& S, const LaneRegs& R, f32x2* tw, f32x2* acc) {
+  const int ch = lane >> 5;
+  if (PD_GRAN_TAPS_WIDE) {
+    const Chunk16* tp = reinterpret_cast<const Chunk16*>(S.taps) + (lane & 31);
+    PD_UNROLL for (int p = 0; p < 4; p++) {
+      const Chunk16 v = tp[32 * p];
+      tw[2 * p] = (f32x2){u2f(v[0]), u2f(v[1])};
+      tw[2 * p + 1] = (f32x2){u2f(v[2]), u2f(v[3])};
+    }
+  } else {
+    PD_UNROLL for (int p = 0; p < 8; p++) tw[p] = (f32x2){S.taps[tab_tap_index(2 * p, lane & 31)], S.taps[tab_tap_index(2 * p + 1, lane & 31)]};
+  }
+  const float* he = &L.hyb[ch][0][R.idx_e];  // slot t at he[33 t]
+  const float* ho = &L.hyb[ch][0][R.idx_o];
+  int io0 = R.idx_o;
+  PD_PIN(io0);
+  const float o0 = L.hyb[ch][0][io0];
+  f32x2 Ee[9], Oo[9];
+  PD_UNROLL for (int m = 0; m < 9; m++) {
+    Ee[m] = (f32x2){he[33 * (2 * m)], he[33 * (2 * m + 1)]};
+    if (m >= 1) Oo[m] = (f32x2){ho[33 * (2 * m - 1)], ho[33 * (2 * m)]};
+  }
+  // (each pair a value of its own from here on: as halves of the 16-byte value, taps 3, 7, 11 and 15 were copied into the
+  //  low half of a fresh pair before their first use)
+  PD_UNROLL for (int p = 0; p < 8; p++) PD_PAIR(tw[p]);
+  PD_UNROLL for (int q0 = 0; q0 < 9; q0 += 3) {
+    f32x2 s[3] = {(f32x2){0.0f, 0.0f}, (f32x2){0.0f, 0.0f}, (f32x2){0.0f, 0.0f}};
+    PD_UNROLL for (int k = 0; k < 8; k++) {
+      PD_UNROLL for (int u = 0; u < 3; u++) { if (k <= q0 + u) s[u] = fma2(PD_TAP2(tw, k), Ee[q0 + u - k], s[u]); }
+      PD_UNROLL for (int u = 0; u < 3; u++) {
+        if (k < q0 + u) s[u] = fma2(PD_TAP2(tw, 8 + k), Oo[q0 + u - k], s[u]);
+        else if (k == q0 + u) s[u][1] = PD_FMA(PD_TAP(tw, 8 + k), o0, s[u][1]);
+      }
+    }
+    PD_UNROLL for (int u = 0; u < 3; u++) acc[q0 + u] = s[u];
   }
 }
 // PCM of a stereo granule of k_decode_g, written THROUGH to memory in 16-byte pieces.  A launch of up to some thousand
@@ -2132,6 +2198,8 @@ PD_FN void pcm_emit_through(int lane, WaveData& L, const float* sum, int16_t* pc
   PD_UNROLL for (int k = 0; k < kFull; k++) PD_STORE16_DEVICE(out16, 1024 * k + 16 * lane, v[k]);
   if (lane < kRest) PD_STORE16_DEVICE(out16, 1024 * kFull + 16 * lane, v[kFull]);
 }
+template <bool F32, bool THROUGH>
+PD_FN void gran_pcm_emit(int lane, WaveData& L, const float* sum, int16_t* pcm_g, float* pcmf_g);
 // ... and the ones that read the history R.he / R.ho (slots 3..17 of the granule before); PCM
 // THROUGH: the PCM in 16-byte write-through stores (k_decode_g; the persistent kernel keeps pcm_emit)
 template <bool F32, bool THROUGH = false>
@@ -2145,6 +2213,42 @@ PD_FN void ph_window_hist(int lane, WaveData& L, const LaneRegs& R, const float*
     }
     sum[t] = s;
   }
+  gran_pcm_emit<F32, THROUGH>(lane, L, sum, pcm_g, pcmf_g);
+}
+// On pairs (ph_window_own's): the we[k] term of sum pair q, k > q, reads (he[13 - 2 j], he[14 - 2 j]) and its wo[k] term
+// (ho[12 - 2 j], ho[13 - 2 j]), j = k - q - 1 -- 56 v_pk_fma_f32; the history's half of the straddling term, wo[q] ho[14], is
+// one scalar FMA on the even sum and comes first, as k = q does.
+template <bool F32, bool THROUGH = false>
+PD_FN void ph_window_hist(int lane, WaveData& L, const LaneRegs& R, const f32x2* taps, const f32x2* acc, int16_t* pcm_g, float* pcmf_g) {
+  // (the tap pairs as values of THIS phase: the broadcast factors (tap k, tap k) are the same expressions as in
+  //  ph_window_own, and shared with it they were made there once and for all -- as register pairs filled by two moves per
+  //  tap, twenty-four moves in every wave, instead of being picked from their pair by the packed FMA itself)
+  f32x2 tw[8];
+  PD_UNROLL for (int p = 0; p < 8; p++) { tw[p] = taps[p]; PD_PAIR(tw[p]); }
+  float sum[18];
+  PD_UNROLL for (int q0 = 0; q0 < 9; q0 += 3) {
+    f32x2 s[3];
+    PD_UNROLL for (int u = 0; u < 3; u++) s[u] = acc[q0 + u];
+    PD_UNROLL for (int k = 0; k < 8; k++) {
+      PD_UNROLL for (int u = 0; u < 3; u++) {
+        const int j = k - (q0 + u) - 1;
+        if (j >= 0) s[u] = fma2(PD_TAP2(tw, k), (f32x2){R.he[13 - 2 * j], R.he[14 - 2 * j]}, s[u]);
+      }
+      PD_UNROLL for (int u = 0; u < 3; u++) {
+        const int j = k - (q0 + u) - 1;
+        if (j >= 0) s[u] = fma2(PD_TAP2(tw, 8 + k), (f32x2){R.ho[12 - 2 * j], R.ho[13 - 2 * j]}, s[u]);
+        else if (j == -1) s[u][0] = PD_FMA(PD_TAP(tw, 8 + k), R.ho[14], s[u][0]);
+      }
+    }
+    PD_UNROLL for (int u = 0; u < 3; u++) { sum[2 * (q0 + u)] = s[u][0]; sum[2 * (q0 + u) + 1] = s[u][1]; }
+  }
+  gran_pcm_emit<F32, THROUGH>(lane, L, sum, pcm_g, pcmf_g);
+}
+#undef PD_TAP
+#undef PD_TAP2
+// the PCM of a stereo granule from its eighteen sums
+template <bool F32, bool THROUGH>
+PD_FN void gran_pcm_emit(int lane, WaveData& L, const float* sum, int16_t* pcm_g, float* pcmf_g) {
   if (THROUGH && PD_GRAN_PCM_FORM == 1) pcm_emit_through<F32>(lane, L, sum, pcm_g, pcmf_g);
   else if (THROUGH && PD_GRAN_PCM_FORM == 2 && !F32) {
     // (timing probe: pcm_emit's nine dword stores, device scope)
@@ -2343,8 +2447,17 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
     PD_GT(11)
     return;
   }
+#if PD_GRAN_WINDOW_PAIRS
+  f32x2 acc[9], tw[8];       // (tw: the lane's sixteen taps as the eight register pairs they were read into)
+  if (PD_EXP_SKIP & 16) { PD_UNROLL for (int t = 0; t < 9; t++) { acc[t] = (f32x2){L.hyb[0][2 * t][lane & 31], L.hyb[0][2 * t + 1][lane & 31]}; tw[t & 7] = acc[t]; } } else { PD_PHASE(ph_window_own(lane, L, S, R, tw, acc)) }
+#define PD_GRAN_ACC(t) acc[(t) / 2][(t) % 2]
+#define PD_GRAN_TAPS tw,
+#else
+#define PD_GRAN_ACC(t) acc[t]
+#define PD_GRAN_TAPS
   float acc[18];
   if (PD_EXP_SKIP & 16) { PD_UNROLL for (int t = 0; t < 18; t++) acc[t] = L.hyb[0][t][lane & 31]; } else { PD_PHASE(ph_window_own(lane, L, S, R, acc)) }
+#endif
   PD_GT(9)
   if (have_halo) { PD_UNROLL for (int s = 0; s < kHistSlots; s++) { R.he[s] = H.he[s]; R.ho[s] = H.ho[s]; } }
   else if (from_caller) {
@@ -2352,8 +2465,12 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
       R.he[s] = a.state_in[(kOvlRegs + s) * 64 + lane];
       R.ho[s] = a.state_in[(kOvlRegs + kHistSlots + s) * 64 + lane];
     }
-  } else if (from_zero) { PD_UNROLL for (int s = 0; s < kHistSlots; s++) { R.he[s] = 0.0f; R.ho[s] = 0.0f; } }
-  else if (RING || gp.w > 0) {
+  } else if (from_zero) {
+    // (the zero is made HERE: as a constant, the compiler set all thirty registers to it ahead of the branches, in every wave)
+    float zero = 0.0f;
+    if (PD_GRAN_WINDOW_PAIRS) PD_PIN(zero);
+    PD_UNROLL for (int s = 0; s < kHistSlots; s++) { R.he[s] = zero; R.ho[s] = zero; }
+  } else if (RING || gp.w > 0) {
     if (RING) gran_lds_wait_tag(&gp.mb[gp.w].rows_full, tag);
     else gran_lds_wait(&gp.mb[gp.w].rows_full);
     const float* rows = gran_rows_box(L) + (lane >> 5) * 32;
@@ -2366,9 +2483,11 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
   }
   (void)from_chain;
   PD_GT(10)
-  if (PD_EXP_SKIP & 32) { a.pcm[(size_t)f * 2304 + gr * 1152 + lane] = (int16_t)(acc[0] + acc[17] + R.he[0] + R.ho[14]); } else { PD_PHASE((ph_window_hist<F32, !RING>(lane, L, R, acc, a.pcm + (size_t)f * 2304 + gr * 1152, F32 ? a.pcm_f32 + (size_t)f * 2304 + gr * 1152 : nullptr))) }
+  if (PD_EXP_SKIP & 32) { a.pcm[(size_t)f * 2304 + gr * 1152 + lane] = (int16_t)(PD_GRAN_ACC(0) + PD_GRAN_ACC(17) + R.he[0] + R.ho[14]); } else { PD_PHASE((ph_window_hist<F32, !RING>(lane, L, R, PD_GRAN_TAPS acc, a.pcm + (size_t)f * 2304 + gr * 1152, F32 ? a.pcm_f32 + (size_t)f * 2304 + gr * 1152 : nullptr))) }
   PD_GT(11)
 #undef PD_GT
+#undef PD_GRAN_ACC
+#undef PD_GRAN_TAPS
 }
 
 // The wave of granule g: which way its frame goes (wave-uniform facts from the side records; both waves of a frame
