@@ -1202,6 +1202,87 @@ int pdmp3_amd_mfcc_long_plan(int n_mels, int n_mfcc, int deltas, int delta_width
 int pdmp3_amd_bulk_decode_clips_mfcc_long(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips,
                                           const pdmp3_amd_mfcc_long_spec* spec, long long* valid);
 
+/* ---- pYIN pitch tracking of clips (Mauch and Dixon 2014, with librosa.pyin's parameters) ----
+ * K clips as one planar float32 batch, frames innermost: f0, voiced flag, voiced probability and pitch bin [K][C][4][F], or the
+ * observation probabilities with the voiced probability in the last row [K][C][n_b + 1][F].  New entry points only.  Framing,
+ * the lags tmin .. tmax, valid[k], rate 0, channels 0, replay, mixed-format clips, destinations and strides are the pitch
+ * call's (section 20); spec.pitch carries them, its threshold and out_mode are not read.  nt = n_thresholds, sr the call's rate.
+ * 1. Curve.  c[tau][f] is the binary32 value that pdmp3_amd_bulk_decode_clips_pitch stores at out_mode 1 for the same frame
+ *    arguments, bit for bit: the kernel is k_clip_pitch, unchanged, its destination a stage of the stream object.
+ * 2. Troughs.  Section 20's rule 5 on [tmin, tmax]: tau is a trough when c(tau) < c(tau - 1) and c(tau) <= c(tau + 1); at tmin:
+ *    c(tmin) < c(tmin + 1); tmax is never one.  In ascending lag they are t_1 < .. < t_n with heights h_j.  A frame without a
+ *    trough has O = 0 everywhere; silence is such a frame (its curve is 1).
+ * 3. Threshold weights.  theta_i = i / nt, i = 1 .. nt, in binary64.  w_i = I(theta_i; a, b) - I(theta_(i-1); a, b), the
+ *    regularised incomplete beta function, a host table in binary64; for integer a, b in 1 .. 64 it is the finite binomial sum.
+ *    Any other beta is refused unless threshold_weights gives nt finite non-negative doubles, which are then used as given.
+ * 4. Candidate probabilities.  i_j = the least i with h_j < theta_i (the binary32 value against the binary64 entry, exactly),
+ *    none if h_j >= 1.  For threshold i: B_i = {j : i_j <= i}, n_i = |B_i|, p_ij = #{j' < j : j' in B_i}.  Prior:
+ *    pi(p, n) = fl(G[p] cN[n]), G[p] = exp(-lambda p), cN[n] = (1 - exp(-lambda)) / (1 - exp(-lambda n)), host tables (scipy's
+ *    boltzmann.pmf).  P_j = sum over i >= i_j, ascending, of w_i pi(p_ij, n_i), in binary64.  g = the first j that attains
+ *    min h, m = #{i : h_g >= theta_i}: P_g += no_trough_prob (w_1 + .. + w_m), the partial sums a host table.
+ * 5. Pitch bins.  n_s = ceil(fl(1 / resolution)), n_b = floor(12 n_s log2(fmax / fmin)) + 1.  period_j = t_j + delta_j, delta
+ *    by section 20's rule 6 in binary64 on the three binary32 curve values, 0 at tmin.  b_j = #{q in 1 .. n_b : period_j <= T_q},
+ *    T_q = sr / (fmin 2^((q - 0.5) / (12 n_s))), a host table in binary64: librosa's clip(round(12 n_s log2(f / fmin)), 0, n_b)
+ *    everywhere but on exact ties, without a logarithm on the device.  b_j = n_b is dropped (librosa's overwrite drops it), and
+ *    so is a trough with P_j = 0.  Of two troughs in one bin the larger lag's P stands (librosa's fancy assignment: no sum).
+ * 6. Observation.  O[b][f] = fl32(P) of the surviving trough in bin b, else +0.  v[f] = fl32(min(1, sum over b ascending of
+ *    O[b][f])), in binary64 on the binary32 values.  Every unvoiced state observes U[f] = (1 - v) / n_b in binary64.
+ * 7. Transitions: librosa's transition_local(n_b, Wd, "triangle", wrap=False), kron'ed with transition_loop(2, 1 - switch_prob).
+ *    msf = round_half_even(max_transition_rate * 12 * H / sr), Wd = msf n_s + 1, hb = Wd / 2 (integer).  An odd Wd (every
+ *    default) has tri[d] = 1 - |d| / ((Wd + 1) / 2) at offset d = i' - i, |d| <= hb.  An even Wd is not made odd: librosa places
+ *    scipy's even triangle -- samples (2 min(m, Wd - 1 - m) + 1) / Wd, m = 0 .. Wd - 1, two equal peaks -- at offsets
+ *    d = m - Wd / 2 + 1 where n_b is even and d = m - Wd / 2 where n_b is odd, and the offset left over at the other end
+ *    holds 0; this call follows that.  Z_i = sum of tri[i' - i] over the i' in range.  Host tables in binary64:
+ *    ltri[d] = ln tri[d], lZ[i] = ln Z_i, l_stay = ln(1 - switch_prob), l_sw = ln(switch_prob), L0 = ln(2^-1022).
+ *    lt(s -> s') = ltri[i' - i] - lZ[i] + (l_stay or l_sw) where tri[i' - i] > 0, and L0 everywhere else: librosa's
+ *    log(0 + tiny); a jump out of the band is allowed at that price.
+ * 8. Path.  States 0 .. n_b - 1 are voiced, n_b .. 2 n_b - 1 unvoiced.  lo[f][s] = ln O or ln U, L0 where the value is 0;
+ *    lp0 = L0 for voiced states and -ln n_b for unvoiced ones.  S(path) = lp0[s_0] + lo[0][s_0] + sum over f ascending of
+ *    (lt(s_(f-1) -> s_f) + lo[f][s_f]).  The call returns a path that maximises S up to the device's own roundings
+ *    (section 25 bounds them) and takes the lowest state among equal values.
+ * 9. Outputs.  out_mode 0: [K][C][4][F]: plane 0 f0 = fl32(fmin 2^(b / (12 n_s))) from a host table where the frame is
+ *    voiced, else `fill` (which may be NaN), or with use_bin_frequency = 1 the bin's frequency all the same (librosa's
+ *    fill_na=None); plane 1 the voiced flag, 1 or 0; plane 2 v; plane 3 the bin b.  out_mode 1: [K][C][n_b + 1][F]: O, v in the
+ *    last row.  Mode 0's path is the definition's on mode 1's output of the same arguments bit for bit.
+ * 10. Refusals (-1, nothing written): whatever pdmp3_amd_pitch_check refuses; n_thresholds outside 1 .. 256; boltzmann <= 0;
+ *    switch_prob or no_trough_prob outside (0, 1); n_s outside 1 .. 20; n_b outside 2 .. 2048; Wd > n_b (librosa refuses it);
+ *    1 / resolution or 12 n_s log2(fmax / fmin) within 1e-9 of an integer, or the quotient of msf within 1e-9 of a half, unless
+ *    the binary64 value of the formula is that boundary itself (section 20's rule 2); rows beyond 31 bits (the curve's, the
+ *    observation's, the back-pointers'); an unknown mode or use_bin_frequency. */
+typedef struct {
+  pdmp3_amd_pitch_spec pitch;          /* rate, channels, width, rolloff, n_frames, frame_length, win_length, hop, fmin, fmax */
+  int n_thresholds;                    /* 100 */
+  double beta_a, beta_b;               /* 2, 18 */
+  const double* threshold_weights;     /* NULL, or n_thresholds weights used in place of the beta distribution's */
+  double boltzmann;                    /* 2: lambda */
+  double resolution;                   /* 0.1 semitones */
+  double max_transition_rate;          /* 35.92 octaves a second */
+  double switch_prob, no_trough_prob;  /* 0.01, 0.01 */
+  float fill;                          /* plane 0 of an unvoiced frame (NaN) */
+  int use_bin_frequency;               /* 1: the bin's frequency there instead */
+  int out_mode;                        /* 0: the path's four planes; 1: the observation */
+} pdmp3_amd_pyin_spec;
+/* 0 when the spec's numbers (n_frames among them) are acceptable at sampling frequency sr, else -1 (item 10) */
+int pdmp3_amd_pyin_check(const pdmp3_amd_pyin_spec* spec, long sr);
+/* Every table the kernels read, one block as pdmp3_hip_clip_pyin takes it: theta[nt] | w[nt] | wsum[nt + 1] (wsum[m] =
+ * w_1 + .. + w_m) | G[mt] | cN[mt + 1] | T[n_b] | ltri[2 hb + 1] (offsets -hb .. hb; -inf where the window holds 0) | lZ[n_b] in
+ * binary64, then the n_b bin frequencies in binary32 (padded to a whole double), then l_stay, l_sw, L0 and -ln n_b, which the
+ * kernels take as parameters; mt = (tmax - 1 - tmin) / 2 + 1, the most troughs a frame can have.
+ * counts (or NULL) receives {nt, mt, n_b, hb}.  Returns the block's size in doubles (tables NULL and cap 0: only that), or -1
+ * as the check, or where cap is too small. */
+int pdmp3_amd_pyin_tables(const pdmp3_amd_pyin_spec* spec, long sr, double* tables, size_t cap, int* counts);
+/* The function the call itself uses.  numbers[8] = {states 2 n_b, n_b, n_s, msf, the band Wd, hb, frames (waves) of a workgroup
+ * of k_clip_pyin_obs: 8, or 4, 2, 1 where its LDS would pass 64 KB, threads of a workgroup of k_clip_pyin_path}; lds[2] = the
+ * LDS bytes of the two kernels (more than 64 KB: k_clip_pyin_path_big, a static array); stage[3] = the bytes a (clip, channel)
+ * takes of the stage for its curve, its observation and its back-pointers (the last two 0 at out_mode 1).  Pointers may be
+ * NULL.  0, or -1 as the check. */
+int pdmp3_amd_pyin_plan(const pdmp3_amd_pyin_spec* spec, long sr, int* numbers, unsigned* lds, unsigned long long* stage);
+/* Row k receives channel c's [4][n_frames] (out_mode 1: [n_b + 1][n_frames]) floats at dst + c * chan_stride.  The audio call
+ * in front, then k_clip_pitch into the stage, k_clip_pyin_obs and (out_mode 0) k_clip_pyin_path (csrc/pyin.hip).  Everything
+ * else as pdmp3_amd_bulk_decode_clips_pitch.  -1 also where pdmp3_amd_pyin_check says so. */
+int pdmp3_amd_bulk_decode_clips_pyin(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pyin_spec* spec,
+                                     long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

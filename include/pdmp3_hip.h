@@ -871,6 +871,44 @@ typedef struct pdmp3_tempogram_params {
 int pdmp3_hip_clip_tempogram(pdmp3_hip_stream* hs, int slot, const pdmp3_tempogram_desc* descs, int n_clips, const float* window,
                              const double* prior, const pdmp3_tempogram_params* params);
 
+/* pYIN pitch tracking of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_pyin).  Two kernels
+ * (pyin.hip) behind k_clip_pitch, which writes its out_mode 1 curve [tmax + 1][n_frames] into a stage:
+ *   k_clip_pyin_obs   a wave a frame, frames_wg waves a workgroup: the frame's curve into LDS, its troughs in passes of 64 lags
+ *                     (ballots and prefix counts, the counts per threshold carried in LDS), their probabilities in binary64,
+ *                     their bins by a search in T_q, the observation row and v in LDS, stored [n_bins + 1][n_frames] (mode 1:
+ *                     the destination) or [n_frames][n_bins + 1] (mode 0: the stage k_clip_pyin_path reads)
+ *   k_clip_pyin_path  (mode 0) a workgroup a (clip, channel), sequential over the frames: the values of the 2 n_bins states
+ *                     double-buffered in LDS as binary64 (the window's logarithms beside them), two band scans and one maximum per half a step, back-pointers two
+ *                     bytes a state [n_frames][2 n_bins], the walk back by one thread, the four planes
+ * The tables are one block of binary64 values in the order theta[n_thr] | w[n_thr] | wsum[n_thr + 1] | G[max_troughs] |
+ * cN[max_troughs + 1] | T[n_bins] | ltri[2 hb + 1] (offsets -hb .. hb) | lZ[n_bins], then n_bins binary32 bin frequencies (csrc/pyin_core.h
+ * pyin_table_layout; pdmp3_amd_pyin_tables fills it). */
+typedef struct pdmp3_pyin_desc {
+  uint64_t curve;                           /* device address of channel 0's curve; channels (tmax + 1) n_frames floats apart  */
+  uint64_t obs;                             /* ... of channel 0's observation; mode 1: the destination, channels dst_chan_stride
+                                               apart; mode 0: the stage, channels (n_bins + 1) n_frames apart                   */
+  uint64_t bp;                              /* ... of channel 0's back-pointers (mode 0), channels 2 n_bins n_frames uint16 apart */
+  uint64_t dst;                             /* ... of channel 0's output                                                        */
+  uint64_t dst_chan_stride;                 /* floats between the channels of the destination                                   */
+} pdmp3_pyin_desc;                          /* 40 bytes */
+typedef struct pdmp3_pyin_params {
+  double no_trough;                         /* no_trough_prob                                                           */
+  double l_stay, l_sw, l0, lp0_u;           /* ln(1 - switch_prob), ln(switch_prob), ln(2^-1022), -ln(n_bins)           */
+  float fill; int32_t use_bin;              /* plane 0 of an unvoiced frame: fill, or (use_bin) the bin's frequency      */
+  int32_t tmin, tmax;                       /* the lag range of the curve                                               */
+  int32_t n_thr, n_bins, hb;                /* thresholds; pitch bins n_b; half the transition band, Wd / 2             */
+  int32_t max_troughs;                      /* (tmax - 1 - tmin) / 2 + 1: troughs lie two lags apart at least           */
+  int32_t n_frames, frames_wg;              /* F; frames (waves) of a workgroup of k_clip_pyin_obs: 8, 4, 2 or 1        */
+  int32_t channels, out_mode;
+  int32_t path_threads;                     /* threads of a workgroup of k_clip_pyin_path: n_bins up to 64s, <= 1024    */
+  uint32_t obs_lds_bytes, path_lds_bytes;   /* obs: <= PDMP3_MEL_LDS_SOFT; path: <= PDMP3_MEL_LDS_MAX                   */
+  uint32_t reserved;
+} pdmp3_pyin_params;
+/* Uploads the descriptors and the tables -- host memory -- and runs k_clip_pyin_obs and (mode 0) k_clip_pyin_path on the slot's
+ * HIP stream.  The geometry must be csrc/pyin_core.h's (pdmp3_amd_pyin_plan's).  Blocks until the rows are written. */
+int pdmp3_hip_clip_pyin(pdmp3_hip_stream* hs, int slot, const pdmp3_pyin_desc* descs, int n_clips, const double* tables,
+                        const pdmp3_pyin_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

@@ -40,7 +40,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_spectral_check", "pdmp3_amd_spectral_plan", "pdmp3_amd_bulk_decode_clips_spectral",
                 "pdmp3_amd_hpss_check", "pdmp3_amd_hpss_plan", "pdmp3_amd_bulk_decode_clips_hpss",
                 "pdmp3_amd_mfcc_long_check", "pdmp3_amd_mfcc_long_dct_table", "pdmp3_amd_mfcc_long_delta_taps", "pdmp3_amd_mfcc_long_plan",
-                "pdmp3_amd_bulk_decode_clips_mfcc_long"]
+                "pdmp3_amd_bulk_decode_clips_mfcc_long",
+                "pdmp3_amd_pyin_check", "pdmp3_amd_pyin_tables", "pdmp3_amd_pyin_plan", "pdmp3_amd_bulk_decode_clips_pyin"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -220,6 +221,11 @@ def load_library():
         lib.pdmp3_amd_pitch_lags.argtypes = [vp, C.c_long] + [C.POINTER(C.c_int)] * 3
         lib.pdmp3_amd_pitch_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]
         lib.pdmp3_amd_bulk_decode_clips_pitch.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_pyin"):         # (pYIN pitch tracking: absent from older builds)
+        lib.pdmp3_amd_pyin_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_pyin_tables.argtypes = [vp, C.c_long, vp, C.c_size_t, C.POINTER(C.c_int)]
+        lib.pdmp3_amd_pyin_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)]
+        lib.pdmp3_amd_bulk_decode_clips_pyin.argtypes = [vp, vp, C.c_int, vp, vp]
     if hasattr(lib, "pdmp3_amd_bulk_decode_clips_tempogram"):    # (onset strength, tempogram, tempo: absent from older builds)
         lib.pdmp3_amd_tempogram_check.argtypes = [vp, C.c_long]
         lib.pdmp3_amd_tempogram_window.argtypes = [C.c_int, vp, C.c_size_t]
@@ -1264,6 +1270,79 @@ def pitch_plan(sample_rate=22050, **kw):
     return f.value, sp.value, b.value, k.value
 
 
+class _PyinSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_pyin_spec
+    _fields_ = [("pitch", _PitchSpec), ("n_thresholds", C.c_int), ("beta_a", C.c_double), ("beta_b", C.c_double),
+                ("threshold_weights", C.c_void_p), ("boltzmann", C.c_double), ("resolution", C.c_double), ("max_transition_rate", C.c_double),
+                ("switch_prob", C.c_double), ("no_trough_prob", C.c_double), ("fill", C.c_float), ("use_bin_frequency", C.c_int),
+                ("out_mode", C.c_int)]
+
+
+PYIN_MODES = {"pitch": 0, "observation": 1}
+
+
+def _pyin_spec(n_frames=1, sample_rate=22050, channels=0, frame_length=2048, win_length=0, hop=0, fmin=PITCH_FMIN, fmax=PITCH_FMAX, n_thresholds=100,
+               beta=(2, 18), threshold_weights=None, boltzmann=2.0, resolution=0.1, max_transition_rate=35.92, switch_prob=0.01,
+               no_trough_prob=0.01, fill=float("nan"), out_mode="pitch", width=0, rolloff=0.0):
+    """-> (spec, what its threshold_weights points to).  fill None: the bin's frequency on unvoiced frames (librosa's
+    fill_na=None); win_length / hop 0 or None: frame_length / 2, frame_length / 4"""
+    pitch = _pitch_spec(n_frames, sample_rate, frame_length, win_length or None, hop or None, fmin, fmax, 0.1, 1, channels, width, rolloff)
+    keep = None
+    if threshold_weights is not None:
+        keep = np.ascontiguousarray(threshold_weights, dtype=np.float64)
+        if keep.shape != (int(n_thresholds),):
+            raise ValueError("threshold_weights must hold n_thresholds values")
+    a, b = beta
+    spec = _PyinSpec(pitch, int(n_thresholds), float(a), float(b), None if keep is None else keep.ctypes.data, float(boltzmann), float(resolution),
+                     float(max_transition_rate), float(switch_prob), float(no_trough_prob), 0.0 if fill is None else float(fill),
+                     1 if fill is None else 0, PYIN_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode))
+    return spec, keep
+
+
+def pyin_check(sample_rate=22050, **kw):
+    """pdmp3_amd_pyin_check -> True when pdmp3_amd_bulk_decode_clips_pyin would accept these numbers (decode_clips_pyin's
+    argument names) at sample_rate"""
+    try:
+        spec, keep = _pyin_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_pyin_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def pyin_tables(sample_rate=22050, **kw):
+    """pdmp3_amd_pyin_tables -> dict of every table the kernels read: theta, w, wsum, G, cN, T, ltri (offsets -hb .. hb), lZ as
+    float64 numpy, f0 (the bins' frequencies) as float32, the scalars l_stay, l_sw, L0, lp0_u, the kernels' block, and the counts n_thresholds, max_troughs, n_bins, hb"""
+    spec, keep = _pyin_spec(sample_rate=sample_rate, **kw)
+    lib = load_library()
+    counts = (C.c_int * 4)()
+    n = lib.pdmp3_amd_pyin_tables(C.byref(spec), int(sample_rate), None, 0, counts)
+    if n < 0:
+        raise ValueError("pdmp3_amd_pyin_tables: bad argument")
+    t = np.zeros(n, dtype=np.float64)
+    if lib.pdmp3_amd_pyin_tables(C.byref(spec), int(sample_rate), t.ctypes.data_as(C.c_void_p), t.size, counts) != n:
+        raise ValueError("pdmp3_amd_pyin_tables: bad argument")
+    nt, mt, nb, hb = (int(x) for x in counts)
+    out, at = dict(n_thresholds=nt, max_troughs=mt, n_bins=nb, hb=hb, block=t), 0
+    for name, size in (("theta", nt), ("w", nt), ("wsum", nt + 1), ("G", mt), ("cN", mt + 1), ("T", nb), ("ltri", 2 * hb + 1), ("lZ", nb)):
+        out[name] = t[at:at + size].copy()
+        at += size
+    out["f0"] = t[at:].view(np.float32)[:nb].copy()
+    out["l_stay"], out["l_sw"], out["L0"], out["lp0_u"] = (float(x) for x in t[-4:])
+    out["block"] = t[:-4]
+    return out
+
+
+def pyin_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_pyin_plan -> dict: states, n_bins, n_s, msf, band (Wd), hb, obs_frames (waves of a workgroup of k_clip_pyin_obs),
+    path_threads, obs_lds, path_lds (bytes), and the stage bytes of a (clip, channel): curve_bytes, obs_bytes, bp_bytes"""
+    spec, keep = _pyin_spec(sample_rate=sample_rate, **kw)
+    v, lds, st = (C.c_int * 8)(), (C.c_uint * 2)(), (C.c_ulonglong * 3)()
+    if load_library().pdmp3_amd_pyin_plan(C.byref(spec), int(sample_rate), v, lds, st) != 0:
+        raise ValueError("pdmp3_amd_pyin_plan: bad argument")
+    names = ("states", "n_bins", "n_s", "msf", "band", "hb", "obs_frames", "path_threads")
+    return dict(zip(names, (int(x) for x in v)), obs_lds=int(lds[0]), path_lds=int(lds[1]), curve_bytes=int(st[0]), obs_bytes=int(st[1]),
+                bp_bytes=int(st[2]))
+
+
 class _TempogramSpec(C.Structure):                 # include/pdmp3_bulk.h pdmp3_amd_tempogram_spec
     _fields_ = [("mel", _MelLongSpec), ("lag", C.c_int), ("max_size", C.c_int), ("win_length", C.c_int), ("start_bpm", C.c_double),
                 ("std_bpm", C.c_double), ("max_tempo", C.c_double), ("out_mode", C.c_int)]
@@ -1798,6 +1877,34 @@ class BulkDecoder:
             except (ValueError, OverflowError, TypeError):
                 raise RuntimeError("pdmp3_amd_bulk_decode_clips_pitch: bad sample_rate, frame_length, win_length, hop, fmin or fmax")
         return self._clips_call("pitch", clips, (rows, f), spec, channels, out, refused=(ValueError, OverflowError, TypeError))
+
+    def decode_clips_pyin(self, clips, n_frames, sample_rate=22050, channels=0, frame_length=2048, win_length=0, hop=0, fmin=PITCH_FMIN,
+                          fmax=PITCH_FMAX, n_thresholds=100, beta=(2, 18), threshold_weights=None, boltzmann=2.0, resolution=0.1,
+                          max_transition_rate=35.92, switch_prob=0.01, no_trough_prob=0.01, fill=float("nan"), out_mode="pitch", out=None, width=0,
+                          rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_pyin: clips as decode_clips_pitch takes them -> (out, valid): probabilistic YIN with
+        librosa.pyin's parameters on the frames decode_clips_pitch reads (centred on sample start + f hop, zeros outside the stream,
+        no reflection).  out_mode "pitch": float32 [K, C, 4, n_frames] -- f0 in Hz of the Viterbi path's pitch bin (`fill` on
+        unvoiced frames; fill=None: the bin's frequency there too, librosa's fill_na=None), the voiced flag 1.0 / 0.0, the voiced
+        probability, the bin.  out_mode "observation": [K, C, n_bins + 1, n_frames], the observation probabilities of the pitch
+        bins with the voiced probability in the last row (pyin_plan gives n_bins).  beta: integers 1 .. 64, or pass
+        threshold_weights (n_thresholds values).  The path depends on the clip's start: a clip's mode-"pitch" frames are not a
+        slice of a longer clip's.  valid, out, RingReplay / MixedFormat as decode_clips_pitch.  Synchronous."""
+        f = int(n_frames)
+        m = PYIN_MODES.get(out_mode) if isinstance(out_mode, str) else out_mode
+        if m not in (0, 1):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_pyin: out_mode is \"pitch\" or \"observation\"")
+        kw = dict(sample_rate=sample_rate, channels=channels, frame_length=frame_length, win_length=win_length, hop=hop, fmin=fmin, fmax=fmax,
+                  n_thresholds=n_thresholds, beta=beta, threshold_weights=threshold_weights, boltzmann=boltzmann, resolution=resolution,
+                  max_transition_rate=max_transition_rate, switch_prob=switch_prob, no_trough_prob=no_trough_prob, fill=fill, out_mode=m,
+                  width=width, rolloff=rolloff)
+        rows = 4
+        if m == 1:
+            try:
+                rows = pyin_plan(n_frames=f, **kw)["n_bins"] + 1
+            except (ValueError, KeyError, OverflowError, TypeError):
+                raise RuntimeError("pdmp3_amd_bulk_decode_clips_pyin: bad arguments")
+        return self._clips_call("pyin", clips, (rows, f), lambda: _pyin_spec(f, **kw), channels, out, refused=(ValueError, KeyError, OverflowError, TypeError))
 
     def _clips_stft(self, call, clips, n_frames, sample_rate, n_fft, hop, win_length, window, normalized, mode, floor, channels, width, rolloff, out,
                     nb=None, spec_of=None):

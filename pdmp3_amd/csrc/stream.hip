@@ -12,6 +12,7 @@
 #include "unpack_core.h"
 #include "resample_core.h"
 #include "pitch_core.h"
+#include "pyin_core.h"
 #include "tempogram_core.h"
 #include "hpss_core.h"
 #include "mfcc_long_core.h"
@@ -621,7 +622,7 @@ struct ClipPart {
 template <class Desc, size_t N, class Launch>
 static int clip_run(pdmp3_hip_stream* hs, int slot, const char* name, const Desc* descs, int n_clips, long long n_frames,
                     const ClipPart (&parts)[N], Launch launch) {
-  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc, pdmp3_fbank_desc or pdmp3_tempogram_desc");
+  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc, pdmp3_fbank_desc, pdmp3_tempogram_desc or pdmp3_pyin_desc");
   char what[160];
   const auto at = [&](const char* step) -> const char* { snprintf(what, sizeof what, "%s: %s", name, step); return what; };
   StreamSlot& t = hs->s[slot];
@@ -1069,6 +1070,30 @@ extern "C" int pdmp3_hip_clip_pitch(pdmp3_hip_stream* hs, int slot, const pdmp3_
   // descriptors alone: the kernel reads no table
   return clip_run(hs, slot, "pdmp3_hip_clip_pitch", descs, n_clips, P.n_frames, {{ClipPart::kScratch, nullptr, 0}},
                   [&](const pdmp3_mel_desc* dk, int nk, int, uint8_t* const*) { return pdmp3_launch_clip_pitch(hs->s[slot].stream, dk, nk, &P); });
+}
+// ---- pYIN (pyin.hip) ----
+extern "C" int pdmp3_hip_clip_pyin(pdmp3_hip_stream* hs, int slot, const pdmp3_pyin_desc* descs, int n_clips, const double* tables,
+                                   const pdmp3_pyin_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !tables || !params)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pyin: bad argument", hipSuccess);
+  const pdmp3_pyin_params& P = *params;
+  // what the kernels' indexing relies on
+  if (P.tmin < 1 || P.tmin >= P.tmax || P.tmax > 2046 || P.n_thr < 1 || P.n_thr > 256 || P.n_bins < 2 || P.n_bins > 2048 || P.hb < 0 ||
+      2 * P.hb > P.n_bins || P.max_troughs != (P.tmax - 1 - P.tmin) / 2 + 1 ||
+      (P.frames_wg != 1 && P.frames_wg != 2 && P.frames_wg != 4 && P.frames_wg != 8) || (P.channels != 1 && P.channels != 2) ||
+      (P.out_mode != 0 && P.out_mode != 1) || P.n_frames < 0 || (P.use_bin != 0 && P.use_bin != 1) ||
+      (unsigned)P.path_threads != pdmp3::pyin_path_threads(P.n_bins) || P.obs_lds_bytes > PDMP3_MEL_LDS_SOFT || P.path_lds_bytes > PDMP3_MEL_LDS_MAX)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pyin: bad parameters", hipSuccess);
+  if (P.obs_lds_bytes < pdmp3::pyin_obs_lds_bytes(P, P.frames_wg) || (size_t)P.path_lds_bytes < (size_t)pdmp3::pyin_path_lds(P).total_d * sizeof(double))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pyin: a workgroup's curves, rows and states do not fit the LDS asked for", hipSuccess);
+  if (((long long)P.n_frames + P.frames_wg - 1) / P.frames_wg * P.channels > 0x7fffffffLL || (long long)P.n_frames * (P.n_bins + 1) > 0x7fffffffLL ||
+      (long long)P.n_frames * (P.tmax + 1) > 0x7fffffffLL)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_pyin: too many frames", hipSuccess);
+  // descriptors | the tables
+  return clip_run(hs, slot, "pdmp3_hip_clip_pyin", descs, n_clips, P.n_frames, {{ClipPart::kUpload, tables, pdmp3::pyin_table_bytes(P)}},
+                  [&](const pdmp3_pyin_desc* dk, int nk, int, uint8_t* const* part) {
+                    return pdmp3_launch_clip_pyin(hs->s[slot].stream, dk, nk, reinterpret_cast<const double*>(part[0]), &P);
+                  });
 }
 // ---- onset strength, tempogram, tempo (tempogram.hip) ----
 extern "C" int pdmp3_hip_clip_tempogram(pdmp3_hip_stream* hs, int slot, const pdmp3_tempogram_desc* descs, int n_clips, const float* window,

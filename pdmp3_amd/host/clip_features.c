@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss, _mfcc_long; DESIGN.md sections 9-24).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss, _mfcc_long, _pyin; DESIGN.md sections 9-25).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -426,6 +426,54 @@ int pdmp3_amd_bulk_decode_clips_pitch(struct bulk* b, const pdmp3_amd_audio_clip
   P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C;
   if (course_launched(pdmp3_hip_clip_pitch(b->hs, CLIP_SLOT, cc.ds, cc.nd, &P)) != 0) return course_finish(&cc, -1);
   return course_finish(&cc, cc.rc);
+}
+
+/* ---- pYIN pitch tracking of clips ---- */
+/* The pitch call's course with its kernel writing the curve into audio stage 3 instead of the destination; behind the clips'
+ * curves there lie (mode 0) their observations and their back-pointers. */
+int pdmp3_amd_bulk_decode_clips_pyin(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pyin_spec* spec,
+                                     long long* valid) {
+  clip_course cc;
+  if (!spec) return -1;
+  pdmp3_amd_pitch_spec ps = spec->pitch;
+  ps.threshold = 0.1; ps.out_mode = 1;                                   /* (the curve: no threshold is read) */
+  if (course_begin(&cc, b, clips, n_clips, valid, ps.n_frames, ps.channels, ps.rate, ps.width, ps.rolloff) != 0) return -1;
+  pdmp3_pitch_params P;
+  pdmp3_pyin_params Q;
+  memset(&P, 0, sizeof P);
+  if (pyin_plan(spec, cc.sr, &Q) != 0 || pitch_plan(&ps, cc.sr, &P) != 0) return -1;   /* (the check is the first step of either) */
+  const int mode = spec->out_mode;
+  if (course_rows(&cc, P.n, P.hop, mode == 0 ? 4 : Q.n_bins + 1, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const size_t F = (size_t)cc.F, C = (size_t)cc.C;
+  const size_t curve_floats = ((size_t)P.tmax + 1) * F;                  /* of a channel in the stage */
+  const size_t obs_floats = mode == 0 ? ((size_t)Q.n_bins + 1) * F : 0, bp_floats = mode == 0 ? (size_t)Q.n_bins * F : 0;   /* (two bytes a state) */
+  pdmp3_mel_desc* md = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *md);
+  pdmp3_pyin_desc* qd = (pdmp3_pyin_desc*)calloc((size_t)cc.nd, sizeof *qd);
+  double* tables = (double*)calloc(pyin_table_bytes(&Q) / sizeof(double) + 1, sizeof *tables);
+  int rc = -1;
+  if (!md || !qd || !tables || pyin_tables_fill(spec, cc.sr, &Q, tables) != 0 || course_signal(&cc) != 0) goto out;
+  float* const stage = (float*)pdmp3_hip_stream_audio_stage(b->hs, 3, (size_t)cc.nd * C * (curve_floats + obs_floats + bp_floats) * sizeof(float));
+  if (!stage) goto out;
+  float* const obs_stage = stage + (size_t)cc.nd * C * curve_floats;
+  float* const bp_stage = obs_stage + (size_t)cc.nd * C * obs_floats;
+  for (int i = 0; i < cc.nd; i++) {
+    md[i] = cc.ds[i];
+    md[i].dst = (uint64_t)(uintptr_t)(stage + (size_t)i * C * curve_floats);
+    md[i].dst_chan_stride = curve_floats;
+    qd[i].curve = md[i].dst;
+    qd[i].dst = cc.ds[i].dst; qd[i].dst_chan_stride = cc.ds[i].dst_chan_stride;
+    qd[i].obs = mode == 0 ? (uint64_t)(uintptr_t)(obs_stage + (size_t)i * C * obs_floats) : qd[i].dst;
+    qd[i].bp = mode == 0 ? (uint64_t)(uintptr_t)(bp_stage + (size_t)i * C * bp_floats) : 0;
+  }
+  P.n_in = cc.T; P.n_frames = (int32_t)cc.F; P.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_pitch(b->hs, CLIP_SLOT, md, cc.nd, &P)) != 0) goto out;
+  Q.n_frames = (int32_t)cc.F; Q.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_pyin(b->hs, CLIP_SLOT, qd, cc.nd, tables, &Q)) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(md); free(qd); free(tables);
+  return course_finish(&cc, rc);
 }
 
 /* ---- the short-time Fourier transform of clips at n_fft 2048 and 4096 ---- */

@@ -26,6 +26,7 @@
  *   clip_loudness.c loudness of clips: the check, the K-weighting's coefficients, the blocked filter's tables, the geometry
  *   clip_r128.c     true peak, short-term loudness and loudness range of clips: the check, the interpolator's taps, the geometry
  *   clip_pitch.c    pitch of clips (YIN): the check, the lag range, the geometry of a workgroup
+ *   clip_pyin.c     pYIN pitch tracking of clips: the check, the derived numbers, every table, the launches' geometry
  *   clip_tempogram.c onset strength, tempogram and tempo of clips: the check, the window, the prior, the launches' geometry
  *   clip_spectral.c spectral descriptors of clips (rms, zcr, centroid, bandwidth, roll-off, flatness): the check, the kernel's plan
  *   clip_hpss.c     harmonic-percussive separation of clips: the check, the widening, the kernel's plan

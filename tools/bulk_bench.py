@@ -1319,6 +1319,83 @@ def clips_pitch(args, api):
     print(json.dumps(res))
 
 
+def clips_pyin(args, api):
+    """--pyin: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono through pYIN with librosa.pyin's defaults
+    (frame 2048, window 1024, hop 512, C2 .. C7, 100 thresholds, 601 bins, a band of 101) in device memory, four ways, run after
+    run in turn: (a) pdmp3_amd_bulk_decode_clips_audio for the same spans; (b) pdmp3_amd_bulk_decode_clips_pitch's curve
+    [K, 1, 339, F], which a caller without this call takes off the device; (c) pdmp3_amd_bulk_decode_clips_pyin's observation
+    [K, 1, 602, F]; (d) its path [K, 1, 4, F].  The kernels' own times come from a kernel-trace run of this mode
+    (profiles/clip_pyin.txt).  Medians and min..max of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, Fm, rate, N, H = args.clips, args.clip_frames, 22050, 2048, 512
+    span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
+    F = span // H + 1
+    T = (F - 1) * H + N
+    tmin, tmax, _ = api.pitch_lags(rate)
+    plan = api.pyin_plan(rate, n_frames=F)
+    sel = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        sel.append((i, rng.randrange(2, max(3, ixs[i].frames - Fm - 4))))
+    clips, spans = [], []
+    for i, a in sel:
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        start = -((-a * ixs[i].frame_samples * l) // m)
+        clips.append((files[i], ixs[i], start))
+        spans.append((files[i], ixs[i], start - N // 2))
+    dev = "cuda:0"
+    sig = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
+    curve = torch.zeros((K, 1, tmax + 1, F), dtype=torch.float32, device=dev)
+    obs = torch.zeros((K, 1, plan["n_bins"] + 1, F), dtype=torch.float32, device=dev)
+    path = torch.zeros((K, 1, 4, F), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    routes = [("audio clips", lambda: dec.decode_clips_audio(spans, T, rate, 1, out=sig)),
+              ("pitch curve clips", lambda: dec.decode_clips_pitch(clips, F, rate, N, H, out_mode="curve", out=curve)),
+              ("pyin observation clips", lambda: dec.decode_clips_pyin(clips, F, rate, 1, out_mode="observation", out=obs)),
+              ("pyin path clips", lambda: dec.decode_clips_pyin(clips, F, rate, 1, out=path))]
+    times = {name: [] for name, _ in routes}
+    seen = None
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+        if r == 0:
+            seen = {"frames": K * F, "voiced_frames": int((path[:, 0, 1] == 1).sum()), "mean_voiced_probability": float(path[:, 0, 2].mean()),
+                    "non_zero_observations_a_frame": float((obs[:, 0, :-1] != 0).sum()) / (K * F),
+                    "path_v_is_observation_v": bool(torch.equal(path[:, 0, 2], obs[:, 0, -1]))}
+    dec.close()
+    res = {"workload": "%d clips of %d frames (%d samples) at %d Hz mono, pYIN, frame %d hop %d, lags %d .. %d, %d bins, band %d: %s" % (
+               K, F, T, rate, N, H, tmin, tmax, plan["n_bins"], plan["band"], "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "plan": plan,
+           "curve_batch_bytes": int(curve.numel() * 4), "stage_bytes": K * (plan["curve_bytes"] + plan["obs_bytes"] + plan["bp_bytes"]),
+           "seen": seen, "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["observation_minus_curve_ms"] = round((med["pyin observation clips"] - med["pitch curve clips"]) * 1e3, 3)
+    res["path_minus_curve_ms"] = round((med["pyin path clips"] - med["pitch curve clips"]) * 1e3, 3)
+    res["path_minus_audio_ms"] = round((med["pyin path clips"] - med["audio clips"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def torch_tempogram(l, lag, wt, f, window, prior, rate, hop, mode):
     """the definition of DESIGN.md section 21 (max_size 1) in torch on the device: l [K, n_mels, n_env + lag] log10 mel ->
     mode 0 [K, n_env], 1 [K, wt, f], 2 [K, 4]"""
@@ -1690,6 +1767,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) as YIN pitch [3, 1292] at 22 050 Hz mono with librosa.yin's defaults "
                          "(pdmp3_amd_bulk_decode_clips_pitch) against the audio call alone and the audio call followed by the same algorithm "
                          "in torch on the device (see clips_pitch())")
+    ap.add_argument("--pyin", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) through pYIN at 22 050 Hz mono with librosa.pyin's defaults "
+                         "(pdmp3_amd_bulk_decode_clips_pyin, both modes) against the audio call alone and against the pitch call's curve "
+                         "(see clips_pyin())")
     ap.add_argument("--tempogram", action="store_true",
                     help="64 clips of 30 s (or --clips / --clip-frames) as onset envelope, tempogram [384, 1292] and tempo at 22 050 Hz mono with "
                          "librosa's defaults (pdmp3_amd_bulk_decode_clips_tempogram, all three modes) against the audio call alone, the log-mel "
@@ -1713,7 +1794,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.tempogram or args.spectral or args.hpss or args.mfcc_long:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.pyin or args.tempogram or args.spectral or args.hpss or args.mfcc_long:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1727,6 +1808,8 @@ def main():
             return clips_loudness(args, api, r128=args.r128)
         if args.pitch:
             return clips_pitch(args, api)
+        if args.pyin:
+            return clips_pyin(args, api)
         if args.tempogram:
             return clips_tempogram(args, api)
         if args.mel_long:
