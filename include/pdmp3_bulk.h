@@ -1283,6 +1283,66 @@ int pdmp3_amd_pyin_plan(const pdmp3_amd_pyin_spec* spec, long sr, int* numbers, 
 int pdmp3_amd_bulk_decode_clips_pyin(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_pyin_spec* spec,
                                      long long* valid);
 
+/* ---- Beat tracking of clips (librosa.beat.beat_track, Ellis 2007, as librosa 0.10 states it) ----
+ * The dynamic programme over the onset envelope of the tempogram call above, the walk back and the trim, per clip and channel.
+ * New entry points only.  Evaluated in binary64 on binary32 values the product itself can return; every binary64 operation
+ * below is rounded once and none is fused.  F = tg.mel.mel.n_frames, H = hop.
+ *  o[f], f = 0 .. F - 1: mode 0 of pdmp3_amd_bulk_decode_clips_tempogram for the clip, bit for bit.  n = valid[k] frames enter;
+ *  frames n .. F - 1 read nothing of the stream and are left out.
+ *  1. Period.  bpm > 0: P = round-half-even(60 sr / (H bpm)).  bpm == 0: the tempogram chain runs in its mode 2 on the widened
+ *     clip exactly as that call does, P = tau*, and o is the middle F values of its envelope (section 21 item 7: mode 0's bit
+ *     for bit).  P lies in 1 .. 1023 (bpm == 0: in first .. Wt - 1, the admissible lags); h = max(1, round-half-even(P / 2)).
+ *  2. Normalisation.  m = S / n, S the sum of o[f]; norm = sqrt(SS / (n - 1)), SS the sum of (o[f] - m)^2.  Both sums run in
+ *     blocks of 64 frames, each block ascending from 0.0, then the blocks' sums ascending from 0.0.  z[f] = o[f] / norm.
+ *  3. Local score.  g[k] = exp(-0.5 (32 k / P)^2), k = 0 .. P, a host table; ls[i] = the sum from 0.0 over j ascending from
+ *     max(0, i - P) to min(n - 1, i + P) of z[j] g[|i - j|] (one product, one addition), rounded once to binary32.
+ *  4. Programme.  tx[d] = -tightness (log d - log P)^2, d = h .. 2 P, a host table.  For i = 0 .. n - 1: among d = h ..
+ *     min(2 P, i) the largest cum[i - d] + tx[d] above -inf, of equal ones the smallest d; cum[i] = (double) ls[i] + it, or
+ *     (double) ls[i] where there is none.  i0 = the first i with (double) ls[i] >= 0.01 * (double) max ls.  back[i] = -1 for
+ *     i < i0 and where no d is taken, else i - d*.
+ *  5. Last beat.  i is a local maximum where i >= 1, cum[i] > cum[i - 1] and (i == n - 1 or cum[i] >= cum[i + 1]).  med = the
+ *     exact median of cum over them (an even count: 0.5 (a + b) of the two middle ones).  The tail is the largest local maximum
+ *     with cum >= 0.5 med.
+ *  6. Walk back from the tail along back until -1: b_0 < .. < b_{q-1}.
+ *  7. Trim.  s_t = (0.5 ls[b_{t-1}] + ls[b_t]) + 0.5 ls[b_{t+1}], missing neighbours 0; thr = 0.5 sqrt((sum of s_t^2 ascending
+ *     from 0.0) / q) with trim, else 0; b_t is kept from the first to the last t with s_t > thr.
+ *  8. No beats (count 0, mask all 0, list all -1): n < 2; norm not finite and positive; no local maximum; no local maximum at
+ *     or above 0.5 med; no s_t above thr.  In the first two cases ls and cum are 0 and back is -1 everywhere.
+ *  9. out_mode 0 "score": [K][C][F] = ls, 0 from frame n on.  1 "dp": [K][C][2][F] = fl32(cum) (0 from n on) and back as floats
+ *     (-1 from n on).  2 "beats": [K][C][2][F], row 0 the beat mask, row 1 the kept beats' frames ascending, then -1.
+ *     stats [K][C][8], may be NULL: the bpm used (the caller's as binary32, or the tempo call's out[0] bit for bit), P, beats
+ *     kept, beats before the trim, the tail frame, norm, thr, n; kept is 0 and the four between are -1 where not reached (modes
+ *     0 and 1 reach norm only).  Mode 2's ls, cum and back are modes 0 and 1's bit for bit.
+ * 10. Refusals (-1, nothing written): whatever pdmp3_amd_tempogram_check refuses; bpm negative or not finite, or a P outside
+ *     1 .. 1023; tightness not finite and positive; out_mode not 0, 1 or 2; n_frames > 32 768 (a clip's local maxima are ranked
+ *     in one stage, its blocks' sums lie in LDS; 32 768 frames are 12.7 minutes at librosa's defaults). */
+typedef struct pdmp3_amd_beat_spec {
+  pdmp3_amd_tempogram_spec tg;                          /* the envelope and, at bpm 0, the tempo; tg.out_mode is not read */
+  double bpm;                                           /* 0: estimated (librosa's default) */
+  double tightness;                                     /* 100 */
+  int trim;                                             /* 1 */
+  int out_mode;                                         /* 0 score, 1 dp, 2 beats */
+} pdmp3_amd_beat_spec;
+#define PDMP3_BEAT_MAX_PERIOD 1023
+#define PDMP3_BEAT_MAX_FRAMES 32768
+/* 0 when the spec's numbers are acceptable at sampling frequency sr, else -1 (item 10) */
+int pdmp3_amd_beat_check(const pdmp3_amd_beat_spec* spec, long sr);
+/* g[0 .. P] and tx[0 .. 2 P] (the entries below h are 0 and not read) of items 3 and 4 for the period P, as the kernels read
+ * them.  At bpm 0 the call uploads them for every P = first .. Wt - 1, 3 P + 2 values each, one P after the other.  Either
+ * pointer may be NULL.  0, or -1 as the check or for a P outside 1 .. 1023. */
+int pdmp3_amd_beat_tables(const pdmp3_amd_beat_spec* spec, long sr, int P, double* g, double* tx);
+/* What the call launches, the function the call itself uses.  numbers[8]: P (0: estimated), h (of p_max where estimated), the
+ * periods the tables hold p_min and p_max, the threads of a workgroup (256), the steps of the programme ceil(F / h), the lanes
+ * of a frame and the frames of a pass of a step.  lds[2]: the LDS bytes of k_clip_beat_score and k_clip_beat_dp.  stage[2]: the
+ * bytes a (clip, channel) takes of the stage for its scratch, and the bytes of the tables.  Pointers may be NULL.  0, or -1. */
+int pdmp3_amd_beat_plan(const pdmp3_amd_beat_spec* spec, long sr, int* numbers, unsigned* lds, unsigned long long* stage);
+/* Row k receives channel c's [F] (mode 0) or [2][F] floats at dst + c * chan_stride; stats: NULL, or [n_clips][C][8] floats in
+ * host or device memory (a refused clip's stay as they are).  The audio call in front, k_clip_mel_long, k_clip_onset and (bpm 0)
+ * k_clip_tempogram and k_clip_tempo into stages, then k_clip_beat_score, k_clip_beat_dp and k_clip_beat_pick (csrc/beat.hip).
+ * Everything else as pdmp3_amd_bulk_decode_clips_tempogram.  -1 also where pdmp3_amd_beat_check says so. */
+int pdmp3_amd_bulk_decode_clips_beats(pdmp3_amd_bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_beat_spec* spec,
+                                      float* stats, long long* valid);
+
 /* A corpus of whole files over the GPUs of a node -- SURVEY 8e's second partitioning ("C4: whole files per GPU, largest
  * first"), the C form of pdmp3_amd/sharding.py assign_files + one decoder per device (nothing of the
  * reference's: it has one handle and one thread).  devices[]: HIP device numbers, one host thread and one whole-stream

@@ -909,6 +909,42 @@ typedef struct pdmp3_pyin_params {
 int pdmp3_hip_clip_pyin(pdmp3_hip_stream* hs, int slot, const pdmp3_pyin_desc* descs, int n_clips, const double* tables,
                         const pdmp3_pyin_params* params);
 
+/* Beat tracking of clips (include/pdmp3_bulk.h pdmp3_amd_bulk_decode_clips_beats).  Three kernels
+ * (beat.hip) behind the tempogram call's, which wrote the onset envelope (and, where the tempo is estimated, k_clip_tempo's four
+ * floats) into a stage:
+ *   k_clip_beat_score  a workgroup a (clip, channel): the blocked sums, the norm, the local score in tiles of 256 frames
+ *   k_clip_beat_dp     a workgroup a (clip, channel): the programme in steps of h frames on a ring of 2 P + h binary64 values
+ *   k_clip_beat_pick   a workgroup a (clip, channel): local maxima, the median by counting, the tail, the walk, the trim, the rows
+ * A (clip, channel) has work_stride doubles of scratch at work + ((first + i) channels + ch) work_stride doubles
+ * (csrc/beat_core.h beat_work): a header of 8 (the tempo call's four floats in the first two, the norm in the third), cum[F],
+ * the local maxima's values [F], then as 32-bit words ls[F], back[F] and the walk's beats [F].
+ * The tables are one block of binary64 values: for every P = p_min .. p_max in turn g[0 .. P], then tx[0 .. 2 P] (the entries
+ * below h are not read), 3 P + 2 values (csrc/beat_core.h beat_table_at; pdmp3_amd_beat_tables fills one P's). */
+typedef struct pdmp3_beat_desc {
+  uint64_t env;                             /* device address of channel 0's o[0]; channels env_stride floats apart             */
+  uint64_t stats;                           /* ... of the clip's [channels][8] floats, or 0                                       */
+  uint64_t dst;                             /* ... of channel 0's output                                                          */
+  uint64_t dst_chan_stride;                 /* floats between the channels of the destination                                     */
+  uint32_t n;                               /* the frames that enter: the centred calls' valid count                              */
+  uint32_t reserved;
+} pdmp3_beat_desc;                          /* 40 bytes */
+typedef struct pdmp3_beat_params {
+  double tightness;
+  float bpm;                                /* the caller's, where period > 0                                            */
+  int32_t period;                           /* P, or 0: the tempo call's tau* in the scratch's header                    */
+  int32_t p_min, p_max;                     /* the periods the tables hold (period > 0: both are it)                     */
+  int32_t n_frames, channels;               /* F                                                                         */
+  int32_t trim, out_mode;                   /* 0 score, 1 dp, 2 beats                                                    */
+  uint32_t env_stride;                      /* floats between the channels of the envelope                               */
+  uint32_t work_stride;                     /* doubles of a (clip, channel)'s scratch                                    */
+  uint32_t score_lds_bytes, dp_lds_bytes;   /* <= PDMP3_MEL_LDS_SOFT                                                     */
+} pdmp3_beat_params;
+/* Uploads the descriptors and the tables -- host memory -- and runs the three kernels (mode 0: the first, mode 1: two) on the
+ * slot's HIP stream.  work: device memory of n_clips channels work_stride doubles.  The geometry must be csrc/beat_core.h's
+ * (pdmp3_amd_beat_plan's).  Blocks until the rows are written. */
+int pdmp3_hip_clip_beat(pdmp3_hip_stream* hs, int slot, const pdmp3_beat_desc* descs, int n_clips, const double* tables, double* work,
+                        const pdmp3_beat_params* params);
+
 /* test hook: the gc records the device built for the slot's last submit_bits (after pdmp3_hip_stream_wait) */
 int pdmp3_hip_stream_fetch_records(pdmp3_hip_stream* hs, int slot, int n_frames, int16_t* spectra, pdmp3_gc_side* side);
 /* block until the slot's PCM is in its pinned buffer (no-op if nothing is in flight) */

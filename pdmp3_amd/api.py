@@ -41,7 +41,8 @@ BULK_EXPORTS = ["pdmp3_amd_bulk_new", "pdmp3_amd_bulk_new_ex", "pdmp3_amd_bulk_n
                 "pdmp3_amd_hpss_check", "pdmp3_amd_hpss_plan", "pdmp3_amd_bulk_decode_clips_hpss",
                 "pdmp3_amd_mfcc_long_check", "pdmp3_amd_mfcc_long_dct_table", "pdmp3_amd_mfcc_long_delta_taps", "pdmp3_amd_mfcc_long_plan",
                 "pdmp3_amd_bulk_decode_clips_mfcc_long",
-                "pdmp3_amd_pyin_check", "pdmp3_amd_pyin_tables", "pdmp3_amd_pyin_plan", "pdmp3_amd_bulk_decode_clips_pyin"]
+                "pdmp3_amd_pyin_check", "pdmp3_amd_pyin_tables", "pdmp3_amd_pyin_plan", "pdmp3_amd_bulk_decode_clips_pyin",
+                "pdmp3_amd_beat_check", "pdmp3_amd_beat_tables", "pdmp3_amd_beat_plan", "pdmp3_amd_bulk_decode_clips_beats"]
 
 # include/pdmp3_hip.h: pdmp3_gc_bits / pdmp3_frame_bits
 GC_BITS_DTYPE = np.dtype([("part2_3_length", "<u2"), ("big_values", "<u2"), ("global_gain", "u1"), ("scalefac_compress", "u1"),
@@ -226,6 +227,11 @@ def load_library():
         lib.pdmp3_amd_pyin_tables.argtypes = [vp, C.c_long, vp, C.c_size_t, C.POINTER(C.c_int)]
         lib.pdmp3_amd_pyin_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)]
         lib.pdmp3_amd_bulk_decode_clips_pyin.argtypes = [vp, vp, C.c_int, vp, vp]
+    if hasattr(lib, "pdmp3_amd_bulk_decode_clips_beats"):        # (beat tracking: absent from older builds)
+        lib.pdmp3_amd_beat_check.argtypes = [vp, C.c_long]
+        lib.pdmp3_amd_beat_tables.argtypes = [vp, C.c_long, C.c_int, vp, vp]
+        lib.pdmp3_amd_beat_plan.argtypes = [vp, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong)]
+        lib.pdmp3_amd_bulk_decode_clips_beats.argtypes = [vp, vp, C.c_int, vp, vp, vp]
     if hasattr(lib, "pdmp3_amd_bulk_decode_clips_tempogram"):    # (onset strength, tempogram, tempo: absent from older builds)
         lib.pdmp3_amd_tempogram_check.argtypes = [vp, C.c_long]
         lib.pdmp3_amd_tempogram_window.argtypes = [C.c_int, vp, C.c_size_t]
@@ -1402,6 +1408,53 @@ def tempogram_plan(sample_rate=22050, **kw):
     return tuple(x.value for x in v) + (b.value,)
 
 
+class _BeatSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_beat_spec
+    _fields_ = [("tg", _TempogramSpec), ("bpm", C.c_double), ("tightness", C.c_double), ("trim", C.c_int), ("out_mode", C.c_int)]
+
+
+BEAT_MODES = {"score": 0, "dp": 1, "beats": 2}
+BEAT_STATS = ("bpm", "period", "kept", "beats", "tail", "norm", "threshold", "frames")
+
+
+def _beat_spec(n_frames=1, sample_rate=22050, bpm=0.0, tightness=100.0, trim=True, out_mode="beats", **kw):
+    """-> (spec, what its window points to).  kw: decode_clips_tempogram's arguments without out_mode"""
+    tg, keep = _tempogram_spec(n_frames, sample_rate, out_mode="onset", **kw)
+    return _BeatSpec(tg, float(bpm), float(tightness), 1 if trim else 0, BEAT_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)), keep
+
+
+def beat_check(sample_rate=22050, **kw):
+    """pdmp3_amd_beat_check -> True when pdmp3_amd_bulk_decode_clips_beats would accept these numbers (decode_clips_beats's
+    argument names) at sample_rate"""
+    try:
+        spec, keep = _beat_spec(sample_rate=sample_rate, **kw)
+    except (ValueError, KeyError, OverflowError, TypeError):
+        return False
+    return load_library().pdmp3_amd_beat_check(C.byref(spec), int(sample_rate)) == 0
+
+
+def beat_tables(period, sample_rate=22050, **kw):
+    """pdmp3_amd_beat_tables -> (g float64 [period + 1], tx float64 [2 period + 1]) as the kernels read them for this period: the
+    local score's Gaussian taps and the programme's transition cost (its entries below h are 0 and not read)"""
+    spec, keep = _beat_spec(sample_rate=sample_rate, **kw)
+    p = int(period)
+    g, tx = np.full(max(p, 0) + 1, np.nan), np.full(2 * max(p, 0) + 1, np.nan)
+    if load_library().pdmp3_amd_beat_tables(C.byref(spec), int(sample_rate), p, g.ctypes.data_as(C.c_void_p), tx.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("pdmp3_amd_beat_tables: bad argument")
+    return g, tx
+
+
+def beat_plan(sample_rate=22050, **kw):
+    """pdmp3_amd_beat_plan -> dict: period (0: estimated), h, p_min, p_max (the periods the tables hold), threads, steps (of the
+    programme), lanes (of a frame), frames (of a pass of a step), score_lds, dp_lds (bytes), work_bytes (the scratch of a clip and
+    channel), table_bytes"""
+    spec, keep = _beat_spec(sample_rate=sample_rate, **kw)
+    v, lds, st = (C.c_int * 8)(), (C.c_uint * 2)(), (C.c_ulonglong * 2)()
+    if load_library().pdmp3_amd_beat_plan(C.byref(spec), int(sample_rate), v, lds, st) != 0:
+        raise ValueError("pdmp3_amd_beat_plan: bad argument")
+    names = ("period", "h", "p_min", "p_max", "threads", "steps", "lanes", "frames")
+    return dict(zip(names, (int(x) for x in v)), score_lds=int(lds[0]), dp_lds=int(lds[1]), work_bytes=int(st[0]), table_bytes=int(st[1]))
+
+
 class _AudioClip(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_audio_clip
     _fields_ = [("mp3", C.c_void_p), ("n", C.c_size_t), ("index", C.c_void_p), ("start", C.c_longlong), ("dst", C.c_void_p),
                 ("chan_stride", C.c_size_t)]
@@ -1939,6 +1992,51 @@ class BulkDecoder:
         if out_mode == "tempogram" and out is None and not tempogram_check(sample_rate, win_length=wt):
             raise RuntimeError("pdmp3_amd_bulk_decode_clips_tempogram: bad win_length")
         return self._clips_call("tempogram", clips, inner, spec, channels, out, refused=(ValueError, KeyError, OverflowError, TypeError))
+
+    def decode_clips_beats(self, clips, n_frames, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384,
+                           start_bpm=120.0, std_bpm=1.0, max_tempo=320.0, bpm=0.0, tightness=100.0, trim=True, out_mode="beats", out=None,
+                           stats=None, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney", floor=1e-10, fft_win_length=None, fft_window=None,
+                           channels=1, width=0, rolloff=0.0):
+        """pdmp3_amd_bulk_decode_clips_beats: clips and the envelope's arguments as decode_clips_tempogram takes them -> (out,
+        stats, valid): librosa.beat.beat_track's dynamic programme (Ellis 2007) on decode_clips_tempogram's onset envelope, per
+        clip and channel, over the clip's valid frames.  bpm 0: the tempo is decode_clips_tempogram(out_mode="tempo")'s and the
+        period its lag; else the period is round(60 sample_rate / (hop bpm)).  out_mode "beats": float32 [K, C, 2, n_frames], row
+        0 the beat mask, row 1 the beats' frames ascending with -1 behind them; "dp": [K, C, 2, n_frames], the cumulative score
+        and the back-links; "score": [K, C, n_frames], the local score.  stats float32 [K, C, 8] (BEAT_STATS): the bpm used, the
+        period, beats kept, beats before the trim, the tail frame, the envelope's norm, the trim's threshold, the frames that
+        entered; -1 where not reached; a torch tensor on the decoder's device or a numpy array, as out; rows of clips that raise
+        RingReplay / MixedFormat (.out, .stats, .valid) stay NaN.  n_frames <= 32768."""
+        f, k = int(n_frames), len(clips)
+        m = BEAT_MODES.get(out_mode) if isinstance(out_mode, str) else out_mode
+        if m not in (0, 1, 2):
+            raise RuntimeError("pdmp3_amd_bulk_decode_clips_beats: out_mode is \"score\", \"dp\" or \"beats\"")
+        c = int(channels) or (out.shape[1] if out is not None else 0)
+        if not c:
+            cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
+            c = cs.pop() if len(cs) == 1 else 1
+        if stats is None:
+            if out is None or hasattr(out, "data_ptr"):
+                import torch
+                stats = torch.full((k, c, 8), float("nan"), dtype=torch.float32,
+                                   device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
+                torch.cuda.synchronize()
+            else:
+                stats = np.full((k, c, 8), np.nan, dtype=np.float32)
+        torch_like = hasattr(stats, "data_ptr")
+        ok = (stats.is_contiguous() and str(stats.dtype) == "torch.float32") if torch_like else (stats.flags["C_CONTIGUOUS"] and stats.dtype == np.float32)
+        assert ok and tuple(stats.shape) == (k, c, 8), "stats: float32 [K, C, 8], contiguous"
+        sp = stats.data_ptr() if torch_like else stats.ctypes.data
+        spec = lambda: _beat_spec(f, sample_rate, bpm, tightness, trim, m, n_fft=n_fft, hop=hop, n_mels=n_mels, lag=lag, max_size=max_size,
+                                  win_length=win_length, start_bpm=start_bpm, std_bpm=std_bpm, max_tempo=max_tempo, f_min=f_min, f_max=f_max,
+                                  scale=scale, norm=norm, floor=floor, fft_win_length=fft_win_length, fft_window=fft_window, channels=channels,
+                                  width=width, rolloff=rolloff)
+        try:
+            out, valid = self._clips_call("beats", clips, (f,) if m == 0 else (2, f), spec, channels, out,
+                                          refused=(ValueError, KeyError, OverflowError, TypeError), extra=(sp if k else None,))
+        except (RingReplay, MixedFormat) as e:
+            e.stats = stats
+            raise
+        return out, stats, valid
 
     def _clips_call(self, call, clips, inner, spec_of, channels, out, made=None, complex_ok=False, refused=(), extra=()):
         """What every decode_clips_<call> does around its spec: the channel count, `out` made when not given (float32

@@ -182,6 +182,9 @@ hipError_t pdmp3_launch_clip_r128(hipStream_t s, const pdmp3_mel_desc* descs, in
 hipError_t pdmp3_launch_clip_pitch(hipStream_t s, const pdmp3_mel_desc* descs, int n_clips, const pdmp3_pitch_params* params);
 // ---- pyin.hip ----
 hipError_t pdmp3_launch_clip_pyin(hipStream_t s, const pdmp3_pyin_desc* descs, int n_clips, const double* tables, const pdmp3_pyin_params* params);
+// ---- beat.hip ----
+hipError_t pdmp3_launch_clip_beat(hipStream_t s, const pdmp3_beat_desc* descs, int n_clips, int first, const double* tables, double* work,
+                                  const pdmp3_beat_params* params);
 // ---- tempogram.hip ----
 hipError_t pdmp3_launch_clip_tempogram(hipStream_t s, const pdmp3_tempogram_desc* descs, int n_clips, const float* window, const double* prior,
                                        const pdmp3_tempogram_params* params);

@@ -14,6 +14,7 @@
 #include "pitch_core.h"
 #include "pyin_core.h"
 #include "tempogram_core.h"
+#include "beat_core.h"
 #include "hpss_core.h"
 #include "mfcc_long_core.h"
 
@@ -622,7 +623,7 @@ struct ClipPart {
 template <class Desc, size_t N, class Launch>
 static int clip_run(pdmp3_hip_stream* hs, int slot, const char* name, const Desc* descs, int n_clips, long long n_frames,
                     const ClipPart (&parts)[N], Launch launch) {
-  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc, pdmp3_fbank_desc, pdmp3_tempogram_desc or pdmp3_pyin_desc");
+  static_assert(sizeof(Desc) == 40, "pdmp3_mel_desc, pdmp3_fbank_desc, pdmp3_tempogram_desc, pdmp3_pyin_desc or pdmp3_beat_desc");
   char what[160];
   const auto at = [&](const char* step) -> const char* { snprintf(what, sizeof what, "%s: %s", name, step); return what; };
   StreamSlot& t = hs->s[slot];
@@ -1120,6 +1121,28 @@ extern "C" int pdmp3_hip_clip_tempogram(pdmp3_hip_stream* hs, int slot, const pd
                   {{ClipPart::kUpload, window, (size_t)P.win * sizeof(float)}, {ClipPart::kUpload, prior, (size_t)P.win * sizeof(double)}},
                   [&](const pdmp3_tempogram_desc* dk, int nk, int, uint8_t* const* part) {
                     return pdmp3_launch_clip_tempogram(hs->s[slot].stream, dk, nk, as_floats(part[0]), reinterpret_cast<const double*>(part[1]), &P);
+                  });
+}
+// ---- beat tracking (beat.hip) ----
+extern "C" int pdmp3_hip_clip_beat(pdmp3_hip_stream* hs, int slot, const pdmp3_beat_desc* descs, int n_clips, const double* tables, double* work,
+                                   const pdmp3_beat_params* params) {
+  if (!SLOT_OK(hs, slot) || n_clips < 0 || (n_clips && !descs) || !tables || !params || (n_clips && params->n_frames > 0 && !work))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_beat: bad argument", hipSuccess);
+  const pdmp3_beat_params& P = *params;
+  // what the kernels' indexing relies on
+  if (P.p_min < 1 || P.p_min > P.p_max || P.p_max > pdmp3::kBeatMaxPeriod || P.period < 0 || (P.period && (P.period != P.p_min || P.period != P.p_max)) ||
+      P.n_frames < 0 || P.n_frames > pdmp3::kBeatMaxFrames || (P.channels != 1 && P.channels != 2) || P.out_mode < 0 || P.out_mode > 2 ||
+      !(P.tightness > 0.0) || P.work_stride < pdmp3::beat_work_of(P.n_frames).total_d || P.score_lds_bytes > PDMP3_MEL_LDS_SOFT ||
+      P.dp_lds_bytes > PDMP3_MEL_LDS_SOFT)
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_beat: bad parameters", hipSuccess);
+  if ((size_t)P.score_lds_bytes < (size_t)pdmp3::beat_score_lds(P.p_max, P.n_frames).total_d * sizeof(double) ||
+      (size_t)P.dp_lds_bytes < (size_t)pdmp3::beat_dp_lds(P.p_max).total_d * sizeof(double))
+    return fail(PDMP3_HIP_EINVAL, "pdmp3_hip_clip_beat: the tiles, the ring and the tables do not fit the LDS asked for", hipSuccess);
+  // descriptors | the tables
+  return clip_run(hs, slot, "pdmp3_hip_clip_beat", descs, n_clips, P.n_frames,
+                  {{ClipPart::kUpload, tables, pdmp3::beat_table_doubles(P.p_min, P.p_max) * sizeof(double)}},
+                  [&](const pdmp3_beat_desc* dk, int nk, int k, uint8_t* const* part) {
+                    return pdmp3_launch_clip_beat(hs->s[slot].stream, dk, nk, k, reinterpret_cast<const double*>(part[0]), work, &P);
                   });
 }
 extern "C" int pdmp3_hip_copy_from_device(void* host_dst, const void* dev_src, size_t bytes) {

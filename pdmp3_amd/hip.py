@@ -33,7 +33,7 @@ EXPORTS = [
     "pdmp3_hip_stream_audio_stage", "pdmp3_hip_clip_audio", "pdmp3_hip_copy_from_device", "pdmp3_hip_clip_mel", "pdmp3_hip_clip_fbank",
     "pdmp3_hip_clip_mfcc", "pdmp3_hip_clip_stft", "pdmp3_hip_clip_stft_long", "pdmp3_hip_clip_mel_long", "pdmp3_hip_clip_spectral",
     "pdmp3_hip_clip_cqt", "pdmp3_hip_clip_chroma", "pdmp3_hip_clip_loudness", "pdmp3_hip_clip_r128",
-    "pdmp3_hip_clip_pitch", "pdmp3_hip_clip_pyin", "pdmp3_hip_clip_tempogram", "pdmp3_hip_clip_hpss", "pdmp3_hip_clip_mfcc_long",
+    "pdmp3_hip_clip_pitch", "pdmp3_hip_clip_pyin", "pdmp3_hip_clip_tempogram", "pdmp3_hip_clip_beat", "pdmp3_hip_clip_hpss", "pdmp3_hip_clip_mfcc_long",
 ]
 
 

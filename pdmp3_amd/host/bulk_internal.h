@@ -416,6 +416,12 @@ HOST_LOCAL int pitch_plan(const pdmp3_amd_pitch_spec* s, long sr, pdmp3_pitch_pa
 HOST_LOCAL int pyin_plan(const pdmp3_amd_pyin_spec* s, long sr, pdmp3_pyin_params* p);
 HOST_LOCAL size_t pyin_table_bytes(const pdmp3_pyin_params* p);
 HOST_LOCAL int pyin_tables_fill(const pdmp3_amd_pyin_spec* s, long sr, const pdmp3_pyin_params* p, double* t);
+/* clip_beat.c: the check, the periods the tables hold and the geometry of the launches of the beat call at sr (env_stride and
+ * channels are left to the call); the bytes of the tables' block of such parameters, and the block itself as pdmp3_hip_clip_beat
+ * takes it (0, or -1 where the check refuses the spec) */
+HOST_LOCAL int beat_plan(const pdmp3_amd_beat_spec* s, long sr, pdmp3_beat_params* p);
+HOST_LOCAL size_t beat_table_bytes(const pdmp3_beat_params* p);
+HOST_LOCAL int beat_tables_fill(const pdmp3_amd_beat_spec* s, const pdmp3_beat_params* p, double* t);
 /* clip_tempogram.c: the check and the geometry of the launches of the tempogram call for the spec at sr, *front and *back the
  * log-mel frames a row needs in front of frame 0 and behind frame F - 1; the frame counts, env_stride and channels are left to the
  * call (0, or -1 where the check refuses the spec) */

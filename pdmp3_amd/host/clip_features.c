@@ -1,6 +1,6 @@
 /* clip_features.c -- libpdmp3.so: clips by sample position as float batches, and the feature calls on top of them
  * (include/pdmp3_bulk.h: pdmp3_amd_bulk_decode_clips_audio, _mel, _mel_long, _fbank, _mfcc, _stft, _stft_long, _cqt, _chroma,
- * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss, _mfcc_long, _pyin; DESIGN.md sections 9-25).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
+ * _loudness, _r128, _pitch, _tempogram, _spectral, _hpss, _mfcc_long, _pyin, _beats; DESIGN.md sections 9-26).  The audio call turns clips into rows of resampled samples; a feature call runs its rows through
  * the audio call into audio stage 2 and its own kernel behind them.  That course -- arguments, rows, signal, copies out -- is
  * written once here (clip_course); an entry point has its check and plan, its tables, its parameters and its launch.  The
  * checks, plans and tables' contents are the clip_*.c files'.  See host_internal.h for the map of the library. */
@@ -904,4 +904,90 @@ int pdmp3_amd_bulk_decode_clips_r128(struct bulk* b, const pdmp3_amd_audio_clip*
                                      float* stats, float* momentary, float* short_term, long long* valid) {
   if (!spec) return -1;
   return loud_clips(b, clips, n_clips, &spec->loudness, spec, stats, momentary, short_term, valid);
+}
+
+/* ---- beat tracking of clips ---- */
+/* The tempogram call's course in its mode 0 (bpm given) or 2 (bpm 0) with every output of its kernels in audio stage 3: the
+ * log-mel, the envelope, (mode 2) the tempogram, and behind them the beat kernels' scratch of every (clip, channel), whose
+ * header takes k_clip_tempo's four floats.  stats is a destination beside the rows, as the loudness call's. */
+int pdmp3_amd_bulk_decode_clips_beats(struct bulk* b, const pdmp3_amd_audio_clip* clips, int n_clips, const pdmp3_amd_beat_spec* spec,
+                                      float* stats, long long* valid) {
+  clip_course cc;
+  if (!spec) return -1;
+  pdmp3_amd_tempogram_spec tg = spec->tg;
+  tg.out_mode = spec->bpm == 0.0 ? 2 : 0;
+  const pdmp3_amd_mel_spec* m = &tg.mel.mel;
+  if (course_begin(&cc, b, clips, n_clips, valid, m->n_frames, m->channels, m->rate, m->width, m->rolloff) != 0) return -1;
+  pdmp3_beat_params B;
+  pdmp3_tempogram_params Q;
+  pdmp3_mel_long_params P;
+  memset(&Q, 0, sizeof Q);
+  memset(&P, 0, sizeof P);
+  if (beat_plan(spec, cc.sr, &B) != 0 || tempogram_plan(&tg, cc.sr, &Q, &cc.front, &cc.back) != 0) return -1;   /* (the check is the first step of either) */
+  if (mel_long_plan(m->n_fft, m->hop, m->n_mels, &P) != 0) return -1;
+  const int tmode = tg.out_mode, Wt = tg.win_length;
+  if (course_rows(&cc, m->n_fft, m->hop, spec->out_mode == 0 ? 1 : 2, 1) != 0) return course_finish(&cc, -1);
+  if (!cc.nd) return course_finish(&cc, cc.rc);
+  const size_t C = (size_t)cc.C, S = 8 * C;
+  const int stats_dev = stats && pdmp3_hip_host_is_pinned(stats, (size_t)n_clips * S * sizeof(float)) == 2;
+  const size_t stat_at = cc.out_floats;
+  if (stats && !stats_dev) cc.out_floats += (size_t)cc.nd * S;
+  const long long F = cc.F, Fe = tmode == 0 ? F : F + Wt - 1, Fm = Fe + tg.lag;
+  const size_t mel_floats = (size_t)m->n_mels * (size_t)Fm, env_floats = ((size_t)Fe + 3) & ~(size_t)3;
+  const size_t tg_floats = tmode == 2 ? (size_t)Wt * (size_t)F : 0;
+  const size_t front_floats = ((size_t)cc.nd * C * (mel_floats + env_floats + tg_floats) + 1) & ~(size_t)1;   /* (the scratch is binary64) */
+  pdmp3_amd_mel_long_spec ms = tg.mel;
+  ms.mel.out_mode = 2;
+  pdmp3_amd_stft_spec frame;
+  mel_long_stft_spec(&ms, &frame);
+  const float* table = stft_long_tables(b, &frame);
+  const float* operand = mel_long_operand(b, cc.sr, m);
+  pdmp3_mel_desc* md = (pdmp3_mel_desc*)calloc((size_t)cc.nd, sizeof *md);
+  pdmp3_tempogram_desc* td = (pdmp3_tempogram_desc*)calloc((size_t)cc.nd, sizeof *td);
+  pdmp3_beat_desc* bd = (pdmp3_beat_desc*)calloc((size_t)cc.nd, sizeof *bd);
+  int* clip_of = (int*)calloc((size_t)cc.nd, sizeof *clip_of);
+  float* w = (float*)malloc((size_t)Wt * sizeof *w);
+  double* prior = (double*)malloc((size_t)Wt * sizeof *prior);
+  double* tables = (double*)malloc(beat_table_bytes(&B) + sizeof(double));
+  int rc = -1;
+  if (!table || !operand || !md || !td || !bd || !clip_of || !w || !prior || !tables || course_signal(&cc) != 0) goto out;
+  if (pdmp3_amd_tempogram_window(Wt, w, (size_t)Wt) != Wt || pdmp3_amd_tempogram_prior(&tg, cc.sr, prior, (size_t)Wt, NULL) != 0) goto out;
+  if (beat_tables_fill(spec, &B, tables) != 0) goto out;
+  float* const out_stage = cc.out_floats ? (float*)pdmp3_hip_stream_audio_stage(b->hs, 1, cc.out_floats * sizeof(float)) : NULL;
+  float* const stage = (float*)pdmp3_hip_stream_audio_stage(b->hs, 3, (front_floats + 2 * (size_t)cc.nd * C * (size_t)B.work_stride) * sizeof(float));
+  if (!stage || (cc.out_floats && !out_stage)) goto out;
+  float* const env_stage = stage + (size_t)cc.nd * C * mel_floats;
+  float* const tg_stage = env_stage + (size_t)cc.nd * C * env_floats;
+  double* const work = (double*)(stage + front_floats);
+  for (int k = 0, i = 0; k < n_clips; k++) {
+    if (clips[k].index->frames < 0 || clips[k].index->mixed) continue;
+    clip_of[i] = k;
+    md[i] = cc.ds[i];
+    md[i].dst = (uint64_t)(uintptr_t)(stage + (size_t)i * C * mel_floats);
+    md[i].dst_chan_stride = mel_floats;
+    td[i].mel = md[i].dst;
+    td[i].env = (uint64_t)(uintptr_t)(env_stage + (size_t)i * C * env_floats);
+    if (tmode == 0) { td[i].dst = td[i].env; td[i].dst_chan_stride = env_floats; }        /* (mode 0 writes the envelope as its rows) */
+    else {
+      td[i].tg = (uint64_t)(uintptr_t)(tg_stage + (size_t)i * C * tg_floats);
+      td[i].dst = (uint64_t)(uintptr_t)(work + (size_t)i * C * (size_t)B.work_stride);  /* the scratch's header */
+      td[i].dst_chan_stride = 2 * (size_t)B.work_stride;
+    }
+    bd[i].env = td[i].env + (tmode == 2 ? (uint64_t)(Wt / 2) * sizeof(float) : 0);
+    bd[i].stats = !stats ? 0 : (uint64_t)(uintptr_t)(stats_dev ? stats + (size_t)k * S : out_stage + stat_at + (size_t)i * S);
+    bd[i].dst = cc.ds[i].dst; bd[i].dst_chan_stride = cc.ds[i].dst_chan_stride;
+    bd[i].n = (uint32_t)cc.valid[k];
+    i++;
+  }
+  P.n_in = cc.T; P.n_frames = (int32_t)Fm; P.channels = cc.C; P.out_mode = 2; P.floor = (float)m->floor;
+  if (course_launched(pdmp3_hip_clip_mel_long(b->hs, CLIP_SLOT, md, cc.nd, table, operand, &P)) != 0) goto out;
+  Q.n_frames = (int32_t)F; Q.n_env = (int32_t)Fe; Q.n_mel_frames = (int32_t)Fm; Q.env_stride = (uint32_t)env_floats; Q.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_tempogram(b->hs, CLIP_SLOT, td, cc.nd, w, prior, &Q)) != 0) goto out;
+  B.env_stride = (uint32_t)env_floats; B.channels = cc.C;
+  if (course_launched(pdmp3_hip_clip_beat(b->hs, CLIP_SLOT, bd, cc.nd, tables, work, &B)) != 0) goto out;
+  if (stats && !stats_dev && copy_floats_out(stats, out_stage + stat_at, clip_of, cc.nd, S) != 0) goto out;
+  rc = cc.rc;
+out:
+  free(md); free(td); free(bd); free(clip_of); free(w); free(prior); free(tables);
+  return course_finish(&cc, rc);
 }

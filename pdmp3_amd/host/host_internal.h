@@ -28,6 +28,7 @@
  *   clip_pitch.c    pitch of clips (YIN): the check, the lag range, the geometry of a workgroup
  *   clip_pyin.c     pYIN pitch tracking of clips: the check, the derived numbers, every table, the launches' geometry
  *   clip_tempogram.c onset strength, tempogram and tempo of clips: the check, the window, the prior, the launches' geometry
+ *   clip_beat.c     beat tracking of clips: the check, the period, the two tables, the launches' geometry
  *   clip_spectral.c spectral descriptors of clips (rms, zcr, centroid, bandwidth, roll-off, flatness): the check, the kernel's plan
  *   clip_hpss.c     harmonic-percussive separation of clips: the check, the widening, the kernel's plan
  *   clip_mfcc_long.c librosa-style MFCC, deltas and dB mel of clips: the check, the DCT table, the delta taps, the kernel's plan

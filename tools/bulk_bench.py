@@ -1396,6 +1396,90 @@ def clips_pyin(args, api):
     print(json.dumps(res))
 
 
+def clips_beat(args, api):
+    """--beat: 64 clips of 30 s (--clips / --clip-frames change that) at 22 050 Hz mono through the beat tracker with librosa's
+    defaults (n_fft 2048, hop 512, 128 bands, tempogram window 384, tightness 100, trim) in device memory, run after run in turn:
+    (a) pdmp3_amd_bulk_decode_clips_tempogram in mode "onset"; (b) the same call in mode "tempo"; (c) pdmp3_amd_bulk_decode_clips_beats
+    with the tempo estimated; (d) with bpm 120 given.  Beside the rotation, twice: (e) mode "onset", a copy to the host and the
+    numpy restatement of the tracker (tests/clip_beat_ref.py) clip by clip at the period (b) decided -- what a caller without this
+    call does.  The kernels' own times come from a kernel-trace run of this mode (profiles/clip_beat.txt).  Medians and min..max
+    of --runs runs."""
+    import random
+    import statistics
+    import torch
+    from math import gcd
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import clip_beat_ref as ref
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+    rng = random.Random(args.seed)
+    K, Fm, rate, N, H = args.clips, args.clip_frames, 22050, 2048, 512
+    span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
+    F = span // H + 1
+    plan_est, plan_given = api.beat_plan(rate, n_frames=F), api.beat_plan(rate, n_frames=F, bpm=120.0)
+    clips = []
+    for _ in range(K):
+        i = rng.randrange(len(files))
+        a = rng.randrange(200, max(201, ixs[i].frames - Fm - 200))
+        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
+        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
+        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    dev = "cuda:0"
+    onset = torch.zeros((K, 1, F), dtype=torch.float32, device=dev)
+    tempo = torch.zeros((K, 1, 4), dtype=torch.float32, device=dev)
+    beats = torch.zeros((K, 1, 2, F), dtype=torch.float32, device=dev)
+    given = torch.zeros((K, 1, 2, F), dtype=torch.float32, device=dev)
+    stats = torch.zeros((K, 1, 8), dtype=torch.float32, device=dev)
+    stats_g = torch.zeros((K, 1, 8), dtype=torch.float32, device=dev)
+    dec = api.BulkDecoder(threads=args.clip_threads)
+    torch.cuda.synchronize()
+    routes = [("tempogram clips, onset", lambda: dec.decode_clips_tempogram(clips, F, rate, out_mode="onset", out=onset)),
+              ("tempogram clips, tempo", lambda: dec.decode_clips_tempogram(clips, F, rate, out_mode="tempo", out=tempo)),
+              ("beat clips, tempo estimated", lambda: dec.decode_clips_beats(clips, F, rate, out=beats, stats=stats)),
+              ("beat clips, bpm 120", lambda: dec.decode_clips_beats(clips, F, rate, bpm=120.0, out=given, stats=stats_g))]
+    times = {name: [] for name, _ in routes}
+    for r in range(args.warmup_runs + args.runs):
+        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= args.warmup_runs:
+                times[name].append(dt)
+    periods = [int(x) for x in tempo[:, 0, 1].cpu().numpy()]
+    tabs = {p: api.beat_tables(p) for p in set(periods)}
+    host_times, same = [], True
+    for r in range(2):
+        t0 = time.perf_counter()
+        dec.decode_clips_tempogram(clips, F, rate, out_mode="onset", out=onset)
+        o = onset.cpu().numpy()
+        rows = [ref.track(o[k, 0], F, periods[k], tabs[periods[k]][0], tabs[periods[k]][1], True)["beats"] for k in range(K)]
+        host_times.append(time.perf_counter() - t0)
+        same = same and bool(np.array_equal(np.stack(rows), beats[:, 0].cpu().numpy()))
+    dec.close()
+    st = stats[:, 0].cpu().numpy()
+    res = {"workload": "%d clips of %d frames at %d Hz mono, beat tracking, n_fft %d hop %d, tightness 100, trim: %s" % (
+               K, F, rate, N, H, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+           "source_rates": sorted(set(ix.rate for _, ix, _ in clips)), "destination": "device memory", "runs": args.runs,
+           "plan_estimated": plan_est, "plan_bpm_120": plan_given,
+           "seen": {"periods": sorted(set(periods)), "beats_kept_mean": float(st[:, 2].mean()), "beats_before_trim_mean": float(st[:, 3].mean()),
+                    "device_is_the_numpy_restatement": same},
+           "onset + copy + numpy restatement": {"seconds": {"min": round(min(host_times), 6), "max": round(max(host_times), 6)}},
+           "host_cpus": os.cpu_count()}
+    for name, ts in times.items():
+        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    res["estimated_minus_tempo_ms"] = round((med["beat clips, tempo estimated"] - med["tempogram clips, tempo"]) * 1e3, 3)
+    res["bpm_120_minus_onset_ms"] = round((med["beat clips, bpm 120"] - med["tempogram clips, onset"]) * 1e3, 3)
+    res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
+    for ix in ixs:
+        ix.close()
+    print(json.dumps(res))
+
+
 def torch_tempogram(l, lag, wt, f, window, prior, rate, hop, mode):
     """the definition of DESIGN.md section 21 (max_size 1) in torch on the device: l [K, n_mels, n_env + lag] log10 mel ->
     mode 0 [K, n_env], 1 [K, wt, f], 2 [K, 4]"""
@@ -1771,6 +1855,10 @@ def main():
                     help="64 clips of 30 s (or --clips / --clip-frames) through pYIN at 22 050 Hz mono with librosa.pyin's defaults "
                          "(pdmp3_amd_bulk_decode_clips_pyin, both modes) against the audio call alone and against the pitch call's curve "
                          "(see clips_pyin())")
+    ap.add_argument("--beat", action="store_true",
+                    help="64 clips of 30 s (or --clips / --clip-frames) through the beat tracker at 22 050 Hz mono with librosa's defaults "
+                         "(pdmp3_amd_bulk_decode_clips_beats, tempo estimated and given) against the tempogram call's onset and tempo modes and "
+                         "against the onset mode followed by a copy to the host and the numpy restatement (see clips_beat())")
     ap.add_argument("--tempogram", action="store_true",
                     help="64 clips of 30 s (or --clips / --clip-frames) as onset envelope, tempogram [384, 1292] and tempo at 22 050 Hz mono with "
                          "librosa's defaults (pdmp3_amd_bulk_decode_clips_tempogram, all three modes) against the audio call alone, the log-mel "
@@ -1794,7 +1882,7 @@ def main():
                     help="--clips: the clips as Kaldi-style MFCC features at 16 kHz mono (pdmp3_amd_bulk_decode_clips_mfcc) against the "
                          "audio call for the same spans and against the fbank call followed by torch.matmul (see clips_mfcc())")
     args = ap.parse_args()
-    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.pyin or args.tempogram or args.spectral or args.hpss or args.mfcc_long:
+    if args.stft_long or args.mel_long or args.cqt or args.chroma or args.loudness or args.r128 or args.pitch or args.pyin or args.beat or args.tempogram or args.spectral or args.hpss or args.mfcc_long:
         args.clips = args.clips or 64
         if not any(a.startswith("--clip-frames") for a in sys.argv[1:]):
             args.clip_frames = 1149
@@ -1810,6 +1898,8 @@ def main():
             return clips_pitch(args, api)
         if args.pyin:
             return clips_pyin(args, api)
+        if args.beat:
+            return clips_beat(args, api)
         if args.tempogram:
             return clips_tempogram(args, api)
         if args.mel_long:
