@@ -389,6 +389,46 @@ def _as_u8(data):
     return a if a.size else np.zeros(1, dtype=np.uint8)
 
 
+def _enum(table, value):
+    """a name of `table` (None where the table has it) -> its number; a number stays one"""
+    return table[value] if isinstance(value, str) or (value is None and None in table) else int(value)
+
+
+def _window_arg(call, window, win_length):
+    """the window / win_length pair of a transform call -> (win_length for the spec, 0 meaning n_fft to the library; the
+    window's address or None; the float32 array behind it, to be kept while the spec is in use)"""
+    w = None
+    if window is not None:
+        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
+        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
+            raise ValueError("%s: window must hold win_length values" % call)
+        win_length = w.size
+    return 0 if win_length is None else int(win_length), w.ctypes.data if w is not None else None, w
+
+
+def _check(spec_of, c_name, sample_rate, kw, refused, *more):
+    """every <feature>_check: spec_of(sample_rate=sample_rate, **kw) -> the spec (or (spec, what it points to)); an exception
+    of the types `refused` from it is False, any other is the caller's; then the library's verdict (more: its arguments
+    behind sample_rate)"""
+    try:
+        made = spec_of(sample_rate=sample_rate, **kw)
+    except refused:
+        return False
+    spec = made[0] if isinstance(made, tuple) else made        # (made keeps the window alive until the call is over)
+    return getattr(load_library(), c_name)(C.byref(spec), int(sample_rate), *[int(m) for m in more]) == 0
+
+
+def _plan(fn, lead, kinds):
+    """fn(*lead, one out-parameter of each ctypes type of `kinds`) -> the tuple of their values"""
+    outs = [kind(0) for kind in kinds]
+    if fn(*lead, *[C.byref(o) for o in outs]) != 0:
+        raise ValueError("%s: bad argument" % fn.__name__)
+    return tuple(o.value for o in outs)
+
+
+_I, _U, _LL = C.c_int, C.c_uint, C.c_longlong
+
+
 class RingReplay(RuntimeError):
     """PDMP3_BULK_REPLAY: the reference would replay its input ring on this stream (include/pdmp3_bulk.h)"""
 
@@ -418,11 +458,7 @@ PDMP3_BULK_MIXED_FORMAT = -3
 
 def audio_span(rate_in, rate_out, start, n, width=0, rolloff=0.0):
     """pdmp3_amd_audio_span -> (first input sample, count) that output samples [start, start + n) read, unclamped"""
-    lib = load_library()
-    a, c = C.c_longlong(0), C.c_longlong(0)
-    if lib.pdmp3_amd_audio_span(int(rate_in), int(rate_out), int(width), float(rolloff), int(start), int(n), C.byref(a), C.byref(c)) != 0:
-        raise ValueError("pdmp3_amd_audio_span: bad argument")
-    return a.value, c.value
+    return _plan(load_library().pdmp3_amd_audio_span, (int(rate_in), int(rate_out), int(width), float(rolloff), int(start), int(n)), (_LL, _LL))
 
 
 def audio_table(rate_in, rate_out, width=0, rolloff=0.0):
@@ -441,11 +477,7 @@ def audio_table(rate_in, rate_out, width=0, rolloff=0.0):
 def audio_lds_plan(rate_in, rate_out, channels, width=0, rolloff=0.0):
     """pdmp3_amd_audio_lds_plan -> (flags, span_cap): what k_clip_audio keeps in LDS for a clip of the pair in a call with
     `channels` channels (flags 1: the input span, 3: the table too, 0: nothing -- every sample straight from memory)"""
-    lib = load_library()
-    f, s = C.c_uint(0), C.c_uint(0)
-    if lib.pdmp3_amd_audio_lds_plan(int(rate_in), int(rate_out), int(width), float(rolloff), int(channels), C.byref(f), C.byref(s)) != 0:
-        raise ValueError("pdmp3_amd_audio_lds_plan: bad argument")
-    return f.value, s.value
+    return _plan(load_library().pdmp3_amd_audio_lds_plan, (int(rate_in), int(rate_out), int(width), float(rolloff), int(channels)), (_U, _U))
 
 
 class _MelSpec(C.Structure):                       # include/pdmp3_bulk.h pdmp3_amd_mel_spec
@@ -461,23 +493,20 @@ MEL_MODES = {"power": 0, "log": 1, "ln": 1, "log10": 2, "whisper": 3}
 
 def _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff):
     return _MelSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), int(n_mels), float(f_min), float(f_max),
-                    MEL_SCALES[scale] if isinstance(scale, str) else int(scale), MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm),
-                    int(n_frames), MEL_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+                    _enum(MEL_SCALES, scale), _enum(MEL_NORMS, norm), int(n_frames), _enum(MEL_MODES, mode), float(floor))
 
 
 def mel_check(sample_rate, n_fft=400, hop=160, n_mels=80, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney", mode="log10", floor=1e-10,
               n_frames=1):
     """pdmp3_amd_mel_check -> True when pdmp3_amd_bulk_decode_clips_mel would accept these numbers at sample_rate"""
-    spec = _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, 1, 0, 0.0)
-    return load_library().pdmp3_amd_mel_check(C.byref(spec), int(sample_rate)) == 0
+    kw = dict(n_frames=n_frames, n_fft=n_fft, hop=hop, n_mels=n_mels, f_min=f_min, f_max=f_max, scale=scale, norm=norm, mode=mode, floor=floor,
+              channels=1, width=0, rolloff=0.0)
+    return _check(_mel_spec, "pdmp3_amd_mel_check", sample_rate, kw, ())
 
 
 def mel_span(n_fft, hop, start, n_frames):
     """pdmp3_amd_mel_span -> (first sample, count) that frames 0 .. n_frames - 1 of a clip at `start` read, unclamped"""
-    a, c = C.c_longlong(0), C.c_longlong(0)
-    if load_library().pdmp3_amd_mel_span(int(n_fft), int(hop), int(start), int(n_frames), C.byref(a), C.byref(c)) != 0:
-        raise ValueError("pdmp3_amd_mel_span: bad argument")
-    return a.value, c.value
+    return _plan(load_library().pdmp3_amd_mel_span, (int(n_fft), int(hop), int(start), int(n_frames)), (_LL, _LL))
 
 
 def mel_dft_table(n_fft):
@@ -495,8 +524,7 @@ def mel_dft_table(n_fft):
 def mel_filterbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney"):
     """pdmp3_amd_mel_filterbank -> float32 numpy [n_mels, n_fft // 2 + 1]"""
     lib = load_library()
-    sc = MEL_SCALES[scale] if isinstance(scale, str) else int(scale)
-    no = MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm)
+    sc, no = _enum(MEL_SCALES, scale), _enum(MEL_NORMS, norm)
     n = lib.pdmp3_amd_mel_filterbank(int(sample_rate), int(n_fft), int(n_mels), float(f_min), float(f_max), sc, no, None, 0)
     if n < 0:
         raise ValueError("pdmp3_amd_mel_filterbank: bad argument")
@@ -507,10 +535,7 @@ def mel_filterbank(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="slan
 
 def mel_tile(n_fft, hop, n_mels):
     """pdmp3_amd_mel_tile -> (frames of a workgroup of k_clip_mel, LDS floats between two hops, LDS bytes of a workgroup)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_mel_tile(int(n_fft), int(hop), int(n_mels), C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_mel_tile: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_mel_tile, (int(n_fft), int(hop), int(n_mels)), (_I, _I, _U))
 
 
 class _FbankSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_fbank_spec
@@ -546,8 +571,7 @@ def _fbank_spec(n_frames=1, sample_rate=16000, frame_length=25.0, frame_shift=10
 def fbank_check(sample_rate=16000, **kw):
     """pdmp3_amd_fbank_check -> True when pdmp3_amd_bulk_decode_clips_fbank would accept these arguments (decode_clips_fbank's,
     and dither / use_power / raw_energy / snip_edges / vtln_warp, which are refused unless they have torchaudio's defaults)"""
-    spec = _fbank_spec(sample_rate=sample_rate, **kw)
-    return load_library().pdmp3_amd_fbank_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_fbank_spec, "pdmp3_amd_fbank_check", sample_rate, kw, ())
 
 
 def fbank_dft_length(win_length, round_to_power_of_two=True):
@@ -595,10 +619,7 @@ def fbank_valid(n_out, start, win_length, hop, n_frames):
 def fbank_tile(win_length, n_dft, hop, num_mel_bins):
     """pdmp3_amd_fbank_tile -> (frames of a workgroup of k_clip_fbank, LDS floats between two hops, LDS bytes of a workgroup;
     more than 64 KB: the static-array kernel)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_fbank_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_fbank_tile: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_fbank_tile, (int(win_length), int(n_dft), int(hop), int(num_mel_bins)), (_I, _I, _U))
 
 
 class _MfccSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_mfcc_spec
@@ -619,8 +640,7 @@ def mfcc_check(sample_rate=16000, **kw):
     """pdmp3_amd_mfcc_check -> True when pdmp3_amd_bulk_decode_clips_mfcc would accept these arguments (decode_clips_mfcc's,
     and use_log_fbank / dither / use_power / raw_energy / snip_edges / vtln_warp, which are refused unless they have
     torchaudio's defaults)"""
-    spec = _mfcc_spec(sample_rate=sample_rate, **kw)
-    return load_library().pdmp3_amd_mfcc_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_mfcc_spec, "pdmp3_amd_mfcc_check", sample_rate, kw, ())
 
 
 def mfcc_dct_table(num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, htk_compat=False, use_energy=False):
@@ -640,11 +660,7 @@ def mfcc_dct_table(num_mel_bins=23, num_ceps=13, cepstral_lifter=22.0, htk_compa
 def mfcc_tile(win_length, n_dft, hop, num_mel_bins, num_ceps):
     """pdmp3_amd_mfcc_tile -> (frames of a workgroup of k_clip_mfcc, LDS floats between two hops, LDS bytes of a workgroup;
     more than 64 KB: the static-array kernel)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_mfcc_tile(int(win_length), int(n_dft), int(hop), int(num_mel_bins), int(num_ceps), C.byref(t), C.byref(p),
-                                          C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_mfcc_tile: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_mfcc_tile, (int(win_length), int(n_dft), int(hop), int(num_mel_bins), int(num_ceps)), (_I, _I, _U))
 
 
 class _StftSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_stft_spec
@@ -659,26 +675,16 @@ STFT_MODES = {"complex": 0, "magnitude": 1, "power": 2, "log": 3, "ln": 3, "log1
 def _stft_spec(n_frames=1, sample_rate=16000, n_fft=400, hop=160, win_length=None, window=None, normalized=False, mode="complex", floor=1e-10,
                channels=1, width=0, rolloff=0.0):
     """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
-    w = None
-    if window is not None:
-        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
-        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
-            raise ValueError("stft: window must hold win_length values")
-        win_length = w.size
-    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
-    spec = _StftSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, w.ctypes.data if w is not None else None,
-                     int(bool(normalized)), int(n_frames), STFT_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+    nw, wp, w = _window_arg("stft", window, win_length)
+    spec = _StftSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, wp, int(bool(normalized)), int(n_frames),
+                     _enum(STFT_MODES, mode), float(floor))
     return spec, w
 
 
 def stft_check(sample_rate=16000, **kw):
     """pdmp3_amd_stft_check -> True when pdmp3_amd_bulk_decode_clips_stft would accept these numbers (decode_clips_stft's
     argument names) at sample_rate"""
-    try:
-        spec, keep = _stft_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError):
-        return False
-    return load_library().pdmp3_amd_stft_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_stft_spec, "pdmp3_amd_stft_check", sample_rate, kw, (ValueError, KeyError))
 
 
 def stft_table(n_fft=400, win_length=None, window=None, normalized=False):
@@ -696,11 +702,7 @@ def stft_table(n_fft=400, win_length=None, window=None, normalized=False):
 
 def stft_tile(n_fft, hop, mode="complex"):
     """pdmp3_amd_stft_tile -> (frames of a workgroup of k_clip_stft, LDS floats between two hops, LDS bytes of a workgroup)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
-    if load_library().pdmp3_amd_stft_tile(int(n_fft), int(hop), m, C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_stft_tile: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_stft_tile, (int(n_fft), int(hop), _enum(STFT_MODES, mode)), (_I, _I, _U))
 
 
 class _CqtSpec(C.Structure):                       # include/pdmp3_bulk.h pdmp3_amd_cqt_spec
@@ -715,17 +717,13 @@ CQT_FMIN = 32.70319566257483                       # C1
 def _cqt_spec(n_frames=1, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, filter_scale=1.0, norm=1, scale=1,
               mode="magnitude", floor=1e-10, channels=1, width=0, rolloff=0.0):
     return _CqtSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(hop), float(fmin), int(n_bins), int(bins_per_octave),
-                    float(filter_scale), int(norm), int(scale), int(n_frames), STFT_MODES[mode] if isinstance(mode, str) else int(mode), float(floor))
+                    float(filter_scale), int(norm), int(scale), int(n_frames), _enum(STFT_MODES, mode), float(floor))
 
 
 def cqt_check(sample_rate=22050, **kw):
     """pdmp3_amd_cqt_check -> True when pdmp3_amd_bulk_decode_clips_cqt would accept these numbers (decode_clips_cqt's argument
     names) at sample_rate"""
-    try:
-        spec = _cqt_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError):
-        return False
-    return load_library().pdmp3_amd_cqt_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_cqt_spec, "pdmp3_amd_cqt_check", sample_rate, kw, (ValueError, KeyError, OverflowError))
 
 
 def cqt_lengths(sample_rate=22050, **kw):
@@ -760,11 +758,7 @@ def cqt_plan(sample_rate=22050, **kw):
     """pdmp3_amd_cqt_plan -> (frames of a workgroup of k_clip_cqt, LDS floats between two hops, LDS bytes of a workgroup, rows
     from which a tile is split, segments of a split tile, tiles that are split)"""
     spec = _cqt_spec(sample_rate=sample_rate, **kw)
-    t, p, sr, sg, ns, b = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_cqt_plan(C.byref(spec), int(sample_rate), C.byref(t), C.byref(p), C.byref(b), C.byref(sr), C.byref(sg),
-                                         C.byref(ns)) != 0:
-        raise ValueError("pdmp3_amd_cqt_plan: bad argument")
-    return t.value, p.value, b.value, sr.value, sg.value, ns.value
+    return _plan(load_library().pdmp3_amd_cqt_plan, (C.byref(spec), int(sample_rate)), (_I, _I, _U, _I, _I, _I))
 
 
 class _ChromaSpec(C.Structure):                    # include/pdmp3_bulk.h pdmp3_amd_chroma_spec
@@ -776,10 +770,10 @@ CHROMA_NORMS = {None: 0, "none": 0, "l1": 1, "l2": 2, "max": 3, "inf": 3}
 
 def _chroma_spec(n_frames=1, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=84, bins_per_octave=12, n_chroma=12, base_class=0, filter_scale=1.0,
                  norm=1, scale=1, quantity="magnitude", chroma_norm="max", norm_floor=1e-10, channels=1, width=0, rolloff=0.0):
-    q = STFT_MODES[quantity] if isinstance(quantity, str) else int(quantity)
+    q = _enum(STFT_MODES, quantity)
     if isinstance(chroma_norm, str) and chroma_norm not in CHROMA_NORMS:
         raise ValueError("chroma_norm is one of %s" % sorted(k for k in CHROMA_NORMS if k))
-    cn = CHROMA_NORMS[chroma_norm] if isinstance(chroma_norm, str) or chroma_norm is None else int(chroma_norm)
+    cn = _enum(CHROMA_NORMS, chroma_norm)
     cqt = _cqt_spec(n_frames, sample_rate, hop, fmin, n_bins, bins_per_octave, filter_scale, norm, scale, q, 0.0, channels, width, rolloff)
     return _ChromaSpec(cqt, int(n_chroma), int(base_class), cn, float(norm_floor))
 
@@ -787,11 +781,7 @@ def _chroma_spec(n_frames=1, sample_rate=22050, hop=512, fmin=CQT_FMIN, n_bins=8
 def chroma_check(sample_rate=22050, **kw):
     """pdmp3_amd_chroma_check -> True when pdmp3_amd_bulk_decode_clips_chroma would accept these numbers (decode_clips_chroma's
     argument names) at sample_rate"""
-    try:
-        spec = _chroma_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError):
-        return False
-    return load_library().pdmp3_amd_chroma_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_chroma_spec, "pdmp3_amd_chroma_check", sample_rate, kw, (ValueError, KeyError, OverflowError))
 
 
 def chroma_map(sample_rate=22050, **kw):
@@ -809,22 +799,13 @@ def chroma_plan(sample_rate=22050, **kw):
     rows from which a tile is split, segments of a split tile, tiles that are split, LDS floats in front of the q plane, LDS
     floats in front of the class plane)"""
     spec = _chroma_spec(sample_rate=sample_rate, **kw)
-    t, p, sr, sg, ns = (C.c_int(0) for _ in range(5))
-    b, qa, ca = (C.c_uint(0) for _ in range(3))
-    if load_library().pdmp3_amd_chroma_plan(C.byref(spec), int(sample_rate), C.byref(t), C.byref(p), C.byref(b), C.byref(sr), C.byref(sg),
-                                            C.byref(ns), C.byref(qa), C.byref(ca)) != 0:
-        raise ValueError("pdmp3_amd_chroma_plan: bad argument")
-    return t.value, p.value, b.value, sr.value, sg.value, ns.value, qa.value, ca.value
+    return _plan(load_library().pdmp3_amd_chroma_plan, (C.byref(spec), int(sample_rate)), (_I, _I, _U, _I, _I, _I, _U, _U))
 
 
 def stft_long_check(sample_rate=44100, n_fft=2048, hop=512, **kw):
     """pdmp3_amd_stft_long_check -> True when pdmp3_amd_bulk_decode_clips_stft_long would accept these numbers
     (decode_clips_stft_long's argument names) at sample_rate"""
-    try:
-        spec, keep = _stft_spec(sample_rate=sample_rate, n_fft=n_fft, hop=hop, **kw)
-    except (ValueError, KeyError):
-        return False
-    return load_library().pdmp3_amd_stft_long_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_stft_spec, "pdmp3_amd_stft_long_check", sample_rate, dict(kw, n_fft=n_fft, hop=hop), (ValueError, KeyError))
 
 
 def stft_long_tables(n_fft=2048, win_length=None, window=None, normalized=False):
@@ -849,11 +830,7 @@ def stft_long_tables(n_fft=2048, win_length=None, window=None, normalized=False)
 
 def stft_long_plan(n_fft, hop, mode="complex"):
     """pdmp3_amd_stft_long_plan -> (frames of a workgroup of k_clip_stft_long, 0, LDS bytes of a workgroup)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
-    if load_library().pdmp3_amd_stft_long_plan(int(n_fft), int(hop), m, C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_stft_long_plan: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_stft_long_plan, (int(n_fft), int(hop), _enum(STFT_MODES, mode)), (_I, _I, _U))
 
 
 class _MelLongSpec(C.Structure):                   # include/pdmp3_bulk.h pdmp3_amd_mel_long_spec
@@ -863,30 +840,19 @@ class _MelLongSpec(C.Structure):                   # include/pdmp3_bulk.h pdmp3_
 def _mel_long_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=128, f_min=0.0, f_max=0.0, scale="slaney", norm="slaney",
                    mode="log10", floor=1e-10, win_length=None, window=None, channels=1, width=0, rolloff=0.0):
     """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
-    w = None
-    if window is not None:
-        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
-        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
-            raise ValueError("mel_long: window must hold win_length values")
-        win_length = w.size
-    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    nw, wp, w = _window_arg("mel_long", window, win_length)
     mel = _mel_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, mode, floor, channels, width, rolloff)
-    return _MelLongSpec(mel, nw, w.ctypes.data if w is not None else None), w
+    return _MelLongSpec(mel, nw, wp), w
 
 
 def mel_long_check(sample_rate=22050, **kw):
     """pdmp3_amd_mel_long_check -> True when pdmp3_amd_bulk_decode_clips_mel_long would accept these numbers
     (decode_clips_mel_long's argument names) at sample_rate"""
-    try:
-        spec, keep = _mel_long_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError):
-        return False
-    return load_library().pdmp3_amd_mel_long_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_mel_long_spec, "pdmp3_amd_mel_long_check", sample_rate, kw, (ValueError, KeyError))
 
 
 def _mel_long_bank(sample_rate, n_fft, n_mels, f_min, f_max, scale, norm):
-    sc = MEL_SCALES[scale] if isinstance(scale, str) else int(scale)
-    no = MEL_NORMS[norm] if (norm is None or isinstance(norm, str)) else int(norm)
+    sc, no = _enum(MEL_SCALES, scale), _enum(MEL_NORMS, norm)
     return int(sample_rate), int(n_fft), int(n_mels), float(f_min), float(f_max), sc, no
 
 
@@ -916,10 +882,7 @@ def mel_long_operand(sample_rate, n_fft, n_mels, f_min=0.0, f_max=0.0, scale="sl
 
 def mel_long_plan(n_fft, hop, n_mels):
     """pdmp3_amd_mel_long_plan -> (frames of a workgroup of k_clip_mel_long, 0, LDS bytes of a workgroup)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_mel_long_plan(int(n_fft), int(hop), int(n_mels), C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_mel_long_plan: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_mel_long_plan, (int(n_fft), int(hop), int(n_mels)), (_I, _I, _U))
 
 
 class _SpectralSpec(C.Structure):                  # include/pdmp3_bulk.h pdmp3_amd_spectral_spec
@@ -934,34 +897,21 @@ SPECTRAL_ROWS = ("rms", "zcr", "centroid", "bandwidth", "rolloff", "flatness")
 def _spectral_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, roll_percent=0.85, amin=1e-10, zcr_threshold=1e-10, channels=1,
                    win_length=None, window=None, width=0, rolloff=0.0):
     """-> (spec, the float32 array its window points to, to be kept while the spec is in use)"""
-    w = None
-    if window is not None:
-        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
-        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
-            raise ValueError("spectral: window must hold win_length values")
-        win_length = w.size
-    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
-    spec = _SpectralSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw,
-                         w.ctypes.data if w is not None else None, int(n_frames), float(roll_percent), float(amin), float(zcr_threshold))
+    nw, wp, w = _window_arg("spectral", window, win_length)
+    spec = _SpectralSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, wp, int(n_frames),
+                         float(roll_percent), float(amin), float(zcr_threshold))
     return spec, w
 
 
 def spectral_check(sample_rate=22050, **kw):
     """pdmp3_amd_spectral_check -> True when pdmp3_amd_bulk_decode_clips_spectral would accept these numbers
     (decode_clips_spectral's argument names) at sample_rate"""
-    try:
-        spec, keep = _spectral_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, TypeError, OverflowError):
-        return False
-    return load_library().pdmp3_amd_spectral_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_spectral_spec, "pdmp3_amd_spectral_check", sample_rate, kw, (ValueError, KeyError, TypeError, OverflowError))
 
 
 def spectral_plan(n_fft, hop):
     """pdmp3_amd_spectral_plan -> (frames of a workgroup of k_clip_spectral, 0, LDS bytes of a workgroup)"""
-    t, p, b = C.c_int(0), C.c_int(0), C.c_uint(0)
-    if load_library().pdmp3_amd_spectral_plan(int(n_fft), int(hop), C.byref(t), C.byref(p), C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_spectral_plan: bad argument")
-    return t.value, p.value, b.value
+    return _plan(load_library().pdmp3_amd_spectral_plan, (int(n_fft), int(hop)), (_I, _I, _U))
 
 
 class _HpssSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_hpss_spec
@@ -977,40 +927,26 @@ def _hpss_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, kernel_size=3
                win_length=None, window=None, width=0, rolloff=0.0):
     """-> (spec, the float32 array its window points to, to be kept while the spec is in use); kernel_size and margin: one
     number or (harmonic, percussive), as librosa takes them"""
-    w = None
-    if window is not None:
-        w = np.ascontiguousarray(window.detach().cpu().numpy() if hasattr(window, "detach") else window, dtype=np.float32)
-        if w.ndim != 1 or (win_length is not None and w.size != int(win_length)) or (win_length is None and not w.size):
-            raise ValueError("hpss: window must hold win_length values")
-        win_length = w.size
-    nw = 0 if win_length is None else int(win_length)      # (0 means n_fft to the library)
+    nw, wp, w = _window_arg("hpss", window, win_length)
     kh, kp = kernel_size if isinstance(kernel_size, (tuple, list)) else (kernel_size, kernel_size)
     mh, mp = margin if isinstance(margin, (tuple, list)) else (margin, margin)
     if int(kh) != kh or int(kp) != kp:
         raise ValueError("hpss: kernel sizes are integers")
-    spec = _HpssSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, w.ctypes.data if w is not None else None,
-                     int(n_frames), int(kh), int(kp), float(mh), float(mp), float(power), HPSS_MODES[mode] if isinstance(mode, str) else int(mode))
+    spec = _HpssSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_fft), int(hop), nw, wp, int(n_frames), int(kh), int(kp),
+                     float(mh), float(mp), float(power), _enum(HPSS_MODES, mode))
     return spec, w
 
 
 def hpss_check(sample_rate=22050, **kw):
     """pdmp3_amd_hpss_check -> True when pdmp3_amd_bulk_decode_clips_hpss would accept these numbers (decode_clips_hpss's
     argument names) at sample_rate"""
-    try:
-        spec, keep = _hpss_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, TypeError, OverflowError):
-        return False
-    return load_library().pdmp3_amd_hpss_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_hpss_spec, "pdmp3_amd_hpss_check", sample_rate, kw, (ValueError, KeyError, TypeError, OverflowError))
 
 
 def hpss_plan(kernel_harm=31, kernel_perc=31):
     """pdmp3_amd_hpss_plan -> (frames in front, frames behind, bins of a workgroup of k_clip_hpss, its frames, the floats between
     two rows of its tile in LDS, its LDS bytes)"""
-    v = [C.c_int(0) for _ in range(5)]
-    b = C.c_uint(0)
-    if load_library().pdmp3_amd_hpss_plan(int(kernel_harm), int(kernel_perc), *[C.byref(x) for x in v], C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_hpss_plan: bad argument")
-    return tuple(x.value for x in v) + (b.value,)
+    return _plan(load_library().pdmp3_amd_hpss_plan, (int(kernel_harm), int(kernel_perc)), (_I,) * 5 + (_U,))
 
 
 class _MfccLongSpec(C.Structure):                  # include/pdmp3_bulk.h pdmp3_amd_mfcc_long_spec
@@ -1027,8 +963,8 @@ def _mfcc_long_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=1
     """-> (spec, what its window points to).  top_db None: no clamp (a negative value to the library)"""
     mel, keep = _mel_long_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, "log10", amin, win_length, window, channels,
                                width, rolloff)
-    mode = MFCC_LONG_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)
-    if mode == 1:                                          # (the dB mode reads none of the cepstral fields)
+    mode = _enum(MFCC_LONG_MODES, out_mode)
+    if mode == 1:                                         # (the dB mode reads none of the cepstral fields)
         n_mfcc, lifter, deltas, delta_width = 0, 0.0, 0, 0
     elif int(n_mfcc) != n_mfcc or int(deltas) != deltas or int(delta_width) != delta_width:
         raise ValueError("mfcc_long: n_mfcc, deltas and delta_width are integers")
@@ -1041,11 +977,7 @@ def _mfcc_long_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=1
 def mfcc_long_check(sample_rate=22050, **kw):
     """pdmp3_amd_mfcc_long_check -> True when pdmp3_amd_bulk_decode_clips_mfcc_long would accept these numbers
     (decode_clips_mfcc_long's argument names) at sample_rate"""
-    try:
-        spec, keep = _mfcc_long_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_mfcc_long_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_mfcc_long_spec, "pdmp3_amd_mfcc_long_check", sample_rate, kw, (ValueError, KeyError, OverflowError, TypeError))
 
 
 def mfcc_long_dct_table(n_mels=128, n_mfcc=20, lifter=0.0):
@@ -1072,12 +1004,8 @@ def mfcc_long_delta_taps(delta_width=9):
 def mfcc_long_plan(n_mels=128, n_mfcc=20, deltas=0, delta_width=9, out_mode="mfcc"):
     """pdmp3_amd_mfcc_long_plan -> (log-mel frames in front of frame 0, behind the last frame, frames of a workgroup of
     k_clip_mfcc_long, the floats between two rows of its plane of dB values, of its plane of cepstra, its LDS bytes)"""
-    v = [C.c_int(0) for _ in range(5)]
-    b = C.c_uint(0)
-    m = MFCC_LONG_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)
-    if load_library().pdmp3_amd_mfcc_long_plan(int(n_mels), int(n_mfcc), int(deltas), int(delta_width), m, *[C.byref(x) for x in v], C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_mfcc_long_plan: bad argument")
-    return tuple(x.value for x in v) + (b.value,)
+    return _plan(load_library().pdmp3_amd_mfcc_long_plan, (int(n_mels), int(n_mfcc), int(deltas), int(delta_width), _enum(MFCC_LONG_MODES, out_mode)),
+                 (_I,) * 5 + (_U,))
 
 
 class StreamIndex:
@@ -1153,11 +1081,7 @@ def _loudness_spec(n_samples=0, sample_rate=0, channels=0, target=None, peak_lim
 def loudness_check(sample_rate, channels=1, **kw):
     """pdmp3_amd_loudness_check -> True when pdmp3_amd_bulk_decode_clips_loudness would accept these numbers (decode_clips_loudness's
     target, peak_limit, dual_mono) at sample_rate and `channels` channels"""
-    try:
-        spec = _loudness_spec(sample_rate=sample_rate, channels=channels, **kw)
-    except (ValueError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_loudness_check(C.byref(spec), int(sample_rate), int(channels)) == 0
+    return _check(_loudness_spec, "pdmp3_amd_loudness_check", sample_rate, dict(kw, channels=channels), (ValueError, OverflowError, TypeError), channels)
 
 
 def loudness_coefficients(sample_rate):
@@ -1181,13 +1105,7 @@ def loudness_tables(sample_rate):
 def loudness_plan(sample_rate, n_samples):
     """pdmp3_amd_loudness_plan -> (samples of a block, blocks of a scan chunk, LDS bytes of a workgroup of k_loud_blocks, q, chunks
     of a row, I, J)"""
-    b, ch, q = C.c_int(0), C.c_int(0), C.c_int(0)
-    lds = C.c_uint(0)
-    nc, i, j = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
-    if load_library().pdmp3_amd_loudness_plan(int(sample_rate), int(n_samples), C.byref(b), C.byref(ch), C.byref(lds), C.byref(q), C.byref(nc),
-                                               C.byref(i), C.byref(j)) != 0:
-        raise ValueError("pdmp3_amd_loudness_plan: bad argument")
-    return b.value, ch.value, lds.value, q.value, nc.value, i.value, j.value
+    return _plan(load_library().pdmp3_amd_loudness_plan, (int(sample_rate), int(n_samples)), (_I, _I, _U, _I) + (_LL,) * 3)
 
 
 class _R128Spec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_r128_spec
@@ -1201,11 +1119,7 @@ def _r128_spec(n_samples=0, sample_rate=0, channels=0, target=None, peak_limit=0
 def r128_check(sample_rate, channels=1, **kw):
     """pdmp3_amd_r128_check -> True when pdmp3_amd_bulk_decode_clips_r128 would accept these numbers (decode_clips_r128's n_samples,
     target, peak_limit, limit_true_peak, dual_mono) at sample_rate and `channels` channels"""
-    try:
-        spec = _r128_spec(sample_rate=sample_rate, channels=channels, **kw)
-    except (ValueError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_r128_check(C.byref(spec), int(sample_rate), int(channels)) == 0
+    return _check(_r128_spec, "pdmp3_amd_r128_check", sample_rate, dict(kw, channels=channels), (ValueError, OverflowError, TypeError), channels)
 
 
 def r128_taps():
@@ -1220,13 +1134,7 @@ def r128_taps():
 def r128_plan(sample_rate, n_samples):
     """pdmp3_amd_r128_plan -> loudness_plan's seven numbers, then Js (3 s windows), Jr (those of the range) and Jsmax (floats of a
     row of short_term)"""
-    b, ch, q = C.c_int(0), C.c_int(0), C.c_int(0)
-    lds = C.c_uint(0)
-    v = [C.c_longlong(0) for _ in range(6)]
-    if load_library().pdmp3_amd_r128_plan(int(sample_rate), int(n_samples), C.byref(b), C.byref(ch), C.byref(lds), C.byref(q),
-                                           *[C.byref(x) for x in v]) != 0:
-        raise ValueError("pdmp3_amd_r128_plan: bad argument")
-    return (b.value, ch.value, lds.value, q.value) + tuple(x.value for x in v)
+    return _plan(load_library().pdmp3_amd_r128_plan, (int(sample_rate), int(n_samples)), (_I, _I, _U, _I) + (_LL,) * 6)
 
 
 class _PitchSpec(C.Structure):                     # include/pdmp3_bulk.h pdmp3_amd_pitch_spec
@@ -1244,36 +1152,26 @@ def _pitch_spec(n_frames=1, sample_rate=22050, frame_length=2048, win_length=Non
     """(None means 0 to the library: win_length frame_length / 2, hop frame_length / 4)"""
     return _PitchSpec(int(sample_rate), int(channels), int(width), float(rolloff), int(n_frames), int(frame_length),
                       0 if win_length is None else int(win_length), 0 if hop is None else int(hop), float(fmin), float(fmax), float(threshold),
-                      PITCH_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode))
+                      _enum(PITCH_MODES, out_mode))
 
 
 def pitch_check(sample_rate=22050, **kw):
     """pdmp3_amd_pitch_check -> True when pdmp3_amd_bulk_decode_clips_pitch would accept these numbers (decode_clips_pitch's
     argument names) at sample_rate"""
-    try:
-        spec = _pitch_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_pitch_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_pitch_spec, "pdmp3_amd_pitch_check", sample_rate, kw, (ValueError, KeyError, OverflowError, TypeError))
 
 
 def pitch_lags(sample_rate=22050, **kw):
     """pdmp3_amd_pitch_lags -> (tmin, tmax, lag tiles of 256 a frame)"""
     spec = _pitch_spec(sample_rate=sample_rate, **kw)
-    a, b, t = C.c_int(0), C.c_int(0), C.c_int(0)
-    if load_library().pdmp3_amd_pitch_lags(C.byref(spec), int(sample_rate), C.byref(a), C.byref(b), C.byref(t)) != 0:
-        raise ValueError("pdmp3_amd_pitch_lags: bad argument")
-    return a.value, b.value, t.value
+    return _plan(load_library().pdmp3_amd_pitch_lags, (C.byref(spec), int(sample_rate)), (_I, _I, _I))
 
 
 def pitch_plan(sample_rate=22050, **kw):
     """pdmp3_amd_pitch_plan -> (frames of a workgroup of k_clip_pitch, LDS floats of its span, LDS bytes, matrix instructions a
     lag tile)"""
     spec = _pitch_spec(sample_rate=sample_rate, **kw)
-    f, k, sp, b = C.c_int(0), C.c_int(0), C.c_uint(0), C.c_uint(0)
-    if load_library().pdmp3_amd_pitch_plan(C.byref(spec), int(sample_rate), C.byref(f), C.byref(sp), C.byref(b), C.byref(k)) != 0:
-        raise ValueError("pdmp3_amd_pitch_plan: bad argument")
-    return f.value, sp.value, b.value, k.value
+    return _plan(load_library().pdmp3_amd_pitch_plan, (C.byref(spec), int(sample_rate)), (_I, _U, _U, _I))
 
 
 class _PyinSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_pyin_spec
@@ -1300,18 +1198,14 @@ def _pyin_spec(n_frames=1, sample_rate=22050, channels=0, frame_length=2048, win
     a, b = beta
     spec = _PyinSpec(pitch, int(n_thresholds), float(a), float(b), None if keep is None else keep.ctypes.data, float(boltzmann), float(resolution),
                      float(max_transition_rate), float(switch_prob), float(no_trough_prob), 0.0 if fill is None else float(fill),
-                     1 if fill is None else 0, PYIN_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode))
+                     1 if fill is None else 0, _enum(PYIN_MODES, out_mode))
     return spec, keep
 
 
 def pyin_check(sample_rate=22050, **kw):
     """pdmp3_amd_pyin_check -> True when pdmp3_amd_bulk_decode_clips_pyin would accept these numbers (decode_clips_pyin's
     argument names) at sample_rate"""
-    try:
-        spec, keep = _pyin_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_pyin_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_pyin_spec, "pdmp3_amd_pyin_check", sample_rate, kw, (ValueError, KeyError, OverflowError, TypeError))
 
 
 def pyin_tables(sample_rate=22050, **kw):
@@ -1365,17 +1259,13 @@ def _tempogram_spec(n_frames=1, sample_rate=22050, n_fft=2048, hop=512, n_mels=1
     mel, keep = _mel_long_spec(n_frames, sample_rate, n_fft, hop, n_mels, f_min, f_max, scale, norm, "log10", floor, fft_win_length, fft_window,
                                channels, width, rolloff)
     return _TempogramSpec(mel, int(lag), int(max_size), int(win_length), float(start_bpm), float(std_bpm), float(max_tempo),
-                          TEMPOGRAM_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)), keep
+                          _enum(TEMPOGRAM_MODES, out_mode)), keep
 
 
 def tempogram_check(sample_rate=22050, **kw):
     """pdmp3_amd_tempogram_check -> True when pdmp3_amd_bulk_decode_clips_tempogram would accept these numbers
     (decode_clips_tempogram's argument names) at sample_rate"""
-    try:
-        spec, keep = _tempogram_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_tempogram_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_tempogram_spec, "pdmp3_amd_tempogram_check", sample_rate, kw, (ValueError, KeyError, OverflowError, TypeError))
 
 
 def tempogram_window(win_length=384):
@@ -1401,11 +1291,7 @@ def tempogram_plan(sample_rate=22050, **kw):
     """pdmp3_amd_tempogram_plan -> (log-mel frames in front of frame 0, behind the last frame, lag tiles of 256, matrix
     instructions a lag tile, frames of a workgroup of k_clip_tempogram, its LDS bytes)"""
     spec, keep = _tempogram_spec(sample_rate=sample_rate, **kw)
-    v = [C.c_int(0) for _ in range(5)]
-    b = C.c_uint(0)
-    if load_library().pdmp3_amd_tempogram_plan(C.byref(spec), int(sample_rate), *[C.byref(x) for x in v], C.byref(b)) != 0:
-        raise ValueError("pdmp3_amd_tempogram_plan: bad argument")
-    return tuple(x.value for x in v) + (b.value,)
+    return _plan(load_library().pdmp3_amd_tempogram_plan, (C.byref(spec), int(sample_rate)), (_I,) * 5 + (_U,))
 
 
 class _BeatSpec(C.Structure):                      # include/pdmp3_bulk.h pdmp3_amd_beat_spec
@@ -1419,17 +1305,13 @@ BEAT_STATS = ("bpm", "period", "kept", "beats", "tail", "norm", "threshold", "fr
 def _beat_spec(n_frames=1, sample_rate=22050, bpm=0.0, tightness=100.0, trim=True, out_mode="beats", **kw):
     """-> (spec, what its window points to).  kw: decode_clips_tempogram's arguments without out_mode"""
     tg, keep = _tempogram_spec(n_frames, sample_rate, out_mode="onset", **kw)
-    return _BeatSpec(tg, float(bpm), float(tightness), 1 if trim else 0, BEAT_MODES[out_mode] if isinstance(out_mode, str) else int(out_mode)), keep
+    return _BeatSpec(tg, float(bpm), float(tightness), 1 if trim else 0, _enum(BEAT_MODES, out_mode)), keep
 
 
 def beat_check(sample_rate=22050, **kw):
     """pdmp3_amd_beat_check -> True when pdmp3_amd_bulk_decode_clips_beats would accept these numbers (decode_clips_beats's
     argument names) at sample_rate"""
-    try:
-        spec, keep = _beat_spec(sample_rate=sample_rate, **kw)
-    except (ValueError, KeyError, OverflowError, TypeError):
-        return False
-    return load_library().pdmp3_amd_beat_check(C.byref(spec), int(sample_rate)) == 0
+    return _check(_beat_spec, "pdmp3_amd_beat_check", sample_rate, kw, (ValueError, KeyError, OverflowError, TypeError))
 
 
 def beat_tables(period, sample_rate=22050, **kw):
@@ -1484,6 +1366,44 @@ def _clip_destination(out, k, c, inner, complex_ok=False):
         assert n <= 1 or s == want or 0 in shape               # (an array without elements has strides of no meaning)
         want *= n
     return base, strides[0] * 4, strides[1]
+
+
+def _address(a):
+    return a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data
+
+
+def _stats_like(out, shape):
+    """float32 `shape` full of NaN where a clip call's stats go: a torch tensor on out's device (the current one without out),
+    or a numpy array where out is one"""
+    if out is None or hasattr(out, "data_ptr"):
+        import torch
+        stats = torch.full(shape, float("nan"), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
+        torch.cuda.synchronize()
+        return stats
+    return np.full(shape, np.nan, dtype=np.float32)
+
+
+def _aux_destination(name, dst, k, want_cols, cols="n"):
+    """an auxiliary destination of a loudness call, float32 [>= k, want_cols()], contiguous, torch or numpy -> its address;
+    want_cols() None: any width (the library refuses the call, or writes nothing)"""
+    ok = (dst.is_contiguous() and str(dst.dtype) == "torch.float32") if hasattr(dst, "data_ptr") else (dst.flags["C_CONTIGUOUS"] and dst.dtype == np.float32)
+    assert ok and len(dst.shape) == 2 and dst.shape[0] >= k, "%s: float32 [>= K, %s], contiguous" % (name, cols)
+    n = want_cols()
+    assert n is None or dst.shape[1] == n, "%s: float32 [>= K, %s]" % (name, n)
+    return _address(dst)
+
+
+def _plan_field(call, plan, field, clips, sample_rate, n_samples):
+    """plan(rate, n_samples)[field] at the rate of decode_clips_<call>: sample_rate, or the clips' own where they share one; None
+    without a rate or samples"""
+    rates = set(ix.rate for _, ix, _ in clips if not ix.replay and ix.one_format and ix.frames)
+    fs = int(sample_rate) or (rates.pop() if len(rates) == 1 else 0)
+    if not (fs and n_samples):
+        return None
+    try:
+        return plan(fs, n_samples)[field]
+    except ValueError:
+        raise RuntimeError("pdmp3_amd_bulk_decode_clips_%s: bad sample_rate or n_samples" % call)
 
 
 class BulkDecoder:
@@ -1834,32 +1754,14 @@ class BulkDecoder:
         at its first sample.  Rows of stats belonging to clips that raise RingReplay / MixedFormat (.out, .stats, .valid) stay
         NaN.  With n_samples = 0 nothing is measured: stats stays NaN."""
         t, k = int(n_samples), len(clips)
-        if out is None or hasattr(out, "data_ptr"):
-            import torch
-            stats = torch.full((k, 8), float("nan"), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
-            torch.cuda.synchronize()
-            sp = stats.data_ptr()
-        else:
-            stats = np.full((k, 8), np.nan, dtype=np.float32)
-            sp = stats.ctypes.data
+        stats = _stats_like(out, (k, 8))
         mp = None
         if momentary is not None:
-            torch_like = hasattr(momentary, "data_ptr")
-            ok = (momentary.is_contiguous() and str(momentary.dtype) == "torch.float32") if torch_like else \
-                (momentary.flags["C_CONTIGUOUS"] and momentary.dtype == np.float32)
-            assert ok and len(momentary.shape) == 2 and momentary.shape[0] >= k, "momentary: float32 [>= K, Jmax], contiguous"
-            rates = set(ix.rate for _, ix, _ in clips if not ix.replay and ix.one_format and ix.frames)
-            fs = int(sample_rate) or (rates.pop() if len(rates) == 1 else 0)
-            if fs and t:                           # (else the library refuses the call, or writes nothing)
-                try:
-                    jmax = loudness_plan(fs, t)[6]
-                except ValueError:
-                    raise RuntimeError("pdmp3_amd_bulk_decode_clips_loudness: bad sample_rate or n_samples")
-                assert momentary.shape[1] == jmax, "momentary: float32 [>= K, %d]" % jmax
-            mp = momentary.data_ptr() if torch_like else momentary.ctypes.data
+            mp = _aux_destination("momentary", momentary, k, lambda: _plan_field("loudness", loudness_plan, 6, clips, sample_rate, t), "Jmax")
         spec = lambda: (_loudness_spec(t, sample_rate, channels, target, peak_limit, dual_mono, width, rolloff), None)
         try:
-            audio, valid = self._clips_call("loudness", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError), extra=(sp, mp))
+            audio, valid = self._clips_call("loudness", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError),
+                                            extra=(_address(stats), mp))
         except (RingReplay, MixedFormat) as e:
             e.stats = stats
             raise
@@ -1877,34 +1779,13 @@ class BulkDecoder:
         float32 [K, Jsmax] destination for the window loudnesses S_j, Jsmax = max(0, n_samples // q - 29).  A clip's filters
         start from rest at its first sample.  Rows of stats belonging to clips that raise RingReplay / MixedFormat stay NaN."""
         t, k = int(n_samples), len(clips)
-        if out is None or hasattr(out, "data_ptr"):
-            import torch
-            stats = torch.full((k, 16), float("nan"), dtype=torch.float32, device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
-            torch.cuda.synchronize()
-            sp = stats.data_ptr()
-        else:
-            stats = np.full((k, 16), np.nan, dtype=np.float32)
-            sp = stats.ctypes.data
-        ptrs = []
-        for name, dst, field in (("momentary", momentary, 6), ("short_term", short_term, 9)):
-            if dst is None:
-                ptrs.append(None)
-                continue
-            torch_like = hasattr(dst, "data_ptr")
-            ok = (dst.is_contiguous() and str(dst.dtype) == "torch.float32") if torch_like else (dst.flags["C_CONTIGUOUS"] and dst.dtype == np.float32)
-            assert ok and len(dst.shape) == 2 and dst.shape[0] >= k, "%s: float32 [>= K, n], contiguous" % name
-            rates = set(ix.rate for _, ix, _ in clips if not ix.replay and ix.one_format and ix.frames)
-            fs = int(sample_rate) or (rates.pop() if len(rates) == 1 else 0)
-            if fs and t:                           # (else the library refuses the call, or writes nothing)
-                try:
-                    n = r128_plan(fs, t)[field]
-                except ValueError:
-                    raise RuntimeError("pdmp3_amd_bulk_decode_clips_r128: bad sample_rate or n_samples")
-                assert dst.shape[1] == n, "%s: float32 [>= K, %d]" % (name, n)
-            ptrs.append(dst.data_ptr() if torch_like else dst.ctypes.data)
+        stats = _stats_like(out, (k, 16))
+        ptrs = [None if dst is None else _aux_destination(name, dst, k, lambda: _plan_field("r128", r128_plan, field, clips, sample_rate, t))
+                for name, dst, field in (("momentary", momentary, 6), ("short_term", short_term, 9))]
         spec = lambda: (_r128_spec(t, sample_rate, channels, target, peak_limit, limit_true_peak, dual_mono, width, rolloff), None)
         try:
-            audio, valid = self._clips_call("r128", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError), extra=(sp, ptrs[0], ptrs[1]))
+            audio, valid = self._clips_call("r128", clips, (t,), spec, channels, out, refused=(ValueError, OverflowError, TypeError),
+                                            extra=(_address(stats), ptrs[0], ptrs[1]))
         except (RingReplay, MixedFormat) as e:
             e.stats = stats
             raise
@@ -1965,7 +1846,7 @@ class BulkDecoder:
         the spec's making refuses is a RuntimeError like the library's own refusals"""
         f = int(n_frames)
         nb = int(n_fft) // 2 + 1 if nb is None else nb
-        m = STFT_MODES[mode] if isinstance(mode, str) else int(mode)
+        m = _enum(STFT_MODES, mode)
         if spec_of is not None:
             spec = lambda: spec_of(f)
         else:
@@ -2015,17 +1896,11 @@ class BulkDecoder:
             cs = set(ix.channels for _, ix, _ in clips if not ix.replay and ix.one_format)
             c = cs.pop() if len(cs) == 1 else 1
         if stats is None:
-            if out is None or hasattr(out, "data_ptr"):
-                import torch
-                stats = torch.full((k, c, 8), float("nan"), dtype=torch.float32,
-                                   device=torch.device("cuda", torch.cuda.current_device()) if out is None else out.device)
-                torch.cuda.synchronize()
-            else:
-                stats = np.full((k, c, 8), np.nan, dtype=np.float32)
-        torch_like = hasattr(stats, "data_ptr")
-        ok = (stats.is_contiguous() and str(stats.dtype) == "torch.float32") if torch_like else (stats.flags["C_CONTIGUOUS"] and stats.dtype == np.float32)
+            stats = _stats_like(out, (k, c, 8))
+        ok = (stats.is_contiguous() and str(stats.dtype) == "torch.float32") if hasattr(stats, "data_ptr") else \
+            (stats.flags["C_CONTIGUOUS"] and stats.dtype == np.float32)
         assert ok and tuple(stats.shape) == (k, c, 8), "stats: float32 [K, C, 8], contiguous"
-        sp = stats.data_ptr() if torch_like else stats.ctypes.data
+        sp = _address(stats)
         spec = lambda: _beat_spec(f, sample_rate, bpm, tightness, trim, m, n_fft=n_fft, hop=hop, n_mels=n_mels, lag=lag, max_size=max_size,
                                   win_length=win_length, start_bpm=start_bpm, std_bpm=std_bpm, max_tempo=max_tempo, f_min=f_min, f_max=f_max,
                                   scale=scale, norm=norm, floor=floor, fft_win_length=fft_win_length, fft_window=fft_window, channels=channels,

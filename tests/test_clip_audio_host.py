@@ -5,10 +5,7 @@ against the binary64 restatement of tests/clip_audio_ref.py within the error bou
 the product itself chooses (pdmp3_amd_audio_lds_plan: clip_features.c audio_lds, held here to its restatement and to the kernel's
 preconditions), to MPEG rates and to odd ones, one table a launch and two."""
 import ctypes as C
-import functools
-import os
 import random
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -16,9 +13,8 @@ import pytest
 
 import clip_audio_ref as ref
 import clip_streams
+from clip_host import build_emul
 from clip_streams import ISO_LSF
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class AudioDesc(C.Structure):                      # include/pdmp3_hip.h pdmp3_audio_desc
@@ -28,12 +24,8 @@ class AudioDesc(C.Structure):                      # include/pdmp3_hip.h pdmp3_a
                 ("flags", C.c_uint32), ("span_cap", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libresample_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "resample_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("resample")
     lib.emul_clip_audio.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int]
     lib.emul_clip_audio.restype = None
     return lib

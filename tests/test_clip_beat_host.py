@@ -6,16 +6,14 @@ that round h down, exactly and up, 2 P > n, n = 2 and 3, n no multiple of h or o
 check, the plan and the refusals; the sanitizer program."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import scipy.signal
 
 import clip_beat_ref as ref
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PERIODS = (1, 2, 7, 21, 22, 23, 45, 200)
 TIGHTNESS = 100.0
 
@@ -25,12 +23,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libbeat_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "beat_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("beat")
     vp = C.c_void_p
     lib.emul_beat_score.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint, vp, vp]
     lib.emul_beat_dp.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_uint, vp, vp]
@@ -321,12 +315,4 @@ def test_tables_refuse_a_bad_period():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/beat_plan.c: pdmp3_amd/host/clip_beat.c's check, tables and plan over the refusals and the edge cases under
     AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "beat_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "beat_plan.c")] +
-                          [os.path.join(host, c) for c in ("clip_beat.c", "clip_tempogram.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c",
-                                                           "clip_stft.c")] + ["-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"beat_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "beat_plan", ("clip_beat.c", "clip_tempogram.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c", "clip_stft.c"))

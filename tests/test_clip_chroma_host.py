@@ -9,8 +9,6 @@ The LDS of a workgroup, restated from include/pdmp3_bulk.h: the span | the eight
 their last read."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,8 +16,8 @@ import pytest
 import clip_chroma_ref as ref
 import clip_cqt_ref as cref
 import test_clip_cqt_host as tch
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = tch.ROOT
 U = ref.U
 C1, C2, C3 = ref.FMIN_C1, ref.FMIN_C2, ref.FMIN_C3
 NORM_NAMES = {0: None, 1: "l1", 2: "l2", 3: "max"}
@@ -40,12 +38,8 @@ GPU_SPECS = {
 }
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libchroma_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "chroma_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("chroma")
     lib.emul_clip_chroma.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
     assert lib.emul_chroma_desc_bytes() == C.sizeof(tch.MelDesc) and lib.emul_chroma_params_bytes() == C.sizeof(ChromaParams)
     return lib
@@ -363,10 +357,4 @@ def test_a_tone_at_a_bins_frequency_gives_its_class_the_maximum(spec):
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/chroma_plan.c: pdmp3_amd/host/clip_chroma.c's check, map and plan over clip_cqt.c under AddressSanitizer and
     UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "chroma_plan_sanitize")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "chroma_plan.c"),
-                           os.path.join(ROOT, "pdmp3_amd", "host", "clip_chroma.c"), os.path.join(ROOT, "pdmp3_amd", "host", "clip_cqt.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"chroma_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "chroma_plan", ("clip_chroma.c", "clip_cqt.c"))

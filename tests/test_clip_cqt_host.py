@@ -4,23 +4,15 @@ refusal, the plan over all hops, and k_clip_cqt's own indexing and arithmetic (p
 g++ into tests/host_emul/cqt_emul.cpp's loops) on random float32 rows against the definition, within the derived binary32
 bound -- no value left out."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_cqt_ref as ref
+from clip_host import MelDesc, build_emul, run_sanitizer_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = ref.U
 C1 = ref.FMIN_C1
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class CqtParams(C.Structure):                      # include/pdmp3_hip.h pdmp3_cqt_params
@@ -40,12 +32,8 @@ GPU_SPECS = {
 }
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libcqt_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "cqt_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("cqt")
     lib.emul_clip_cqt.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
     assert lib.emul_cqt_desc_bytes() == C.sizeof(MelDesc) and lib.emul_cqt_params_bytes() == C.sizeof(CqtParams)
     return lib
@@ -367,10 +355,4 @@ def test_frames_are_frames_on_the_host(case):
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/cqt_plan.c: pdmp3_amd/host/clip_cqt.c's check, lengths, table, plan and the decoder's cache of tables under
     AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "cqt_plan_sanitize")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "cqt_plan.c"),
-                           os.path.join(ROOT, "pdmp3_amd", "host", "clip_cqt.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"cqt_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "cqt_plan", ("clip_cqt.c",))

@@ -7,24 +7,16 @@ value left out.
 torchaudio is not installed where these tests were written: nothing independent pins the restatement to Kaldi.  The last test
 compares with torchaudio.compliance.kaldi.fbank where it is installed, and skips where it is not."""
 import ctypes as C
-import functools
 import itertools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_fbank_ref as ref
+from clip_host import FbankDesc, build_emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = ref.U
-
-
-class FbankDesc(C.Structure):                      # include/pdmp3_hip.h pdmp3_fbank_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("valid", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class FbankParams(C.Structure):                    # include/pdmp3_hip.h pdmp3_fbank_params
@@ -35,12 +27,8 @@ class FbankParams(C.Structure):                    # include/pdmp3_hip.h pdmp3_f
                 ("energy_log_floor", C.c_float), ("span_floats", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libfbank_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "fbank_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("fbank")
     lib.emul_clip_fbank.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.emul_fbank_desc_bytes() == C.sizeof(FbankDesc) and lib.emul_fbank_params_bytes() == C.sizeof(FbankParams)
     return lib

@@ -6,24 +6,17 @@ the rounding's bound (exactly at power inf), the modes against each other bit fo
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_hpss_ref as href
 import clip_stft_ref as sref
+from clip_host import MelDesc, build_emul, run_sanitizer_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD_VALUE = np.float32(-3e9)
 INF = float("inf")
 SIZES = [(31, 31), (3, 31), (31, 3), (17, 5)]
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class HpssParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_hpss_params
@@ -33,12 +26,8 @@ class HpssParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_h
                 ("pad_", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libhpss_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "hpss_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("hpss")
     lib.emul_clip_hpss.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.emul_hpss_lds_floats.restype = C.c_uint
     lib.emul_hpss_lds_at.restype = C.c_uint
@@ -342,11 +331,4 @@ def test_the_emulator_refuses_parameters_that_are_not_the_plans():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/hpss_plan.c: pdmp3_amd/host/clip_hpss.c's check and plan over the refusals, the windows' ends and every
     pair of kernel sizes under AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "hpss_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "hpss_plan.c")] +
-                          [os.path.join(host, c) for c in ("clip_hpss.c", "clip_stft_long.c")] + ["-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"hpss_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "hpss_plan", ("clip_hpss.c", "clip_stft_long.c"))

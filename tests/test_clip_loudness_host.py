@@ -6,16 +6,14 @@ every momentary value, the audio times g bit for bit."""
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_loudness_ref as ref
 import test_clip_cqt_host as tch
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = tch.ROOT
 RATES = [8000, 22050, 48000]
 MPEG_RATES = [8000, 11025, 12000, 16000, 22050, 24000, 32000, 44100, 48000]
 BS1770_48K = ([1.53512485958697, -2.69169618940638, 1.19839281085285], [1.0, -1.69065929318241, 0.73248077421585],
@@ -32,12 +30,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libloudness_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "loudness_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("loudness")
     lib.emul_clip_loudness.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.emul_loudness_params_bytes() == C.sizeof(LoudParams)
     assert lib.emul_loudness_tables_bytes() == (70 * 16 + 4 * 64) * 8 + (64 * 64 + 64 * 4) * 4
@@ -288,10 +282,4 @@ def test_refusals_of_the_planning_calls():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/loudness_plan.c: pdmp3_amd/host/clip_loudness.c's check, coefficients, tables and plan under AddressSanitizer
     and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "loudness_plan_sanitize")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "loudness_plan.c"),
-                           os.path.join(ROOT, "pdmp3_amd", "host", "clip_loudness.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"loudness_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "loudness_plan", ("clip_loudness.c",))

@@ -3,23 +3,15 @@ pdmp3_amd/host/clip_mel.c against the binary64 restatement tests/clip_mel_ref.py
 arithmetic (pdmp3_amd/csrc/mel_core.h, compiled here with g++ into tests/host_emul/mel_emul.cpp's loops) on random float32
 rows against the definition, within the derived binary32 bound -- no value left out."""
 import ctypes as C
-import functools
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_mel_ref as ref
+from clip_host import MelDesc, build_emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = ref.U
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class MelParams(C.Structure):                      # include/pdmp3_hip.h pdmp3_mel_params
@@ -28,12 +20,8 @@ class MelParams(C.Structure):                      # include/pdmp3_hip.h pdmp3_m
                 ("channels", C.c_int32), ("out_mode", C.c_int32), ("floor", C.c_float), ("span_floats", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libmel_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "mel_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("mel")
     lib.emul_clip_mel.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.emul_mel_desc_bytes() == C.sizeof(MelDesc) and lib.emul_mel_params_bytes() == C.sizeof(MelParams)
     return lib

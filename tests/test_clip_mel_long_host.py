@@ -4,10 +4,7 @@ and order of the bins), their refusals, and k_clip_mel_long's own index maps and
 compiled here with g++ into tests/host_emul/mel_long_emul.cpp's loops) on random float32 rows against the definition in
 binary64, within the derived binary32 bound -- no value left out."""
 import ctypes as C
-import functools
 import itertools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,14 +12,9 @@ import pytest
 import clip_mel_long_ref as mlref
 import clip_mel_ref as mref
 import clip_stft_ref as sref
+from clip_host import MelDesc, build_emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = mref.U
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class MelLongParams(C.Structure):                  # include/pdmp3_hip.h pdmp3_mel_long_params
@@ -31,12 +23,8 @@ class MelLongParams(C.Structure):                  # include/pdmp3_hip.h pdmp3_m
                 ("floor", C.c_float), ("span_floats", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libmel_long_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "mel_long_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("mel_long")
     lib.emul_clip_mel_long.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emul_mel_long_lds_floats.restype = C.c_uint
     assert lib.emul_mel_long_desc_bytes() == C.sizeof(MelDesc) and lib.emul_mel_long_params_bytes() == C.sizeof(MelLongParams)

@@ -6,26 +6,18 @@ value left out.
 
 torchaudio is not installed where these tests were written: nothing independent pins the restatement to Kaldi."""
 import ctypes as C
-import functools
 import itertools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_fbank_ref as fref
 import clip_mfcc_ref as ref
+from clip_host import FbankDesc, build_emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = ref.U
 LN_EPS = math.log(ref.EPS)
-
-
-class FbankDesc(C.Structure):                      # include/pdmp3_hip.h pdmp3_fbank_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("valid", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class FbankParams(C.Structure):                    # include/pdmp3_hip.h pdmp3_fbank_params
@@ -40,12 +32,8 @@ class MfccParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_m
     _fields_ = [("fb", FbankParams), ("n_ceps", C.c_int32), ("ceps16", C.c_int32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libmfcc_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "mfcc_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("mfcc")
     lib.emul_clip_mfcc.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.emul_mfcc_desc_bytes() == C.sizeof(FbankDesc) and lib.emul_mfcc_params_bytes() == C.sizeof(MfccParams)
     return lib

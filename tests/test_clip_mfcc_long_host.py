@@ -4,23 +4,15 @@ own values, LDS planes and stencil (pdmp3_amd/csrc/mfcc_long_core.h, compiled he
 tests/host_emul/mfcc_long_emul.cpp's loops) on random log-mel input: the dB values bit for bit, the cepstra and the deltas within
 the derived bounds of tests/clip_mfcc_long_ref.py."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_mfcc_long_ref as ref
+from clip_host import MelDesc, build_emul, run_sanitizer_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GUARD_VALUE = np.float32(-3e9)
 LDS_MAX = 160 * 1024 - 64              # include/pdmp3_hip.h PDMP3_MEL_LDS_MAX
-
-
-class MelDesc(C.Structure):            # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64), ("lead", C.c_uint32),
-                ("pad_", C.c_uint32)]
 
 
 class MfccLongParams(C.Structure):     # include/pdmp3_hip.h pdmp3_mfcc_long_params
@@ -29,12 +21,8 @@ class MfccLongParams(C.Structure):     # include/pdmp3_hip.h pdmp3_mfcc_long_par
                [("top_db", C.c_float), ("lds_bytes", C.c_uint32), ("taps", (C.c_double * 17) * 2)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libmfcc_long_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "mfcc_long_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("mfcc_long")
     lib.emul_clip_mfcc_long.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     for name in ("lds_floats", "d_at", "c_at", "b_at", "result_at"):
         getattr(lib, "emul_mfcc_long_" + name).restype = C.c_uint
@@ -266,12 +254,4 @@ def test_the_emulator_refuses_what_the_engine_refuses():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/mfcc_long_plan.c: pdmp3_amd/host/clip_mfcc_long.c's check, table, taps and plan over the refusals, buffers that
     are too small and every edge of the shapes under AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "mfcc_long_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "mfcc_long_plan.c")] +
-                          [os.path.join(host, c) for c in ("clip_mfcc_long.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c", "clip_stft.c")] +
-                          ["-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"mfcc_long_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "mfcc_long_plan", ("clip_mfcc_long.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c", "clip_stft.c"))

@@ -4,17 +4,14 @@ compiled here with g++ into tests/host_emul/pitch_emul.cpp and run thread by thr
 against the binary64 definition within the derived bound: impulses at the window's edges and the tiles' edges, noise, a sine
 between two lags, a glide, every geometry of lag tiles and workgroups, silence, and item 7's self-consistency of the two modes."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_pitch_ref as ref
 import test_clip_cqt_host as tch
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = tch.ROOT
 LDS_MAX = 160 * 1024 - 64
 CAP = 0.1                                          # the share of a test's frames that may be undecided
 
@@ -31,12 +28,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libpitch_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "pitch_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("pitch")
     lib.emul_clip_pitch.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.emul_pitch_at.restype = C.c_uint
     assert lib.emul_pitch_params_bytes() == C.sizeof(PitchParams) and lib.emul_pitch_desc_bytes() == C.sizeof(tch.MelDesc)
@@ -322,10 +315,4 @@ def test_silence_is_exactly_0_1_0():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/pitch_plan.c: pdmp3_amd/host/clip_pitch.c's check, lags and plan over the refusals and the edge cases under
     AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "pitch_plan_sanitize")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "pitch_plan.c"),
-                           os.path.join(ROOT, "pdmp3_amd", "host", "clip_pitch.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"pitch_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "pitch_plan", ("clip_pitch.c",))

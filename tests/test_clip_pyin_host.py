@@ -7,16 +7,13 @@ a switch of voicing; a glide, then noise, then silence through the emulated k_cl
 import ctypes as C
 import functools
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_pyin_ref as ref
 import test_clip_pitch_host as tph
-
-ROOT = tph.ROOT
+from clip_host import build_emul, run_sanitizer_program
 
 
 class PyinParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_pyin_params
@@ -32,12 +29,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libpyin_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "pyin_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("pyin")
     lib.emul_pyin_obs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emul_pyin_path.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emul_pyin_table_bytes.argtypes = [C.c_void_p]
@@ -399,11 +392,4 @@ def test_a_glide_then_noise_then_silence():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/pyin_plan.c: pdmp3_amd/host/clip_pyin.c's check, tables and plan over the refusals and the edge cases under
     AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "pyin_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "pyin_plan.c"),
-                           os.path.join(host, "clip_pyin.c"), os.path.join(host, "clip_pitch.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"pyin_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "pyin_plan", ("clip_pyin.c", "clip_pitch.c"))

@@ -6,8 +6,6 @@ tests/host_emul/r128_emul.cpp's loops) against the binary64 definition within th
 for bit what the loudness call's emulation gives."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +14,8 @@ import clip_loudness_ref as lref
 import clip_r128_ref as ref
 import test_clip_cqt_host as tch
 import test_clip_loudness_host as tlh
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = tch.ROOT
 RATES = [8000, 22050, 48000]
 
 
@@ -30,12 +28,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libr128_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "r128_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("r128")
     lib.emul_clip_r128.argtypes = [C.c_void_p] + [C.c_int] + [C.c_void_p] * 6
     lib.emul_clip_loudness.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.emul_r128_indices.argtypes = [C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -404,10 +398,4 @@ def test_refusals_of_the_planning_calls():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/r128_plan.c: pdmp3_amd/host/clip_r128.c's check, taps and plan over the edge lengths under AddressSanitizer
     and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "r128_plan_sanitize")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "r128_plan.c"),
-                           os.path.join(ROOT, "pdmp3_amd", "host", "clip_r128.c"), os.path.join(ROOT, "pdmp3_amd", "host", "clip_loudness.c"), "-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"r128_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "r128_plan", ("clip_r128.c", "clip_loudness.c"))

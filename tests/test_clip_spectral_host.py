@@ -5,23 +5,16 @@ tests/host_emul/spectral_emul.cpp's loops) on random float32 rows against the de
 -- no value left out; the roll-off by the undecided rule, its share printed and held to the cap."""
 import ctypes as C
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_spectral_ref as spref
 import clip_stft_ref as sref
+from clip_host import MelDesc, build_emul, run_sanitizer_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = spref.U
 GUARD_VALUE = np.float32(-3e9)
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class SpectralParams(C.Structure):                 # include/pdmp3_hip.h pdmp3_spectral_params
@@ -30,12 +23,8 @@ class SpectralParams(C.Structure):                 # include/pdmp3_hip.h pdmp3_s
                 ("zcr_threshold", C.c_float), ("span_floats", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libspectral_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "spectral_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("spectral")
     lib.emul_clip_spectral.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.emul_spectral_lds_floats.restype = C.c_uint
     lib.emul_spectral_col.restype = C.c_uint
@@ -343,11 +332,4 @@ def test_the_emulator_refuses_parameters_that_leave_the_lds():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/spectral_plan.c: pdmp3_amd/host/clip_spectral.c's check and plan over the refusals, the windows' ends and
     every hop under AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "spectral_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "spectral_plan.c")] +
-                          [os.path.join(host, c) for c in ("clip_spectral.c", "clip_stft_long.c")] + ["-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"spectral_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "spectral_plan", ("clip_spectral.c", "clip_stft_long.c"))

@@ -4,24 +4,16 @@ float64 (an implementation from outside), and k_clip_stft's own indexing, pointw
 (pdmp3_amd/csrc/stft_core.h, compiled here with g++ into tests/host_emul/stft_emul.cpp's loops) on random float32 rows against
 the definition, within the derived binary32 bound -- no value left out."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_stft_ref as ref
+from clip_host import MelDesc, build_emul
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = ref.U
 
 SHAPES = [(16, 16), (400, 400), (400, 301), (512, 1), (1024, 1024)]          # (N, Nw)
-
-
-class MelDesc(C.Structure):                        # include/pdmp3_hip.h pdmp3_mel_desc
-    _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("src_chan_stride", C.c_uint64), ("dst_chan_stride", C.c_uint64),
-                ("lead", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class StftParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_stft_params
@@ -30,12 +22,8 @@ class StftParams(C.Structure):                     # include/pdmp3_hip.h pdmp3_s
                 ("out_mode", C.c_int32), ("floor", C.c_float), ("span_floats", C.c_uint32), ("lds_bytes", C.c_uint32)]
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libstft_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "stft_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("stft")
     lib.emul_clip_stft.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     assert lib.emul_stft_desc_bytes() == C.sizeof(MelDesc) and lib.emul_stft_params_bytes() == C.sizeof(StftParams)
     return lib

@@ -5,17 +5,13 @@ thread on wave_emul.h's fibers over a poisoned LDS) against the binary64 definit
 log-mel arrays: every band count, neighbourhood and lag of the flux, every geometry of lag tiles and workgroups, silence, a click
 train, and item 7's consistency of the three modes."""
 import ctypes as C
-import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clip_tempogram_ref as ref
-import test_clip_cqt_host as tch
+from clip_host import build_emul, run_sanitizer_program
 
-ROOT = tch.ROOT
 LDS_MAX = ref.LDS_MAX
 
 
@@ -35,12 +31,8 @@ def _api():
     return api
 
 
-@functools.lru_cache(maxsize=None)
 def _emul():
-    d = os.path.join(ROOT, "tests", "host_emul")
-    so = os.path.join(d, "libtempogram_emul.so")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-o", so, os.path.join(d, "tempogram_emul.cpp")])
-    lib = C.CDLL(so)
+    lib = build_emul("tempogram")
     lib.emul_clip_tempogram.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.emul_tempogram_params_bytes() == C.sizeof(TgParams) and lib.emul_tempogram_desc_bytes() == C.sizeof(TgDesc)
     return lib
@@ -247,12 +239,4 @@ def test_a_click_train_of_period_45_frames():
 def test_the_sanitizer_program_of_the_planning_calls(tmp_path):
     """tools/sanitize/tempogram_plan.c: pdmp3_amd/host/clip_tempogram.c's check, window, prior and plan over the refusals and the
     edge values under AddressSanitizer and UBSan, a stand-alone program on the CPU"""
-    exe = str(tmp_path / "tempogram_plan_sanitize")
-    host = os.path.join(ROOT, "pdmp3_amd", "host")
-    subprocess.check_call(["gcc", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "pdmp3_amd", "csrc"), "-o", exe, os.path.join(ROOT, "tools", "sanitize", "tempogram_plan.c")] +
-                          [os.path.join(host, c) for c in ("clip_tempogram.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c", "clip_stft.c")] +
-                          ["-lm", "-w"])
-    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
-    assert r.returncode == 0, r.stdout.decode()
-    assert b"tempogram_plan: ok" in r.stdout
+    run_sanitizer_program(tmp_path, "tempogram_plan", ("clip_tempogram.c", "clip_mel_long.c", "clip_mel.c", "clip_stft_long.c", "clip_stft.c"))

@@ -25,14 +25,77 @@ into device memory with pdmp3_amd_bulk_decode_clips, against decoding the files 
 import argparse
 import json
 import os
+import random
+import statistics
 import sys
 import time
+from math import gcd
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 
 
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")     # before HIP starts (torch brings it up): see host/stream_api.c shared_ctx_on
+
+
+def clip_corpus(args, api):
+    """what the clip modes cut their clips from: the C3 file (python -m pdmp3_amd.packer c3) with --c3, else the C4 corpus
+    (python -m pdmp3_amd.packer c4) -> (files, a StreamIndex of each, close() for the indices)"""
+    from pdmp3_amd.packer import packer
+    from pdmp3_amd.packer.__main__ import c4_specs
+    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
+    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
+    ixs = [api.StreamIndex(f) for f in files]
+
+    def close():
+        for ix in ixs:
+            ix.close()
+    return files, ixs, close
+
+
+def corpus_name(args, files):
+    return "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)
+
+
+def clip_selection(args, ixs, first=0, margin=0):
+    """--clips picks of (file, frame) from --seed: the file, then a frame from `first` on that leaves --clip-frames + margin
+    frames behind it where the file has them"""
+    rng = random.Random(args.seed)
+    sel = []
+    for _ in range(args.clips):
+        i = rng.randrange(len(ixs))
+        sel.append((i, rng.randrange(first, max(first + 1, ixs[i].frames - args.clip_frames - margin))))
+    return sel
+
+
+def clip_start(ix, frame, rate, floor_at=0):
+    """the first sample at `rate` at or behind the first sample of frame `frame` of the stream, floor_at at the least"""
+    g = gcd(ix.rate, rate) if ix.rate else 1
+    m, l = (ix.rate // g, rate // g) if ix.rate else (1, 1)
+    return max(-((-frame * ix.frame_samples * l) // m), floor_at)
+
+
+def time_routes(routes, warmup_runs, runs, after_first=None):
+    """routes [(name, callable)] run in turn warmup_runs + runs times, every round starting one route later
+    -> {name: [seconds of each round behind the warm-up]}; after_first() once, behind the first round"""
+    n = len(routes)
+    times = {name: [] for name, _ in routes}
+    for r in range(warmup_runs + runs):
+        for name, fn in routes[r % n:] + routes[:r % n]:
+            t0 = time.perf_counter()
+            fn()
+            dt = time.perf_counter() - t0
+            if r >= warmup_runs:
+                times[name].append(dt)
+        if r == 0 and after_first is not None:
+            after_first()
+    return times
+
+
+def route_stats(times, K):
+    """time_routes's result -> the result line's entry of every route"""
+    return {name: {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
+                   "clips_per_s": {"median": round(K / statistics.median(ts), 1)}} for name, ts in times.items()}
 
 
 def c4(args, api):
@@ -196,21 +259,10 @@ def clips_audio(args, api):
     mean, one strided conv1d per source rate with the same filter table, pad).  The chain starts every clip at its frame's first
     sample, the audio call at the first output sample at or behind it: the two are not compared value by value (the tests
     check the audio call against the definition).  Medians of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, C = args.clips, args.clip_frames, args.audio, 1 if args.mono else 2
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    sel = clip_selection(args, ixs)
     T = F * 1152 * rate // 44100
     spans = [(int(ixs[i].pcm_offsets[a]) // 2, int(ixs[i].pcm_offsets[min(a + F, ixs[i].frames)]) // 2) for i, a in sel]
     stride = max(hi - lo for lo, hi in spans)
@@ -220,11 +272,7 @@ def clips_audio(args, api):
     out_t = torch.zeros((K, C, T), dtype=torch.float32, device=dev)
     dec = api.BulkDecoder(threads=args.clip_threads)
     plain = [(files[i], ixs[i], a, F) for i, a in sel]
-    audio = []
-    for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        audio.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    audio = [(files[i], ixs[i], clip_start(ixs[i], a, rate)) for i, a in sel]
     kern = {}
     for r in sorted(set(ixs[i].rate for i, _ in sel)):
         if r and r != rate:
@@ -280,13 +328,11 @@ def clips_audio(args, api):
                 times[name].append(dt)
     dec.close()
     res = {"workload": "%d clips of %d frames' length (%d samples at %d Hz, %d channel(s)): %s" % (
-               K, F, T, rate, C, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, T, rate, C, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}, "frames_decoded": frames[name]}
-    for ix in ixs:
-        ix.close()
+    for name, entry in route_stats(times, K).items():
+        res[name] = dict(entry, frames_decoded=frames[name])
+    close()
     print(json.dumps(res))
 
 
@@ -298,29 +344,16 @@ def clips_mel(args, api):
     window, abs() ** 2, a matmul with the same filterbank, log10; a dense matmul against the same DFT table where torch.stft
     cannot run --; (c) pdmp3_amd_bulk_decode_clips_mel.  (b) and (c) are compared once (largest difference of the log10 values,
     printed, not asserted: the tests check (c) against the definition).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop, n_mels, floor = args.clips, args.clip_frames, 16000, 400, 160, 80, 1e-10
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    sel = clip_selection(args, ixs)
     Fm = (F * 1152 * rate // 44100) // hop
     T = (Fm - 1) * hop + n_fft
     dev = "cuda:0"
     mel, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        start = clip_start(ixs[i], a, rate, n_fft // 2)                        # (no leading zeros: (a)'s rows start at start - n_fft / 2)
         mel.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - n_fft // 2))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -355,30 +388,18 @@ def clips_mel(args, api):
         dec.decode_clips_mel(mel, Fm, rate, n_fft, hop, n_mels, floor=floor, out=out_m)
 
     routes = [("audio clips", audio_route), ("audio clips + torch chain", torch_route), ("mel clips", mel_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = float((out_t - out_m).abs().max())
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(diff=float((out_t - out_m).abs().max())))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as %d frames x %d bands at %d Hz mono (n_fft %d, hop %d, log10): %s" % (
-               K, F, Fm, n_mels, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, Fm, n_mels, rate, n_fft, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_chain": how["stft"],
-           "largest_difference_of_the_two_log10_results": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+           "largest_difference_of_the_two_log10_results": seen["diff"], "host_cpus": os.cpu_count()}
+    res.update(route_stats(times, K))
     b = times["audio clips + torch chain"]
     res["mel_minus_audio_ms"] = round((statistics.median(times["mel clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
     res["mel_not_above_torch_chain_by_more_than_its_spread"] = bool(statistics.median(times["mel clips"]) - statistics.median(b) <= max(b) - min(b))
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -392,32 +413,19 @@ def clips_stft(args, api, long=False):
     span): what a loader does today; a dense matmul against the same table where torch.stft cannot run; (c)
     pdmp3_amd_bulk_decode_clips_stft.  (b) and (c) are compared once (largest difference, printed, not asserted: the tests
     check (c) against the definition).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop = args.clips, args.clip_frames, 16000, 400, 160
     if long:
         rate, n_fft, hop = 44100, 2048, 512
     bins = n_fft // 2 + 1
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    sel = clip_selection(args, ixs)
     Fm = (F * 1152 * rate // 44100) // hop
     T = (Fm - 1) * hop + n_fft
     dev = "cuda:0"
     stft, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        start = clip_start(ixs[i], a, rate, n_fft // 2)                        # (no leading zeros: (a)'s rows start at start - n_fft / 2)
         stft.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - n_fft // 2))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -455,33 +463,21 @@ def clips_stft(args, api, long=False):
         (dec.decode_clips_stft_long if long else dec.decode_clips_stft)(stft, Fm, rate, n_fft, hop, out=out_s)
 
     routes = [("audio clips", audio_route), ("audio clips + torch.stft", torch_route), ("stft clips", stft_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = float((out_t - out_s).abs().max())
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(diff=float((out_t - out_s).abs().max())))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as %d frames x %d bins complex64 at %d Hz mono (n_fft %d, hop %d): %s" % (
-               K, F, Fm, bins, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, Fm, bins, rate, n_fft, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
-           "largest_difference_of_the_two_results": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+           "largest_difference_of_the_two_results": seen["diff"], "host_cpus": os.cpu_count()}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     spread = max(max(ts) - min(ts) for ts in times.values())
     res["stft_minus_audio_ms"] = round((med["stft clips"] - med["audio clips"]) * 1e3, 3)
     res["torch_minus_audio_ms"] = round((med["audio clips + torch.stft"] - med["audio clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(spread * 1e3, 3)
     res["stft_cheaper_than_torch_stft_by_more_than_the_spread"] = bool(med["audio clips + torch.stft"] - med["stft clips"] > spread)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -494,30 +490,17 @@ def clips_mel_long(args, api):
     log10 -- the route that writes the power batch to memory and reads it back.  (c) is compared once with (b) and (d)
     (largest difference, printed, not asserted: the tests check (c) against the definition).  Medians and min..max of --runs
     runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop, n_mels, floor = args.clips, args.clip_frames, 44100, 2048, 512, 128, 1e-10
     bins = n_fft // 2 + 1
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
     T = (Fm - 1) * hop + n_fft
     dev = "cuda:0"
     mel, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        start = clip_start(ixs[i], a, rate, n_fft // 2)                        # (no leading zeros: (a)'s rows start at start - n_fft / 2)
         mel.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - n_fft // 2))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -563,26 +546,16 @@ def clips_mel_long(args, api):
 
     routes = [("audio clips", audio_route), ("audio clips + torch.stft + matmul + log10", torch_route), ("mel_long clips", mel_route),
               ("stft_long power clips + matmul + log10", power_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 4:] + routes[:r % 4]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = {"torch_route": float((out_b - out_c).abs().max()), "power_route": float((out_d - out_c).abs().max())}
+    diff = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: diff.update(
+        {"torch_route": float((out_b - out_c).abs().max()), "power_route": float((out_d - out_c).abs().max())}))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as %d log10-mel bands x %d frames at %d Hz mono (n_fft %d, hop %d): %s" % (
-               K, F, n_mels, Fm, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, n_mels, Fm, rate, n_fft, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
            "power_batch_bytes": K * bins * Fm * 4, "result_bytes": K * n_mels * Fm * 4,
            "largest_difference_from_mel_long": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     spread = max(max(ts) - min(ts) for ts in times.values())
     res["mel_long_minus_audio_ms"] = round((med["mel_long clips"] - med["audio clips"]) * 1e3, 3)
@@ -591,8 +564,7 @@ def clips_mel_long(args, api):
     res["largest_spread_ms"] = round(spread * 1e3, 3)
     res["mel_long_cheaper_than_the_power_route_by_more_than_the_spread"] = bool(
         med["stft_long power clips + matmul + log10"] - med["mel_long clips"] > spread)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -606,30 +578,17 @@ def clips_spectral(args, api):
     which (d) does not have: it computes four rows, and is the cheaper for it).  (c) is compared once with (b) and (d) (largest
     relative difference per row, printed, not asserted: the tests check (c) against the definition).  Medians and min..max of
     --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop, roll, amin, zt = args.clips, args.clip_frames, 44100, 2048, 512, 0.85, 1e-10, 1e-10
     bins = n_fft // 2 + 1
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
     T = (Fm - 1) * hop + n_fft
     dev = "cuda:0"
     clips, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2)       # (no leading zeros: (a)'s rows start at start - n_fft / 2)
+        start = clip_start(ixs[i], a, rate, n_fft // 2)                        # (no leading zeros: (a)'s rows start at start - n_fft / 2)
         clips.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - n_fft // 2))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -690,27 +649,17 @@ def clips_spectral(args, api):
 
     routes = [("audio clips", audio_route), ("audio clips + torch.stft + reductions", torch_route), ("spectral clips", spectral_route),
               ("stft_long magnitude clips + reductions", magnitude_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 4:] + routes[:r % 4]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            rel = lambda o, rows: [float(((o[:, 0, i] - out_c[:, 0, i]).abs() / torch.clamp(out_c[:, 0, i].abs(), min=1e-3)).max()) for i in rows]
-            diff = {"torch_route_rows_0_to_5": rel(out_b, range(6)), "magnitude_route_rows_2_to_5": rel(out_d, range(2, 6))}
+    rel = lambda o, rows: [float(((o[:, 0, i] - out_c[:, 0, i]).abs() / torch.clamp(out_c[:, 0, i].abs(), min=1e-3)).max()) for i in rows]
+    diff = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: diff.update(
+        {"torch_route_rows_0_to_5": rel(out_b, range(6)), "magnitude_route_rows_2_to_5": rel(out_d, range(2, 6))}))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as 6 spectral descriptors x %d frames at %d Hz mono (n_fft %d, hop %d): %s" % (
-               K, F, Fm, rate, n_fft, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, Fm, rate, n_fft, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_route": how["stft"],
            "magnitude_batch_bytes": K * bins * Fm * 4, "result_bytes": K * 6 * Fm * 4,
            "largest_relative_difference_from_spectral": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     spread = max(max(ts) - min(ts) for ts in times.values())
     res["spectral_minus_audio_ms"] = round((med["spectral clips"] - med["audio clips"]) * 1e3, 3)
@@ -721,8 +670,7 @@ def clips_spectral(args, api):
         med["stft_long magnitude clips + reductions"] - med["spectral clips"] > spread)
     res["spectral_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(
         med["audio clips + torch.stft + reductions"] - med["spectral clips"] > spread)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -734,31 +682,18 @@ def clips_hpss(args, api):
     followed by the same algorithm in torch -- unfold + median along both axes, then the mask.  (c) is compared once with (d)
     (largest difference, printed, not asserted: the tests check (c) against the definition).  Also timed with device events: a
     plain copy of two planes, the bytes k_clip_hpss writes.  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop, lh, lp = args.clips, args.clip_frames, 22050, 2048, 512, 31, 31
     bins, rh, rp = n_fft // 2 + 1, lh // 2, lp // 2
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
     Fw = Fm + 2 * rh
     T = (Fw - 1) * hop + n_fft
     dev = "cuda:0"
     clips, wide, audio = [], [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2 + rh * hop)      # (no leading zeros in the widened clip)
+        start = clip_start(ixs[i], a, rate, n_fft // 2 + rh * hop)                       # (no leading zeros in the widened clip)
         clips.append((files[i], ixs[i], start))
         wide.append((files[i], ixs[i], start - rh * hop))
         audio.append((files[i], ixs[i], start - rh * hop - n_fft // 2))
@@ -796,17 +731,8 @@ def clips_hpss(args, api):
 
     routes = [("audio clips", audio_route), ("stft_long magnitude clips", magnitude_route), ("hpss clips", hpss_route),
               ("stft_long magnitude clips + torch medians and masks", torch_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 4:] + routes[:r % 4]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = float((out_d - out_c).abs().max())
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(diff=float((out_d - out_c).abs().max())))
     copies = []
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for r in range(args.warmup_runs + args.runs):
@@ -819,14 +745,12 @@ def clips_hpss(args, api):
     dec.close()
     res = {"workload": "%d clips of %d frames' length as harmonic and percussive masks [2, %d, %d] at %d Hz mono (n_fft %d, hop %d, kernels %d / %d, "
                        "power 2): %s" % (K, F, bins, Fm, rate, n_fft, hop, lh, lp,
-                                         "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+                                         corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
-           "stage_bytes": K * bins * Fw * 4, "result_bytes": K * 2 * bins * Fm * 4, "largest_difference_of_the_torch_route_from_hpss": diff,
+           "stage_bytes": K * bins * Fw * 4, "result_bytes": K * 2 * bins * Fm * 4, "largest_difference_of_the_torch_route_from_hpss": seen["diff"],
            "plain_copy_of_the_result_ms": {"median": round(statistics.median(copies), 4), "min": round(min(copies), 4), "max": round(max(copies), 4)},
            "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     spread = max(max(ts) - min(ts) for ts in times.values())
     res["hpss_minus_magnitude_ms"] = round((med["hpss clips"] - med["stft_long magnitude clips"]) * 1e3, 3)
@@ -834,8 +758,7 @@ def clips_hpss(args, api):
     res["largest_spread_ms"] = round(spread * 1e3, 3)
     res["hpss_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(
         med["stft_long magnitude clips + torch medians and masks"] - med["hpss clips"] > spread)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -845,30 +768,17 @@ def clips_mfcc_long(args, api):
     in turn: (a) pdmp3_amd_bulk_decode_clips_mel_long (log10) of the widened clips alone; (b) pdmp3_amd_bulk_decode_clips_mfcc_long;
     (c) (a) followed by the same chain in torch -- amax, clamp, matmul, conv1d.  (b) is compared once with (c) (largest
     difference, printed, not asserted: the tests check (b) against the definition).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, n_fft, hop, nm, nc, w, top = args.clips, args.clip_frames, 22050, 2048, 512, 128, 20, 9, 80.0
     h = (w - 1) // 2
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = (30 * rate) // hop if F == 1149 else (F * 1152 * rate // 44100) // hop
     Fw = Fm + 2 * h
     dev = "cuda:0"
     clips, wide = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), n_fft // 2 + h * hop)
+        start = clip_start(ixs[i], a, rate, n_fft // 2 + h * hop)
         clips.append((files[i], ixs[i], start))
         wide.append((files[i], ixs[i], start - h * hop))
     out_l = torch.zeros((K, 1, nm, Fw), dtype=torch.float32, device=dev)
@@ -897,27 +807,16 @@ def clips_mfcc_long(args, api):
         torch.cuda.synchronize()
 
     routes = [("mel_long log10 clips", mel_route), ("mfcc_long clips", mfcc_route), ("mel_long log10 clips + torch amax, clamp, matmul, conv1d", torch_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = float((out_c - out_b).abs().max())
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(diff=float((out_c - out_b).abs().max())))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as MFCC, delta and delta-delta [%d, %d] at %d Hz mono (n_fft %d, hop %d, %d bands, %d cepstra, "
                        "top_db %g, width %d): %s" % (K, F, 3 * nc, Fm, rate, n_fft, hop, nm, nc, top, w,
-                                                     "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+                                                     corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
-           "stage_bytes": K * nm * Fw * 4, "result_bytes": K * 3 * nc * Fm * 4, "largest_difference_of_the_torch_route_from_mfcc_long": diff,
+           "stage_bytes": K * nm * Fw * 4, "result_bytes": K * 3 * nc * Fm * 4, "largest_difference_of_the_torch_route_from_mfcc_long": seen["diff"],
            "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     spread = max(max(ts) - min(ts) for ts in times.values())
     res["mfcc_long_minus_mel_long_ms"] = round((med["mfcc_long clips"] - med["mel_long log10 clips"]) * 1e3, 3)
@@ -925,8 +824,7 @@ def clips_mfcc_long(args, api):
     res["mfcc_long_over_mel_long"] = round(med["mfcc_long clips"] / med["mel_long log10 clips"], 4)
     res["largest_spread_ms"] = round(spread * 1e3, 3)
     res["mfcc_long_cheaper_than_the_torch_route_by_more_than_the_spread"] = bool(med[routes[2][0]] - med["mfcc_long clips"] > spread)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -937,32 +835,19 @@ def clips_cqt(args, api):
     the table as a dense [N_0, 2 x 84] matrix (every bin at the longest filter's length), eight clips at a time, and the
     magnitude; (c) pdmp3_amd_bulk_decode_clips_cqt.  (c) is compared once with (b) (largest difference, printed, not asserted:
     the tests check (c) against the definition).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, hop, n_bins = args.clips, args.clip_frames, 22050, 512, 84
     f_k, half = api.cqt_lengths(rate)
     h0 = int(half[0])
     n0 = 2 * h0 + 1
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = 1292 if F == 1149 else (F * 1152 * rate // 44100) // hop + 1
     T = (Fm - 1) * hop + n0
     dev = "cuda:0"
     cq, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), h0)               # (no leading zeros: (a)'s rows start at start - h_0)
+        start = clip_start(ixs[i], a, rate, h0)                                # (no leading zeros: (a)'s rows start at start - h_0)
         cq.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - h0))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -993,33 +878,22 @@ def clips_cqt(args, api):
         dec.decode_clips_cqt(cq, Fm, rate, hop, out=out_c)
 
     routes = [("audio clips", audio_route), ("audio clips + dense torch matmul + magnitude", torch_route), ("cqt clips", cqt_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = {"torch_route": float((out_b - out_c).abs().max()), "largest_magnitude": float(out_c.abs().max())}
+    diff = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: diff.update(
+        {"torch_route": float((out_b - out_c).abs().max()), "largest_magnitude": float(out_c.abs().max())}))
     dec.close()
     plan = api.cqt_plan(rate, hop=hop)
     res = {"workload": "%d clips of %d frames' length as %d constant-Q bins x %d frames at %d Hz mono (C1, 12 an octave, hop %d): %s" % (
-               K, F, n_bins, Fm, rate, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, n_bins, Fm, rate, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
            "plan": {"tile": plan[0], "lds_bytes": plan[2], "split_tiles": plan[5], "table_rows": int(rows.sum()), "dense_rows": 6 * int(rows[0])},
            "result_bytes": K * n_bins * Fm * 4, "largest_difference_from_cqt": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["cqt_minus_audio_ms"] = round((med["cqt clips"] - med["audio clips"]) * 1e3, 3)
     res["torch_route_minus_audio_ms"] = round((med["audio clips + dense torch matmul + magnitude"] - med["audio clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1030,31 +904,18 @@ def clips_chroma(args, api):
     folded over the seven octaves and divided by the frame's maximum in torch; (c) pdmp3_amd_bulk_decode_clips_chroma.  (c) is
     compared once with (b) (largest difference, printed, not asserted: torch adds the octaves in its own order, and the tests
     check (c) against the definition and against the sequential fold).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, hop, n_bins, n_chroma, floor = args.clips, args.clip_frames, 22050, 512, 84, 12, 1e-10
     h0 = int(api.cqt_lengths(rate)[1][0])
     n0 = 2 * h0 + 1
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
+    sel = clip_selection(args, ixs, margin=2)
     Fm = 1292 if F == 1149 else (F * 1152 * rate // 44100) // hop + 1
     T = (Fm - 1) * hop + n0
     dev = "cuda:0"
     cq, audio = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = max(-((-a * ixs[i].frame_samples * l) // m), h0)               # (no leading zeros: (a)'s rows start at start - h_0)
+        start = clip_start(ixs[i], a, rate, h0)                                # (no leading zeros: (a)'s rows start at start - h_0)
         cq.append((files[i], ixs[i], start))
         audio.append((files[i], ixs[i], start - h0))
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
@@ -1077,35 +938,24 @@ def clips_chroma(args, api):
         dec.decode_clips_chroma(cq, Fm, rate, hop, channels=1, norm_floor=floor, out=out_c)
 
     routes = [("audio clips", audio_route), ("cqt clips + fold + max norm in torch", cqt_route), ("chroma clips", chroma_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = {"torch_route": float((out_b - out_c).abs().max()), "largest_value": float(out_c.abs().max()),
-                    "frames_at_one": int((out_c.amax(dim=2) == 1.0).sum()), "frames": K * Fm}
+    diff = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: diff.update(
+        {"torch_route": float((out_b - out_c).abs().max()), "largest_value": float(out_c.abs().max()),
+         "frames_at_one": int((out_c.amax(dim=2) == 1.0).sum()), "frames": K * Fm}))
     dec.close()
     plan = api.chroma_plan(rate, hop=hop)
     res = {"workload": "%d clips of %d frames' length as %d pitch classes x %d frames at %d Hz mono (C1, %d bins, 12 an octave, hop %d): %s" % (
-               K, F, n_chroma, Fm, rate, n_bins, hop, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, n_chroma, Fm, rate, n_bins, hop, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
            "plan": {"tile": plan[0], "lds_bytes": plan[2], "split_tiles": plan[5]},
            "result_bytes": K * n_chroma * Fm * 4, "cqt_bytes": K * n_bins * Fm * 4, "largest_difference_from_chroma": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["chroma_minus_audio_ms"] = round((med["chroma clips"] - med["audio clips"]) * 1e3, 3)
     res["cqt_route_minus_audio_ms"] = round((med["cqt clips + fold + max norm in torch"] - med["audio clips"]) * 1e3, 3)
     res["chroma_minus_cqt_route_ms"] = round((med["chroma clips"] - med["cqt clips + fold + max norm in torch"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1118,27 +968,12 @@ def clips_loudness(args, api, r128=False):
     -14 LUFS (audio times the gain, stats, no momentary curve).  There is no torch route to hold against: torch without
     torchaudio has no recursive filter.  (b) minus (a) is reported, not capped.  The kernels' own times come from a
     kernel-trace run of this mode (profiles/clip_loudness.txt).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, target = args.clips, args.clip_frames, 32000, -14.0
     T = 30 * rate if F == 1149 else F * 1152 * rate // 44100
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F - 2))))
-    clips = []
-    for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    sel = clip_selection(args, ixs, margin=2)
+    clips = [(files[i], ixs[i], clip_start(ixs[i], a, rate)) for i, a in sel]
     dev = "cuda:0"
     out_a = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
     out_b = torch.zeros((K, 2, T), dtype=torch.float32, device=dev)
@@ -1157,45 +992,36 @@ def clips_loudness(args, api, r128=False):
         stats[1] = dec.decode_clips_r128(clips, T, rate, 2, target=target, out=out_c)[1]
 
     routes = [("audio clips", audio_route), ("loudness clips", loudness_route)] + ([("r128 clips", r128_route)] if r128 else [])
-    times = {name: [] for name, _ in routes}
-    seen = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            st = stats[0].cpu().numpy()
-            fin = np.isfinite(st[:, 0])
-            seen = {"audio_is_x_times_g": bool(torch.equal(out_b, out_a * stats[0][:, 3].view(K, 1, 1))), "clips_with_a_loudness": int(fin.sum()),
-                    "L_min": float(st[fin, 0].min()) if fin.any() else None, "L_max": float(st[fin, 0].max()) if fin.any() else None,
-                    "g_min": float(st[:, 3].min()), "g_max": float(st[:, 3].max()), "blocks": int(st[0, 5])}
-            if r128:
-                sr = stats[1].cpu().numpy()
-                seen.update({"r128_audio_is_x_times_g": bool(torch.equal(out_c, out_a * stats[1][:, 3].view(K, 1, 1))),
-                             "r128_first_three_are_the_loudness_calls": bool((sr[:, :3].view(np.uint32) == st[:, :3].view(np.uint32)).all()),
-                             "clips_held_to_the_true_peak": int((sr[:, 3] < st[:, 3]).sum()), "TP_over_P_max": float((sr[:, 8] / np.maximum(sr[:, 2], 1e-30)).max()),
-                             "TP_max": float(sr[:, 8].max()), "LRA_min": float(sr[:, 10].min()), "LRA_max": float(sr[:, 10].max()),
-                             "windows": int(sr[0, 12]), "range_windows": int(sr[0, 13])})
+    seen = {}
+
+    def compare():
+        st = stats[0].cpu().numpy()
+        fin = np.isfinite(st[:, 0])
+        seen.update({"audio_is_x_times_g": bool(torch.equal(out_b, out_a * stats[0][:, 3].view(K, 1, 1))), "clips_with_a_loudness": int(fin.sum()),
+                     "L_min": float(st[fin, 0].min()) if fin.any() else None, "L_max": float(st[fin, 0].max()) if fin.any() else None,
+                     "g_min": float(st[:, 3].min()), "g_max": float(st[:, 3].max()), "blocks": int(st[0, 5])})
+        if r128:
+            sr = stats[1].cpu().numpy()
+            seen.update({"r128_audio_is_x_times_g": bool(torch.equal(out_c, out_a * stats[1][:, 3].view(K, 1, 1))),
+                         "r128_first_three_are_the_loudness_calls": bool((sr[:, :3].view(np.uint32) == st[:, :3].view(np.uint32)).all()),
+                         "clips_held_to_the_true_peak": int((sr[:, 3] < st[:, 3]).sum()), "TP_over_P_max": float((sr[:, 8] / np.maximum(sr[:, 2], 1e-30)).max()),
+                         "TP_max": float(sr[:, 8].max()), "LRA_min": float(sr[:, 10].min()), "LRA_max": float(sr[:, 10].max()),
+                         "windows": int(sr[0, 12]), "range_windows": int(sr[0, 13])})
+    times = time_routes(routes, args.warmup_runs, args.runs, compare)
     dec.close()
     plan = api.loudness_plan(rate, T)
     res = {"workload": "%d clips of %d samples at %d Hz stereo, K-weighted, gated and scaled to %g LUFS: %s" % (
-               K, T, rate, target, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, T, rate, target, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
            "plan": {"block": plan[0], "chunk_blocks": plan[1], "lds_bytes": plan[2], "q": plan[3], "chunks": plan[4], "I": plan[5], "J": plan[6]},
            "batch_bytes": K * 2 * T * 4, "seen": seen, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["loudness_minus_audio_ms"] = round((med["loudness clips"] - med["audio clips"]) * 1e3, 3)
     if r128:
         res["r128_minus_loudness_ms"] = round((med["r128 clips"] - med["loudness clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1241,30 +1067,17 @@ def clips_pitch(args, api):
     (share of frames with the same lag and the largest f0 difference among them, printed, not asserted: the tests check (c)
     against the definition).  k_clip_pitch's own time comes from a kernel-trace run of this mode (profiles/clip_pitch.txt).
     Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, Fm, rate, N, W, H, thr = args.clips, args.clip_frames, 22050, 2048, 1024, 512, 0.1
     span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
     F = span // H + 1
     T = (F - 1) * H + N
     tmin, tmax, tiles = api.pitch_lags(rate)
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(2, max(3, ixs[i].frames - Fm - 4))))
+    sel = clip_selection(args, ixs, first=2, margin=4)
     clips, spans = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = -((-a * ixs[i].frame_samples * l) // m)
+        start = clip_start(ixs[i], a, rate)
         clips.append((files[i], ixs[i], start))
         spans.append((files[i], ixs[i], start - N // 2))
     dev = "cuda:0"
@@ -1286,36 +1099,27 @@ def clips_pitch(args, api):
         dec.decode_clips_pitch(clips, F, rate, N, H, out=out_c)
 
     routes = [("audio clips", audio_route), ("audio clips + torch yin", torch_route), ("pitch clips", pitch_route)]
-    times = {name: [] for name, _ in routes}
-    seen = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            same = out_b[:, 0, 2] == out_c[:, 0, 2]
-            seen = {"frames": int(same.numel()), "frames_with_torchs_lag": int(same.sum()),
-                    "largest_f0_difference_among_them_hz": float((out_b[:, 0, 0] - out_c[:, 0, 0])[same].abs().max()) if bool(same.any()) else None,
-                    "voiced_frames": int((out_c[:, 0, 1] < thr).sum()), "frames_of_zeros": int((out_c[:, 0, 2] == 0).sum())}
+    seen = {}
+
+    def compare():
+        same = out_b[:, 0, 2] == out_c[:, 0, 2]
+        seen.update({"frames": int(same.numel()), "frames_with_torchs_lag": int(same.sum()),
+                     "largest_f0_difference_among_them_hz": float((out_b[:, 0, 0] - out_c[:, 0, 0])[same].abs().max()) if bool(same.any()) else None,
+                     "voiced_frames": int((out_c[:, 0, 1] < thr).sum()), "frames_of_zeros": int((out_c[:, 0, 2] == 0).sum())})
+    times = time_routes(routes, args.warmup_runs, args.runs, compare)
     dec.close()
     plan = api.pitch_plan(rate)
     res = {"workload": "%d clips of %d frames (%d samples) at %d Hz mono, YIN, frame %d window %d hop %d, lags %d .. %d: %s" % (
-               K, F, T, rate, N, W, H, tmin, tmax, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, T, rate, N, W, H, tmin, tmax, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
            "plan": {"frames_a_workgroup": plan[0], "span_floats": plan[1], "lds_bytes": plan[2], "matrix_instructions_a_tile": plan[3], "lag_tiles": tiles},
            "matrix_instructions": K * F * tiles * plan[3], "seen": seen, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["pitch_minus_audio_ms"] = round((med["pitch clips"] - med["audio clips"]) * 1e3, 3)
     res["torch_minus_audio_ms"] = round((med["audio clips + torch yin"] - med["audio clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1326,31 +1130,18 @@ def clips_pyin(args, api):
     [K, 1, 339, F], which a caller without this call takes off the device; (c) pdmp3_amd_bulk_decode_clips_pyin's observation
     [K, 1, 602, F]; (d) its path [K, 1, 4, F].  The kernels' own times come from a kernel-trace run of this mode
     (profiles/clip_pyin.txt).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, Fm, rate, N, H = args.clips, args.clip_frames, 22050, 2048, 512
     span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
     F = span // H + 1
     T = (F - 1) * H + N
     tmin, tmax, _ = api.pitch_lags(rate)
     plan = api.pyin_plan(rate, n_frames=F)
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(2, max(3, ixs[i].frames - Fm - 4))))
+    sel = clip_selection(args, ixs, first=2, margin=4)
     clips, spans = [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = -((-a * ixs[i].frame_samples * l) // m)
+        start = clip_start(ixs[i], a, rate)
         clips.append((files[i], ixs[i], start))
         spans.append((files[i], ixs[i], start - N // 2))
     dev = "cuda:0"
@@ -1364,35 +1155,24 @@ def clips_pyin(args, api):
               ("pitch curve clips", lambda: dec.decode_clips_pitch(clips, F, rate, N, H, out_mode="curve", out=curve)),
               ("pyin observation clips", lambda: dec.decode_clips_pyin(clips, F, rate, 1, out_mode="observation", out=obs)),
               ("pyin path clips", lambda: dec.decode_clips_pyin(clips, F, rate, 1, out=path))]
-    times = {name: [] for name, _ in routes}
-    seen = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            seen = {"frames": K * F, "voiced_frames": int((path[:, 0, 1] == 1).sum()), "mean_voiced_probability": float(path[:, 0, 2].mean()),
-                    "non_zero_observations_a_frame": float((obs[:, 0, :-1] != 0).sum()) / (K * F),
-                    "path_v_is_observation_v": bool(torch.equal(path[:, 0, 2], obs[:, 0, -1]))}
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(
+        {"frames": K * F, "voiced_frames": int((path[:, 0, 1] == 1).sum()), "mean_voiced_probability": float(path[:, 0, 2].mean()),
+         "non_zero_observations_a_frame": float((obs[:, 0, :-1] != 0).sum()) / (K * F),
+         "path_v_is_observation_v": bool(torch.equal(path[:, 0, 2], obs[:, 0, -1]))}))
     dec.close()
     res = {"workload": "%d clips of %d frames (%d samples) at %d Hz mono, pYIN, frame %d hop %d, lags %d .. %d, %d bins, band %d: %s" % (
-               K, F, T, rate, N, H, tmin, tmax, plan["n_bins"], plan["band"], "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, T, rate, N, H, tmin, tmax, plan["n_bins"], plan["band"], corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "plan": plan,
            "curve_batch_bytes": int(curve.numel() * 4), "stage_bytes": K * (plan["curve_bytes"] + plan["obs_bytes"] + plan["bp_bytes"]),
            "seen": seen, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["observation_minus_curve_ms"] = round((med["pyin observation clips"] - med["pitch curve clips"]) * 1e3, 3)
     res["path_minus_curve_ms"] = round((med["pyin path clips"] - med["pitch curve clips"]) * 1e3, 3)
     res["path_minus_audio_ms"] = round((med["pyin path clips"] - med["audio clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1404,29 +1184,15 @@ def clips_beat(args, api):
     numpy restatement of the tracker (tests/clip_beat_ref.py) clip by clip at the period (b) decided -- what a caller without this
     call does.  The kernels' own times come from a kernel-trace run of this mode (profiles/clip_beat.txt).  Medians and min..max
     of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
     import clip_beat_ref as ref
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, Fm, rate, N, H = args.clips, args.clip_frames, 22050, 2048, 512
     span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
     F = span // H + 1
     plan_est, plan_given = api.beat_plan(rate, n_frames=F), api.beat_plan(rate, n_frames=F, bpm=120.0)
-    clips = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        a = rng.randrange(200, max(201, ixs[i].frames - Fm - 200))
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    clips = [(files[i], ixs[i], clip_start(ixs[i], a, rate)) for i, a in clip_selection(args, ixs, first=200, margin=200)]
     dev = "cuda:0"
     onset = torch.zeros((K, 1, F), dtype=torch.float32, device=dev)
     tempo = torch.zeros((K, 1, 4), dtype=torch.float32, device=dev)
@@ -1440,14 +1206,7 @@ def clips_beat(args, api):
               ("tempogram clips, tempo", lambda: dec.decode_clips_tempogram(clips, F, rate, out_mode="tempo", out=tempo)),
               ("beat clips, tempo estimated", lambda: dec.decode_clips_beats(clips, F, rate, out=beats, stats=stats)),
               ("beat clips, bpm 120", lambda: dec.decode_clips_beats(clips, F, rate, bpm=120.0, out=given, stats=stats_g))]
-    times = {name: [] for name, _ in routes}
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
+    times = time_routes(routes, args.warmup_runs, args.runs)
     periods = [int(x) for x in tempo[:, 0, 1].cpu().numpy()]
     tabs = {p: api.beat_tables(p) for p in set(periods)}
     host_times, same = [], True
@@ -1461,22 +1220,19 @@ def clips_beat(args, api):
     dec.close()
     st = stats[:, 0].cpu().numpy()
     res = {"workload": "%d clips of %d frames at %d Hz mono, beat tracking, n_fft %d hop %d, tightness 100, trim: %s" % (
-               K, F, rate, N, H, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, rate, N, H, corpus_name(args, files)),
            "source_rates": sorted(set(ix.rate for _, ix, _ in clips)), "destination": "device memory", "runs": args.runs,
            "plan_estimated": plan_est, "plan_bpm_120": plan_given,
            "seen": {"periods": sorted(set(periods)), "beats_kept_mean": float(st[:, 2].mean()), "beats_before_trim_mean": float(st[:, 3].mean()),
                     "device_is_the_numpy_restatement": same},
            "onset + copy + numpy restatement": {"seconds": {"min": round(min(host_times), 6), "max": round(max(host_times), 6)}},
            "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     res["estimated_minus_tempo_ms"] = round((med["beat clips, tempo estimated"] - med["tempogram clips, tempo"]) * 1e3, 3)
     res["bpm_120_minus_onset_ms"] = round((med["beat clips, bpm 120"] - med["tempogram clips, onset"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1509,31 +1265,18 @@ def clips_tempogram(args, api):
     (d) are compared once (largest differences and the share of clips with the same lag, printed, not asserted: the tests check
     (d) against the definition).  The kernels' own times come from a kernel-trace run of this mode
     (profiles/clip_tempogram.txt).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, Fm, rate, N, H, nm, lag, wt = args.clips, args.clip_frames, 22050, 2048, 512, 128, 1, 384
     span = 30 * rate if Fm == 1149 else Fm * 1152 * rate // 44100
     F = span // H + 1
     front, back, tiles, ksteps, frames_wg, lds = api.tempogram_plan(rate)
     Fw = F + front + back                                                       # frames of the widened clips
     T = (Fw - 1) * H + N
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(400, max(401, ixs[i].frames - Fm - 4))))
+    sel = clip_selection(args, ixs, first=400, margin=4)
     clips, wide, wide0, spans = [], [], [], []
     for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        start = -((-a * ixs[i].frame_samples * l) // m)
+        start = clip_start(ixs[i], a, rate)
         assert start - front * H - N // 2 >= 0
         clips.append((files[i], ixs[i], start))
         wide.append((files[i], ixs[i], start - front * H))
@@ -1574,40 +1317,28 @@ def clips_tempogram(args, api):
     routes = [("audio clips", audio_route), ("mel_long clips", mel_route)]
     for m in shapes:
         routes += [("mel_long clips + torch " + m, torch_route(m)), ("tempogram clips, " + m, product_route(m))]
-    times = {name: [] for name, _ in routes}
-    seen = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % len(routes):] + routes[:r % len(routes)]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            same = out_t["tempo"][:, 1] == out_p["tempo"][:, 0, 1]
-            seen = {"largest_onset_difference": float((out_t["onset"] - out_p["onset"][:, 0]).abs().max()),
-                    "largest_onset": float(out_p["onset"].max()),
-                    "largest_tempogram_difference": float((out_t["tempogram"] - out_p["tempogram"][:, 0]).abs().max()),
-                    "clips": K, "clips_with_torchs_lag": int(same.sum()),
-                    "bpm": sorted(set(round(float(v), 2) for v in out_p["tempo"][:, 0, 0].cpu()))[:8]}
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(
+        {"largest_onset_difference": float((out_t["onset"] - out_p["onset"][:, 0]).abs().max()),
+         "largest_onset": float(out_p["onset"].max()),
+         "largest_tempogram_difference": float((out_t["tempogram"] - out_p["tempogram"][:, 0]).abs().max()),
+         "clips": K, "clips_with_torchs_lag": int((out_t["tempo"][:, 1] == out_p["tempo"][:, 0, 1]).sum()),
+         "bpm": sorted(set(round(float(v), 2) for v in out_p["tempo"][:, 0, 0].cpu()))[:8]}))
     dec.close()
     res = {"workload": "%d clips of %d frames at %d Hz mono, n_fft %d hop %d, %d bands, lag %d, tempogram window %d (%d log-mel frames a clip): %s" % (
-               K, F, rate, N, H, nm, lag, wt, Fw, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, rate, N, H, nm, lag, wt, Fw, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
            "plan": {"frames_in_front": front, "frames_behind": back, "lag_tiles": tiles, "matrix_instructions_a_tile": ksteps,
                     "frames_a_workgroup": frames_wg, "lds_bytes": lds},
            "matrix_instructions": K * F * tiles * ksteps, "stage_bytes": {"log_mel": K * nm * Fw * 4, "envelope": K * (F + wt - 1) * 4, "tempogram": K * wt * F * 4},
            "seen": seen, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+    res.update(route_stats(times, K))
     med = {name: statistics.median(ts) for name, ts in times.items()}
     for m in shapes:
         res[m + "_minus_mel_long_ms"] = round((med["tempogram clips, " + m] - med["mel_long clips"]) * 1e3, 3)
         res[m + "_torch_minus_mel_long_ms"] = round((med["mel_long clips + torch " + m] - med["mel_long clips"]) * 1e3, 3)
     res["largest_spread_ms"] = round(max(max(ts) - min(ts) for ts in times.values()) * 1e3, 3)
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1620,31 +1351,16 @@ def clips_fbank(args, api):
     DFT where torch.fft cannot run --; (c) pdmp3_amd_bulk_decode_clips_fbank.  (b) and (c) are compared once (largest
     difference of the ln values above -10, printed, not asserted: the tests check (c) against the definition).  Medians and
     min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, nw, hop, n_mels, rho = args.clips, args.clip_frames, 16000, 400, 160, 80, 0.97
     n = api.fbank_dft_length(nw)
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    sel = clip_selection(args, ixs)
     seconds = max(F * 1152 // 44100, 1)
     Fm = 1 + (seconds * rate - nw) // hop                                          # (Kaldi's snip_edges count: 2998 for 30 s)
     T = (Fm - 1) * hop + nw
     dev = "cuda:0"
-    clips = []
-    for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    clips = [(files[i], ixs[i], clip_start(ixs[i], a, rate)) for i, a in sel]
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
     out_t = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
     out_f = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
@@ -1682,32 +1398,23 @@ def clips_fbank(args, api):
         dec.decode_clips_fbank(clips, Fm, rate, win_length=nw, hop=hop, num_mel_bins=n_mels, out=out_f)
 
     routes = [("audio clips", audio_route), ("audio clips + torch chain", torch_route), ("fbank clips", fbank_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            big = out_t > -10.0
-            diff = float((out_t - out_f)[big].abs().max()) if bool(big.any()) else 0.0
+    seen = {}
+
+    def compare():
+        big = out_t > -10.0
+        seen["diff"] = float((out_t - out_f)[big].abs().max()) if bool(big.any()) else 0.0
+    times = time_routes(routes, args.warmup_runs, args.runs, compare)
     dec.close()
     res = {"workload": "%d clips of %d frames' length as %d frames x %d bins at %d Hz mono (Nw %d, hop %d, N %d, povey, ln): %s" % (
-               K, F, Fm, n_mels, rate, nw, hop, n, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, Fm, n_mels, rate, nw, hop, n, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs, "torch_chain": how["dft"],
-           "largest_difference_of_the_two_ln_results_above_minus_10": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+           "largest_difference_of_the_two_ln_results_above_minus_10": seen["diff"], "host_cpus": os.cpu_count()}
+    res.update(route_stats(times, K))
     b = times["audio clips + torch chain"]
     res["fbank_minus_audio_ms"] = round((statistics.median(times["fbank clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
     res["torch_chain_minus_audio_ms"] = round((statistics.median(b) - statistics.median(times["audio clips"])) * 1e3, 3)
     res["fbank_faster_than_torch_chain_by_more_than_its_spread"] = bool(statistics.median(b) - statistics.median(times["fbank clips"]) > max(b) - min(b))
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
@@ -1719,30 +1426,15 @@ def clips_mfcc(args, api):
     the loader builds itself (lifter folded in, as pdmp3_amd_mfcc_dct_table gives it) and the copy into the output -- what a
     loader does today; (c) pdmp3_amd_bulk_decode_clips_mfcc.  (b) and (c) are compared once (largest difference, printed, not
     asserted: the tests check (c) against the definition).  Medians and min..max of --runs runs."""
-    import random
-    import statistics
     import torch
-    from math import gcd
-    from pdmp3_amd.packer import packer
-    from pdmp3_amd.packer.__main__ import c4_specs
-    specs = [dict(n_frames=137813, seed=0xC3, sfreq=0, mode=1, mode_ext=2, bitrate_index=14)] if args.c3 else c4_specs(4096)
-    files = [np.frombuffer(packer.generate(**s), dtype=np.uint8) for s in specs]
-    ixs = [api.StreamIndex(f) for f in files]
-    rng = random.Random(args.seed)
+    files, ixs, close = clip_corpus(args, api)
     K, F, rate, nw, hop, n_mels, n_ceps, lift = args.clips, args.clip_frames, 16000, 400, 160, 23, 13, 22.0
-    sel = []
-    for _ in range(K):
-        i = rng.randrange(len(files))
-        sel.append((i, rng.randrange(max(1, ixs[i].frames - F))))
+    sel = clip_selection(args, ixs)
     seconds = max(F * 1152 // 44100, 1)
     Fm = 1 + (seconds * rate - nw) // hop
     T = (Fm - 1) * hop + nw
     dev = "cuda:0"
-    clips = []
-    for i, a in sel:
-        g = gcd(ixs[i].rate, rate) if ixs[i].rate else 1
-        m, l = (ixs[i].rate // g, rate // g) if ixs[i].rate else (1, 1)
-        clips.append((files[i], ixs[i], -((-a * ixs[i].frame_samples * l) // m)))
+    clips = [(files[i], ixs[i], clip_start(ixs[i], a, rate)) for i, a in sel]
     out_a = torch.zeros((K, 1, T), dtype=torch.float32, device=dev)
     out_l = torch.zeros((K, 1, Fm, n_mels), dtype=torch.float32, device=dev)
     out_t = torch.zeros((K, 1, Fm, n_ceps), dtype=torch.float32, device=dev)
@@ -1763,31 +1455,19 @@ def clips_mfcc(args, api):
         dec.decode_clips_mfcc(clips, Fm, rate, n_ceps, lift, n_mels, win_length=nw, hop=hop, out=out_c)
 
     routes = [("audio clips", audio_route), ("fbank clips + torch.matmul", fbank_route), ("mfcc clips", mfcc_route)]
-    times = {name: [] for name, _ in routes}
-    diff = None
-    for r in range(args.warmup_runs + args.runs):
-        for name, fn in routes[r % 3:] + routes[:r % 3]:
-            t0 = time.perf_counter()
-            fn()
-            dt = time.perf_counter() - t0
-            if r >= args.warmup_runs:
-                times[name].append(dt)
-        if r == 0:
-            diff = float((out_t - out_c).abs().max())
+    seen = {}
+    times = time_routes(routes, args.warmup_runs, args.runs, lambda: seen.update(diff=float((out_t - out_c).abs().max())))
     dec.close()
     res = {"workload": "%d clips of %d frames' length as %d frames x %d cepstra of %d bands at %d Hz mono (Nw %d, hop %d, povey, lifter %g): %s" % (
-               K, F, Fm, n_ceps, n_mels, rate, nw, hop, lift, "C3 file" if args.c3 else "C4 corpus (%d files, >= 4096 frames each)" % len(files)),
+               K, F, Fm, n_ceps, n_mels, rate, nw, hop, lift, corpus_name(args, files)),
            "source_rates": sorted(set(ixs[i].rate for i, _ in sel)), "destination": "device memory", "runs": args.runs,
-           "largest_difference_of_the_two_results": diff, "host_cpus": os.cpu_count()}
-    for name, ts in times.items():
-        res[name] = {"seconds": {"median": round(statistics.median(ts), 6), "min": round(min(ts), 6), "max": round(max(ts), 6)},
-                     "clips_per_s": {"median": round(K / statistics.median(ts), 1)}}
+           "largest_difference_of_the_two_results": seen["diff"], "host_cpus": os.cpu_count()}
+    res.update(route_stats(times, K))
     b = times["fbank clips + torch.matmul"]
     res["mfcc_minus_audio_ms"] = round((statistics.median(times["mfcc clips"]) - statistics.median(times["audio clips"])) * 1e3, 3)
     res["fbank_matmul_minus_audio_ms"] = round((statistics.median(b) - statistics.median(times["audio clips"])) * 1e3, 3)
     res["mfcc_faster_than_fbank_matmul_by_more_than_its_spread"] = bool(statistics.median(b) - statistics.median(times["mfcc clips"]) > max(b) - min(b))
-    for ix in ixs:
-        ix.close()
+    close()
     print(json.dumps(res))
 
 
