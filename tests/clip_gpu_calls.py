@@ -1,19 +1,24 @@
 """What is particular to one clip feature call and used by more than one test module on the GPU: how the call is run into a
 guarded destination (clip_gpu.run with the call's shapes) and how its rows are held to the definition of tests/clip_*_ref.py on
 the product's own signal (clip_gpu.signal).  A helper that one test module alone uses stays in that module."""
+import functools
+
 import numpy as np
 
 import clip_audio_ref as aref
+import clip_beat_ref as bref
 import clip_cqt_ref as qref
 import clip_fbank_ref as fref
 import clip_gpu as cg
 import clip_loudness_ref as lref
 import clip_mel_ref as mref
 import clip_mfcc_ref as cref
+import clip_pitch_ref as pref
+import clip_pyin_ref as yref
 import clip_r128_ref as rref
 import clip_stft_long_ref as slref
 import clip_stft_ref as sref
-from clip_gpu import SENT
+from clip_gpu import GUARD, SENT
 
 MEL_MODES = ["power", "log", "log10", "whisper"]
 STFT_MODES = ["complex", "magnitude", "power", "log", "log10"]
@@ -372,3 +377,136 @@ def r128_check(x, want_valid, got, fs, curves=True, **kw):
     print("r128: worst error / bound %.3g, smallest range-gate margin %.3g dB = %.3g bounds, %d undecided of %d" %
           (worst, margin_db, margin, undecided, x.shape[0]))
     return refs, worst, margin, undecided
+
+
+# ---- decode_clips_pyin ----
+@functools.lru_cache(maxsize=None)
+def _pyin_tables_cached(key):
+    from pdmp3_amd import api
+    a = dict(key)
+    return api.pyin_tables(a["sample_rate"], **{k: v for k, v in a.items() if k != "sample_rate"})
+
+
+def pyin_tables(a):
+    """api.pyin_tables of the arguments a (clip_pyin_ref.args), once a process"""
+    return _pyin_tables_cached(tuple(sorted((k, v) for k, v in a.items() if k != "channels")))
+
+
+def pyin_pitch_args(a, channels):
+    """what decode_clips_pitch takes for the curve that decode_clips_pyin works on"""
+    n, w, hop = pref.defaults(a["frame_length"], a["win_length"], a["hop"])
+    return dict(sample_rate=a["sample_rate"], frame_length=n, win_length=w, hop=hop, fmin=a["fmin"], fmax=a["fmax"], channels=channels)
+
+
+def pyin_run(dec, kind, clips, f, a, channels, mode, **more):
+    """clips: (stream name, start) -> (host copy [k, c, 4 or n_b + 1, f], valid)"""
+    rows = 4 if mode == "pitch" else yref.numbers(a)["n_b"] + 1
+    return cg.run(dec, "decode_clips_pyin", kind, clips, f, channels, (rows, f), out_mode=mode, channels=channels, **dict(a, **more))
+
+
+def pyin_curve(dec, clips, f, a, channels):
+    """decode_clips_pitch's own curve of the clips -> (host copy [k, c, tmax + 1, f], valid)"""
+    k = yref.numbers(a)
+    return cg.run(dec, "decode_clips_pitch", "device", clips, f, channels, (k["tmax"] + 1, f), out_mode="curve", **pyin_pitch_args(a, channels))
+
+
+def pyin_check_both(clips, curve, obs, planes, a, channels):
+    """-> (worst error / bound of the observation, the most troughs of a frame, frames without the margin, frames)"""
+    k, t = yref.numbers(a), pyin_tables(a)
+    worst, most, open_frames, frames = 0.0, 0, 0, 0
+    for i in range(len(clips)):
+        for c in range(channels):
+            w, m = yref.check_observation(curve[i, c], obs[i, c], t, k["tmin"], k["tmax"], a["no_trough_prob"])
+            o, _, _ = yref.check_path(obs[i, c], planes[i, c], t)
+            worst, most, open_frames, frames = max(worst, w), max(most, m), open_frames + o, frames + obs.shape[-1]
+    return worst, most, open_frames, frames
+
+
+# ---- decode_clips_beats ----
+BEAT_P0 = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384, channels=1)      # the defaults, spelled out
+BEAT_TIGHTNESS = 100.0
+
+
+@functools.lru_cache(maxsize=None)
+def beat_tables(period, tightness=BEAT_TIGHTNESS):
+    from pdmp3_amd import api
+    return api.beat_tables(period, tightness=tightness)
+
+
+def beat_bpm_of(period, sr, hop):
+    """a bpm whose period is `period`: the middle of its rounding interval"""
+    bpm = 60.0 * sr / (hop * period)
+    assert bref.period_of(bpm, sr, hop) == period
+    return bpm
+
+
+def beat_run(dec, kind, clips, f, p, mode, **kw):
+    """-> (host copy [k, c, f] or [k, c, 2, f], stats [k, c, 8], valid); the guard floats behind every row are looked at"""
+    k, c = len(clips), p["channels"]
+    rows = 1 if mode == "score" else 2
+    big, view = cg.destination(kind, k, c, (rows, f))
+    dst = view[:, :, 0] if mode == "score" else view
+    stats = cg.filled(kind, (k, c, 8))
+    out, st, valid = dec.decode_clips_beats(cg.src(clips), f, out_mode=mode, out=dst, stats=stats, **dict(p, **kw))
+    assert out is dst and st is stats
+    per = rows * f
+    host = cg.host(big).reshape(k, c, per + GUARD)
+    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
+    got = host[:, :, :per].copy()
+    return (got if mode == "score" else got.reshape(k, c, 2, f)), cg.host(stats).copy(), valid
+
+
+def beat_onset(dec, clips, f, p):
+    """decode_clips_tempogram's onset envelope of the clips -> (host copy [k, c, f], valid)"""
+    q = {a: p[a] for a in BEAT_P0}
+    big, view = cg.destination("device", len(clips), p["channels"], (1, f))
+    out, valid = dec.decode_clips_tempogram(cg.src(clips), f, out_mode="onset", out=view[:, :, 0], **q)
+    return cg.host(big)[:, :, :f].copy(), valid
+
+
+def beat_same(a, b, what):
+    assert np.array_equal(cg.bits(np.asarray(a, dtype=np.float32)), cg.bits(np.asarray(b, dtype=np.float32))), what
+
+
+def beat_check_chain(dec, clips, f, p, period, kind="device"):
+    """every stage of the clips at this period against the restatement on the stage before; -> (beats rows, stats, valid)"""
+    sr = cg.rate(p, clips[0][0])
+    bpm = beat_bpm_of(period, sr, p["hop"])
+    g, tx = beat_tables(period)
+    env, valid = beat_onset(dec, clips, f, p)
+    score, s0, v0 = beat_run(dec, kind, clips, f, p, "score", bpm=bpm)
+    dp, s1, v1 = beat_run(dec, kind, clips, f, p, "dp", bpm=bpm)
+    assert np.array_equal(valid, v0) and np.array_equal(valid, v1)
+    beat_same(s0, s1, "stats of modes 0 and 1")
+    res = {}
+    for trim in (True, False):
+        beats, s2, v2 = beat_run(dec, kind, clips, f, p, "beats", bpm=bpm, trim=trim)
+        assert np.array_equal(valid, v2)
+        for i in range(len(clips)):
+            n = int(valid[i])
+            for c in range(p["channels"]):
+                what = (clips[i], period, trim, c)
+                o = env[i, c, :n]
+                run = bref.runs(o)
+                # the score stage on the onset mode's own output
+                want = bref.local_score(o, period, g)[1] if run else np.zeros(n, dtype=np.float32)
+                beat_same(score[i, c, :n], want, what + ("score",))
+                assert not score[i, c, n:].any()
+                # the programme stage on mode "score"'s output
+                cum, back = bref.programme(score[i, c, :n], period, tx) if run else (np.zeros(n), np.full(n, -1))
+                with np.errstate(over="ignore"):
+                    beat_same(dp[i, c, 0, :n], cum.astype(np.float32), what + ("cum",))
+                beat_same(dp[i, c, 1, :n], back.astype(np.float32), what + ("back",))
+                assert not dp[i, c, 0, n:].any() and (dp[i, c, 1, n:] == -1).all()
+                # the beats stage on that programme; mode "beats" alone is the chain
+                whole = bref.track(o, f, period, g, tx, trim)
+                if run:
+                    r = bref.pick(score[i, c, :n], cum, back, trim)
+                    b = r["beats"]
+                    assert np.array_equal(np.nonzero(beats[i, c, 0])[0], b) and np.array_equal(beats[i, c, 1, :b.size], b), what
+                beat_same(beats[i, c], whole["beats"], what + ("beats",))
+                beat_same(s2[i, c, 2:], whole["stats"], what + ("stats", s2[i, c], whole["stats"]))
+                assert s2[i, c, 0] == np.float32(bpm) and s2[i, c, 1] == period
+                beat_same(s0[i, c], [np.float32(bpm), period, 0, -1, -1, whole["stats"][3], -1, n], what + ("stats of mode 0",))
+        res[trim] = (beats, s2)
+    return res, valid

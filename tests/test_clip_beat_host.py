@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import scipy.signal
 
+import clip_beat_cases as bc
 import clip_beat_ref as ref
 from clip_host import build_emul, run_sanitizer_program
 
@@ -192,6 +193,9 @@ def same(got, want, what):
 
 CASES = [(p, n, f) for p in PERIODS for n, f in ((261, 261), (250, 261))] + [(22, 675, 675), (7, 2, 11), (7, 3, 11), (2, 11, 11), (1, 65, 70),
                                                                             (45, 129, 129), (200, 300, 300), (1023, 2100, 2100), (383, 700, 700)]
+# the lane counts 32 and 4 of a frame of the programme's step, h = 256 (the last one-pass step) and h = 258 (the first of two
+# passes), each with more than 2 P + 3 h frames: whole windows over more than two steps
+CASES += [(12, 261, 261), (12, 250, 261), (100, 512, 520), (513, 1800, 1800), (515, 1810, 1811)]
 
 
 @pytest.mark.parametrize("period,n,n_frames", CASES)
@@ -247,7 +251,17 @@ def test_no_local_maximum_and_no_tail():
     assert list(res) == [0, 0, -1, -1, want["maxima"]] and not rows[0].any()
 
 
-@pytest.mark.parametrize("period", (2, 7, 22, 200))
+TIE_PERIODS = (2, 7, 12, 22, 45, 100, 200, 300, 515)
+
+
+def test_the_tie_periods_reach_every_form_of_the_step():
+    """64, 32, 16, 8, 4, 2 lanes a frame and one, and the step of two passes (h > 256)"""
+    plans = [_api().beat_plan(22050, n_frames=3 * p + 41, bpm=bpm_of(p)) for p in TIE_PERIODS]
+    assert [q["period"] for q in plans] == list(TIE_PERIODS)
+    assert [q["lanes"] for q in plans] == [64, 64, 32, 16, 8, 4, 2, 1, 1] and [q["h"] > 256 for q in plans] == [False] * 8 + [True]
+
+
+@pytest.mark.parametrize("period", TIE_PERIODS)
 def test_a_tie_planted_in_cum(period):
     """a flat transition cost and small integer scores make many candidates of a frame equal: the smallest d wins in the programme,
     whichever lane held it, and equal local maxima rank as the median's rule says"""
@@ -268,6 +282,24 @@ def test_a_tie_planted_in_cum(period):
         b = want["beats"]
         assert np.array_equal(np.nonzero(rows[0])[0], b) and np.array_equal(rows[1, :b.size], b) and np.all(rows[1, b.size:] == -1)
         assert list(res[:3]) == [b.size, want["q"], want["tail"]] and np.float32(res[3]) == np.float32(want["thr"])
+
+
+@pytest.mark.parametrize("period", TIE_PERIODS)
+def test_a_tie_from_a_planted_envelope(period):
+    """the same from an envelope, as the device test hands it to the three kernels (tests/clip_beat_cases.py tie_envelope): the
+    product's g, a flat transition cost, and stretches where the local score is exactly 0"""
+    n = 3 * period + 41
+    o = bc.tie_envelope(period, n)
+    g, tx = product_tables(period)[0], np.zeros(2 * period + 1)
+    run, ls, norm = emul_score(o, n, period)
+    want = ref.track(o, n, period, g, tx, True)
+    assert run and np.array_equal(ls.view(np.uint32), want["score"].view(np.uint32)) and (ls == 0).sum() > period // 4
+    cum, back = ref.programme(ls, period, tx)
+    assert bc.tied_frames(cum, period) > n // 8, "the case must hold ties"
+    ecum, eback = emul_dp(ls, n, n, period, tx)
+    assert np.array_equal(cum, ecum) and np.array_equal(back, eback)
+    rows, res = emul_pick(ls, ecum, eback, n, True)
+    assert np.array_equal(rows.view(np.uint32), want["beats"].view(np.uint32)) and list(res[:3]) == [want["stats"][0], want["stats"][1], want["stats"][2]]
 
 
 # ---- the check, the plan, the refusals ----

@@ -11,6 +11,7 @@ import math
 import numpy as np
 import pytest
 
+import clip_pyin_cases as pc
 import clip_pyin_ref as ref
 import test_clip_pitch_host as tph
 from clip_host import build_emul, run_sanitizer_program
@@ -206,6 +207,22 @@ def test_the_candidate_stage_at_the_defaults_and_passes_of_64():
     assert most > 64 and worst <= 1.0 and (got[-1] > 0).all()
 
 
+@pytest.mark.parametrize("f", [3, 9])
+@pytest.mark.parametrize("case", ["nb2048-obs4", "nb2048-nt256-obs2", "nb2048-tmax2000-obs2"])
+def test_the_candidate_stage_at_four_and_two_frames_a_workgroup(case, f):
+    """lags up to 1600 or 2000, or 256 thresholds: a workgroup's curves, rows and counts leave room for 4 or 2 frames only (asserted
+    on the plan); F = 3 leaves the last workgroup's waves without a frame, F = 9 ends on a workgroup of one"""
+    a, frames_wg = pc.MANY[case]
+    k = ref.numbers(a)
+    assert _api().pyin_plan(a["sample_rate"], n_frames=f, **_kw(a))["obs_frames"] == frames_wg and k["n_b"] == 2048
+    rng = np.random.default_rng(k["tmax"] + f)
+    curve = (1.0 + 0.3 * rng.standard_normal((k["tmax"] + 1, f))).astype(np.float32).clip(0.01, 2.0)
+    curve[:, 1] *= 0.3
+    got, worst, most = run_obs(curve, a)
+    print("%s, F %d: troughs up to %d a frame, worst error / bound %.3f, entries at bins >= 1024: %d" % (case, f, most, worst, np.count_nonzero(got[1024:-1])))
+    assert most > 300 and worst <= 1.0 and np.count_nonzero(got[1024:-1]) > f
+
+
 def test_two_troughs_in_one_bin_the_larger_lag_stands():
     a = WIDE
     k, t = ref.numbers(a), tables(a)
@@ -262,7 +279,10 @@ def test_silence_is_exactly_zero_and_unvoiced():
 TWO = ref.args(sample_rate=16000, fmin=100.0, fmax=108.0, resolution=1.0, max_transition_rate=0.0)                   # n_b 2, Wd 1
 SIZES = {"nb2-wd1": TWO, "nb25-wd25": dict(WIDE, max_transition_rate=62.5), "nb25-wd15": WIDE, "nb601-wd101": ref.args(),
          "nb601-wd1": ref.args(max_transition_rate=0.0), "nb61-wd6": ref.args(hop=256, resolution=1.0),
-         "nb60-wd6": ref.args(hop=256, resolution=1.0, fmax=2000.0)}
+         "nb60-wd6": ref.args(hop=256, resolution=1.0, fmax=2000.0),
+         # one bin a thread at the thread limit, the first bin of a second turn, and two bins a thread: all of them more states than
+         # a dynamic LDS request holds (k_clip_pyin_path_big on the device)
+         "nb1024-wd141": pc.BINS_1024, "nb1025-wd141": pc.BINS_1025, "nb1201-wd201": pc.BINS_1201, "nb2048-wd101": pc.BINS_2048}
 
 
 def random_obs(nb, f, rng, density=3):
@@ -322,6 +342,80 @@ def test_the_optimum_switches_voicing():
     und, s, best = ref.check_path(obs, planes, t)
     assert planes[1].tolist() == [0.0] * 5 + [1.0] * 6 + [0.0] * 6 and (planes[3, 5:11] == 300).all()
     assert np.isnan(planes[0, :5]).all() and (planes[0, 5:11] == t["f0"][300]).all()
+
+
+def test_the_optimum_switches_voicing_on_a_planted_curve():
+    """test_the_optimum_switches_voicing from a curve, as the device test hands it to the kernels: no trough, six frames of one
+    trough (a second one in the middle frame), no trough.  The definition alone first: the voicing of every frame and the bin of
+    every voiced frame are decided; the unvoiced frames' bins are not (equal states), and are left to check_path's score rule"""
+    a = ref.args()
+    t = tables(a)
+    nb, f = 601, 17
+    curve, b = pc.voiced_stretch(a, t, f, 5, 11, 300)
+    o64 = pc.observation(curve, a, t)
+    assert np.count_nonzero(o64[:nb, 8]) == 2 and np.count_nonzero(o64[:nb]) == 7
+    voiced, sure_v = pc.voicing(o64, t)
+    want, sure = pc.decided(o64, t)
+    assert voiced.tolist() == [False] * 5 + [True] * 6 + [False] * 6 and sure_v.all() and (want[5:11] == b).all() and sure[5:11].all()
+    obs = emul_obs(curve, a)
+    planes = emul_path(obs, a)
+    ref.check_path(obs, planes, t)
+    assert np.array_equal(planes[1] == 1, voiced) and (planes[3, 5:11] == b).all()
+    assert np.isnan(planes[0, ~voiced]).all() and (planes[0, 5:11] == t["f0"][b]).all()
+
+
+def test_a_planted_trough_in_the_1025th_bin():
+    """1025 bins on 1024 threads: bin 1024 is thread 0's second and narrower than a lag (0.06 lags), so streams hardly ever put an
+    entry there.  A trough whose parabola's vertex lies in its middle does: the observation's one entry is at bin 1024 with
+    P = v = 1, and the path is voiced there in every frame, decided (the definition alone first)"""
+    a = pc.BINS_1025
+    t = tables(a)
+    curve, b = pc.top_bin(a, t, 9)
+    o64 = pc.observation(curve, a, t)
+    want, sure = pc.decided(o64, t)
+    assert b == 1024 and (np.flatnonzero(o64[:-1, 0]) == [b]).all() and (want == b).all() and sure.all()
+    obs, worst, most = run_obs(curve, a)
+    planes = emul_path(obs, a)
+    und, s, best = ref.check_path(obs, planes, t)
+    assert und == 0 and (planes[3] == b).all() and (planes[1] == 1).all() and (obs[b] == 1.0).all() and np.count_nonzero(obs[:-1]) == 9
+
+
+def test_a_planted_glide_through_the_second_bin_of_a_thread():
+    """2048 bins on 1024 threads: noise never steers the path above bin 800 or so (its lowest trough sits at long lags), so the
+    second turn of the step's loop decides nothing there.  One shallow trough a frame whose lag falls from 120 to 42 does: the
+    bin rises through 1024 by no more than hb a frame.  First the definition alone on its own observation: voiced at the planted
+    bin in every frame but the first (a voiced state starts at L0), decided; then the emulated kernels."""
+    a = pc.BINS_2048
+    t, k = tables(a), ref.numbers(a)
+    f = 17
+    curve, bins = pc.glide(a, t, f, 900, 23)
+    assert (np.abs(np.diff(bins)) <= k["hb"]).all() and (bins >= 1024).sum() >= 5 and (bins < 1024).sum() >= 5
+    want, sure = pc.decided(pc.observation(curve, a, t), t)
+    assert np.array_equal(want[1:], bins[1:]) and sure.all(), "the reference's own decode does not follow the planted bins"
+    obs = emul_obs(curve, a)
+    planes = emul_path(obs, a)
+    und, s, best = ref.check_path(obs, planes, t)
+    print("planted glide: bins %s, v %s" % (planes[3].astype(int).tolist(), planes[2, :2]))
+    assert und == 0 and np.array_equal(planes[3, 1:], bins[1:]) and (planes[1, 1:] == 1).all() and planes[1, 0] == 0
+    assert (planes[3] >= 1024).sum() >= 5
+
+
+def test_the_optimum_takes_an_l0_jump_between_two_upper_bins():
+    """test_the_optimum_takes_an_l0_jump at 2048 bins, from a curve: a trough under every threshold has P = 1 and v = 1, so only
+    its bin is left; both bins are a thread's second, 500 bins (ten bands) apart"""
+    a = pc.BINS_2048
+    t = tables(a)
+    nb, f, hb = 2048, 9, 50
+    curve, bins = pc.jump(a, t, f, 4, 1200, 1700)
+    assert bins[0] >= 1024 and bins[-1] - bins[0] > 8 * hb and bins[-1] < nb - hb
+    want, sure = pc.decided(pc.observation(curve, a, t), t)
+    assert np.array_equal(want, bins) and sure.all(), "the reference's own decode does not take the jump"
+    obs = emul_obs(curve, a)
+    assert (obs[nb] == 1.0).all() and np.count_nonzero(obs[:nb]) == f
+    planes = emul_path(obs, a)
+    und, s, best = ref.check_path(obs, planes, t)
+    assert und == 0 and np.array_equal(planes[3], bins) and (planes[1] == 1).all()
+    assert abs(s - (2 * ref.L0 + 7 * (t["ltri"][hb] - t["lZ"][bins[0]] + t["l_stay"]))) < 1e-9 and t["lZ"][bins[0]] == t["lZ"][bins[-1]]
 
 
 # ---- 5. the whole chain on the emulated kernels ----

@@ -12,6 +12,7 @@ import pytest
 
 import clip_beat_ref as ref
 import clip_gpu as cg
+import clip_gpu_calls as cc
 import clip_mel_long_ref as mlref
 import clip_mel_ref as mref
 import clip_streams
@@ -20,8 +21,7 @@ from clip_gpu import GUARD, SENT
 from clip_streams import ISO_LSF
 
 pytestmark = pytest.mark.gpu
-P0 = dict(sample_rate=22050, n_fft=2048, hop=512, n_mels=128, lag=1, max_size=1, win_length=384, channels=1)      # the defaults, spelled out
-TIGHTNESS = 100.0
+P0 = cc.BEAT_P0
 
 
 @functools.lru_cache(maxsize=None)
@@ -38,88 +38,8 @@ def _periodic():
 cg.STREAMS["beat/periodic-44k"] = _periodic
 
 
-@functools.lru_cache(maxsize=None)
-def tables(period, tightness=TIGHTNESS):
-    from pdmp3_amd import api
-    return api.beat_tables(period, tightness=tightness)
-
-
-def bpm_of(period, sr, hop):
-    """a bpm whose period is `period`: the middle of its rounding interval"""
-    bpm = 60.0 * sr / (hop * period)
-    assert ref.period_of(bpm, sr, hop) == period
-    return bpm
-
-
-def _run(dec, kind, clips, f, p, mode, **kw):
-    """-> (host copy [k, c, f] or [k, c, 2, f], stats [k, c, 8], valid); the guard floats behind every row are looked at"""
-    k, c = len(clips), p["channels"]
-    rows = 1 if mode == "score" else 2
-    big, view = cg.destination(kind, k, c, (rows, f))
-    dst = view[:, :, 0] if mode == "score" else view
-    stats = cg.filled(kind, (k, c, 8))
-    out, st, valid = dec.decode_clips_beats(cg.src(clips), f, out_mode=mode, out=dst, stats=stats, **dict(p, **kw))
-    assert out is dst and st is stats
-    per = rows * f
-    host = cg.host(big).reshape(k, c, per + GUARD)
-    assert (host[:, :, per:] == SENT).all(), "written behind a row's floats"
-    got = host[:, :, :per].copy()
-    return (got if mode == "score" else got.reshape(k, c, 2, f)), cg.host(stats).copy(), valid
-
-
-def _onset(dec, clips, f, p):
-    q = {a: p[a] for a in P0}
-    big, view = cg.destination("device", len(clips), p["channels"], (1, f))
-    out, valid = dec.decode_clips_tempogram(cg.src(clips), f, out_mode="onset", out=view[:, :, 0], **q)
-    return cg.host(big)[:, :, :f].copy(), valid
-
-
-def _same(a, b, what):
-    assert np.array_equal(cg.bits(np.asarray(a, dtype=np.float32)), cg.bits(np.asarray(b, dtype=np.float32))), what
-
-
-def _check_chain(dec, clips, f, p, period, kind="device"):
-    """every stage of the clips at this period against the restatement on the stage before; -> (beats rows, stats, valid)"""
-    sr = cg.rate(p, clips[0][0])
-    bpm = bpm_of(period, sr, p["hop"])
-    g, tx = tables(period)
-    env, valid = _onset(dec, clips, f, p)
-    score, s0, v0 = _run(dec, kind, clips, f, p, "score", bpm=bpm)
-    dp, s1, v1 = _run(dec, kind, clips, f, p, "dp", bpm=bpm)
-    assert np.array_equal(valid, v0) and np.array_equal(valid, v1)
-    _same(s0, s1, "stats of modes 0 and 1")
-    res = {}
-    for trim in (True, False):
-        beats, s2, v2 = _run(dec, kind, clips, f, p, "beats", bpm=bpm, trim=trim)
-        assert np.array_equal(valid, v2)
-        for i in range(len(clips)):
-            n = int(valid[i])
-            for c in range(p["channels"]):
-                what = (clips[i], period, trim, c)
-                o = env[i, c, :n]
-                run = ref.runs(o)
-                # the score stage on the onset mode's own output
-                want = ref.local_score(o, period, g)[1] if run else np.zeros(n, dtype=np.float32)
-                _same(score[i, c, :n], want, what + ("score",))
-                assert not score[i, c, n:].any()
-                # the programme stage on mode "score"'s output
-                cum, back = ref.programme(score[i, c, :n], period, tx) if run else (np.zeros(n), np.full(n, -1))
-                with np.errstate(over="ignore"):
-                    _same(dp[i, c, 0, :n], cum.astype(np.float32), what + ("cum",))
-                _same(dp[i, c, 1, :n], back.astype(np.float32), what + ("back",))
-                assert not dp[i, c, 0, n:].any() and (dp[i, c, 1, n:] == -1).all()
-                # the beats stage on that programme; mode "beats" alone is the chain
-                whole = ref.track(o, f, period, g, tx, trim)
-                if run:
-                    r = ref.pick(score[i, c, :n], cum, back, trim)
-                    b = r["beats"]
-                    assert np.array_equal(np.nonzero(beats[i, c, 0])[0], b) and np.array_equal(beats[i, c, 1, :b.size], b), what
-                _same(beats[i, c], whole["beats"], what + ("beats",))
-                _same(s2[i, c, 2:], whole["stats"], what + ("stats", s2[i, c], whole["stats"]))
-                assert s2[i, c, 0] == np.float32(bpm) and s2[i, c, 1] == period
-                _same(s0[i, c], [np.float32(bpm), period, 0, -1, -1, whole["stats"][3], -1, n], what + ("stats of mode 0",))
-        res[trim] = (beats, s2)
-    return res, valid
+tables, bpm_of = cc.beat_tables, cc.beat_bpm_of
+_run, _onset, _same, _check_chain = cc.beat_run, cc.beat_onset, cc.beat_same, cc.beat_check_chain
 
 
 CASES = {"mono-resampled": ("44k-mono", dict(P0)), "stereo-own-rate": ("48k", dict(P0, sample_rate=0, channels=2))}

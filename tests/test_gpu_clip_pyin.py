@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import clip_gpu as cg
+import clip_gpu_calls as cc
 import clip_pitch_ref as pref
 import clip_pyin_ref as ref
 import clip_streams
@@ -21,47 +22,8 @@ SMALL = ref.args(sample_rate=16000, frame_length=256, win_length=128, hop=64, fm
 PERIODIC = ref.args(sample_rate=16000, frame_length=2048, win_length=512, hop=256, fmin=7.0, fmax=13.92)                # lags 1149 .. 1535, 120 bins
 
 
-def _kw(a):
-    return {k: v for k, v in a.items() if k != "sample_rate"}
-
-
-@functools.lru_cache(maxsize=None)
-def _tables_cached(key):
-    from pdmp3_amd import api
-    a = dict(key)
-    return api.pyin_tables(a["sample_rate"], **_kw(a))
-
-
-def tables(a):
-    return _tables_cached(tuple(sorted((k, v) for k, v in a.items() if k != "channels")))
-
-
-def _pitch_args(a, channels):
-    n, w, hop = pref.defaults(a["frame_length"], a["win_length"], a["hop"])
-    return dict(sample_rate=a["sample_rate"], frame_length=n, win_length=w, hop=hop, fmin=a["fmin"], fmax=a["fmax"], channels=channels)
-
-
-def _run(dec, kind, clips, f, a, channels, mode, **more):
-    rows = 4 if mode == "pitch" else ref.numbers(a)["n_b"] + 1
-    return cg.run(dec, "decode_clips_pyin", kind, clips, f, channels, (rows, f), out_mode=mode, channels=channels, **dict(a, **more))
-
-
-def _curve(dec, clips, f, a, channels):
-    k = ref.numbers(a)
-    return cg.run(dec, "decode_clips_pitch", "device", clips, f, channels, (k["tmax"] + 1, f), out_mode="curve", **_pitch_args(a, channels))
-
-
-def _check_both(clips, curve, obs, planes, a, channels):
-    """-> (worst error / bound of the observation, the most troughs of a frame, frames without the margin, frames)"""
-    k, t = ref.numbers(a), tables(a)
-    worst, most, open_frames, frames = 0.0, 0, 0, 0
-    for i in range(len(clips)):
-        for c in range(channels):
-            w, m = ref.check_observation(curve[i, c], obs[i, c], t, k["tmin"], k["tmax"], a["no_trough_prob"])
-            o, _, _ = ref.check_path(obs[i, c], planes[i, c], t)
-            worst, most, open_frames, frames = max(worst, w), max(most, m), open_frames + o, frames + obs.shape[-1]
-    return worst, most, open_frames, frames
-
+tables = cc.pyin_tables
+_pitch_args, _run, _curve, _check_both = cc.pyin_pitch_args, cc.pyin_run, cc.pyin_curve, cc.pyin_check_both
 
 CASES = {"n256-16k": (SMALL, "16k-mono"), "defaults-22k": (ref.args(), "22k")}
 
