@@ -420,6 +420,7 @@ struct LaneRegs {
   float ho[15];      // same for idx_o   (together = what the lane needs of v_vec[ch][], P:1983)
   float in[18];      // scratch: this granule's antialiased IMDCT input
   Chunk16 pf0, pf1, pf2, pf3;   // next granule's spectra / side records in flight
+  unsigned route;    // granule kernel: the lane's byte of the routing gather, in flight with them (gran_route_issue)
   int idx_e, idx_o;  // which DCT coefficient the lane reads from even-/odd-aged slots
 };
 
@@ -484,6 +485,57 @@ PD_FN bool frame_is_rare(const pdmp3_gc_side* rec) {
   const unsigned fr = b[7];
   const bool is = ((fr & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) == 1 && (fr & (1u << PDMP3_FR_MODEEXT_SHIFT));
   return is || (b[offsetof(pdmp3_gc_side, lsf)] & PDMP3_LSF_VERSION_MASK) != 0;
+}
+
+// The granule kernel's routing facts (run_granule_wave, run_granule) as ONE gather and ONE ballot: the wave of granule g --
+// frame f = g >> 1 -- decides from byte 7 and the `lsf` byte of frames f, f - 1 and f + 1 (clamped at the launch's ends),
+// and the flags byte of record (f, gr 1, ch 1).  (Byte 7 of frame 0, which run_granule asks about RESET, is wanted by the
+// waves of frame 0 alone: to them it is frame f's.)  Lane k = lane & 15 asks for ONE of those bytes
+// (gran_route_offset: its place from the launch's first record) and forms ONE predicate on it (gran_route_pred); the ballot's
+// low word is a GranRoute:
+//   bits 4 x + 0..3, x = 0: frame f, 1: the frame before, 2: the frame after
+//        + 0 not mono   + 1 intensity stereo (joint stereo with mode_extension bit 0)   + 2 RESET   + 3 an LSF version
+//   bit 12  (f, 1, 1) is a short block (H5)
+// One byte load per lane and one wait where there were four byte loads and three frame_is_rare() calls, each waited for
+// alone -- and the load can be asked for where the wave's input is (the kernel's entry), ahead of everything it decides.
+struct GranRoute {
+  unsigned w;
+  PD_MFN bool rare(int x) const { return ((w >> (4 * x)) & 0xAu) != 0; }                 // frame_is_rare()
+  PD_MFN bool stereo(int x) const { return ((w >> (4 * x)) & 0xBu) == 0x1u; }            // not mono and not rare
+  PD_MFN bool reset(int x) const { return ((w >> (4 * x)) & 0x4u) != 0; }
+  PD_MFN bool takes_chain(int x) const { return ((w >> (4 * x)) & 0xFu) == 0x1u; }       // stereo, and not from zero
+  PD_MFN bool h5() const { return (w & (1u << 12)) != 0; }
+};
+PD_HD size_t gran_route_offset(int lane, int f, int n_frames) {
+  // (selects between values, no arms with work in them: as nested choices the compiler made branches of this)
+  const int k = lane & 15, x = k >> 2;
+  int fx = f + (x == 2 ? 1 : 0) - (x == 1 ? 1 : 0);
+  fx = fx < 0 ? 0 : fx;                              // the clamps of run_granule_wave: frame 0's "frame before" is frame 0,
+  fx = fx < n_frames ? fx : f;                       // the last frame's "frame after" is the last frame
+  const unsigned in_rec = (k & 3) == 3 ? (unsigned)offsetof(pdmp3_gc_side, lsf) : 7u;
+  const unsigned byte = x == 3 ? 3u * (unsigned)sizeof(pdmp3_gc_side) + 3u : in_rec;   // (lanes 13 to 15 repeat lane 12: nobody reads their bits)
+  return (size_t)fx * 4 * sizeof(pdmp3_gc_side) + byte;
+}
+// every predicate is (b & mask) == want or its negation; mask and want a byte per kind.  Kind 1 serves both "intensity
+// stereo" on a frame byte and "short block" on a record's flags: the two patterns happen to be the same bits
+PD_HD bool gran_route_pred(int lane, unsigned b) {
+  constexpr unsigned kIsMask = PDMP3_FR_MODE_MASK | (1u << PDMP3_FR_MODEEXT_SHIFT), kIsWant = (1u << PDMP3_FR_MODE_SHIFT) | (1u << PDMP3_FR_MODEEXT_SHIFT);
+  constexpr unsigned kShortMask = PDMP3_GC_WIN_SWITCH | PDMP3_GC_BLOCK_TYPE_MASK, kShortWant = PDMP3_GC_WIN_SWITCH | (2u << PDMP3_GC_BLOCK_TYPE_SHIFT);
+  static_assert(kIsMask == kShortMask && kIsWant == kShortWant, "one pattern for both");
+  constexpr unsigned kMasks = PDMP3_FR_MODE_MASK | (kIsMask << 8) | (PDMP3_FR_RESET << 16) | (PDMP3_LSF_VERSION_MASK << 24);
+  constexpr unsigned kWants = PDMP3_FR_MODE_MASK | (kIsWant << 8) | (PDMP3_FR_RESET << 16);      // kinds 0 and 3 negated: not mono, a version other than 0
+  const int k = lane & 15;
+  const int kind = k < 12 ? (k & 3) : 1;
+  const bool eq = (b & (kMasks >> (8 * kind)) & 0xffu) == ((kWants >> (8 * kind)) & 0xffu);
+  return eq != (kind == 0 || kind == 3);
+}
+// the two halves on a wave: the load (its result is not looked at: it stays in flight) ...
+PD_FN unsigned gran_route_issue(int lane, const pdmp3_gc_side* side, int g, int n_frames) {
+  return reinterpret_cast<const uint8_t*>(side)[gran_route_offset(lane, g >> 1, n_frames)];
+}
+// ... and the word (wave-uniform)
+PD_FN GranRoute gran_route_word(int lane, unsigned b) {
+  return GranRoute{(unsigned)PD_BALLOT(gran_route_pred(lane, b))};
 }
 
 PD_HD uint32_t f2u(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
@@ -2288,9 +2340,10 @@ PD_SLOW_FN void gran_slow_chunk(DecodeArgs a, GlobalTables T, BankPtr cb, int f,
 // its start is derived by this wave the independent way (run_chunk's halo as a called function);
 // g_pf: the granule whose input is asked for while this one is windowed (this wave's next), -1: none.
 // SCTAB: the band scales of the wave's own granule from the workgroup's tables (GranPos::sc, ph_scales_tab)
+// route: the wave's routing word (run_granule_wave formed it)
 template <bool F32, bool RING = false, bool SCTAB = false>
 PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, int g, WaveData& L, TabLds& S, const GranPos& gp,
-                       bool fresh, bool h5, bool next_takes, const LaneRegs& pf, LaneRegs* Rp = nullptr, bool emit = true,
+                       bool fresh, bool h5, bool next_takes, GranRoute route, const LaneRegs& pf, LaneRegs* Rp = nullptr, bool emit = true,
                        bool zero_in = false, bool halo_in = false, int g_pf = -1) {
   LaneRegs R;
   (void)Rp;
@@ -2300,7 +2353,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
   if (RING) PD_PIN(lane_);
   const int lane = lane_;
   const int f = g >> 1, gr = g & 1;
-  const bool from_caller = fresh && gr == 0 && f == 0 && a.state_in && !(reinterpret_cast<const uint8_t*>(a.side)[7] & PDMP3_FR_RESET);
+  const bool from_caller = fresh && gr == 0 && f == 0 && a.state_in && !route.reset(0);
   const bool from_zero = (fresh && gr == 0 && !from_caller) || (RING && zero_in);
   const bool from_chain = !from_caller && !from_zero;
   const unsigned tag = gran_tag(gp, g);
@@ -2345,7 +2398,7 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
       LaneRegs R0;
       float tail = 0.0f;
       PD_PHASE(ph_prefetch(lane, R0, a.spectra + (size_t)(g - 1) * 1152, a.side + (size_t)(g - 1) * 2))
-      if (fresh && f == 0 && a.state_in && !(reinterpret_cast<const uint8_t*>(a.side)[7] & PDMP3_FR_RESET) && lane < 3) tail = a.state_in[lane];
+      if (fresh && f == 0 && a.state_in && !route.reset(0) && lane < 3) tail = a.state_in[lane];
       PD_PHASE(ph_commit(lane, L, R0))
       PD_PHASE(if (SCTAB) ph_scales_tab(lane, L, *gp.sc); else ph_scales(lane, L))
       PD_PHASE((ph_requant<false, 1, false, true, false, false>(lane, L, S, cb, T, nullptr, nullptr)))
@@ -2493,36 +2546,33 @@ PD_FN void run_granule(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, i
 // The wave of granule g: which way its frame goes (wave-uniform facts from the side records; both waves of a frame
 // decide alike).  gp = this granule's place; pf = its input, prefetched.
 // RING: see run_granule; g_emit = the range's first granule proper (granules before it are its halo frame).
-template <bool F32, bool RING = false, bool SCTAB = false>
+// ENTRY: the kernel's entry has asked for the wave's routing byte together with its input (pf.route: gran_route_issue right
+// behind ph_prefetch); otherwise it is asked for here.
+template <bool F32, bool RING = false, bool SCTAB = false, bool ENTRY = false>
 PD_FN void run_granule_wave(const DecodeArgs& a, const GlobalTables& T, BankPtr cb, int g, WaveData& L, TabLds& S, const GranPos& gp,
                             const LaneRegs& pf, LaneRegs* Rp = nullptr, int g_emit = 0, bool halo_by_wave = false, int g_pf = -1) {
   const int f = g >> 1, gr = g & 1;
-  const uint8_t fb = reinterpret_cast<const uint8_t*>(a.side + (size_t)f * 4)[7];
-  const uint8_t pb = reinterpret_cast<const uint8_t*>(a.side + (size_t)(f > 0 ? f - 1 : 0) * 4)[7];
-  const uint8_t nb = reinterpret_cast<const uint8_t*>(a.side + (size_t)(f + 1 < a.n_frames ? f + 1 : f) * 4)[7];
-  const uint8_t fl = reinterpret_cast<const uint8_t*>(a.side + (size_t)(2 * f + 1) * 2 + 1)[3];
+  const int lane = PD_LANE();
+  const GranRoute route = gran_route_word(lane, ENTRY ? pf.route : gran_route_issue(lane, a.side, g, a.n_frames));
   // (frames with intensity stereo -- and LSF ones, should a caller hand them to this kernel -- go the way mono frames
   //  go: decoded as a whole by the wave of their first granule, with run_chunk's RARE copy; to the frames around them
   //  they look like mono frames do: nothing is taken from them through the chain)
-  const bool rare = frame_is_rare(a.side + (size_t)f * 4);
-  const bool prev_rare = frame_is_rare(a.side + (size_t)(f > 0 ? f - 1 : 0) * 4);
-  const bool next_rare = frame_is_rare(a.side + (size_t)(f + 1 < a.n_frames ? f + 1 : f) * 4);
-  const bool stereo = ((fb & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) != 3 && !rare;
-  const bool fresh = f == 0 || (fb & PDMP3_FR_RESET);       // its input state is the caller's / zero
-  const bool prev_stereo = ((pb & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) != 3 && !prev_rare;
+  const bool stereo = route.stereo(0);
+  const bool fresh = f == 0 || route.reset(0);              // its input state is the caller's / zero
+  const bool prev_stereo = route.stereo(1);
   const bool chained = stereo && (fresh || prev_stereo);
-  const bool h5 = (fl & PDMP3_GC_WIN_SWITCH) && ((fl & PDMP3_GC_BLOCK_TYPE_MASK) >> PDMP3_GC_BLOCK_TYPE_SHIFT) == 2;
+  const bool h5 = route.h5();
   bool next_takes = false;
   if (chained) {
     // who takes this granule's state from the chain: granule 1 of the same frame; or the next frame, if it is a stereo
     // frame that does not start from zero (this frame being stereo, it then goes this way too)
-    next_takes = gr == 0 || (f + 1 < a.n_frames && ((nb & PDMP3_FR_MODE_MASK) >> PDMP3_FR_MODE_SHIFT) != 3 && !(nb & PDMP3_FR_RESET) && !next_rare);
+    next_takes = gr == 0 || (f + 1 < a.n_frames && route.takes_chain(2));
     if (RING) {
       if (g + 1 >= gp.g_end) next_takes = false;          // (the next range derives its opening state itself)
       const bool halo_frame = g < g_emit;                 // (then this frame is chained or fresh: run_granule_ring chose it so)
-      run_granule<F32, true, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf, Rp, !halo_frame, halo_frame && gr == 0 && !fresh,
+      run_granule<F32, true, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, route, pf, Rp, !halo_frame, halo_frame && gr == 0 && !fresh,
                              halo_by_wave && g == g_emit && !fresh, g_pf);
-    } else run_granule<F32, false, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, pf);
+    } else run_granule<F32, false, SCTAB>(a, T, cb, g, L, S, gp, fresh, h5, next_takes, route, pf);
     return;
   }
   if (gr == 0) {                                             // the frame is decoded by the wave of its first granule

@@ -152,9 +152,15 @@ __device__ __forceinline__ void gran_workgroup(const GranArgs& ga, unsigned long
   const int w = tid >> 6;
   const int g = (int)blockIdx.x * W + w;
   const bool valid = g < 2 * a.n_frames;
-  // the wave's own input first: its round trip passes under the workgroup's table loads
+  // the wave's own input first: its round trip passes under the workgroup's table loads.  Right behind it the wave's byte
+  // of the routing gather (decode_core.h GranRoute): everything run_granule_wave decides from is on its way before the
+  // barrier, and the wait behind the table loads below -- which the input has to pass anyway -- covers it.  (The table
+  // pieces and the lane's B fragments asked for here too, ahead of the barrier, measured slower: DESIGN.md §3 "Entry".)
   LaneRegs pf;
-  if (valid) ph_prefetch(tid & 63, pf, a.spectra + (size_t)g * 1152, a.side + (size_t)g * 2);
+  if (valid) {
+    ph_prefetch(tid & 63, pf, a.spectra + (size_t)g * 1152, a.side + (size_t)g * 2);
+    pf.route = gran_route_issue(tid & 63, a.side, g, a.n_frames);
+  }
   if (tid < W * (int)(sizeof(GranMb) / 4)) reinterpret_cast<unsigned*>(mb)[tid] = 0u;
   if (tid == 0) tabs_ready = 0u;
   __syncthreads();                       // (nothing to wait for in front of it: the waves arrive together)
@@ -169,7 +175,7 @@ __device__ __forceinline__ void gran_workgroup(const GranArgs& ga, unsigned long
   if (!valid) return;
   if (PROF && (tid & 63) == 0) a.prof[(size_t)g * kProfSlots] = t_entry;
   const GranPos gp{L, mb, w, W, &tabs_ready, 0, 0, 0, &G};
-  run_granule_wave<F32, false, PD_GRAN_SCALE_TABS != 0>(a, T, (BankPtr)&c_bank, g, L[w], S, gp, pf);
+  run_granule_wave<F32, false, PD_GRAN_SCALE_TABS != 0, true>(a, T, (BankPtr)&c_bank, g, L[w], S, gp, pf);
 }
 
 template <bool F32, int W>
